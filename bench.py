@@ -8,10 +8,18 @@ time.  Every problem is one independent call of the reference exactly as its not
     .mpc_fixed_log_newton(n_fix = 1, k_fix = 1e-2)          % x_init = [] -> cold start
 Inputs (x0, x0_pre, nu0) are resident in HBM before the timed region; synthetic data per SURVEY.md §8(d).
 
+A plain run sets up, warms up, times exactly --steps steps of the headline and prints the JSON line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds of one timed step, the headline's own `roofline`).  Everything else below
+(roofline_per_problem_factor, roofline.contiguous_rows, cpu_baseline*, extra) is measured only with --full.
+--dump-outputs DIR writes what the last timed step handed its caller to DIR/<name>.npy (float64): z_sample (a fixed, seeded
+sample of the batch's rows of z), z_sample_rows (their indices), u0, iters, status.  The inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
+
 The JSON line carries
   roofline             the headline's OWN kernels (what the timed region ran): bound "hbm", SURVEY §8(d)'s compulsory 47 952 B
                        per problem x problems of a step / device time of a step (HIP events around the timed regions);
                        `executed` = matrix instructions issued against the fp64 peak
+(--full only:)
   roofline_per_problem_factor
                        the PER-PROBLEM-FACTOR kernel in a leg of its own (every problem factors its own Y: explicit start),
                        priced at SURVEY §8(d)'s 11.64 MFLOP per problem-iteration, with its own ms_per_step; `n_newton_5` =
@@ -21,7 +29,7 @@ The JSON line carries
   extra                configs[2] (512 realisations), configs[4] (n = 65, T = 60, fp32 factor), two steps in flight,
                        Newton budget 5, the closed loops, configs[0] (VAR(1) + ramp rows), the literal fmpc_solve_once call
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-extra] [--no-cpu-baseline]]
 For N > 1 either launch with torch.distributed.run (one rank per GPU) or run `python bench.py --gpus N` from a plain shell:
 without WORLD_SIZE in the environment it starts the N ranks itself as child processes (self_launch).  Weak scaling, every rank solves its own 2000-timestep
 replay batch per step and the first moves are all-gathered over RCCL; `extra.configs3_sharded` is BASELINE configs[3]
@@ -50,7 +58,10 @@ FP32_PEAK_TFLOPS = 157.3     # MI355X_MICROARCH.md: fp32 matrix = vector peak
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s
 MIN_LEG_MS = 50.0            # every timed GPU leg lasts at least this long
 HEAD_SETS = 4                # buffer sets the headline rotates through: 4 x 82 MB of z > the 256 MB Infinity Cache
-HEAD_REGIONS = int(os.environ.get("FMPC_BENCH_REGIONS", "15"))   # timed regions of EXACTLY --steps steps each; the median is reported
+HEAD_REGIONS = int(os.environ.get("FMPC_BENCH_REGIONS", "1"))    # timed regions of EXACTLY --steps steps each; the median is reported
+HEAD_GRAPH_STEPS = 512       # steps per recorded HIP graph: a longer region replays recorded chunks (a multiple of HEAD_SETS)
+HEAD_PRIME_S = 0.25          # seconds of untimed replays of the recorded steps right before the headline's region
+DUMP_Z_ROWS, DUMP_SEED = 512, 20260   # --dump-outputs: rows of z written (of 2000: 21 MB in float64) and the seed choosing them
 
 
 def flops_per_problem_factor(n, m, T):
@@ -158,8 +169,11 @@ def _main(real_out):
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--n-newton", type=int, default=N_NEWTON)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="only the headline and the two roofline blocks")
+    ap.add_argument("--full", action="store_true", help="also the per-problem-factor roofline, the contiguous-rows leg, the CPU "
+                                                        "baselines and the `extra` legs (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: only the headline and the two roofline blocks")
     ap.add_argument("--in-flight", type=int, default=1, help="independent steps in flight per GPU for the HEADLINE (SolveLanes); the "
                                                              "configs[1] figure is 1, two in flight is reported as extra.two_in_flight")
     args = ap.parse_args()
@@ -230,19 +244,18 @@ def _main(real_out):
             torch.cuda.synchronize(dev)
 
     def timed(step_fn, steps, warmup, min_ms=MIN_LEG_MS, after=None, exact=False, regions=1, all_regions=None, dev_regions=None,
-              rank_times=None, region_fn=None):
+              rank_times=None, recorded=None, prime_s=0.0):
         """W warm-up steps, then `steps` timed steps between barriers -- exactly `steps` for the headline (exact=True),
-        otherwise as many more as it takes for the timed region to last min_ms.  regions > 1 (headline): that many timed
+        otherwise as many more as it takes for the timed region to last min_ms.  regions > 1: that many timed
         regions of exactly `steps` steps back to back, each bracketed by barrier + synchronize; the MEDIAN region is
         returned (a single 20-step region lasts 1 ms and spread by 15 % from run to run in round 2), all of them in
-        `all_regions`.  region_fn (headline, one GPU): the `steps` steps of a region as ONE host call -- a HIP graph of exactly
-        that many solves recorded beforehand (RecordedSolves) -- instead of `steps` calls of step_fn.
+        `all_regions`.  recorded (one GPU): a RecordedRegion of exactly `steps` steps -- HIP graphs
+        of those solves recorded beforehand -- whose replay() is a region instead of `steps` calls of step_fn; before the
+        first region its graphs are replayed untimed, once and then until prime_s seconds have passed.
         Returns (elapsed_s, steps_done, kernel_ms): kernel_ms = median device time of ONE step run alone, from HIP
         events on the stream the step is enqueued on, measured outside the timed region."""
         for _ in range(warmup):
             step_fn()
-        if region_fn is not None:
-            region_fn()                                                 # (the recorded form is warmed up too: one untimed replay)
         if after:
             after()
         sync()
@@ -254,6 +267,15 @@ def _main(real_out):
             after()
         sync()
         kern_ms = float(np.median([a.elapsed_time(b) for a, b in ev]))
+        if recorded is not None:
+            # the recorded form is warmed up too, by untimed replays right before the region: a region that follows the single
+            # steps above instead ran 8 % slower on the device than one that follows a replay
+            t_prime = time.perf_counter()
+            while True:
+                recorded.warm()
+                torch.cuda.synchronize(dev)
+                if time.perf_counter() - t_prime >= prime_s:
+                    break
         if world == 1 and not exact:
             steps = max(steps, int(np.ceil(min_ms / max(kern_ms, 1e-3))))
         times, rev = [], []
@@ -261,8 +283,8 @@ def _main(real_out):
             ra, rb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0 = time.perf_counter()
             ra.record()                                                 # HIP events on the stream the steps are enqueued on
-            if region_fn is not None:
-                region_fn()                                             # (exactly `steps` steps, recorded once: one host call)
+            if recorded is not None:
+                recorded.replay()                                       # (exactly `steps` steps, recorded beforehand)
             else:
                 for _ in range(steps):
                     step_fn()
@@ -326,13 +348,43 @@ def _main(real_out):
                 d_ = data if i_ == 0 else pkg.synthetic.make_replay_batch(model, r=rank + 1000 * i_, steps=B)
                 self.sets.append(Replay(h_, to_dev(d_["x0"]), to_dev(d_["x0_pre"]), to_dev(d_["nu0"]), n_newton, want_z=want_z, pad_z=pad_z))
             self.i = 0
+            self.last = None                                            # the set the latest step() wrote
 
         def step(self, u0_out=None):
             self.sets[self.i].step(u0_out)
+            self.last = self.sets[self.i]
             self.i = (self.i + 1) % len(self.sets)
+
+        def run(self, k):
+            """k steps from set 0 on: what RecordedRegion records."""
+            self.i = 0
+            for _ in range(k):
+                self.step()
 
         def check(self):
             return sum(s_.check() for s_ in self.sets) / len(self.sets)
+
+    class RecordedRegion:
+        """The `steps` steps of a ring as replays of HIP graphs recorded once (the inputs of a replay batch are known in advance):
+        graphs of at most HEAD_GRAPH_STEPS steps, every one starting at set 0, so that recording costs the same for any --steps
+        and a long region replays one recorded chunk over and over.  `last` = the set the region's last step writes."""
+        def __init__(self, ring, steps):
+            full_, rest_ = divmod(steps, HEAD_GRAPH_STEPS)
+            chunk_ = pkg.RecordedSolves(lambda: ring.run(HEAD_GRAPH_STEPS)) if full_ else None
+            tail_ = pkg.RecordedSolves(lambda: ring.run(rest_)) if rest_ else None
+            self.graphs = [g_ for g_ in (chunk_, tail_) if g_ is not None]
+            self.order = [chunk_] * full_ + ([tail_] if tail_ is not None else [])
+            self.last = ring.sets[((rest_ or HEAD_GRAPH_STEPS) - 1) % len(ring.sets)]
+            if not all(g_.valid() for g_ in self.graphs):
+                raise RuntimeError("device buffers were reallocated while the region was recorded")
+
+        def warm(self):
+            for g_ in self.graphs:
+                g_.replay()
+
+        def replay(self):
+            for g_ in self.order:
+                g_.replay()
 
     PAD_Z = args.n_newton == 1 and os.environ.get("FMPC_BENCH_CONTIGUOUS_Z", "0") != "1"   # (padded rows: the cold-start step with a budget of 1 only)
     head = Ring(h, args.n_newton, pad_z=PAD_Z)
@@ -379,28 +431,47 @@ def _main(real_out):
             if gather_state["pending"][s_] is not None:
                 gather_state["pending"][s_].wait(); gather_state["pending"][s_] = None
 
+    def last_outputs(z_, u0_, iters_, status_):
+        """What the last timed step handed its caller (--dump-outputs), as float64 host arrays: z as a fixed, seeded sample of
+        DUMP_Z_ROWS problems (all of it is 82 MB), the first moves, iterations and status of every problem."""
+        rows_ = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=min(B, DUMP_Z_ROWS), replace=False))
+        f64_ = lambda t_: t_.to(torch.float64).cpu().numpy()
+        return {"z_sample": f64_(z_[torch.from_numpy(rows_).to(dev)]), "z_sample_rows": rows_.astype(np.float64),
+                "u0": f64_(u0_), "iters": f64_(iters_), "status": f64_(status_)}
+
     head_regions, head_dev_regions, head_rank_times = [], [], []
-    # One GPU: the K steps of a timed region are recorded once into a HIP graph (the inputs of a replay batch are known in advance)
-    # and a region is one replay -- inside a graph the launches follow each other more closely than the host can submit them.
+    # One GPU: the K steps of a timed region are recorded beforehand into HIP graphs (RecordedRegion) and a region is their
+    # replays -- inside a graph the launches follow each other more closely than the host can submit them.
     # With ranks the first moves are gathered every GROUP steps by the host (RCCL): submitted step by step as before.
     GRAPH = depth == 1 and not dist_on and os.environ.get("FMPC_BENCH_EAGER", "0") != "1"
     head_rec = None
     if GRAPH:
         try:
-            head_rec = pkg.RecordedSolves(lambda: [head.step() for _ in range(args.steps)])
+            head_rec = RecordedRegion(head, args.steps)
         except Exception as ex_:                                           # (a runtime without stream capture: eager submission)
             print("[bench] HIP graph capture of the headline failed (%s): eager submission" % repr(ex_)[:200], file=sys.stderr)
             head_rec, GRAPH = None, False
+    dumped = None
     if depth == 1:
         elapsed, steps_done, kern_ms = timed(head_step, args.steps, args.warmup, after=head_after, exact=True,
                                              regions=HEAD_REGIONS, all_regions=head_regions, dev_regions=head_dev_regions,
-                                             rank_times=head_rank_times, region_fn=head_rec.replay if head_rec is not None else None)
+                                             rank_times=head_rank_times, recorded=head_rec, prime_s=HEAD_PRIME_S)
+        if args.dump_outputs and rank == 0:
+            rp_ = head_rec.last if head_rec is not None else head.last
+            dumped = last_outputs(rp_.z, rp_.z[:, :m] if dist_on else rp_.u0, rp_.it, rp_.st)   # (with ranks u0 went to the gather buffers)
     else:
         lanes = pkg.SolveLanes(make_handle, B, depth=depth, device=dev)
         lane_step = lambda: lanes.submit(x0, x0p, None, None, nu0, args.n_newton, K_BAR, after_current=False)
         elapsed, steps_done, _ = timed(lane_step, args.steps, args.warmup, after=lanes.synchronize, exact=True)
+        if args.dump_outputs and rank == 0:
+            ln_ = lanes.lanes[(lanes.submitted - 1) % lanes.depth]
+            dumped = last_outputs(ln_.z, ln_.u0, ln_.iters, ln_.status)
         _, _, kern_ms = timed(head_step, 5, 2)
         lanes.close()
+    if dumped is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name_, a_ in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name_ + ".npy"), a_)
     iters_head = head.check()
     gather_ok = None
     if dist_on and not rehearse:
@@ -412,17 +483,17 @@ def _main(real_out):
     # The same leg with the z rows of consecutive problems CONTIGUOUS (N_z doubles apart: the layout a caller of the reference's
     # N_z x batch column-major array has), same submission, same regions: reported inside `roofline` beside the padded figure.
     contig = None
-    if depth == 1 and PAD_Z and not dist_on:
+    if args.full and depth == 1 and PAD_Z and not dist_on:
         hc = Ring(h, args.n_newton)
         rec_c = None
         if GRAPH:
             try:
-                rec_c = pkg.RecordedSolves(lambda: [hc.step() for _ in range(args.steps)])
+                rec_c = RecordedRegion(hc, args.steps)
             except Exception as ex_:
                 print("[bench] HIP graph capture of the contiguous-rows leg failed (%s): eager submission" % repr(ex_)[:200], file=sys.stderr)
         cdev = []
         eC, sC, kC = timed(hc.step, args.steps, args.warmup, exact=True, regions=HEAD_REGIONS, dev_regions=cdev,
-                           region_fn=rec_c.replay if rec_c is not None else None)
+                           recorded=rec_c, prime_s=HEAD_PRIME_S)
         hc.check()
         contig = {"elapsed": eC, "steps": sC, "kernel_ms": kC, "ms_dev": float(np.median(cdev)) / sC * 1e3,
                   "submission": "hip_graph" if rec_c is not None else "eager"}
@@ -435,7 +506,7 @@ def _main(real_out):
 
     extra = {}
     roof_pp = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # ------------------------------------------------------------------ per-problem-factor regime (the roofline block)
         zc = np.tile(np.concatenate([(model["u_min"] + model["u_max"]) / 2, (model["x_min"] + model["x_max"]) / 2]), T)
         zi = to_dev(np.tile(zc, (B, 1)))          # the cold-start values passed explicitly: no shared factor, every problem factors
@@ -508,7 +579,7 @@ def _main(real_out):
             except Exception:
                 pass
 
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         ksteps = max(5, args.steps // 10)
         eL, sL, _ = timed(head_step, args.steps, 2)
         extra["headline_min_50ms"] = {"what": "the headline leg again over a timed region of at least %.0f ms" % MIN_LEG_MS,
@@ -862,7 +933,7 @@ def _main(real_out):
                                                "that has been written before runs at 55 GB/s), ctypes; never `value`" % (zh.nbytes / 1e6),
                                        "ms_per_solve_median": float(np.median(th[1:])) * 1e3, "MPC_steps_per_s": B / float(np.median(th[1:]))}
 
-    if dist_on and not args.no_extra:
+    if args.full and dist_on and not args.no_extra:
         # ------------------------------------------------------------------ configs[3] literally: 4096 realisations sharded over the ranks
         BG = 4096
         sh = pkg.ShardedFastMPC.from_handle(h)
@@ -958,13 +1029,16 @@ def _main(real_out):
                                                  if shared and dense else "two sweeps through the shared block factor (panels of 16 problems)") if shared else None,
                        "gather": ("all-gather of the first moves u0 (RCCL), one collective per %d steps (and at the end of the timed region), two buffers in turn" % GROUP) if dist_on else "none (1 GPU)",
                        "steps_requested": args.steps,
-                       "timing": "median of %d timed regions of exactly %d steps each (barrier + synchronize on both sides of every region); "
-                                 "regions (ms): min %.3f, median %.3f, max %.3f" % (len(head_regions) or 1, steps_done,
-                                                                                   1e3 * min(head_regions or [elapsed]), 1e3 * elapsed, 1e3 * max(head_regions or [elapsed])),
+                       "timing": ("median of %d timed regions of exactly %d steps each (barrier + synchronize on both sides of every region); "
+                                  "regions (ms): min %.3f, median %.3f, max %.3f" % (len(head_regions), steps_done,
+                                                                                    1e3 * min(head_regions), 1e3 * elapsed, 1e3 * max(head_regions)))
+                                 if len(head_regions) > 1 else
+                                 "one timed region of exactly %d steps (barrier + synchronize on both sides): %.3f ms" % (steps_done, 1e3 * elapsed),
                        "buffers": "%d input/output sets solved in turn (%.0f MB of z in rotation: larger than the 256 MB Infinity Cache)" % (HEAD_SETS, HEAD_SETS * B * T * (n + m) * 8 / 1e6),
-                       "submission": ("the %d steps of a timed region are recorded once into a HIP graph (RecordedSolves: torch.cuda.CUDAGraph around the "
-                                      "C-ABI calls, capture-safe once the workspaces exist) and a region is one replay; `extra.headline_eager_submission` is "
-                                      "the same leg with one host call per step" % steps_done) if GRAPH else "one host call per step",
+                       "submission": ("the %d steps of a timed region are recorded beforehand into HIP graphs of at most %d steps (RecordedSolves: "
+                                      "torch.cuda.CUDAGraph around the C-ABI calls, capture-safe once the workspaces exist) and a region is their replays "
+                                      "back to back; `extra.headline_eager_submission` is the same leg with one host call per step"
+                                      % (steps_done, HEAD_GRAPH_STEPS)) if GRAPH else "one host call per step",
                        "z_layout": ("rows of consecutive problems %d doubles apart (N_z = %d padded to a multiple of 128 bytes, fmpc_set_z_ld: whole cache lines, "
                                     "non-temporal stores); `extra.headline_contiguous_z` is the same leg with contiguous rows" % (LDZ, T * (n + m))) if PAD_Z
                                    else "contiguous rows (N_z = %d doubles)" % (T * (n + m)),
@@ -981,7 +1055,7 @@ def _main(real_out):
                              "steps_per_collective": GROUP, "gathered_equals_local_bitwise": gather_ok}
         if extra:
             out["extra"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out.update(cpu_baselines(pkg, model, data, args.n_newton))
         real_out.write(json.dumps(out) + "\n"); real_out.flush()
     h.close()

@@ -2,10 +2,10 @@
 """Minimal reader for real, dense, double-precision variables of a MATLAB v7.3 MAT-file (= HDF5), without h5py.
 
 Why: the reference ships the estimator's linear model `model_approx.mat` (variables A_s, b_s; loaded at
-/root/reference/README.md:294 and used at README.md:478 `ad_est = lsqminnorm(A_s'*A_s, A_s'*(Y_M - b_s))`) as the one piece
-of reference-held NUMERICAL DATA on a SURVEY §8 row.  This script turns it into the fixture
-`tests/golden/model_approx_As_bs.npz` (data, not source), so that the estimator's linear half is pinned to the reference's
-own numbers on the GPU box, where /root/reference does not exist.
+README.md:294 of the reference and used at README.md:478 `ad_est = lsqminnorm(A_s'*A_s, A_s'*(Y_M - b_s))`) as the one piece
+of reference-held NUMERICAL DATA on a SURVEY §8 row.  The file itself is kept as the fixture tests/golden/model_approx.mat, and
+this script turns it into the fixture `tests/golden/model_approx_As_bs.npz` (data, not source), so that the estimator's linear
+half is pinned to the reference's own numbers.
 
 Only what such a file needs is implemented (HDF5 File Format Specification, version 0 structures):
   * user block of 512 bytes (the MATLAB text header), superblock version 0, 8-byte offsets and lengths
@@ -17,7 +17,7 @@ Only what such a file needs is implemented (HDF5 File Format Specification, vers
 MATLAB stores an r x c array column-major, i.e. as an HDF5 dataset of shape (c, r): `read_mat73` returns the array in
 MATLAB's orientation (transposed back).
 
-  python tests/golden/read_mat73.py [/root/reference/model_approx.mat [tests/golden/model_approx_As_bs.npz]]
+  python tests/golden/read_mat73.py [tests/golden/model_approx.mat [tests/golden/model_approx_As_bs.npz]]
 """
 import os
 import struct
@@ -235,8 +235,8 @@ def read_mat73(path):
 
 
 def main(argv):
-    src = argv[1] if len(argv) > 1 else "/root/reference/model_approx.mat"
     here = os.path.dirname(os.path.abspath(__file__))
+    src = argv[1] if len(argv) > 1 else os.path.join(here, "model_approx.mat")
     dst = argv[2] if len(argv) > 2 else os.path.join(here, "model_approx_As_bs.npz")
     v = read_mat73(src)
     A_s, b_s = v["A_s"], v["b_s"]

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,7 +41,7 @@ def test_bench_gpus2_self_launch_rehearsal(gpu):
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line_has_both_rooflines(gpu):
-    out = _run(["--steps", "20", "--warmup", "5", "--no-extra", "--no-cpu-baseline"], {"FMPC_BENCH_REGIONS": "3"})
+    out = _run(["--full", "--steps", "20", "--warmup", "5", "--no-extra", "--no-cpu-baseline"], {"FMPC_BENCH_REGIONS": "3"})
     r, rp = out["roofline"], out["roofline_per_problem_factor"]
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
     # the headline's roofline describes the timed region: bytes per unit x units / device time per step
@@ -57,3 +58,29 @@ def test_bench_single_gpu_line_has_both_rooflines(gpu):
     assert rp["hbm_streamed_factor_model"]["bytes_per_unit"] == 41472 + 8 * 2 * 30 * 3 * 27 * 27
     assert rp["bound"] == "mfma" and "n_newton_5" in rp and rp["n_newton_5"]["frac"] > 0
     assert abs(rp["achieved"] - rp["flops_per_unit"] * rp["units_per_launch"] / (rp["ms_per_step"] * 1e-3) / 1e12) <= 1e-9 * rp["achieved"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_step(pkg, gpu, tmp_path):
+    """Without --full the line carries the headline alone, timed over exactly --steps steps; --dump-outputs writes what the
+    last timed step handed its caller.  37 steps from buffer set 0 of 4: the last one solves set 0, the batch of realisation 0."""
+    from tests.util import oracle_batch, rel_err
+    out = _run(["--steps", "37", "--warmup", "3", "--dump-outputs", str(tmp_path)], {})
+    assert out["steps"] == 37 and out["warmup"] == 3 and out["ms_per_step"] > 0 and out["dtype"] == "f64"
+    assert out["higher_is_better"] is True and out["unit"] == "MPC steps/s"
+    assert abs(out["value"] - out["config"]["batch_per_gpu"] / (out["ms_per_step"] * 1e-3)) <= 1e-6 * out["value"]
+    assert not any(k in out for k in ("extra", "cpu_baseline", "roofline_per_problem_factor")) and "contiguous_rows" not in out["roofline"]
+    got = {p.name[:-4]: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(got) == {"z_sample", "z_sample_rows", "u0", "iters", "status"}
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    n, m, T, B = 27, 144, 30, 2000
+    rows = got["z_sample_rows"].astype(int)
+    assert got["z_sample"].shape == (len(rows), T * (n + m)) and got["u0"].shape == (B, m) and got["iters"].shape == (B,)
+    assert len(np.unique(rows)) == len(rows) == 512 and rows.min() >= 0 and rows.max() < B
+    assert np.array_equal(got["u0"][rows], got["z_sample"][:, :m]) and (got["status"] >= 0).all()
+    model = pkg.synthetic.make_model(n, m, T)
+    data = pkg.synthetic.make_replay_batch(model, r=0, steps=B)
+    pick = rows[:4]
+    zo, _, ito, _, _ = oracle_batch(model, {k: (None if v is None else v[pick]) for k, v in data.items()}, 1, 1e-2)
+    assert np.array_equal(got["iters"][pick], ito)
+    assert max(rel_err(got["z_sample"][i], zo[i]) for i in range(len(pick))) <= 1e-9
