@@ -19,7 +19,7 @@
 #include "fmpc_tiled.h"
 #include "fmpc_rampcold.h"
 #define FMPC_PRODUCT_MIN_BATCH_DEFAULT 65   // closed-loop steps with first moves only: the product form from this many realisations on
-#include "fmpc_alloc.h"                    // counted hipMalloc / hipFree (fmpc_alloc_generation), shared with fmpc_est_api.hip
+#include "fmpc_alloc.h"                    // owned, counted buffers (fmpc_alloc_generation), shared with fmpc_est_api.hip
 
 std::atomic<unsigned long long> fmpc_alloc_gen{0};
 extern "C" unsigned long long fmpc_alloc_generation(void) { return fmpc_alloc_gen.load(); }
@@ -58,16 +58,7 @@ int fmpc_wave_waves_per_wg();
 size_t fmpc_wave_ws_doubles(int n, int m, int mp, int T, int nb);
 void fmpc_wave_make_images(int n, const double* blk, double* out);
 hipError_t fmpc_wave_prepare(int n, size_t lds_bytes);
-hipError_t fmpc_launch_wave(const FmpcDevModel& M, const FwModel& V, int batch, int grid,
-                            const double* x0, const double* x0p, const double* w, const double* zinit,
-                            const double* nu0, int max_iter, double kbar, double* zout, double* nuout,
-                            int* status, int* iters, double* step, int step_ld, double* ws,
-                            size_t ws_stride, size_t lds_bytes, hipStream_t stream,
-                            int mode, double* sh_fac, double* sh_rs, int* sh_ok, const double* cold,
-                            const double* gate = nullptr, const double* epsp = nullptr, int* handed = nullptr,
-                            const double* nuws = nullptr, double* u0out = nullptr,
-                            int pphase = 0, const double* rnp = nullptr, int* list = nullptr, int u0_done = 0,
-                            int* nflag = nullptr, int zld = 0);
+hipError_t fmpc_launch_wave(const FwParams& P, int grid, size_t lds_bytes, hipStream_t stream);
 size_t fmpc_wave_shared_fac_doubles(int n, int nb);
 void fmpc_wave_cold_layout(int n, int mp, int* off9);
 
@@ -81,77 +72,78 @@ struct fmpc_handle_s {
     int num_cu;
     FmpcDevModel dev;            // device pointers into `pool`
     const double* loop_M1; const double* loop_M2;   // closed-loop prediction matrices (T n) x n, row-major
-    double* pool_d;              // one allocation for all shared doubles
-    int* pool_i;                 // and one for the index arrays
+    DevBuf<double> pool_d;       // one allocation for all shared doubles
+    DevBuf<int> pool_i;          // and one for the index arrays
     size_t lds_bytes;
     int wg_per_cu;
     // wave kernel (n = 27): used when available unless FMPC_FORCE_GENERIC=1
-    int use_wave;
-    double* fm_forms;            // diagnostic: where the one-step first-move kernel leaves the bounds its decision used (fmpc_debug_first_move_forms)
-    double* fm_compact;          // compact batch of the stopped realisations of a walk (fmpc_loop_run_walk)
-    int* fm_walk_i; size_t fm_walk_cap;   // start / stop step per realisation of a walk
+    int use_wave = 0;
+    double* fm_forms = nullptr;  // diagnostic: where the one-step first-move kernel leaves the bounds its decision used (fmpc_debug_first_move_forms)
+    DevBuf<double> fm_compact;   // compact batch of the stopped realisations of a walk (fmpc_loop_run_walk)
+    DevBuf<int> fm_walk_i; size_t fm_walk_cap = 0;   // start / stop step per realisation of a walk
     // affine form of the cold-start step without w (fmpc_kernel_affine.hip), built with the first-move form
-    FaParams fa_P; int fa_valid, fa_disabled; int* fa_need; size_t fa_need_cap;
-    double* ao_scr; size_t ao_cap;       // fmpc_ao_step_device: a zero a[k] and scratch x0 / x0_pre for the loop-input kernel (3 batch n)
-    FlParams fs_P; FlStepIn fs_I; int fs_valid, fs_disabled, fs_min_batch;   // the fused step (fmpc_loop_step27): images in its column order, B's images
-    FlParams fl_P; int fl_valid, fl_disabled;       // first-move form as a product: closed-loop steps of > 64 realisations (fmpc_kernel_loopu0.hip)
+    FaParams fa_P; int fa_valid = 0, fa_disabled = 0; DevBuf<int> fa_need;
+    DevBuf<double> ao_scr;               // fmpc_ao_step_device: a zero a[k] and scratch x0 / x0_pre for the loop-input kernel (3 batch n)
+    FlParams fs_P; FlStepIn fs_I; int fs_valid = 0, fs_disabled = 0, fs_min_batch = FMPC_PRODUCT_MIN_BATCH_DEFAULT;   // the fused step (fmpc_loop_step27): images in its column order, B's images
+    FlParams fl_P; int fl_valid = 0, fl_disabled = 0;   // first-move form as a product: closed-loop steps of > 64 realisations (fmpc_kernel_loopu0.hip)
     FwModel wave;
-    double* wave_pool_d;
-    int* wave_pool_i;
-    size_t wave_lds;
+    DevBuf<double> wave_pool_d;
+    DevBuf<int> wave_pool_i;
+    size_t wave_lds = 0;
     // shared cold-start factor (SURVEY §7.2a regime (ii)): Phi, Y and its Cholesky factor are the
     // same for every problem in the first Newton step from the mid-box start; it depends only on the
     // model and on k, so it is computed once per (handle, k) and kept in HBM (L2-resident, 0.5 MB).
-    double* sh_fac; double* sh_rs; int* sh_ok; double* sh_scratch;
-    double sh_k; int sh_valid; int sh_enabled;
-    double* cold_d;                      // cold-start constants on the device (FwCold layout)
+    DevBuf<double> sh_fac, sh_rs; DevBuf<int> sh_ok; DevBuf<double> sh_scratch;
+    double sh_k = 0.0; int sh_valid = 0, sh_enabled = 0;
+    DevBuf<double> cold_d;               // cold-start constants on the device (FwCold layout)
     // panel kernel (fmpc_kernel_panel.hip): the cold-start step on 16-problem panels, n_newton = 1
-    int pn_enabled, pn_valid, pn_mp;
-    int last_path;
-    size_t pn_lds;
-    double* pn_pool;                     // [simg | btimg | aimg | vec | ucon]
+    int pn_enabled = 0, pn_valid = 0, pn_mp = 0;
+    int last_path = 0;
+    size_t pn_lds = 0;
+    DevBuf<double> pn_pool;              // [simg | btimg | aimg | vec | ucon]
     size_t pn_o_simg, pn_o_limg, pn_o_bt, pn_o_aimg, pn_o_vec, pn_o_ucon, pn_o_dump, pn_doubles;
-    int* pn_cnt;                         // problems the exact path had to solve in the last call (diagnostic)
-    int* gn_list; double* gn_nu; int* gn_cnt; int* gn_cnt_host; size_t gn_cap; int gn_split;   // explicit-start batches with a budget > 1: first step / continuation split (FMPC_NO_GENERAL_SPLIT=1: one launch)
-    int* fa_nflag;                       // affine form: [running count of flagged problems | the count the last exact-path launch dealt with | its
+    DevBuf<int> pn_cnt;                  // problems the exact path had to solve in the last call (diagnostic)
+    DevBuf<int> gn_list; DevBuf<double> gn_nu; DevBuf<int> gn_cnt; PinnedBuf<int> gn_cnt_host; size_t gn_cap = 0;   // explicit-start batches with a budget > 1: first step / continuation split
+    int gn_split = 1;                                                                                           // (FMPC_NO_GENERAL_SPLIT=1: one launch)
+    DevBuf<int> fa_nflag;                // affine form: [running count of flagged problems | the count the last exact-path launch dealt with | its
                                          // ticket]: the exact-path launch leaves at once while the two counts agree (FwParams::nflag)
-    size_t pn_cap;                       // per-batch buffers of the panel path, grown together
-    double* pn_gate; double* pn_epsp; double* pn_nuws;
-    double* pn_rnp; int* pn_list;        // budgets > 1: next-exit-test partials, compacted list of the problems that go on
-    int* pn_cnt_host;                    // pinned copy of pn_cnt of an EARLIER call (never waited for): sizes the continuation grid
+    size_t pn_cap = 0;                   // per-batch buffers of the panel path, grown together
+    DevBuf<double> pn_gate, pn_epsp, pn_nuws;
+    DevBuf<double> pn_rnp; DevBuf<int> pn_list;   // budgets > 1: next-exit-test partials, compacted list of the problems that go on
+    PinnedBuf<int> pn_cnt_host;          // pinned copy of pn_cnt of an EARLIER call (never waited for): sizes the continuation grid
     size_t pn_o_dz; int pn_dz_len;
-    size_t pn_dz_lds;
-    double pn_rd2_0, pn_rp2c;
+    size_t pn_dz_lds = 0;
+    double pn_rd2_0 = 0.0, pn_rp2c = 0.0;
     // dense form of the cold-start dual solve (fmpc_kernel_inv.hip): nu+ = nuc + J d, built per (handle, k) on first use
-    int inv_enabled, inv_valid, inv_jks, inv_max_batch, inv_last; double inv_k;
-    int inv_failed; double inv_failed_k;                         // the build for this k gave a non-finite J: not retried
-    double* inv_jimg; double* inv_nuc; double* inv_eimg;
-    double* inv_jst; double* inv_nucst; int inv_fuse;            // per-stage rows of J_x and nuc: the dual solve fused into d_z (w = NULL, no xf, budget 1)
-    double* inv_jimg2; int inv_jks2;     // J' = [J_x | -J_w M1 | -J_w M2]: closed-loop steps, w = -M1 B u1 - M2 B u2 (fmpc_loop_step_device)
-    double* lp_v; size_t lp_cap; int lp_hint;                    // [B u1 ; B u2] per problem of the running loop step
+    int inv_enabled = 0, inv_valid = 0, inv_jks = 0, inv_max_batch = 768, inv_last = 0; double inv_k = 0.0;
+    int inv_failed = 0; double inv_failed_k = 0.0;               // the build for this k gave a non-finite J: not retried
+    DevBuf<double> inv_jimg, inv_nuc, inv_eimg;
+    DevBuf<double> inv_jst, inv_nucst; int inv_fuse = 0;         // per-stage rows of J_x and nuc: the dual solve fused into d_z (w = NULL, no xf, budget 1)
+    DevBuf<double> inv_jimg2; int inv_jks2 = 0;  // J' = [J_x | -J_w M1 | -J_w M2]: closed-loop steps, w = -M1 B u1 - M2 B u2 (fmpc_loop_step_device)
+    DevBuf<double> lp_v; int lp_hint = 0;                        // [B u1 ; B u2] per problem of the running loop step
     // first-move form of the closed-loop step (fmpc_kernel_first.hip): host copies of J (columns [x0 | x0_pre | B u1 | B u2]) and
     // nuc kept by fmpc_build_inverse, the derived matrices on the device per (handle, k), a flag per realisation
-    std::vector<double> hm_J4, hm_nuc; double hm_J4_k; int hm_J4_valid;
-    double* fm_pool; int fm_valid, fm_disabled; double fm_k; FmParams fm_P; int* fm_need; size_t fm_need_cap;
+    std::vector<double> hm_J4, hm_nuc; double hm_J4_k = 0.0; int hm_J4_valid = 0;
+    DevBuf<double> fm_pool; int fm_valid = 0, fm_disabled = 0; double fm_k = 0.0; FmParams fm_P; DevBuf<int> fm_need;
     std::vector<double> hm_m1, hm_m2;
     std::vector<double> hm_Q2, hm_Qf2, hm_ql, hm_qfl, hm_xf, hm_blocks;
     std::vector<int> hm_idxD, hm_idx1, hm_idx2;
-    int* pn_sched; int pn_nsf, pn_nsb, pn_limg_cap;
+    DevBuf<int> pn_sched; int pn_nsf = 0, pn_nsb = 0, pn_limg_cap = 0;
     std::vector<double> hm_R2, hm_rl, hm_umin, hm_umax, hm_umid, hm_xmid, hm_bt, hm_a1, hm_a2;   // host copies
     // tiled kernel (fmpc_kernel_tiled.hip): workgroup per problem, any n <= 79; images per arithmetic type, built on first use
     int generic_ok;                      // the generic kernel's LDS tiles fit (n <= 64), or generic_big
     int prefer_tiled;                    // the fp64 tiled kernel exists for this size: it is 1.3 (n = 4) to 9 (n = 45) times faster than the
                                          // generic kernel at every batch size (round 5 measurement): the default; FMPC_FORCE_GENERIC=1: generic
     int generic_big;                     // sizes no other kernel takes (n > 79 ...), diagonal weights: the generic kernel with its tiles in the workspace
-    int prec;                            // FMPC_PREC_F64 / FMPC_PREC_F32_MIXED of the per-problem-factor path
-    int force_tiled;                     // FMPC_TILED=1: route every solve through the tiled kernel (tests, profiles)
-    struct Tiled { int ready, NB, NW; size_t lds; void* pool; int* ipool; double* bm; FtModel V; } tl[2];   // bm: padded fp64 images   // [0] fp64, [1] fp32
-    double* tl_ws; size_t tl_ws_doubles; int tl_prepared;         // (bit NW: that wavefront count of the fp64 instance is prepared)
-    int tl_last_nw;                       // wavefronts per problem of the last tiled launch (diagnostic)
-    int z_ld;                             // fmpc_set_z_ld: doubles between the z rows of consecutive problems (0: T (n + m))
-    int small_tiled;                      // per-problem-factor solves of few problems go to the tiled kernel (FMPC_NO_SMALL_TILED=1: off)
-    int small_nw;                         // ... with this many wavefronts per problem: 4 (default since round 5) or 2 (FMPC_SMALL_TILED_NW=2 /
-                                          // fmpc_set_small_batch_kernel(h, 4): opt-in, see the note at FT_DISPATCH in fmpc_kernel_tiled.hip)
+    int prec = FMPC_PREC_F64;            // FMPC_PREC_F64 / FMPC_PREC_F32_MIXED of the per-problem-factor path
+    int force_tiled = 0;                 // FMPC_TILED=1: route every solve through the tiled kernel (tests, profiles)
+    struct Tiled { int ready = 0, NB = 0, NW = 0; size_t lds = 0; DevBuf<char> pool; DevBuf<int> ipool; DevBuf<double> bm; FtModel V; } tl[2];   // bm: padded fp64 images   // [0] fp64, [1] fp32
+    DevBuf<double> tl_ws; int tl_prepared = 0;                   // (bit NW: that wavefront count of the fp64 instance is prepared)
+    int tl_last_nw = 0;                   // wavefronts per problem of the last tiled launch (diagnostic)
+    int z_ld = 0;                         // fmpc_set_z_ld: doubles between the z rows of consecutive problems (0: T (n + m))
+    int small_tiled = 1;                  // per-problem-factor solves of few problems go to the tiled kernel (FMPC_NO_SMALL_TILED=1: off)
+    int small_nw = 4;                     // ... with this many wavefronts per problem: 4, the default (round 5), or 2 (FMPC_SMALL_TILED_NW=2 /
+                                          // fmpc_set_small_batch_kernel(h, 2))
     std::vector<double> hm_b;            // B row-major n x m
     std::vector<double> hm_a1f, hm_a2f;  // A1, A2 row-major (always kept: the tiled kernel's images)
     int denseQ;                          // Q or Qf not diagonal: tiled kernel only
@@ -159,29 +151,41 @@ struct fmpc_handle_s {
     std::vector<double> hm_r2full;       // 2R, m x m row-major
     std::vector<double> hm_q2m, hm_qf2m, hm_xm, hm_xfm;   // 2Q, 2Qf, (2Q)^-1, (2Qf)^-1 row-major
     // ramp-rate rows (VAR_1): bounds on the device, own workspace (dense Y per workgroup)
-    double* ramp_du;             // [du_min | du_max], 2 m doubles; nullptr until fmpc_set_ramp
-    double* ramp_ws; size_t ramp_ws_doubles;
+    DevBuf<double> ramp_du;      // [du_min | du_max], 2 m doubles; empty until fmpc_set_ramp
+    DevBuf<double> ramp_ws;
     // cold-start step with the ramp rows in its Woodbury form (fmpc_ramp_cold): constants per (handle, k, ramp bounds)
     std::vector<double> hm_dumin, hm_dumax;
-    int rc_disabled, rc_valid, rc_failed, rc_last; double rc_k, rc_failed_k;
-    double* rc_pool; FrColdParams rc_P;
-    double* rc_ws; size_t rc_ws_doubles;
-    double* rc_nu; int* rc_si; size_t rc_cap;     // nu / status / iters of the first step when the caller passes none (budgets > 1)
+    int rc_disabled = 0, rc_valid = 0, rc_failed = 0, rc_last = 0; double rc_k = 0.0, rc_failed_k = 0.0;
+    DevBuf<double> rc_pool; FrColdParams rc_P;
+    DevBuf<double> rc_ws;
+    DevBuf<double> rc_nu; DevBuf<int> rc_si; size_t rc_cap = 0;   // nu / status / iters of the first step when the caller passes none (budgets > 1)
     // A handle's device workspaces serve ONE solve at a time.  Solves enqueued on different streams are ordered on
     // the device: every solve records `ev`, and a solve on another stream than the last one waits for it first.
-    hipEvent_t ev; int ev_valid; hipStream_t last_stream;
+    hipEvent_t ev = nullptr; int ev_valid = 0; hipStream_t last_stream = nullptr;
     // workspace, grown on demand; `mu` serialises the host-side enqueue (a handle may be shared between threads)
     std::mutex mu;
     std::mutex host_mu;          // serialises the host-pointer entry points (shared staging)
-    double* ws;
-    size_t ws_doubles;
+    DevBuf<double> ws;
     // z_out == NULL (first moves only): the working iterate of the problems a kernel has to iterate on lives here
-    double* zs; size_t zs_doubles;
+    DevBuf<double> zs;
     // staging for the host-pointer entry points
-    void* stage;
-    size_t stage_bytes;
-    void* pin; void* pin_dev; size_t pin_bytes;         // pinned host twin of the staging block for small host-pointer solves (fmpc_solve_host)
+    DevBuf<char> stage;
+    PinnedBuf<char> pin; void* pin_dev = nullptr;   // pinned host twin of the staging block for small host-pointer solves (fmpc_solve_host)
+
+    ~fmpc_handle_s() { if (ev) (void)hipEventDestroy(ev); }
 };
+
+// The arguments of one device solve, as fmpc_solve_device_inner and the path it picks read them
+struct FmpcSolve {
+    int batch;
+    const double* x0; const double* x0_pre; const double* w; const double* z_init; const double* nu0;
+    int n_newton; double k;
+    double* z_out; double* nu_out; int* status; int* iters; double* step;
+    double* u0_out;                      // the first moves, or NULL
+    hipStream_t stream;
+    int ldz;                             // doubles between the z rows of consecutive problems (0: contiguous; -1: the handle's fmpc_set_z_ld value)
+};
+static inline int fmpc_max_iter(const FmpcSolve& s) { return s.n_newton > 0 ? s.n_newton : 1000; }
 
 extern "C" int fmpc_version(void) { return FMPC_VERSION; }
 
@@ -331,40 +335,22 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
     if (!h) return FMPC_E_ALLOC;
     h->n = n; h->m = m; h->T = T; h->var_order = var_order; h->has_xf = xf ? 1 : 0;
     h->nb = T + h->has_xf; h->device = device;
-    h->pool_d = nullptr; h->pool_i = nullptr; h->ws = nullptr; h->ws_doubles = 0; h->zs = nullptr; h->zs_doubles = 0;
-    h->stage = nullptr; h->stage_bytes = 0; h->lds_bytes = lds;
-    h->pin = nullptr; h->pin_bytes = 0; h->pin_dev = nullptr;
-    h->ramp_du = nullptr; h->ramp_ws = nullptr; h->ramp_ws_doubles = 0;
+    h->lds_bytes = lds;
     { const char* e = getenv("FMPC_NO_RAMP_COLD"); h->rc_disabled = (e && e[0] == '1') ? 1 : 0; }
-    h->rc_valid = 0; h->rc_failed = 0; h->rc_last = 0; h->rc_k = 0.0; h->rc_failed_k = 0.0; h->rc_pool = nullptr;
-    h->rc_ws = nullptr; h->rc_ws_doubles = 0; h->rc_nu = nullptr; h->rc_si = nullptr; h->rc_cap = 0;
-    h->ev = nullptr; h->ev_valid = 0; h->last_stream = nullptr;
     h->generic_ok = generic_ok ? 1 : 0; h->generic_big = generic_big ? 1 : 0;
     { const char* fg = getenv("FMPC_FORCE_GENERIC"); h->prefer_tiled = (tiled64_any && !generic_big && !(fg && fg[0] == '1')) ? 1 : 0; }
     // fp64 wherever an fp64 kernel on the matrix cores (or the generic kernel) exists -- the reference is fp64 throughout and the literal
     // drop-in call (fmpc_solve_once) has no precision argument; the fp32 factor (BASELINE configs[4]) is a request since round 5
     h->prec = (generic_ok || tiled64_any) ? FMPC_PREC_F64 : FMPC_PREC_F32_MIXED;
     { const char* ft = getenv("FMPC_TILED"); h->force_tiled = (ft && ft[0] == '1') ? 1 : 0; }
-    memset(h->tl, 0, sizeof(h->tl)); h->tl_ws = nullptr; h->tl_ws_doubles = 0; h->tl_prepared = 0;
     { const char* ns = getenv("FMPC_NO_SMALL_TILED"); h->small_tiled = (ns && ns[0] == '1') ? 0 : 1; }
-    h->z_ld = 0;
     { const char* nw = getenv("FMPC_SMALL_TILED_NW"); h->small_nw = (nw && nw[0] == '2') ? 2 : 4; }      // (four: the default again, round 5)
-    h->use_wave = 0; h->wave_pool_d = nullptr; h->wave_pool_i = nullptr; h->wave_lds = 0;
-    h->sh_fac = nullptr; h->sh_rs = nullptr; h->sh_ok = nullptr; h->sh_scratch = nullptr; h->sh_k = 0.0; h->sh_valid = 0; h->sh_enabled = 0; h->cold_d = nullptr;
-    h->last_path = 0; h->pn_sched = nullptr; h->pn_nsf = 0; h->pn_nsb = 0; h->pn_limg_cap = 0; h->pn_enabled = 0; h->pn_valid = 0; h->pn_mp = 0; h->pn_lds = 0; h->pn_pool = nullptr;
-    h->hm_J4_valid = 0; h->hm_J4_k = 0.0; h->fm_pool = nullptr; h->fm_valid = 0; h->fm_disabled = 0; h->fm_k = 0.0; h->fm_need = nullptr; h->fm_need_cap = 0; h->fm_compact = nullptr; h->fm_forms = nullptr; h->fm_walk_i = nullptr; h->fm_walk_cap = 0;
-    h->tl_last_nw = 0; h->ao_scr = nullptr; h->ao_cap = 0;
-    h->fa_valid = 0; h->fa_need = nullptr; h->fa_need_cap = 0; h->fl_valid = 0; h->fs_valid = 0;
     { const char* na = getenv("FMPC_NO_AFFINE"); h->fa_disabled = (na && na[0] == '1') ? 1 : 0; }
     { const char* na = getenv("FMPC_NO_LOOP_U0"); h->fl_disabled = (na && na[0] == '1') ? 1 : 0; }
     { const char* na = getenv("FMPC_NO_LOOP_FUSE"); h->fs_disabled = (na && na[0] == '1') ? 1 : 0; }
     { const char* na = getenv("FMPC_PRODUCT_MIN_BATCH"); h->fs_min_batch = (na && atoi(na) >= 1) ? atoi(na) : FMPC_PRODUCT_MIN_BATCH_DEFAULT; }
     { const char* nf = getenv("FMPC_NO_FIRST_MOVE"); h->fm_disabled = (nf && nf[0] == '1') ? 1 : 0; }
-    h->inv_failed = 0; h->inv_failed_k = 0.0; h->inv_enabled = 0; h->inv_last = 0; h->inv_valid = 0; h->inv_jks = 0; h->inv_max_batch = 768; h->inv_k = 0.0; h->inv_jimg = nullptr; h->inv_nuc = nullptr; h->inv_eimg = nullptr; h->inv_jst = nullptr; h->inv_nucst = nullptr; h->inv_fuse = 0; h->inv_jimg2 = nullptr; h->inv_jks2 = 0; h->lp_v = nullptr; h->lp_cap = 0; h->lp_hint = 0;
-    h->fa_nflag = nullptr;
-    h->gn_list = nullptr; h->gn_nu = nullptr; h->gn_cnt = nullptr; h->gn_cnt_host = nullptr; h->gn_cap = 0;
     { const char* gs = getenv("FMPC_NO_GENERAL_SPLIT"); h->gn_split = (gs && gs[0] == '1') ? 0 : 1; }
-    h->pn_cnt = nullptr; h->pn_cap = 0; h->pn_gate = nullptr; h->pn_epsp = nullptr; h->pn_nuws = nullptr; h->pn_rnp = nullptr; h->pn_list = nullptr; h->pn_cnt_host = nullptr; h->pn_dz_lds = 0; h->pn_rd2_0 = 0.0; h->pn_rp2c = 0.0;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) { delete h; return FMPC_E_HIP; }
     h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -468,16 +454,9 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
     ipool.insert(ipool.end(), idx1.begin(), idx1.end());
     ipool.insert(ipool.end(), idx2.begin(), idx2.end());
 
-    if (hipMalloc((void**)&h->pool_d, pool.size() * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&h->pool_i, ipool.size() * sizeof(int)) != hipSuccess) {
-        fmpc_destroy(h);
-        return FMPC_E_ALLOC;
-    }
-    if (hipMemcpy(h->pool_d, pool.data(), pool.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(h->pool_i, ipool.data(), ipool.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-        fmpc_destroy(h);
-        return FMPC_E_HIP;
-    }
+    int rc = h->pool_d.assign(pool.data(), pool.size(), nullptr);
+    if (rc == FMPC_OK) rc = h->pool_i.assign(ipool.data(), ipool.size(), nullptr);
+    if (rc != FMPC_OK) { fmpc_destroy(h); return rc; }
     FmpcDevModel& D = h->dev;
     D.n = n; D.m = m; D.T = T; D.nb = h->nb; D.has_xf = h->has_xf; D.var2 = var2 ? 1 : 0;
     D.A1 = h->pool_d + oA1; D.A2 = h->pool_d + oA2; D.A1t = h->pool_d + oA1t; D.A2t = h->pool_d + oA2t;
@@ -524,16 +503,9 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
         for (int i = 0; i < h->nb; ++i) wi.push_back(idxD[i]);
         for (int i = 0; i < h->nb; ++i) wi.push_back(idx1[i] >= 0 ? idx1[i] : nblk);
         for (int i = 0; i < h->nb; ++i) wi.push_back(idx2[i] >= 0 ? idx2[i] : nblk);
-        if (hipMalloc((void**)&h->wave_pool_d, wpool.size() * sizeof(double)) != hipSuccess ||
-            hipMalloc((void**)&h->wave_pool_i, wi.size() * sizeof(int)) != hipSuccess) {
-            fmpc_destroy(h);
-            return FMPC_E_ALLOC;
-        }
-        if (hipMemcpy(h->wave_pool_d, wpool.data(), wpool.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(h->wave_pool_i, wi.data(), wi.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-            fmpc_destroy(h);
-            return FMPC_E_HIP;
-        }
+        rc = h->wave_pool_d.assign(wpool.data(), wpool.size(), nullptr);
+        if (rc == FMPC_OK) rc = h->wave_pool_i.assign(wi.data(), wi.size(), nullptr);
+        if (rc != FMPC_OK) { fmpc_destroy(h); return rc; }
         h->wave.mp = mp;
         h->wave.img = h->wave_pool_d;
         h->wave.BtP = h->wave_pool_d + oBtP;
@@ -547,10 +519,8 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
         if (!(nosh && nosh[0] == '1') && h->nb * n <= 840) {     // the cold path keeps rhs/y/d_nu in an 840-double LDS vector
             const size_t nf = fmpc_wave_shared_fac_doubles(n, h->nb);
             const size_t nscr = (size_t)T * (n + m) + 64 + (size_t)n;      // zero state + z of the export solve
-            if (hipMalloc((void**)&h->sh_fac, nf * sizeof(double)) != hipSuccess ||
-                hipMalloc((void**)&h->sh_rs, (size_t)h->nb * 32 * sizeof(double)) != hipSuccess ||
-                hipMalloc((void**)&h->sh_ok, sizeof(int)) != hipSuccess ||
-                hipMalloc((void**)&h->sh_scratch, nscr * sizeof(double)) != hipSuccess) {
+            if (h->sh_fac.alloc(nf, nullptr) != FMPC_OK || h->sh_rs.alloc((size_t)h->nb * 32, nullptr) != FMPC_OK ||
+                h->sh_ok.alloc(1, nullptr) != FMPC_OK || h->sh_scratch.alloc(nscr, nullptr) != FMPC_OK) {
                 fmpc_destroy(h);
                 return FMPC_E_ALLOC;
             }
@@ -558,7 +528,7 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
             (void)hipMemset(h->sh_scratch, 0, nscr * sizeof(double));
             int off9[14];
             fmpc_wave_cold_layout(n, mp, off9);
-            if (hipMalloc((void**)&h->cold_d, (size_t)off9[8] * sizeof(double)) != hipSuccess) { fmpc_destroy(h); return FMPC_E_ALLOC; }
+            if (h->cold_d.alloc((size_t)off9[8], nullptr) != FMPC_OK) { fmpc_destroy(h); return FMPC_E_ALLOC; }
             h->hm_R2 = R2; h->hm_rl.assign(m, 0.0); if (r) h->hm_rl.assign(r, r + m);
             h->hm_umin.assign(u_min, u_min + m); h->hm_umax.assign(u_max, u_max + m);
             h->hm_umid = umid; h->hm_xmid = xmid; h->hm_bt = bt; h->hm_a1 = a1; h->hm_a2 = a2;
@@ -574,12 +544,11 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
                 h->pn_o_simg = PL.o_simg; h->pn_limg_cap = PL.limg_cap; h->pn_o_limg = PL.o_limg; h->pn_o_bt = PL.o_bt;
                 h->pn_o_aimg = PL.o_aimg; h->pn_o_vec = PL.o_vec; h->pn_o_ucon = PL.o_ucon; h->pn_o_dz = PL.o_dz;
                 h->pn_doubles = PL.pool_doubles;
-                if (hipMalloc((void**)&h->pn_pool, o * sizeof(double)) != hipSuccess ||
-                    hipMalloc((void**)&h->pn_cnt, 2 * sizeof(int)) != hipSuccess || hipMalloc((void**)&h->fa_nflag, 4 * sizeof(int)) != hipSuccess ||
-                    hipMalloc((void**)&h->pn_sched, (size_t)2 * FP_MAX_STEPS(h->nb) * FP_STEP_INTS * sizeof(int)) != hipSuccess) { fmpc_destroy(h); return FMPC_E_ALLOC; }
+                if (h->pn_pool.alloc(o, nullptr) != FMPC_OK || h->pn_cnt.alloc(2, nullptr) != FMPC_OK || h->fa_nflag.alloc(4, nullptr) != FMPC_OK ||
+                    h->pn_sched.alloc((size_t)2 * FP_MAX_STEPS(h->nb) * FP_STEP_INTS, nullptr) != FMPC_OK) { fmpc_destroy(h); return FMPC_E_ALLOC; }
                 (void)hipMemset(h->pn_cnt, 0, 2 * sizeof(int));     // [handed over, length of the continuation list]
                 (void)hipMemset(h->fa_nflag, 0, 4 * sizeof(int));
-                if (hipHostMalloc((void**)&h->pn_cnt_host, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess) { fmpc_destroy(h); return FMPC_E_ALLOC; }
+                if (h->pn_cnt_host.alloc(2, nullptr) != FMPC_OK) { fmpc_destroy(h); return FMPC_E_ALLOC; }
                 h->pn_cnt_host[0] = -1; h->pn_cnt_host[1] = -1;   // nothing known yet
                 h->pn_dz_lds = fmpc_dz_lds_bytes(pmp, 1);
                 if (fmpc_panel_prepare(plds) != hipSuccess || fmpc_dz_prepare(pmp) != hipSuccess) { fmpc_destroy(h); return FMPC_E_HIP; }
@@ -597,12 +566,12 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
                     h->inv_jks = FP_XKS + (T * n + 3) / 4;
                     h->inv_jks2 = 2 * FP_XKS;                       // [x0 ; x0_pre ; 0 0 ; B u1 ; B u2 ; 0 0]
                     const size_t nrt = ((size_t)h->nb * n + 15) / 16;
-                    if (h->inv_enabled && (hipMalloc((void**)&h->inv_jimg, nrt * (size_t)(16 * ((h->inv_jks + 15) / 16 + 3)) * 64 * sizeof(double)) != hipSuccess ||
-                                           hipMalloc((void**)&h->inv_nuc, nrt * 16 * sizeof(double)) != hipSuccess ||
-                                           hipMalloc((void**)&h->inv_eimg, 4 * FP_XKS * 64 * sizeof(double)) != hipSuccess ||
-                                           hipMalloc((void**)&h->inv_jst, (size_t)h->nb * 2 * FP_XKS * 64 * sizeof(double)) != hipSuccess ||
-                                           hipMalloc((void**)&h->inv_nucst, (size_t)h->nb * 32 * sizeof(double)) != hipSuccess ||
-                                           hipMalloc((void**)&h->inv_jimg2, nrt * (size_t)(16 * ((2 * FP_XKS + 15) / 16 + 3)) * 64 * sizeof(double)) != hipSuccess)) { fmpc_destroy(h); return FMPC_E_ALLOC; }
+                    if (h->inv_enabled && (h->inv_jimg.alloc(nrt * (size_t)(16 * ((h->inv_jks + 15) / 16 + 3)) * 64, nullptr) != FMPC_OK ||
+                                           h->inv_nuc.alloc(nrt * 16, nullptr) != FMPC_OK ||
+                                           h->inv_eimg.alloc(4 * FP_XKS * 64, nullptr) != FMPC_OK ||
+                                           h->inv_jst.alloc((size_t)h->nb * 2 * FP_XKS * 64, nullptr) != FMPC_OK ||
+                                           h->inv_nucst.alloc((size_t)h->nb * 32, nullptr) != FMPC_OK ||
+                                           h->inv_jimg2.alloc(nrt * (size_t)(16 * ((2 * FP_XKS + 15) / 16 + 3)) * 64, nullptr) != FMPC_OK)) { fmpc_destroy(h); return FMPC_E_ALLOC; }
                 }
             }
         }
@@ -614,59 +583,6 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
 extern "C" int fmpc_destroy(fmpc_handle h) {
     if (!h) return FMPC_E_NULL;
     (void)hipSetDevice(h->device);
-    if (h->pool_d) (void)hipFree(h->pool_d);
-    if (h->pool_i) (void)hipFree(h->pool_i);
-    if (h->wave_pool_d) (void)hipFree(h->wave_pool_d);
-    if (h->wave_pool_i) (void)hipFree(h->wave_pool_i);
-    if (h->sh_fac) (void)hipFree(h->sh_fac);
-    if (h->sh_rs) (void)hipFree(h->sh_rs);
-    if (h->sh_ok) (void)hipFree(h->sh_ok);
-    if (h->sh_scratch) (void)hipFree(h->sh_scratch);
-    if (h->cold_d) (void)hipFree(h->cold_d);
-    if (h->inv_jimg) (void)hipFree(h->inv_jimg);
-    if (h->inv_nuc) (void)hipFree(h->inv_nuc);
-    if (h->inv_eimg) (void)hipFree(h->inv_eimg);
-    if (h->inv_jst) (void)hipFree(h->inv_jst);
-    if (h->inv_nucst) (void)hipFree(h->inv_nucst);
-    if (h->inv_jimg2) (void)hipFree(h->inv_jimg2);
-    if (h->fm_pool) (void)hipFree(h->fm_pool);
-    if (h->fm_need) (void)hipFree(h->fm_need);
-    if (h->fa_need) (void)hipFree(h->fa_need);
-    if (h->ao_scr) (void)hipFree(h->ao_scr);
-    if (h->fm_compact) (void)hipFree(h->fm_compact);
-    if (h->fm_walk_i) (void)hipFree(h->fm_walk_i);
-    if (h->lp_v) (void)hipFree(h->lp_v);
-    if (h->pn_pool) (void)hipFree(h->pn_pool);
-    if (h->pn_cnt) (void)hipFree(h->pn_cnt);
-    if (h->fa_nflag) (void)hipFree(h->fa_nflag);
-    if (h->gn_list) (void)hipFree(h->gn_list);
-    if (h->gn_nu) (void)hipFree(h->gn_nu);
-    if (h->gn_cnt) (void)hipFree(h->gn_cnt);
-    if (h->gn_cnt_host) (void)hipHostFree(h->gn_cnt_host);
-    if (h->pn_sched) (void)hipFree(h->pn_sched);
-    if (h->pn_gate) (void)hipFree(h->pn_gate);
-    if (h->pn_epsp) (void)hipFree(h->pn_epsp);
-    if (h->pn_nuws) (void)hipFree(h->pn_nuws);
-    if (h->pn_rnp) (void)hipFree(h->pn_rnp);
-    if (h->pn_list) (void)hipFree(h->pn_list);
-    if (h->pn_cnt_host) (void)hipHostFree(h->pn_cnt_host);
-    for (int t = 0; t < 2; ++t) {
-        if (h->tl[t].pool) (void)hipFree(h->tl[t].pool);
-        if (h->tl[t].ipool) (void)hipFree(h->tl[t].ipool);
-        if (h->tl[t].bm) (void)hipFree(h->tl[t].bm);
-    }
-    if (h->tl_ws) (void)hipFree(h->tl_ws);
-    if (h->ev) (void)hipEventDestroy(h->ev);
-    if (h->ramp_du) (void)hipFree(h->ramp_du);
-    if (h->ramp_ws) (void)hipFree(h->ramp_ws);
-    if (h->rc_pool) (void)hipFree(h->rc_pool);
-    if (h->rc_ws) (void)hipFree(h->rc_ws);
-    if (h->rc_nu) (void)hipFree(h->rc_nu);
-    if (h->rc_si) (void)hipFree(h->rc_si);
-    if (h->ws) (void)hipFree(h->ws);
-    if (h->zs) (void)hipFree(h->zs);
-    if (h->stage) (void)hipFree(h->stage);
-    if (h->pin) (void)hipHostFree(h->pin);
     delete h;
     return FMPC_OK;
 }
@@ -761,7 +677,7 @@ static int fmpc_upload_panel(fmpc_handle h, double k, hipStream_t stream) {
 // Images of the tiled kernel for one arithmetic type (0: fp64, 1: fp32): the unique constant Y blocks and B' as
 // zero-padded 16 x 16 tiles, block ids with the zero block substituted for "none".  Built on first use.
 template <typename R>
-static int fmpc_tiled_build(fmpc_handle h, int t) {
+static int fmpc_tiled_build(fmpc_handle h, int t, hipStream_t stream) {
     fmpc_handle_s::Tiled& X = h->tl[t];
     const int n = h->n, m = h->m, nb = h->nb, nn = n * n;
     int NB = 0, NW = 0;
@@ -803,17 +719,15 @@ static int fmpc_tiled_build(fmpc_handle h, int t) {
     if (h->denseR)
         for (int a = 0; a < m; ++a)
             for (int b = 0; b < m; ++b) pad[oR2 + (size_t)a * MP + b] = h->hm_r2full[(size_t)a * m + b];
-    if (hipMalloc(&X.pool, img.size() * sizeof(R)) != hipSuccess ||
-        hipMalloc((void**)&X.ipool, ids.size() * sizeof(int)) != hipSuccess ||
-        hipMalloc((void**)&X.bm, pad.size() * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-    if (hipMemcpy(X.pool, img.data(), img.size() * sizeof(R), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(X.ipool, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(X.bm, pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return FMPC_E_HIP;
+    int rc = X.pool.assign((const char*)img.data(), img.size() * sizeof(R), stream);
+    if (rc == FMPC_OK) rc = X.ipool.assign(ids.data(), ids.size(), stream);
+    if (rc == FMPC_OK) rc = X.bm.assign(pad.data(), pad.size(), stream);
+    if (rc != FMPC_OK) return rc;
     X.NB = NB; X.NW = NW;
     X.lds = fmpc_tiled_lds_bytes(NB, mb, NW, t, nb, h->denseR ? ft_pr_doubles(n, m) : 0);
     if (fmpc_tiled_prepare(n, NB, NW, t, X.lds, h->denseR) != hipSuccess) return FMPC_E_HIP;
     X.V.NB = NB; X.V.mb = mb; X.V.cn = n / 16; X.V.nl = n % 16; X.V.nblk = nblk;
-    X.V.yimg = X.pool; X.V.btimg = (const R*)X.pool + obt;
+    X.V.yimg = X.pool; X.V.btimg = (const R*)X.pool.p + obt;
     X.V.iD = X.ipool; X.V.i1 = X.ipool + nb; X.V.i2 = X.ipool + 2 * nb;
     X.V.BtP = X.bm + oBt; X.V.BmP = X.bm + oBm; X.V.A1P = X.bm + oA1; X.V.A2P = X.bm + oA2; X.V.A1tP = X.bm + oA1t; X.V.A2tP = X.bm + oA2t;
     X.V.denseR = h->denseR; X.V.R2P = h->denseR ? X.bm + oR2 : nullptr;
@@ -836,7 +750,7 @@ struct FmpcTiledPlan { int NWu; size_t ldsu; int grid; size_t slot; };
 static int fmpc_tiled_plan(fmpc_handle h, int t, int batch, hipStream_t stream, int nw_override, int grid_hint, FmpcTiledPlan* out) {
     fmpc_handle_s::Tiled& X = h->tl[t];
     if (!X.ready) {
-        const int rc = t ? fmpc_tiled_build<float>(h, 1) : fmpc_tiled_build<double>(h, 0);
+        const int rc = t ? fmpc_tiled_build<float>(h, 1, stream) : fmpc_tiled_build<double>(h, 0, stream);
         if (rc != FMPC_OK) return rc;
     }
     int NWu = X.NW; size_t ldsu = X.lds;
@@ -860,46 +774,42 @@ static int fmpc_tiled_plan(fmpc_handle h, int t, int batch, hipStream_t stream, 
     // continuation list of 200 would otherwise allocate 0.5-1.4 GB per handle); grown geometrically up to the full grid,
     // so that a growing sequence of batch sizes reallocates (and synchronises) a logarithmic number of times
     const size_t need = L.total * (size_t)grid, full = L.total * (size_t)cap;
-    if (need > h->tl_ws_doubles) {
+    if (need > h->tl_ws.cap) {
         if (capturing) {
-            const size_t have = h->tl_ws_doubles / L.total;
+            const size_t have = h->tl_ws.cap / L.total;
             if (have < 1) return FMPC_E_ALLOC;
             grid = (int)have;
         } else {
-            size_t want = 2 * h->tl_ws_doubles;
+            size_t want = 2 * h->tl_ws.cap;
             if (want < need) want = need;
             if (want > full) want = full;
-            if (h->tl_ws) { (void)hipDeviceSynchronize(); (void)hipFree(h->tl_ws); h->tl_ws = nullptr; h->tl_ws_doubles = 0; }
-            if (hipMalloc((void**)&h->tl_ws, want * sizeof(double)) != hipSuccess) {
-                if (want == need || hipMalloc((void**)&h->tl_ws, need * sizeof(double)) != hipSuccess) { h->tl_ws = nullptr; return FMPC_E_ALLOC; }
-                want = need;
-            }
-            h->tl_ws_doubles = want;
+            int rc = h->tl_ws.alloc(want, stream);
+            if (rc != FMPC_OK && want != need) rc = h->tl_ws.alloc(need, stream);
+            if (rc != FMPC_OK) return rc;
         }
     }
     out->NWu = NWu; out->ldsu = ldsu; out->grid = grid; out->slot = L.total;
     return FMPC_OK;
 }
 
-static int fmpc_solve_tiled(fmpc_handle h, int t, int batch, const double* x0, const double* x0_pre, const double* w,
-                            const double* z_init, const double* nu0, int n_newton, double k, double* z_out,
-                            double* nu_out, int* status, int* iters, double* step, double* u0_out, hipStream_t stream,
-                            int nw_override = 0, const int* list = nullptr, const int* nlist = nullptr, const double* nuws = nullptr,
-                            int grid_hint = 0, const FmpcTiledPlan* planned = nullptr) {
+// list / nlist / nuws: a continuation over the problems of a list (the panel path's and the first-step split's)
+static int fmpc_solve_tiled(fmpc_handle h, int t, const FmpcSolve& s, int nw_override = 0, const int* list = nullptr,
+                            const int* nlist = nullptr, const double* nuws = nullptr, int grid_hint = 0,
+                            const FmpcTiledPlan* planned = nullptr) {
     FmpcTiledPlan plan;
     if (planned) plan = *planned;
-    else { const int rc = fmpc_tiled_plan(h, t, batch, stream, nw_override, grid_hint, &plan); if (rc != FMPC_OK) return rc; }
+    else { const int rc = fmpc_tiled_plan(h, t, s.batch, s.stream, nw_override, grid_hint, &plan); if (rc != FMPC_OK) return rc; }
     fmpc_handle_s::Tiled& X = h->tl[t];
     FtParams P;
-    P.M = h->dev; P.V = X.V; P.batch = batch;
-    P.x0 = x0; P.x0p = x0_pre; P.w = w; P.zinit = z_init; P.nu0 = nu0;
-    P.max_iter = n_newton > 0 ? n_newton : 1000; P.kbar = k;
-    P.zout = z_out; P.nuout = nu_out; P.status = status; P.iters = iters; P.step = step; P.step_ld = fmpc_step_ld(n_newton);
-    P.ws = h->tl_ws; P.ws_stride = plan.slot; P.u0out = u0_out;
+    P.M = h->dev; P.V = X.V; P.batch = s.batch;
+    P.x0 = s.x0; P.x0p = s.x0_pre; P.w = s.w; P.zinit = s.z_init; P.nu0 = s.nu0;
+    P.max_iter = fmpc_max_iter(s); P.kbar = s.k;
+    P.zout = s.z_out; P.nuout = s.nu_out; P.status = s.status; P.iters = s.iters; P.step = s.step; P.step_ld = fmpc_step_ld(s.n_newton);
+    P.ws = h->tl_ws; P.ws_stride = plan.slot; P.u0out = s.u0_out;
     P.list = list; P.nlist = nlist; P.nuws = nuws;
     h->tl_last_nw = plan.NWu;
     if (!list) h->last_path = t ? FMPC_PATH_TILED_F32 : FMPC_PATH_TILED;
-    return fmpc_launch_tiled(P, X.NB, plan.NWu, t, plan.grid, plan.ldsu, stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
+    return fmpc_launch_tiled(P, X.NB, plan.NWu, t, plan.grid, plan.ldsu, s.stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
 extern "C" int fmpc_set_precision(fmpc_handle h, int mode) {
@@ -925,16 +835,10 @@ static int fmpc_grid_for(fmpc_handle h, int batch) {
 }
 
 // grows the per-workgroup workspace; caller holds h->mu
-static int fmpc_ensure_ws(fmpc_handle h, int grid, size_t* stride) {
+static int fmpc_ensure_ws(fmpc_handle h, int grid, size_t* stride, hipStream_t stream) {
     const FmpcWsLayout L = fmpc_ws_layout(h->n, h->m, h->T, h->nb, h->generic_big != 0, h->denseR != 0);
     *stride = L.total;
-    const size_t need = L.total * (size_t)grid;
-    if (need > h->ws_doubles) {
-        if (h->ws) { (void)hipDeviceSynchronize(); (void)hipFree(h->ws); h->ws = nullptr; h->ws_doubles = 0; }
-        if (hipMalloc((void**)&h->ws, need * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-        h->ws_doubles = need;
-    }
-    return FMPC_OK;
+    return h->ws.grow(L.total * (size_t)grid, stream);
 }
 
 // Orders the solves of a handle that arrive on different streams (they share the handle's workspaces): called with
@@ -989,11 +893,11 @@ static int fmpc_build_inverse(fmpc_handle h, double k, hipStream_t stream) {
             hw[(size_t)(1 + ncol + j) * TN + e] = -scale * h->hm_m1[(size_t)e * n + j];
             hw[(size_t)(1 + ncol + n + j) * TN + e] = -scale * h->hm_m2[(size_t)e * n + j];
         }
-    double* d = nullptr;
+    DevBuf<double> d;                                                 // (released on return)
     const size_t o_x0 = 0, o_x0p = o_x0 + hx0.size(), o_w = o_x0p + hx0p.size(), o_gate = o_w + hw.size(),
                  o_nu = o_gate + 2 * (size_t)np, total = o_nu + (size_t)npanels * nrow * FP_NP;
-    if (hipMalloc((void**)&d, total * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-    int rc = FMPC_OK;
+    int rc = d.alloc(total, stream);
+    if (rc != FMPC_OK) return rc;
     std::vector<double> nu((size_t)npanels * nrow * FP_NP);
     if (hipMemcpyAsync(d + o_x0, hx0.data(), hx0.size() * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess ||
         hipMemcpyAsync(d + o_x0p, hx0p.data(), hx0p.size() * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess ||
@@ -1009,7 +913,7 @@ static int fmpc_build_inverse(fmpc_handle h, double k, hipStream_t stream) {
             hipMemcpyAsync(nu.data(), d + o_nu, nu.size() * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
             hipStreamSynchronize(stream) != hipSuccess) rc = FMPC_E_HIP;
     }
-    (void)hipFree(d);
+    d.release();
     if (rc != FMPC_OK) return rc;
     auto at = [&](int p, int row) { return nu[((size_t)(p / FP_NP) * nrow + row) * FP_NP + (p % FP_NP)]; };
     const int nrt = (nrow + 15) / 16, jks = h->inv_jks, jksp = 16 * ((jks + 15) / 16 + 3);
@@ -1100,7 +1004,7 @@ static int fmpc_build_inverse(fmpc_handle h, double k, hipStream_t stream) {
 }
 
 // Matrices of the first-move form for barrier weight k (fmpc_host_build_first_move), uploaded as one pool.
-static int fmpc_build_first_move(fmpc_handle h, double k) {
+static int fmpc_build_first_move(fmpc_handle h, double k, hipStream_t stream) {
     h->fm_valid = 0;
     if (!h->hm_J4_valid || h->hm_J4_k != k) return FMPC_E_UNSUPPORTED;
     const int n = h->n, m = h->m, T = h->T, TN = T * n;
@@ -1164,9 +1068,8 @@ static int fmpc_build_first_move(fmpc_handle h, double k) {
         fmpc_host_build_loop_images(O, n, m, FL_KS, true, In.bt, LI);
         oSU = push(LI.imgU); oSE = push(LI.imgE); oSEp = push(LI.imgEp); oSB = push(LI.imgB);
     }
-    if (h->fm_pool) { (void)hipDeviceSynchronize(); (void)hipFree(h->fm_pool); h->fm_pool = nullptr; }
-    if (hipMalloc((void**)&h->fm_pool, pool.size() * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-    if (hipMemcpy(h->fm_pool, pool.data(), pool.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return FMPC_E_HIP;
+    const int rc = h->fm_pool.assign(pool.data(), pool.size(), stream);
+    if (rc != FMPC_OK) return rc;
     FmParams& P = h->fm_P;
     memset(&P, 0, sizeof(P));
     P.n = n; P.m = m; P.T = T; P.nb = h->nb; P.var2 = In.var2; P.has_xf = h->has_xf;
@@ -1203,17 +1106,43 @@ static int fmpc_build_first_move(fmpc_handle h, double k) {
 }
 
 // The wave kernel's workspace: one slot per resident wavefront of the whole chip.  Caller holds h->mu.
-static int fmpc_ensure_wave_ws(fmpc_handle h, size_t* stride_out) {
+static int fmpc_ensure_wave_ws(fmpc_handle h, size_t* stride_out, hipStream_t stream) {
     const int wpw = fmpc_wave_waves_per_wg();
     const size_t stride = fmpc_wave_ws_doubles(h->n, h->m, h->wave.mp, h->T, h->nb);
-    const size_t need = stride * (size_t)h->num_cu * wpw;
-    if (need > h->ws_doubles) {
-        if (h->ws) { (void)hipDeviceSynchronize(); (void)hipFree(h->ws); h->ws = nullptr; h->ws_doubles = 0; }
-        if (hipMalloc((void**)&h->ws, need * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-        h->ws_doubles = need;
-    }
+    const int rc = h->ws.grow(stride * (size_t)h->num_cu * wpw, stream);
+    if (rc != FMPC_OK) return rc;
     *stride_out = stride;
     return FMPC_OK;
+}
+
+// The FwParams every launch of the wave kernel shares: model, images, shared factor, cold-start constants, workspace and the
+// solve's arguments.  Each call site sets only what differs (mode, panel-path inputs, list, ...).
+static FwParams fmpc_wave_params(fmpc_handle h, const FmpcSolve& s, size_t stride, int zld = 0) {
+    FwParams P;
+    memset(&P, 0, sizeof(P));
+    P.M = h->dev; P.V = h->wave;
+    P.batch = s.batch; P.max_iter = fmpc_max_iter(s); P.step_ld = fmpc_step_ld(s.n_newton); P.kbar = s.k;
+    P.x0 = s.x0; P.x0p = s.x0_pre; P.w = s.w; P.zinit = s.z_init; P.nu0 = s.nu0;
+    P.zout = s.z_out; P.nuout = s.nu_out; P.status = s.status; P.iters = s.iters; P.step = s.step; P.u0out = s.u0_out;
+    P.zld = zld > 0 ? zld : h->T * (h->n + h->m);
+    P.ws = h->ws; P.ws_stride = stride;
+    P.sh_fac = h->sh_fac; P.sh_rs = h->sh_rs; P.sh_ok = h->sh_ok; P.cold = h->cold_d;
+    return P;
+}
+
+// one wavefront per problem, 8 per workgroup, one workgroup per CU
+static int fmpc_wave_grid(fmpc_handle h, int batch) {
+    const int wpw = fmpc_wave_waves_per_wg();
+    const int grid = (batch + wpw - 1) / wpw;
+    return grid < h->num_cu ? grid : h->num_cu;
+}
+
+// The exact path in flag mode behind a kernel that has decided the step of every problem (the affine, first-move and loop
+// forms): from the cold start with the shared factor, it redoes the problems flagged in `need` and counts them in pn_cnt
+static int fmpc_launch_flagged(fmpc_handle h, const FmpcSolve& s, int grid, size_t stride, int* need, int* nflag = nullptr, int zld = 0) {
+    FwParams P = fmpc_wave_params(h, s, stride, zld);
+    P.mode = FW_MODE_SHARED; P.handed = h->pn_cnt; P.pphase = 3; P.list = need; P.nflag = nflag;
+    return fmpc_launch_wave(P, grid, h->wave_lds, s.stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
 // Cold-start constants of barrier weight k: the shared factor (an export launch of the wave kernel on one problem), the
@@ -1224,317 +1153,306 @@ static int fmpc_ensure_cold(fmpc_handle h, double k, size_t stride, hipStream_t 
     // the previous k, which the blocking uploads below overwrite
     if (h->sh_valid && hipStreamSynchronize(stream) != hipSuccess) return FMPC_E_HIP;
     double* scr = h->sh_scratch;                 // a zero state: x0 = x0_pre = 0, w = nu0 = 0
-    const hipError_t e = fmpc_launch_wave(h->dev, h->wave, 1, 1, scr, scr, nullptr, nullptr, nullptr, 1, k,
-                                          scr + ((h->n + 15) & ~15), nullptr, nullptr, nullptr, nullptr, 1, h->ws, stride,
-                                          h->wave_lds, stream, 2, h->sh_fac, h->sh_rs, h->sh_ok, h->cold_d);
-    if (e != hipSuccess) return FMPC_E_HIP;
+    const FmpcSolve one = {1, scr, scr, nullptr, nullptr, nullptr, 1, k, scr + ((h->n + 15) & ~15), nullptr, nullptr, nullptr, nullptr,
+                           nullptr, stream, 0};
+    FwParams P = fmpc_wave_params(h, one, stride);
+    P.mode = FW_MODE_EXPORT;
+    if (fmpc_launch_wave(P, 1, h->wave_lds, stream) != hipSuccess) return FMPC_E_HIP;
     if (fmpc_upload_cold(h, k, stream) != FMPC_OK) return FMPC_E_HIP;
     if (h->pn_enabled && fmpc_upload_panel(h, k, stream) != FMPC_OK) return FMPC_E_HIP;
     h->sh_valid = 1; h->sh_k = k;
     return FMPC_OK;
 }
 
-// set by the host-pointer entry around its device solve: its staging block has contiguous rows whatever fmpc_set_z_ld says
-static thread_local int fmpc_tl_contiguous_z = 0;
-// set by fmpc_solve_u0_device_ld around its solve: the row distance of THIS call's z_out (>= 0), whatever the handle's persistent
-// value says (-1: none given, the handle's fmpc_set_z_ld value applies).  Thread-local, so a concurrent solve on the same handle
-// from another thread never inherits it (the set / solve / restore of fmpc_set_z_ld was not atomic).
-static thread_local int fmpc_tl_zld_explicit = -1;
-static inline int fmpc_effective_zld(fmpc_handle h) { return fmpc_tl_zld_explicit >= 0 ? fmpc_tl_zld_explicit : h->z_ld; }
+// z_out == NULL (first moves only): the kernels that iterate on z work in the handle's scratch iterate
+static int fmpc_scratch_z(fmpc_handle h, int batch, hipStream_t stream) {
+    return h->zs.grow((size_t)batch * h->T * (h->n + h->m), stream);
+}
 
-// fmpc_solve_device (u0_out == NULL) / fmpc_solve_u0_device: the first moves are written by the solve's last kernel
-// where that kernel visits every problem anyway (the wave kernel), by the unpack kernel otherwise
-static int fmpc_solve_device_inner(fmpc_handle h, int batch,
-                                  const double* x0, const double* x0_pre, const double* w,
-                                  const double* z_init, const double* nu0,
-                                  int n_newton, double k,
-                                  double* z_out, double* nu_out, int* status, int* iters, double* step,
-                                  double* u0_out, void* stream) {
-    if (!h || !x0 || (!z_out && !u0_out)) return FMPC_E_NULL;
-    if (batch < 0) return FMPC_E_DIM;
-    if (batch == 0) return FMPC_OK;
-    const int max_iter = n_newton > 0 ? n_newton : 1000;
-    hipError_t e;
-    // Output options (README.md:558-570,589: the loop uses U(1:nu) only): z_out == NULL with u0_out given returns the first
-    // moves alone.  The kernels that iterate on z then work in a scratch array of the handle; the cold-start panel path
-    // with a budget of 1 does not write z at all (fmpc_cold_dz<.., .., true>).
-    const bool z_null = z_out == nullptr;
-    if (z_null) {
-        const size_t need = (size_t)batch * h->T * (h->n + h->m);
-        if (need > h->zs_doubles) {
-            if (h->zs) { (void)hipDeviceSynchronize(); (void)hipFree(h->zs); h->zs = nullptr; h->zs_doubles = 0; }
-            if (hipMalloc((void**)&h->zs, need * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-            h->zs_doubles = need;
-        }
-        z_out = h->zs;
-    }
-    // Padded z rows (fmpc_set_z_ld): the affine form of the cold-start step and its exact path honour them, nothing else does
-    const int zld = (!z_null && !fmpc_tl_contiguous_z && fmpc_effective_zld(h) > h->T * (h->n + h->m)) ? fmpc_effective_zld(h) : 0;
-    if (zld && (w != nullptr || z_init != nullptr || max_iter != 1 || h->prec == FMPC_PREC_F32_MIXED || h->force_tiled || h->denseQ ||
-                h->denseR || !h->use_wave || !h->sh_enabled || !h->pn_enabled)) return FMPC_E_UNSUPPORTED;
-    if (h->prec == FMPC_PREC_F32_MIXED || h->force_tiled || ((h->denseQ || h->denseR) && !h->generic_big) ||
-        (!h->use_wave && (!h->generic_ok || h->prefer_tiled)))
-    {
-        // fp64, one or two blocks of 16 (n <= 31), few problems per CU: four wavefronts per problem instead of two -- 7 to 24 % less
-        // time up to 256 problems, 20 to 60 % MORE at 2048 (round 5 sweep, n = 8 .. 31).  (n = 27 has its own dispatch below; a size
-        // that reaches this point with the wave kernel switched off keeps the handle's setting.)
-        const int t_ = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
-        const int few = (!t_ && !h->denseR && h->n <= 31 && h->n != FP_N && batch <= 512 && !h->force_tiled) ? 4 : 0;
-        return fmpc_solve_tiled(h, t_, batch, x0, x0_pre, w, z_init, nu0, n_newton, k,
-                                z_out, nu_out, status, iters, step, u0_out, (hipStream_t)stream, few);
-    }
-    if (h->use_wave) {
-        // one wavefront per problem, 8 per workgroup, one workgroup per CU
-        const int wpw = fmpc_wave_waves_per_wg();
-        int grid = (batch + wpw - 1) / wpw;
-        if (grid > h->num_cu) grid = h->num_cu;
-        size_t stride = 0;
-        { const int rcw = fmpc_ensure_wave_ws(h, &stride); if (rcw != FMPC_OK) return rcw; }
-        int mode = 0;
-        if (h->sh_enabled && z_init == nullptr) {
-            // cold start: the first Newton step of every problem shares one factor (depends on k only)
-            const int rce = fmpc_ensure_cold(h, k, stride, (hipStream_t)stream);
-            if (rce != FMPC_OK) return rce;
-            mode = 1;
-        }
-        if (mode == 1 && h->pn_enabled && h->pn_valid) {
-            // first Newton step from the cold start (the reference's own call has just this one): 16-problem panels
-            // on the matrix cores; the exact-path launch below decides every problem's step length, redoes the
-            // problems whose decision is not clear-cut and runs the remaining iterations of the budget
-            const int npanels = (batch + FP_NP - 1) / FP_NP;
-            if ((size_t)batch > h->pn_cap) {
-                (void)hipDeviceSynchronize();
-                if (h->pn_gate) (void)hipFree(h->pn_gate);
-                if (h->pn_epsp) (void)hipFree(h->pn_epsp);
-                if (h->pn_nuws) (void)hipFree(h->pn_nuws);
-                if (h->pn_rnp) (void)hipFree(h->pn_rnp);
-                if (h->pn_list) (void)hipFree(h->pn_list);
-                h->pn_gate = nullptr; h->pn_epsp = nullptr; h->pn_nuws = nullptr; h->pn_rnp = nullptr; h->pn_list = nullptr; h->pn_cap = 0;
-                if (hipMalloc((void**)&h->pn_gate, (size_t)batch * 2 * sizeof(double)) != hipSuccess ||
-                    hipMalloc((void**)&h->pn_epsp, (size_t)npanels * h->T * FP_NP * sizeof(double)) != hipSuccess ||
-                    hipMalloc((void**)&h->pn_rnp, (size_t)npanels * h->T * FP_NP * sizeof(double)) != hipSuccess ||
-                    hipMalloc((void**)&h->pn_list, (size_t)batch * sizeof(int)) != hipSuccess ||
-                    hipMalloc((void**)&h->pn_nuws, (size_t)npanels * FP_NP * h->nb * h->n * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-                h->pn_cap = batch;
-            }
-            FpParams Q;
-            fmpc_panel_params(h, k, Q);
-            Q.batch = batch; Q.npanels = npanels; Q.step_ld = fmpc_step_ld(n_newton);
-            Q.x0 = x0; Q.x0p = x0_pre; Q.w = w; Q.nu0 = nu0;
-            Q.zout = z_out; Q.status = status; Q.iters = iters; Q.step = step;
-            Q.nuws = h->pn_nuws; Q.nuout = nu_out;
-            Q.gate = h->pn_gate; Q.epsp = h->pn_epsp; Q.handed = h->pn_cnt;
-            Q.rnp = h->pn_rnp;
-            // The dual solve in its dense form (no dependency chain, fmpc_kernel_inv.hip): always without w (56 columns),
-            // with w while the product is cheaper than the two sweeps of a panel (few panels leave the chip empty)
-            // (a closed-loop step hands over [B u1 ; B u2], the 2 n numbers its w depends on: 28 k-steps at any batch)
-            const bool lowrank = h->lp_hint && w != nullptr && h->lp_v != nullptr;
-            const bool dense_form = h->inv_enabled && (w == nullptr || lowrank || batch <= h->inv_max_batch);
-            if (dense_form && (!h->inv_valid || h->inv_k != k) && !(h->inv_failed && h->inv_failed_k == k)) {
-                if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return FMPC_E_HIP;   // earlier solves may still read J
-                const int rcb = fmpc_build_inverse(h, k, (hipStream_t)stream);
-                if (rcb != FMPC_OK) return rcb;
-                // J or nuc not finite: the sweep form is taken, and the build (a stream synchronisation, allocations and a
-                // 5 ms launch) is not retried on every later solve with this k
-                h->inv_failed = h->inv_valid ? 0 : 1; h->inv_failed_k = k;
-            }
-            // Without w, with a budget of 1 and no nu requested the whole step is ONE product on the matrix cores (affine form,
-            // fmpc_kernel_affine.hip) + the exact path in flag mode for the problems whose decision is not clear-cut
-            if (dense_form && h->inv_valid && w == nullptr && max_iter == 1 && (nu_out == nullptr || !z_null) && !h->fa_disabled && h->n == FP_N) {
-                if (!h->fm_valid || h->fm_k != k) {
-                    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return FMPC_E_HIP;
-                    const int rcf = fmpc_build_first_move(h, k);
-                    if (rcf != FMPC_OK && rcf != FMPC_E_UNSUPPORTED) return rcf;
-                }
-                if (h->fm_valid && h->fm_k == k && h->fa_valid) {
-                    if ((size_t)batch > h->fa_need_cap) {
-                        (void)hipDeviceSynchronize();
-                        if (h->fa_need) (void)hipFree(h->fa_need);
-                        h->fa_need = nullptr; h->fa_need_cap = 0;
-                        size_t cap = 256;
-                        while (cap < (size_t)batch) cap *= 2;
-                        if (hipMalloc((void**)&h->fa_need, cap * sizeof(int)) != hipSuccess) return FMPC_E_ALLOC;
-                        h->fa_need_cap = cap;
-                    }
-                    FaParams A = h->fa_P;
-                    A.batch = batch; A.step_ld = fmpc_step_ld(n_newton);
-                    A.x0 = x0; A.x0p = x0_pre; A.nu0 = nu0; A.zout = z_null ? nullptr : z_out; A.nuout = nu_out; A.u0out = u0_out;
-                    A.status = status; A.iters = iters; A.step = step; A.need = h->fa_need; A.handed = h->pn_cnt;
-                    int* const nf = h->fa_nflag;                          // [running count of flagged problems | count dealt with | ticket]: device
-                                                                          // state only, the same in an eager call and in a recorded graph
-                    static const bool no_nflag = [] { const char* e = getenv("FMPC_NO_NFLAG"); return e && e[0] == '1'; }();   // A/B switch
-                    A.nflag = no_nflag ? nullptr : nf;
-                    A.ldz = zld;                                          // (0: contiguous rows)
-                    if (fmpc_launch_affine(A, h->num_cu, (hipStream_t)stream) != hipSuccess) return FMPC_E_HIP;
-                    int g3 = grid < 64 ? grid : 64;                    // flag mode: the waves walk over the flags, few are set
-                    e = fmpc_launch_wave(h->dev, h->wave, batch, g3, x0, x0_pre, nullptr, nullptr, nu0, 1, k, z_out, nu_out, status, iters, step,
-                                         fmpc_step_ld(n_newton), h->ws, stride, h->wave_lds, (hipStream_t)stream, 1, h->sh_fac, h->sh_rs, h->sh_ok,
-                                         h->cold_d, nullptr, nullptr, h->pn_cnt, nullptr, u0_out, 3, nullptr, h->fa_need, 0, no_nflag ? nullptr : nf, zld);
-                    h->last_path = FMPC_PATH_PANEL; h->inv_last = 2;
-                    return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
-                }
-            }
-            if (zld) return FMPC_E_UNSUPPORTED;                       // (nothing of this solve is enqueued yet)
-            const int split = max_iter > 1;                           // budgets > 1: decide, compact, continue (two launches)
-            const int pgrid = npanels < h->num_cu ? npanels : h->num_cu;
-            // (a small LDS footprint lets a d_z workgroup of another stream share the CU)
-            h->inv_last = dense_form && h->inv_valid;
-            // without w, without the terminal row and with a budget of 1 nobody but d_z reads nu+: d_z computes it itself
-            const bool fuse = h->inv_last && h->inv_fuse && w == nullptr && !h->has_xf && max_iter == 1;
-            Q.gate_only = fuse ? 1 : 0;
-            const bool u0only = z_null && max_iter == 1 && nu_out == nullptr;       // nothing of z leaves the chip
-            Q.u0out = u0_out;
-            if (h->inv_last) {
-                if (lowrank) { Q.gw = h->lp_v; Q.gwn = 2 * h->n; Q.jimg = h->inv_jimg2; Q.jks = h->inv_jks2; Q.jksp = 16 * ((h->inv_jks2 + 15) / 16 + 3); }
-                else { Q.gw = w; Q.gwn = h->T * h->n; }
-            }
-            if (h->inv_last) e = fmpc_launch_inv(Q, (hipStream_t)stream);
-            else e = fmpc_launch_panel(Q, pgrid, fmpc_panel_lds_used(h->nb, h->pn_mp, h->pn_nsf + h->pn_nsb), (hipStream_t)stream);
-            if (e != hipSuccess) return FMPC_E_HIP;
-            const int ntasks = npanels * h->T;
-            // one task per wave, 8 per workgroup; workgroups b, b + 8, ... take the panels b % 8, b % 8 + 8, ...
-            const int ppx = (npanels + 7) / 8;                       // panels of the fullest XCD share
-            const int dgrid = 8 * ((ppx * h->T + FD_WAVES - 1) / FD_WAVES);
-            (void)ntasks;
-            e = fmpc_launch_dz(Q, dgrid, split, (hipStream_t)stream, fuse ? 1 : 0, u0only ? 1 : 0);
-            if (e != hipSuccess) return FMPC_E_HIP;
-            // decides the step length of every problem; solves exactly those whose decision is not clear-cut.  Budget 1:
-            // one launch.  Budgets > 1: a decide-only launch that also evaluates the next exit test and COMPACTS the
-            // problems that go on (typically a few per cent), then the continuation over that list on as few
-            // workgroups as it needs -- the rest of the chip stays free for other streams.
-            for (int ph = split ? 1 : 0; ph <= (split ? 2 : 0); ++ph) {
-                int g2 = grid;
-                if (ph == 2) {
-                    // Every workgroup of the continuation needs a CU with its whole LDS free, also those that find the
-                    // list empty -- behind other streams' long-running continuations they would wait for a slot.  Size
-                    // the grid from the list length an EARLIER call of this handle reported (never waited for); the
-                    // kernel loops over the list, so any grid is correct.
-                    const int last = ((volatile int*)h->pn_cnt_host)[1];
-                    if (last >= 0) {
-                        const int wpw2 = fmpc_wave_waves_per_wg();
-                        int want = (last + last / 2 + wpw2 - 1) / wpw2 + 4;
-                        if (want < 8) want = 8;
-                        if (want < g2) g2 = want;
-                    }
-                }
-                if (ph == 2 && h->small_tiled) {
-                    // the continuation is a handful of problems per CU at most: the tiled kernel (4 wavefronts per problem)
-                    // finishes one in 0.45 ms where the one-wavefront kernel needs 1.0 ms (round 2 measurement)
-                    const int last = ((volatile int*)h->pn_cnt_host)[1];
-                    const int hint = last >= 0 ? last + last / 2 + 16 : 0;
-                    const int rc_t = fmpc_solve_tiled(h, 0, batch, x0, x0_pre, w, nullptr, nu0, n_newton, k, z_out, nu_out, status, iters,
-                                                      step, u0_out, (hipStream_t)stream, h->small_nw, h->pn_list, h->pn_cnt + 1, h->pn_nuws, hint);
-                    if (rc_t == FMPC_OK) continue;
-                    // (no workspace for the tiled kernel: the panel, d_z and decision kernels are already enqueued -- the
-                    // one-wavefront kernel below, whose workspace exists, finishes the solve instead of aborting it half-way)
-                    if (rc_t != FMPC_E_UNSUPPORTED && rc_t != FMPC_E_ALLOC) return rc_t;
-                }
-                e = fmpc_launch_wave(h->dev, h->wave, batch, g2, x0, x0_pre, w, z_init, nu0, max_iter, k,
-                                     z_out, nu_out, status, iters, step, fmpc_step_ld(n_newton), h->ws, stride,
-                                     h->wave_lds, (hipStream_t)stream, mode, h->sh_fac, h->sh_rs, h->sh_ok, h->cold_d,
-                                     h->pn_gate, h->pn_epsp, h->pn_cnt, h->pn_nuws, u0_out, ph, h->pn_rnp, h->pn_list, u0only ? 1 : 0);
-                if (e != hipSuccess) return FMPC_E_HIP;
-            }
-            if (split && hipMemcpyAsync(h->pn_cnt_host, h->pn_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess)
-                return FMPC_E_HIP;
-            h->last_path = FMPC_PATH_PANEL;
-            return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
-        }
-        if (zld) return FMPC_E_UNSUPPORTED;
-        if (mode == 0 && h->small_tiled && batch <= 1024) {
-            // Every problem factors its own Schur complement and there are at most 4 problems per CU: the tiled kernel's
-            // 2 (4) wavefronts per problem finish a problem in 0.5 (0.4) ms where the one-wavefront kernel needs 1.0 ms;
-            // beyond 1024 problems the one-wavefront kernel's 8 problems per CU win (measured in round 2)
-            const int rc_t = fmpc_solve_tiled(h, 0, batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step,
-                                              u0_out, (hipStream_t)stream, batch <= 512 ? h->small_nw : 2);
-            if (rc_t != FMPC_E_UNSUPPORTED) return rc_t;
-        }
-        FmpcTiledPlan gplan;
-        int gn_hint = 0;
-        bool gn_go = mode == 0 && max_iter > 1 && h->small_tiled && h->gn_split;
-        if (gn_go) {
-            // the continuation's launch is planned (instance, size, workspace) BEFORE the first-step launch is enqueued: if the tiled
-            // kernel cannot run, the single launch below solves the batch and nothing is left half done
-            const int last = h->gn_cnt_host ? ((volatile int*)h->gn_cnt_host)[1] : -1;   // list length an EARLIER call reported (never waited for)
-            gn_hint = last >= 0 ? last + last / 2 + 16 : 0;
-            if (fmpc_tiled_plan(h, 0, batch, (hipStream_t)stream, h->small_nw, gn_hint, &gplan) != FMPC_OK) gn_go = false;
-        }
-        if (gn_go) {
-            // Explicit-start batch too large for the tiled kernel, budget > 1: with one problem per wavefront slot a launch lasts
-            // as long as its slowest wavefront, so the few per cent of problems that take a second step double it (round 3:
-            // 2.0 ms for 2180 problem-iterations, 1.2 ms for the 2000 first ones).  Two launches instead: the one-wavefront
-            // kernel takes the first step of every problem and the NEXT exit test (pphase 4), appending the problems that go on
-            // to a list; the tiled kernel (two wavefronts per problem: half the latency of one problem) works through that list.
-            const size_t nbn = (size_t)h->nb * h->n;
-            if ((size_t)batch > h->gn_cap) {
-                (void)hipDeviceSynchronize();
-                if (h->gn_list) (void)hipFree(h->gn_list);
-                if (h->gn_nu) (void)hipFree(h->gn_nu);
-                if (h->gn_cnt) (void)hipFree(h->gn_cnt);
-                h->gn_list = nullptr; h->gn_nu = nullptr; h->gn_cnt = nullptr; h->gn_cap = 0;
-                if (hipMalloc((void**)&h->gn_list, (size_t)batch * sizeof(int)) != hipSuccess || hipMalloc((void**)&h->gn_cnt, 2 * sizeof(int)) != hipSuccess ||
-                    hipMalloc((void**)&h->gn_nu, (size_t)batch * nbn * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-                h->gn_cap = batch;
-            }
-            if (!h->gn_cnt_host) {
-                if (hipHostMalloc((void**)&h->gn_cnt_host, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess) return FMPC_E_ALLOC;
-                h->gn_cnt_host[0] = -1; h->gn_cnt_host[1] = -1;
-            }
-            double* nu_arr = nu_out ? nu_out : h->gn_nu;               // nu after the first step, per problem: what the continuation starts from
-            // (a kernel, not hipMemsetAsync: a captured graph holding the 8-byte memset node faulted on its SECOND launch --
-            // "write access to a read-only page", ROCm 7.2, round 5; with this kernel node instead, and the 8-byte device-to-host
-            // copy node below kept, any number of launches is fine: tests/test_gpu_recorded.py)
-            hipLaunchKernelGGL(fmpc_zero_ints, dim3(1), dim3(64), 0, (hipStream_t)stream, h->gn_cnt, 2);
-            if (hipGetLastError() != hipSuccess) return FMPC_E_HIP;
-            e = fmpc_launch_wave(h->dev, h->wave, batch, grid, x0, x0_pre, w, z_init, nu0, max_iter, k,
-                                 z_out, nu_arr, status, iters, step, fmpc_step_ld(n_newton), h->ws, stride,
-                                 h->wave_lds, (hipStream_t)stream, mode, h->sh_fac, h->sh_rs, h->sh_ok, h->cold_d,
-                                 nullptr, nullptr, h->gn_cnt, nullptr, u0_out, 4, nullptr, h->gn_list);
-            if (e != hipSuccess) return FMPC_E_HIP;
-            h->last_path = FMPC_PATH_WAVE;
-            const int rc_t = fmpc_solve_tiled(h, 0, batch, x0, x0_pre, w, nullptr, nu0, n_newton, k, z_out, nu_arr, status, iters, step,
-                                              u0_out, (hipStream_t)stream, h->small_nw, h->gn_list, h->gn_cnt + 1, nullptr, gn_hint, &gplan);
-            if (rc_t != FMPC_OK) return rc_t;
-            if (hipMemcpyAsync(h->gn_cnt_host, h->gn_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess) return FMPC_E_HIP;
-            return FMPC_OK;
-        }
-        e = fmpc_launch_wave(h->dev, h->wave, batch, grid, x0, x0_pre, w, z_init, nu0, max_iter, k,
-                             z_out, nu_out, status, iters, step, fmpc_step_ld(n_newton), h->ws, stride,
-                             h->wave_lds, (hipStream_t)stream, mode, h->sh_fac, h->sh_rs, h->sh_ok, h->cold_d,
-                             nullptr, nullptr, nullptr, nullptr, u0_out);
-        h->last_path = mode == 1 ? FMPC_PATH_SHARED : FMPC_PATH_WAVE;
-    } else {
-        h->last_path = FMPC_PATH_GENERIC;
-        const int grid = fmpc_grid_for(h, batch);
-        size_t stride = 0;
-        // full size once: no regrowth (big: a slot holds the whole factor -- as many slots as the launch has workgroups, grown on demand)
-        int rc = fmpc_ensure_ws(h, h->generic_big ? grid : h->num_cu * h->wg_per_cu, &stride);
-        if (rc != FMPC_OK) return rc;
-        e = fmpc_launch_generic(h->dev, batch, grid, x0, x0_pre, w, z_init, nu0, max_iter, k,
-                                z_out, nu_out, status, iters, step, fmpc_step_ld(n_newton),
-                                h->ws, stride, (hipStream_t)stream, h->generic_big);
-        if (e == hipSuccess && u0_out)
-            e = fmpc_launch_unpack(h->n, h->m, h->T, batch, z_out, nullptr, nullptr, u0_out, (hipStream_t)stream);
-    }
+// ---- the paths of a device solve (fmpc_solve_device_inner picks one; caller holds h->mu)
+
+// The tiled kernel: the fp32 factor, FMPC_TILED=1, dense weights, and sizes without the wave kernel where it is preferred
+static int fmpc_path_tiled(fmpc_handle h, const FmpcSolve& s) {
+    // fp64, one or two blocks of 16 (n <= 31), few problems per CU: four wavefronts per problem instead of two -- 7 to 24 % less
+    // time up to 256 problems, 20 to 60 % MORE at 2048 (round 5 sweep, n = 8 .. 31).  (n = 27 has its own dispatch below; a size
+    // that reaches this point with the wave kernel switched off keeps the handle's setting.)
+    const int t_ = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
+    const int few = (!t_ && !h->denseR && h->n <= 31 && h->n != FP_N && s.batch <= 512 && !h->force_tiled) ? 4 : 0;
+    return fmpc_solve_tiled(h, t_, s, few);
+}
+
+// The generic kernel: sizes without the wave kernel that the tiled kernel does not take
+static int fmpc_path_generic(fmpc_handle h, const FmpcSolve& s) {
+    h->last_path = FMPC_PATH_GENERIC;
+    const int grid = fmpc_grid_for(h, s.batch);
+    size_t stride = 0;
+    // full size once: no regrowth (big: a slot holds the whole factor -- as many slots as the launch has workgroups, grown on demand)
+    const int rc = fmpc_ensure_ws(h, h->generic_big ? grid : h->num_cu * h->wg_per_cu, &stride, s.stream);
+    if (rc != FMPC_OK) return rc;
+    hipError_t e = fmpc_launch_generic(h->dev, s.batch, grid, s.x0, s.x0_pre, s.w, s.z_init, s.nu0, fmpc_max_iter(s), s.k,
+                                       s.z_out, s.nu_out, s.status, s.iters, s.step, fmpc_step_ld(s.n_newton),
+                                       h->ws, stride, s.stream, h->generic_big);
+    if (e == hipSuccess && s.u0_out)
+        e = fmpc_launch_unpack(h->n, h->m, h->T, s.batch, s.z_out, nullptr, nullptr, s.u0_out, s.stream);
     return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
-static int fmpc_solve_device_impl(fmpc_handle h, int batch,
-                                  const double* x0, const double* x0_pre, const double* w,
-                                  const double* z_init, const double* nu0,
-                                  int n_newton, double k,
-                                  double* z_out, double* nu_out, int* status, int* iters, double* step,
-                                  double* u0_out, void* stream) {
-    if (!h || !x0 || (!z_out && !u0_out)) return FMPC_E_NULL;
-    if (batch < 0) return FMPC_E_DIM;
-    if (batch == 0) return FMPC_OK;
+// Without w, with a budget of 1 and no nu requested the whole cold-start step is ONE product on the matrix cores (affine form,
+// fmpc_kernel_affine.hip) + the exact path in flag mode for the problems whose decision is not clear-cut.
+// FMPC_E_UNSUPPORTED: the form does not exist for this k, nothing is enqueued.
+static int fmpc_path_affine(fmpc_handle h, const FmpcSolve& s, size_t stride, int zld, bool z_null) {
+    if (!h->fm_valid || h->fm_k != s.k) {
+        if (hipStreamSynchronize(s.stream) != hipSuccess) return FMPC_E_HIP;
+        const int rcf = fmpc_build_first_move(h, s.k, s.stream);
+        if (rcf != FMPC_OK && rcf != FMPC_E_UNSUPPORTED) return rcf;
+    }
+    if (!(h->fm_valid && h->fm_k == s.k && h->fa_valid)) return FMPC_E_UNSUPPORTED;
+    if ((size_t)s.batch > h->fa_need.cap) {
+        size_t cap = 256;
+        while (cap < (size_t)s.batch) cap *= 2;
+        const int rc = h->fa_need.alloc(cap, s.stream);
+        if (rc != FMPC_OK) return rc;
+    }
+    FaParams A = h->fa_P;
+    A.batch = s.batch; A.step_ld = fmpc_step_ld(s.n_newton);
+    A.x0 = s.x0; A.x0p = s.x0_pre; A.nu0 = s.nu0; A.zout = z_null ? nullptr : s.z_out; A.nuout = s.nu_out; A.u0out = s.u0_out;
+    A.status = s.status; A.iters = s.iters; A.step = s.step; A.need = h->fa_need; A.handed = h->pn_cnt;
+    int* const nf = h->fa_nflag;                          // [running count of flagged problems | count dealt with | ticket]: device
+                                                          // state only, the same in an eager call and in a recorded graph
+    static const bool no_nflag = [] { const char* e = getenv("FMPC_NO_NFLAG"); return e && e[0] == '1'; }();   // A/B switch
+    A.nflag = no_nflag ? nullptr : nf;
+    A.ldz = zld;                                          // (0: contiguous rows)
+    if (fmpc_launch_affine(A, h->num_cu, s.stream) != hipSuccess) return FMPC_E_HIP;
+    const int grid = fmpc_wave_grid(h, s.batch);
+    const int g3 = grid < 64 ? grid : 64;                 // flag mode: the waves walk over the flags, few are set
+    const int rc = fmpc_launch_flagged(h, s, g3, stride, h->fa_need, no_nflag ? nullptr : nf, zld);
+    h->last_path = FMPC_PATH_PANEL; h->inv_last = 2;
+    return rc;
+}
+
+// First Newton step from the cold start (the reference's own call has just this one): 16-problem panels on the matrix cores;
+// the exact-path launch behind them decides every problem's step length, redoes the problems whose decision is not clear-cut
+// and runs the remaining iterations of the budget
+static int fmpc_path_panel(fmpc_handle h, const FmpcSolve& s, size_t stride, int zld, bool z_null) {
+    const int batch = s.batch, max_iter = fmpc_max_iter(s);
+    const int npanels = (batch + FP_NP - 1) / FP_NP;
+    if ((size_t)batch > h->pn_cap) {
+        h->pn_cap = 0;
+        if (h->pn_gate.alloc((size_t)batch * 2, s.stream) != FMPC_OK ||
+            h->pn_epsp.alloc((size_t)npanels * h->T * FP_NP, s.stream) != FMPC_OK ||
+            h->pn_rnp.alloc((size_t)npanels * h->T * FP_NP, s.stream) != FMPC_OK ||
+            h->pn_list.alloc((size_t)batch, s.stream) != FMPC_OK ||
+            h->pn_nuws.alloc((size_t)npanels * FP_NP * h->nb * h->n, s.stream) != FMPC_OK) return FMPC_E_ALLOC;
+        h->pn_cap = batch;
+    }
+    // The dual solve in its dense form (no dependency chain, fmpc_kernel_inv.hip): always without w (56 columns),
+    // with w while the product is cheaper than the two sweeps of a panel (few panels leave the chip empty)
+    // (a closed-loop step hands over [B u1 ; B u2], the 2 n numbers its w depends on: 28 k-steps at any batch)
+    const bool lowrank = h->lp_hint && s.w != nullptr && h->lp_v != nullptr;
+    const bool dense_form = h->inv_enabled && (s.w == nullptr || lowrank || batch <= h->inv_max_batch);
+    if (dense_form && (!h->inv_valid || h->inv_k != s.k) && !(h->inv_failed && h->inv_failed_k == s.k)) {
+        if (hipStreamSynchronize(s.stream) != hipSuccess) return FMPC_E_HIP;   // earlier solves may still read J
+        const int rcb = fmpc_build_inverse(h, s.k, s.stream);
+        if (rcb != FMPC_OK) return rcb;
+        // J or nuc not finite: the sweep form is taken, and the build (a stream synchronisation, allocations and a
+        // 5 ms launch) is not retried on every later solve with this k
+        h->inv_failed = h->inv_valid ? 0 : 1; h->inv_failed_k = s.k;
+    }
+    if (dense_form && h->inv_valid && s.w == nullptr && max_iter == 1 && (s.nu_out == nullptr || !z_null) && !h->fa_disabled && h->n == FP_N) {
+        const int rca = fmpc_path_affine(h, s, stride, zld, z_null);
+        if (rca != FMPC_E_UNSUPPORTED) return rca;
+    }
+    if (zld) return FMPC_E_UNSUPPORTED;                       // (nothing of this solve is enqueued yet)
+    FpParams Q;
+    fmpc_panel_params(h, s.k, Q);
+    Q.batch = batch; Q.npanels = npanels; Q.step_ld = fmpc_step_ld(s.n_newton);
+    Q.x0 = s.x0; Q.x0p = s.x0_pre; Q.w = s.w; Q.nu0 = s.nu0;
+    Q.zout = s.z_out; Q.status = s.status; Q.iters = s.iters; Q.step = s.step;
+    Q.nuws = h->pn_nuws; Q.nuout = s.nu_out;
+    Q.gate = h->pn_gate; Q.epsp = h->pn_epsp; Q.handed = h->pn_cnt;
+    Q.rnp = h->pn_rnp;
+    const int split = max_iter > 1;                           // budgets > 1: decide, compact, continue (two launches)
+    const int pgrid = npanels < h->num_cu ? npanels : h->num_cu;
+    // (a small LDS footprint lets a d_z workgroup of another stream share the CU)
+    h->inv_last = dense_form && h->inv_valid;
+    // without w, without the terminal row and with a budget of 1 nobody but d_z reads nu+: d_z computes it itself
+    const bool fuse = h->inv_last && h->inv_fuse && s.w == nullptr && !h->has_xf && max_iter == 1;
+    Q.gate_only = fuse ? 1 : 0;
+    const bool u0only = z_null && max_iter == 1 && s.nu_out == nullptr;     // nothing of z leaves the chip
+    Q.u0out = s.u0_out;
+    if (h->inv_last) {
+        if (lowrank) { Q.gw = h->lp_v; Q.gwn = 2 * h->n; Q.jimg = h->inv_jimg2; Q.jks = h->inv_jks2; Q.jksp = 16 * ((h->inv_jks2 + 15) / 16 + 3); }
+        else { Q.gw = s.w; Q.gwn = h->T * h->n; }
+    }
+    hipError_t e;
+    if (h->inv_last) e = fmpc_launch_inv(Q, s.stream);
+    else e = fmpc_launch_panel(Q, pgrid, fmpc_panel_lds_used(h->nb, h->pn_mp, h->pn_nsf + h->pn_nsb), s.stream);
+    if (e != hipSuccess) return FMPC_E_HIP;
+    // one task per wave, 8 per workgroup; workgroups b, b + 8, ... take the panels b % 8, b % 8 + 8, ...
+    const int ppx = (npanels + 7) / 8;                       // panels of the fullest XCD share
+    const int dgrid = 8 * ((ppx * h->T + FD_WAVES - 1) / FD_WAVES);
+    e = fmpc_launch_dz(Q, dgrid, split, s.stream, fuse ? 1 : 0, u0only ? 1 : 0);
+    if (e != hipSuccess) return FMPC_E_HIP;
+    // decides the step length of every problem; solves exactly those whose decision is not clear-cut.  Budget 1:
+    // one launch.  Budgets > 1: a decide-only launch that also evaluates the next exit test and COMPACTS the
+    // problems that go on (typically a few per cent), then the continuation over that list on as few
+    // workgroups as it needs -- the rest of the chip stays free for other streams.
+    const int grid = fmpc_wave_grid(h, batch);
+    for (int ph = split ? 1 : 0; ph <= (split ? 2 : 0); ++ph) {
+        int g2 = grid;
+        if (ph == 2) {
+            // Every workgroup of the continuation needs a CU with its whole LDS free, also those that find the
+            // list empty -- behind other streams' long-running continuations they would wait for a slot.  Size
+            // the grid from the list length an EARLIER call of this handle reported (never waited for); the
+            // kernel loops over the list, so any grid is correct.
+            const int last = ((volatile int*)h->pn_cnt_host.p)[1];
+            if (last >= 0) {
+                const int wpw2 = fmpc_wave_waves_per_wg();
+                int want = (last + last / 2 + wpw2 - 1) / wpw2 + 4;
+                if (want < 8) want = 8;
+                if (want < g2) g2 = want;
+            }
+        }
+        if (ph == 2 && h->small_tiled) {
+            // the continuation is a handful of problems per CU at most: the tiled kernel (4 wavefronts per problem)
+            // finishes one in 0.45 ms where the one-wavefront kernel needs 1.0 ms (round 2 measurement)
+            const int last = ((volatile int*)h->pn_cnt_host.p)[1];
+            const int hint = last >= 0 ? last + last / 2 + 16 : 0;
+            const int rc_t = fmpc_solve_tiled(h, 0, s, h->small_nw, h->pn_list, h->pn_cnt + 1, h->pn_nuws, hint);
+            if (rc_t == FMPC_OK) continue;
+            // (no workspace for the tiled kernel: the panel, d_z and decision kernels are already enqueued -- the
+            // one-wavefront kernel below, whose workspace exists, finishes the solve instead of aborting it half-way)
+            if (rc_t != FMPC_E_UNSUPPORTED && rc_t != FMPC_E_ALLOC) return rc_t;
+        }
+        FwParams P = fmpc_wave_params(h, s, stride);
+        P.mode = FW_MODE_SHARED; P.gate = h->pn_gate; P.epsp = h->pn_epsp; P.handed = h->pn_cnt; P.nuws = h->pn_nuws;
+        P.pphase = ph; P.rnp = h->pn_rnp; P.list = h->pn_list; P.u0_done = u0only ? 1 : 0;
+        e = fmpc_launch_wave(P, g2, h->wave_lds, s.stream);
+        if (e != hipSuccess) return FMPC_E_HIP;
+    }
+    if (split && hipMemcpyAsync(h->pn_cnt_host, h->pn_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, s.stream) != hipSuccess)
+        return FMPC_E_HIP;
+    h->last_path = FMPC_PATH_PANEL;
+    return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
+}
+
+// Every problem factors its own Schur complement and there are at most 4 problems per CU: the tiled kernel's
+// 2 (4) wavefronts per problem finish a problem in 0.5 (0.4) ms where the one-wavefront kernel needs 1.0 ms;
+// beyond 1024 problems the one-wavefront kernel's 8 problems per CU win (measured in round 2)
+static int fmpc_path_small_tiled(fmpc_handle h, const FmpcSolve& s) {
+    return fmpc_solve_tiled(h, 0, s, s.batch <= 512 ? h->small_nw : 2);
+}
+
+// Explicit-start batch too large for the tiled kernel, budget > 1: with one problem per wavefront slot a launch lasts
+// as long as its slowest wavefront, so the few per cent of problems that take a second step double it (round 3:
+// 2.0 ms for 2180 problem-iterations, 1.2 ms for the 2000 first ones).  Two launches instead: the one-wavefront
+// kernel takes the first step of every problem and the NEXT exit test (pphase 4), appending the problems that go on
+// to a list; the tiled kernel (two wavefronts per problem: half the latency of one problem) works through that list.
+static int fmpc_path_split(fmpc_handle h, const FmpcSolve& s, size_t stride) {
+    // the continuation's launch is planned (instance, size, workspace) BEFORE the first-step launch is enqueued: if the tiled
+    // kernel cannot run, FMPC_E_UNSUPPORTED -- the caller's single launch solves the batch and nothing is left half done
+    const int last = h->gn_cnt_host ? ((volatile int*)h->gn_cnt_host.p)[1] : -1;   // list length an EARLIER call reported (never waited for)
+    const int gn_hint = last >= 0 ? last + last / 2 + 16 : 0;
+    FmpcTiledPlan gplan;
+    if (fmpc_tiled_plan(h, 0, s.batch, s.stream, h->small_nw, gn_hint, &gplan) != FMPC_OK) return FMPC_E_UNSUPPORTED;
+    const size_t nbn = (size_t)h->nb * h->n;
+    if ((size_t)s.batch > h->gn_cap) {
+        h->gn_cap = 0;
+        if (h->gn_list.alloc((size_t)s.batch, s.stream) != FMPC_OK || h->gn_cnt.alloc(2, s.stream) != FMPC_OK ||
+            h->gn_nu.alloc((size_t)s.batch * nbn, s.stream) != FMPC_OK) return FMPC_E_ALLOC;
+        h->gn_cap = s.batch;
+    }
+    if (!h->gn_cnt_host) {
+        if (h->gn_cnt_host.alloc(2, s.stream) != FMPC_OK) return FMPC_E_ALLOC;
+        h->gn_cnt_host[0] = -1; h->gn_cnt_host[1] = -1;
+    }
+    double* nu_arr = s.nu_out ? s.nu_out : h->gn_nu;            // nu after the first step, per problem: what the continuation starts from
+    // (a kernel, not hipMemsetAsync: a captured graph holding the 8-byte memset node faulted on its SECOND launch --
+    // "write access to a read-only page", ROCm 7.2, round 5; with this kernel node instead, and the 8-byte device-to-host
+    // copy node below kept, any number of launches is fine: tests/test_gpu_recorded.py)
+    hipLaunchKernelGGL(fmpc_zero_ints, dim3(1), dim3(64), 0, s.stream, h->gn_cnt, 2);
+    if (hipGetLastError() != hipSuccess) return FMPC_E_HIP;
+    FwParams P = fmpc_wave_params(h, s, stride);
+    P.nuout = nu_arr; P.handed = h->gn_cnt; P.pphase = 4; P.list = h->gn_list;
+    if (fmpc_launch_wave(P, fmpc_wave_grid(h, s.batch), h->wave_lds, s.stream) != hipSuccess) return FMPC_E_HIP;
+    h->last_path = FMPC_PATH_WAVE;
+    FmpcSolve c = s;
+    c.z_init = nullptr; c.nu_out = nu_arr;
+    const int rc_t = fmpc_solve_tiled(h, 0, c, h->small_nw, h->gn_list, h->gn_cnt + 1, nullptr, gn_hint, &gplan);
+    if (rc_t != FMPC_OK) return rc_t;
+    if (hipMemcpyAsync(h->gn_cnt_host, h->gn_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, s.stream) != hipSuccess) return FMPC_E_HIP;
+    return FMPC_OK;
+}
+
+// One launch of the one-wavefront kernel for the whole batch
+static int fmpc_path_wave(fmpc_handle h, const FmpcSolve& s, int mode, size_t stride) {
+    FwParams P = fmpc_wave_params(h, s, stride);
+    P.mode = mode;
+    const hipError_t e = fmpc_launch_wave(P, fmpc_wave_grid(h, s.batch), h->wave_lds, s.stream);
+    h->last_path = mode == FW_MODE_SHARED ? FMPC_PATH_SHARED : FMPC_PATH_WAVE;
+    return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
+}
+
+// fmpc_solve_device (u0_out == NULL) / fmpc_solve_u0_device: the first moves are written by the solve's last kernel
+// where that kernel visits every problem anyway (the wave kernel), by the unpack kernel otherwise.  Picks the path in a fixed
+// order; a path that does not apply returns before it enqueues anything.  Caller holds h->mu; s.ldz >= 0.
+static int fmpc_solve_device_inner(fmpc_handle h, FmpcSolve s) {
+    if (!h || !s.x0 || (!s.z_out && !s.u0_out)) return FMPC_E_NULL;
+    if (s.batch < 0) return FMPC_E_DIM;
+    if (s.batch == 0) return FMPC_OK;
+    const int max_iter = fmpc_max_iter(s);
+    // Output options (README.md:558-570,589: the loop uses U(1:nu) only): z_out == NULL with u0_out given returns the first
+    // moves alone.  The kernels that iterate on z then work in a scratch array of the handle; the cold-start panel path
+    // with a budget of 1 does not write z at all (fmpc_cold_dz<.., .., true>).
+    const bool z_null = s.z_out == nullptr;
+    if (z_null) {
+        const int rcz = fmpc_scratch_z(h, s.batch, s.stream);
+        if (rcz != FMPC_OK) return rcz;
+        s.z_out = h->zs;
+    }
+    // Padded z rows (fmpc_set_z_ld): the affine form of the cold-start step and its exact path honour them, nothing else does
+    const int zld = (!z_null && s.ldz > h->T * (h->n + h->m)) ? s.ldz : 0;
+    if (zld && (s.w != nullptr || s.z_init != nullptr || max_iter != 1 || h->prec == FMPC_PREC_F32_MIXED || h->force_tiled || h->denseQ ||
+                h->denseR || !h->use_wave || !h->sh_enabled || !h->pn_enabled)) return FMPC_E_UNSUPPORTED;
+    if (h->prec == FMPC_PREC_F32_MIXED || h->force_tiled || ((h->denseQ || h->denseR) && !h->generic_big) ||
+        (!h->use_wave && (!h->generic_ok || h->prefer_tiled)))
+        return fmpc_path_tiled(h, s);
+    if (!h->use_wave) return fmpc_path_generic(h, s);
+    size_t stride = 0;
+    int rc = fmpc_ensure_wave_ws(h, &stride, s.stream);
+    if (rc != FMPC_OK) return rc;
+    int mode = FW_MODE_NORMAL;
+    if (h->sh_enabled && s.z_init == nullptr) {
+        // cold start: the first Newton step of every problem shares one factor (depends on k only)
+        rc = fmpc_ensure_cold(h, s.k, stride, s.stream);
+        if (rc != FMPC_OK) return rc;
+        mode = FW_MODE_SHARED;
+    }
+    if (mode == FW_MODE_SHARED && h->pn_enabled && h->pn_valid) return fmpc_path_panel(h, s, stride, zld, z_null);
+    if (zld) return FMPC_E_UNSUPPORTED;
+    if (mode == FW_MODE_NORMAL && h->small_tiled && s.batch <= 1024) {
+        rc = fmpc_path_small_tiled(h, s);
+        if (rc != FMPC_E_UNSUPPORTED) return rc;
+    }
+    if (mode == FW_MODE_NORMAL && max_iter > 1 && h->small_tiled && h->gn_split) {
+        rc = fmpc_path_split(h, s, stride);                   // (FMPC_E_UNSUPPORTED: not planned, nothing enqueued)
+        if (rc != FMPC_E_UNSUPPORTED) return rc;
+    }
+    return fmpc_path_wave(h, s, mode, stride);
+}
+
+// s.ldz < 0: the handle's fmpc_set_z_ld value applies
+static int fmpc_solve_device_impl(fmpc_handle h, FmpcSolve s) {
+    if (!h || !s.x0 || (!s.z_out && !s.u0_out)) return FMPC_E_NULL;
+    if (s.batch < 0) return FMPC_E_DIM;
+    if (s.batch == 0) return FMPC_OK;
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
     std::lock_guard<std::mutex> lk(h->mu);
-    int rc = fmpc_guard_begin(h, (hipStream_t)stream);
+    if (s.ldz < 0) s.ldz = h->z_ld;
+    int rc = fmpc_guard_begin(h, s.stream);
     if (rc != FMPC_OK) return rc;
-    rc = fmpc_solve_device_inner(h, batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step,
-                                 u0_out, stream);
-    fmpc_guard_end(h, (hipStream_t)stream);
+    rc = fmpc_solve_device_inner(h, s);
+    fmpc_guard_end(h, s.stream);
     return rc;
 }
 
@@ -1544,8 +1462,8 @@ extern "C" int fmpc_solve_device(fmpc_handle h, int batch,
                                  int n_newton, double k,
                                  double* z_out, double* nu_out, int* status, int* iters, double* step,
                                  void* stream) {
-    return fmpc_solve_device_impl(h, batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step,
-                                  nullptr, stream);
+    return fmpc_solve_device_impl(h, {batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step,
+                                      nullptr, (hipStream_t)stream, -1});
 }
 
 extern "C" int fmpc_solve_u0_device(fmpc_handle h, int batch,
@@ -1555,11 +1473,13 @@ extern "C" int fmpc_solve_u0_device(fmpc_handle h, int batch,
                                     double* z_out, double* nu_out, int* status, int* iters, double* step,
                                     double* u0_out, void* stream) {
     if (!u0_out) return FMPC_E_NULL;
-    return fmpc_solve_device_impl(h, batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step,
-                                  u0_out, stream);
+    return fmpc_solve_device_impl(h, {batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step,
+                                      u0_out, (hipStream_t)stream, -1});
 }
 
-// fmpc_solve_u0_device with the row distance of z_out as an ARGUMENT of the call (0: contiguous rows) instead of handle state
+// fmpc_solve_u0_device with the row distance of z_out as an ARGUMENT of the call (0: contiguous rows) instead of handle state:
+// a concurrent solve on the same handle from another thread never sees it (the set / solve / restore of
+// fmpc_set_z_ld was not atomic)
 extern "C" int fmpc_solve_u0_device_ld(fmpc_handle h, int batch,
                                        const double* x0, const double* x0_pre, const double* w,
                                        const double* z_init, const double* nu0,
@@ -1568,11 +1488,8 @@ extern "C" int fmpc_solve_u0_device_ld(fmpc_handle h, int batch,
                                        double* u0_out, int ldz, void* stream) {
     if (!h) return FMPC_E_NULL;
     if (ldz < 0 || (ldz != 0 && ldz < h->T * (h->n + h->m))) return FMPC_E_DIM;
-    fmpc_tl_zld_explicit = ldz;
-    const int rc = fmpc_solve_device_impl(h, batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step,
-                                          u0_out, stream);
-    fmpc_tl_zld_explicit = -1;
-    return rc;
+    return fmpc_solve_device_impl(h, {batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step,
+                                      u0_out, (hipStream_t)stream, ldz});
 }
 
 // Closed-loop step of a few realisations in the first-move form (fmpc_kernel_first.hip): ONE launch computes the loop inputs,
@@ -1584,7 +1501,7 @@ static int fmpc_first_move_ensure(fmpc_handle h, int batch, double k, hipStream_
     if (h->fm_disabled || !h->use_wave || !h->sh_enabled || !h->pn_enabled || !h->inv_enabled || h->n != FP_N || batch > max_batch)
         return FMPC_E_UNSUPPORTED;
     size_t stride = 0;
-    int rc = fmpc_ensure_wave_ws(h, &stride);
+    int rc = fmpc_ensure_wave_ws(h, &stride, stream);
     if (rc != FMPC_OK) return rc;
     rc = fmpc_ensure_cold(h, k, stride, stream);
     if (rc != FMPC_OK) return rc;
@@ -1599,22 +1516,14 @@ static int fmpc_first_move_ensure(fmpc_handle h, int batch, double k, hipStream_
     }
     if (!h->fm_valid || h->fm_k != k) {
         if (hipStreamSynchronize(stream) != hipSuccess) return FMPC_E_HIP;
-        rc = fmpc_build_first_move(h, k);
+        rc = fmpc_build_first_move(h, k, stream);
         if (rc != FMPC_OK) return rc;
     }
     // scratch iterate for realisations the exact path redoes, one flag per realisation
-    const size_t needz = (size_t)batch * h->T * (h->n + h->m);
-    if (needz > h->zs_doubles) {
-        if (h->zs) { (void)hipDeviceSynchronize(); (void)hipFree(h->zs); h->zs = nullptr; h->zs_doubles = 0; }
-        if (hipMalloc((void**)&h->zs, needz * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-        h->zs_doubles = needz;
-    }
-    if ((size_t)batch > h->fm_need_cap) {
-        if (h->fm_need) { (void)hipDeviceSynchronize(); (void)hipFree(h->fm_need); h->fm_need = nullptr; h->fm_need_cap = 0; }
-        const size_t cap = batch > FMPC_FIRST_MOVE_MAX_BATCH ? (size_t)batch : (size_t)FMPC_FIRST_MOVE_MAX_BATCH;
-        if (hipMalloc((void**)&h->fm_need, cap * sizeof(int)) != hipSuccess) return FMPC_E_ALLOC;
-        h->fm_need_cap = cap;
-    }
+    rc = fmpc_scratch_z(h, batch, stream);
+    if (rc != FMPC_OK) return rc;
+    rc = h->fm_need.grow(batch > FMPC_FIRST_MOVE_MAX_BATCH ? (size_t)batch : (size_t)FMPC_FIRST_MOVE_MAX_BATCH, stream);
+    if (rc != FMPC_OK) return rc;
     *stride_out = stride;
     return FMPC_OK;
 }
@@ -1637,9 +1546,8 @@ static int fmpc_first_move_step(fmpc_handle h, int batch, const double* a_k, con
     // the exact path for flagged realisations (cold start with the shared factor), first moves from its own z
     const int wpw = fmpc_wave_waves_per_wg();
     const int grid = (batch + wpw - 1) / wpw;
-    if (fmpc_launch_wave(h->dev, h->wave, batch, grid, xs, xps, w, nullptr, nu0, 1, k, h->zs, nullptr, status, iters, step,
-                         fmpc_step_ld(1), h->ws, stride, h->wave_lds, stream, 1, h->sh_fac, h->sh_rs, h->sh_ok, h->cold_d,
-                         nullptr, nullptr, h->pn_cnt, nullptr, u0_out, 3, nullptr, h->fm_need) != hipSuccess) return FMPC_E_HIP;
+    const FmpcSolve f = {batch, xs, xps, w, nullptr, nu0, 1, k, h->zs, nullptr, status, iters, step, u0_out, stream, 0};
+    if (fmpc_launch_flagged(h, f, grid, stride, h->fm_need) != FMPC_OK) return FMPC_E_HIP;
     h->last_path = FMPC_PATH_PANEL; h->inv_last = 1;
     return FMPC_OK;
 }
@@ -1670,20 +1578,14 @@ static int fmpc_loop_u0_step(fmpc_handle h, int batch, const double* a_k, const 
         L.x0w = x0; L.x0pw = x0_pre;
         I.a = a_k; I.x0_last = x0_last; I.u1 = u1; I.u2 = u2; I.w = w;
         if (fmpc_launch_loop_step27(L, I, stream) != hipSuccess) return FMPC_E_HIP;
-        if (fmpc_launch_wave(h->dev, h->wave, batch, grid, xs, xps, w, nullptr, nu0, 1, k, h->zs, nullptr, status, iters, step,
-                             fmpc_step_ld(1), h->ws, stride, h->wave_lds, stream, 1, h->sh_fac, h->sh_rs, h->sh_ok, h->cold_d,
-                             nullptr, nullptr, h->pn_cnt, nullptr, u0_out, 3, nullptr, h->fm_need) != hipSuccess) return FMPC_E_HIP;
+        const FmpcSolve f = {batch, xs, xps, w, nullptr, nu0, 1, k, h->zs, nullptr, status, iters, step, u0_out, stream, 0};
+        if (fmpc_launch_flagged(h, f, grid, stride, h->fm_need) != FMPC_OK) return FMPC_E_HIP;
         h->last_path = FMPC_PATH_PANEL; h->inv_last = 4;
         return FMPC_OK;
     }
     if (given) return FMPC_E_UNSUPPORTED;          // (the caller takes the general route)
-    if ((size_t)batch > h->lp_cap) {
-        (void)hipDeviceSynchronize();
-        if (h->lp_v) (void)hipFree(h->lp_v);
-        h->lp_v = nullptr; h->lp_cap = 0;
-        if (hipMalloc((void**)&h->lp_v, (size_t)batch * 2 * h->n * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-        h->lp_cap = batch;
-    }
+    rc = h->lp_v.grow((size_t)batch * 2 * h->n, stream);
+    if (rc != FMPC_OK) return rc;
     if (fmpc_launch_loop_inputs(h->n, h->m, h->T, batch, h->dev.Bt, h->loop_M1, h->loop_M2, a_k, x0_last, u1, u2,
                                 x0, x0_pre, w, stream, h->lp_v) != hipSuccess) return FMPC_E_HIP;
     FlParams L = h->fl_P;
@@ -1691,9 +1593,8 @@ static int fmpc_loop_u0_step(fmpc_handle h, int batch, const double* a_k, const 
     L.x0 = x0; L.x0_pre = x0_pre; L.v = h->lp_v; L.nu0 = nu0;
     L.u0out = u0_out; L.status = status; L.iters = iters; L.step = step; L.need = h->fm_need; L.handed = h->pn_cnt;
     if (fmpc_launch_loop_u0(L, stream) != hipSuccess) return FMPC_E_HIP;
-    if (fmpc_launch_wave(h->dev, h->wave, batch, grid, x0, x0_pre, w, nullptr, nu0, 1, k, h->zs, nullptr, status, iters, step,
-                         fmpc_step_ld(1), h->ws, stride, h->wave_lds, stream, 1, h->sh_fac, h->sh_rs, h->sh_ok, h->cold_d,
-                         nullptr, nullptr, h->pn_cnt, nullptr, u0_out, 3, nullptr, h->fm_need) != hipSuccess) return FMPC_E_HIP;
+    const FmpcSolve f = {batch, x0, x0_pre, w, nullptr, nu0, 1, k, h->zs, nullptr, status, iters, step, u0_out, stream, 0};
+    if (fmpc_launch_flagged(h, f, grid, stride, h->fm_need) != FMPC_OK) return FMPC_E_HIP;
     h->last_path = FMPC_PATH_PANEL; h->inv_last = 3;
     return FMPC_OK;
 }
@@ -1731,32 +1632,23 @@ static int fmpc_loop_step_impl(fmpc_handle h, int batch, const double* a_k, cons
         if (rc != FMPC_E_UNSUPPORTED) { fmpc_guard_end(h, (hipStream_t)stream); return rc; }
         rc = FMPC_OK;
     }
-    if (lr && (size_t)batch > h->lp_cap) {
-        (void)hipDeviceSynchronize();
-        if (h->lp_v) (void)hipFree(h->lp_v);
-        h->lp_v = nullptr; h->lp_cap = 0;
-        if (hipMalloc((void**)&h->lp_v, (size_t)batch * 2 * h->n * sizeof(double)) != hipSuccess) { fmpc_guard_end(h, (hipStream_t)stream); return FMPC_E_ALLOC; }
-        h->lp_cap = batch;
-    }
+    if (lr && (rc = h->lp_v.grow((size_t)batch * 2 * h->n, (hipStream_t)stream)) != FMPC_OK) { fmpc_guard_end(h, (hipStream_t)stream); return rc; }
     const double* a_in = a_k; const double* xl_in = x0_last; double* x0_o = x0; double* x0p_o = x0_pre;
     if (given) {
         // the loop-input kernel only has to produce w: a = 0, its x0 / x0_pre go to scratch (3 batch n doubles of the handle)
-        if ((size_t)batch > h->ao_cap) {
-            (void)hipDeviceSynchronize();
-            if (h->ao_scr) (void)hipFree(h->ao_scr);
-            h->ao_scr = nullptr; h->ao_cap = 0;
-            if (hipMalloc((void**)&h->ao_scr, (size_t)3 * batch * h->n * sizeof(double)) != hipSuccess) { fmpc_guard_end(h, (hipStream_t)stream); return FMPC_E_ALLOC; }
+        if ((size_t)batch * 3 * h->n > h->ao_scr.cap) {
+            if ((rc = h->ao_scr.alloc((size_t)3 * batch * h->n, (hipStream_t)stream)) != FMPC_OK) { fmpc_guard_end(h, (hipStream_t)stream); return rc; }
             if (hipMemsetAsync(h->ao_scr, 0, (size_t)batch * h->n * sizeof(double), (hipStream_t)stream) != hipSuccess) { fmpc_guard_end(h, (hipStream_t)stream); return FMPC_E_HIP; }
-            h->ao_cap = batch;
         }
-        a_in = h->ao_scr; xl_in = nullptr; x0_o = h->ao_scr + (size_t)h->ao_cap * h->n; x0p_o = h->ao_scr + (size_t)2 * h->ao_cap * h->n;
+        const size_t cap = h->ao_scr.cap / (3 * h->n);          // (problems the scratch was sized for: the offsets of its thirds)
+        a_in = h->ao_scr; xl_in = nullptr; x0_o = h->ao_scr + cap * h->n; x0p_o = h->ao_scr + 2 * cap * h->n;
     }
     if (fmpc_launch_loop_inputs(h->n, h->m, h->T, batch, h->dev.Bt, h->loop_M1, h->loop_M2, a_in, xl_in, u1, u2,
                                 x0_o, x0p_o, w, (hipStream_t)stream, lr ? h->lp_v : nullptr) != hipSuccess) rc = FMPC_E_HIP;
     if (rc == FMPC_OK) {
         h->lp_hint = lr ? 1 : 0;
-        rc = fmpc_solve_device_inner(h, batch, given ? a_k : x0, given ? x0_last : x0_pre, w, nullptr, nu0, n_newton, k, z_out, nu_out, status, iters, step,
-                                     u0_out, stream);
+        rc = fmpc_solve_device_inner(h, {batch, given ? a_k : x0, given ? x0_last : x0_pre, w, nullptr, nu0, n_newton, k, z_out, nu_out,
+                                         status, iters, step, u0_out, (hipStream_t)stream, h->z_ld});
         h->lp_hint = 0;
     }
     fmpc_guard_end(h, (hipStream_t)stream);
@@ -1818,14 +1710,11 @@ static int fmpc_loop_run_walk(fmpc_handle h, int batch, int steps, int upto, con
             size_t stride = 0;
             rc = fmpc_first_move_ensure(h, 1, k, stream, &stride);
             if (rc == FMPC_OK && (size_t)batch > h->fm_walk_cap) {
-                (void)hipDeviceSynchronize();
-                if (h->fm_walk_i) (void)hipFree(h->fm_walk_i);
-                if (h->fm_compact) (void)hipFree(h->fm_compact);
-                h->fm_walk_i = nullptr; h->fm_compact = nullptr; h->fm_walk_cap = 0;
+                h->fm_walk_cap = 0;
                 size_t cap = 64;
                 while (cap < (size_t)batch) cap *= 2;
                 const size_t nd = fmpc_compact_doubles(h->n, h->m, h->T, h->nb, (int)cap);
-                if (hipMalloc((void**)&h->fm_walk_i, 2 * cap * sizeof(int)) != hipSuccess || hipMalloc((void**)&h->fm_compact, nd * sizeof(double)) != hipSuccess) rc = FMPC_E_ALLOC;
+                if (h->fm_walk_i.alloc(2 * cap, stream) != FMPC_OK || h->fm_compact.alloc(nd, stream) != FMPC_OK) rc = FMPC_E_ALLOC;
                 else h->fm_walk_cap = cap;
             }
             if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
@@ -1987,7 +1876,7 @@ extern "C" int fmpc_set_ramp(fmpc_handle h, const double* du_min, const double* 
     if (h->n > 64 || lds > FMPC_LDS_LIMIT || h->denseQ || h->denseR) return FMPC_E_UNSUPPORTED;   // (the ramp kernel keeps Q, Qf as diagonals)
     std::lock_guard<std::mutex> lk(h->mu);
     if (!h->ramp_du) {
-        if (hipMalloc((void**)&h->ramp_du, 2 * (size_t)h->m * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
+        if (h->ramp_du.alloc(2 * (size_t)h->m, nullptr) != FMPC_OK) return FMPC_E_ALLOC;
         if (fmpc_ramp_prepare(lds) != hipSuccess) return FMPC_E_HIP;
     } else if (hipDeviceSynchronize() != hipSuccess) {
         return FMPC_E_HIP;
@@ -2002,7 +1891,7 @@ extern "C" int fmpc_set_ramp(fmpc_handle h, const double* du_min, const double* 
 // Constants of the cold-start step's Woodbury form for barrier weight k (fmpc_host_build_ramp_cold): built on the host in long
 // double on first use of a k, uploaded as one pool.  FMPC_E_UNSUPPORTED: the general path takes the solve (LDS, a start point
 // at which Phibar or Ybar is not positive definite, FMPC_NO_RAMP_COLD=1).  Caller holds h->mu.
-static int fmpc_ensure_ramp_cold(fmpc_handle h, double k) {
+static int fmpc_ensure_ramp_cold(fmpc_handle h, double k, hipStream_t stream) {
     if (h->rc_disabled) return FMPC_E_UNSUPPORTED;
     if (h->rc_valid && h->rc_k == k) return FMPC_OK;
     if (h->rc_failed && h->rc_failed_k == k) return FMPC_E_UNSUPPORTED;
@@ -2041,10 +1930,9 @@ static int fmpc_ensure_ramp_cold(fmpc_handle h, double k) {
                 }
         o_Gt = push(Gt);
     }
-    if (h->rc_pool) { (void)hipDeviceSynchronize(); (void)hipFree(h->rc_pool); h->rc_pool = nullptr; }
     h->rc_valid = 0;
-    if (hipMalloc((void**)&h->rc_pool, pool.size() * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-    if (hipMemcpy(h->rc_pool, pool.data(), pool.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return FMPC_E_HIP;
+    const int rc = h->rc_pool.assign(pool.data(), pool.size(), stream);
+    if (rc != FMPC_OK) return rc;
     if (fmpc_ramp_cold_prepare(lds) != hipSuccess) return FMPC_E_HIP;
     FrColdParams& P = h->rc_P;
     memset(&P, 0, sizeof(P));
@@ -2058,14 +1946,16 @@ static int fmpc_ensure_ramp_cold(fmpc_handle h, double k) {
 
 // fmpc_solve_ramp_device (u0_out == NULL) / fmpc_solve_ramp_u0_device: the first moves come from the cold-start kernel itself when
 // it takes the whole solve (budget 1), from the unpack kernel otherwise; z_out == NULL (first moves only) works in a scratch array
-static int fmpc_solve_ramp_device_impl(fmpc_handle h, int batch,
-                                       const double* x0, const double* x0_pre, const double* w, const double* u_prev,
-                                       const double* z_init, const double* nu0, int n_newton, double k,
-                                       double* z_out, double* nu_out, int* status, int* iters, double* step,
-                                       double* u0_out, void* stream) {
+// (s.ldz < 0: the handle's fmpc_set_z_ld value applies)
+static int fmpc_solve_ramp_device_impl(fmpc_handle h, const FmpcSolve& s, const double* u_prev) {
+    const int batch = s.batch, n_newton = s.n_newton;
+    const double k = s.k;
+    const double* x0 = s.x0; const double* x0_pre = s.x0_pre; const double* w = s.w; const double* z_init = s.z_init; const double* nu0 = s.nu0;
+    double* z_out = s.z_out; double* nu_out = s.nu_out; int* status = s.status; int* iters = s.iters; double* step = s.step; double* u0_out = s.u0_out;
+    const hipStream_t stream = s.stream;
     if (!h || !x0 || (!z_out && !u0_out) || !u_prev) return FMPC_E_NULL;
     if (!h->ramp_du) return FMPC_E_UNSUPPORTED;                    // fmpc_set_ramp first
-    if (!fmpc_tl_contiguous_z && fmpc_effective_zld(h) > h->T * (h->n + h->m)) return FMPC_E_UNSUPPORTED;   // padded z rows: the cold-start affine step only
+    if ((s.ldz < 0 ? h->z_ld : s.ldz) > h->T * (h->n + h->m)) return FMPC_E_UNSUPPORTED;   // padded z rows: the cold-start affine step only
     if (batch < 0) return FMPC_E_DIM;
     if (batch == 0) return FMPC_OK;
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
@@ -2074,12 +1964,8 @@ static int fmpc_solve_ramp_device_impl(fmpc_handle h, int batch,
     const bool z_null = z_out == nullptr;
     const bool cold_only = z_init == nullptr && max_iter == 1 && !h->rc_disabled;   // (the cold-start kernel then needs no z array at all)
     if (z_null && !cold_only) {
-        const size_t need = (size_t)batch * h->T * (h->n + h->m);
-        if (need > h->zs_doubles) {
-            if (h->zs) { (void)hipDeviceSynchronize(); (void)hipFree(h->zs); h->zs = nullptr; h->zs_doubles = 0; }
-            if (hipMalloc((void**)&h->zs, need * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-            h->zs_doubles = need;
-        }
+        const int rcz = fmpc_scratch_z(h, batch, stream);
+        if (rcz != FMPC_OK) return rcz;
         z_out = h->zs;
     }
     // one workgroup per problem in flight; the workspace holds the dense Y of each (nb n)^2 doubles
@@ -2093,42 +1979,31 @@ static int fmpc_solve_ramp_device_impl(fmpc_handle h, int batch,
     if ((size_t)cap * stride > budget) cap = (int)(budget / stride);
     if (cap < 1) return FMPC_E_ALLOC;
     const int grid = batch < cap ? batch : cap;
-    auto ensure_general_ws = [&]() -> int {                          // (the cold-start form with a budget of 1 never needs it)
-        const size_t need = stride * (size_t)grid;
-        if (need > h->ramp_ws_doubles) {
-            if (h->ramp_ws) { (void)hipDeviceSynchronize(); (void)hipFree(h->ramp_ws); h->ramp_ws = nullptr; h->ramp_ws_doubles = 0; }
-            if (hipMalloc((void**)&h->ramp_ws, need * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-            h->ramp_ws_doubles = need;
-        }
-        return FMPC_OK;
-    };
+    // (the cold-start form with a budget of 1 never needs it)
+    auto ensure_general_ws = [&]() -> int { return h->ramp_ws.grow(stride * (size_t)grid, stream); };
     h->last_path = FMPC_PATH_RAMP;
     h->rc_last = 0;
     // Cold start: the first Newton step in its Woodbury form (one m x m factorisation per problem, fmpc_ramp_cold); a budget > 1
     // continues with the general kernel from the iterate that step leaves (it0 = 1).
     if (z_init == nullptr) {
-        const int rcc = fmpc_ensure_ramp_cold(h, k);
+        const int rcc = fmpc_ensure_ramp_cold(h, k, stream);
         if (rcc != FMPC_OK && rcc != FMPC_E_UNSUPPORTED) return rcc;
         if (rcc == FMPC_OK) {
             const size_t cstride = fmpc_ramp_cold_ws_doubles(h->m);
             const int cgrid = batch < h->num_cu ? batch : h->num_cu;
-            if (cstride * (size_t)cgrid > h->rc_ws_doubles) {
-                if (h->rc_ws) { (void)hipDeviceSynchronize(); (void)hipFree(h->rc_ws); h->rc_ws = nullptr; h->rc_ws_doubles = 0; }
+            if (cstride * (size_t)cgrid > h->rc_ws.cap) {
                 size_t want = cstride * (size_t)(batch < h->num_cu ? (batch < 16 ? 16 : batch) : h->num_cu);
                 if (want > cstride * (size_t)h->num_cu) want = cstride * (size_t)h->num_cu;
-                if (hipMalloc((void**)&h->rc_ws, want * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-                h->rc_ws_doubles = want;
+                const int rcw = h->rc_ws.alloc(want, stream);
+                if (rcw != FMPC_OK) return rcw;
             }
             double* nu_first = nu_out;
             int* st_first = status; int* it_first = iters;
             if (max_iter > 1 && (!nu_out || !status || !iters)) {
                 if ((size_t)batch > h->rc_cap) {
-                    (void)hipDeviceSynchronize();
-                    if (h->rc_nu) (void)hipFree(h->rc_nu);
-                    if (h->rc_si) (void)hipFree(h->rc_si);
-                    h->rc_nu = nullptr; h->rc_si = nullptr; h->rc_cap = 0;
-                    if (hipMalloc((void**)&h->rc_nu, (size_t)batch * h->nb * h->n * sizeof(double)) != hipSuccess ||
-                        hipMalloc((void**)&h->rc_si, 2 * (size_t)batch * sizeof(int)) != hipSuccess) return FMPC_E_ALLOC;
+                    h->rc_cap = 0;
+                    if (h->rc_nu.alloc((size_t)batch * h->nb * h->n, stream) != FMPC_OK ||
+                        h->rc_si.alloc(2 * (size_t)batch, stream) != FMPC_OK) return FMPC_E_ALLOC;
                     h->rc_cap = batch;
                 }
                 if (!nu_out) nu_first = h->rc_nu;
@@ -2143,36 +2018,32 @@ static int fmpc_solve_ramp_device_impl(fmpc_handle h, int batch,
             }
             P.zout = z_out; P.nuout = nu_first; P.u0out = max_iter == 1 ? u0_out : nullptr; P.status = st_first; P.iters = it_first; P.step = step;
             P.step_ld = fmpc_step_ld(n_newton); P.ws = h->rc_ws; P.ws_stride = cstride;
-            if (fmpc_guard_begin(h, (hipStream_t)stream) != FMPC_OK) return FMPC_E_HIP;
-            hipError_t e = fmpc_launch_ramp_cold(P, cgrid, (hipStream_t)stream);
+            if (fmpc_guard_begin(h, stream) != FMPC_OK) return FMPC_E_HIP;
+            hipError_t e = fmpc_launch_ramp_cold(P, cgrid, stream);
             h->rc_last = 1;
             if (e == hipSuccess && max_iter > 1)
                 e = fmpc_launch_ramp(h->dev, h->ramp_du, h->ramp_du + h->m, batch, grid, x0, x0_pre, w, u_prev, z_out,
                                      nu_first, max_iter, k, z_out, nu_out, st_first, it_first, step, fmpc_step_ld(n_newton),
-                                     h->ramp_ws, stride, threads, (hipStream_t)stream, 1);
+                                     h->ramp_ws, stride, threads, stream, 1);
             if (e == hipSuccess && max_iter > 1 && u0_out)
-                e = fmpc_launch_unpack(h->n, h->m, h->T, batch, z_out, nullptr, nullptr, u0_out, (hipStream_t)stream);
-            fmpc_guard_end(h, (hipStream_t)stream);
+                e = fmpc_launch_unpack(h->n, h->m, h->T, batch, z_out, nullptr, nullptr, u0_out, stream);
+            fmpc_guard_end(h, stream);
             return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
         }
         if (z_null && !z_out) {                                      // the cold-start form is not available after all: scratch iterate
-            const size_t need = (size_t)batch * h->T * (h->n + h->m);
-            if (need > h->zs_doubles) {
-                if (h->zs) { (void)hipDeviceSynchronize(); (void)hipFree(h->zs); h->zs = nullptr; h->zs_doubles = 0; }
-                if (hipMalloc((void**)&h->zs, need * sizeof(double)) != hipSuccess) return FMPC_E_ALLOC;
-                h->zs_doubles = need;
-            }
+            const int rcz = fmpc_scratch_z(h, batch, stream);
+            if (rcz != FMPC_OK) return rcz;
             z_out = h->zs;
         }
     }
     { const int rw = ensure_general_ws(); if (rw != FMPC_OK) return rw; }
-    if (fmpc_guard_begin(h, (hipStream_t)stream) != FMPC_OK) return FMPC_E_HIP;
+    if (fmpc_guard_begin(h, stream) != FMPC_OK) return FMPC_E_HIP;
     hipError_t e = fmpc_launch_ramp(h->dev, h->ramp_du, h->ramp_du + h->m, batch, grid, x0, x0_pre, w, u_prev, z_init,
                                     nu0, max_iter, k, z_out, nu_out, status, iters, step, fmpc_step_ld(n_newton),
-                                    h->ramp_ws, stride, threads, (hipStream_t)stream);
+                                    h->ramp_ws, stride, threads, stream);
     if (e == hipSuccess && u0_out)
-        e = fmpc_launch_unpack(h->n, h->m, h->T, batch, z_out, nullptr, nullptr, u0_out, (hipStream_t)stream);
-    fmpc_guard_end(h, (hipStream_t)stream);
+        e = fmpc_launch_unpack(h->n, h->m, h->T, batch, z_out, nullptr, nullptr, u0_out, stream);
+    fmpc_guard_end(h, stream);
     return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
@@ -2182,7 +2053,8 @@ extern "C" int fmpc_solve_ramp_device(fmpc_handle h, int batch,
                                       double* z_out, double* nu_out, int* status, int* iters, double* step,
                                       void* stream) {
     if (!z_out) return FMPC_E_NULL;
-    return fmpc_solve_ramp_device_impl(h, batch, x0, x0_pre, w, u_prev, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step, nullptr, stream);
+    return fmpc_solve_ramp_device_impl(h, {batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step, nullptr,
+                                           (hipStream_t)stream, -1}, u_prev);
 }
 
 extern "C" int fmpc_solve_ramp_u0_device(fmpc_handle h, int batch,
@@ -2191,7 +2063,8 @@ extern "C" int fmpc_solve_ramp_u0_device(fmpc_handle h, int batch,
                                          double* z_out, double* nu_out, int* status, int* iters, double* step,
                                          double* u0_out, void* stream) {
     if (!u0_out) return FMPC_E_NULL;
-    return fmpc_solve_ramp_device_impl(h, batch, x0, x0_pre, w, u_prev, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step, u0_out, stream);
+    return fmpc_solve_ramp_device_impl(h, {batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step, u0_out,
+                                           (hipStream_t)stream, -1}, u_prev);
 }
 
 // host-pointer solve; u_prev != NULL selects the ramp-rate path
@@ -2232,24 +2105,18 @@ static int fmpc_solve_host(fmpc_handle h, int batch,
     char* pin_dev = nullptr;
     {
         std::lock_guard<std::mutex> lk(h->mu);
-        if (off > h->stage_bytes) {
-            if (h->stage) { (void)hipDeviceSynchronize(); (void)hipFree(h->stage); h->stage = nullptr; h->stage_bytes = 0; }
-            if (hipMalloc(&h->stage, off) != hipSuccess) return FMPC_E_ALLOC;
-            h->stage_bytes = off;
-        }
-        base = (char*)h->stage;
+        const int rcs = h->stage.grow(off, nullptr);
+        if (rcs != FMPC_OK) return rcs;
+        base = h->stage;
         if (pinned) {
-            if (off > h->pin_bytes) {
-                if (h->pin) { (void)hipDeviceSynchronize(); (void)hipHostFree(h->pin); h->pin = nullptr; h->pin_bytes = 0; }
+            if (off > h->pin.cap) {
                 size_t want = 64 * 1024;
                 while (want < off) want *= 2;
                 h->pin_dev = nullptr;
-                if (hipHostMalloc(&h->pin, want, hipHostMallocDefault) == hipSuccess) {
-                    h->pin_bytes = want;
-                    if (hipHostGetDevicePointer(&h->pin_dev, h->pin, 0) != hipSuccess) h->pin_dev = nullptr;   // (the block as the kernels see it)
-                } else h->pin = nullptr;                            // (no pinned memory: the blocking copies below still work)
+                if (h->pin.alloc(want, nullptr) == FMPC_OK &&                       // (no pinned memory: the blocking copies below still work)
+                    hipHostGetDevicePointer(&h->pin_dev, h->pin, 0) != hipSuccess) h->pin_dev = nullptr;   // (the block as the kernels see it)
             }
-            pin = (char*)h->pin;
+            pin = h->pin;
             pin_dev = (char*)h->pin_dev;
         }
     }
@@ -2278,15 +2145,12 @@ static int fmpc_solve_host(fmpc_handle h, int batch,
     int* d_it = (int*)(base_o + o_it);
     double* d_nu = nu_out ? (double*)(base_o + o_nu) : nullptr;
     double* d_step = step ? (double*)(base_o + o_step) : nullptr;
-    fmpc_tl_contiguous_z = 1;                                   // (the staging block's rows are contiguous: fmpc_set_z_ld is for device batches)
     double* d_z = z_out ? (double*)(base_o + o_z) : nullptr;
-    int rc = u_prev ? fmpc_solve_ramp_device(h, batch, dptr(x0, o_x0), dptr(x0_pre, o_x0p), dptr(w, o_w), dptr(u_prev, o_up), dptr(z_init, o_zi),
-                                             dptr(nu0, o_nu0), n_newton, k, d_z, d_nu, d_st, d_it, d_step, nullptr)
-            : u0_out ? fmpc_solve_u0_device(h, batch, dptr(x0, o_x0), dptr(x0_pre, o_x0p), dptr(w, o_w), dptr(z_init, o_zi), dptr(nu0, o_nu0),
-                                            n_newton, k, d_z, d_nu, d_st, d_it, d_step, (double*)(base_o + o_u0), nullptr)
-                    : fmpc_solve_device(h, batch, dptr(x0, o_x0), dptr(x0_pre, o_x0p), dptr(w, o_w), dptr(z_init, o_zi), dptr(nu0, o_nu0),
-                                        n_newton, k, d_z, d_nu, d_st, d_it, d_step, nullptr);
-    fmpc_tl_contiguous_z = 0;
+    double* d_u0 = u0_out ? (double*)(base_o + o_u0) : nullptr;
+    // (ldz 0: the staging block's rows are contiguous, fmpc_set_z_ld is for device batches)
+    const FmpcSolve s = {batch, dptr(x0, o_x0), dptr(x0_pre, o_x0p), dptr(w, o_w), dptr(z_init, o_zi), dptr(nu0, o_nu0), n_newton, k,
+                         d_z, d_nu, d_st, d_it, d_step, d_u0, nullptr, 0};
+    int rc = u_prev ? fmpc_solve_ramp_device_impl(h, s, dptr(u_prev, o_up)) : fmpc_solve_device_impl(h, s);
     if (rc != FMPC_OK) { (void)hipDeviceSynchronize(); return rc; }
     std::vector<int> stv;
     const int* st;
@@ -2388,22 +2252,18 @@ extern "C" int fmpc_unpack(fmpc_handle h, int batch, const double* z, double* U,
     if (batch == 0) return FMPC_OK;
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
     const size_t B = batch, Nz = (size_t)h->T * (h->n + h->m), Tm = (size_t)h->T * h->m, Tn = (size_t)h->T * h->n;
-    double *dz = nullptr, *dU = nullptr, *dX = nullptr, *du0 = nullptr;
+    DevBuf<double> dz, dU, dX, du0;                               // (released on return)
     int rc = FMPC_OK;
-    if (hipMalloc((void**)&dz, Nz * B * 8) != hipSuccess) return FMPC_E_ALLOC;
-    if ((U && hipMalloc((void**)&dU, Tm * B * 8) != hipSuccess) ||
-        (X && hipMalloc((void**)&dX, Tn * B * 8) != hipSuccess) ||
-        (u0 && hipMalloc((void**)&du0, h->m * B * 8) != hipSuccess)) rc = FMPC_E_ALLOC;
+    if (dz.alloc(Nz * B, nullptr) != FMPC_OK) return FMPC_E_ALLOC;
+    if ((U && dU.alloc(Tm * B, nullptr) != FMPC_OK) ||
+        (X && dX.alloc(Tn * B, nullptr) != FMPC_OK) ||
+        (u0 && du0.alloc(h->m * B, nullptr) != FMPC_OK)) rc = FMPC_E_ALLOC;
     if (rc == FMPC_OK && hipMemcpy(dz, z, Nz * B * 8, hipMemcpyHostToDevice) != hipSuccess) rc = FMPC_E_HIP;
     if (rc == FMPC_OK) rc = fmpc_unpack_device(h, batch, dz, dU, dX, du0, nullptr);
     if (rc == FMPC_OK && hipDeviceSynchronize() != hipSuccess) rc = FMPC_E_HIP;
     if (rc == FMPC_OK && U && hipMemcpy(U, dU, Tm * B * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = FMPC_E_HIP;
     if (rc == FMPC_OK && X && hipMemcpy(X, dX, Tn * B * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = FMPC_E_HIP;
     if (rc == FMPC_OK && u0 && hipMemcpy(u0, du0, h->m * B * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = FMPC_E_HIP;
-    (void)hipFree(dz);
-    if (dU) (void)hipFree(dU);
-    if (dX) (void)hipFree(dX);
-    if (du0) (void)hipFree(du0);
     return rc;
 }
 

@@ -70,3 +70,43 @@ struct FwModel {
     const int* i1;          //                of Y_{i,i+1}   (zero block if none)
     const int* i2;          //                of Y_{i,i+2}   (zero block if none)
 };
+
+// Launch parameters of the one-wave-per-problem kernel
+#define FW_MODE_NORMAL 0                // every problem factors its own Y
+#define FW_MODE_SHARED 1                // first Newton step from a cold start uses the handle's shared factor
+#define FW_MODE_EXPORT 2                // compute that shared factor (batch 1) and publish it
+
+// The kernel's ONLY parameter: phases re-read it from the kernarg segment (scalar loads).
+struct FwParams {
+    FmpcDevModel M;
+    FwModel V;
+    int batch, max_iter, step_ld;
+    int mode;                       // FW_MODE_*
+    double kbar;
+    const double* x0; const double* x0p; const double* w; const double* zinit; const double* nu0;
+    double* zout; double* nuout; int* status; int* iters; double* step;
+    int zld;                        // doubles between the z rows of consecutive problems (T (n + m) unless fmpc_set_z_ld: flag mode only)
+    double* ws; size_t ws_stride;
+    double* sh_fac; double* sh_rs; int* sh_ok;     // shared (cold-start) factor owned by the handle
+    const double* cold;                             // cold-start constants (FwCold layout), k-dependent
+    // panel path (fmpc_kernel_panel.hip + fmpc_kernel_dz.hip ran before this launch): per problem ||r_p||^2 and a
+    // lower bound of rho^2 (gate), per (panel, stage, problem) the partial ||e||^2 (epsp).  Non-null: decide the
+    // step length of every problem first and solve only those whose decision is not clear-cut.
+    const double* gate; const double* epsp; int* handed;
+    const double* nuws;             // nu+ of the panel kernels, panel layout [panel][stage row][16]
+    double* u0out;                  // optional: the first move u0 = z(1:m) of every problem (README.md:589), written here too
+    // Newton budgets > 1 on the panel path run in two launches so that the few problems that go on are COMPACTED:
+    // pphase 1 decides every problem (step length of the panel step, then the exit test of the next iteration from
+    // rnp) and appends those that need this kernel to `list`; pphase 2 works through the list.  pphase 0: one launch
+    // (budget 1: decide, and redo the handed-over problems right away).
+    int pphase;
+    const double* rnp;              // per (panel, stage, problem): partial ||r_d||^2 at the new point (fmpc_cold_dz<true>)
+    int* list;                      // problem index, bit 30 set = handed over (to be redone from scratch)
+    int flags;                      // experiment switches (environment FMPC_WAVE_FLAGS); 0 in production
+    int* nflag;                             // flag mode behind the affine kernel: nflag[0] = running count of the problems the affine kernel has
+                                    // flagged since the handle exists, nflag[1] = the count the last flag-mode launch has dealt with,
+                                    // nflag[2] = its ticket.  Equal counts: nothing new is flagged, leave at once (two scalar loads, no store).
+                                    // Nothing depends on the order of host calls, so a recorded graph replays it as it stands
+    int u0_done;                    // panel path, first moves only: fmpc_cold_dz has written u0out itself (zout is a scratch
+                                    // array that only the problems redone here touch)
+};

@@ -39,10 +39,6 @@
 #define FW_VEC_STRIDE 840               // doubles per wave (nb*n <= 840 checked on the host)
 // ... followed by [cu | hc | wc | ubar] (4*mp doubles) for the cold step's epilogue: LDS reads do not queue behind
 // the global stores of the previous column block (vmcnt counts stores too)
-#define FW_MODE_NORMAL 0                // every problem factors its own Y
-#define FW_MODE_SHARED 1                // first Newton step from a cold start uses the handle's shared factor
-#define FW_MODE_EXPORT 2                // compute that shared factor (batch 1) and publish it
-
 typedef double d4 __attribute__((ext_vector_type(4)));
 #define MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 typedef __attribute__((address_space(3))) double* fw_lds_t;
@@ -143,40 +139,6 @@ __host__ __device__ static inline FwCold fw_cold_layout(int N, int mp) {
     return c;
 }
 
-// The kernel's ONLY parameter: phases re-read it from the kernarg segment (scalar loads).
-struct FwParams {
-    FmpcDevModel M;
-    FwModel V;
-    int batch, max_iter, step_ld;
-    int mode;                       // FW_MODE_*
-    double kbar;
-    const double* x0; const double* x0p; const double* w; const double* zinit; const double* nu0;
-    double* zout; double* nuout; int* status; int* iters; double* step;
-    int zld;                        // doubles between the z rows of consecutive problems (T (n + m) unless fmpc_set_z_ld: flag mode only)
-    double* ws; size_t ws_stride;
-    double* sh_fac; double* sh_rs; int* sh_ok;     // shared (cold-start) factor owned by the handle
-    const double* cold;                             // cold-start constants (FwCold layout), k-dependent
-    // panel path (fmpc_kernel_panel.hip + fmpc_kernel_dz.hip ran before this launch): per problem ||r_p||^2 and a
-    // lower bound of rho^2 (gate), per (panel, stage, problem) the partial ||e||^2 (epsp).  Non-null: decide the
-    // step length of every problem first and solve only those whose decision is not clear-cut.
-    const double* gate; const double* epsp; int* handed;
-    const double* nuws;             // nu+ of the panel kernels, panel layout [panel][stage row][16]
-    double* u0out;                  // optional: the first move u0 = z(1:m) of every problem (README.md:589), written here too
-    // Newton budgets > 1 on the panel path run in two launches so that the few problems that go on are COMPACTED:
-    // pphase 1 decides every problem (step length of the panel step, then the exit test of the next iteration from
-    // rnp) and appends those that need this kernel to `list`; pphase 2 works through the list.  pphase 0: one launch
-    // (budget 1: decide, and redo the handed-over problems right away).
-    int pphase;
-    const double* rnp;              // per (panel, stage, problem): partial ||r_d||^2 at the new point (fmpc_cold_dz<true>)
-    int* list;                      // problem index, bit 30 set = handed over (to be redone from scratch)
-    int flags;                      // experiment switches (environment FMPC_WAVE_FLAGS); 0 in production
-    int* nflag;                             // flag mode behind the affine kernel: nflag[0] = running count of the problems the affine kernel has
-                                    // flagged since the handle exists, nflag[1] = the count the last flag-mode launch has dealt with,
-                                    // nflag[2] = its ticket.  Equal counts: nothing new is flagged, leave at once (two scalar loads, no store).
-                                    // Nothing depends on the order of host calls, so a recorded graph replays it as it stands
-    int u0_done;                    // panel path, first moves only: fmpc_cold_dz has written u0out itself (zout is a scratch
-                                    // array that only the problems redone here touch)
-};
 #define FW_LIST_HANDED (1 << 30)
 #define FW_LIST_GENERAL (1 << 29)     // (= FT_LIST_GENERAL of fmpc_tiled.h)
 
@@ -2317,26 +2279,13 @@ hipError_t fmpc_wave_prepare(int n, size_t lds_bytes) {
     return hipFuncSetAttribute((const void*)fmpc_newton_wave<27, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
 }
 
-hipError_t fmpc_launch_wave(const FmpcDevModel& M, const FwModel& V, int batch, int grid,
-                            const double* x0, const double* x0p, const double* w, const double* zinit,
-                            const double* nu0, int max_iter, double kbar, double* zout, double* nuout,
-                            int* status, int* iters, double* step, int step_ld, double* ws,
-                            size_t ws_stride, size_t lds_bytes, hipStream_t stream,
-                            int mode, double* sh_fac, double* sh_rs, int* sh_ok, const double* cold,
-                            const double* gate, const double* epsp, int* handed, const double* nuws, double* u0out,
-                            int pphase, const double* rnp, int* list, int u0_done, int* nflag, int zld) {
-    if (M.n != 27) return hipErrorInvalidValue;
-    FwParams P;
-    P.zld = zld > 0 ? zld : M.T * (M.n + M.m);
-    P.gate = gate; P.epsp = epsp; P.handed = handed; P.nuws = nuws; P.u0out = u0out;
-    P.pphase = pphase; P.rnp = rnp; P.list = list; P.u0_done = u0_done; P.nflag = nflag;
+hipError_t fmpc_launch_wave(const FwParams& params, int grid, size_t lds_bytes, hipStream_t stream) {
+    if (params.M.n != 27) return hipErrorInvalidValue;
+    FwParams P = params;
     static const int env_flags = [] { const char* e = getenv("FMPC_WAVE_FLAGS"); return e && e[0] ? atoi(e) : 0; }();
     P.flags = env_flags;
-    if (pphase == 1) lds_bytes = 0;                  // the decide-only launch touches no LDS: cheap to place
-    P.M = M; P.V = V; P.batch = batch; P.max_iter = max_iter; P.step_ld = step_ld; P.mode = mode; P.sh_fac = sh_fac; P.sh_rs = sh_rs; P.sh_ok = sh_ok; P.cold = cold;
-    P.kbar = kbar; P.x0 = x0; P.x0p = x0p; P.w = w; P.zinit = zinit; P.nu0 = nu0; P.zout = zout;
-    P.nuout = nuout; P.status = status; P.iters = iters; P.step = step; P.ws = ws; P.ws_stride = ws_stride;
-    if (mode == FW_MODE_EXPORT) hipLaunchKernelGGL((fmpc_newton_wave<27, true>), dim3(grid), dim3(FW_THREADS), lds_bytes, stream, P);
+    if (P.pphase == 1) lds_bytes = 0;                // the decide-only launch touches no LDS: cheap to place
+    if (P.mode == FW_MODE_EXPORT) hipLaunchKernelGGL((fmpc_newton_wave<27, true>), dim3(grid), dim3(FW_THREADS), lds_bytes, stream, P);
     else hipLaunchKernelGGL((fmpc_newton_wave<27, false>), dim3(grid), dim3(FW_THREADS), lds_bytes, stream, P);
     return hipGetLastError();
 }

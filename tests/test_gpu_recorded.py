@@ -168,3 +168,50 @@ def test_recorded_explicit_start_budget_split_and_ramp_cold_form(pkg, gpu):
     assert all(torch.equal(a, b) for a, b in zip((z1, u1, u1b, s1, i1), ref1))
     assert torch.equal(u1, z1[:, :144])
     h1.close()
+
+
+def test_growth_under_capture_fails_cleanly(pkg, gpu):
+    """A solve that would have to grow the handle's buffers while its stream is being captured fails with FMPC_E_ALLOC before it
+    synchronises, releases or allocates anything: the allocation counter does not move, the capture ends cleanly, and the handle
+    solves the same batch eagerly afterwards exactly as a fresh handle does."""
+    import gc
+    import torch
+    dev = torch.device("cuda:0")
+    md = pkg.synthetic.make_model(27, 144, 30)
+    h = handle_from_model(pkg, md)
+
+    def inputs(batch, r):
+        d = pkg.synthetic.make_replay_batch(md, r=r, steps=batch)
+        return dict(x0=torch.from_numpy(d["x0"]).to(dev), x0p=torch.from_numpy(d["x0_pre"]).to(dev), nu0=torch.from_numpy(d["nu0"]).to(dev),
+                    z=torch.full((batch, h.nz), -3.0, dtype=torch.float64, device=dev),
+                    st=torch.full((batch,), -9, dtype=torch.int32, device=dev), it=torch.full((batch,), -9, dtype=torch.int32, device=dev))
+
+    def solve(hh, s):
+        hh.solve_device(s["x0"], s["x0p"], None, None, s["nu0"], 1, 1e-2, z_out=s["z"], status=s["st"], iters=s["it"])
+
+    solve(h, inputs(70, 3))                                  # warm: constants and the workspaces of 70 problems
+    torch.cuda.synchronize()
+    big = inputs(2000, 4)
+    gen = int(pkg._lib.load().fmpc_alloc_generation())
+    side = torch.cuda.Stream()
+    graph = torch.cuda.CUDAGraph()
+    gc.collect()
+    gc.disable()
+    try:
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(graph, stream=side):
+                with pytest.raises(pkg.FastMPCError) as ei:
+                    solve(h, big)
+    finally:
+        gc.enable()
+    torch.cuda.synchronize()
+    assert ei.value.code == pkg._lib.FMPC_E_ALLOC
+    assert int(pkg._lib.load().fmpc_alloc_generation()) == gen
+    solve(h, big)
+    fresh = handle_from_model(pkg, md)
+    ref = inputs(2000, 4)
+    solve(fresh, ref)
+    torch.cuda.synchronize()
+    assert torch.equal(big["z"], ref["z"]) and torch.equal(big["st"], ref["st"]) and torch.equal(big["it"], ref["it"])
+    fresh.close()
+    h.close()
