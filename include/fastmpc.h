@@ -48,7 +48,8 @@ extern "C" {
                                      fast_mpc_ineq_const.m:4-9, fast_mpc_objective.m:17-47,
                                      fast_mpc_init.m:13-14)                                    */
 #define FMPC_E_UNSUPPORTED   -3   /* valid for the reference, not implemented on the device
-                                     yet (n > 79, sizes beyond the LDS budget, dense R with n > 47) */
+                                     yet (fmpc_set_precision / fmpc_set_ramp at sizes no kernel
+                                     takes, e.g. ramp rows beyond the workspace budget)         */
 #define FMPC_E_NOT_PD_PHI    -4   /* chol(KKT_H) would fail (inf_newton_solver.m:24)          */
 #define FMPC_E_NOT_PD_SCHUR  -5   /* chol(Schur) would fail (inf_newton_solver.m:30)          */
 #define FMPC_E_HIP           -6   /* HIP runtime error                                         */
@@ -76,7 +77,7 @@ const char* fmpc_strerror(int code);
  *              R: the u block of Phi is then a dense m x m matrix per stage and Newton step (inf_newton_KKT_H.m:13), factored
  *              per stage (ft_dense_r) -- in LDS by the tiled kernel in fp64 (n <= 47, m (m + 1) / 2 + m (n + 2) doubles:
  *              m = 144 fits), in the workspace beyond; a generality path, ~13 x slower than a diagonal R.  Ramp rows
- *              (fmpc_set_ramp) need diagonal weights and n <= 64.
+ *              (fmpc_set_ramp) take any size and dense weights too (fmpc_newton_ramp_ws beyond n <= 64, diagonal weights).
  *              Not positive definite / not symmetric: FMPC_E_NOT_PD_PHI (the reference's chol(KKT_H) error,
  *              inf_newton_solver.m:24).
  *   q,r,qf     NULL = zeros (fast_mpc_objective.m:26-47).
@@ -276,7 +277,11 @@ int fmpc_loop_run_device(fmpc_handle h, int batch, int steps, const double* a, c
  * fmpc_set_ramp stores the bounds (m each, du_min < du_max) in the handle; fmpc_solve_ramp[_device] is
  * fmpc_solve[_device] with the extra per-problem input u_prev (m x batch).  The rows couple consecutive stages, so
  * Y = C Phi^-1 C' is dense across the horizon: this path factors a dense (T n)^2 matrix per problem and Newton
- * step (fmpc_kernel_ramp.hip); it needs diagonal Q, R, Qf like the other device paths.
+ * step.  n <= 64 with diagonal Q, R, Qf and B' plus its tiles in LDS: fmpc_newton_ramp (fmpc_kernel_ramp.hip, FMPC_PATH_RAMP).
+ * Any other (n, m, T) and any symmetric positive definite Q, Qf, R (the reference takes them, fast_mpc_objective.m:50-55):
+ * fmpc_newton_ramp_ws (fmpc_kernel_ramp_ws.hip, FMPC_PATH_RAMP_WS), the same solve with its operands in the HBM workspace --
+ * for a dense R the u-part of Phi is block-tridiagonal and is factored by block Cholesky over the stages on the matrix cores.
+ * A size and weight fallback without a speed claim; it takes the cold start itself (no Woodbury form).
  * From the COLD START (z_init == NULL, the reference loop's call: Fast_MPC2(..., x_init = []).mpc_fixed_log_newton(1, k))
  * only the ramp rows of stage 0 (u_0 - u_prev) depend on the problem -- every other ramp slack u_j - u_{j-1} is zero at the
  * mid-box start -- so the KKT matrix of the first Newton step is a CONSTANT matrix plus a diagonal term on the m entries of u_0,
@@ -284,10 +289,14 @@ int fmpc_loop_run_device(fmpc_handle h, int batch, int steps, const double* a, c
  * (handle, k, bounds) on the host (Woodbury form, fmpc_ramp_cold; fmpc_last_dual_form = 5): 0.8 instead of 18.7 MFLOP at
  * (27, 144, 10).  A budget n_newton > 1 continues with the dense factorisation from the iterate that step leaves.  Same
  * results to rounding (tests/test_gpu_ramp.py: both forms against the dense oracle); FMPC_NO_RAMP_COLD=1 at create time keeps
- * the general path.
- * FMPC_E_UNSUPPORTED: fmpc_set_ramp has not been called (or n > 64).
+ * the general path.  The Woodbury form needs what fmpc_newton_ramp needs (n <= 64, LDS, diagonal weights).
+ * FMPC_E_UNSUPPORTED: fmpc_set_ramp has not been called, or (fmpc_set_ramp) the workspace of one problem exceeds the 16 GB
+ * ramp budget or its 16 (T n + 1) doubles of LDS exceed 160 KiB.
  */
 int fmpc_set_ramp(fmpc_handle h, const double* du_min, const double* du_max);
+/* Cross-checks: enabled != 0 sends every ramp solve of the handle to fmpc_newton_ramp_ws, also where fmpc_newton_ramp would
+ * take it (cold start included); 0 restores the default choice. */
+int fmpc_set_ramp_workspace(fmpc_handle h, int enabled);
 int fmpc_solve_ramp(fmpc_handle h, int batch,
                     const double* x0, const double* x0_pre, const double* w, const double* u_prev,
                     const double* z_init, const double* nu0, int n_newton, double k,
@@ -342,7 +351,8 @@ int fmpc_set_precision(fmpc_handle h, int mode);
  * this handle took, and how many problems the panel kernel handed to the exact per-problem path because
  * their step-length / exit decision was not clear-cut.  Synchronises the device.
  *   path  0 generic kernel, 1 wave kernel (per-problem factor), 2 wave kernel (shared cold-start factor),
- *         3 panel kernel (+ exact path for `handed_over` problems), 4 ramp-rate kernel.
+ *         3 panel kernel (+ exact path for `handed_over` problems), 4 ramp-rate kernel, 7 ramp-rate kernel with its
+ *         operands in the workspace (any size, dense weights).
  */
 #define FMPC_PATH_GENERIC 0
 #define FMPC_PATH_WAVE    1
@@ -351,6 +361,7 @@ int fmpc_set_precision(fmpc_handle h, int mode);
 #define FMPC_PATH_RAMP    4
 #define FMPC_PATH_TILED   5   /* tiled kernel, fp64 factor */
 #define FMPC_PATH_TILED_F32 6 /* tiled kernel, fp32 factor + fp64 residuals */
+#define FMPC_PATH_RAMP_WS 7   /* ramp-rate kernel, workspace form (fmpc_newton_ramp_ws) */
 int fmpc_last_dispatch(fmpc_handle h, int* path, int* handed_over);
 /* Diagnostic: wavefronts per problem of the last launch of the tiled kernel on this handle (0 = none yet); the kernel runs with
  * 2, 4 or 8 depending on n, the precision and the batch (few problems: more wavefronts each). */

@@ -30,6 +30,7 @@ FMPC_PATH_PANEL = 3
 FMPC_PATH_RAMP = 4
 FMPC_PATH_TILED = 5
 FMPC_PATH_TILED_F32 = 6
+FMPC_PATH_RAMP_WS = 7
 FMPC_PREC_F64 = 0
 FMPC_PREC_F32_MIXED = 1
 
@@ -66,6 +67,7 @@ SIGNATURES = {
     "fmpc_solve_u0_device_ld": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [C.c_int, C.c_double] + [_vp] * 6 + [C.c_int, _vp]),
     "fmpc_solve_u0": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [C.c_int, C.c_double] + [_vp] * 4),
     "fmpc_set_ramp": (C.c_int, [_vp, _vp, _vp]),
+    "fmpc_set_ramp_workspace": (C.c_int, [_vp, C.c_int]),
     "fmpc_set_precision": (C.c_int, [_vp, C.c_int]),
     "fmpc_var_identify_device": (C.c_int, [C.c_int] * 4 + [_vp] * 5),
     "fmpc_solve_ramp": (C.c_int, [_vp, C.c_int] + [_vp] * 6 + [C.c_int, C.c_double] + [_vp] * 5),

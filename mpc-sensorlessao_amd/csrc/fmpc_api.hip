@@ -38,6 +38,15 @@ hipError_t fmpc_launch_ramp(const FmpcDevModel& M, const double* dumin, const do
                             const double* zinit, const double* nu0, int max_iter, double kbar, double* zout,
                             double* nuout, int* status, int* iters, double* step, int step_ld, double* ws,
                             size_t ws_stride, int threads, hipStream_t stream, int it0 = 0);
+// fmpc_kernel_ramp_ws.hip
+size_t fmpc_ramp_ws_lds_bytes(int n, int nb);
+size_t fmpc_ramp_ws_ws_doubles(int n, int m, int T, int nb, int dense_r);
+hipError_t fmpc_ramp_ws_prepare(size_t lds_bytes);
+hipError_t fmpc_launch_ramp_ws(const FmpcDevModel& M, const double* dumin, const double* dumax, int batch, int grid,
+                               const double* x0, const double* x0p, const double* w, const double* uprev,
+                               const double* zinit, const double* nu0, int max_iter, double kbar, double* zout,
+                               double* nuout, int* status, int* iters, double* step, int step_ld, double* ws,
+                               size_t ws_stride, hipStream_t stream);
 hipError_t fmpc_launch_generic(const FmpcDevModel& M, int batch, int grid, const double* x0,
                                const double* x0p, const double* w, const double* zinit,
                                const double* nu0, int max_iter, double kbar, double* zout,
@@ -153,6 +162,9 @@ struct fmpc_handle_s {
     // ramp-rate rows (VAR_1): bounds on the device, own workspace (dense Y per workgroup)
     DevBuf<double> ramp_du;      // [du_min | du_max], 2 m doubles; empty until fmpc_set_ramp
     DevBuf<double> ramp_ws;
+    // fmpc_newton_ramp (and the cold-start form) take the handle: n <= 64, their LDS fits, diagonal weights (fmpc_set_ramp);
+    // every other ramp solve, and every one after fmpc_set_ramp_workspace(h, 1), runs fmpc_newton_ramp_ws
+    int ramp_lds_ok = 0, ramp_force_ws = 0;
     // cold-start step with the ramp rows in its Woodbury form (fmpc_ramp_cold): constants per (handle, k, ramp bounds)
     std::vector<double> hm_dumin, hm_dumax;
     int rc_disabled = 0, rc_valid = 0, rc_failed = 0, rc_last = 0; double rc_k = 0.0, rc_failed_k = 0.0;
@@ -1867,17 +1879,28 @@ extern "C" int fmpc_last_dispatch(fmpc_handle h, int* path, int* handed_over) {
     return FMPC_OK;
 }
 
+// doubles (16 GB) of ramp workspace for all workgroups together
+#define FMPC_RAMP_WS_BUDGET ((size_t)2 << 30)
+
 extern "C" int fmpc_set_ramp(fmpc_handle h, const double* du_min, const double* du_max) {
     if (!h || !du_min || !du_max) return FMPC_E_NULL;
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
     for (int c = 0; c < h->m; ++c)
         if (!(du_min[c] < du_max[c])) return FMPC_E_DIM;
+    // fmpc_newton_ramp: n <= 64, B' and its tiles in LDS, diagonal weights.  Everything else: fmpc_newton_ramp_ws, whose LDS
+    // grows only with the 16 NTl doubles of the substitution vector and whose workspace (one problem) must fit the budget.
     const size_t lds = fmpc_ramp_lds_bytes(h->n, h->m, h->nb * h->n);
-    if (h->n > 64 || lds > FMPC_LDS_LIMIT || h->denseQ || h->denseR) return FMPC_E_UNSUPPORTED;   // (the ramp kernel keeps Q, Qf as diagonals)
+    const bool lds_ok = h->n <= 64 && lds <= FMPC_LDS_LIMIT && !h->denseQ && !h->denseR;
+    const size_t lds_ws = fmpc_ramp_ws_lds_bytes(h->n, h->nb);
+    const bool ws_ok = lds_ws <= FMPC_LDS_LIMIT && fmpc_ramp_ws_ws_doubles(h->n, h->m, h->T, h->nb, h->denseR) <= FMPC_RAMP_WS_BUDGET;
+    if (!lds_ok && !ws_ok) return FMPC_E_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(h->mu);
     if (!h->ramp_du) {
         if (h->ramp_du.alloc(2 * (size_t)h->m, nullptr) != FMPC_OK) return FMPC_E_ALLOC;
-        if (fmpc_ramp_prepare(lds) != hipSuccess) return FMPC_E_HIP;
+        if (lds_ok && fmpc_ramp_prepare(lds) != hipSuccess) return FMPC_E_HIP;
+        if (ws_ok && fmpc_ramp_ws_prepare(lds_ws) != hipSuccess) return FMPC_E_HIP;
+        h->ramp_lds_ok = lds_ok ? 1 : 0;
+        if (!ws_ok) h->ramp_force_ws = 0;
     } else if (hipDeviceSynchronize() != hipSuccess) {
         return FMPC_E_HIP;
     }
@@ -1885,6 +1908,18 @@ extern "C" int fmpc_set_ramp(fmpc_handle h, const double* du_min, const double* 
         hipMemcpy(h->ramp_du + h->m, du_max, h->m * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return FMPC_E_HIP;
     h->hm_dumin.assign(du_min, du_min + h->m); h->hm_dumax.assign(du_max, du_max + h->m);
     h->rc_valid = 0; h->rc_failed = 0;                              // (the constants of the cold-start form depend on the bounds)
+    return FMPC_OK;
+}
+
+extern "C" int fmpc_set_ramp_workspace(fmpc_handle h, int enabled) {
+    if (!h) return FMPC_E_NULL;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (enabled) {
+        const size_t lds_ws = fmpc_ramp_ws_lds_bytes(h->n, h->nb);
+        if (lds_ws > FMPC_LDS_LIMIT || fmpc_ramp_ws_ws_doubles(h->n, h->m, h->T, h->nb, h->denseR) > FMPC_RAMP_WS_BUDGET) return FMPC_E_UNSUPPORTED;
+        if (hipSetDevice(h->device) != hipSuccess || fmpc_ramp_ws_prepare(lds_ws) != hipSuccess) return FMPC_E_HIP;
+    }
+    h->ramp_force_ws = enabled ? 1 : 0;
     return FMPC_OK;
 }
 
@@ -1896,7 +1931,8 @@ static int fmpc_ensure_ramp_cold(fmpc_handle h, double k, hipStream_t stream) {
     if (h->rc_valid && h->rc_k == k) return FMPC_OK;
     if (h->rc_failed && h->rc_failed_k == k) return FMPC_E_UNSUPPORTED;
     const size_t lds = fmpc_ramp_cold_lds_bytes(h->n, h->m, h->T, h->nb);
-    if (lds > FMPC_LDS_LIMIT || h->n > 64) return FMPC_E_UNSUPPORTED;
+    // (the constants are built from the DIAGONALS hm_Q2, hm_Qf2, hm_R2: never for dense weights)
+    if (lds > FMPC_LDS_LIMIT || h->n > 64 || h->denseQ || h->denseR) return FMPC_E_UNSUPPORTED;
     FmpcRampColdIn In;
     In.n = h->n; In.m = h->m; In.T = h->T; In.nb = h->nb; In.var2 = h->var_order == 2 ? 1 : 0; In.has_xf = h->has_xf;
     In.bt = h->hm_bt.data(); In.a1 = h->hm_a1f.data(); In.a2 = h->hm_a2f.data();
@@ -1944,6 +1980,28 @@ static int fmpc_ensure_ramp_cold(fmpc_handle h, double k, hipStream_t stream) {
     return FMPC_OK;
 }
 
+// Every ramp solve fmpc_newton_ramp cannot take (n > 64, its LDS, dense Q / Qf / R; or fmpc_set_ramp_workspace): the workspace
+// kernel, cold start included (the Woodbury form of the first step is not used).  One 512-thread workgroup per problem in flight.
+static int fmpc_solve_ramp_ws(fmpc_handle h, const FmpcSolve& s, const double* u_prev, double* z_out) {
+    const int max_iter = s.n_newton > 0 ? s.n_newton : 1000;
+    const size_t stride = fmpc_ramp_ws_ws_doubles(h->n, h->m, h->T, h->nb, h->denseR);
+    int cap = h->num_cu;
+    if ((size_t)cap * stride > FMPC_RAMP_WS_BUDGET) cap = (int)(FMPC_RAMP_WS_BUDGET / stride);
+    if (cap < 1) return FMPC_E_ALLOC;
+    const int grid = s.batch < cap ? s.batch : cap;
+    { const int rw = h->ramp_ws.grow(stride * (size_t)grid, s.stream); if (rw != FMPC_OK) return rw; }
+    h->last_path = FMPC_PATH_RAMP_WS;
+    h->rc_last = 0;
+    if (fmpc_guard_begin(h, s.stream) != FMPC_OK) return FMPC_E_HIP;
+    hipError_t e = fmpc_launch_ramp_ws(h->dev, h->ramp_du, h->ramp_du + h->m, s.batch, grid, s.x0, s.x0_pre, s.w, u_prev, s.z_init,
+                                       s.nu0, max_iter, s.k, z_out, s.nu_out, s.status, s.iters, s.step, fmpc_step_ld(s.n_newton),
+                                       h->ramp_ws, stride, s.stream);
+    if (e == hipSuccess && s.u0_out)
+        e = fmpc_launch_unpack(h->n, h->m, h->T, s.batch, z_out, nullptr, nullptr, s.u0_out, s.stream);
+    fmpc_guard_end(h, s.stream);
+    return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
+}
+
 // fmpc_solve_ramp_device (u0_out == NULL) / fmpc_solve_ramp_u0_device: the first moves come from the cold-start kernel itself when
 // it takes the whole solve (budget 1), from the unpack kernel otherwise; z_out == NULL (first moves only) works in a scratch array
 // (s.ldz < 0: the handle's fmpc_set_z_ld value applies)
@@ -1962,12 +2020,14 @@ static int fmpc_solve_ramp_device_impl(fmpc_handle h, const FmpcSolve& s, const 
     std::lock_guard<std::mutex> lk(h->mu);
     const int max_iter = n_newton > 0 ? n_newton : 1000;
     const bool z_null = z_out == nullptr;
-    const bool cold_only = z_init == nullptr && max_iter == 1 && !h->rc_disabled;   // (the cold-start kernel then needs no z array at all)
+    const bool use_ws = !h->ramp_lds_ok || h->ramp_force_ws;
+    const bool cold_only = !use_ws && z_init == nullptr && max_iter == 1 && !h->rc_disabled;   // (the cold-start kernel then needs no z array at all)
     if (z_null && !cold_only) {
         const int rcz = fmpc_scratch_z(h, batch, stream);
         if (rcz != FMPC_OK) return rcz;
         z_out = h->zs;
     }
+    if (use_ws) return fmpc_solve_ramp_ws(h, s, u_prev, z_out);
     // one workgroup per problem in flight; the workspace holds the dense Y of each (nb n)^2 doubles
     const size_t stride = fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb);
     // up to one problem per CU: 512-thread workgroups (latency: 0.61 instead of 0.82 ms per Newton step at n = 27,

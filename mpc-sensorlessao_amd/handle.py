@@ -87,11 +87,20 @@ class FastMPCHandle:
     # ------------------------------------------------------------------ host buffers
     def set_ramp(self, du_min, du_max):
         """Ramp-rate bounds of the VAR_1 variant (VAR_1/fast_mpc_ineq_const.m:58-76): fmpc_set_ramp.
-        Afterwards `solve(..., u_prev=...)` / `solve_device(..., u_prev=...)` add the ramp rows."""
+        Afterwards `solve(..., u_prev=...)` / `solve_device(..., u_prev=...)` add the ramp rows.  Any (n, m, T) and any
+        symmetric positive definite Q, Qf, R: n <= 64 with diagonal weights (and B' in LDS) runs fmpc_newton_ramp
+        (FMPC_PATH_RAMP), everything else the workspace kernel fmpc_newton_ramp_ws (FMPC_PATH_RAMP_WS)."""
         du_min = _f64(du_min, (self.m,), "du_min"); du_max = _f64(du_max, (self.m,), "du_max")
         rc = self._lib.fmpc_set_ramp(self._h, _ptr(du_min), _ptr(du_max))
         if rc != _lib.FMPC_OK:
             raise FastMPCError(rc, "fmpc_set_ramp")
+
+    def set_ramp_workspace(self, enabled):
+        """fmpc_set_ramp_workspace: True sends every ramp solve to the workspace kernel (FMPC_PATH_RAMP_WS), also sizes the
+        LDS kernel takes (cross-checks); False restores the default choice."""
+        rc = self._lib.fmpc_set_ramp_workspace(self._h, int(bool(enabled)))
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_set_ramp_workspace")
 
     def set_precision(self, mode):
         """fmpc_set_precision: 'f64' or 'f32' (fp32 factor + fp64 residuals, BASELINE configs[4])."""
