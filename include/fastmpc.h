@@ -277,9 +277,9 @@ int fmpc_loop_run_device(fmpc_handle h, int batch, int steps, const double* a, c
  * fmpc_set_ramp stores the bounds (m each, du_min < du_max) in the handle; fmpc_solve_ramp[_device] is
  * fmpc_solve[_device] with the extra per-problem input u_prev (m x batch).  The rows couple consecutive stages, so
  * Y = C Phi^-1 C' is dense across the horizon: this path factors a dense (T n)^2 matrix per problem and Newton
- * step.  n <= 64 with diagonal Q, R, Qf and B' plus its tiles in LDS: fmpc_newton_ramp (fmpc_kernel_ramp.hip, FMPC_PATH_RAMP).
- * Any other (n, m, T) and any symmetric positive definite Q, Qf, R (the reference takes them, fast_mpc_objective.m:50-55):
- * fmpc_newton_ramp_ws (fmpc_kernel_ramp_ws.hip, FMPC_PATH_RAMP_WS), the same solve with its operands in the HBM workspace --
+ * step.  Both Newton kernels are one body in fmpc_kernel_ramp.hip.  n <= 64 with diagonal Q, R, Qf and B' plus its tiles in
+ * LDS: fmpc_newton_ramp (FMPC_PATH_RAMP).  Any other (n, m, T) and any symmetric positive definite Q, Qf, R (the reference
+ * takes them, fast_mpc_objective.m:50-55): fmpc_newton_ramp_ws (FMPC_PATH_RAMP_WS), the same solve with its operands in the HBM workspace --
  * for a dense R the u-part of Phi is block-tridiagonal and is factored by block Cholesky over the stages on the matrix cores.
  * A size and weight fallback without a speed claim; it takes the cold start itself (no Woodbury form).
  * From the COLD START (z_init == NULL, the reference loop's call: Fast_MPC2(..., x_init = []).mpc_fixed_log_newton(1, k))

@@ -29,24 +29,11 @@ extern "C" unsigned long long fmpc_alloc_generation(void) { return fmpc_alloc_ge
 size_t fmpc_generic_lds_bytes(int n, int m);
 size_t fmpc_generic_big_lds_bytes(int n, int m);
 hipError_t fmpc_generic_prepare(size_t lds_bytes, int big);
-// fmpc_kernel_ramp.hip
-size_t fmpc_ramp_lds_bytes(int n, int m, int nbn);
-size_t fmpc_ramp_ws_doubles(int n, int m, int T, int nb);
-hipError_t fmpc_ramp_prepare(size_t lds_bytes);
-hipError_t fmpc_launch_ramp(const FmpcDevModel& M, const double* dumin, const double* dumax, int batch, int grid,
-                            const double* x0, const double* x0p, const double* w, const double* uprev,
-                            const double* zinit, const double* nu0, int max_iter, double kbar, double* zout,
-                            double* nuout, int* status, int* iters, double* step, int step_ld, double* ws,
-                            size_t ws_stride, int threads, hipStream_t stream, int it0 = 0);
-// fmpc_kernel_ramp_ws.hip
-size_t fmpc_ramp_ws_lds_bytes(int n, int nb);
-size_t fmpc_ramp_ws_ws_doubles(int n, int m, int T, int nb, int dense_r);
-hipError_t fmpc_ramp_ws_prepare(size_t lds_bytes);
-hipError_t fmpc_launch_ramp_ws(const FmpcDevModel& M, const double* dumin, const double* dumax, int batch, int grid,
-                               const double* x0, const double* x0p, const double* w, const double* uprev,
-                               const double* zinit, const double* nu0, int max_iter, double kbar, double* zout,
-                               double* nuout, int* status, int* iters, double* step, int step_ld, double* ws,
-                               size_t ws_stride, hipStream_t stream);
+// fmpc_kernel_ramp.hip (ws = 0: fmpc_newton_ramp, 1: fmpc_newton_ramp_ws)
+size_t fmpc_ramp_lds_bytes(int n, int m, int nb, int ws);
+size_t fmpc_ramp_ws_doubles(int n, int m, int T, int nb, int ws, int dense_r);
+hipError_t fmpc_ramp_prepare(int ws, size_t lds_bytes);
+hipError_t fmpc_launch_ramp(const FrParams& P, int grid, hipStream_t stream);
 hipError_t fmpc_launch_generic(const FmpcDevModel& M, int batch, int grid, const double* x0,
                                const double* x0p, const double* w, const double* zinit,
                                const double* nu0, int max_iter, double kbar, double* zout,
@@ -1882,6 +1869,14 @@ extern "C" int fmpc_last_dispatch(fmpc_handle h, int* path, int* handed_over) {
 // doubles (16 GB) of ramp workspace for all workgroups together
 #define FMPC_RAMP_WS_BUDGET ((size_t)2 << 30)
 
+// The historical LDS bound that admits a handle to fmpc_newton_ramp (it still counts a 1024-thread variant and LDS scratch the
+// kernel no longer has); kept as it is so that every (n, m, T) stays on the path it has always taken.
+static size_t fmpc_ramp_lds_admit_bytes(int n, int m, int nbn) {
+    const size_t ntl = ((size_t)nbn + 1 + 15) / 16;
+    const size_t d = (size_t)m * n + 2 * (size_t)n * (n + 1) + 2 * (size_t)n + 16 * 64 + 16 + (16 * 17 + 16 * ntl + 16 * 16 + 16);
+    return d * sizeof(double);
+}
+
 extern "C" int fmpc_set_ramp(fmpc_handle h, const double* du_min, const double* du_max) {
     if (!h || !du_min || !du_max) return FMPC_E_NULL;
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
@@ -1889,16 +1884,15 @@ extern "C" int fmpc_set_ramp(fmpc_handle h, const double* du_min, const double* 
         if (!(du_min[c] < du_max[c])) return FMPC_E_DIM;
     // fmpc_newton_ramp: n <= 64, B' and its tiles in LDS, diagonal weights.  Everything else: fmpc_newton_ramp_ws, whose LDS
     // grows only with the 16 NTl doubles of the substitution vector and whose workspace (one problem) must fit the budget.
-    const size_t lds = fmpc_ramp_lds_bytes(h->n, h->m, h->nb * h->n);
-    const bool lds_ok = h->n <= 64 && lds <= FMPC_LDS_LIMIT && !h->denseQ && !h->denseR;
-    const size_t lds_ws = fmpc_ramp_ws_lds_bytes(h->n, h->nb);
-    const bool ws_ok = lds_ws <= FMPC_LDS_LIMIT && fmpc_ramp_ws_ws_doubles(h->n, h->m, h->T, h->nb, h->denseR) <= FMPC_RAMP_WS_BUDGET;
+    const bool lds_ok = h->n <= 64 && fmpc_ramp_lds_admit_bytes(h->n, h->m, h->nb * h->n) <= FMPC_LDS_LIMIT && !h->denseQ && !h->denseR;
+    const size_t lds_ws = fmpc_ramp_lds_bytes(h->n, h->m, h->nb, 1);
+    const bool ws_ok = lds_ws <= FMPC_LDS_LIMIT && fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb, 1, h->denseR) <= FMPC_RAMP_WS_BUDGET;
     if (!lds_ok && !ws_ok) return FMPC_E_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(h->mu);
     if (!h->ramp_du) {
         if (h->ramp_du.alloc(2 * (size_t)h->m, nullptr) != FMPC_OK) return FMPC_E_ALLOC;
-        if (lds_ok && fmpc_ramp_prepare(lds) != hipSuccess) return FMPC_E_HIP;
-        if (ws_ok && fmpc_ramp_ws_prepare(lds_ws) != hipSuccess) return FMPC_E_HIP;
+        if (lds_ok && fmpc_ramp_prepare(0, fmpc_ramp_lds_bytes(h->n, h->m, h->nb, 0)) != hipSuccess) return FMPC_E_HIP;
+        if (ws_ok && fmpc_ramp_prepare(1, lds_ws) != hipSuccess) return FMPC_E_HIP;
         h->ramp_lds_ok = lds_ok ? 1 : 0;
         if (!ws_ok) h->ramp_force_ws = 0;
     } else if (hipDeviceSynchronize() != hipSuccess) {
@@ -1915,9 +1909,9 @@ extern "C" int fmpc_set_ramp_workspace(fmpc_handle h, int enabled) {
     if (!h) return FMPC_E_NULL;
     std::lock_guard<std::mutex> lk(h->mu);
     if (enabled) {
-        const size_t lds_ws = fmpc_ramp_ws_lds_bytes(h->n, h->nb);
-        if (lds_ws > FMPC_LDS_LIMIT || fmpc_ramp_ws_ws_doubles(h->n, h->m, h->T, h->nb, h->denseR) > FMPC_RAMP_WS_BUDGET) return FMPC_E_UNSUPPORTED;
-        if (hipSetDevice(h->device) != hipSuccess || fmpc_ramp_ws_prepare(lds_ws) != hipSuccess) return FMPC_E_HIP;
+        const size_t lds_ws = fmpc_ramp_lds_bytes(h->n, h->m, h->nb, 1);
+        if (lds_ws > FMPC_LDS_LIMIT || fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb, 1, h->denseR) > FMPC_RAMP_WS_BUDGET) return FMPC_E_UNSUPPORTED;
+        if (hipSetDevice(h->device) != hipSuccess || fmpc_ramp_prepare(1, lds_ws) != hipSuccess) return FMPC_E_HIP;
     }
     h->ramp_force_ws = enabled ? 1 : 0;
     return FMPC_OK;
@@ -1980,131 +1974,123 @@ static int fmpc_ensure_ramp_cold(fmpc_handle h, double k, hipStream_t stream) {
     return FMPC_OK;
 }
 
-// Every ramp solve fmpc_newton_ramp cannot take (n > 64, its LDS, dense Q / Qf / R; or fmpc_set_ramp_workspace): the workspace
-// kernel, cold start included (the Woodbury form of the first step is not used).  One 512-thread workgroup per problem in flight.
-static int fmpc_solve_ramp_ws(fmpc_handle h, const FmpcSolve& s, const double* u_prev, double* z_out) {
-    const int max_iter = s.n_newton > 0 ? s.n_newton : 1000;
-    const size_t stride = fmpc_ramp_ws_ws_doubles(h->n, h->m, h->T, h->nb, h->denseR);
+// The launch parameters of a ramp solve s (u_prev: the previous moves); form ws, workspace stride per workgroup.
+static FrParams fmpc_ramp_params(fmpc_handle h, const FmpcSolve& s, const double* u_prev, bool ws, size_t stride) {
+    FrParams P;
+    P.M = h->dev; P.dumin = h->ramp_du; P.dumax = h->ramp_du + h->m;
+    P.batch = s.batch; P.max_iter = fmpc_max_iter(s); P.step_ld = fmpc_step_ld(s.n_newton); P.ws = ws ? 1 : 0; P.it0 = 0; P.kbar = s.k;
+    P.x0 = s.x0; P.x0p = s.x0_pre; P.w = s.w; P.uprev = u_prev; P.zinit = s.z_init; P.nu0 = s.nu0;
+    P.zout = s.z_out; P.nuout = s.nu_out; P.status = s.status; P.iters = s.iters; P.step = s.step;
+    P.ws_buf = h->ramp_ws; P.ws_stride = stride;
+    return P;
+}
+
+// One launch of fmpc_newton_ramp (ws = false) or fmpc_newton_ramp_ws from s.z_init or the mid-box start, then the first moves
+// by the unpack kernel if they are asked for.
+static int fmpc_ramp_path_newton(fmpc_handle h, const FmpcSolve& s, const double* u_prev, bool ws, size_t stride, int grid) {
+    { const int rw = h->ramp_ws.grow(stride * (size_t)grid, s.stream); if (rw != FMPC_OK) return rw; }
+    h->last_path = ws ? FMPC_PATH_RAMP_WS : FMPC_PATH_RAMP;
+    h->rc_last = 0;
+    hipError_t e = fmpc_launch_ramp(fmpc_ramp_params(h, s, u_prev, ws, stride), grid, s.stream);
+    if (e == hipSuccess && s.u0_out)
+        e = fmpc_launch_unpack(h->n, h->m, h->T, s.batch, s.z_out, nullptr, nullptr, s.u0_out, s.stream);
+    return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
+}
+
+// Cold start on fmpc_newton_ramp's domain: the first Newton step in its Woodbury form (fmpc_ramp_cold, one m x m factorisation
+// per problem); a budget > 1 continues with fmpc_newton_ramp from the iterate that step leaves (it0 = 1).  The first moves come
+// from the cold-start kernel itself when it takes the whole solve (budget 1; s.z_out may then be NULL), from the unpack kernel
+// otherwise.  FMPC_E_UNSUPPORTED: the form is not available, nothing is enqueued.
+static int fmpc_ramp_path_cold(fmpc_handle h, const FmpcSolve& s, const double* u_prev, size_t stride, int grid) {
+    const int rcc = fmpc_ensure_ramp_cold(h, s.k, s.stream);
+    if (rcc != FMPC_OK) return rcc;
+    const int batch = s.batch, max_iter = fmpc_max_iter(s);
+    const size_t cstride = fmpc_ramp_cold_ws_doubles(h->m);
+    const int cgrid = batch < h->num_cu ? batch : h->num_cu;
+    if (cstride * (size_t)cgrid > h->rc_ws.cap) {
+        size_t want = cstride * (size_t)(batch < h->num_cu ? (batch < 16 ? 16 : batch) : h->num_cu);
+        if (want > cstride * (size_t)h->num_cu) want = cstride * (size_t)h->num_cu;
+        const int rcw = h->rc_ws.alloc(want, s.stream);
+        if (rcw != FMPC_OK) return rcw;
+    }
+    // the continuation reads nu, status and iters of the first step: scratch arrays where the caller passes none
+    double* nu_first = s.nu_out;
+    int* st_first = s.status; int* it_first = s.iters;
+    if (max_iter > 1 && (!s.nu_out || !s.status || !s.iters)) {
+        if ((size_t)batch > h->rc_cap) {
+            h->rc_cap = 0;
+            if (h->rc_nu.alloc((size_t)batch * h->nb * h->n, s.stream) != FMPC_OK ||
+                h->rc_si.alloc(2 * (size_t)batch, s.stream) != FMPC_OK) return FMPC_E_ALLOC;
+            h->rc_cap = batch;
+        }
+        if (!s.nu_out) nu_first = h->rc_nu;
+        if (!s.status) st_first = h->rc_si;
+        if (!s.iters) it_first = h->rc_si + batch;
+    }
+    if (max_iter > 1) { const int rw = h->ramp_ws.grow(stride * (size_t)grid, s.stream); if (rw != FMPC_OK) return rw; }
+    FrColdParams P = h->rc_P;
+    P.batch = batch; P.x0 = s.x0; P.x0p = s.x0_pre; P.w = s.w; P.uprev = u_prev; P.nu0 = s.nu0;
+    P.zout = s.z_out; P.nuout = nu_first; P.u0out = max_iter == 1 ? s.u0_out : nullptr; P.status = st_first; P.iters = it_first; P.step = s.step;
+    P.step_ld = fmpc_step_ld(s.n_newton); P.ws = h->rc_ws; P.ws_stride = cstride;
+    hipError_t e = fmpc_launch_ramp_cold(P, cgrid, s.stream);
+    h->rc_last = 1;
+    if (e == hipSuccess && max_iter > 1) {
+        FrParams Q = fmpc_ramp_params(h, s, u_prev, false, stride);
+        Q.zinit = s.z_out; Q.nu0 = nu_first; Q.status = st_first; Q.iters = it_first; Q.it0 = 1;
+        e = fmpc_launch_ramp(Q, grid, s.stream);
+    }
+    if (e == hipSuccess && max_iter > 1 && s.u0_out)
+        e = fmpc_launch_unpack(h->n, h->m, h->T, batch, s.z_out, nullptr, nullptr, s.u0_out, s.stream);
+    return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
+}
+
+// Selects the ramp path: fmpc_newton_ramp on its domain (n <= 64, its LDS fits, diagonal weights; cold start: the Woodbury form
+// first), fmpc_newton_ramp_ws for everything else and after fmpc_set_ramp_workspace(h, 1).  Caller holds h->mu.
+static int fmpc_solve_ramp_device_inner(fmpc_handle h, FmpcSolve& s, const double* u_prev) {
+    const bool ws = !h->ramp_lds_ok || h->ramp_force_ws;
+    const bool cold_only = !ws && !s.z_init && fmpc_max_iter(s) == 1 && !h->rc_disabled;   // (the cold-start kernel then needs no z array at all)
+    if (!s.z_out && !cold_only) {                                   // first moves only: the iterate goes to a scratch array
+        const int rcz = fmpc_scratch_z(h, s.batch, s.stream);
+        if (rcz != FMPC_OK) return rcz;
+        s.z_out = h->zs;
+    }
+    // one workgroup per problem in flight, at most one per CU; the workspace of all of them within the budget
+    const size_t stride = fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb, ws, h->denseR);
     int cap = h->num_cu;
     if ((size_t)cap * stride > FMPC_RAMP_WS_BUDGET) cap = (int)(FMPC_RAMP_WS_BUDGET / stride);
     if (cap < 1) return FMPC_E_ALLOC;
     const int grid = s.batch < cap ? s.batch : cap;
-    { const int rw = h->ramp_ws.grow(stride * (size_t)grid, s.stream); if (rw != FMPC_OK) return rw; }
-    h->last_path = FMPC_PATH_RAMP_WS;
-    h->rc_last = 0;
-    if (fmpc_guard_begin(h, s.stream) != FMPC_OK) return FMPC_E_HIP;
-    hipError_t e = fmpc_launch_ramp_ws(h->dev, h->ramp_du, h->ramp_du + h->m, s.batch, grid, s.x0, s.x0_pre, s.w, u_prev, s.z_init,
-                                       s.nu0, max_iter, s.k, z_out, s.nu_out, s.status, s.iters, s.step, fmpc_step_ld(s.n_newton),
-                                       h->ramp_ws, stride, s.stream);
-    if (e == hipSuccess && s.u0_out)
-        e = fmpc_launch_unpack(h->n, h->m, h->T, s.batch, z_out, nullptr, nullptr, s.u0_out, s.stream);
-    fmpc_guard_end(h, s.stream);
-    return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
+    if (!ws) {
+        h->last_path = FMPC_PATH_RAMP;
+        h->rc_last = 0;
+        if (!s.z_init) {
+            const int rc = fmpc_ramp_path_cold(h, s, u_prev, stride, grid);
+            if (rc != FMPC_E_UNSUPPORTED) return rc;
+            if (!s.z_out) {                                         // the cold-start form is not available after all: scratch iterate
+                const int rcz = fmpc_scratch_z(h, s.batch, s.stream);
+                if (rcz != FMPC_OK) return rcz;
+                s.z_out = h->zs;
+            }
+        }
+    }
+    return fmpc_ramp_path_newton(h, s, u_prev, ws, stride, grid);
 }
 
-// fmpc_solve_ramp_device (u0_out == NULL) / fmpc_solve_ramp_u0_device: the first moves come from the cold-start kernel itself when
-// it takes the whole solve (budget 1), from the unpack kernel otherwise; z_out == NULL (first moves only) works in a scratch array
+// fmpc_solve_ramp_device (u0_out == NULL) / fmpc_solve_ramp_u0_device; z_out == NULL: first moves only
 // (s.ldz < 0: the handle's fmpc_set_z_ld value applies)
-static int fmpc_solve_ramp_device_impl(fmpc_handle h, const FmpcSolve& s, const double* u_prev) {
-    const int batch = s.batch, n_newton = s.n_newton;
-    const double k = s.k;
-    const double* x0 = s.x0; const double* x0_pre = s.x0_pre; const double* w = s.w; const double* z_init = s.z_init; const double* nu0 = s.nu0;
-    double* z_out = s.z_out; double* nu_out = s.nu_out; int* status = s.status; int* iters = s.iters; double* step = s.step; double* u0_out = s.u0_out;
-    const hipStream_t stream = s.stream;
-    if (!h || !x0 || (!z_out && !u0_out) || !u_prev) return FMPC_E_NULL;
+static int fmpc_solve_ramp_device_impl(fmpc_handle h, FmpcSolve s, const double* u_prev) {
+    if (!h || !s.x0 || (!s.z_out && !s.u0_out) || !u_prev) return FMPC_E_NULL;
     if (!h->ramp_du) return FMPC_E_UNSUPPORTED;                    // fmpc_set_ramp first
     if ((s.ldz < 0 ? h->z_ld : s.ldz) > h->T * (h->n + h->m)) return FMPC_E_UNSUPPORTED;   // padded z rows: the cold-start affine step only
-    if (batch < 0) return FMPC_E_DIM;
-    if (batch == 0) return FMPC_OK;
+    if (s.batch < 0) return FMPC_E_DIM;
+    if (s.batch == 0) return FMPC_OK;
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
     std::lock_guard<std::mutex> lk(h->mu);
-    const int max_iter = n_newton > 0 ? n_newton : 1000;
-    const bool z_null = z_out == nullptr;
-    const bool use_ws = !h->ramp_lds_ok || h->ramp_force_ws;
-    const bool cold_only = !use_ws && z_init == nullptr && max_iter == 1 && !h->rc_disabled;   // (the cold-start kernel then needs no z array at all)
-    if (z_null && !cold_only) {
-        const int rcz = fmpc_scratch_z(h, batch, stream);
-        if (rcz != FMPC_OK) return rcz;
-        z_out = h->zs;
-    }
-    if (use_ws) return fmpc_solve_ramp_ws(h, s, u_prev, z_out);
-    // one workgroup per problem in flight; the workspace holds the dense Y of each (nb n)^2 doubles
-    const size_t stride = fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb);
-    // up to one problem per CU: 512-thread workgroups (latency: 0.61 instead of 0.82 ms per Newton step at n = 27,
-    // m = 144, T = 10); beyond: 256-thread workgroups, 3 per CU (throughput: 4.3e5 instead of 3.6e5 problems/s)
-    int threads = 512;      // (8 wavefronts per problem, one problem per CU: faster than 3 x 256 threads per CU at every batch size)
-    { const char* e = getenv("FMPC_RAMP_THREADS"); if (e && e[0]) { const int t = atoi(e); if (t == 256 || t == 512 || t == 1024) threads = t; } }   // experiments
-    int cap = (threads == 256 ? 3 : 1) * h->num_cu;
-    const size_t budget = (size_t)2 << 30;                         // doubles (16 GB) for all workgroups together
-    if ((size_t)cap * stride > budget) cap = (int)(budget / stride);
-    if (cap < 1) return FMPC_E_ALLOC;
-    const int grid = batch < cap ? batch : cap;
-    // (the cold-start form with a budget of 1 never needs it)
-    auto ensure_general_ws = [&]() -> int { return h->ramp_ws.grow(stride * (size_t)grid, stream); };
-    h->last_path = FMPC_PATH_RAMP;
-    h->rc_last = 0;
-    // Cold start: the first Newton step in its Woodbury form (one m x m factorisation per problem, fmpc_ramp_cold); a budget > 1
-    // continues with the general kernel from the iterate that step leaves (it0 = 1).
-    if (z_init == nullptr) {
-        const int rcc = fmpc_ensure_ramp_cold(h, k, stream);
-        if (rcc != FMPC_OK && rcc != FMPC_E_UNSUPPORTED) return rcc;
-        if (rcc == FMPC_OK) {
-            const size_t cstride = fmpc_ramp_cold_ws_doubles(h->m);
-            const int cgrid = batch < h->num_cu ? batch : h->num_cu;
-            if (cstride * (size_t)cgrid > h->rc_ws.cap) {
-                size_t want = cstride * (size_t)(batch < h->num_cu ? (batch < 16 ? 16 : batch) : h->num_cu);
-                if (want > cstride * (size_t)h->num_cu) want = cstride * (size_t)h->num_cu;
-                const int rcw = h->rc_ws.alloc(want, stream);
-                if (rcw != FMPC_OK) return rcw;
-            }
-            double* nu_first = nu_out;
-            int* st_first = status; int* it_first = iters;
-            if (max_iter > 1 && (!nu_out || !status || !iters)) {
-                if ((size_t)batch > h->rc_cap) {
-                    h->rc_cap = 0;
-                    if (h->rc_nu.alloc((size_t)batch * h->nb * h->n, stream) != FMPC_OK ||
-                        h->rc_si.alloc(2 * (size_t)batch, stream) != FMPC_OK) return FMPC_E_ALLOC;
-                    h->rc_cap = batch;
-                }
-                if (!nu_out) nu_first = h->rc_nu;
-                if (!status) st_first = h->rc_si;
-                if (!iters) it_first = h->rc_si + batch;
-            }
-            if (max_iter > 1) { const int rw = ensure_general_ws(); if (rw != FMPC_OK) return rw; }
-            FrColdParams P = h->rc_P;
-            P.batch = batch; P.x0 = x0; P.x0p = x0_pre; P.w = w; P.uprev = u_prev; P.nu0 = nu0;
-            if (max_iter > 1 && !z_out) {                            // (cold_only was assumed but the budget is larger: cannot happen; guard)
-                return FMPC_E_NULL;
-            }
-            P.zout = z_out; P.nuout = nu_first; P.u0out = max_iter == 1 ? u0_out : nullptr; P.status = st_first; P.iters = it_first; P.step = step;
-            P.step_ld = fmpc_step_ld(n_newton); P.ws = h->rc_ws; P.ws_stride = cstride;
-            if (fmpc_guard_begin(h, stream) != FMPC_OK) return FMPC_E_HIP;
-            hipError_t e = fmpc_launch_ramp_cold(P, cgrid, stream);
-            h->rc_last = 1;
-            if (e == hipSuccess && max_iter > 1)
-                e = fmpc_launch_ramp(h->dev, h->ramp_du, h->ramp_du + h->m, batch, grid, x0, x0_pre, w, u_prev, z_out,
-                                     nu_first, max_iter, k, z_out, nu_out, st_first, it_first, step, fmpc_step_ld(n_newton),
-                                     h->ramp_ws, stride, threads, stream, 1);
-            if (e == hipSuccess && max_iter > 1 && u0_out)
-                e = fmpc_launch_unpack(h->n, h->m, h->T, batch, z_out, nullptr, nullptr, u0_out, stream);
-            fmpc_guard_end(h, stream);
-            return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
-        }
-        if (z_null && !z_out) {                                      // the cold-start form is not available after all: scratch iterate
-            const int rcz = fmpc_scratch_z(h, batch, stream);
-            if (rcz != FMPC_OK) return rcz;
-            z_out = h->zs;
-        }
-    }
-    { const int rw = ensure_general_ws(); if (rw != FMPC_OK) return rw; }
-    if (fmpc_guard_begin(h, stream) != FMPC_OK) return FMPC_E_HIP;
-    hipError_t e = fmpc_launch_ramp(h->dev, h->ramp_du, h->ramp_du + h->m, batch, grid, x0, x0_pre, w, u_prev, z_init,
-                                    nu0, max_iter, k, z_out, nu_out, status, iters, step, fmpc_step_ld(n_newton),
-                                    h->ramp_ws, stride, threads, stream);
-    if (e == hipSuccess && u0_out)
-        e = fmpc_launch_unpack(h->n, h->m, h->T, batch, z_out, nullptr, nullptr, u0_out, stream);
-    fmpc_guard_end(h, stream);
-    return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
+    int rc = fmpc_guard_begin(h, s.stream);
+    if (rc != FMPC_OK) return rc;
+    rc = fmpc_solve_ramp_device_inner(h, s, u_prev);
+    fmpc_guard_end(h, s.stream);
+    return rc;
 }
 
 extern "C" int fmpc_solve_ramp_device(fmpc_handle h, int batch,

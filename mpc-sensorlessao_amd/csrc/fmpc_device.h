@@ -61,6 +61,20 @@ __host__ __device__ static inline FmpcWsLayout fmpc_ws_layout(int n, int m, int 
     return L;
 }
 
+// Launch parameters of the ramp-rate Newton kernels (fmpc_kernel_ramp.hip); fmpc_launch_ramp unpacks them into the arguments of
+// the kernel that ws selects.
+struct FrParams {
+    FmpcDevModel M;
+    const double* dumin; const double* dumax;
+    int batch, max_iter, step_ld;
+    int ws;                         // 0: fmpc_newton_ramp (B' in LDS), 1: fmpc_newton_ramp_ws (operands in the workspace)
+    int it0;                        // fmpc_newton_ramp only: 1 = the continuation behind fmpc_ramp_cold
+    double kbar;
+    const double* x0; const double* x0p; const double* w; const double* uprev; const double* zinit; const double* nu0;
+    double* zout; double* nuout; int* status; int* iters; double* step;
+    double* ws_buf; size_t ws_stride;                // per workgroup: fr_ws_layout
+};
+
 // Extras of the one-wave-per-problem kernel (fmpc_kernel_wave.hip), device pointers.
 struct FwModel {
     int mp;                 // m rounded up to a multiple of 4 (MFMA k-steps)

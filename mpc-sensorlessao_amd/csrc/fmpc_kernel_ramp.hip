@@ -1,4 +1,4 @@
-// fastMPC Newton kernel WITH ramp-rate rows (the VAR_1 variant of the reference) for gfx950: any (n <= 64, m, T).
+// fastMPC Newton kernels WITH ramp-rate rows (the VAR_1 variant of the reference) for gfx950.
 //
 // Reference: Fast_MPC/VAR_1/fast_mpc_ineq_const.m:58-76 appends, per stage j, the rows
 //      u_j - u_{j-1} <= du_max ,  -(u_j - u_{j-1}) <= -du_min          (u_{-1} = u_prev, moved into h: :70-72)
@@ -11,16 +11,31 @@
 //     (R diagonal, as on the other device paths); the x-part stays 2Q;
 //   * Y = C Phi^-1 C' is therefore DENSE across stages (SURVEY.md §8 a6'):  Y_IJ = Yx_IJ + B diag(g^{IJ}) B' with
 //     g^{IJ}_c = (Phi_u,c^-1)_{IJ} and Yx the iteration-invariant block-penta-diagonal part the handle already holds.
-// One 256-thread workgroup owns one problem at a time:
+// One Newton body (fr_newton), two kernels; one 512-thread workgroup owns one problem at a time:
+//   fmpc_newton_ramp     n <= 64, diagonal Q, Qf, R: B' in LDS (it0 = 1: the continuation behind fmpc_ramp_cold);
+//   fmpc_newton_ramp_ws  any (n, m, T), any symmetric positive definite Q, Qf, R (fast_mpc_objective.m:50-55;
+//                        VAR_1/Fast_MPC2.m:26-27): B' read from the model, nothing in LDS that grows with the problem.
+// Both keep the residuals, G and Y in the per-workgroup HBM workspace (fr_ws_layout).
 //   P1  slacks, barrier terms, r_d, r_p, exit test
-//   P2  per actuator: LDL' of its tridiagonal, Phi_u^-1 r_d, the explicit inverse g^{IJ} (O(T^2) recurrence);
+//   P2  the u-part of Phi: per actuator LDL' of its tridiagonal, Phi_u^-1 r_d, the explicit inverse g^{IJ} (O(T^2) recurrence);
 //       rhs = r_p - C Phi^-1 r_d
-//   P3  Y assembled block by block into the HBM workspace (lower block triangle)
-//   P4  blocked left-looking Cholesky of Y (n x n tiles through LDS), forward and backward substitution -> d_nu
+//   P3  [Y | rhs] assembled block by block into the workspace as 16 x 16 tiles (upper tile triangle)
+//   P4  Cholesky of Y on those tiles (fr_tile_cholesky, fmpc_ramp_tiles.h), forward and backward substitution -> d_nu
 //   P5  d_z = Phi^-1(-r_d - C' d_nu) (tridiagonal solves), closed-form line search, update
 // The two O(n^3)-class parts run on the matrix cores (v_mfma_f64_16x16x4_f64, generic 16 x 16 tiling with masked
 // edges): the B diag(g) B' products of P3 (k = actuators) and the panel updates of the Cholesky factorisation (k = the
-// columns already factored).  This is the path of BASELINE config 0 (VAR(1), T = 10); measured numbers in DESIGN.md §6.
+// columns already factored).  The workspace form adds:
+//   * dense R: Phi_u is block-tridiagonal, D_j = 2R + diag(hb_j + er_j + er_{j+1}), E_j = -diag(er_{j+1}).  Block Cholesky
+//     over the stages, L_j L_j' = D_j - M_j M_j' with M_j = E_{j-1} L_{j-1}^-T, in the R form of the tiles (L_j = R_j'):
+//     stage j factors the tile matrix A_j = [D_j - M_j M_j' | I | V sources] and its forward substitution leaves
+//     [R_j | Z_j = L_j^-1 | V_{j,0..j}], V = L^-1 (I_T (x) B'), i.e. V_jj = Z_j B', V_ji = Z_j diag(er_j) Z_{j-1}' V_{j-1,i}.
+//     The inputs of stage j + 1 are one product Z_j' [Z_j | V_{j,0..j}] (M M' = diag(er) Z' Z diag(er)).  Then
+//     Y_u(I, J) = sum_{k >= I} V_kI' V_kJ (lower block triangle only); Phi_u^-1 r_d and d_u by the two block substitutions with
+//     the explicit Z_j.  The factor panels, the substitution against [I | B' | ...] and V'V all run on the matrix cores;
+//   * dense Q, Qf: the state part of Phi is constant (no state rows in P), so Yx is the handle's Yblk as it stands (built
+//     from X = (2Q)^-1); r_d[x] applies 2Q / 2Qf and d_x applies X / Xf as matrices.
+// fmpc_newton_ramp is the path of BASELINE config 0 (VAR(1), T = 10); fmpc_newton_ramp_ws is a size and weight fallback
+// ("exact, slow", like the generic kernel's big instance).  Measured numbers of both in DESIGN.md §6.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "fmpc_device.h"
@@ -28,13 +43,11 @@
 #include "fmpc_rampcold.h"
 #include "../../include/fastmpc.h"
 
-#define FR_MAXKS 16                     // k-steps of 4 covering n <= 64
-
 typedef double d4 __attribute__((ext_vector_type(4)));
 #define MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
 #ifdef FW_TIMING
-// per-phase time of workgroup 0 (100 MHz ticks): P1, P2, P3, P4 factor, P4 substitutions, P5
+// per-phase time of workgroup 0 (100 MHz ticks): P1, P2, P3, P4 factor, P4 substitutions, P5 (fmpc_newton_ramp)
 __device__ unsigned long long fr_timing[16];
 extern "C" int fmpc_debug_ramp_timing(unsigned long long* out) {
     unsigned long long z[16] = {0};
@@ -49,15 +62,26 @@ extern "C" int fmpc_debug_ramp_timing(unsigned long long* out) {
 #endif
 #include "fmpc_ramp_tiles.h"
 
-struct FrWsLayout { size_t b, nu, hs, er, gr, dg, lo, rdu, rdx, phx, phu, rp, y, dnu, G, Y, W, total; };
-__host__ __device__ static inline FrWsLayout fr_ws_layout(int n, int m, int T, int nb) {
+#define FR_NT 512                       // threads per workgroup of both Newton kernels
+
+// The per-workgroup workspace of the Newton kernels.  ws: the workspace form (d_x, an m-long scratch vector); dense_r (workspace
+// form only): the dense-R factors A in place of g.
+struct FrWsLayout {
+    size_t b, nu, hs, er, gr, dg, lo, rdu, rdx, dx, phx, phu, rp, y, dnu, tmp, G, A, Y, W, total;
+    int ntr, ntn, ntc;                      // dense R: tile rows of A_j (m), tiles per V block (n), tile columns of A_j
+};
+__host__ __device__ static inline FrWsLayout fr_ws_layout(int n, int m, int T, int nb, bool ws, bool dense_r) {
     FrWsLayout L; size_t o = 0;
     const size_t nbn = (size_t)nb * n, Tm = (size_t)T * m, Tn = (size_t)T * n;
     L.b = o; o += nbn;   L.nu = o; o += nbn;
     L.hs = o; o += Tm;   L.er = o; o += Tm;   L.gr = o; o += Tm;   L.dg = o; o += Tm;   L.lo = o; o += Tm;
-    L.rdu = o; o += Tm;  L.rdx = o; o += Tn;  L.phx = o; o += Tn;  L.phu = o; o += Tm;
-    L.rp = o; o += nbn;  L.y = o; o += nbn;   L.dnu = o; o += nbn;
-    L.G = o; o += (size_t)T * (T + 1) / 2 * m;
+    L.rdu = o; o += Tm;  L.rdx = o; o += Tn;  L.dx = o; if (ws) o += Tn;  L.phx = o; o += Tn;  L.phu = o; o += Tm;
+    L.rp = o; o += nbn;  L.y = o; o += nbn;   L.dnu = o; o += nbn; L.tmp = o; if (ws) o += (size_t)m;
+    L.ntr = (m + 15) / 16; L.ntn = (n + 15) / 16; L.ntc = 2 * L.ntr + T * L.ntn;
+    L.G = o; if (!dense_r) o += (size_t)T * (T + 1) / 2 * m;                 // diagonal R: g^{IJ} per actuator
+    // dense R: per stage j the tile matrix A_j, NTr x NTc row-major 16 x 16 tiles: column tiles [0, NTr) D_j - M_j M_j' -> R_j,
+    // [NTr, 2 NTr) I -> Z_j (lower tile triangle used), then T blocks of NTn: block i <= j the source of V_ji -> V_ji
+    L.A = o; if (dense_r) o += (size_t)T * L.ntr * L.ntc * 256;
     const size_t NTl = (nbn + 1 + 15) / 16;  // 16 x 16 tiles covering [Y | rhs] (the rhs is column nbn)
     L.Y = o; o += NTl * NTl * 256;          // dense Y / its factor R (Y = R'R), tile (I, J) at (I NTl + J) 256, upper triangle used
     L.W = o; o += NTl * 256;                // R(kb,kb)^-1 per diagonal tile
@@ -229,46 +253,180 @@ __device__ __noinline__ int fr_tile_cholesky_lds(double* tiles_g, int NTm, int m
     return 0;
 }
 
-// NT threads per workgroup: 256 (3 workgroups per CU, throughput) or 512 (one problem spread over twice the waves, latency)
-template <int NT>
-__global__ void __launch_bounds__(NT, NT == 256 ? 3 : (NT == 512 ? 2 : 1))
-fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double* __restrict__ dumax, int batch,
-                 const double* __restrict__ x0, const double* __restrict__ x0p, const double* __restrict__ w,
-                 const double* __restrict__ uprev, const double* zinit, const double* __restrict__ nu0,
-                 int max_iter, double kbar, double* zout, double* __restrict__ nuout, int* __restrict__ status,
-                 int* __restrict__ iters, double* __restrict__ step, int step_ld, double* __restrict__ ws,
-                 size_t ws_stride, int it0) {
-    // it0 = 1: CONTINUATION behind fmpc_ramp_cold, which has taken the first Newton step of every problem: zinit (= zout) and nu0
-    // hold the iterate after that step, status / iters / step[0] its record; this launch runs the iterations 1 .. max_iter - 1 with
-    // their exit tests (inf_newton_solver.m:19-22) and adds to the record.  A problem whose first step ended in an error, or that
-    // left before stepping, is skipped.
+// Cholesky in the R form of the leading nr x nr part of the tile matrix At (NTr tile rows, ld tile columns, row-major 16 x 16
+// tiles), with the forward substitution R^-T applied to its tile columns [NTr, ncol): left-looking per block row kb, pass A
+// P(kb, J) = A(kb, J) - sum_{k<kb} R(k,kb)' R(k,J) on the matrix cores (the owner of the diagonal tile factors it, ft_potrf16),
+// pass B R(kb, J) = W P(kb, J) with W = R(kb,kb)^-T.  Tile columns [NTr, 2 NTr) hold an identity: their tile (k, NTr + i) is zero
+// for i > k before and after, so those tiles are skipped and the sums start at k = i.  sW: 16 x 17 doubles of LDS.
+// Returns 1 if a pivot is not positive.
+__device__ __noinline__ int frw_potrf(double* At, int ld, int NTr, int ncol, int nr, double* sW) {
+    typedef FtT<double> TT;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, NW = blockDim.x >> 6, c = lane & 15, g = lane >> 4;
+    __shared__ int sfail;
+    if (tid == 0) sfail = 0;
+    __syncthreads();
+    for (int kb = 0; kb < NTr; ++kb) {
+        const int cnt = nr - 16 * kb < 16 ? nr - 16 * kb : 16;
+        for (int J = kb + wv; J < ncol; J += NW) {
+            const bool zc = J >= NTr && J < 2 * NTr;
+            if (zc && J - NTr > kb) continue;
+            double* tp = At + ((size_t)kb * ld + J) * 256;
+            ft_d4 acc;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[r] = tp[64 * r + lane];
+            for (int k = zc ? J - NTr : 0; k < kb; ++k) {
+                const double* X = At + ((size_t)k * ld + kb) * 256;
+                const double* Z = At + ((size_t)k * ld + J) * 256;
+                double xv[4], zv[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { xv[r] = X[64 * r + lane]; zv[r] = Z[64 * r + lane]; }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc = TT::mfma_sub(xv[r], zv[r], acc);
+            }
+            if (J == kb) {
+                ft_d4 Ro, Wo;
+                const bool ok = ft_potrf16<double>(acc, cnt, c, g, Ro, Wo);
+                if (!ok && lane == 0) sfail = 1;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { sW[c * 17 + TT::row(g, r)] = Wo[r]; tp[64 * r + lane] = Ro[r]; }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) tp[64 * r + lane] = acc[r];
+            }
+        }
+        __syncthreads();
+        if (sfail) return 1;                                                // uniform
+        double wop[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) wop[r] = sW[TT::row(g, r) * 17 + c];
+        for (int J = kb + 1 + wv; J < ncol; J += NW) {
+            if (J >= NTr && J < 2 * NTr && J - NTr > kb) continue;
+            double* tp = At + ((size_t)kb * ld + J) * 256;
+            ft_d4 pv, o = {0, 0, 0, 0};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) pv[r] = tp[64 * r + lane];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o = TT::mfma(wop[r], pv[r], o);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) tp[64 * r + lane] = o[r];
+        }
+        __syncthreads();
+    }
+    return 0;
+}
+
+// acc += sum_{k = k0 .. k1-1} X(k)' Z(k) over 16 x 16 tiles in memory, X(k) = Xt + k xs tiles, Z(k) = Zt + k zs tiles
+__device__ __forceinline__ void frw_xtz(ft_d4& acc, const double* Xt, size_t xs, const double* Zt, size_t zs, int k0, int k1, int lane) {
+    for (int k = k0; k < k1; ++k) {
+        const double* X = Xt + (size_t)k * xs * 256;
+        const double* Z = Zt + (size_t)k * zs * 256;
+        double xv[4], zv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { xv[r] = X[64 * r + lane]; zv[r] = Z[64 * r + lane]; }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc = FtT<double>::mfma(xv[r], zv[r], acc);
+    }
+}
+
+// f (T m, stage-major) <- Phi_u^-1 f for dense R, with the explicit Z_j of the factor: forward w_j = Z_j (f_j + e_j (Z_{j-1}' w_{j-1})),
+// backward x_j = Z_j' (w_j + Z_j (e_{j+1} x_{j+1})), e_j = er_j.  Element (a, b) of Z_j is in tile (a / 16, NTr + b / 16) of A_j.
+// tmp: m doubles.  Thread a owns row a.  (O(T m^2) per solve, on the vector units.)
+__device__ __forceinline__ void frw_phiu_solve(const double* A, int NTr, int NTc, const double* er, double* f, double* tmp, int m, int T) {
+    const int tid = threadIdx.x, NT = blockDim.x;
+    const size_t stg = (size_t)NTr * NTc * 256;
+    auto zel = [=](const double* Aj, int a, int b) { return Aj[((size_t)(a >> 4) * NTc + NTr + (b >> 4)) * 256 + (a & 15) * 16 + (b & 15)]; };
+    for (int j = 0; j < T; ++j) {
+        const double* Aj = A + (size_t)j * stg;
+        for (int a = tid; a < m; a += NT) {
+            double v = f[j * m + a];
+            if (j > 0) {
+                const double* Ap = Aj - stg;
+                double s0 = 0.0, s1 = 0.0;
+                int k = a;
+                for (; k + 1 < m; k += 2) { s0 += zel(Ap, k, a) * f[(j - 1) * m + k]; s1 += zel(Ap, k + 1, a) * f[(j - 1) * m + k + 1]; }
+                if (k < m) s0 += zel(Ap, k, a) * f[(j - 1) * m + k];
+                v += er[j * m + a] * (s0 + s1);
+            }
+            tmp[a] = v;
+        }
+        __syncthreads();
+        for (int a = tid; a < m; a += NT) {
+            double s0 = 0.0, s1 = 0.0;
+            int k = 0;
+            for (; k + 1 <= a; k += 2) { s0 += zel(Aj, a, k) * tmp[k]; s1 += zel(Aj, a, k + 1) * tmp[k + 1]; }
+            if (k <= a) s0 += zel(Aj, a, k) * tmp[k];
+            f[j * m + a] = s0 + s1;
+        }
+        __syncthreads();
+    }
+    for (int j = T - 1; j >= 0; --j) {
+        const double* Aj = A + (size_t)j * stg;
+        for (int a = tid; a < m; a += NT) {
+            double v = f[j * m + a];
+            if (j + 1 < T) {
+                double s0 = 0.0, s1 = 0.0;
+                int k = 0;
+                for (; k + 1 <= a; k += 2) {
+                    s0 += zel(Aj, a, k) * (er[(j + 1) * m + k] * f[(j + 1) * m + k]);
+                    s1 += zel(Aj, a, k + 1) * (er[(j + 1) * m + k + 1] * f[(j + 1) * m + k + 1]);
+                }
+                if (k <= a) s0 += zel(Aj, a, k) * (er[(j + 1) * m + k] * f[(j + 1) * m + k]);
+                v += s0 + s1;
+            }
+            tmp[a] = v;
+        }
+        __syncthreads();
+        for (int a = tid; a < m; a += NT) {
+            double s0 = 0.0, s1 = 0.0;
+            int k = a;
+            for (; k + 1 < m; k += 2) { s0 += zel(Aj, k, a) * tmp[k]; s1 += zel(Aj, k + 1, a) * tmp[k + 1]; }
+            if (k < m) s0 += zel(Aj, k, a) * tmp[k];
+            f[j * m + a] = s0 + s1;
+        }
+        __syncthreads();
+    }
+}
+
+#define FR_NEWTON_TICK(k) do { if constexpr (!WS) FR_TICK(k); } while (0)      // phase counters of fr_newton: the LDS form only
+
+// One Newton solve per problem of the batch, phases P0-P5 of the head of the file.  WS selects the form: false = fmpc_newton_ramp
+// (B' in LDS, diagonal weights), true = fmpc_newton_ramp_ws (B' from the model, dense Q / R as the model says).  it0 = 1 (LDS
+// form): CONTINUATION behind fmpc_ramp_cold, which has taken the first Newton step of every problem: zinit (= zout) and nu0 hold
+// the iterate after that step, status / iters / step[0] its record; this launch runs the iterations 1 .. max_iter - 1 with their
+// exit tests (inf_newton_solver.m:19-22) and adds to the record.  A problem whose first step ended in an error, or that left
+// before stepping, is skipped.
+template <int NT, bool WS>
+__device__ __forceinline__ void fr_newton(const FmpcDevModel& M, const double* dumin, const double* dumax, int batch,
+                                          const double* x0, const double* x0p, const double* w, const double* uprev,
+                                          const double* zinit, const double* nu0, int max_iter, double kbar, double* zout,
+                                          double* nuout, int* status, int* iters, double* step, int step_ld, double* ws,
+                                          size_t ws_stride, int it0) {
+    typedef FtT<double> TT;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     constexpr int NW = NT / 64;
     const int n = M.n, m = M.m, T = M.T, nb = M.nb;
-    const int s = n + m, Nz = T * s, nbn = nb * n, ldt = n + 1, tsz = n * ldt;
+    const int s = n + m, Nz = T * s, nbn = nb * n;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, lk = lane >> 4;
     const int ntile = (n + 15) >> 4;
-    const bool var2 = M.var2 != 0;
+    const bool var2 = M.var2 != 0, dQ = WS && M.denseQ != 0, dR = WS && M.denseR != 0;
 
-    // ---- LDS carve
-    double* sBt = lds;                    // m*n   Bt[c*n + r] = B[r][c]
-    double* tA = sBt + (size_t)m * n;     // n*ldt: the diagonal block being factored
-    double* tB = tA + tsz;                // n*ldt: its inverse factor
-    double* sv = tB + tsz;                // n     vector of the backward substitution
-    double* srs = sv + n;                 // n     1/sqrt(pivot)
-    double* sred = srs + n;               // NW x 64 partial sums of the backward substitution
-    double* red = sred + NW * 64;   // NW
-    double* sCh = red + 16;         // scratch of fr_tile_cholesky: 16 x 17 + 16 NTl + 16 NW + 16
+    // ---- LDS (the same offsets in both forms up to sBt: fr_tile_cholesky and frw_potrf see one constant scratch address)
+    double* red = lds;                                  // 16
+    double* sCh = red + 16;                             // scratch of fr_tile_cholesky (16 x 17 + 16 NTl + 16 NW + 16); frw_potrf uses its first 16 x 17
+    double* sBt = sCh + (16 * 17 + 16 * ((nbn + 1 + 15) >> 4) + 16 * NW + 16);     // LDS form: m*n   Bt[c*n + r] = B[r][c]
+    const double* Bt = WS ? M.Bt : sBt;
+    if (!WS)
+        for (int i = tid; i < m * n; i += NT) sBt[i] = M.Bt[i];
 
-    for (int i = tid; i < m * n; i += NT) sBt[i] = M.Bt[i];
-
-    const FrWsLayout L = fr_ws_layout(n, m, T, nb);
+    const FrWsLayout L = fr_ws_layout(n, m, T, nb, WS, dR);
     double* wsp = ws + (size_t)blockIdx.x * ws_stride;
     double* b = wsp + L.b;     double* nu = wsp + L.nu;   double* hs = wsp + L.hs;   double* er = wsp + L.er;
     double* gr = wsp + L.gr;   double* dg = wsp + L.dg;   double* lo = wsp + L.lo;   double* rdu = wsp + L.rdu;
-    double* rdx = wsp + L.rdx; double* phx = wsp + L.phx; double* phu = wsp + L.phu; double* rp = wsp + L.rp;
-    double* y = wsp + L.y;     double* dnu = wsp + L.dnu; double* G = wsp + L.G;     double* Yd = wsp + L.Y;
-    double* Wg = wsp + L.W;
+    double* rdx = wsp + L.rdx; double* dx = wsp + L.dx;   double* phx = wsp + L.phx; double* phu = wsp + L.phu;
+    double* rp = wsp + L.rp;   double* y = wsp + L.y;     double* dnu = wsp + L.dnu; double* tmp = wsp + L.tmp;
+    double* G = wsp + L.G;     double* Aw = wsp + L.A;    double* Yd = wsp + L.Y;    double* Wg = wsp + L.W;
+    const int NTr = L.ntr, NTn = L.ntn, NTc = L.ntc;
+    const size_t stg = (size_t)NTr * NTc * 256;
 
     for (int p = blockIdx.x; p < batch; p += gridDim.x) {
         double* zp = zout + (size_t)p * Nz;
@@ -320,18 +478,34 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
                 const double hb = kbar * (dp * dp + dm * dm);
                 const bool nx = j + 1 < T;
                 double dot = 0.0;
-                const double* bt = sBt + c * n;
+                const double* bt = Bt + (size_t)c * n;
                 const double* nj = nu + j * n;
                 for (int r = 0; r < n; ++r) dot += bt[r] * nj[r];
-                const double rd = M.R2[c] * u + M.rl[c] + kbar * (dp - dm) + gr[idx] - (nx ? gr[idx + m] : 0.0) - dot;
+                double ru;
+                if (dR) {
+                    const double* uj = zp + j * s;
+                    ru = 0.0;
+                    for (int q = 0; q < m; ++q) ru += M.R2m[(size_t)q * m + c] * uj[q];      // (2R symmetric: column c = row c)
+                } else {
+                    ru = M.R2[c] * u;
+                }
+                const double rd = ru + M.rl[c] + kbar * (dp - dm) + gr[idx] - (nx ? gr[idx + m] : 0.0) - dot;
                 hs[idx] = hb + er[idx] + (nx ? er[idx + m] : 0.0);          // diagonal of k P'DP
                 rdu[idx] = rd;
                 acc_d += rd * rd;
             }
             for (int idx = tid; idx < T * n; idx += NT) {
                 const int jj = idx / n, r = idx - jj * n, j = jj + 1;   // x_j, j = 1..T
-                const double x = zp[jj * s + m + r];
-                double v = (j == T ? M.Qf2[r] * x + M.qfl[r] : M.Q2[r] * x + M.ql[r]) + nu[jj * n + r];
+                const double* xj = zp + jj * s + m;
+                double v;
+                if (dQ) {
+                    const double* Qm = j == T ? M.Qf2m : M.Q2m;
+                    v = j == T ? M.qfl[r] : M.ql[r];
+                    for (int c = 0; c < n; ++c) v += Qm[(size_t)c * n + r] * xj[c];
+                } else {
+                    v = j == T ? M.Qf2[r] * xj[r] + M.qfl[r] : M.Q2[r] * xj[r] + M.ql[r];
+                }
+                v += nu[jj * n + r];
                 if (j < T) {
                     const double* nj = nu + j * n;
                     for (int c = 0; c < n; ++c) v -= M.A1[c * n + r] * nj[c];
@@ -342,7 +516,7 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
                 }
                 if (j == T && M.has_xf) v += nu[T * n + r];
                 rdx[idx] = v;
-                phx[idx] = v / (j == T ? M.Qf2[r] : M.Q2[r]);           // Phi^-1 r_d on x_j
+                if (!dQ) phx[idx] = v / (j == T ? M.Qf2[r] : M.Q2[r]);  // Phi^-1 r_d on x_j
                 acc_d += v * v;
             }
             for (int idx = tid; idx < nbn; idx += NT) {
@@ -351,7 +525,7 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
                 if (i < T) {
                     v = zp[i * s + m + r] - b[idx];
                     const double* ui = zp + i * s;
-                    for (int c = 0; c < m; ++c) v -= sBt[c * n + r] * ui[c];
+                    for (int c = 0; c < m; ++c) v -= Bt[(size_t)c * n + r] * ui[c];
                     if (i >= 1) {
                         const double* xi = zp + (i - 1) * s + m;
                         for (int c = 0; c < n; ++c) v -= M.A1t[c * n + r] * xi[c];
@@ -370,29 +544,40 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
             const double rho2 = fr_block_sum<NT>(acc_d, red) + rp2;
             // early exit, tested before the step (inf_newton_solver.m:19-22)
             if (sqrt(rho2) <= 1e-6 && sqrt(rp2) <= 1e-8) break;
-            FR_TICK(0);
-
-            // ================= P2: per actuator LDL' of the tridiagonal u-part of Phi, Phi_u^-1 r_d, explicit inverse
-            int bad = 0;
-            for (int c = tid; c < m; c += NT) {
-                double lprev = 0.0, oprev = 0.0;
-                for (int j = 0; j < T; ++j) {
-                    double d = M.R2[c] + hs[j * m + c];
-                    if (j > 0) d -= lprev * oprev;
-                    if (!(d > 0.0) || isinf(d)) bad = 1;
-                    dg[j * m + c] = d;
-                    if (j + 1 < T) {
-                        oprev = -er[(j + 1) * m + c];
-                        lprev = oprev / d;
-                        lo[j * m + c] = lprev;
-                    }
+            if (dQ) {                                                   // Phi^-1 r_d on x_j = X r_d[x_j] (X = (2Q)^-1, Xf on x_T)
+                for (int idx = tid; idx < T * n; idx += NT) {
+                    const int jj = idx / n, r = idx - jj * n;
+                    const double* Xm = jj + 1 == T ? M.Xfm : M.Xm;
+                    const double* rj = rdx + jj * n;
+                    double v = 0.0;
+                    for (int c = 0; c < n; ++c) v += Xm[(size_t)r * n + c] * rj[c];
+                    phx[idx] = v;
                 }
-                for (int j = 0; j < T; ++j) phu[j * m + c] = rdu[j * m + c];
-                fr_tri_solve(dg, lo, phu, T, m, c);
-                // inverse, pairs (i <= j) at index i*T - i(i-1)/2 + (j - i):  inv[j][j] = 1/d_j + l_j^2 inv[j+1][j+1] ,
-                // inv[j][k] = -l_j inv[j+1][k] (k > j) = (-l_j)(-l_{j+1}) ... (-l_{k-1}) inv[k][k]: the diagonal as one chain carried in
-                // a register, then every column k upwards from its diagonal entry -- no load of a value this thread has just stored
-                {
+            }
+            FR_NEWTON_TICK(0);
+
+            // ================= P2: the u-part of Phi: factor, Phi_u^-1 r_d
+            int bad = 0;
+            if (!dR) {
+                // per actuator LDL' of the tridiagonal, Phi_u^-1 r_d, the explicit inverse g^{IJ}
+                for (int c = tid; c < m; c += NT) {
+                    double lprev = 0.0, oprev = 0.0;
+                    for (int j = 0; j < T; ++j) {
+                        double d = M.R2[c] + hs[j * m + c];
+                        if (j > 0) d -= lprev * oprev;
+                        if (!(d > 0.0) || isinf(d)) bad = 1;
+                        dg[j * m + c] = d;
+                        if (j + 1 < T) {
+                            oprev = -er[(j + 1) * m + c];
+                            lprev = oprev / d;
+                            lo[j * m + c] = lprev;
+                        }
+                    }
+                    for (int j = 0; j < T; ++j) phu[j * m + c] = rdu[j * m + c];
+                    fr_tri_solve(dg, lo, phu, T, m, c);
+                    // inverse, pairs (i <= j) at index i*T - i(i-1)/2 + (j - i):  inv[j][j] = 1/d_j + l_j^2 inv[j+1][j+1] ,
+                    // inv[j][k] = -l_j inv[j+1][k] (k > j) = (-l_j)(-l_{j+1}) ... (-l_{k-1}) inv[k][k]: the diagonal as one chain carried in
+                    // a register, then every column k upwards from its diagonal entry -- no load of a value this thread has just stored
                     double dprev = 0.0;
                     for (int j = T - 1; j >= 0; --j) {
                         const size_t rowj = (size_t)j * T - (size_t)j * (j - 1) / 2;
@@ -407,6 +592,66 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
                         dprev = dv;
                     }
                 }
+            } else {
+                // block Cholesky over the stages on the matrix cores (see the head of the file)
+                for (int j = 0; j < T; ++j) {
+                    double* Aj = Aw + (size_t)j * stg;
+                    const double* Ap = Aj - stg;                        // (j > 0 only)
+                    const int vcol = 2 * NTr + j * NTn;                 // tile column of the block V_jj
+                    const int ncol = vcol + NTn;
+                    // ---- form A_j: one output tile per wavefront task
+                    const int nzt = NTr * (NTr + 1) / 2;                // S tiles (upper tile triangle), then Z tiles (lower), then V tiles
+                    const int ntask = 2 * nzt + NTr * (j + 1) * NTn;
+                    for (int task = wv; task < ntask; task += NW) {
+                        int rt, ct, kind;                               // kind 0: S, 1: identity, 2: V source from stage j - 1, 3: B'
+                        if (task < 2 * nzt) {
+                            const int q = task < nzt ? task : task - nzt;
+                            int a = (int)((sqrt(8.0 * q + 1.0) - 1.0) * 0.5);          // q = a (a + 1) / 2 + b , b <= a
+                            while (a * (a + 1) / 2 > q) --a;
+                            while ((a + 1) * (a + 2) / 2 <= q) ++a;
+                            const int bq = q - a * (a + 1) / 2;
+                            if (task < nzt) { rt = bq; ct = a; kind = 0; } else { rt = a; ct = NTr + bq; kind = 1; }
+                        } else {
+                            const int q = task - 2 * nzt;
+                            rt = q % NTr; ct = 2 * NTr + q / NTr;
+                            kind = ct >= vcol ? 3 : 2;
+                        }
+                        ft_d4 acc = {0, 0, 0, 0};
+                        if (j > 0 && kind == 0)                         // Z_{j-1}' Z_{j-1}, tile (rt, ct): k >= max(rt, ct) = ct
+                            frw_xtz(acc, Ap + ((size_t)NTr + rt) * 256, NTc, Ap + ((size_t)NTr + ct) * 256, NTc, ct, NTr, lane);
+                        else if (kind == 2)                             // Z_{j-1}' V_{j-1,i}
+                            frw_xtz(acc, Ap + ((size_t)NTr + rt) * 256, NTc, Ap + (size_t)ct * 256, NTc, rt, NTr, lane);
+                        double* tp = Aj + ((size_t)rt * NTc + ct) * 256;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int a = 16 * rt + TT::row(lk, r);     // row of A_j (actuator)
+                            double v = 0.0;
+                            if (kind == 0) {
+                                const int bc = 16 * ct + li;
+                                if (a < m && bc < m) {
+                                    v = M.R2m[(size_t)a * m + bc] + (a == bc ? hs[j * m + a] : 0.0);
+                                    if (j > 0) v -= er[j * m + a] * acc[r] * er[j * m + bc];
+                                }
+                            } else if (kind == 1) {
+                                v = a == 16 * (ct - NTr) + li ? 1.0 : 0.0;
+                            } else if (kind == 2) {
+                                v = a < m ? er[j * m + a] * acc[r] : 0.0;
+                            } else {
+                                const int bc = 16 * (ct - vcol) + li;
+                                v = a < m && bc < n ? Bt[(size_t)a * n + bc] : 0.0;
+                            }
+                            tp[64 * r + lane] = v;
+                        }
+                    }
+                    __syncthreads();
+                    if (frw_potrf(Aj, NTc, NTr, ncol, m, sCh)) bad = 1;
+                    if (bad) break;
+                }
+                if (!bad) {
+                    for (int idx = tid; idx < T * m; idx += NT) phu[idx] = rdu[idx];
+                    __syncthreads();
+                    frw_phiu_solve(Aw, NTr, NTc, er, phu, tmp, m, T);
+                }
             }
             const double badsum = fr_block_sum<NT>((double)bad, red);
             if (badsum > 0.0) { st = FMPC_E_NOT_PD_PHI; break; }
@@ -417,7 +662,7 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
                 if (i < T) {
                     cv = phx[i * n + r];
                     const double* pu = phu + i * m;
-                    for (int c = 0; c < m; ++c) cv -= sBt[c * n + r] * pu[c];
+                    for (int c = 0; c < m; ++c) cv -= Bt[(size_t)c * n + r] * pu[c];
                     if (i >= 1) {
                         const double* px = phx + (i - 1) * n;
                         for (int c = 0; c < n; ++c) cv -= M.A1t[c * n + r] * px[c];
@@ -432,13 +677,13 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
                 y[idx] = rp[idx] - cv;
             }
             __syncthreads();
-            FR_TICK(1);
+            FR_NEWTON_TICK(1);
 
             // ================= P3: [Y | rhs] into the workspace as 16 x 16 tiles (upper tile triangle; fr_tile_cholesky).
-            // Y_IJ = Yx_IJ + B diag(g^{JI}) B' on the matrix cores: a wave per 16 x 16 piece of a block, k = 4 actuators per
-            // MFMA; A operand B[a][c] g_c (row a = lane % 16, c = 4 ks + lane / 16), B operand B[b][c]; result register r of
-            // lane (lk, li) is element (4 r + lk, li) of the piece.  The blocks (n x n) and the tiles (16 x 16) do not line up:
-            // every element goes to its tile on its own; a diagonal tile receives both halves.
+            // Y_IJ = Yx_IJ + B diag(g^{JI}) B' (diagonal R) or Yx_IJ + sum_{k >= I} V_kI' V_kJ (dense R) on the matrix cores: a wave
+            // per 16 x 16 piece of a block; result register r of lane (lk, li) is element (4 r + lk, li) of the piece.  The blocks
+            // (n x n) and the tiles (16 x 16) do not line up: every element goes to its tile on its own; a diagonal tile receives both
+            // halves.  (No workgroup barrier in this phase: every wave walks its own blocks.)
             const int NTl = (nbn + 1 + 15) >> 4;
             for (size_t idx = tid; idx < (size_t)NTl * NTl * 256; idx += NT) Yd[idx] = 0.0;
             __syncthreads();
@@ -446,9 +691,8 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
                 Yd[((size_t)(gr_ >> 4) * NTl + (gc_ >> 4)) * 256 + (gr_ & 15) * 16 + (gc_ & 15)] = v;
             };
             for (int idx = tid; idx < nbn; idx += NT) put(idx, nbn, y[idx]);
-            // (no workgroup barrier in this phase: every wave walks its own blocks)
-            if (ntile <= 2) {
-                // n <= 32: a wave takes a whole block (I, J) with its (up to) four 16 x 16 pieces in registers: per k-step
+            if (!WS && ntile <= 2) {
+                // LDS form, n <= 32: a wave takes a whole block (I, J) with its (up to) four 16 x 16 pieces in registers: per k-step
                 // (4 actuators) two LDS reads and two multiplications by g feed four products.
                 const int nblk = nb * (nb + 1) / 2;
                 const int ra0 = li < n ? li : n - 1, ra1 = 16 + li < n ? 16 + li : n - 1;
@@ -519,19 +763,19 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
             } else {
                 const int nblk = nb * (nb + 1) / 2, tpb = ntile * ntile;
                 for (int task = wv; task < nblk * tpb; task += NW) {
-                    const int blk = task / tpb, tp = task - blk * tpb;
+                    const int blk = task / tpb, tq = task - blk * tpb;
                     int I = (int)((sqrt(8.0 * blk + 1.0) - 1.0) * 0.5);          // blk = I (I + 1) / 2 + J , J <= I
                     while (I * (I + 1) / 2 > blk) --I;
                     while ((I + 1) * (I + 2) / 2 <= blk) ++I;
                     const int J = blk - I * (I + 1) / 2;
-                    const int ta = tp / ntile, tb = tp - ta * ntile;
+                    const int ta = tq / ntile, tb = tq - ta * ntile;
                     if (I == J && ta < tb) continue;                  // diagonal blocks: the lower pieces, mirrored below
                     const bool hasu = I < T;                         // (J <= I): both stages carry u
                     const double* Yc = nullptr; bool tr = false;
                     if (I == J) Yc = M.Yblk + (size_t)M.idxD[I] * n * n;
                     else if (I == J + 1 && M.idx1[J] >= 0) { Yc = M.Yblk + (size_t)M.idx1[J] * n * n; tr = true; }
                     else if (I == J + 2 && M.idx2[J] >= 0) { Yc = M.Yblk + (size_t)M.idx2[J] * n * n; tr = true; }
-                    d4 acc = {0, 0, 0, 0};
+                    ft_d4 acc = {0, 0, 0, 0};
                     const int bcol = 16 * tb + li;
                     // everything the task reads from memory first: the constant part of its four elements, then g
                     double yc4[4];
@@ -543,21 +787,42 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
                         yc4[r] = ysrc[tr ? bc * n + ar : ar * n + bc];
                     }
                     const double ycf = Yc ? 1.0 : 0.0;
-                    if (hasu) {
+                    if (hasu && !dR) {
                         const double* gv = G + ((size_t)J * T - (size_t)J * (J - 1) / 2 + (I - J)) * m;
                         const int ra = 16 * ta + li < n ? 16 * ta + li : n - 1, rb = 16 * tb + li < n ? 16 * tb + li : n - 1;
-                        // 36 k-steps (144 actuators) at a time: their g values are requested before the first product
-                        for (int c0 = 0; c0 < m; c0 += 144) {
-                            double gq[36];
+                        if constexpr (WS) {
+                            // B' from memory: 8 k-steps (32 actuators) at a time, g and both operands requested first
+                            for (int c0 = 0; c0 < m; c0 += 32) {
+                                double gq[8], xa[8], xb[8];
 #pragma unroll
-                            for (int q = 0; q < 36; ++q) { const int cq = c0 + 4 * q + lk; gq[q] = gv[cq < m ? cq : m - 1]; }
+                                for (int q = 0; q < 8; ++q) {
+                                    const int cq = c0 + 4 * q + lk, cc = cq < m ? cq : m - 1;
+                                    gq[q] = cq < m ? gv[cc] : 0.0;
+                                    xa[q] = Bt[(size_t)cc * n + ra]; xb[q] = Bt[(size_t)cc * n + rb];
+                                }
 #pragma unroll
-                            for (int q = 0; q < 36; ++q) {             // (straight-line: past m the A operand is zero)
-                                const int cq = c0 + 4 * q + lk;
-                                const int cc = cq < m ? cq : m - 1;
-                                const double msk = cq < m ? 1.0 : 0.0;
-                                acc = MFMA64(sBt[cc * n + ra] * (gq[q] * msk), sBt[cc * n + rb], acc);
+                                for (int q = 0; q < 8; ++q) acc = TT::mfma(xa[q] * gq[q], xb[q], acc);
                             }
+                        } else {
+                            // B' in LDS: 36 k-steps (144 actuators) at a time, their g values requested before the first product
+                            for (int c0 = 0; c0 < m; c0 += 144) {
+                                double gq[36];
+#pragma unroll
+                                for (int q = 0; q < 36; ++q) { const int cq = c0 + 4 * q + lk; gq[q] = gv[cq < m ? cq : m - 1]; }
+#pragma unroll
+                                for (int q = 0; q < 36; ++q) {             // (straight-line: past m the A operand is zero)
+                                    const int cq = c0 + 4 * q + lk;
+                                    const int cc = cq < m ? cq : m - 1;
+                                    const double msk = cq < m ? 1.0 : 0.0;
+                                    acc = MFMA64(sBt[cc * n + ra] * (gq[q] * msk), sBt[cc * n + rb], acc);
+                                }
+                            }
+                        }
+                    } else if (hasu) {
+                        for (int k = I; k < T; ++k) {
+                            const double* Ak = Aw + (size_t)k * stg;
+                            frw_xtz(acc, Ak + (size_t)(2 * NTr + I * NTn + ta) * 256, NTc, Ak + (size_t)(2 * NTr + J * NTn + tb) * 256, NTc,
+                                    0, NTr, lane);
                         }
                     }
 #pragma unroll
@@ -573,23 +838,24 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
                 }
             }
             __syncthreads();
-            FR_TICK(2);
+            FR_NEWTON_TICK(2);
 
             // ================= P4: Cholesky of Y on 16 x 16 tiles (forward substitution in the rhs column), backward substitution
             if (fr_tile_cholesky(Yd, NTl, nbn, Wg, dnu, sCh)) { st = FMPC_E_NOT_PD_SCHUR; break; }
-            FR_TICK(3);
-            FR_TICK(4);
+            FR_NEWTON_TICK(3);
+            FR_NEWTON_TICK(4);
             // ================= P5: d_z, line-search scalars, update
             for (int idx = tid; idx < T * m; idx += NT) {           // rhs of Phi_u d_u = B' d_nu_j - r_d,u
                 const int j = idx / m, c = idx - j * m;
                 double dot = 0.0;
-                const double* bt = sBt + c * n;
+                const double* bt = Bt + (size_t)c * n;
                 const double* dj = dnu + j * n;
                 for (int r = 0; r < n; ++r) dot += bt[r] * dj[r];
                 phu[idx] = dot - rdu[idx];
             }
             __syncthreads();
-            for (int c = tid; c < m; c += NT) fr_tri_solve(dg, lo, phu, T, m, c);     // phu = d_u
+            if (dR) frw_phiu_solve(Aw, NTr, NTc, er, phu, tmp, m, T);                      // phu = d_u
+            else for (int c = tid; c < m; c += NT) fr_tri_solve(dg, lo, phu, T, m, c);
             __syncthreads();
             double be = 0.0, e2 = 0.0;
             for (int idx = tid; idx < T * m; idx += NT) {
@@ -612,23 +878,23 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
                     for (int c = 0; c < n; ++c) v += M.A2[c * n + r] * dj[c];
                 }
                 if (j == T && M.has_xf) v -= dnu[T * n + r];
-                rdx[idx] = v / (j == T ? M.Qf2[r] : M.Q2[r]);               // reuse as d_x
+                if (dQ) dx[idx] = v;
+                else rdx[idx] = v / (j == T ? M.Qf2[r] : M.Q2[r]);         // reuse as d_x
+            }
+            if (dQ) {
+                __syncthreads();
+                for (int idx = tid; idx < T * n; idx += NT) {
+                    const int jj = idx / n, r = idx - jj * n;
+                    const double* Xm = jj + 1 == T ? M.Xfm : M.Xm;
+                    const double* vj = dx + jj * n;
+                    double v = 0.0;
+                    for (int c = 0; c < n; ++c) v += Xm[(size_t)r * n + c] * vj[c];
+                    rdx[idx] = v;                                           // d_x
+                }
             }
             const double beta_e = fr_block_sum<NT>(be, red);
             const double eps2 = fr_block_sum<NT>(e2, red);
-            // closed form of backtracking_inf_newton.m:2-11 with the frozen barrier gradient:
-            // ||r(t)||^2 - ((1-al t) rho)^2 = t * gq(t)
-            double t = 1.0;
-            {
-                const double al = 1e-4;
-                int halv = 0;
-                while (true) {
-                    const double gq = (t - 2.0 + 2.0 * al - al * al * t) * rho2 - 2.0 * (1.0 - t) * beta_e + t * eps2;
-                    if (gq <= 0.0) break;
-                    t *= 0.5;
-                    if (++halv >= FR_MAX_HALVINGS) { t = 0.0; st = FMPC_W_LINESEARCH; break; }
-                }
-            }
+            const double t = fr_line_search(rho2, beta_e, eps2, st);
             for (int idx = tid; idx < Nz; idx += NT) {
                 const int j = idx / s, e = idx - j * s;
                 zp[idx] += t * (e < m ? phu[j * m + e] : rdx[j * n + e - m]);
@@ -637,7 +903,7 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
             if (step && tid == 0 && it < step_ld) step[(size_t)p * step_ld + it] = t;
             ++nsteps;
             __syncthreads();
-            FR_TICK(5);
+            FR_NEWTON_TICK(5);
         }
         if (nuout)
             for (int idx = tid; idx < nbn; idx += NT) nuout[(size_t)p * nbn + idx] = nu[idx];
@@ -646,6 +912,30 @@ fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double*
             if (iters) iters[p] = nsteps;
         }
     }
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT, 2)
+fmpc_newton_ramp(FmpcDevModel M, const double* __restrict__ dumin, const double* __restrict__ dumax, int batch,
+                 const double* __restrict__ x0, const double* __restrict__ x0p, const double* __restrict__ w,
+                 const double* __restrict__ uprev, const double* zinit, const double* __restrict__ nu0,
+                 int max_iter, double kbar, double* zout, double* __restrict__ nuout, int* __restrict__ status,
+                 int* __restrict__ iters, double* __restrict__ step, int step_ld, double* __restrict__ ws,
+                 size_t ws_stride, int it0) {
+    fr_newton<NT, false>(M, dumin, dumax, batch, x0, x0p, w, uprev, zinit, nu0, max_iter, kbar, zout, nuout, status, iters, step,
+                         step_ld, ws, ws_stride, it0);
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT, 1)
+fmpc_newton_ramp_ws(FmpcDevModel M, const double* __restrict__ dumin, const double* __restrict__ dumax, int batch,
+                    const double* __restrict__ x0, const double* __restrict__ x0p, const double* __restrict__ w,
+                    const double* __restrict__ uprev, const double* zinit, const double* __restrict__ nu0,
+                    int max_iter, double kbar, double* zout, double* __restrict__ nuout, int* __restrict__ status,
+                    int* __restrict__ iters, double* __restrict__ step, int step_ld, double* __restrict__ ws,
+                    size_t ws_stride) {
+    fr_newton<NT, true>(M, dumin, dumax, batch, x0, x0p, w, uprev, zinit, nu0, max_iter, kbar, zout, nuout, status, iters, step,
+                        step_ld, ws, ws_stride, 0);
 }
 
 // =====================================================================================================================
@@ -967,16 +1257,7 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 2 : 1) fmpc_ramp_cold(FrColdPa
                 }
                 const double beta_e = fr_block_sum<NT>(be, red);
                 const double eps2 = fr_block_sum<NT>(e2, red);
-                {
-                    const double al = 1e-4;
-                    int halv = 0;
-                    while (true) {
-                        const double gq = (t - 2.0 + 2.0 * al - al * al * t) * rho2 - 2.0 * (1.0 - t) * beta_e + t * eps2;
-                        if (gq <= 0.0) break;
-                        t *= 0.5;
-                        if (++halv >= FR_MAX_HALVINGS) { t = 0.0; st = FMPC_W_LINESEARCH; break; }
-                    }
-                }
+                t = fr_line_search(rho2, beta_e, eps2, st);
                 moved = true;
                 nsteps = 1;
             }
@@ -1038,36 +1319,29 @@ hipError_t fmpc_launch_ramp_cold(const FrColdParams& P, int grid, hipStream_t st
     return hipGetLastError();
 }
 
+
 // ---------------------------------------------------------------- host side
-size_t fmpc_ramp_lds_bytes(int n, int m, int nbn) {      // sized for the 1024-thread variant (16 waves)
-    const size_t ntl = ((size_t)nbn + 1 + 15) / 16;
-    const size_t d = (size_t)m * n + 2 * (size_t)n * (n + 1) + 2 * (size_t)n + 16 * 64 + 16 + (16 * 17 + 16 * ntl + 16 * 16 + 16);
-    return d * sizeof(double);
+size_t fmpc_ramp_lds_bytes(int n, int m, int nb, int ws) {
+    const size_t ntl = ((size_t)nb * n + 1 + 15) / 16;
+    const size_t bt = ws ? 0 : (size_t)m * n;                                  // the LDS form's copy of B'
+    return (bt + 16 + (16 * 17 + 16 * ntl + 16 * (FR_NT / 64) + 16)) * sizeof(double);
 }
-size_t fmpc_ramp_ws_doubles(int n, int m, int T, int nb) { return fr_ws_layout(n, m, T, nb).total; }
+size_t fmpc_ramp_ws_doubles(int n, int m, int T, int nb, int ws, int dense_r) { return fr_ws_layout(n, m, T, nb, ws != 0, dense_r != 0).total; }
 
-hipError_t fmpc_ramp_prepare(size_t lds_bytes) {
-    hipError_t e = hipFuncSetAttribute((const void*)fmpc_newton_ramp<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)fmpc_newton_ramp<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)fmpc_newton_ramp<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+hipError_t fmpc_ramp_prepare(int ws, size_t lds_bytes) {
+    const void* k = ws ? (const void*)fmpc_newton_ramp_ws<FR_NT> : (const void*)fmpc_newton_ramp<FR_NT>;
+    return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
 }
 
-hipError_t fmpc_launch_ramp(const FmpcDevModel& M, const double* dumin, const double* dumax, int batch, int grid,
-                            const double* x0, const double* x0p, const double* w, const double* uprev,
-                            const double* zinit, const double* nu0, int max_iter, double kbar, double* zout,
-                            double* nuout, int* status, int* iters, double* step, int step_ld, double* ws,
-                            size_t ws_stride, int threads, hipStream_t stream, int it0) {
-    const size_t lds = fmpc_ramp_lds_bytes(M.n, M.m, M.nb * M.n);
-    if (threads == 1024)
-        hipLaunchKernelGGL(fmpc_newton_ramp<1024>, dim3(grid), dim3(1024), lds, stream, M, dumin, dumax, batch, x0, x0p, w, uprev,
-                           zinit, nu0, max_iter, kbar, zout, nuout, status, iters, step, step_ld, ws, ws_stride, it0);
-    else if (threads == 512)
-        hipLaunchKernelGGL(fmpc_newton_ramp<512>, dim3(grid), dim3(512), lds, stream, M, dumin, dumax, batch, x0, x0p, w, uprev,
-                           zinit, nu0, max_iter, kbar, zout, nuout, status, iters, step, step_ld, ws, ws_stride, it0);
+hipError_t fmpc_launch_ramp(const FrParams& P, int grid, hipStream_t stream) {
+    const size_t lds = fmpc_ramp_lds_bytes(P.M.n, P.M.m, P.M.nb, P.ws);
+    if (P.ws)
+        hipLaunchKernelGGL(fmpc_newton_ramp_ws<FR_NT>, dim3(grid), dim3(FR_NT), lds, stream, P.M, P.dumin, P.dumax, P.batch, P.x0, P.x0p,
+                           P.w, P.uprev, P.zinit, P.nu0, P.max_iter, P.kbar, P.zout, P.nuout, P.status, P.iters, P.step, P.step_ld,
+                           P.ws_buf, P.ws_stride);
     else
-        hipLaunchKernelGGL(fmpc_newton_ramp<256>, dim3(grid), dim3(256), lds, stream, M, dumin, dumax, batch, x0, x0p, w, uprev,
-                           zinit, nu0, max_iter, kbar, zout, nuout, status, iters, step, step_ld, ws, ws_stride, it0);
+        hipLaunchKernelGGL(fmpc_newton_ramp<FR_NT>, dim3(grid), dim3(FR_NT), lds, stream, P.M, P.dumin, P.dumax, P.batch, P.x0, P.x0p,
+                           P.w, P.uprev, P.zinit, P.nu0, P.max_iter, P.kbar, P.zout, P.nuout, P.status, P.iters, P.step, P.step_ld,
+                           P.ws_buf, P.ws_stride, P.it0);
     return hipGetLastError();
 }

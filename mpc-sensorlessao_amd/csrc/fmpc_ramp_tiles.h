@@ -1,10 +1,11 @@
-// Device pieces shared by the two ramp-rate Newton kernels: fmpc_newton_ramp (fmpc_kernel_ramp.hip, n <= 64, operands in LDS)
-// and fmpc_newton_ramp_ws (fmpc_kernel_ramp_ws.hip, any size and dense weights, operands in the HBM workspace).  The including
-// file declares fr_timing[16] first when FW_TIMING is defined.  Internal to the library.
+// Device pieces of the ramp-rate kernels (fmpc_kernel_ramp.hip): the Newton kernels fmpc_newton_ramp / fmpc_newton_ramp_ws and
+// the cold-start step fmpc_ramp_cold.  The including file declares fr_timing[16] first when FW_TIMING is defined.  Internal to the
+// library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "fmpc_tile_ops.h"
+#include "../../include/fastmpc.h"
 
 #define FR_MAX_HALVINGS 64
 #define FR_OWN 3                        // tiles of a block row a wavefront keeps in registers (fr_tile_cholesky)
@@ -25,6 +26,21 @@ __device__ __forceinline__ double fr_block_sum(double v, double* red) {
     double s = 0.0;
     for (int i = 0; i < (NT >> 6); ++i) s += red[i];
     return s;
+}
+
+// Closed form of backtracking_inf_newton.m:2-11 with the frozen barrier gradient: ||r(t)||^2 - ((1 - al t) rho)^2 = t gq(t),
+// al = 1e-4.  From t = 1, halve until gq(t) <= 0; after FR_MAX_HALVINGS halvings t = 0 and st = FMPC_W_LINESEARCH.
+__device__ __forceinline__ double fr_line_search(double rho2, double beta_e, double eps2, int& st) {
+    const double al = 1e-4;
+    double t = 1.0;
+    int halv = 0;
+    while (true) {
+        const double gq = (t - 2.0 + 2.0 * al - al * al * t) * rho2 - 2.0 * (1.0 - t) * beta_e + t * eps2;
+        if (gq <= 0.0) break;
+        t *= 0.5;
+        if (++halv >= FR_MAX_HALVINGS) { t = 0.0; st = FMPC_W_LINESEARCH; break; }
+    }
+    return t;
 }
 
 // Solve the tridiagonal system of actuator c in place (LDL' factors dg = pivots, lo = multipliers), stride m.
