@@ -335,8 +335,9 @@ int fmpc_var_identify_device(int n, int num_train, int num_samples, int batch, c
  *   FMPC_PREC_F32_MIXED  "fp32 mixed precision" (BASELINE configs[4]): Y = C Phi^-1 C', its block Cholesky factor
  *                        (inf_newton_solver.m:27,30) and the two triangular sweeps (:31-32) in fp32 on the matrix
  *                        cores; the residuals r_d, r_p (:12-17), the right-hand side (:28-29), d_z, the line search
- *                        and the iterate z, nu stay fp64, so every Newton step refines the fp32 KKT solve of the
- *                        previous one against fp64 residuals.  On request, n <= 111 with a diagonal R: 2.2 x faster than fp64
+ *                        and the iterate z, nu stay fp64.  By default nothing corrects the fp32 solve inside a Newton step:
+ *                        the next step, taken against fp64 residuals, is what refines it, so a problem the fp64 path ends
+ *                        after one step can take two; fmpc_set_refinement (below) corrects the solve inside the step.  On request, n <= 111 with a diagonal R: 2.2 x faster than fp64
  *                        at configs[4] (n = 65), 35 x faster than the exact fallback at n = 96; a step differs from the
  *                        fp64 one by ~1e-6.  The default only where it is the only matrix-core kernel that fits (fp64 tiles
  *                        beyond the LDS: very large m).
@@ -345,6 +346,20 @@ int fmpc_var_identify_device(int n, int num_train, int num_samples, int batch, c
 #define FMPC_PREC_F64        0
 #define FMPC_PREC_F32_MIXED  1
 int fmpc_set_precision(fmpc_handle h, int mode);
+
+/*
+ * Iterative refinement of the fp32 factor's solve (no counterpart in the reference).  With sweeps > 0 every Newton step of a solve
+ * that reports FMPC_PATH_TILED_F32 corrects d_nu `sweeps` times before d_z and the line search: rho = rhs - C Phi^-1 C' d_nu in
+ * fp64 against the operator itself, e = R^-1 R^-T rho with the fp32 factor already stored, d_nu += e in fp64.  No second
+ * factorisation: the factor stream is read twice more per sweep.  One sweep takes the Schur residual from ~1e-6 |rhs| to the fp64
+ * level on the AO models, which gives the fp64 paths' iteration counts and step lengths.  sweeps = 0 .. FMPC_MAX_REFINEMENT,
+ * default 0 (results are then bitwise those of a handle that never called this).  FMPC_E_NULL for a null handle, FMPC_E_DIM outside
+ * the range.  Accepted on every handle; the fp64 paths (every path but FMPC_PATH_TILED_F32) ignore it.
+ * fmpc_last_refinement: the sweeps per Newton step applied by the handle's last solve, 0 when its path was not the fp32 factor.
+ */
+#define FMPC_MAX_REFINEMENT 3
+int fmpc_set_refinement(fmpc_handle h, int sweeps);
+int fmpc_last_refinement(fmpc_handle h);
 
 /*
  * Diagnostic (no counterpart in the reference): which device path the last fmpc_solve[_device] call of

@@ -33,6 +33,7 @@ FMPC_PATH_TILED_F32 = 6
 FMPC_PATH_RAMP_WS = 7
 FMPC_PREC_F64 = 0
 FMPC_PREC_F32_MIXED = 1
+FMPC_MAX_REFINEMENT = 3
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -69,6 +70,8 @@ SIGNATURES = {
     "fmpc_set_ramp": (C.c_int, [_vp, _vp, _vp]),
     "fmpc_set_ramp_workspace": (C.c_int, [_vp, C.c_int]),
     "fmpc_set_precision": (C.c_int, [_vp, C.c_int]),
+    "fmpc_set_refinement": (C.c_int, [_vp, C.c_int]),
+    "fmpc_last_refinement": (C.c_int, [_vp]),
     "fmpc_var_identify_device": (C.c_int, [C.c_int] * 4 + [_vp] * 5),
     "fmpc_solve_ramp": (C.c_int, [_vp, C.c_int] + [_vp] * 6 + [C.c_int, C.c_double] + [_vp] * 5),
     "fmpc_solve_ramp_device": (C.c_int, [_vp, C.c_int] + [_vp] * 6 + [C.c_int, C.c_double] + [_vp] * 5 + [_vp]),

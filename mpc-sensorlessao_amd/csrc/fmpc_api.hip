@@ -132,6 +132,8 @@ struct fmpc_handle_s {
                                          // generic kernel at every batch size (round 5 measurement): the default; FMPC_FORCE_GENERIC=1: generic
     int generic_big;                     // sizes no other kernel takes (n > 79 ...), diagonal weights: the generic kernel with its tiles in the workspace
     int prec = FMPC_PREC_F64;            // FMPC_PREC_F64 / FMPC_PREC_F32_MIXED of the per-problem-factor path
+    int refine = 0;                      // fmpc_set_refinement: sweeps of iterative refinement per Newton step of the fp32 factor
+    int refine_last = 0;                 // ... of the last launch with the fp32 factor (fmpc_last_refinement)
     int force_tiled = 0;                 // FMPC_TILED=1: route every solve through the tiled kernel (tests, profiles)
     struct Tiled { int ready = 0, NB = 0, NW = 0; size_t lds = 0; DevBuf<char> pool; DevBuf<int> ipool; DevBuf<double> bm; FtModel V; } tl[2];   // bm: padded fp64 images   // [0] fp64, [1] fp32
     DevBuf<double> tl_ws; int tl_prepared = 0;                   // (bit NW: that wavefront count of the fp64 instance is prepared)
@@ -768,7 +770,9 @@ static int fmpc_tiled_plan(fmpc_handle h, int t, int batch, hipStream_t stream, 
     const bool capturing = fmpc_capturing(stream);
     int grid = batch < cap ? batch : cap;
     if (!capturing && grid_hint > 0 && grid_hint < grid) grid = grid_hint;   // (a list: as many workgroups as it is expected to be long)
-    const FtWs L = ft_ws_layout(h->n, h->m, h->T, h->nb, X.NB, t ? 4 : 8, h->denseR);
+    // (refinement of the fp32 solve keeps three more vectors per slot, behind everything else: a handle that never asks for it
+    // allocates and addresses what it always did)
+    const FtWs L = ft_ws_layout(h->n, h->m, h->T, h->nb, X.NB, t ? 4 : 8, h->denseR, (t && h->refine > 0) ? 1 : 0);
     // one workspace slot per LAUNCHED workgroup (not per workgroup the chip could hold: a warm start of one problem or a
     // continuation list of 200 would otherwise allocate 0.5-1.4 GB per handle); grown geometrically up to the full grid,
     // so that a growing sequence of batch sizes reallocates (and synchronises) a logarithmic number of times
@@ -806,7 +810,9 @@ static int fmpc_solve_tiled(fmpc_handle h, int t, const FmpcSolve& s, int nw_ove
     P.zout = s.z_out; P.nuout = s.nu_out; P.status = s.status; P.iters = s.iters; P.step = s.step; P.step_ld = fmpc_step_ld(s.n_newton);
     P.ws = h->tl_ws; P.ws_stride = plan.slot; P.u0out = s.u0_out;
     P.list = list; P.nlist = nlist; P.nuws = nuws;
+    P.refine = t ? h->refine : 0;                                     // (the fp64 instances have no such phase)
     h->tl_last_nw = plan.NWu;
+    if (t) h->refine_last = P.refine;
     if (!list) h->last_path = t ? FMPC_PATH_TILED_F32 : FMPC_PATH_TILED;
     return fmpc_launch_tiled(P, X.NB, plan.NWu, t, plan.grid, plan.ldsu, s.stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
@@ -826,6 +832,19 @@ extern "C" int fmpc_set_precision(fmpc_handle h, int mode) {
     }
     h->prec = mode;
     return FMPC_OK;
+}
+
+extern "C" int fmpc_set_refinement(fmpc_handle h, int sweeps) {
+    if (!h) return FMPC_E_NULL;
+    if (sweeps < 0 || sweeps > FMPC_MAX_REFINEMENT) return FMPC_E_DIM;
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->refine = sweeps;
+    return FMPC_OK;
+}
+extern "C" int fmpc_last_refinement(fmpc_handle h) {
+    if (!h) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return h->last_path == FMPC_PATH_TILED_F32 ? h->refine_last : 0;
 }
 
 static int fmpc_grid_for(fmpc_handle h, int batch) {

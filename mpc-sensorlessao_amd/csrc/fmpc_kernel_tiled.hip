@@ -19,8 +19,10 @@
 //           tiles of the row, Rwide(kb,.) = W P(kb,.) (4 MFMAs per tile), into LDS (operands of the following rows and
 //           stages) and into the factor stream in HBM (read back once by P4).
 // Column n of the blocks carries rhs_i -> y_i, so the forward substitution needs no instruction of its own.
-// REAL = float: Y, the factor and both sweeps in fp32; r_d, r_p, the rhs, the line search and z, nu stay fp64
-// (the Newton iteration itself is the fp64 residual refinement of the fp32 KKT solves).
+// REAL = float: Y, the factor and both sweeps in fp32; r_d, r_p, the rhs, the line search and z, nu stay fp64.
+// Left at that, the Newton iteration itself is the only fp64 refinement of the fp32 KKT solves (a solve leaves ~1e-6 |rhs| in the
+// Schur system, which costs a Newton step against the fp64 path where the exit test is absolute).  FtParams::refine > 0 adds
+// classical iterative refinement of d_nu inside the step, between P4 and P5: ft_phase_refres, ft_forward, ft_backward<.., true>.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -57,7 +59,8 @@ __device__ __forceinline__ int ft_lt_index(int NB, int I, int J) { return I * NB
 
 // P4 as a function of its own (not inlined): the backward sweep needs few registers, but inside the kernel body it
 // inherits the register pressure of the factor phase and its loads get spilled addresses with full waits in front.
-template <typename R, int NB, int NW>
+// ACC (a refinement sweep): the solution is a correction, added in fp64 to the d_nu that is in the staging area.
+template <typename R, int NB, int NW, bool ACC = false>
 __device__ __noinline__ void ft_backward(const R* fac_, const double* yv_, R* sXV_, R* sPART_, double* sNU_, int n, int nb, int NUROWS) {
     // The arguments arrive as generic pointers: left so, every access below is a FLAT one -- counted on both memory
     // counters, possibly out of order, so the compiler waits for everything in flight before each use and no request can
@@ -80,7 +83,8 @@ __device__ __noinline__ void ft_backward(const R* fac_, const double* yv_, R* sX
     constexpr int MAXT = (REC_TILES - 1 + NG - 1) / NG;    // tiles 1 .. 3 NB - 1 of a record, dealt to the groups
     const int tg = tid >> 8, ta = (tid >> 4) & (RSTEP - 1), tb = tid & 15;
     for (int q = tid; q < 3 * NP; q += NT) sXV[q] = (R)0;
-    for (int q = tid; q < NUROWS * LDN; q += NT) sNU[q] = 0.0;   // d_nu as [stage][state] for P5 (the U slots are dead)
+    if (!ACC)
+        for (int q = tid; q < NUROWS * LDN; q += NT) sNU[q] = 0.0;   // d_nu as [stage][state] for P5 (the U slots are dead)
     __syncthreads();
     if (NB > 2) {
         // One record (block row) per step, the records of the NEXT G steps requested a group ahead: the factor stream of a
@@ -143,7 +147,7 @@ __device__ __noinline__ void ft_backward(const R* fac_, const double* yv_, R* sX
                     if (tb == 0) {
                         const int lr = ta + RSTEP * h;
                         XC[16 * kb + lr] = xv;
-                        if (16 * kb + lr < n) sNU[i * LDN + 16 * kb + lr] = (double)xv;
+                        if (16 * kb + lr < n) { if (ACC) sNU[i * LDN + 16 * kb + lr] += (double)xv; else sNU[i * LDN + 16 * kb + lr] = (double)xv; }
                     }
                 }
             }
@@ -243,7 +247,7 @@ __device__ __noinline__ void ft_backward(const R* fac_, const double* yv_, R* sX
                     if (tb == 0) {
                         const int lr = ta + RSTEP * h;
                         XC[16 * kb + lr] = xv;
-                        if (16 * kb + lr < n) sNU[i * LDN + 16 * kb + lr] = (double)xv;
+                        if (16 * kb + lr < n) { if (ACC) sNU[i * LDN + 16 * kb + lr] += (double)xv; else sNU[i * LDN + 16 * kb + lr] = (double)xv; }
                     }
                 }
             }
@@ -252,6 +256,132 @@ __device__ __noinline__ void ft_backward(const R* fac_, const double* yv_, R* sX
     }
     }
 
+}
+
+// Forward substitution R'y = rho with the stored factor, for a refinement sweep (FtParams::refine; the forward sweep of the Newton
+// step itself rides in column n of the blocks while they are factored).  The mirror of ft_backward: the same records, from stage 0
+// upward, requested a group ahead, every load unconditional at a constant offset from an opaque record offset.  A record is a ROW
+// of R, and R' y needs its columns, so the sweep runs in the PUSH orientation: once y of the 16-row block (i, kb) is known,
+// tile' y is subtracted from the right-hand sides of the blocks the record's tiles point at -- R(kb, J) at (i, J), U1(kb, J) at
+// (i + 1, J), U2(kb, J) at (i + 2, J) -- which are kept in LDS for the three stages i, i + 1, i + 2 (sACC: the x vectors of the
+// backward sweep).  A tile is read by ONE wavefront, 16 bytes per lane (lane l: row l / 4, columns 4 (l % 4) ..+3, a contiguous
+// kilobyte), so the sum over the tile's rows stays inside the wavefront (two DPP rotations, two lane exchanges) and every
+// right-hand side has one writer per step: the order of the fp32 sums is fixed.  rho is read from yv and y written over it.
+template <typename R>
+__device__ __forceinline__ ft_f4 ft_col_sum4(ft_f4 v) {      // sum over the lanes l = c (mod 4) of a wavefront, per component
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        R x = v[k];
+        x += ft_dpp<0x124>(x); x += ft_dpp<0x128>(x);
+        x += __shfl_xor(x, 16, 64); x += __shfl_xor(x, 32, 64);
+        v[k] = x;
+    }
+    return v;
+}
+template <typename R, int NB, int NW>
+__device__ __noinline__ void ft_forward(const R* fac_, double* yv_, R* sACC_, R* sY_, int n, int nb) {
+    static_assert(sizeof(R) == 4, "refinement exists for the fp32 factor only");
+    typedef const ft_f4 __attribute__((address_space(1))) * GV;
+    typedef const R __attribute__((address_space(1))) * GR;
+    typedef double __attribute__((address_space(1))) * GD;
+    typedef R __attribute__((address_space(3))) * LR;
+    typedef ft_f4 __attribute__((address_space(3))) * LV;
+    const GR fac = (GR)fac_;
+    const GD yv = (GD)yv_;
+    const LR sACC = (LR)sACC_, sY = (LR)sY_;
+    constexpr int NT = NW * 64, NP = 16 * NB, REC_TILES = 3 * NB;
+    constexpr int MAXT = (REC_TILES - 1 + NW - 1) / NW;    // tiles 1 .. 3 NB - 1 of a record, dealt to the wavefronts
+    constexpr int G = 3;
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tr = lane >> 2, cq = lane & 3;
+    const int nblk = nb * NB;
+    for (int q = tid; q < 3 * NP; q += NT) {                // right-hand sides of the stages 0, 1, 2
+        const int i = q / NP, e = q - i * NP;
+        const double v = yv[(i < nb ? i : nb - 1) * n + (e < n ? e : n - 1)];
+        sACC[q] = (i < nb && e < n) ? (R)v : (R)0;
+    }
+    __syncthreads();
+    ft_f4 tvA[G][MAXT], rivA[G];
+    double rhA[G];
+    auto request = [&](int base, ft_f4 (&tv)[G][MAXT], ft_f4 (&riv)[G], double (&rh)[G]) {
+#pragma unroll
+        for (int u = 0; u < G; ++u) {
+            const int blk = base + u < nblk ? base + u : nblk - 1;      // (past the end of the horizon: a harmless re-read)
+            unsigned off = (unsigned)blk * (unsigned)(REC_TILES * FT_TILE) + (unsigned)(4 * lane);
+            asm volatile("" : "+v"(off));
+            const GR rec = fac + off;
+#pragma unroll
+            for (int q = 0; q < MAXT; ++q) {
+                const int t = 1 + wv + q * NW;
+                const int tc = t < REC_TILES ? t : REC_TILES - 1;
+                tv[u][q] = *(GV)(rec + tc * FT_TILE);
+            }
+            riv[u] = *(GV)rec;
+            // rho of the block that takes this one's place in LDS: (i + 3, kb)
+            const int i = blk / NB, kb = blk - i * NB, row = 16 * kb + (lane & 15);
+            rh[u] = yv[(i + 3 < nb ? i + 3 : nb - 1) * n + (row < n ? row : n - 1)];
+        }
+    };
+    auto step = [&](int blk, ft_f4 (&tv)[MAXT], ft_f4 riv, double rh) {
+        const int i = blk / NB, kb = blk - i * NB;
+        const int s0 = (i % 3) * NP, s1 = ((i + 1) % 3) * NP, s2 = ((i + 2) % 3) * NP;
+        // y_kb = R(kb,kb)^-T t_kb with t_kb the right-hand side less everything pushed so far
+        if (wv == 0) {
+            ft_f4 v = riv * sACC[s0 + 16 * kb + tr];
+            v = ft_col_sum4<R>(v);
+            if (lane < 4) {
+                *(LV)(sY + 4 * cq) = v;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int row = 16 * kb + 4 * cq + k;
+                    if (row < n) yv[i * n + row] = (double)v[k];
+                }
+            }
+        }
+        ft_lds_barrier();
+        const R yr = sY[tr];
+#pragma unroll
+        for (int q = 0; q < MAXT; ++q) {
+            const int t = 1 + wv + q * NW;
+            const int tc = t < REC_TILES ? t : REC_TILES - 1;
+            const bool use = t < REC_TILES && (t >= NB || t > kb);     // (tiles 1..kb of a record do not exist)
+            const ft_f4 zero = {0, 0, 0, 0};
+            ft_f4 v = (use ? tv[q] : zero) * yr;
+            v = ft_col_sum4<R>(v);
+            const int J = tc < NB ? tc : (tc < 2 * NB ? tc - NB : tc - 2 * NB);
+            const int sl = tc < NB ? s0 : (tc < 2 * NB ? s1 : s2);
+            if (use && lane < 4) {
+                const LV dst = (LV)(sACC + sl + 16 * J + 4 * cq);
+                ft_f4 a = *dst;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) a[k] -= 16 * J + 4 * cq + k < n ? v[k] : (R)0;   // (column n of a tile is the riding rhs)
+                *dst = a;
+            }
+        }
+        // the block just solved makes room for the same block three stages on
+        if (wv == NW - 1 && lane < 16) sACC[s0 + 16 * kb + lane] = (i + 3 < nb && 16 * kb + lane < n) ? (R)rh : (R)0;
+        ft_lds_barrier();
+    };
+    int base = 0;
+    for (int left = nblk % G; left > 0; --left, ++base) {
+        request(base, tvA, rivA, rhA);
+        step(base, tvA[0], rivA[0], rhA[0]);
+    }
+    request(base, tvA, rivA, rhA);
+    for (; base < nblk; base += G) {
+        ft_f4 tvB[G][MAXT], rivB[G];
+        double rhB[G];
+        request(base + G, tvB, rivB, rhB);
+#pragma unroll
+        for (int u = 0; u < G; ++u) step(base + u, tvA[u], rivA[u], rhA[u]);
+#pragma unroll
+        for (int u = 0; u < G; ++u) {
+#pragma unroll
+            for (int q = 0; q < MAXT; ++q) tvA[u][q] = tvB[u][q];
+            rivA[u] = rivB[u];
+            rhA[u] = rhB[u];
+        }
+    }
 }
 
 // (dense R: ft_dense_r lives in fmpc_dense_r.h, shared with the generic kernel's workspace instance)
@@ -1017,6 +1147,113 @@ __device__ __noinline__ FtStep ft_phase_update(FtKP Pin, int p, double rho2) {
     return out;
 }
 
+// The residual of a refinement sweep (fp32 factor, FtParams::refine): rho = rhs - Y d_nu in fp64 with Y = C Phi^-1 C' APPLIED, never
+// formed -- C' d_nu and Phi^-1 as P5 does them, C as P2 does, the same zero-padded fp64 operands on the fp64 matrix cores (the
+// fp32 image of Y that the factor phase reads is what the refinement corrects for, so it has no part here).  d_nu is in the
+// staging area (left there by P4), rhs in the copy P2 kept; rho goes to yv, where the forward sweep takes it.  phx is free between
+// P2 and the next P1.  Workgroup-collective.
+template <typename R, int NB, int NW>
+__device__ __noinline__ void ft_phase_refres(FtKP Pin) {
+    FT_VIEW(R, NB, NW, false);
+    const double* rhs = wsp + L.rhs;
+    double* pu = wsp + L.pu;
+    double* vx = wsp + L.vx;
+    const bool dq = P->V.denseQ != 0;
+    for (int item = wv; item < NB * TA + mb * TA; item += NW) {
+        ft_d4 acc = {0, 0, 0, 0};
+        if (item < NB * TA) {
+            // ---- (C' d_nu)[x_j] = d_nu_{j-1} - A1' d_nu_j - A2' d_nu_{j+1}  [+ d_nu_T], then (2Q_j)^-1 of it
+            const int Jr = item / TA, A = item - Jr * TA;
+            const int jj = 16 * A + c, r = 16 * Jr + c;
+            const bool rok = r < n;
+            const double f1 = jj + 1 < T ? 1.0 : 0.0, f2 = jj + 2 < T ? 1.0 : 0.0;
+            ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
+                        [&](int k) { return sNU[(jj + 1) * LDN + k] * f1; },
+                        [&](int k) { return P->V.A1P[k * NP + r]; });
+            if (var2)
+                ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
+                            [&](int k) { return sNU[(jj + 2) * LDN + k] * f2; },
+                            [&](int k) { return P->V.A2P[k * NP + r]; });
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int jo = 16 * A + g + 4 * rr;
+                if (jo < T && rok) {
+                    const bool last = jo + 1 == T;
+                    double v = sNU[jo * LDN + r] - acc[rr];
+                    if (last && P->M.has_xf) v += sNU[T * LDN + r];
+                    if (dq) vx[jo * n + r] = v;                                            // dense weights: the product below
+                    else phx[jo * n + r] = v * ft_rcp(last ? P->M.Qf2[r] : P->M.Q2[r]);
+                }
+            }
+        } else {
+            // ---- (C' d_nu)[u_j] = -B' d_nu_j, then Rt_j^-1 of it
+            const int it3 = item - NB * TA, J = it3 / TA, A = it3 - J * TA;
+            const int j = 16 * A + c, q = 16 * J + c;
+            const bool qok = q < m;
+            ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
+                        [&](int k) { return sNU[j * LDN + k]; },
+                        [&](int k) { return P->V.BmP[(size_t)k * MP + q]; });
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int jo = 16 * A + g + 4 * rr;
+                if (jo < T && qok) pu[jo * m + q] = -acc[rr] * winv[jo * m + q];
+            }
+        }
+    }
+    __syncthreads();
+    if (dq) {
+        for (int item = wv; item < NB * TA; item += NW) {
+            const int Jr = item / TA, A = item - Jr * TA;
+            const int jj = 16 * A + c, r = 16 * Jr + c;
+            const double* vj = vx + (size_t)(jj < T ? jj : T - 1) * n;
+            const double fq = jj + 1 < T ? 1.0 : 0.0, fqf = jj + 1 == T ? 1.0 : 0.0;
+            ft_d4 acc = {0, 0, 0, 0};
+            ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
+                        [&](int k) { return vj[k < n ? k : n - 1] * fq; },
+                        [&](int k) { return P->V.XP[k * NP + r]; });
+            ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
+                        [&](int k) { return vj[k < n ? k : n - 1] * fqf; },
+                        [&](int k) { return P->V.XfP[k * NP + r]; });
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int jo = 16 * A + g + 4 * rr;
+                if (jo < T && r < n) phx[jo * n + r] = acc[rr];
+            }
+        }
+        __syncthreads();
+    }
+    // ---- rho_i = rhs_i - (C p)_i with p = Phi^-1 C' d_nu: the products of P2
+    for (int item = wv; item < NB * TA; item += NW) {
+        const int Jr = item / TA, A = item - Jr * TA;
+        const int i = 16 * A + c, r = 16 * Jr + c;
+        const bool rok = r < n;
+        ft_d4 acc = {0, 0, 0, 0};
+        const size_t iu = (size_t)(i < T ? i : T - 1) * m;
+        const double* ph1 = phx + (size_t)((i >= 1 && i < T) ? i - 1 : 0) * n;
+        const double* ph2 = phx + (size_t)((i >= 2 && i < T) ? i - 2 : 0) * n;
+        const double f1 = (i >= 1 && i < T) ? 1.0 : 0.0, f2 = (i >= 2 && i < T) ? 1.0 : 0.0;
+        ft_vec_gemm<12>(acc, MP, g,
+                    [&](int k) { return pu[iu + (k < m ? k : m - 1)]; },
+                    [&](int k) { return P->V.BtP[(size_t)k * NP + r]; });
+        ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
+                    [&](int k) { return ph1[k < n ? k : n - 1] * f1; },
+                    [&](int k) { return P->V.A1tP[k * NP + r]; });
+        if (var2)
+            ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
+                        [&](int k) { return ph2[k < n ? k : n - 1] * f2; },
+                        [&](int k) { return P->V.A2tP[k * NP + r]; });
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int io = 16 * A + g + 4 * rr;
+            if (io < nb && rok) {
+                const double cv = io < T ? phx[io * n + r] - acc[rr] : phx[(T - 1) * n + r];
+                yv[io * n + r] = rhs[io * n + r] - cv;
+            }
+        }
+    }
+    __syncthreads();
+}
+
 // NL: live rows of the last 16-row block of a stage, n - 16 (NB - 1), when known at compile time (the AO sizes), else -1
 template <typename R, int NB, int NW, int NL, bool DR = false>
 __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
@@ -1066,6 +1303,8 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
     double* phx = wsp + L.phx;
     double* rp = wsp + L.rp;
     double* yv = wsp + L.y;
+    constexpr bool REFINE = sizeof(R) == 4 && !DR;                  // iterative refinement of d_nu: the fp32 factor's instances only
+    [[maybe_unused]] double* rhsc = wsp + L.rhs;
     R* fac = (R*)(wsp + L.fac);
     R* gws = (R*)(wsp + L.gt);
     constexpr int STAGE_TILES = 3 * NB * NB, REC_TILES = 3 * NB;       // factor stream: one record per 16-row block
@@ -1198,6 +1437,7 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
                     if (io < nb && rok) {
                         const double cv = io < T ? phx[io * n + r] - acc[rr] : phx[(T - 1) * n + r];
                         yv[io * n + r] = rp[io * n + r] - cv;
+                        if constexpr (REFINE) { if (P.refine > 0) rhsc[io * n + r] = rp[io * n + r] - cv; }   // (the factor phase turns yv into y)
                     }
                 }
             }
@@ -1236,6 +1476,18 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
             // current one is reduced.  x of stage i lives in buffer i % 3.
             ft_backward<R, NB, NW>(fac, yv, sXV, sPART, sNU, n, nb, NUROWS);
             __syncthreads();
+            // ================= iterative refinement of the fp32 solve (on request): rho = rhs - Y d_nu in fp64 against the operator
+            // itself, e = R^-1 R^-T rho with the factor just stored (two more reads of its stream, no factorisation), d_nu += e in fp64.
+            // The rounding of rho to fp32 on the way in and of e on the way out is the method: each sweep takes ~2^-24 cond(Y) off.
+            if constexpr (REFINE) {
+                for (int sw = 0; sw < P.refine; ++sw) {
+                    ft_phase_refres<R, NB, NW>(ft_params());
+                    ft_forward<R, NB, NW>(fac, yv, sXV, sPART, n, nb);
+                    __syncthreads();                                   // y is in HBM (same workgroup reads it)
+                    ft_backward<R, NB, NW, true>(fac, yv, sXV, sPART, sNU, n, nb, NUROWS);
+                    __syncthreads();
+                }
+            }
             FT_TICK(7);
 
             // ================= P5: d_z, line-search scalars, update (the same stage-batched GEMMs with d_nu)

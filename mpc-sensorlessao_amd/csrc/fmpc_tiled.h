@@ -5,7 +5,8 @@
 // block of the Schur complement handled as NB x NB tiles of 16 x 16 (n_pad = 16 NB >= n + 1: column n of a stage's
 // blocks carries the right-hand side, so the forward substitution rides along in the matrix products).  It is
 // templated on the arithmetic type of the factorisation: double (parity path) or float ("fp32 mixed precision":
-// fp32 factor and substitutions, all residuals, the line search and the iterate in fp64).
+// fp32 factor and substitutions, all residuals, the line search and the iterate in fp64; on request the solve for d_nu is
+// refined against the fp64 Schur operator with the stored factor, FtParams::refine).
 #pragma once
 #include <stddef.h>
 #include <hip/hip_runtime.h>
@@ -50,8 +51,12 @@ struct FtModel {
 // Per-workgroup scratch in HBM.  Vectors in doubles, then the factor stream in REAL.
 struct FtWs {
     size_t b, nu, hess, winv, rdu, rdx, phx, rp, y, dnu, zt, gt, fac, total;   // offsets in doubles
+    size_t rhs, pu, vx;     // iterative refinement of the fp32 solve (behind everything else: nothing moves when it is off)
 };
-__host__ __device__ static inline FtWs ft_ws_layout(int n, int m, int T, int nb, int NB, int real_bytes, int denseR = 0) {
+// refine: the slot also holds what the refinement sweeps need -- the fp64 rhs of the Schur system (the factor phase turns the
+// one in `y` into the forward sweep's result), Phi^-1 C' d_nu on the inputs, C' d_nu on the states (dense Q, Qf).  The kernel
+// takes the offsets from the layout without the flag: they are the same, only `total` grows.
+__host__ __device__ static inline FtWs ft_ws_layout(int n, int m, int T, int nb, int NB, int real_bytes, int denseR = 0, int refine = 0) {
     FtWs L; size_t o = 0;
     const size_t nbn = (size_t)nb * n, Tm = (size_t)T * m, Tn = (size_t)T * n;
     auto take = [&](size_t cnt) { size_t r = o; o += (cnt + 1) & ~(size_t)1; return r; };
@@ -65,6 +70,9 @@ __host__ __device__ static inline FtWs ft_ws_layout(int n, int m, int T, int nb,
     L.fac = o;
     o += ((size_t)nb * ft_stage_tiles(NB) * FT_TILE * real_bytes + 7) / 8;
     L.total = (o + 31) & ~(size_t)31;
+    o = L.total;
+    L.rhs = take(nbn); L.pu = take(Tm); L.vx = take(Tn);
+    if (refine) L.total = (o + 31) & ~(size_t)31;
     return L;
 }
 
@@ -117,6 +125,7 @@ struct FtParams {
     // from the compacted list the decision launch wrote (entry = problem | FT_LIST_HANDED: redo from the cold start; else z+ is in
     // zout and nu+ in the panel workspace, the first step is done).  list == NULL: all problems 0 .. batch-1 from the start.
     const int* list; const int* nlist; const double* nuws;
+    int refine;             // fp32 factor only: sweeps of iterative refinement of d_nu per Newton step (fmpc_set_refinement), 0 = none
 };
 #define FT_LIST_HANDED (1 << 30)       // (= FW_LIST_HANDED of fmpc_kernel_wave.hip)
 #define FT_LIST_GENERAL (1 << 29)      // (= FW_LIST_GENERAL) continue behind ONE step of the one-wavefront kernel from an explicit start: z in

@@ -109,6 +109,17 @@ class FastMPCHandle:
         if rc != _lib.FMPC_OK:
             raise FastMPCError(rc, "fmpc_set_precision")
 
+    def set_refinement(self, sweeps):
+        """fmpc_set_refinement: sweeps (0 .. 3, default 0) of fp64 iterative refinement of the fp32 factor's solve per Newton step.
+        Accepted on every handle; acts on solves that report FMPC_PATH_TILED_F32 (set_precision('f32')), ignored by the fp64 paths."""
+        rc = self._lib.fmpc_set_refinement(self._h, int(sweeps))
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_set_refinement")
+
+    def last_refinement(self):
+        """Sweeps per Newton step the last solve applied (fmpc_last_refinement): 0 unless its path was the fp32 factor."""
+        return int(self._lib.fmpc_last_refinement(self._h))
+
     def solve(self, x0, x0_pre=None, w=None, z_init=None, nu0=None, n_newton=1, k=1e-2,
               return_info=False, check=True, u_prev=None, z_out=None):
         """One `inf_newton_solver` per problem.  x0: (batch, n) or (n,).  Returns z (batch, N_z)
