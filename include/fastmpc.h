@@ -328,6 +328,59 @@ int fmpc_var_identify_device(int n, int num_train, int num_samples, int batch, c
                              double* A1, double* A2, int* status, void* stream);
 
 /*
+ * Model bank: one VAR model (A1, A2) per problem of a batched solve.  In the reference a realisation's model is its own: A1, A2 are
+ * identified from the training stretch of that realisation's coefficient series (README.md:108-130) and handed to Fast_MPC2
+ * (README.md:548-556).  B, the weights, the bounds and T belong to the mirror and the controller and stay the handle's.
+ *
+ * fmpc_bank_set_device: count models; A1, A2: count arrays n x n column-major in DEVICE memory, exactly what
+ * fmpc_var_identify_device writes (A2 is ignored for var_order 1 and may be NULL then).  Builds the bank's device images -- per model
+ * the operands of the state recursion (fast_mpc_eq_const.m:39-47) and the constant blocks of Y = C Phi^-1 C'
+ * (inf_newton_solver.m:27) in the arithmetic of the handle's precision at the time of the call -- on `stream`, one workgroup
+ * per model; replaces an earlier bank.  The inputs are not retained.  Call fmpc_set_precision first: a bank built for the other
+ * arithmetic is not used (FMPC_E_UNSUPPORTED from the bank solve).
+ * FMPC_E_UNSUPPORTED, before anything is enqueued: the tiled kernel has no instance for the handle's size in its precision
+ * (fp64: n <= 79; fp32 factor: n <= 111), or the handle has ramp-rate rows.  While `stream` is being captured a bank that has to
+ * grow gives FMPC_E_ALLOC (as every allocation does; fmpc_alloc_generation moves whenever the bank is allocated or released).
+ * A call that fails while it allocates leaves the handle WITHOUT a bank (fmpc_bank_count 0); one refused under capture leaves the
+ * bank as it was.  The bank calls of a handle on different streams are ordered on the device like its solves.
+ * fmpc_bank_release frees the bank's memory; it synchronises the device first (a bank solve in flight reads the images), so it must
+ * not be called while a stream is being captured -- as fmpc_destroy must not.
+ * Every other entry point ignores the bank: fmpc_solve*, fmpc_loop_*, fmpc_ao_step_device answer from the fmpc_create model.
+ */
+int fmpc_bank_set_device(fmpc_handle h, int count, const double* A1, const double* A2, void* stream);
+int fmpc_bank_count(fmpc_handle h);          /* 0 = no bank (also for a NULL handle) */
+int fmpc_bank_release(fmpc_handle h);
+
+/*
+ * fmpc_solve_u0_device where problem p uses model model_of[p] of the bank (device int array; NULL = model p, then
+ * batch <= count).  Same arguments, outputs, status codes and step record otherwise; u0_out and z_out may each be NULL, not both.
+ * A problem whose index is outside [0, count) gets status FMPC_E_DIM and iters 0, nothing of a model is read for it and its other
+ * outputs are not written; the other problems are unaffected.
+ * The factor of Y is no longer shared between problems, so none of the shared-factor cold-start forms applies: a bank solve
+ * always runs the per-problem-factor tiled kernel (inf_newton_solver.m:10-41 per problem), from the cold start too;
+ * fmpc_last_dispatch reports FMPC_PATH_TILED / FMPC_PATH_TILED_F32, fmpc_set_refinement is honoured.
+ * FMPC_E_UNSUPPORTED, before anything is enqueued: no bank, a bank built for the other precision, ramp-rate rows, padded z
+ * rows (fmpc_set_z_ld), model_of == NULL with batch > count.
+ * Once the bank and the workspace exist the call allocates nothing and does not synchronise: it can be recorded into a HIP graph.
+ */
+int fmpc_solve_bank_device(fmpc_handle h, int batch, const int* model_of,
+                           const double* x0, const double* x0_pre, const double* w,
+                           const double* z_init, const double* nu0, int n_newton, double k,
+                           double* z_out, double* nu_out, int* status, int* iters, double* step,
+                           double* u0_out, void* stream);
+
+/*
+ * fmpc_loop_inputs_device with the bank's models (README.md:482-497): x0 = a_k + B u1, x0_pre = x0_last,
+ * w = -M1 B u1 - M2 B u2 with M1, M2 of model model_of[p] (NULL: model p) -- computed as the free response of that model,
+ * p_i = A1 p_{i-1} + A2 p_{i-2} from p_-1 = B u1, p_-2 = B u2, w_i = -p_i, which is what the prediction matrices of
+ * MPC_DesignMatrices express; no M1, M2 are stored per model.  NULL u1 / u2 / x0_last drop their terms, x0 may alias x0_last.
+ * A problem whose index is outside the bank is left alone (nothing written).  FMPC_E_UNSUPPORTED without a bank.
+ */
+int fmpc_loop_inputs_bank_device(fmpc_handle h, int batch, const int* model_of,
+                                 const double* a_k, const double* x0_last, const double* u1,
+                                 const double* u2, double* x0, double* x0_pre, double* w, void* stream);
+
+/*
  * Arithmetic of the per-problem-factor path (no counterpart in the reference, which is fp64 throughout).
  *   FMPC_PREC_F64        everything in fp64: the default wherever an fp64 kernel on the matrix cores exists (n <= 79; round 5 --
  *                        the reference is fp64 throughout and the literal call fmpc_solve_once has no precision argument) and

@@ -18,6 +18,7 @@
 #include "fmpc_loopu0.h"
 #include "fmpc_tiled.h"
 #include "fmpc_rampcold.h"
+#include "fmpc_bank.h"
 #define FMPC_PRODUCT_MIN_BATCH_DEFAULT 65   // closed-loop steps with first moves only: the product form from this many realisations on
 #include "fmpc_alloc.h"                    // owned, counted buffers (fmpc_alloc_generation), shared with fmpc_est_api.hip
 
@@ -136,6 +137,13 @@ struct fmpc_handle_s {
     int refine_last = 0;                 // ... of the last launch with the fp32 factor (fmpc_last_refinement)
     int force_tiled = 0;                 // FMPC_TILED=1: route every solve through the tiled kernel (tests, profiles)
     struct Tiled { int ready = 0, NB = 0, NW = 0; size_t lds = 0; DevBuf<char> pool; DevBuf<int> ipool; DevBuf<double> bm; FtModel V; } tl[2];   // bm: padded fp64 images   // [0] fp64, [1] fp32
+    // model bank (fmpc_bank_set_device): per model the plain and padded images of A1, A2 and the constant Y tiles; one block table
+    // for all models, built from the handle alone and uploaded once
+    struct Bank {
+        int count = 0, t = 0, nblk = 0, table_ready = 0, prepared[2] = {0, 0};
+        size_t plain_stride = 0, pad_stride = 0, yimg_stride = 0;    // doubles, doubles, elements of the factor's type
+        DevBuf<double> plain, pad; DevBuf<char> yimg; DevBuf<int> ipool;   // ipool: [desc | iD | i1 | i2]
+    } bank;
     DevBuf<double> tl_ws; int tl_prepared = 0;                   // (bit NW: that wavefront count of the fp64 instance is prepared)
     int tl_last_nw = 0;                   // wavefronts per problem of the last tiled launch (diagnostic)
     int z_ld = 0;                         // fmpc_set_z_ld: doubles between the z rows of consecutive problems (0: T (n + m))
@@ -1471,6 +1479,172 @@ static int fmpc_solve_device_impl(fmpc_handle h, FmpcSolve s) {
     if (rc != FMPC_OK) return rc;
     rc = fmpc_solve_device_inner(h, s);
     fmpc_guard_end(h, s.stream);
+    return rc;
+}
+
+// ---- model bank (include/fastmpc.h; fmpc_bank.h, fmpc_kernel_bank.hip)
+static int fmpc_bank_unsupported(fmpc_handle h, int t) {
+    if (h->ramp_du.p) return 1;                                        // ramp-rate rows: their kernels have no bank form
+    return fmpc_tiled_supports(h->n, h->m, h->nb, t, nullptr, nullptr, h->denseR) ? 0 : 1;
+}
+extern "C" int fmpc_bank_set_device(fmpc_handle h, int count, const double* A1, const double* A2, void* stream_) {
+    if (!h || !A1) return FMPC_E_NULL;
+    if (h->var_order == 2 && !A2) return FMPC_E_NULL;
+    if (count <= 0) return FMPC_E_DIM;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int t = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
+    if (fmpc_bank_unsupported(h, t)) return FMPC_E_UNSUPPORTED;
+    fmpc_handle_s::Tiled& X = h->tl[t];
+    fmpc_handle_s::Bank& B = h->bank;
+    const bool capturing = fmpc_capturing(stream);
+    if (!X.ready) {
+        if (capturing) return FMPC_E_ALLOC;
+        const int rc = t ? fmpc_tiled_build<float>(h, 1, stream) : fmpc_tiled_build<double>(h, 0, stream);
+        if (rc != FMPC_OK) return rc;
+    }
+    const int n = h->n, nb = h->nb, NB = X.NB, NP = 16 * NB, NQ = NB * NB;
+    if (!B.table_ready) {
+        if (capturing) return FMPC_E_ALLOC;
+        FmpcBankTable tab;
+        const bool xf_is_x = h->hm_xm.size() == h->hm_xfm.size() &&
+                             memcmp(h->hm_xm.data(), h->hm_xfm.data(), h->hm_xm.size() * sizeof(double)) == 0;
+        fmpc_host_bank_table(h->T, h->var_order == 2, h->has_xf != 0, xf_is_x, tab);
+        const int nblk = (int)tab.blocks.size();
+        std::vector<int> ids((size_t)nblk * FB_DESC_INTS, 0);
+        for (int k = 0; k < nblk; ++k) {
+            int* d = ids.data() + (size_t)k * FB_DESC_INTS;
+            d[0] = tab.blocks[k].nterms;
+            for (int q = 0; q < tab.blocks[k].nterms; ++q) {
+                const FmpcBankTerm& tm = tab.blocks[k].t[q];
+                d[1 + 4 * q] = tm.sign; d[2 + 4 * q] = tm.L; d[3 + 4 * q] = tm.X; d[4 + 4 * q] = tm.R;
+            }
+        }
+        for (int i = 0; i < nb; ++i) ids.push_back(tab.idxD[i]);
+        for (int i = 0; i < nb; ++i) ids.push_back(tab.idx1[i] >= 0 ? tab.idx1[i] : nblk);
+        for (int i = 0; i < nb; ++i) ids.push_back(tab.idx2[i] >= 0 ? tab.idx2[i] : nblk);
+        const int rc = B.ipool.assign(ids.data(), ids.size(), stream);
+        if (rc != FMPC_OK) return rc;
+        B.nblk = nblk; B.table_ready = 1;
+    }
+    if (!B.prepared[t]) {
+        if (fmpc_tiled_prepare(n, NB, X.NW, t, X.lds, h->denseR, 1) != hipSuccess) return FMPC_E_HIP;
+        if (fmpc_bank_build_prepare(NB, t) != hipSuccess) return FMPC_E_HIP;
+        B.prepared[t] = 1;
+    }
+    const size_t plain_stride = 4 * (size_t)n * n, pad_stride = 4 * (size_t)NP * NP;
+    const size_t yimg_stride = (size_t)(B.nblk + 1) * NQ * FT_TILE;
+    const size_t ybytes = yimg_stride * (size_t)count * (t ? sizeof(float) : sizeof(double));
+    if (capturing && (plain_stride * (size_t)count > B.plain.cap || pad_stride * (size_t)count > B.pad.cap || ybytes > B.yimg.cap))
+        return FMPC_E_ALLOC;                                           // (the bank that is there stays as it is)
+    B.count = 0;                                                       // (no bank while it is being replaced)
+    int rc = fmpc_guard_begin(h, stream);                             // (an earlier bank solve may still read the old images)
+    if (rc != FMPC_OK) return rc;
+    rc = B.plain.grow(plain_stride * (size_t)count, stream);
+    if (rc == FMPC_OK) rc = B.pad.grow(pad_stride * (size_t)count, stream);
+    if (rc == FMPC_OK) rc = B.yimg.grow(ybytes, stream);
+    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }      // (the handle is left without a bank)
+    FbParams Q;
+    Q.n = n; Q.NB = NB; Q.count = count; Q.nblk = B.nblk; Q.is_float = t;
+    Q.A1 = A1; Q.A2 = h->var_order == 2 ? A2 : nullptr;
+    Q.XP = X.V.XP; Q.XfP = X.V.XfP; Q.desc = B.ipool;
+    Q.plain = B.plain; Q.plain_stride = plain_stride; Q.pad = B.pad; Q.pad_stride = pad_stride;
+    Q.yimg = B.yimg.p; Q.yimg_stride = yimg_stride;
+    const bool launched = fmpc_launch_bank_build(Q, stream) == hipSuccess;
+    fmpc_guard_end(h, stream);
+    if (!launched) return FMPC_E_HIP;
+    B.plain_stride = plain_stride; B.pad_stride = pad_stride; B.yimg_stride = yimg_stride;
+    B.t = t; B.count = count;
+    return FMPC_OK;
+}
+extern "C" int fmpc_bank_count(fmpc_handle h) {
+    if (!h) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return h->bank.count;
+}
+extern "C" int fmpc_bank_release(fmpc_handle h) {
+    if (!h) return FMPC_E_NULL;
+    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    std::lock_guard<std::mutex> lk(h->mu);
+    fmpc_handle_s::Bank& B = h->bank;
+    if (B.plain.p || B.pad.p || B.yimg.p) (void)hipDeviceSynchronize();   // (a bank solve in flight reads them)
+    B.plain.release(); B.pad.release(); B.yimg.release();
+    B.count = 0;
+    return FMPC_OK;
+}
+
+extern "C" int fmpc_solve_bank_device(fmpc_handle h, int batch, const int* model_of,
+                                      const double* x0, const double* x0_pre, const double* w,
+                                      const double* z_init, const double* nu0, int n_newton, double k,
+                                      double* z_out, double* nu_out, int* status, int* iters, double* step,
+                                      double* u0_out, void* stream_) {
+    if (!h || !x0 || (!z_out && !u0_out)) return FMPC_E_NULL;
+    if (batch < 0) return FMPC_E_DIM;
+    if (batch == 0) return FMPC_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    std::lock_guard<std::mutex> lk(h->mu);
+    fmpc_handle_s::Bank& B = h->bank;
+    const int t = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
+    if (B.count <= 0 || B.t != t || fmpc_bank_unsupported(h, t) || !h->tl[t].ready) return FMPC_E_UNSUPPORTED;
+    if (h->z_ld > h->T * (h->n + h->m)) return FMPC_E_UNSUPPORTED;
+    if (!model_of && batch > B.count) return FMPC_E_UNSUPPORTED;
+    FmpcSolve s{batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step, u0_out, stream, 0};
+    int rc = fmpc_guard_begin(h, stream);
+    if (rc != FMPC_OK) return rc;
+    if (!s.z_out) {                                                    // first moves only: the iterate lives in the handle's scratch
+        rc = fmpc_scratch_z(h, batch, stream);
+        if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
+        s.z_out = h->zs;
+    }
+    FmpcTiledPlan plan;
+    rc = fmpc_tiled_plan(h, t, batch, stream, 0, 0, &plan);
+    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
+    fmpc_handle_s::Tiled& X = h->tl[t];
+    const int nb = h->nb, NP = 16 * X.NB;
+    const size_t nn = (size_t)h->n * h->n, PP = (size_t)NP * NP;
+    FtParams P;
+    P.M = h->dev; P.V = X.V; P.batch = batch;
+    P.M.A1 = B.plain; P.M.A2 = B.plain + nn; P.M.A1t = B.plain + 2 * nn; P.M.A2t = B.plain + 3 * nn;
+    P.M.Yblk = nullptr; P.M.idxD = nullptr; P.M.idx1 = nullptr; P.M.idx2 = nullptr;      // (the handle's: not the bank's, and not read)
+    P.V.A1P = B.pad; P.V.A2P = B.pad + PP; P.V.A1tP = B.pad + 2 * PP; P.V.A2tP = B.pad + 3 * PP;
+    P.V.yimg = B.yimg.p; P.V.nblk = B.nblk;
+    const int* tab = B.ipool + (size_t)B.nblk * FB_DESC_INTS;
+    P.V.iD = tab; P.V.i1 = tab + nb; P.V.i2 = tab + 2 * nb;
+    P.x0 = s.x0; P.x0p = s.x0_pre; P.w = s.w; P.zinit = s.z_init; P.nu0 = s.nu0;
+    P.max_iter = fmpc_max_iter(s); P.kbar = s.k;
+    P.zout = s.z_out; P.nuout = s.nu_out; P.status = s.status; P.iters = s.iters; P.step = s.step; P.step_ld = fmpc_step_ld(s.n_newton);
+    P.ws = h->tl_ws; P.ws_stride = plan.slot; P.u0out = s.u0_out;
+    P.list = nullptr; P.nlist = nullptr; P.nuws = nullptr;             // (the continuation lists belong to the shared-factor forms)
+    P.refine = t ? h->refine : 0;
+    P.model_of = model_of; P.bk_count = B.count;
+    P.bk_plain = B.plain_stride; P.bk_pad = B.pad_stride; P.bk_yimg = B.yimg_stride;
+    h->tl_last_nw = plan.NWu;
+    if (t) h->refine_last = P.refine;
+    h->last_path = t ? FMPC_PATH_TILED_F32 : FMPC_PATH_TILED;
+    rc = fmpc_launch_tiled(P, X.NB, plan.NWu, t, plan.grid, plan.ldsu, stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
+    fmpc_guard_end(h, stream);
+    return rc;
+}
+
+extern "C" int fmpc_loop_inputs_bank_device(fmpc_handle h, int batch, const int* model_of,
+                                            const double* a_k, const double* x0_last, const double* u1,
+                                            const double* u2, double* x0, double* x0_pre, double* w, void* stream) {
+    if (!h || !a_k || !x0 || !x0_pre || !w) return FMPC_E_NULL;
+    if (batch < 0) return FMPC_E_DIM;
+    if (batch == 0) return FMPC_OK;
+    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const fmpc_handle_s::Bank& B = h->bank;
+    if (B.count <= 0 || (!model_of && batch > B.count)) return FMPC_E_UNSUPPORTED;
+    // (the bank's images are rewritten in place by fmpc_bank_set_device: ordered against it like the bank solve)
+    int rc = fmpc_guard_begin(h, (hipStream_t)stream);
+    if (rc != FMPC_OK) return rc;
+    rc = fmpc_launch_loop_inputs_bank(h->n, h->m, h->T, h->var_order == 2, batch, h->dev.Bt, B.plain, B.plain_stride, B.count,
+                                      model_of, a_k, x0_last, u1, u2, x0, x0_pre, w, (hipStream_t)stream) == hipSuccess
+             ? FMPC_OK : FMPC_E_HIP;
+    fmpc_guard_end(h, (hipStream_t)stream);
     return rc;
 }
 

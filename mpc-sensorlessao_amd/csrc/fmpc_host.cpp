@@ -1,6 +1,7 @@
 // Host-only builders (see fmpc_host.h).  Plain C++: also compiled by g++ with the address and undefined-behaviour
 // sanitizers (tests/host_san).
 #include "fmpc_host.h"
+#include "fmpc_bank.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -58,6 +59,75 @@ void fmpc_host_y_blocks(int n, int T, bool var2, bool has_xf, const std::vector<
     if (has_xf) {
         idxD[T] = intern(Xf);
         idx1[T - 1] = idxD[T];
+    }
+}
+
+// The block table of a model bank (fmpc_bank.h): the walk of fmpc_host_y_blocks above with term lists in place of numbers.
+void fmpc_host_bank_table(int T, bool var2, bool has_xf, bool xf_is_x, FmpcBankTable& out) {
+    const int nb = T + (has_xf ? 1 : 0);
+    out.blocks.clear();
+    out.idxD.assign(nb, -1); out.idx1.assign(nb, -1); out.idx2.assign(nb, -1);
+    auto kind = [&](int j) { return (j == T && !xf_is_x) ? FB_XF : FB_X; };
+    auto intern = [&](const FmpcBankBlock& blk) {
+        for (size_t k = 0; k < out.blocks.size(); ++k) {
+            const FmpcBankBlock& o = out.blocks[k];
+            bool same = o.nterms == blk.nterms;
+            for (int t = 0; same && t < blk.nterms; ++t)
+                same = o.t[t].sign == blk.t[t].sign && o.t[t].L == blk.t[t].L && o.t[t].X == blk.t[t].X && o.t[t].R == blk.t[t].R;
+            if (same) return (int)k;
+        }
+        out.blocks.push_back(blk);
+        return (int)out.blocks.size() - 1;
+    };
+    auto add = [](FmpcBankBlock& blk, int sign, int L, int X, int R) { blk.t[blk.nterms++] = FmpcBankTerm{sign, L, X, R}; };
+    for (int i = 0; i < T; ++i) {
+        FmpcBankBlock d{};
+        add(d, 1, FB_I, kind(i + 1), FB_I);
+        if (i >= 1) add(d, 1, FB_A1, kind(i), FB_A1);
+        if (i >= 2 && var2) add(d, 1, FB_A2, kind(i - 1), FB_A2);
+        out.idxD[i] = intern(d);
+        if (i + 1 < T) {
+            FmpcBankBlock o{};
+            add(o, -1, FB_I, kind(i + 1), FB_A1);
+            if (i >= 1 && var2) add(o, 1, FB_A1, kind(i), FB_A2);
+            out.idx1[i] = intern(o);
+        }
+        if (i + 2 < T && var2) {
+            FmpcBankBlock o{};
+            add(o, -1, FB_I, kind(i + 1), FB_A2);
+            out.idx2[i] = intern(o);
+        }
+    }
+    if (has_xf) {
+        FmpcBankBlock d{};
+        add(d, 1, FB_I, kind(T), FB_I);
+        out.idxD[T] = intern(d);
+        out.idx1[T - 1] = out.idxD[T];
+    }
+}
+
+void fmpc_host_bank_eval(const FmpcBankBlock& blk, int n, const double* a1, const double* a2, const double* X, const double* Xf,
+                         std::vector<long double>& out) {
+    out.assign((size_t)n * n, 0.0L);
+    std::vector<long double> LX((size_t)n * n);
+    auto el = [&](int which, int r, int c) -> long double {
+        return which == FB_I ? (r == c ? 1.0L : 0.0L) : (long double)(which == FB_A1 ? a1 : a2)[(size_t)r * n + c];
+    };
+    for (int t = 0; t < blk.nterms; ++t) {
+        const FmpcBankTerm& tm = blk.t[t];
+        const double* Xk = tm.X == FB_XF ? Xf : X;
+        for (int a = 0; a < n; ++a)
+            for (int c = 0; c < n; ++c) {
+                long double v = 0.0L;
+                for (int k = 0; k < n; ++k) v += el(tm.L, a, k) * (long double)Xk[(size_t)k * n + c];
+                LX[(size_t)a * n + c] = v;
+            }
+        for (int a = 0; a < n; ++a)
+            for (int b = 0; b < n; ++b) {
+                long double v = 0.0L;
+                for (int c = 0; c < n; ++c) v += LX[(size_t)a * n + c] * el(tm.R, b, c);
+                out[(size_t)a * n + b] += tm.sign * v;
+            }
     }
 }
 

@@ -401,8 +401,21 @@ __device__ __forceinline__ FtKP ft_uniform(FtKP P) {             // a function a
     const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
     return (FtKP)(((unsigned long long)hi << 32) | lo);
 }
-template <typename R, int NB, int NW, int NL, bool DR>
-__device__ __noinline__ bool ft_phase_factor(FtKP Pin) {
+// Model bank (fmpc_solve_bank_device; FtParams::model_of, bk_*): the BK instances read the model-dependent operands -- the constant Y tiles,
+// the padded A1, A2 and their transposes, the plain transposes of P0 -- at base + model * stride, the model index handed down from the
+// problem loop and made wave-uniform here.  The offset is added to the pointer the parameter block holds, so the operand keeps its address
+// space and every load stays unconditional.  BK = false: FtSel is empty (no argument is passed) and the accessors are the plain fields.
+template <bool BK> struct FtSel {};
+template <> struct FtSel<true> { int mi; };
+template <bool BK> __device__ __forceinline__ size_t ft_moff(FtSel<BK> sel, size_t stride) {
+    if constexpr (BK) return (size_t)(unsigned)__builtin_amdgcn_readfirstlane(sel.mi) * stride;
+    else return 0;
+}
+#define FT_MP(f) (BK ? P->V.f + mo_pad : P->V.f)                    /* padded fp64 image f of this problem's model */
+#define FT_MY(R) (BK ? (const R*)P->V.yimg + mo_y : (const R*)P->V.yimg)
+
+template <typename R, int NB, int NW, int NL, bool DR, bool BK = false>
+__device__ __noinline__ bool ft_phase_factor(FtKP Pin, FtSel<BK> sel = {}) {
     typedef FtT<R> TT;
     typedef typename TT::v4 v4;
     constexpr int NS = NB * (NB + 1) / 2, NQ = NB * NB;
@@ -427,7 +440,8 @@ __device__ __noinline__ bool ft_phase_factor(FtKP Pin) {
     double* yv = wsp + L.y;
     R* fac = (R*)(wsp + L.fac);
     R* gws = (R*)(wsp + L.gt);
-    const R* yimg = (const R*)P->V.yimg;
+    [[maybe_unused]] const size_t mo_y = ft_moff<BK>(sel, P->bk_yimg);
+    const R* yimg = FT_MY(R);
     const ft_cidx Vi1 = (ft_cidx)P->V.i1, Vi2 = (ft_cidx)P->V.i2;
     const int firstS = wv, firstM1 = ((wv - NS) % NW + NW) % NW, firstM2 = ((wv - NS - NQ) % NW + 2 * NW) % NW;
     int sI[SS], sJ[SS];
@@ -757,8 +771,8 @@ __device__ __noinline__ bool ft_phase_factor(FtKP Pin) {
 
 // The S pre-pass of the kernel below (S0_i = Y_ii const + B W_i B' of every block row) as a function of its own: see ft_phase_factor.
 // Workgroup-collective (barriers inside): every thread of the workgroup calls it.
-template <typename R, int NB, int NW, bool DR>
-__device__ __noinline__ void ft_phase_spre(FtKP Pin) {
+template <typename R, int NB, int NW, bool DR, bool BK = false>
+__device__ __noinline__ void ft_phase_spre(FtKP Pin, FtSel<BK> sel = {}) {
     typedef FtT<R> TT;
     typedef typename TT::v4 v4;
     constexpr int NT = NW * 64;
@@ -779,7 +793,8 @@ __device__ __noinline__ void ft_phase_spre(FtKP Pin) {
     double* winv = wsp + L.winv;
     double* yv = wsp + L.y;
     R* gws = (R*)(wsp + L.gt);
-    const R* yimg = (const R*)P->V.yimg;
+    [[maybe_unused]] const size_t mo_y = ft_moff<BK>(sel, P->bk_yimg);
+    const R* yimg = FT_MY(R);
     const ft_cidx ViD = (ft_cidx)P->V.iD;
     {
         const R* src = (const R*)P->V.btimg;
@@ -902,9 +917,10 @@ struct FtResid { double rp2, rho2, bad; };
 struct FtStep { double t; int collapsed; };
 
 // P1 of the kernel below (residuals of problem p, their norms) as a function of its own: see ft_phase_factor.  Workgroup-collective.
-template <typename R, int NB, int NW, bool DR>
-__device__ __noinline__ FtResid ft_phase_resid(FtKP Pin, int p) {
+template <typename R, int NB, int NW, bool DR, bool BK = false>
+__device__ __noinline__ FtResid ft_phase_resid(FtKP Pin, int p, FtSel<BK> sel = {}) {
     FT_VIEW(R, NB, NW, DR);
+    [[maybe_unused]] const size_t mo_pad = ft_moff<BK>(sel, P->bk_pad);
     p = __builtin_amdgcn_readfirstlane(p);
     double* zp = P->zout + (size_t)p * Nz;
     double acc_d = 0.0, acc_p = 0.0;
@@ -935,11 +951,11 @@ __device__ __noinline__ FtResid ft_phase_resid(FtKP Pin, int p) {
                             [&](int k) { return P->V.BtP[(size_t)k * NP + r]; });
                 ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
                             [&](int k) { return zi1[k < n ? k : n - 1] * f1; },
-                            [&](int k) { return P->V.A1tP[k * NP + r]; });
+                            [&](int k) { return FT_MP(A1tP)[k * NP + r]; });
                 if (var2)
                     ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
                                 [&](int k) { return zi2[k < n ? k : n - 1] * f2; },
-                                [&](int k) { return P->V.A2tP[k * NP + r]; });
+                                [&](int k) { return FT_MP(A2tP)[k * NP + r]; });
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
                     const int io = 16 * A + g + 4 * rr;
@@ -957,11 +973,11 @@ __device__ __noinline__ FtResid ft_phase_resid(FtKP Pin, int p) {
                 const double f1 = jj + 1 < T ? 1.0 : 0.0, f2 = jj + 2 < T ? 1.0 : 0.0;
                 ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
                             [&](int k) { return sNU[(jj + 1) * LDN + k] * f1; },
-                            [&](int k) { return P->V.A1P[k * NP + r]; });
+                            [&](int k) { return FT_MP(A1P)[k * NP + r]; });
                 if (var2)
                     ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
                                 [&](int k) { return sNU[(jj + 2) * LDN + k] * f2; },
-                                [&](int k) { return P->V.A2P[k * NP + r]; });
+                                [&](int k) { return FT_MP(A2P)[k * NP + r]; });
                 ft_d4 accq = {0, 0, 0, 0};                       // dense state weights: 2Q_j x_j as a product (Qf at the last stage)
                 if (P->V.denseQ) {
                     const double* xj = zp + (size_t)(jj < T ? jj : T - 1) * s + m;
@@ -1030,9 +1046,10 @@ __device__ __noinline__ FtResid ft_phase_resid(FtKP Pin, int p) {
 }
 
 // P5 of the kernel below (d_z, line search, update of z and nu of problem p) as a function of its own.  Workgroup-collective.
-template <typename R, int NB, int NW, bool DR>
-__device__ __noinline__ FtStep ft_phase_update(FtKP Pin, int p, double rho2) {
+template <typename R, int NB, int NW, bool DR, bool BK = false>
+__device__ __noinline__ FtStep ft_phase_update(FtKP Pin, int p, double rho2, FtSel<BK> sel = {}) {
     FT_VIEW(R, NB, NW, DR);
+    [[maybe_unused]] const size_t mo_pad = ft_moff<BK>(sel, P->bk_pad);
     p = __builtin_amdgcn_readfirstlane(p);
     double* zp = P->zout + (size_t)p * Nz;
     double be = 0.0, e2 = 0.0;
@@ -1046,11 +1063,11 @@ __device__ __noinline__ FtStep ft_phase_update(FtKP Pin, int p, double rho2) {
             const double f1 = jj + 1 < T ? 1.0 : 0.0, f2 = jj + 2 < T ? 1.0 : 0.0;
             ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
                         [&](int k) { return sNU[(jj + 1) * LDN + k] * f1; },
-                        [&](int k) { return P->V.A1P[k * NP + r]; });
+                        [&](int k) { return FT_MP(A1P)[k * NP + r]; });
             if (var2)
                 ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
                             [&](int k) { return sNU[(jj + 2) * LDN + k] * f2; },
-                            [&](int k) { return P->V.A2P[k * NP + r]; });
+                            [&](int k) { return FT_MP(A2P)[k * NP + r]; });
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 const int jo = 16 * A + g + 4 * rr;
@@ -1152,9 +1169,10 @@ __device__ __noinline__ FtStep ft_phase_update(FtKP Pin, int p, double rho2) {
 // fp32 image of Y that the factor phase reads is what the refinement corrects for, so it has no part here).  d_nu is in the
 // staging area (left there by P4), rhs in the copy P2 kept; rho goes to yv, where the forward sweep takes it.  phx is free between
 // P2 and the next P1.  Workgroup-collective.
-template <typename R, int NB, int NW>
-__device__ __noinline__ void ft_phase_refres(FtKP Pin) {
+template <typename R, int NB, int NW, bool BK = false>
+__device__ __noinline__ void ft_phase_refres(FtKP Pin, FtSel<BK> sel = {}) {
     FT_VIEW(R, NB, NW, false);
+    [[maybe_unused]] const size_t mo_pad = ft_moff<BK>(sel, P->bk_pad);
     const double* rhs = wsp + L.rhs;
     double* pu = wsp + L.pu;
     double* vx = wsp + L.vx;
@@ -1169,11 +1187,11 @@ __device__ __noinline__ void ft_phase_refres(FtKP Pin) {
             const double f1 = jj + 1 < T ? 1.0 : 0.0, f2 = jj + 2 < T ? 1.0 : 0.0;
             ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
                         [&](int k) { return sNU[(jj + 1) * LDN + k] * f1; },
-                        [&](int k) { return P->V.A1P[k * NP + r]; });
+                        [&](int k) { return FT_MP(A1P)[k * NP + r]; });
             if (var2)
                 ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
                             [&](int k) { return sNU[(jj + 2) * LDN + k] * f2; },
-                            [&](int k) { return P->V.A2P[k * NP + r]; });
+                            [&](int k) { return FT_MP(A2P)[k * NP + r]; });
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 const int jo = 16 * A + g + 4 * rr;
@@ -1237,11 +1255,11 @@ __device__ __noinline__ void ft_phase_refres(FtKP Pin) {
                     [&](int k) { return P->V.BtP[(size_t)k * NP + r]; });
         ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
                     [&](int k) { return ph1[k < n ? k : n - 1] * f1; },
-                    [&](int k) { return P->V.A1tP[k * NP + r]; });
+                    [&](int k) { return FT_MP(A1tP)[k * NP + r]; });
         if (var2)
             ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
                         [&](int k) { return ph2[k < n ? k : n - 1] * f2; },
-                        [&](int k) { return P->V.A2tP[k * NP + r]; });
+                        [&](int k) { return FT_MP(A2tP)[k * NP + r]; });
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const int io = 16 * A + g + 4 * rr;
@@ -1255,7 +1273,7 @@ __device__ __noinline__ void ft_phase_refres(FtKP Pin) {
 }
 
 // NL: live rows of the last 16-row block of a stage, n - 16 (NB - 1), when known at compile time (the AO sizes), else -1
-template <typename R, int NB, int NW, int NL, bool DR = false>
+template <typename R, int NB, int NW, int NL, bool DR = false, bool BK = false>
 __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
     typedef FtT<R> TT;
     typedef typename TT::v4 v4;
@@ -1327,6 +1345,19 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
         bool cont = false;                                           // continue behind the panel path's first step
         bool gen = false;                                            // ... behind one step of the one-wavefront kernel (FT_LIST_GENERAL)
         if (P.list) { const int e = P.list[item_p]; p = e & (FT_LIST_GENERAL - 1); cont = !(e & FT_LIST_HANDED); gen = (e & FT_LIST_GENERAL) != 0; }
+        // model bank: this problem's model (model_of NULL: model p).  An index outside the bank ends the problem here, before
+        // anything of it is read or written but its status (wave-uniform: every thread of the workgroup takes the same way)
+        [[maybe_unused]] FtSel<BK> sel;
+        [[maybe_unused]] size_t mo_plain = 0, mo_pad = 0;
+        if constexpr (BK) {
+            const int mi = __builtin_amdgcn_readfirstlane(P.model_of ? P.model_of[p] : p);
+            if ((unsigned)mi >= (unsigned)P.bk_count) {
+                if (tid == 0) { if (P.status) P.status[p] = FMPC_E_DIM; if (P.iters) P.iters[p] = 0; }
+                continue;
+            }
+            sel.mi = mi;
+            mo_plain = (size_t)mi * P.bk_plain; mo_pad = (size_t)mi * P.bk_pad;
+        }
         double* zp = P.zout + (size_t)p * Nz;
         const double* x0v = P.x0 + (size_t)p * n;
         const double* x0pv = P.x0p ? P.x0p + (size_t)p * n : nullptr;
@@ -1348,14 +1379,14 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
             double v = (i < T && P.w) ? P.w[(size_t)p * T * n + idx] : 0.0;
             if (i == 0) {
 #pragma unroll 9
-                for (int q = 0; q < n; ++q) v += M.A1t[q * n + r] * x0v[q];
+                for (int q = 0; q < n; ++q) v += (BK ? M.A1t + mo_plain : M.A1t)[q * n + r] * x0v[q];
                 if (var2 && x0pv) {
 #pragma unroll 9
-                    for (int q = 0; q < n; ++q) v += M.A2t[q * n + r] * x0pv[q];
+                    for (int q = 0; q < n; ++q) v += (BK ? M.A2t + mo_plain : M.A2t)[q * n + r] * x0pv[q];
                 }
             } else if (i == 1 && i < T && var2) {
 #pragma unroll 9
-                for (int q = 0; q < n; ++q) v += M.A2t[q * n + r] * x0v[q];
+                for (int q = 0; q < n; ++q) v += (BK ? M.A2t + mo_plain : M.A2t)[q * n + r] * x0v[q];
             }
             if (i == T) v = M.xf[r];
             b[idx] = v;
@@ -1370,7 +1401,7 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
             // ================= P1: residuals.  Every product is a GEMM with the horizon stages as one dimension
             // (out[stage][entry] = sum_k X[k][stage] Z[k][entry]) on the fp64 matrix cores; Z (B, A1, A2 and transposes)
             // is read from L2 with 128-byte rows, the epilogues read and write along the entries of a stage.
-            const FtResid rs_ = ft_phase_resid<R, NB, NW, DR>(ft_params(), p);      // (not inlined: see ft_phase_factor)
+            const FtResid rs_ = ft_phase_resid<R, NB, NW, DR, BK>(ft_params(), p, sel);      // (not inlined: see ft_phase_factor)
             const double rp2 = rs_.rp2, rho2 = rs_.rho2, badsum = rs_.bad;
             // early exit, tested before the step (inf_newton_solver.m:19-22)
             if (sqrt(rho2) <= 1e-6 && sqrt(rp2) <= 1e-8) break;
@@ -1426,11 +1457,11 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
                                 [&](int k) { return V.BtP[(size_t)k * NP + r]; });
                 ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
                             [&](int k) { return ph1[k < n ? k : n - 1] * f1; },
-                            [&](int k) { return V.A1tP[k * NP + r]; });
+                            [&](int k) { return (BK ? V.A1tP + mo_pad : V.A1tP)[k * NP + r]; });
                 if (var2)
                     ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
                                 [&](int k) { return ph2[k < n ? k : n - 1] * f2; },
-                                [&](int k) { return V.A2tP[k * NP + r]; });
+                                [&](int k) { return (BK ? V.A2tP + mo_pad : V.A2tP)[k * NP + r]; });
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
                     const int io = 16 * A + g + 4 * rr;
@@ -1446,7 +1477,7 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
             // rhs_i in column n) of EVERY block row, all independent, ahead of the serial factorisation.  The B' tiles are
             // in LDS only for this (the factor phase reuses the space); Phi^-1 of FT_GCH stages at a time in LDS.
             FT_TICK(12);
-            ft_phase_spre<R, NB, NW, DR>(ft_params());                 // (not inlined: see ft_phase_factor)
+            ft_phase_spre<R, NB, NW, DR, BK>(ft_params(), sel);                 // (not inlined: see ft_phase_factor)
             __syncthreads();
             FT_TICK(13);
             // zero the three U slots: stages 0 and 1 then need no special cases
@@ -1465,7 +1496,7 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
             // and subtracted in the stage itself.
             // (a function of its own, not inlined: inside the kernel body the factor phase's ~150 registers of tiles compete with
             // everything else that is live there -- the n = 65 instance spilled 928 bytes per lane, ~300 scratch accesses per stage)
-            const bool fail = ft_phase_factor<R, NB, NW, NL, DR>(ft_params());
+            const bool fail = ft_phase_factor<R, NB, NW, NL, DR, BK>(ft_params(), sel);
             if (fail) { st = FMPC_E_NOT_PD_SCHUR; break; }
             __syncthreads();                                           // the factor stream and y are in HBM (same workgroup reads them)
             FT_TICK(6);
@@ -1481,7 +1512,7 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
             // The rounding of rho to fp32 on the way in and of e on the way out is the method: each sweep takes ~2^-24 cond(Y) off.
             if constexpr (REFINE) {
                 for (int sw = 0; sw < P.refine; ++sw) {
-                    ft_phase_refres<R, NB, NW>(ft_params());
+                    ft_phase_refres<R, NB, NW, BK>(ft_params(), sel);
                     ft_forward<R, NB, NW>(fac, yv, sXV, sPART, n, nb);
                     __syncthreads();                                   // y is in HBM (same workgroup reads it)
                     ft_backward<R, NB, NW, true>(fac, yv, sXV, sPART, sNU, n, nb, NUROWS);
@@ -1493,7 +1524,7 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
             // ================= P5: d_z, line-search scalars, update (the same stage-batched GEMMs with d_nu)
             double t;
             {
-                const FtStep sp_ = ft_phase_update<R, NB, NW, DR>(ft_params(), p, rho2);   // (not inlined: see ft_phase_factor)
+                const FtStep sp_ = ft_phase_update<R, NB, NW, DR, BK>(ft_params(), p, rho2, sel);   // (not inlined: see ft_phase_factor)
                 t = sp_.t;
                 if (sp_.collapsed) st = FMPC_W_LINESEARCH;
             }
@@ -1516,56 +1547,56 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
 }
 
 // ---------------------------------------------------------------- host side
-template <typename R, int NB, int NW, int NL = -1, bool DR = false>
+template <bool BK, typename R, int NB, int NW, int NL = -1, bool DR = false>
 static hipError_t ft_launch(const FtParams& P, int grid, size_t lds, hipStream_t stream) {
-    hipLaunchKernelGGL((fmpc_newton_tiled<R, NB, NW, NL, DR>), dim3(grid), dim3(NW * 64), lds, stream, P);
+    hipLaunchKernelGGL((fmpc_newton_tiled<R, NB, NW, NL, DR, BK>), dim3(grid), dim3(NW * 64), lds, stream, P);
     return hipGetLastError();
 }
-template <typename R, int NB, int NW, int NL = -1, bool DR = false>
+template <bool BK, typename R, int NB, int NW, int NL = -1, bool DR = false>
 static hipError_t ft_prepare(size_t lds) {
-    return hipFuncSetAttribute((const void*)fmpc_newton_tiled<R, NB, NW, NL, DR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return hipFuncSetAttribute((const void*)fmpc_newton_tiled<R, NB, NW, NL, DR, BK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
 // instantiations: fp64 for n <= 79 (NB <= 5; 4 and 5 on request), fp32 for n <= 111 (NB <= 7; 6 and 7 on request); NW wavefronts per problem
-#define FT_DISPATCH(fn, ...)                                                                   \
+#define FT_DISPATCH(fn, BKV, ...)                                                                   \
     /* dense R: fp64, eight wavefronts (the per-stage m x m factorisation is workgroup-wide vector work) */                  \
     if (denseR) {                                                                              \
         if (is_float || NW != 8) return hipErrorInvalidValue;                                  \
-        if (NB == 1) return fn<double, 1, 8, -1, true>(__VA_ARGS__);                           \
-        if (NB == 2) return fn<double, 2, 8, -1, true>(__VA_ARGS__);                           \
-        if (NB == 3) return fn<double, 3, 8, -1, true>(__VA_ARGS__);                           \
+        if (NB == 1) return fn<BKV, double, 1, 8, -1, true>(__VA_ARGS__);                           \
+        if (NB == 2) return fn<BKV, double, 2, 8, -1, true>(__VA_ARGS__);                           \
+        if (NB == 3) return fn<BKV, double, 3, 8, -1, true>(__VA_ARGS__);                           \
         return hipErrorInvalidValue;                                                           \
     }                                                                                          \
     /* the AO sizes (n = 27 Zernike modes; n = 65: radial order 10) with their block structure at compile time, for the   \
        default wavefront counts only; other wavefront counts use the run-time form.  (An instance <double, 2, 4, 11> existed  \
        until round 5: miscompiled by round 2's monolithic build, never root-caused, bitwise equal to the run-time form since  \
        the phases are separate functions, 3-4 % faster -- removed rather than kept as a switch; docs/DESIGN_HISTORY.md.)    */ \
-    if (!is_float && nlast == 11 && NB == 2 && NW == 2) return fn<double, 2, 2, 11>(__VA_ARGS__);  \
-    if (is_float && nlast == 11 && NB == 2 && NW == 4) return fn<float, 2, 4, 11>(__VA_ARGS__);    \
-    if (is_float && nlast == 1 && NB == 5 && NW == 8) return fn<float, 5, 8, 1>(__VA_ARGS__);      \
-    if (is_float && nlast == 1 && NB == 5 && NW == 4) return fn<float, 5, 4, 1>(__VA_ARGS__);      \
+    if (!is_float && nlast == 11 && NB == 2 && NW == 2) return fn<BKV, double, 2, 2, 11>(__VA_ARGS__);  \
+    if (is_float && nlast == 11 && NB == 2 && NW == 4) return fn<BKV, float, 2, 4, 11>(__VA_ARGS__);    \
+    if (is_float && nlast == 1 && NB == 5 && NW == 8) return fn<BKV, float, 5, 8, 1>(__VA_ARGS__);      \
+    if (is_float && nlast == 1 && NB == 5 && NW == 4) return fn<BKV, float, 5, 4, 1>(__VA_ARGS__);      \
     if (!is_float) {                                                                           \
-        if (NB == 1 && NW == 2) return fn<double, 1, 2>(__VA_ARGS__);                          \
-        if (NB == 2 && NW == 2) return fn<double, 2, 2>(__VA_ARGS__);                          \
-        if (NB == 3 && NW == 2) return fn<double, 3, 2>(__VA_ARGS__);                          \
-        if (NB == 1 && NW == 4) return fn<double, 1, 4>(__VA_ARGS__);                          \
-        if (NB == 2 && NW == 4) return fn<double, 2, 4>(__VA_ARGS__);                          \
-        if (NB == 3 && NW == 4) return fn<double, 3, 4>(__VA_ARGS__);                          \
+        if (NB == 1 && NW == 2) return fn<BKV, double, 1, 2>(__VA_ARGS__);                          \
+        if (NB == 2 && NW == 2) return fn<BKV, double, 2, 2>(__VA_ARGS__);                          \
+        if (NB == 3 && NW == 2) return fn<BKV, double, 3, 2>(__VA_ARGS__);                          \
+        if (NB == 1 && NW == 4) return fn<BKV, double, 1, 4>(__VA_ARGS__);                          \
+        if (NB == 2 && NW == 4) return fn<BKV, double, 2, 4>(__VA_ARGS__);                          \
+        if (NB == 3 && NW == 4) return fn<BKV, double, 3, 4>(__VA_ARGS__);                          \
         /* fp64 on request where the fp32 factor is the default (47 < n <= 79, fmpc_set_precision): one workgroup of 8 per CU */ \
-        if (NB == 4 && NW == 8) return fn<double, 4, 8>(__VA_ARGS__);                          \
-        if (NB == 5 && NW == 8) return fn<double, 5, 8>(__VA_ARGS__);                          \
+        if (NB == 4 && NW == 8) return fn<BKV, double, 4, 8>(__VA_ARGS__);                          \
+        if (NB == 5 && NW == 8) return fn<BKV, double, 5, 8>(__VA_ARGS__);                          \
     } else {                                                                                   \
-        if (NB == 1 && NW == 2) return fn<float, 1, 2>(__VA_ARGS__);                           \
-        if (NB == 2 && NW == 2) return fn<float, 2, 2>(__VA_ARGS__);                           \
-        if (NB == 2 && NW == 4) return fn<float, 2, 4>(__VA_ARGS__);                           \
-        if (NB == 3 && NW == 4) return fn<float, 3, 4>(__VA_ARGS__);                           \
-        if (NB == 4 && NW == 4) return fn<float, 4, 4>(__VA_ARGS__);                           \
-        if (NB == 4 && NW == 8) return fn<float, 4, 8>(__VA_ARGS__);                           \
-        if (NB == 5 && NW == 4) return fn<float, 5, 4>(__VA_ARGS__);                           \
-        if (NB == 5 && NW == 8) return fn<float, 5, 8>(__VA_ARGS__);                           \
+        if (NB == 1 && NW == 2) return fn<BKV, float, 1, 2>(__VA_ARGS__);                           \
+        if (NB == 2 && NW == 2) return fn<BKV, float, 2, 2>(__VA_ARGS__);                           \
+        if (NB == 2 && NW == 4) return fn<BKV, float, 2, 4>(__VA_ARGS__);                           \
+        if (NB == 3 && NW == 4) return fn<BKV, float, 3, 4>(__VA_ARGS__);                           \
+        if (NB == 4 && NW == 4) return fn<BKV, float, 4, 4>(__VA_ARGS__);                           \
+        if (NB == 4 && NW == 8) return fn<BKV, float, 4, 8>(__VA_ARGS__);                           \
+        if (NB == 5 && NW == 4) return fn<BKV, float, 5, 4>(__VA_ARGS__);                           \
+        if (NB == 5 && NW == 8) return fn<BKV, float, 5, 8>(__VA_ARGS__);                           \
         /* 79 < n <= 111 with the fp32 factor, on request (round 5): one workgroup of 8 per CU */ \
-        if (NB == 6 && NW == 8) return fn<float, 6, 8>(__VA_ARGS__);                           \
-        if (NB == 7 && NW == 8) return fn<float, 7, 8>(__VA_ARGS__);                           \
+        if (NB == 6 && NW == 8) return fn<BKV, float, 6, 8>(__VA_ARGS__);                           \
+        if (NB == 7 && NW == 8) return fn<BKV, float, 7, 8>(__VA_ARGS__);                           \
     }                                                                                          \
     return hipErrorInvalidValue;
 
@@ -1602,12 +1633,17 @@ static int ft_nlast(int n, int NB) {
     const char* e = getenv("FMPC_TILED_GENERIC");                 // experiments: the instance with the block structure at run time
     return (e && e[0] == '1') ? -1 : n - 16 * (NB - 1);
 }
-hipError_t fmpc_tiled_prepare(int n, int NB, int NW, int is_float, size_t lds_bytes, int denseR) {
-    const int nlast = ft_nlast(n, NB);
-    FT_DISPATCH(ft_prepare, lds_bytes)
+// bank: the instances that read their model per problem (fmpc_solve_bank_device)
+static hipError_t ft_prepare_any(int bank, int nlast, int NB, int NW, int is_float, size_t lds_bytes, int denseR) {
+    if (bank) { FT_DISPATCH(ft_prepare, true, lds_bytes) }
+    FT_DISPATCH(ft_prepare, false, lds_bytes)
+}
+hipError_t fmpc_tiled_prepare(int n, int NB, int NW, int is_float, size_t lds_bytes, int denseR, int bank) {
+    return ft_prepare_any(bank, ft_nlast(n, NB), NB, NW, is_float, lds_bytes, denseR);
 }
 hipError_t fmpc_launch_tiled(const FtParams& P, int NB, int NW, int is_float, int grid, size_t lds_bytes, hipStream_t stream) {
     const int nlast = ft_nlast(P.M.n, NB);
     const int denseR = P.V.denseR;
-    FT_DISPATCH(ft_launch, P, grid, lds_bytes, stream)
+    if (P.bk_count > 0) { FT_DISPATCH(ft_launch, true, P, grid, lds_bytes, stream) }
+    FT_DISPATCH(ft_launch, false, P, grid, lds_bytes, stream)
 }

@@ -126,6 +126,13 @@ struct FtParams {
     // zout and nu+ in the panel workspace, the first step is done).  list == NULL: all problems 0 .. batch-1 from the start.
     const int* list; const int* nlist; const double* nuws;
     int refine;             // fp32 factor only: sweeps of iterative refinement of d_nu per Newton step (fmpc_set_refinement), 0 = none
+    // Model bank (fmpc_solve_bank_device; behind everything else: the other launches address what they always did).  bk_count > 0
+    // selects the bank instances: problem p takes model model_of[p] (NULL: model p) of bk_count, and M.A1 .. M.A2t, V.yimg,
+    // V.A1P .. V.A2tP are the images of model 0 with those of model j at + j * stride (V.iD, V.i1, V.i2, V.nblk: the bank's one
+    // block table, fmpc_bank.h).  An index outside [0, bk_count) gives that problem FMPC_E_DIM and nothing else.
+    const int* model_of = nullptr; int bk_count = 0;
+    size_t bk_plain = 0, bk_pad = 0;    // doubles between the plain (M.*) / the padded (V.A*P) images of consecutive models
+    size_t bk_yimg = 0;                 // REAL elements between their constant Y tiles
 };
 #define FT_LIST_HANDED (1 << 30)       // (= FW_LIST_HANDED of fmpc_kernel_wave.hip)
 #define FT_LIST_GENERAL (1 << 29)      // (= FW_LIST_GENERAL) continue behind ONE step of the one-wavefront kernel from an explicit start: z in
@@ -134,5 +141,5 @@ struct FtParams {
 // supported (type, NB) pairs
 bool fmpc_tiled_supports(int n, int m, int nb, int is_float, int* NB_out, int* NW_out, int denseR = 0);
 size_t fmpc_tiled_lds_bytes(int NB, int mb, int NW, int is_float, int nb, size_t pr_doubles = 0);
-hipError_t fmpc_tiled_prepare(int n, int NB, int NW, int is_float, size_t lds_bytes, int denseR = 0);
+hipError_t fmpc_tiled_prepare(int n, int NB, int NW, int is_float, size_t lds_bytes, int denseR = 0, int bank = 0);
 hipError_t fmpc_launch_tiled(const FtParams& P, int NB, int NW, int is_float, int grid, size_t lds_bytes, hipStream_t stream);

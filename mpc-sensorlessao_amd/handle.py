@@ -339,6 +339,101 @@ class FastMPCHandle:
         if rc != _lib.FMPC_OK:
             raise FastMPCError(rc, "fmpc_loop_inputs_device")
 
+    # ------------------------------------------------------------------ model bank
+    def set_model_bank(self, A1, A2=None):
+        """fmpc_bank_set_device: one VAR model per problem.  A1, A2: (count, n, n) float64 HIP tensors, A[b, i, j] = A_b(i, j)
+        (A2 None for var_order 1).  `identify_var2_device` returns exactly that as transposed views of column-major buffers
+        (strides (n*n, 1, n)): such a tensor is passed by pointer, with no copy; any other layout is copied into that order first.
+        The bank is built on torch's current stream; the tensors are not retained."""
+        import torch
+        n = self.n
+
+        def colmajor(t, name):
+            if t is None:
+                return None
+            if not (t.is_cuda and t.dtype == torch.float64 and t.dim() == 3 and tuple(t.shape[1:]) == (n, n)):
+                raise FastMPCError(_lib.FMPC_E_DIM, f"{name}: need a (count, {n}, {n}) float64 HIP tensor")
+            if t.shape[0] == 0 or tuple(t.stride()) == (n * n, 1, n):
+                return t
+            return t.transpose(1, 2).contiguous().transpose(1, 2)      # column-major per model
+
+        a1 = colmajor(A1, "A1")
+        a2 = colmajor(A2, "A2") if self.var_order == 2 else None
+        if a1 is None or (self.var_order == 2 and a2 is None):
+            raise FastMPCError(_lib.FMPC_E_NULL, "set_model_bank: A1 (and A2 for var_order 2)")
+        if a2 is not None and a2.shape[0] != a1.shape[0]:
+            raise FastMPCError(_lib.FMPC_E_DIM, "A2: as many models as A1")
+        stream = C.c_void_p(torch.cuda.current_stream(a1.device).cuda_stream)
+        rc = self._lib.fmpc_bank_set_device(self._h, int(a1.shape[0]), C.c_void_p(a1.data_ptr()),
+                                            None if a2 is None else C.c_void_p(a2.data_ptr()), stream)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_bank_set_device")
+
+    def release_model_bank(self):
+        rc = self._lib.fmpc_bank_release(self._h)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_bank_release")
+
+    @property
+    def model_bank_count(self):
+        """Models in the bank (fmpc_bank_count; 0 = no bank)."""
+        return int(self._lib.fmpc_bank_count(self._h))
+
+    def solve_bank_device(self, x0, x0_pre=None, w=None, z_init=None, nu0=None, n_newton=1, k=1e-2, model_of=None,
+                          z_out=None, nu_out=None, status=None, iters=None, step=None, u0_out=None, want_z=True):
+        """fmpc_solve_bank_device: `solve_device` where problem p uses model model_of[p] of the bank (int32 HIP tensor; None:
+        model p).  Returns (z_out, status, iters); a problem whose index is outside the bank gets status FMPC_E_DIM."""
+        import torch
+        batch = x0.shape[0]
+        dev = x0.device
+
+        def chk(t, cols, name, dtype=torch.float64):
+            if t is not None and not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() == batch * cols):
+                raise FastMPCError(_lib.FMPC_E_DIM, f"{name}: need a contiguous {dtype} HIP tensor of {(batch, cols)}")
+
+        n_newton = 0 if n_newton is None else int(n_newton)
+        if not want_z and u0_out is None:
+            raise FastMPCError(_lib.FMPC_E_NULL, "want_z=False needs u0_out")
+        if z_out is None and want_z:
+            z_out = torch.empty((batch, self.nz), dtype=torch.float64, device=dev)
+        if not want_z:
+            z_out = None
+        if status is None:
+            status = torch.empty(batch, dtype=torch.int32, device=dev)
+        if iters is None:
+            iters = torch.empty(batch, dtype=torch.int32, device=dev)
+        chk(x0, self.n, "x0"); chk(x0_pre, self.n, "x0_pre"); chk(w, self.T * self.n, "w")
+        chk(z_init, self.nz, "z_init"); chk(nu0, self.nu_len, "nu0"); chk(z_out, self.nz, "z_out")
+        chk(nu_out, self.nu_len, "nu_out"); chk(u0_out, self.m, "u0_out")
+        chk(status, 1, "status", torch.int32); chk(iters, 1, "iters", torch.int32); chk(model_of, 1, "model_of", torch.int32)
+        if step is not None:
+            chk(step, self._lib.fmpc_step_ld(n_newton), "step")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = self._lib.fmpc_solve_bank_device(self._h, batch, p(model_of), p(x0), p(x0_pre), p(w), p(z_init), p(nu0), n_newton,
+                                              float(k), p(z_out), p(nu_out), p(status), p(iters), p(step), p(u0_out), stream)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_solve_bank_device")
+        return z_out, status, iters
+
+    def loop_inputs_bank(self, a_k, x0_last, u1, u2, x0, x0_pre, w, model_of=None):
+        """fmpc_loop_inputs_bank_device: `loop_inputs_device` with M1, M2 of the bank's model model_of[p] (None: model p)."""
+        import torch
+        batch = a_k.shape[0]
+        for t, cols, name in ((a_k, self.n, "a_k"), (x0_last, self.n, "x0_last"), (u1, self.m, "u1"), (u2, self.m, "u2"),
+                              (x0, self.n, "x0"), (x0_pre, self.n, "x0_pre"), (w, self.T * self.n, "w")):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == batch * cols):
+                raise FastMPCError(_lib.FMPC_E_DIM, f"{name}: need a contiguous float64 HIP tensor of {(batch, cols)}")
+        if model_of is not None and not (model_of.is_cuda and model_of.dtype == torch.int32 and model_of.is_contiguous()
+                                         and model_of.numel() == batch):
+            raise FastMPCError(_lib.FMPC_E_DIM, "model_of: need a contiguous int32 HIP tensor of (batch,)")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(a_k.device).cuda_stream)
+        rc = self._lib.fmpc_loop_inputs_bank_device(self._h, batch, p(model_of), p(a_k), p(x0_last), p(u1), p(u2), p(x0), p(x0_pre),
+                                                    p(w), stream)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_loop_inputs_bank_device")
+
     def loop_step_device(self, a_k, x0_last, u1, u2, x0, x0_pre, w, nu0=None, n_newton=1, k=1e-2,
                          z_out=None, status=None, iters=None, u0_out=None):
         """fmpc_loop_step_device: loop inputs + solve with first-move output in one call (same results as
