@@ -345,7 +345,8 @@ int fmpc_var_identify_device(int n, int num_train, int num_samples, int batch, c
  * bank as it was.  The bank calls of a handle on different streams are ordered on the device like its solves.
  * fmpc_bank_release frees the bank's memory; it synchronises the device first (a bank solve in flight reads the images), so it must
  * not be called while a stream is being captured -- as fmpc_destroy must not.
- * Every other entry point ignores the bank: fmpc_solve*, fmpc_loop_*, fmpc_ao_step_device answer from the fmpc_create model.
+ * Every other entry point but fmpc_loop_step_bank_device / fmpc_loop_run_bank_device ignores the bank: fmpc_solve*, the other
+ * fmpc_loop_*, fmpc_ao_step_device answer from the fmpc_create model.
  */
 int fmpc_bank_set_device(fmpc_handle h, int count, const double* A1, const double* A2, void* stream);
 int fmpc_bank_count(fmpc_handle h);          /* 0 = no bank (also for a NULL handle) */
@@ -357,7 +358,8 @@ int fmpc_bank_release(fmpc_handle h);
  * A problem whose index is outside [0, count) gets status FMPC_E_DIM and iters 0, nothing of a model is read for it and its other
  * outputs are not written; the other problems are unaffected.
  * The factor of Y is no longer shared between problems, so none of the shared-factor cold-start forms applies: a bank solve
- * always runs the per-problem-factor tiled kernel (inf_newton_solver.m:10-41 per problem), from the cold start too;
+ * always runs the per-problem-factor tiled kernel (inf_newton_solver.m:10-41 per problem), from the cold start too (there the
+ * factorisation of the first step can be taken from a store: fmpc_bank_prefactor_device);
  * fmpc_last_dispatch reports FMPC_PATH_TILED / FMPC_PATH_TILED_F32, fmpc_set_refinement is honoured.
  * FMPC_E_UNSUPPORTED, before anything is enqueued: no bank, a bank built for the other precision, ramp-rate rows, padded z
  * rows (fmpc_set_z_ld), model_of == NULL with batch > count.
@@ -379,6 +381,59 @@ int fmpc_solve_bank_device(fmpc_handle h, int batch, const int* model_of,
 int fmpc_loop_inputs_bank_device(fmpc_handle h, int batch, const int* model_of,
                                  const double* a_k, const double* x0_last, const double* u1,
                                  const double* u2, double* x0, double* x0_pre, double* w, void* stream);
+
+/*
+ * Stored cold-start factor per model of the bank.  The reference's loop calls the solver from the cold start at every timestep
+ * (README.md:548-556: x_init = [], n_fix = 1), where z is the mid-box point (fast_mpc_init.m:12-27), so Phi does not depend on the
+ * data and Y_j = C_j Phi^-1 C_j' and its block Cholesky factor (inf_newton_solver.m:24-32) depend only on the model j, on k and on
+ * the handle.  fmpc_bank_prefactor_device factors Y_j at that point for every model of the bank and barrier weight k, on the device
+ * on `stream` (one workgroup per model at a time, the Newton kernel's own phases), and keeps every model's factor stream in device
+ * memory, in the arithmetic the bank was built for.
+ * MEMORY: nb * 3 NB^2 * 256 * sizeof(REAL) bytes per model (nb = T, + 1 with xf; NB = n / 16 + 1; REAL = double, or float with the
+ * fp32 factor): 737 KB at (n, m, T) = (27, 144, 30) in fp64, so 189 MB for 256 models and 3.0 GB for 4096.  That is why the store is
+ * opt-in.  Allocation follows fmpc_bank_set_device: FMPC_E_ALLOC while `stream` is being captured and the store has to grow, and
+ * fmpc_alloc_generation moves whenever the store is allocated or released.
+ * A model whose factorisation fails (Phi or Y_j not positive definite, a NaN entry) is marked in a per-model device flag and is not
+ * an error of the call; fmpc_bank_prefactor_count is the number of models WITH a stored factor (it synchronises the device and reads
+ * the flags back: not while a stream is being captured).  fmpc_bank_set_device, fmpc_bank_release and fmpc_set_precision invalidate
+ * the store (count 0; the last two also free it or leave it unused), fmpc_bank_prefactor_release frees it (synchronises the device).
+ * FMPC_E_UNSUPPORTED, before anything is enqueued: no bank, a bank built for the other precision, a dense R, ramp-rate rows.
+ *
+ * fmpc_solve_bank_device (and the loop calls below) use the store when the call starts cold (z_init == NULL) and its k equals the
+ * stored k bit for bit: iteration 0 of every problem whose model has a stored factor then forms its residuals and right-hand side as
+ * always, makes NO factorisation, solves R'y = rhs and R d_nu = y by two sweeps through the model's stored records, and goes on with
+ * d_z and the line search; the refinement sweeps of the fp32 factor read the stored records too.  Later iterations of a budget,
+ * problems of a marked model and every other call take the path they always took.  Results agree with the unstored path to rounding
+ * (the forward sweep sums in another order than the one that rides along the factorisation), not bitwise.
+ * fmpc_last_bank_stored_factor: 1 when the last bank solve was handed the stored factors.
+ * WHEN TO USE IT (MI355X, (27, 144, 30), one model per realisation, one Newton step): a loop step takes 0.30 ms
+ * against 0.58 ms at 256 realisations and 1.19 against 1.92 ms at 2048; the build costs about one unstored step of as many
+ * realisations (0.61 ms for 256 models, 3.8 ms for 4096), so a stretch of three or more steps at one k gains.  It does not pay for a
+ * single solve, for a k that changes from call to call, or for warm starts (never used there); it lost at no batch size measured.
+ */
+int fmpc_bank_prefactor_device(fmpc_handle h, double k, void* stream);
+int fmpc_bank_prefactor_count(fmpc_handle h);      /* models with a stored factor; 0 = none (also for a NULL handle) */
+int fmpc_bank_prefactor_release(fmpc_handle h);
+int fmpc_last_bank_stored_factor(fmpc_handle h);   /* 1: the last bank solve was given the stored factors */
+
+/*
+ * The closed loop with the bank's models (README.md:444-626 with every realisation's own model, README.md:108-130).
+ * fmpc_loop_step_bank_device: fmpc_loop_step_device plus model_of -- fmpc_loop_inputs_bank_device followed by
+ * fmpc_solve_bank_device from the cold start (same results as the two calls), under one lock.  z_out may be NULL (first moves only).
+ * fmpc_loop_run_bank_device: fmpc_loop_run_device plus model_of -- `steps` such steps with the first moves fed back on the device
+ * (u[k] into U0, the residuals x0 into X0 when it is not NULL), x0 updated in place.
+ * Neither synchronises, and neither allocates once the workspace exists: both can be recorded into a HIP graph.  With a stored
+ * factor for k (fmpc_bank_prefactor_device) every step takes it.  FMPC_E_UNSUPPORTED as for fmpc_solve_bank_device.
+ */
+int fmpc_loop_step_bank_device(fmpc_handle h, int batch, const int* model_of, const double* a_k, const double* x0_last,
+                               const double* u1, const double* u2, double* x0, double* x0_pre, double* w,
+                               const double* nu0, int n_newton, double k,
+                               double* z_out, double* nu_out, int* status, int* iters, double* step,
+                               double* u0_out, void* stream);
+int fmpc_loop_run_bank_device(fmpc_handle h, int batch, int steps, const int* model_of, const double* a, const double* nu0,
+                              const double* u_before1, const double* u_before2, int have_x0_last,
+                              int n_newton, double k, double* x0, double* x0_pre, double* w,
+                              double* U0, double* X0, int* status, int* iters, void* stream);
 
 /*
  * Arithmetic of the per-problem-factor path (no counterpart in the reference, which is fp64 throughout).

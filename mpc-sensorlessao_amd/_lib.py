@@ -81,6 +81,12 @@ SIGNATURES = {
     "fmpc_bank_release": (C.c_int, [_vp]),
     "fmpc_solve_bank_device": (C.c_int, [_vp, C.c_int, _vp] + [_vp] * 5 + [C.c_int, C.c_double] + [_vp] * 6 + [_vp]),
     "fmpc_loop_inputs_bank_device": (C.c_int, [_vp, C.c_int, _vp] + [_vp] * 7 + [_vp]),
+    "fmpc_bank_prefactor_device": (C.c_int, [_vp, C.c_double, _vp]),
+    "fmpc_bank_prefactor_count": (C.c_int, [_vp]),
+    "fmpc_bank_prefactor_release": (C.c_int, [_vp]),
+    "fmpc_last_bank_stored_factor": (C.c_int, [_vp]),
+    "fmpc_loop_step_bank_device": (C.c_int, [_vp, C.c_int, _vp] + [_vp] * 8 + [C.c_int, C.c_double] + [_vp] * 6 + [_vp]),
+    "fmpc_loop_run_bank_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp] + [_vp] * 4 + [C.c_int, C.c_int, C.c_double] + [_vp] * 7 + [_vp]),
     "fmpc_phase_residual_device": (C.c_int, [_vp, C.c_int, C.c_longlong] + [_vp] * 4 + [_vp]),
     "fmpc_est_create": (C.c_int, [C.POINTER(_vp)] + [C.c_int] * 4 + [_vp, _vp, C.c_double, _vp, _vp, C.c_int, C.c_int, C.c_int]),
     "fmpc_est_destroy": (C.c_int, [_vp]),

@@ -21,8 +21,19 @@ class ClosedLoop:
     """ramp=True (after `handle.set_ramp`): every solve carries the VAR_1 variant's ramp-rate rows against the
     previous first move, u_prev = U(1:nu) (README.md:589; VAR_1/fast_mpc_ineq_const.m:58-76), zeros at the first step."""
 
-    def __init__(self, handle, batch, n_newton=1, k=1e-2, device=None, ramp=False, fused=True, keep_z=True):
+    def __init__(self, handle, batch, n_newton=1, k=1e-2, device=None, ramp=False, fused=True, keep_z=True, bank=False, model_of=None):
         import torch
+        # bank=True (after `handle.set_model_bank`): realisation p runs with model model_of[p] of the handle's bank (int32 HIP tensor;
+        # None: model p), as in the reference, where every realisation identifies its own A1, A2 (README.md:108-130) -- `step` and
+        # `run_recorded` go through fmpc_loop_step_bank_device / fmpc_loop_run_bank_device; with `handle.prefactor_model_bank(k)`
+        # every step sweeps through its model's stored cold-start factor.
+        self.bank = bool(bank)
+        if self.bank and ramp:
+            raise ValueError("ClosedLoop: the model bank has no form with ramp-rate rows")
+        if model_of is not None and not (self.bank and model_of.is_cuda and model_of.dtype == torch.int32 and model_of.is_contiguous()
+                                         and model_of.numel() == int(batch)):
+            raise ValueError("model_of: needs bank=True and a contiguous int32 HIP tensor of (batch,)")
+        self.model_of = model_of
         self.h, self.batch, self.n_newton, self.k = handle, int(batch), int(n_newton), float(k)
         dev = torch.device("cuda", handle.device) if device is None else device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -50,6 +61,7 @@ class ClosedLoop:
         self._p = dict(xb=[vp(b) for b in self._xb], x0_pre=vp(self.x0_pre), w=vp(self.w), u=[vp(u) for u in self.u], z=vp(self.z),
                        status=vp(self.status), iters=vp(self.iters))
         self._fn = handle._lib.fmpc_loop_step_device
+        self._p["model_of"] = vp(model_of)
         self._n_newton_c, self._k_c = int(self.n_newton), float(self.k)
 
     @property
@@ -80,7 +92,12 @@ class ClosedLoop:
         a view into the loop's ring buffer (valid until two further steps)."""
         s = self.steps_done
         u_new, u1, u2 = self.u[s % 3], self.u[(s - 1) % 3], self.u[(s - 2) % 3]
-        if self.ramp or not self.fused:
+        if self.bank:
+            # (x0 in place: fmpc_loop_inputs_bank_device reads x0_last before it writes x0)
+            self.h.loop_step_bank(a_k, self.x0 if s >= 1 else None, u1 if s >= 1 else None, u2 if s >= 2 else None, self.x0, self.x0_pre,
+                                  self.w, nu0, self.n_newton, self.k, model_of=self.model_of, z_out=self.z, status=self.status,
+                                  iters=self.iters, u0_out=u_new)
+        elif self.ramp or not self.fused:
             self.h.loop_inputs_device(a_k, self.x0 if s >= 1 else None, u1 if s >= 1 else None, u2 if s >= 2 else None,
                                       self.x0, self.x0_pre, self.w)
             self.h.solve_device(self.x0, self.x0_pre, self.w, None, nu0, self.n_newton, self.k, z_out=self.z,
@@ -95,7 +112,7 @@ class ClosedLoop:
         """The whole stretch a (steps, batch, n) in ONE C call (fmpc_loop_run_device): first moves only, fed back on the device.
         Continues from this object's state.  Returns (U0 (steps, batch, m), X0 (steps, batch, n) or None)."""
         torch, C = self._torch, self._C
-        if self.ramp or not self.fused:
+        if not self.bank and (self.ramp or not self.fused):
             raise ValueError("run_recorded: the fused step without ramp rows only")
         steps = a.shape[0]
         assert a.is_cuda and a.dtype == torch.float64 and a.is_contiguous() and tuple(a.shape[1:]) == (self.batch, self.h.n)
@@ -105,6 +122,14 @@ class ClosedLoop:
         s = self.steps_done
         P = self._p
         vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        if self.bank:
+            self.h.loop_run_bank(a, self.x0, self.x0_pre, self.w, U0, X0, None if nu0 is None else nu0.view(steps, self.batch, self.h.nu_len),
+                                 self.u[(s - 1) % 3] if s >= 1 else None, self.u[(s - 2) % 3] if s >= 2 else None, s >= 1,
+                                 self.n_newton, self.k, model_of=self.model_of, status=self.status, iters=self.iters)
+            for j in range(min(steps, 2)):
+                self.u[(s + steps - 1 - j) % 3].copy_(U0[steps - 1 - j])
+            self.steps_done = s + steps
+            return U0, X0
         rc = self.h._lib.fmpc_loop_run_device(self.h._h, self.batch, steps, vp(a), vp(nu0), P["u"][(s - 1) % 3] if s >= 1 else None,
                                               P["u"][(s - 2) % 3] if s >= 2 else None, 1 if s >= 1 else 0, self._n_newton_c, self._k_c,
                                               P["xb"][self._cur], P["x0_pre"], P["w"], vp(U0), vp(X0), P["status"], P["iters"],

@@ -144,6 +144,14 @@ struct fmpc_handle_s {
         size_t plain_stride = 0, pad_stride = 0, yimg_stride = 0;    // doubles, doubles, elements of the factor's type
         DevBuf<double> plain, pad; DevBuf<char> yimg; DevBuf<int> ipool;   // ipool: [desc | iD | i1 | i2]
     } bank;
+    // stored cold-start factor per model of the bank (fmpc_bank_prefactor_device): the factor stream of Y_j at the mid-box start for
+    // barrier weight k, count * stride elements of the bank's arithmetic; flag[j] != 0: model j has none
+    struct BankFactor {
+        int valid = 0, count = 0, t = 0, prepared[2] = {0, 0};
+        double k = 0.0; size_t stride = 0;
+        DevBuf<char> fac; DevBuf<int> flag;
+    } bkf;
+    int bank_last_stored = 0;             // the last bank solve was handed the stored factors (fmpc_last_bank_stored_factor)
     DevBuf<double> tl_ws; int tl_prepared = 0;                   // (bit NW: that wavefront count of the fp64 instance is prepared)
     int tl_last_nw = 0;                   // wavefronts per problem of the last tiled launch (diagnostic)
     int z_ld = 0;                         // fmpc_set_z_ld: doubles between the z rows of consecutive problems (0: T (n + m))
@@ -839,6 +847,7 @@ extern "C" int fmpc_set_precision(fmpc_handle h, int mode) {
         h->generic_ok = 1; h->generic_big = 1; h->lds_bytes = lds; h->wg_per_cu = 2;
     }
     h->prec = mode;
+    h->bkf.valid = 0;                                                  // (the stored factors of a bank belong to the arithmetic they were built in)
     return FMPC_OK;
 }
 
@@ -1539,6 +1548,7 @@ extern "C" int fmpc_bank_set_device(fmpc_handle h, int count, const double* A1, 
     if (capturing && (plain_stride * (size_t)count > B.plain.cap || pad_stride * (size_t)count > B.pad.cap || ybytes > B.yimg.cap))
         return FMPC_E_ALLOC;                                           // (the bank that is there stays as it is)
     B.count = 0;                                                       // (no bank while it is being replaced)
+    h->bkf.valid = 0;                                                  // (and no stored factors of the models that leave)
     int rc = fmpc_guard_begin(h, stream);                             // (an earlier bank solve may still read the old images)
     if (rc != FMPC_OK) return rc;
     rc = B.plain.grow(plain_stride * (size_t)count, stream);
@@ -1571,7 +1581,70 @@ extern "C" int fmpc_bank_release(fmpc_handle h) {
     if (B.plain.p || B.pad.p || B.yimg.p) (void)hipDeviceSynchronize();   // (a bank solve in flight reads them)
     B.plain.release(); B.pad.release(); B.yimg.release();
     B.count = 0;
+    h->bkf.valid = 0; h->bkf.fac.release(); h->bkf.flag.release();
     return FMPC_OK;
+}
+
+// The parameter block of a launch over the bank's models (the bank solve, the build of the stored factors): the handle's constants
+// with the model-dependent images replaced by the bank's.  Caller holds h->mu; the per-call fields are the caller's.
+static void fmpc_bank_params(fmpc_handle h, int t, FtParams& P) {
+    const fmpc_handle_s::Bank& B = h->bank;
+    const fmpc_handle_s::Tiled& X = h->tl[t];
+    const int nb = h->nb, NP = 16 * X.NB;
+    const size_t nn = (size_t)h->n * h->n, PP = (size_t)NP * NP;
+    P.M = h->dev; P.V = X.V;
+    P.M.A1 = B.plain; P.M.A2 = B.plain + nn; P.M.A1t = B.plain + 2 * nn; P.M.A2t = B.plain + 3 * nn;
+    P.M.Yblk = nullptr; P.M.idxD = nullptr; P.M.idx1 = nullptr; P.M.idx2 = nullptr;      // (the handle's: not the bank's, and not read)
+    P.V.A1P = B.pad; P.V.A2P = B.pad + PP; P.V.A1tP = B.pad + 2 * PP; P.V.A2tP = B.pad + 3 * PP;
+    P.V.yimg = B.yimg.p; P.V.nblk = B.nblk;
+    const int* tab = B.ipool + (size_t)B.nblk * FB_DESC_INTS;
+    P.V.iD = tab; P.V.i1 = tab + nb; P.V.i2 = tab + 2 * nb;
+    P.list = nullptr; P.nlist = nullptr; P.nuws = nullptr;             // (the continuation lists belong to the shared-factor forms)
+    P.bk_count = B.count;
+    P.bk_plain = B.plain_stride; P.bk_pad = B.pad_stride; P.bk_yimg = B.yimg_stride;
+}
+
+// What a bank solve refuses before anything is enqueued.  Caller holds h->mu.
+static int fmpc_bank_solve_check(fmpc_handle h, int batch, const int* model_of) {
+    const fmpc_handle_s::Bank& B = h->bank;
+    const int t = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
+    if (B.count <= 0 || B.t != t || fmpc_bank_unsupported(h, t) || !h->tl[t].ready) return FMPC_E_UNSUPPORTED;
+    if (h->z_ld > h->T * (h->n + h->m)) return FMPC_E_UNSUPPORTED;
+    if (!model_of && batch > B.count) return FMPC_E_UNSUPPORTED;
+    return FMPC_OK;
+}
+// Everything a bank solve allocates (the scratch iterate of a first-moves-only call, the tiled workspace), before its launch and
+// before a caller's own launch in front of it (the loop inputs of fmpc_loop_step_bank_device).  Caller holds h->mu.
+static int fmpc_bank_solve_plan(fmpc_handle h, FmpcSolve& s, FmpcTiledPlan* plan) {
+    const int t = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
+    if (!s.z_out) {                                                    // first moves only: the iterate lives in the handle's scratch
+        const int rc = fmpc_scratch_z(h, s.batch, s.stream);
+        if (rc != FMPC_OK) return rc;
+        s.z_out = h->zs;
+    }
+    return fmpc_tiled_plan(h, t, s.batch, s.stream, 0, 0, plan);
+}
+static int fmpc_bank_solve_launch(fmpc_handle h, const FmpcSolve& s, const int* model_of, const FmpcTiledPlan& plan) {
+    const int t = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
+    fmpc_handle_s::Tiled& X = h->tl[t];
+    const fmpc_handle_s::BankFactor& F = h->bkf;
+    FtParams P;
+    fmpc_bank_params(h, t, P);
+    P.batch = s.batch;
+    P.x0 = s.x0; P.x0p = s.x0_pre; P.w = s.w; P.zinit = s.z_init; P.nu0 = s.nu0;
+    P.max_iter = fmpc_max_iter(s); P.kbar = s.k;
+    P.zout = s.z_out; P.nuout = s.nu_out; P.status = s.status; P.iters = s.iters; P.step = s.step; P.step_ld = fmpc_step_ld(s.n_newton);
+    P.ws = h->tl_ws; P.ws_stride = plan.slot; P.u0out = s.u0_out;
+    P.refine = t ? h->refine : 0;
+    P.model_of = model_of;
+    // the stored cold-start factors: from the cold start only, and only for the k they were built for, bit for bit
+    const bool stored = F.valid && F.t == t && F.count == h->bank.count && !h->denseR && !s.z_init && memcmp(&s.k, &F.k, sizeof(double)) == 0;
+    if (stored) { P.pf_fac = F.fac.p; P.pf_flag = F.flag; P.pf_stride = F.stride; }
+    h->bank_last_stored = stored ? 1 : 0;
+    h->tl_last_nw = plan.NWu;
+    if (t) h->refine_last = P.refine;
+    h->last_path = t ? FMPC_PATH_TILED_F32 : FMPC_PATH_TILED;
+    return fmpc_launch_tiled(P, X.NB, plan.NWu, t, plan.grid, plan.ldsu, s.stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
 extern "C" int fmpc_solve_bank_device(fmpc_handle h, int batch, const int* model_of,
@@ -1585,49 +1658,97 @@ extern "C" int fmpc_solve_bank_device(fmpc_handle h, int batch, const int* model
     hipStream_t stream = (hipStream_t)stream_;
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
     std::lock_guard<std::mutex> lk(h->mu);
-    fmpc_handle_s::Bank& B = h->bank;
-    const int t = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
-    if (B.count <= 0 || B.t != t || fmpc_bank_unsupported(h, t) || !h->tl[t].ready) return FMPC_E_UNSUPPORTED;
-    if (h->z_ld > h->T * (h->n + h->m)) return FMPC_E_UNSUPPORTED;
-    if (!model_of && batch > B.count) return FMPC_E_UNSUPPORTED;
-    FmpcSolve s{batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step, u0_out, stream, 0};
-    int rc = fmpc_guard_begin(h, stream);
+    int rc = fmpc_bank_solve_check(h, batch, model_of);
     if (rc != FMPC_OK) return rc;
-    if (!s.z_out) {                                                    // first moves only: the iterate lives in the handle's scratch
-        rc = fmpc_scratch_z(h, batch, stream);
-        if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
-        s.z_out = h->zs;
-    }
+    FmpcSolve s{batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step, u0_out, stream, 0};
+    rc = fmpc_guard_begin(h, stream);
+    if (rc != FMPC_OK) return rc;
     FmpcTiledPlan plan;
-    rc = fmpc_tiled_plan(h, t, batch, stream, 0, 0, &plan);
-    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
-    fmpc_handle_s::Tiled& X = h->tl[t];
-    const int nb = h->nb, NP = 16 * X.NB;
-    const size_t nn = (size_t)h->n * h->n, PP = (size_t)NP * NP;
-    FtParams P;
-    P.M = h->dev; P.V = X.V; P.batch = batch;
-    P.M.A1 = B.plain; P.M.A2 = B.plain + nn; P.M.A1t = B.plain + 2 * nn; P.M.A2t = B.plain + 3 * nn;
-    P.M.Yblk = nullptr; P.M.idxD = nullptr; P.M.idx1 = nullptr; P.M.idx2 = nullptr;      // (the handle's: not the bank's, and not read)
-    P.V.A1P = B.pad; P.V.A2P = B.pad + PP; P.V.A1tP = B.pad + 2 * PP; P.V.A2tP = B.pad + 3 * PP;
-    P.V.yimg = B.yimg.p; P.V.nblk = B.nblk;
-    const int* tab = B.ipool + (size_t)B.nblk * FB_DESC_INTS;
-    P.V.iD = tab; P.V.i1 = tab + nb; P.V.i2 = tab + 2 * nb;
-    P.x0 = s.x0; P.x0p = s.x0_pre; P.w = s.w; P.zinit = s.z_init; P.nu0 = s.nu0;
-    P.max_iter = fmpc_max_iter(s); P.kbar = s.k;
-    P.zout = s.z_out; P.nuout = s.nu_out; P.status = s.status; P.iters = s.iters; P.step = s.step; P.step_ld = fmpc_step_ld(s.n_newton);
-    P.ws = h->tl_ws; P.ws_stride = plan.slot; P.u0out = s.u0_out;
-    P.list = nullptr; P.nlist = nullptr; P.nuws = nullptr;             // (the continuation lists belong to the shared-factor forms)
-    P.refine = t ? h->refine : 0;
-    P.model_of = model_of; P.bk_count = B.count;
-    P.bk_plain = B.plain_stride; P.bk_pad = B.pad_stride; P.bk_yimg = B.yimg_stride;
-    h->tl_last_nw = plan.NWu;
-    if (t) h->refine_last = P.refine;
-    h->last_path = t ? FMPC_PATH_TILED_F32 : FMPC_PATH_TILED;
-    rc = fmpc_launch_tiled(P, X.NB, plan.NWu, t, plan.grid, plan.ldsu, stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
+    rc = fmpc_bank_solve_plan(h, s, &plan);
+    if (rc == FMPC_OK) rc = fmpc_bank_solve_launch(h, s, model_of, plan);
     fmpc_guard_end(h, stream);
     return rc;
 }
 
+// ---- stored cold-start factor per model of the bank (include/fastmpc.h)
+extern "C" int fmpc_bank_prefactor_device(fmpc_handle h, double k, void* stream_) {
+    if (!h) return FMPC_E_NULL;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    std::lock_guard<std::mutex> lk(h->mu);
+    fmpc_handle_s::Bank& B = h->bank;
+    fmpc_handle_s::BankFactor& F = h->bkf;
+    const int t = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
+    if (B.count <= 0 || B.t != t || h->denseR || fmpc_bank_unsupported(h, t) || !h->tl[t].ready) return FMPC_E_UNSUPPORTED;
+    fmpc_handle_s::Tiled& X = h->tl[t];
+    const size_t stride = (size_t)h->nb * ft_stage_tiles(X.NB) * FT_TILE;                  // elements of the factor's type per model
+    const size_t bytes = stride * (size_t)B.count * (t ? sizeof(float) : sizeof(double));
+    if (fmpc_capturing(stream) && (bytes > F.fac.cap || (size_t)B.count > F.flag.cap || !F.prepared[t])) return FMPC_E_ALLOC;
+    F.valid = 0;                                                       // (no store while it is being rebuilt)
+    int rc = fmpc_guard_begin(h, stream);                             // (an earlier bank solve may still read the old factors)
+    if (rc != FMPC_OK) return rc;
+    FmpcTiledPlan plan;
+    rc = fmpc_tiled_plan(h, t, B.count, stream, 0, 0, &plan);
+    if (rc == FMPC_OK) rc = fmpc_scratch_z(h, plan.grid, stream);     // the start point, one per workgroup
+    if (rc == FMPC_OK) rc = F.fac.grow(bytes, stream);
+    if (rc == FMPC_OK) rc = F.flag.grow((size_t)B.count, stream);
+    if (rc == FMPC_OK && !F.prepared[t]) {
+        if (fmpc_bank_prefactor_prepare(h->n, X.NB, plan.NWu, t, plan.ldsu) == hipSuccess) F.prepared[t] = 1;
+        else rc = FMPC_E_HIP;
+    }
+    if (rc == FMPC_OK) {
+        FtParams P;
+        fmpc_bank_params(h, t, P);
+        P.batch = B.count;
+        P.x0 = nullptr; P.x0p = nullptr; P.w = nullptr; P.zinit = nullptr; P.nu0 = nullptr;
+        P.max_iter = 1; P.kbar = k;
+        P.zout = h->zs; P.nuout = nullptr; P.status = nullptr; P.iters = nullptr; P.step = nullptr; P.step_ld = 0;
+        P.ws = h->tl_ws; P.ws_stride = plan.slot; P.u0out = nullptr;
+        P.refine = 0; P.model_of = nullptr;
+        P.pf_fac = F.fac.p; P.pf_flag = F.flag; P.pf_stride = stride;
+        if (fmpc_launch_bank_prefactor(P, X.NB, plan.NWu, t, plan.grid, plan.ldsu, stream) != hipSuccess) rc = FMPC_E_HIP;
+    }
+    fmpc_guard_end(h, stream);
+    if (rc != FMPC_OK) return rc;
+    F.valid = 1; F.count = B.count; F.t = t; F.k = k; F.stride = stride;
+    return FMPC_OK;
+}
+extern "C" int fmpc_bank_prefactor_count(fmpc_handle h) {
+    if (!h) return 0;
+    if (hipSetDevice(h->device) != hipSuccess) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const fmpc_handle_s::BankFactor& F = h->bkf;
+    if (!F.valid || F.count <= 0) return 0;
+    std::vector<int> fl((size_t)F.count);
+    if (hipDeviceSynchronize() != hipSuccess) return 0;               // (the build may still be running, on any stream)
+    if (hipMemcpy(fl.data(), F.flag, fl.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    int good = 0;
+    for (int f : fl) good += f == 0 ? 1 : 0;
+    return good;
+}
+extern "C" int fmpc_bank_prefactor_release(fmpc_handle h) {
+    if (!h) return FMPC_E_NULL;
+    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    std::lock_guard<std::mutex> lk(h->mu);
+    fmpc_handle_s::BankFactor& F = h->bkf;
+    if (F.fac.p || F.flag.p) (void)hipDeviceSynchronize();           // (a bank solve in flight reads them)
+    F.valid = 0; F.count = 0;
+    F.fac.release(); F.flag.release();
+    return FMPC_OK;
+}
+extern "C" int fmpc_last_bank_stored_factor(fmpc_handle h) {
+    if (!h) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return h->bank_last_stored;
+}
+
+// caller holds h->mu and has checked that a bank exists
+static int fmpc_loop_inputs_bank_launch(fmpc_handle h, int batch, const int* model_of, const double* a_k, const double* x0_last,
+                                        const double* u1, const double* u2, double* x0, double* x0_pre, double* w, hipStream_t stream) {
+    const fmpc_handle_s::Bank& B = h->bank;
+    return fmpc_launch_loop_inputs_bank(h->n, h->m, h->T, h->var_order == 2, batch, h->dev.Bt, B.plain, B.plain_stride, B.count,
+                                        model_of, a_k, x0_last, u1, u2, x0, x0_pre, w, stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
+}
 extern "C" int fmpc_loop_inputs_bank_device(fmpc_handle h, int batch, const int* model_of,
                                             const double* a_k, const double* x0_last, const double* u1,
                                             const double* u2, double* x0, double* x0_pre, double* w, void* stream) {
@@ -1641,11 +1762,57 @@ extern "C" int fmpc_loop_inputs_bank_device(fmpc_handle h, int batch, const int*
     // (the bank's images are rewritten in place by fmpc_bank_set_device: ordered against it like the bank solve)
     int rc = fmpc_guard_begin(h, (hipStream_t)stream);
     if (rc != FMPC_OK) return rc;
-    rc = fmpc_launch_loop_inputs_bank(h->n, h->m, h->T, h->var_order == 2, batch, h->dev.Bt, B.plain, B.plain_stride, B.count,
-                                      model_of, a_k, x0_last, u1, u2, x0, x0_pre, w, (hipStream_t)stream) == hipSuccess
-             ? FMPC_OK : FMPC_E_HIP;
+    rc = fmpc_loop_inputs_bank_launch(h, batch, model_of, a_k, x0_last, u1, u2, x0, x0_pre, w, (hipStream_t)stream);
     fmpc_guard_end(h, (hipStream_t)stream);
     return rc;
+}
+
+// One closed-loop step with the bank's models: fmpc_loop_inputs_bank_device + fmpc_solve_bank_device from the cold start under one
+// lock; everything the solve allocates exists before the loop inputs are enqueued.
+extern "C" int fmpc_loop_step_bank_device(fmpc_handle h, int batch, const int* model_of, const double* a_k, const double* x0_last,
+                                          const double* u1, const double* u2, double* x0, double* x0_pre, double* w,
+                                          const double* nu0, int n_newton, double k,
+                                          double* z_out, double* nu_out, int* status, int* iters, double* step,
+                                          double* u0_out, void* stream_) {
+    if (!h || !a_k || !x0 || !x0_pre || !w || !u0_out) return FMPC_E_NULL;                 // z_out may be NULL: first moves only
+    if (batch < 0) return FMPC_E_DIM;
+    if (batch == 0) return FMPC_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    std::lock_guard<std::mutex> lk(h->mu);
+    int rc = fmpc_bank_solve_check(h, batch, model_of);
+    if (rc != FMPC_OK) return rc;
+    FmpcSolve s{batch, x0, x0_pre, w, nullptr, nu0, n_newton, k, z_out, nu_out, status, iters, step, u0_out, stream, 0};
+    rc = fmpc_guard_begin(h, stream);
+    if (rc != FMPC_OK) return rc;
+    FmpcTiledPlan plan;
+    rc = fmpc_bank_solve_plan(h, s, &plan);
+    if (rc == FMPC_OK) rc = fmpc_loop_inputs_bank_launch(h, batch, model_of, a_k, x0_last, u1, u2, x0, x0_pre, w, stream);
+    if (rc == FMPC_OK) rc = fmpc_bank_solve_launch(h, s, model_of, plan);
+    fmpc_guard_end(h, stream);
+    return rc;
+}
+
+// A stretch of the loop with the bank's models in ONE host call: steps consecutive fmpc_loop_step_bank_device calls with the first
+// moves fed back on the device (u[k] = U0[k], u[k-1] = U0[k-1], ...), x0 updated in place.
+extern "C" int fmpc_loop_run_bank_device(fmpc_handle h, int batch, int steps, const int* model_of, const double* a, const double* nu0,
+                                         const double* u_before1, const double* u_before2, int have_x0_last,
+                                         int n_newton, double k, double* x0, double* x0_pre, double* w,
+                                         double* U0, double* X0, int* status, int* iters, void* stream) {
+    if (!h || !a || !x0 || !x0_pre || !w || !U0) return FMPC_E_NULL;
+    if (batch < 0 || steps < 0) return FMPC_E_DIM;
+    if (batch == 0 || steps == 0) return FMPC_OK;
+    const size_t sn = (size_t)batch * h->n, sm = (size_t)batch * h->m, snu = (size_t)batch * h->nb * h->n;
+    for (int s = 0; s < steps; ++s) {
+        const double* u1 = s >= 1 ? U0 + (size_t)(s - 1) * sm : u_before1;
+        const double* u2 = s >= 2 ? U0 + (size_t)(s - 2) * sm : (s == 1 ? u_before1 : u_before2);
+        const int rc = fmpc_loop_step_bank_device(h, batch, model_of, a + (size_t)s * sn, (s >= 1 || have_x0_last) ? x0 : nullptr, u1, u2,
+                                                  x0, x0_pre, w, nu0 ? nu0 + (size_t)s * snu : nullptr, n_newton, k, nullptr, nullptr,
+                                                  status, iters, nullptr, U0 + (size_t)s * sm, stream);
+        if (rc != FMPC_OK) return rc;
+        if (X0 && hipMemcpyAsync(X0 + (size_t)s * sn, x0, sn * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return FMPC_E_HIP;
+    }
+    return FMPC_OK;
 }
 
 extern "C" int fmpc_solve_device(fmpc_handle h, int batch,

@@ -258,21 +258,29 @@ __device__ __noinline__ void ft_backward(const R* fac_, const double* yv_, R* sX
 
 }
 
-// Forward substitution R'y = rho with the stored factor, for a refinement sweep (FtParams::refine; the forward sweep of the Newton
-// step itself rides in column n of the blocks while they are factored).  The mirror of ft_backward: the same records, from stage 0
-// upward, requested a group ahead, every load unconditional at a constant offset from an opaque record offset.  A record is a ROW
-// of R, and R' y needs its columns, so the sweep runs in the PUSH orientation: once y of the 16-row block (i, kb) is known,
-// tile' y is subtracted from the right-hand sides of the blocks the record's tiles point at -- R(kb, J) at (i, J), U1(kb, J) at
-// (i + 1, J), U2(kb, J) at (i + 2, J) -- which are kept in LDS for the three stages i, i + 1, i + 2 (sACC: the x vectors of the
-// backward sweep).  A tile is read by ONE wavefront, 16 bytes per lane (lane l: row l / 4, columns 4 (l % 4) ..+3, a contiguous
-// kilobyte), so the sum over the tile's rows stays inside the wavefront (two DPP rotations, two lane exchanges) and every
-// right-hand side has one writer per step: the order of the fp32 sums is fixed.  rho is read from yv and y written over it.
+// Forward substitution R'y = rho with a stored factor: a refinement sweep of the fp32 factor (FtParams::refine), and the forward
+// sweep of a cold-start step that is handed its model's stored factor (FtParams::pf_fac) in either arithmetic.  (The forward sweep
+// of a step that factors rides in column n of the blocks while they are factored.)  The mirror of ft_backward: the same records,
+// from stage 0 upward, requested a group ahead, every load unconditional at a constant offset from an opaque record offset.  A
+// record is a ROW of R, and R' y needs its columns, so the sweep runs in the PUSH orientation: once y of the 16-row block (i, kb)
+// is known, tile' y is subtracted from the right-hand sides of the blocks the record's tiles point at -- R(kb, J) at (i, J),
+// U1(kb, J) at (i + 1, J), U2(kb, J) at (i + 2, J) -- which are kept in LDS for the three stages i, i + 1, i + 2 (sACC: the x
+// vectors of the backward sweep).  A tile is read by ONE wavefront, 16 bytes per lane and load, every load a contiguous kilobyte:
+//   fp32  one load: lane l has row l / 4, columns 4 (l % 4) .. + 3
+//   fp64  two loads (a tile is 2 KB): lane l has rows l / 8 and 8 + l / 8, columns 2 (l % 8), + 1
+// so the sum over the tile's rows stays inside the wavefront (DPP rotations inside a row of 16 lanes, two lane exchanges across
+// them) and every right-hand side has one writer per step: the order of the sums is fixed.  rho is read from yv and y written
+// over it.
+template <typename R> struct FtFwd;
+template <> struct FtFwd<float> { typedef ft_f4 vec; static constexpr int EPL = 4, NH = 1; };
+template <> struct FtFwd<double> { typedef ft_d2 vec; static constexpr int EPL = 2, NH = 2; };
 template <typename R>
-__device__ __forceinline__ ft_f4 ft_col_sum4(ft_f4 v) {      // sum over the lanes l = c (mod 4) of a wavefront, per component
+__device__ __forceinline__ typename FtFwd<R>::vec ft_col_sum(typename FtFwd<R>::vec v) {   // sum over the lanes with this lane's columns, per component
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < FtFwd<R>::EPL; ++k) {
         R x = v[k];
-        x += ft_dpp<0x124>(x); x += ft_dpp<0x128>(x);
+        if (FtFwd<R>::EPL == 4) x += ft_dpp<0x124>(x);
+        x += ft_dpp<0x128>(x);
         x += __shfl_xor(x, 16, 64); x += __shfl_xor(x, 32, 64);
         v[k] = x;
     }
@@ -280,12 +288,14 @@ __device__ __forceinline__ ft_f4 ft_col_sum4(ft_f4 v) {      // sum over the lan
 }
 template <typename R, int NB, int NW>
 __device__ __noinline__ void ft_forward(const R* fac_, double* yv_, R* sACC_, R* sY_, int n, int nb) {
-    static_assert(sizeof(R) == 4, "refinement exists for the fp32 factor only");
-    typedef const ft_f4 __attribute__((address_space(1))) * GV;
+    typedef typename FtFwd<R>::vec V;
+    constexpr int EPL = FtFwd<R>::EPL, NH = FtFwd<R>::NH;
+    constexpr int CL = 16 / EPL, RPL = 64 / CL;            // lanes per tile row, tile rows per load
+    typedef const V __attribute__((address_space(1))) * GV;
     typedef const R __attribute__((address_space(1))) * GR;
     typedef double __attribute__((address_space(1))) * GD;
     typedef R __attribute__((address_space(3))) * LR;
-    typedef ft_f4 __attribute__((address_space(3))) * LV;
+    typedef V __attribute__((address_space(3))) * LV;
     const GR fac = (GR)fac_;
     const GD yv = (GD)yv_;
     const LR sACC = (LR)sACC_, sY = (LR)sY_;
@@ -293,7 +303,7 @@ __device__ __noinline__ void ft_forward(const R* fac_, double* yv_, R* sACC_, R*
     constexpr int MAXT = (REC_TILES - 1 + NW - 1) / NW;    // tiles 1 .. 3 NB - 1 of a record, dealt to the wavefronts
     constexpr int G = 3;
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tr = lane >> 2, cq = lane & 3;
+    const int tr = lane / CL, cq = lane % CL;
     const int nblk = nb * NB;
     for (int q = tid; q < 3 * NP; q += NT) {                // right-hand sides of the stages 0, 1, 2
         const int i = q / NP, e = q - i * NP;
@@ -301,60 +311,70 @@ __device__ __noinline__ void ft_forward(const R* fac_, double* yv_, R* sACC_, R*
         sACC[q] = (i < nb && e < n) ? (R)v : (R)0;
     }
     __syncthreads();
-    ft_f4 tvA[G][MAXT], rivA[G];
+    V tvA[G][MAXT][NH], rivA[G][NH];
     double rhA[G];
-    auto request = [&](int base, ft_f4 (&tv)[G][MAXT], ft_f4 (&riv)[G], double (&rh)[G]) {
+    auto request = [&](int base, V (&tv)[G][MAXT][NH], V (&riv)[G][NH], double (&rh)[G]) {
 #pragma unroll
         for (int u = 0; u < G; ++u) {
             const int blk = base + u < nblk ? base + u : nblk - 1;      // (past the end of the horizon: a harmless re-read)
-            unsigned off = (unsigned)blk * (unsigned)(REC_TILES * FT_TILE) + (unsigned)(4 * lane);
+            unsigned off = (unsigned)blk * (unsigned)(REC_TILES * FT_TILE) + (unsigned)(EPL * lane);
             asm volatile("" : "+v"(off));
             const GR rec = fac + off;
 #pragma unroll
             for (int q = 0; q < MAXT; ++q) {
                 const int t = 1 + wv + q * NW;
                 const int tc = t < REC_TILES ? t : REC_TILES - 1;
-                tv[u][q] = *(GV)(rec + tc * FT_TILE);
+#pragma unroll
+                for (int h = 0; h < NH; ++h) tv[u][q][h] = *(GV)(rec + tc * FT_TILE + h * 64 * EPL);
             }
-            riv[u] = *(GV)rec;
+#pragma unroll
+            for (int h = 0; h < NH; ++h) riv[u][h] = *(GV)(rec + h * 64 * EPL);
             // rho of the block that takes this one's place in LDS: (i + 3, kb)
             const int i = blk / NB, kb = blk - i * NB, row = 16 * kb + (lane & 15);
             rh[u] = yv[(i + 3 < nb ? i + 3 : nb - 1) * n + (row < n ? row : n - 1)];
         }
     };
-    auto step = [&](int blk, ft_f4 (&tv)[MAXT], ft_f4 riv, double rh) {
+    auto step = [&](int blk, V (&tv)[MAXT][NH], V (&riv)[NH], double rh) {
         const int i = blk / NB, kb = blk - i * NB;
         const int s0 = (i % 3) * NP, s1 = ((i + 1) % 3) * NP, s2 = ((i + 2) % 3) * NP;
         // y_kb = R(kb,kb)^-T t_kb with t_kb the right-hand side less everything pushed so far
         if (wv == 0) {
-            ft_f4 v = riv * sACC[s0 + 16 * kb + tr];
-            v = ft_col_sum4<R>(v);
-            if (lane < 4) {
-                *(LV)(sY + 4 * cq) = v;
+            V v = riv[0] * sACC[s0 + 16 * kb + tr];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int row = 16 * kb + 4 * cq + k;
+            for (int h = 1; h < NH; ++h) v += riv[h] * sACC[s0 + 16 * kb + tr + RPL * h];
+            v = ft_col_sum<R>(v);
+            if (lane < CL) {
+                *(LV)(sY + EPL * cq) = v;
+#pragma unroll
+                for (int k = 0; k < EPL; ++k) {
+                    const int row = 16 * kb + EPL * cq + k;
                     if (row < n) yv[i * n + row] = (double)v[k];
                 }
             }
         }
         ft_lds_barrier();
-        const R yr = sY[tr];
+        R yr[NH];
+#pragma unroll
+        for (int h = 0; h < NH; ++h) yr[h] = sY[tr + RPL * h];
 #pragma unroll
         for (int q = 0; q < MAXT; ++q) {
             const int t = 1 + wv + q * NW;
             const int tc = t < REC_TILES ? t : REC_TILES - 1;
             const bool use = t < REC_TILES && (t >= NB || t > kb);     // (tiles 1..kb of a record do not exist)
-            const ft_f4 zero = {0, 0, 0, 0};
-            ft_f4 v = (use ? tv[q] : zero) * yr;
-            v = ft_col_sum4<R>(v);
+            V zero;
+#pragma unroll
+            for (int k = 0; k < EPL; ++k) zero[k] = (R)0;
+            V v = (use ? tv[q][0] : zero) * yr[0];
+#pragma unroll
+            for (int h = 1; h < NH; ++h) v += (use ? tv[q][h] : zero) * yr[h];
+            v = ft_col_sum<R>(v);
             const int J = tc < NB ? tc : (tc < 2 * NB ? tc - NB : tc - 2 * NB);
             const int sl = tc < NB ? s0 : (tc < 2 * NB ? s1 : s2);
-            if (use && lane < 4) {
-                const LV dst = (LV)(sACC + sl + 16 * J + 4 * cq);
-                ft_f4 a = *dst;
+            if (use && lane < CL) {
+                const LV dst = (LV)(sACC + sl + 16 * J + EPL * cq);
+                V a = *dst;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) a[k] -= 16 * J + 4 * cq + k < n ? v[k] : (R)0;   // (column n of a tile is the riding rhs)
+                for (int k = 0; k < EPL; ++k) a[k] -= 16 * J + EPL * cq + k < n ? v[k] : (R)0;   // (column n of a tile is the riding rhs)
                 *dst = a;
             }
         }
@@ -369,7 +389,7 @@ __device__ __noinline__ void ft_forward(const R* fac_, double* yv_, R* sACC_, R*
     }
     request(base, tvA, rivA, rhA);
     for (; base < nblk; base += G) {
-        ft_f4 tvB[G][MAXT], rivB[G];
+        V tvB[G][MAXT][NH], rivB[G][NH];
         double rhB[G];
         request(base + G, tvB, rivB, rhB);
 #pragma unroll
@@ -377,8 +397,11 @@ __device__ __noinline__ void ft_forward(const R* fac_, double* yv_, R* sACC_, R*
 #pragma unroll
         for (int u = 0; u < G; ++u) {
 #pragma unroll
-            for (int q = 0; q < MAXT; ++q) tvA[u][q] = tvB[u][q];
-            rivA[u] = rivB[u];
+            for (int q = 0; q < MAXT; ++q)
+#pragma unroll
+                for (int h = 0; h < NH; ++h) tvA[u][q][h] = tvB[u][q][h];
+#pragma unroll
+            for (int h = 0; h < NH; ++h) rivA[u][h] = rivB[u][h];
             rhA[u] = rhB[u];
         }
     }
@@ -1358,6 +1381,12 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
             sel.mi = mi;
             mo_plain = (size_t)mi * P.bk_plain; mo_pad = (size_t)mi * P.bk_pad;
         }
+        // the stored cold-start factor of this problem's model, when the launch was handed the store and the model has a valid one
+        // (wave-uniform; the flag is one scalar load per problem)
+        [[maybe_unused]] const R* sfac = nullptr;
+        if constexpr (BK && !DR) {
+            if (P.pf_fac && P.pf_flag[sel.mi] == 0) sfac = (const R*)P.pf_fac + (size_t)sel.mi * P.pf_stride;
+        }
         double* zp = P.zout + (size_t)p * Nz;
         const double* x0v = P.x0 + (size_t)p * n;
         const double* x0pv = P.x0p ? P.x0p + (size_t)p * n : nullptr;
@@ -1473,6 +1502,21 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
                 }
             }
             __syncthreads();                                           // (the staging area of nu is the U slots' space)
+            // ================= stored cold-start factor (model bank, fmpc_bank_prefactor_device): at the mid-box start Phi, so Y of this
+            // problem's model and its factor, do not depend on the data.  No S pre-pass and no P3 then: y = R^-T rhs by a forward sweep
+            // through the model's stored records, which the backward sweep (and the refinement sweeps) below read as well.
+            // (Residuals that are not finite -- a NaN in the data -- take the factorisation, which ends such a problem as it always did.)
+            const R* facp = fac;                                       // the factor stream P4 reads: this workgroup's slot, or the store
+            bool stored = false;
+            if constexpr (BK && !DR) {
+                stored = sfac != nullptr && it == 0 && !cont && rho2 < INFINITY;
+                if (stored) {
+                    ft_forward<R, NB, NW>(sfac, yv, sXV, sPART, n, nb);
+                    __syncthreads();                                   // y is in HBM (same workgroup reads it)
+                    facp = sfac;
+                }
+            }
+            if (!stored) {
             // ================= S pre-pass: the initial diagonal blocks S0_i = Y_ii const + B W_i B' (upper-triangular tiles,
             // rhs_i in column n) of EVERY block row, all independent, ahead of the serial factorisation.  The B' tiles are
             // in LDS only for this (the factor phase reuses the space); Phi^-1 of FT_GCH stages at a time in LDS.
@@ -1500,12 +1544,13 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
             if (fail) { st = FMPC_E_NOT_PD_SCHUR; break; }
             __syncthreads();                                           // the factor stream and y are in HBM (same workgroup reads them)
             FT_TICK(6);
+            }
 
             // ================= P4: backward sweep, d_nu_i = R_i^-1 (y_i - U1_i d_nu_{i+1} - U2_i d_nu_{i+2}), one 16-row
             // block at a time from the bottom: x_kb = RI(kb) (y_kb - sum of tile x vector products).  16 consecutive threads
             // read a tile row (coalesced) and sum over it by DPP; the tiles of the NEXT block row are requested before the
             // current one is reduced.  x of stage i lives in buffer i % 3.
-            ft_backward<R, NB, NW>(fac, yv, sXV, sPART, sNU, n, nb, NUROWS);
+            ft_backward<R, NB, NW>(facp, yv, sXV, sPART, sNU, n, nb, NUROWS);
             __syncthreads();
             // ================= iterative refinement of the fp32 solve (on request): rho = rhs - Y d_nu in fp64 against the operator
             // itself, e = R^-1 R^-T rho with the factor just stored (two more reads of its stream, no factorisation), d_nu += e in fp64.
@@ -1513,9 +1558,9 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
             if constexpr (REFINE) {
                 for (int sw = 0; sw < P.refine; ++sw) {
                     ft_phase_refres<R, NB, NW, BK>(ft_params(), sel);
-                    ft_forward<R, NB, NW>(fac, yv, sXV, sPART, n, nb);
+                    ft_forward<R, NB, NW>(facp, yv, sXV, sPART, n, nb);
                     __syncthreads();                                   // y is in HBM (same workgroup reads it)
-                    ft_backward<R, NB, NW, true>(fac, yv, sXV, sPART, sNU, n, nb, NUROWS);
+                    ft_backward<R, NB, NW, true>(facp, yv, sXV, sPART, sNU, n, nb, NUROWS);
                     __syncthreads();
                 }
             }
@@ -1546,7 +1591,71 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_newton_tiled(FtParams P) {
     FT_TL_END();
 }
 
+// The stored cold-start factors of a model bank (fmpc_bank_prefactor_device): ONE WORKGROUP PER MODEL at a time factors Y_j at the
+// mid-box start (fast_mpc_init.m:19-20) for barrier weight kbar with the phase functions of the Newton kernel above -- P1 for Phi^-1
+// at the start point (its residuals are not used: nu, b are zero), the S pre-pass with a zero right-hand side in column n, P3 -- in
+// this workgroup's workspace slot, and copies the factor stream to the model's place in the store.  A model whose Phi or Y is not
+// positive definite (a NaN entry of A1, A2 among them) is flagged and keeps no factor.  P.zout: T (n + m) doubles per workgroup.
+template <typename R, int NB, int NW, int NL>
+__global__ void __launch_bounds__(NW * 64, 2) fmpc_bank_prefactor_k(FtParams P) {
+    constexpr int NT = NW * 64, NQ = NB * NB, STAGE_TILES = 3 * NB * NB;
+    constexpr bool TS = !(sizeof(R) == 8 && NW == 2);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const FmpcDevModel& M = P.M;
+    const int n = M.n, m = M.m, T = M.T, nb = M.nb;
+    const int s = n + m, Nz = T * s, nbn = nb * n;
+    const int tid = threadIdx.x;
+    const FtLds LL = ft_lds_layout(NB, P.V.mb, NW, (int)sizeof(R), nb, 0);
+    R* sSLOT = (R*)(smem + LL.slot);
+    int* sflag = (int*)(smem + LL.flag);
+    const FtWs L = ft_ws_layout(n, m, T, nb, NB, (int)sizeof(R), 0);
+    double* wsp = P.ws + (size_t)blockIdx.x * P.ws_stride;
+    double* b = wsp + L.b;
+    double* nu = wsp + L.nu;
+    double* yv = wsp + L.y;
+    const ft_d2* fac = (const ft_d2*)(wsp + L.fac);
+    double* zp = P.zout + (size_t)blockIdx.x * Nz;
+    const size_t nvec = (size_t)nb * STAGE_TILES * FT_TILE * sizeof(R) / sizeof(ft_d2);
+    for (int mi = blockIdx.x; mi < P.bk_count; mi += gridDim.x) {
+        FtSel<true> sel; sel.mi = mi;
+        __syncthreads();
+        for (int idx = tid; idx < Nz; idx += NT) { const int e = idx % s; zp[idx] = e < m ? M.umid[e] : M.xmid[e - m]; }
+        for (int idx = tid; idx < nbn; idx += NT) { nu[idx] = 0.0; b[idx] = 0.0; yv[idx] = 0.0; }
+        __syncthreads();
+        const FtResid rs = ft_phase_resid<R, NB, NW, false, true>(ft_params(), blockIdx.x, sel);
+        bool bad = rs.bad > 0.0;
+        __syncthreads();
+        if (!bad) {
+            ft_phase_spre<R, NB, NW, false, true>(ft_params(), sel);
+            __syncthreads();
+            for (int q = tid; q < (TS ? 2 : 3) * NQ * FT_TILE; q += NT) sSLOT[q] = (R)0;
+            if (tid == 0) sflag[0] = 0;
+            __syncthreads();
+            bad = ft_phase_factor<R, NB, NW, NL, false, true>(ft_params(), sel);
+            __syncthreads();
+        }
+        if (!bad) {
+            ft_d2* dst = (ft_d2*)((R*)P.pf_fac + (size_t)mi * P.pf_stride);
+            for (size_t q = tid; q < nvec; q += NT) dst[q] = fac[q];
+        }
+        if (tid == 0) P.pf_flag[mi] = bad ? 1 : 0;
+    }
+}
+
 // ---------------------------------------------------------------- host side
+template <bool BK, typename R, int NB, int NW, int NL = -1, bool DR = false>
+static hipError_t ft_launch_pf(const FtParams& P, int grid, size_t lds, hipStream_t stream) {
+    if constexpr (DR) return hipErrorInvalidValue;
+    else {
+        hipLaunchKernelGGL((fmpc_bank_prefactor_k<R, NB, NW, NL>), dim3(grid), dim3(NW * 64), lds, stream, P);
+        return hipGetLastError();
+    }
+}
+template <bool BK, typename R, int NB, int NW, int NL = -1, bool DR = false>
+static hipError_t ft_prepare_pf(size_t lds) {
+    if constexpr (DR) return hipErrorInvalidValue;
+    else return hipFuncSetAttribute((const void*)fmpc_bank_prefactor_k<R, NB, NW, NL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
 template <bool BK, typename R, int NB, int NW, int NL = -1, bool DR = false>
 static hipError_t ft_launch(const FtParams& P, int grid, size_t lds, hipStream_t stream) {
     hipLaunchKernelGGL((fmpc_newton_tiled<R, NB, NW, NL, DR, BK>), dim3(grid), dim3(NW * 64), lds, stream, P);
@@ -1640,6 +1749,14 @@ static hipError_t ft_prepare_any(int bank, int nlast, int NB, int NW, int is_flo
 }
 hipError_t fmpc_tiled_prepare(int n, int NB, int NW, int is_float, size_t lds_bytes, int denseR, int bank) {
     return ft_prepare_any(bank, ft_nlast(n, NB), NB, NW, is_float, lds_bytes, denseR);
+}
+hipError_t fmpc_bank_prefactor_prepare(int n, int NB, int NW, int is_float, size_t lds_bytes) {
+    const int nlast = ft_nlast(n, NB), denseR = 0;
+    FT_DISPATCH(ft_prepare_pf, true, lds_bytes)
+}
+hipError_t fmpc_launch_bank_prefactor(const FtParams& P, int NB, int NW, int is_float, int grid, size_t lds_bytes, hipStream_t stream) {
+    const int nlast = ft_nlast(P.M.n, NB), denseR = 0;
+    FT_DISPATCH(ft_launch_pf, true, P, grid, lds_bytes, stream)
 }
 hipError_t fmpc_launch_tiled(const FtParams& P, int NB, int NW, int is_float, int grid, size_t lds_bytes, hipStream_t stream) {
     const int nlast = ft_nlast(P.M.n, NB);

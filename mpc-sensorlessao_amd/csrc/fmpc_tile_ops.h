@@ -8,6 +8,7 @@
 
 typedef double ft_d4 __attribute__((ext_vector_type(4)));
 typedef float ft_f4 __attribute__((ext_vector_type(4)));
+typedef double ft_d2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ void ft_lds_barrier() {       // orders LDS traffic only; global loads/stores stay in flight
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");

@@ -133,6 +133,12 @@ struct FtParams {
     const int* model_of = nullptr; int bk_count = 0;
     size_t bk_plain = 0, bk_pad = 0;    // doubles between the plain (M.*) / the padded (V.A*P) images of consecutive models
     size_t bk_yimg = 0;                 // REAL elements between their constant Y tiles
+    // Stored cold-start factor per model (fmpc_bank_prefactor_device): the factor stream of Y_j at the mid-box start for this call's kbar,
+    // [stage][record] as ft_phase_factor writes it, model j at pf_fac + j * pf_stride REAL elements; pf_flag[j] != 0: no valid factor
+    // for model j.  A solve is handed them (pf_fac != NULL) only from the cold start: iteration 0 of a problem whose model has a valid
+    // factor then makes no S pre-pass and no P3, it sweeps through the stored records (ft_forward, ft_backward).  The build kernel
+    // (fmpc_bank_prefactor_k) writes both through the same fields.
+    void* pf_fac = nullptr; int* pf_flag = nullptr; size_t pf_stride = 0;
 };
 #define FT_LIST_HANDED (1 << 30)       // (= FW_LIST_HANDED of fmpc_kernel_wave.hip)
 #define FT_LIST_GENERAL (1 << 29)      // (= FW_LIST_GENERAL) continue behind ONE step of the one-wavefront kernel from an explicit start: z in
@@ -143,3 +149,6 @@ bool fmpc_tiled_supports(int n, int m, int nb, int is_float, int* NB_out, int* N
 size_t fmpc_tiled_lds_bytes(int NB, int mb, int NW, int is_float, int nb, size_t pr_doubles = 0);
 hipError_t fmpc_tiled_prepare(int n, int NB, int NW, int is_float, size_t lds_bytes, int denseR = 0, int bank = 0);
 hipError_t fmpc_launch_tiled(const FtParams& P, int NB, int NW, int is_float, int grid, size_t lds_bytes, hipStream_t stream);
+// the build of the stored cold-start factors of a bank (one workgroup per model at a time; P.zout: grid x T (n + m) doubles of scratch)
+hipError_t fmpc_bank_prefactor_prepare(int n, int NB, int NW, int is_float, size_t lds_bytes);
+hipError_t fmpc_launch_bank_prefactor(const FtParams& P, int NB, int NW, int is_float, int grid, size_t lds_bytes, hipStream_t stream);

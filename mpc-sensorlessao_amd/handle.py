@@ -434,6 +434,78 @@ class FastMPCHandle:
         if rc != _lib.FMPC_OK:
             raise FastMPCError(rc, "fmpc_loop_inputs_bank_device")
 
+    def prefactor_model_bank(self, k=1e-2):
+        """fmpc_bank_prefactor_device: factor Y of every model of the bank at the mid-box start for barrier weight k, on torch's
+        current stream, and keep the factors on the device (nb * 3 NB^2 * 256 * sizeof(REAL) bytes per model).  Cold-start bank
+        solves and bank loop steps with exactly this k then sweep through the stored factor in their first Newton step."""
+        import torch
+        stream = C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+        rc = self._lib.fmpc_bank_prefactor_device(self._h, float(k), stream)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_bank_prefactor_device")
+
+    def release_bank_prefactor(self):
+        rc = self._lib.fmpc_bank_prefactor_release(self._h)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_bank_prefactor_release")
+
+    @property
+    def bank_prefactor_count(self):
+        """Models of the bank with a stored cold-start factor (fmpc_bank_prefactor_count; 0 = none).  Synchronises the device."""
+        return int(self._lib.fmpc_bank_prefactor_count(self._h))
+
+    def last_bank_stored_factor(self):
+        """True when the last bank solve was handed the stored factors (fmpc_last_bank_stored_factor)."""
+        return bool(self._lib.fmpc_last_bank_stored_factor(self._h))
+
+    def _bank_loop_checks(self, batch, pairs, model_of, status, iters):
+        import torch
+        for t, shape, name in pairs:
+            if t is not None and not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
+                raise FastMPCError(_lib.FMPC_E_DIM, f"{name}: need a contiguous float64 HIP tensor of {shape}")
+        for t, name in ((model_of, "model_of"), (status, "status"), (iters, "iters")):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (batch,)):
+                raise FastMPCError(_lib.FMPC_E_DIM, f"{name}: need a contiguous int32 HIP tensor of ({batch},)")
+
+    def loop_step_bank(self, a_k, x0_last, u1, u2, x0, x0_pre, w, nu0=None, n_newton=1, k=1e-2, model_of=None,
+                       z_out=None, nu_out=None, status=None, iters=None, step=None, u0_out=None):
+        """fmpc_loop_step_bank_device: `loop_inputs_bank` + `solve_bank_device` from the cold start in one call (same results);
+        problem p uses model model_of[p] of the bank (None: model p).  z_out=None: first moves only (u0_out is required)."""
+        import torch
+        batch = a_k.shape[0]
+        n_newton = 0 if n_newton is None else int(n_newton)
+        self._bank_loop_checks(batch, (
+            (a_k, (batch, self.n), "a_k"), (x0_last, (batch, self.n), "x0_last"), (u1, (batch, self.m), "u1"), (u2, (batch, self.m), "u2"),
+            (x0, (batch, self.n), "x0"), (x0_pre, (batch, self.n), "x0_pre"), (w, (batch, self.T * self.n), "w"),
+            (nu0, (batch, self.nu_len), "nu0"), (z_out, (batch, self.nz), "z_out"), (nu_out, (batch, self.nu_len), "nu_out"),
+            (step, (batch, self._lib.fmpc_step_ld(n_newton)), "step"), (u0_out, (batch, self.m), "u0_out")), model_of, status, iters)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(a_k.device).cuda_stream)
+        rc = self._lib.fmpc_loop_step_bank_device(self._h, batch, p(model_of), p(a_k), p(x0_last), p(u1), p(u2), p(x0), p(x0_pre), p(w),
+                                                  p(nu0), n_newton, float(k), p(z_out), p(nu_out), p(status), p(iters), p(step),
+                                                  p(u0_out), stream)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_loop_step_bank_device")
+
+    def loop_run_bank(self, a, x0, x0_pre, w, U0, X0=None, nu0=None, u_before1=None, u_before2=None, have_x0_last=False,
+                      n_newton=1, k=1e-2, model_of=None, status=None, iters=None):
+        """fmpc_loop_run_bank_device: a.shape[0] consecutive `loop_step_bank` calls in one C call, first moves fed back on the device
+        (u[s] into U0[s], the residual x0 of step s into X0[s]); x0 is updated in place (have_x0_last: it holds the previous step's)."""
+        import torch
+        steps, batch = int(a.shape[0]), int(a.shape[1])
+        self._bank_loop_checks(batch, (
+            (a, (steps, batch, self.n), "a"), (x0, (batch, self.n), "x0"), (x0_pre, (batch, self.n), "x0_pre"),
+            (w, (batch, self.T * self.n), "w"), (U0, (steps, batch, self.m), "U0"), (X0, (steps, batch, self.n), "X0"),
+            (nu0, (steps, batch, self.nu_len), "nu0"), (u_before1, (batch, self.m), "u_before1"),
+            (u_before2, (batch, self.m), "u_before2")), model_of, status, iters)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
+        rc = self._lib.fmpc_loop_run_bank_device(self._h, batch, steps, p(model_of), p(a), p(nu0), p(u_before1), p(u_before2),
+                                                 1 if have_x0_last else 0, 0 if n_newton is None else int(n_newton), float(k),
+                                                 p(x0), p(x0_pre), p(w), p(U0), p(X0), p(status), p(iters), stream)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_loop_run_bank_device")
+
     def loop_step_device(self, a_k, x0_last, u1, u2, x0, x0_pre, w, nu0=None, n_newton=1, k=1e-2,
                          z_out=None, status=None, iters=None, u0_out=None):
         """fmpc_loop_step_device: loop inputs + solve with first-move output in one call (same results as

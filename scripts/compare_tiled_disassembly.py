@@ -6,7 +6,8 @@ Both arguments are objects of csrc/fmpc_kernel_tiled.hip (lib/obj/fmpc_kernel_ti
 tree).  The gfx950 code object is taken out of each, disassembled, and every function of the older one is compared, instruction
 by instruction, with the function of the same name in the newer one; trailing template arguments that the newer tree added with
 the value `false` (the model-bank flag BK, the empty FtSel<false> argument) are dropped from its names first, and instances with
-such an argument `true` are new and skipped.  PC-relative literals (the s_add_u32 / s_addc_u32 pair behind s_getpc_b64 that
+such an argument `true` are new and skipped -- unless the older tree has a function of exactly the same name (both trees have
+the bank instances), which is then the one compared.  PC-relative literals (the s_add_u32 / s_addc_u32 pair behind s_getpc_b64 that
 forms a callee's address) move with the code layout and are masked.  Also compares the kernels' register and scratch totals
 (what -Rpass-analysis=kernel-resource-usage prints) from the code objects' metadata.  Needs /opt/rocm/llvm/bin and c++filt."""
 import collections
@@ -89,6 +90,8 @@ def main():
         nk = new_key(v)
         if nk is not None:
             newer[nk] = k
+    for k, v in dn.items():                                 # both trees spell the name alike (both have the bank instances): that wins
+        newer[key(v)] = k
     same = differ = missing = moved = 0
     for k, v in do.items():
         nk = newer.get(key(v))
