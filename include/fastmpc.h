@@ -436,6 +436,49 @@ int fmpc_loop_run_bank_device(fmpc_handle h, int batch, int steps, const int* mo
                               double* U0, double* X0, int* status, int* iters, void* stream);
 
 /*
+ * Per-model first-move form of the bank's cold-start loop step.  From the cold start the step is an affine map of the data
+ * d = [x0 ; x0_pre ; B u1 ; B u2]: the first move is u0 = u0c + K0 d, and the step-length / exit decision rests on two quadratic
+ * forms of d (fmpc_kernel_first.hip; the shared-model loop has taken this form since fmpc_loop_step_device).  All the reference's loop
+ * applies of a step is u[k] = U(1:nu) (README.md:589).  fmpc_bank_first_move_device builds, on the device on `stream`, the operands of
+ * that form for EVERY model of the bank and barrier weight k: K0t, u0c, the circulant halves of E and Ep, e, ep, the scalars e0, ep0,
+ * rd2_0 and the four norms of the decision's rounding guard, one workgroup per model at a time -- the 4n + 1 right-hand sides of
+ * nu+ = nuc + J d are swept through the model's STORED factor, so fmpc_bank_prefactor_device(h, k, ...) must have been called with
+ * exactly this k; the Gram sums run on the fp64 matrix cores and their rounding bound is folded into the guard norms.
+ * MEMORY: (4n m + m + 2 (2n + 1) 4n + 2 * 4n + n, each rounded up to even, + 8) doubles per model -- 27828 doubles = 222624 bytes at
+ * (n, m) = (27, 144), so 57 MB for 256 models and 456 MB for 2048; besides, the build's scratch of 0.86 MB per
+ * compute unit (about 220 MB on 256 compute units) STAYS allocated after the build, so that the form can be rebuilt under capture,
+ * until fmpc_bank_first_move_release, fmpc_bank_release or fmpc_destroy.  The
+ * operands are the form's own memory: they stay valid after fmpc_bank_prefactor_release.  fmpc_bank_set_device, fmpc_bank_release and
+ * fmpc_set_precision invalidate them (count 0), fmpc_bank_first_move_release frees them (synchronises the device).  Allocation follows
+ * fmpc_bank_prefactor_device: FMPC_E_ALLOC while `stream` is being captured and something has to grow (or k is new: its constants are
+ * uploaded by a blocking copy), and fmpc_alloc_generation moves whenever the operands are allocated or released.
+ * A model without a valid stored factor is marked in a per-model device flag and never uses the form, and so is a model whose
+ * operands come out non-finite; neither is an error of the call.  fmpc_bank_first_move_count is the number of models WITH valid
+ * operands (it synchronises the device: not under capture).
+ * FMPC_E_UNSUPPORTED, before anything is enqueued: no bank; no stored factor at exactly this k; a bank built for the fp32 factor (a
+ * 1e-6 solve would give 1e-6 first moves); a dense R, Q or Qf; ramp-rate rows; a size the first-move kernel does not take (today
+ * n = 27 and 4 m + 16 n <= 1024, that is m <= 148); B diag(a^2) B' not positive definite.
+ *
+ * fmpc_loop_step_bank_device, and through it fmpc_loop_run_bank_device, take the form when the call asks for first moves only
+ * (z_out == NULL and nu_out == NULL), n_newton == 1 and k equals the built k bit for bit.  x0, x0_pre and w are written by the
+ * bank's loop-input kernel as always; a realisation whose decision is clear-cut gets u0 = u0c + K0 d, status FMPC_OK, iters 1 and the
+ * step record t = 1.  A realisation that is not clear-cut, or whose model is marked, is redone from the cold start by the bank's
+ * exact path in the same call (a device-side list; nothing is read back) and gets the results it gets today; a model index out of
+ * range gives FMPC_E_DIM and nothing else, as today.  Every other call, and every call on a handle that never built the form, is
+ * bitwise what it was.  FMPC_NO_BANK_FIRST_MOVE=1 in the environment at fmpc_create keeps the form off.
+ * fmpc_last_bank_first_move: 1 when the last bank loop step took the form; fmpc_last_dispatch then reports in handed_over how many
+ * realisations went to the exact path.
+ * WHEN TO USE IT: for stretches of the loop.  Measured on one MI355X at (27, 144, 30), one model per realisation (DESIGN.md section 6,
+ * scripts/bank_first_move_timing.py): a step in the form takes 0.075 ms at 256 realisations and 0.313 ms at 2048, against 0.296 and
+ * 1.244 ms of the stored-factor step (3.9 x at both sizes; 0.76 and 1.46 TB/s against the operand count above), so the form is taken
+ * at every batch size.  The build costs 18.3 ms for 256 models and 145 ms for 2048: it is repaid after 83 and 156 steps.
+ */
+int fmpc_bank_first_move_device(fmpc_handle h, double k, void* stream);
+int fmpc_bank_first_move_count(fmpc_handle h);     /* models with valid operands; 0 = none (also for a NULL handle) */
+int fmpc_bank_first_move_release(fmpc_handle h);
+int fmpc_last_bank_first_move(fmpc_handle h);      /* 1: the last bank loop step took the first-move form */
+
+/*
  * Arithmetic of the per-problem-factor path (no counterpart in the reference, which is fp64 throughout).
  *   FMPC_PREC_F64        everything in fp64: the default wherever an fp64 kernel on the matrix cores exists (n <= 79; round 5 --
  *                        the reference is fp64 throughout and the literal call fmpc_solve_once has no precision argument) and

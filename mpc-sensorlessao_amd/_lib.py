@@ -85,6 +85,10 @@ SIGNATURES = {
     "fmpc_bank_prefactor_count": (C.c_int, [_vp]),
     "fmpc_bank_prefactor_release": (C.c_int, [_vp]),
     "fmpc_last_bank_stored_factor": (C.c_int, [_vp]),
+    "fmpc_bank_first_move_device": (C.c_int, [_vp, C.c_double, _vp]),
+    "fmpc_bank_first_move_count": (C.c_int, [_vp]),
+    "fmpc_bank_first_move_release": (C.c_int, [_vp]),
+    "fmpc_last_bank_first_move": (C.c_int, [_vp]),
     "fmpc_loop_step_bank_device": (C.c_int, [_vp, C.c_int, _vp] + [_vp] * 8 + [C.c_int, C.c_double] + [_vp] * 6 + [_vp]),
     "fmpc_loop_run_bank_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp] + [_vp] * 4 + [C.c_int, C.c_int, C.c_double] + [_vp] * 7 + [_vp]),
     "fmpc_phase_residual_device": (C.c_int, [_vp, C.c_int, C.c_longlong] + [_vp] * 4 + [_vp]),

@@ -152,6 +152,14 @@ struct fmpc_handle_s {
         DevBuf<char> fac; DevBuf<int> flag;
     } bkf;
     int bank_last_stored = 0;             // the last bank solve was handed the stored factors (fmpc_last_bank_stored_factor)
+    // per-model first-move form of the bank (fmpc_bank_first_move_device): count * stride doubles of operands, its own memory
+    struct BankFirst {
+        int valid = 0, count = 0, disabled = 0, prepared = 0;
+        double k = 0.0, cst_k = 0.0; int cst_valid = 0; size_t stride = 0, oK = 0, ou = 0, oE = 0, oe = 0, oEp = 0, oep = 0, od = 0, osc = 0;
+        DevBuf<double> ops, scratch, cst; DevBuf<int> flag, need, list, cnt;
+    } bfm;
+    int bank_last_first = 0;              // the last bank loop step took the form (fmpc_last_bank_first_move)
+    int bank_first_dispatch = 0;          // the last TILED dispatch was that form's: fmpc_last_dispatch reports its hand-over count
     DevBuf<double> tl_ws; int tl_prepared = 0;                   // (bit NW: that wavefront count of the fp64 instance is prepared)
     int tl_last_nw = 0;                   // wavefronts per problem of the last tiled launch (diagnostic)
     int z_ld = 0;                         // fmpc_set_z_ld: doubles between the z rows of consecutive problems (0: T (n + m))
@@ -367,6 +375,7 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
     { const char* na = getenv("FMPC_NO_LOOP_FUSE"); h->fs_disabled = (na && na[0] == '1') ? 1 : 0; }
     { const char* na = getenv("FMPC_PRODUCT_MIN_BATCH"); h->fs_min_batch = (na && atoi(na) >= 1) ? atoi(na) : FMPC_PRODUCT_MIN_BATCH_DEFAULT; }
     { const char* nf = getenv("FMPC_NO_FIRST_MOVE"); h->fm_disabled = (nf && nf[0] == '1') ? 1 : 0; }
+    { const char* nf = getenv("FMPC_NO_BANK_FIRST_MOVE"); h->bfm.disabled = (nf && nf[0] == '1') ? 1 : 0; }
     { const char* gs = getenv("FMPC_NO_GENERAL_SPLIT"); h->gn_split = (gs && gs[0] == '1') ? 0 : 1; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) { delete h; return FMPC_E_HIP; }
@@ -829,7 +838,7 @@ static int fmpc_solve_tiled(fmpc_handle h, int t, const FmpcSolve& s, int nw_ove
     P.refine = t ? h->refine : 0;                                     // (the fp64 instances have no such phase)
     h->tl_last_nw = plan.NWu;
     if (t) h->refine_last = P.refine;
-    if (!list) h->last_path = t ? FMPC_PATH_TILED_F32 : FMPC_PATH_TILED;
+    if (!list) { h->last_path = t ? FMPC_PATH_TILED_F32 : FMPC_PATH_TILED; h->bank_first_dispatch = 0; }
     return fmpc_launch_tiled(P, X.NB, plan.NWu, t, plan.grid, plan.ldsu, s.stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
@@ -848,6 +857,7 @@ extern "C" int fmpc_set_precision(fmpc_handle h, int mode) {
     }
     h->prec = mode;
     h->bkf.valid = 0;                                                  // (the stored factors of a bank belong to the arithmetic they were built in)
+    h->bfm.valid = 0;                                                  // (and so does the first-move form built from them)
     return FMPC_OK;
 }
 
@@ -1549,6 +1559,7 @@ extern "C" int fmpc_bank_set_device(fmpc_handle h, int count, const double* A1, 
         return FMPC_E_ALLOC;                                           // (the bank that is there stays as it is)
     B.count = 0;                                                       // (no bank while it is being replaced)
     h->bkf.valid = 0;                                                  // (and no stored factors of the models that leave)
+    h->bfm.valid = 0;                                                  // (nor their first-move form)
     int rc = fmpc_guard_begin(h, stream);                             // (an earlier bank solve may still read the old images)
     if (rc != FMPC_OK) return rc;
     rc = B.plain.grow(plain_stride * (size_t)count, stream);
@@ -1582,6 +1593,7 @@ extern "C" int fmpc_bank_release(fmpc_handle h) {
     B.plain.release(); B.pad.release(); B.yimg.release();
     B.count = 0;
     h->bkf.valid = 0; h->bkf.fac.release(); h->bkf.flag.release();
+    h->bfm.valid = 0; h->bfm.count = 0; h->bfm.ops.release(); h->bfm.scratch.release(); h->bfm.flag.release();
     return FMPC_OK;
 }
 
@@ -1624,7 +1636,8 @@ static int fmpc_bank_solve_plan(fmpc_handle h, FmpcSolve& s, FmpcTiledPlan* plan
     }
     return fmpc_tiled_plan(h, t, s.batch, s.stream, 0, 0, plan);
 }
-static int fmpc_bank_solve_launch(fmpc_handle h, const FmpcSolve& s, const int* model_of, const FmpcTiledPlan& plan) {
+static int fmpc_bank_solve_launch(fmpc_handle h, const FmpcSolve& s, const int* model_of, const FmpcTiledPlan& plan,
+                                  const int* list = nullptr, const int* nlist = nullptr) {
     const int t = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
     fmpc_handle_s::Tiled& X = h->tl[t];
     const fmpc_handle_s::BankFactor& F = h->bkf;
@@ -1637,6 +1650,7 @@ static int fmpc_bank_solve_launch(fmpc_handle h, const FmpcSolve& s, const int* 
     P.ws = h->tl_ws; P.ws_stride = plan.slot; P.u0out = s.u0_out;
     P.refine = t ? h->refine : 0;
     P.model_of = model_of;
+    P.list = list; P.nlist = nlist;                                    // (the first-move form's hand-over: FT_LIST_HANDED entries)
     // the stored cold-start factors: from the cold start only, and only for the k they were built for, bit for bit
     const bool stored = F.valid && F.t == t && F.count == h->bank.count && !h->denseR && !s.z_init && memcmp(&s.k, &F.k, sizeof(double)) == 0;
     if (stored) { P.pf_fac = F.fac.p; P.pf_flag = F.flag; P.pf_stride = F.stride; }
@@ -1644,6 +1658,7 @@ static int fmpc_bank_solve_launch(fmpc_handle h, const FmpcSolve& s, const int* 
     h->tl_last_nw = plan.NWu;
     if (t) h->refine_last = P.refine;
     h->last_path = t ? FMPC_PATH_TILED_F32 : FMPC_PATH_TILED;
+    h->bank_first_dispatch = list ? 1 : 0;                             // (a list here is the first-move form's hand-over)
     return fmpc_launch_tiled(P, X.NB, plan.NWu, t, plan.grid, plan.ldsu, s.stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
@@ -1742,6 +1757,161 @@ extern "C" int fmpc_last_bank_stored_factor(fmpc_handle h) {
     return h->bank_last_stored;
 }
 
+// ---- per-model first-move form of the bank's cold-start loop step (include/fastmpc.h; fmpc_bank_first_build_k, fmpc_first_move_bank)
+extern "C" int fmpc_bank_first_move_device(fmpc_handle h, double k, void* stream_) {
+    if (!h) return FMPC_E_NULL;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    std::lock_guard<std::mutex> lk(h->mu);
+    fmpc_handle_s::Bank& B = h->bank;
+    const fmpc_handle_s::BankFactor& PF = h->bkf;
+    fmpc_handle_s::BankFirst& F = h->bfm;
+    const int n = h->n, m = h->m, T = h->T, nb = h->nb, nc = 4 * n, Hc = nc / 2 + 1;
+    if (B.count <= 0 || B.t != 0 || h->prec != FMPC_PREC_F64 || h->denseR || h->denseQ || fmpc_bank_unsupported(h, 0) || !h->tl[0].ready)
+        return FMPC_E_UNSUPPORTED;
+    if (!PF.valid || PF.t != 0 || PF.count != B.count || memcmp(&k, &PF.k, sizeof(double)) != 0) return FMPC_E_UNSUPPORTED;
+    // the application kernel's sizes (fmpc_launch_first_move_bank), and the depth the builder's rounding bound is written for
+    // (4 m + 16 n <= 1024 are the slots of the kernel's partial sums: m <= 148 at n = 27)
+    if (n != 27 || m > 160 || 4 * m + 16 * n > 1024 || nb * n + 2 * n + 8 > 4096) return FMPC_E_UNSUPPORTED;
+    fmpc_handle_s::Tiled& X = h->tl[0];
+    auto even = [](size_t v) { return (v + 1) & ~(size_t)1; };
+    size_t o = 0;
+    const size_t oK = o; o += even((size_t)nc * m);
+    const size_t ou = o; o += even(m);
+    const size_t oE = o; o += even((size_t)Hc * nc);
+    const size_t oe = o; o += even(nc);
+    const size_t oEp = o; o += even((size_t)Hc * nc);
+    const size_t oep = o; o += even(nc);
+    const size_t od = o; o += even(n);
+    const size_t osc = o; o += 8;
+    const size_t stride = o;                                           // 27828 doubles = 222624 bytes per model at (27, 144)
+    FmpcTiledPlan plan;
+    const bool capturing = fmpc_capturing(stream);
+    size_t s_ld = 0; int ncp = 0;
+    const size_t sdoubles = fmpc_bank_first_scratch_doubles(n, nb, &s_ld, &ncp);
+    int grid = B.count < h->num_cu ? B.count : h->num_cu;              // (a workgroup's scratch is 0.86 MB: one per CU)
+    if (capturing && (stride * (size_t)B.count > F.ops.cap || (size_t)B.count > F.flag.cap || sdoubles * (size_t)grid > F.scratch.cap ||
+                      !F.cst_valid || memcmp(&k, &F.cst_k, sizeof(double)) != 0 || !F.cnt.p || !F.prepared)) return FMPC_E_ALLOC;
+    // the model-independent constants, in long double: L L' = B diag(a^2) B', L y0 = B (a^2 o cu)   (fmpc_host_build_first_move: Ma2, bg)
+    typedef long double ld;
+    const int NX = 32;
+    std::vector<double> cst((size_t)NX * NX + NX + 8, 0.0);
+    {
+        std::vector<ld> a2(m), cu(m), Ma((size_t)n * n, 0.0L), v0(n, 0.0L), Lm((size_t)n * n, 0.0L), y0(n, 0.0L);
+        ld acu2 = 0.0L;
+        for (int j = 0; j < m; ++j) {
+            const double sp = h->hm_umax[j] - h->hm_umid[j], sm = h->hm_umid[j] - h->hm_umin[j];
+            const double dp = 1.0 / sp, dm = 1.0 / sm;
+            const double hc = k * (dp * dp + dm * dm);
+            cu[j] = (ld)(h->hm_R2[j] * h->hm_umid[j] + h->hm_rl[j] + k * (dp - dm));
+            const double av = hc * (1.0 / (h->hm_R2[j] + hc));
+            a2[j] = (ld)av * (ld)av;
+            acu2 += a2[j] * cu[j] * cu[j];
+        }
+        const double* bt = h->hm_bt.data();
+        for (int r = 0; r < n; ++r) {
+            for (int q = 0; q < n; ++q) { ld t = 0.0L; for (int j = 0; j < m; ++j) t += (ld)bt[(size_t)j * n + r] * a2[j] * (ld)bt[(size_t)j * n + q]; Ma[(size_t)r * n + q] = t; }
+            for (int j = 0; j < m; ++j) v0[r] += (ld)bt[(size_t)j * n + r] * a2[j] * cu[j];
+        }
+        for (int j = 0; j < n; ++j) {                                  // Cholesky; not positive definite: no form for this handle
+            ld d = Ma[(size_t)j * n + j];
+            for (int q = 0; q < j; ++q) d -= Lm[(size_t)j * n + q] * Lm[(size_t)j * n + q];
+            if (!(d > 0.0L) || !std::isfinite((double)d)) return FMPC_E_UNSUPPORTED;
+            const ld dj = sqrtl(d);
+            Lm[(size_t)j * n + j] = dj;
+            for (int i = j + 1; i < n; ++i) {
+                ld t = Ma[(size_t)i * n + j];
+                for (int q = 0; q < j; ++q) t -= Lm[(size_t)i * n + q] * Lm[(size_t)j * n + q];
+                Lm[(size_t)i * n + j] = t / dj;
+            }
+        }
+        ld y2 = 0.0L, lf2 = 0.0L;
+        for (int i = 0; i < n; ++i) {
+            ld t = v0[i];
+            for (int q = 0; q < i; ++q) t -= Lm[(size_t)i * n + q] * y0[q];
+            y0[i] = t / Lm[(size_t)i * n + i];
+            y2 += y0[i] * y0[i];
+        }
+        for (int i = 0; i < n; ++i)
+            for (int q = 0; q <= i; ++q) { cst[(size_t)q * NX + i] = (double)Lm[(size_t)i * n + q]; lf2 += Lm[(size_t)i * n + q] * Lm[(size_t)i * n + q]; }
+        for (int i = 0; i < n; ++i) cst[(size_t)NX * NX + i] = (double)y0[i];
+        const ld c0 = (ld)T * (acu2 - y2);
+        cst[(size_t)NX * NX + NX] = (double)(c0 > 0.0L ? c0 : 0.0L);
+        cst[(size_t)NX * NX + NX + 1] = (double)lf2 * (1.0 + 1e-12);
+        cst[(size_t)NX * NX + NX + 2] = (double)((ld)T * y2) * (1.0 + 1e-12);
+    }
+    F.valid = 0;                                                       // (no form while it is being rebuilt)
+    int rc = fmpc_guard_begin(h, stream);                             // (an earlier loop step may still read the old operands)
+    if (rc != FMPC_OK) return rc;
+    rc = fmpc_tiled_plan(h, 0, grid, stream, 0, 0, &plan);
+    if (rc == FMPC_OK && plan.grid < grid) grid = plan.grid;
+    if (rc == FMPC_OK) rc = fmpc_scratch_z(h, grid, stream);
+    if (rc == FMPC_OK) rc = F.ops.grow(stride * (size_t)B.count, stream);
+    if (rc == FMPC_OK) rc = F.flag.grow((size_t)B.count, stream);
+    if (rc == FMPC_OK) rc = F.scratch.grow(sdoubles * (size_t)grid, stream);
+    if (rc == FMPC_OK) rc = F.cst.grow(cst.size(), stream);
+    if (rc == FMPC_OK && !F.cnt.p) { rc = F.cnt.alloc(2, stream); if (rc == FMPC_OK) (void)hipMemset(F.cnt, 0, 2 * sizeof(int)); }
+    if (rc == FMPC_OK && !F.prepared) {
+        if (fmpc_bank_first_build_prepare(X.NB, plan.NWu, plan.ldsu) == hipSuccess) F.prepared = 1;
+        else rc = FMPC_E_UNSUPPORTED;                                  // (a wavefront count the builder has no instance for)
+    }
+    // (under capture the constants of this k are on the device already: checked above; otherwise a blocking copy)
+    if (rc == FMPC_OK && !capturing) {
+        F.cst_valid = 0;
+        if (hipMemcpy(F.cst, cst.data(), cst.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = FMPC_E_HIP;
+        else { F.cst_valid = 1; F.cst_k = k; }
+    }
+    if (rc == FMPC_OK) {
+        FtParams P;
+        fmpc_bank_params(h, 0, P);
+        P.batch = B.count;
+        P.x0 = nullptr; P.x0p = nullptr; P.w = nullptr; P.zinit = nullptr; P.nu0 = nullptr;
+        P.max_iter = 1; P.kbar = k;
+        P.zout = h->zs; P.nuout = nullptr; P.status = nullptr; P.iters = nullptr; P.step = nullptr; P.step_ld = 0;
+        P.ws = h->tl_ws; P.ws_stride = plan.slot; P.u0out = nullptr;
+        P.refine = 0; P.model_of = nullptr;
+        P.pf_fac = PF.fac.p; P.pf_flag = PF.flag; P.pf_stride = PF.stride;
+        FbfParams Q;
+        Q.S = F.scratch; Q.s_ld = s_ld; Q.s_stride = sdoubles; Q.ncp = ncp;
+        Q.out = F.ops; Q.out_stride = stride; Q.oK = oK; Q.ou = ou; Q.oE = oE; Q.oe = oe; Q.oEp = oEp; Q.oep = oep; Q.od = od; Q.osc = osc;
+        Q.flag = F.flag; Q.cst = F.cst;
+        if (fmpc_launch_bank_first_build(P, Q, X.NB, plan.NWu, grid, plan.ldsu, stream) != hipSuccess) rc = FMPC_E_HIP;
+    }
+    fmpc_guard_end(h, stream);
+    if (rc != FMPC_OK) return rc;
+    F.valid = 1; F.count = B.count; F.k = k; F.stride = stride;
+    F.oK = oK; F.ou = ou; F.oE = oE; F.oe = oe; F.oEp = oEp; F.oep = oep; F.od = od; F.osc = osc;
+    return FMPC_OK;
+}
+extern "C" int fmpc_bank_first_move_count(fmpc_handle h) {
+    if (!h) return 0;
+    if (hipSetDevice(h->device) != hipSuccess) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const fmpc_handle_s::BankFirst& F = h->bfm;
+    if (!F.valid || F.count <= 0) return 0;
+    std::vector<int> fl((size_t)F.count);
+    if (hipDeviceSynchronize() != hipSuccess) return 0;               // (the build may still be running, on any stream)
+    if (hipMemcpy(fl.data(), F.flag, fl.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    int good = 0;
+    for (int f : fl) good += f == 0 ? 1 : 0;
+    return good;
+}
+extern "C" int fmpc_bank_first_move_release(fmpc_handle h) {
+    if (!h) return FMPC_E_NULL;
+    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    std::lock_guard<std::mutex> lk(h->mu);
+    fmpc_handle_s::BankFirst& F = h->bfm;
+    if (F.ops.p || F.scratch.p || F.flag.p) (void)hipDeviceSynchronize();   // (a loop step in flight reads them)
+    F.valid = 0; F.count = 0;
+    F.ops.release(); F.scratch.release(); F.flag.release();            // (need, list, cnt, cst: a few bytes per realisation, kept until fmpc_destroy)
+    return FMPC_OK;
+}
+extern "C" int fmpc_last_bank_first_move(fmpc_handle h) {
+    if (!h) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return h->bank_last_first;
+}
+
 // caller holds h->mu and has checked that a bank exists
 static int fmpc_loop_inputs_bank_launch(fmpc_handle h, int batch, const int* model_of, const double* a_k, const double* x0_last,
                                         const double* u1, const double* u2, double* x0, double* x0_pre, double* w, hipStream_t stream) {
@@ -1787,8 +1957,31 @@ extern "C" int fmpc_loop_step_bank_device(fmpc_handle h, int batch, const int* m
     if (rc != FMPC_OK) return rc;
     FmpcTiledPlan plan;
     rc = fmpc_bank_solve_plan(h, s, &plan);
+    // the per-model first-move form: first moves only, one Newton step, the k it was built for bit for bit -- and its per-batch
+    // buffers exist (under capture nothing grows: the call is then the exact path's)
+    fmpc_handle_s::BankFirst& F = h->bfm;
+    bool form = rc == FMPC_OK && F.valid && !F.disabled && F.count == h->bank.count && h->prec == FMPC_PREC_F64 && !z_out && !nu_out &&
+                n_newton == 1 && memcmp(&k, &F.k, sizeof(double)) == 0;
+    if (form && (F.need.grow((size_t)batch, stream) != FMPC_OK || F.list.grow((size_t)batch, stream) != FMPC_OK)) form = false;
+    h->bank_last_first = form ? 1 : 0;
     if (rc == FMPC_OK) rc = fmpc_loop_inputs_bank_launch(h, batch, model_of, a_k, x0_last, u1, u2, x0, x0_pre, w, stream);
-    if (rc == FMPC_OK) rc = fmpc_bank_solve_launch(h, s, model_of, plan);
+    if (rc == FMPC_OK && form) {
+        FmParams P;
+        memset(&P, 0, sizeof(P));
+        P.n = h->n; P.m = h->m; P.T = h->T; P.nb = h->nb; P.var2 = h->var_order == 2 ? 1 : 0; P.has_xf = h->has_xf;
+        P.step_ld = fmpc_step_ld(n_newton); P.x0_given = 1;
+        P.a_k = x0; P.x0_last = x0_pre; P.u1 = u1; P.u2 = u2; P.nu0 = nu0;
+        P.x0 = x0; P.x0_pre = x0_pre; P.w = w; P.u0out = u0_out; P.status = status; P.iters = iters; P.step = step;
+        P.need = F.need; P.handed = nullptr; P.bt = h->dev.Bt;
+        P.K0t = F.ops + F.oK; P.u0c = F.ops + F.ou; P.E = F.ops + F.oE; P.e = F.ops + F.oe; P.Ep = F.ops + F.oEp; P.ep = F.ops + F.oep;
+        P.dx0T = F.ops + F.od; P.bk_sc = F.ops + F.osc;
+        P.model_of = model_of; P.bk_count = F.count; P.bk_stride = F.stride; P.bk_flag = F.flag;
+        if (fmpc_launch_first_move_bank(P, batch, stream) != hipSuccess ||
+            fmpc_launch_need_compact(F.need, batch, FT_LIST_HANDED, F.list, F.cnt, stream) != hipSuccess) rc = FMPC_E_HIP;
+        if (rc == FMPC_OK) rc = fmpc_bank_solve_launch(h, s, model_of, plan, F.list, F.cnt + 1);
+    } else if (rc == FMPC_OK) {
+        rc = fmpc_bank_solve_launch(h, s, model_of, plan);
+    }
     fmpc_guard_end(h, stream);
     return rc;
 }
@@ -2221,6 +2414,10 @@ extern "C" int fmpc_last_dispatch(fmpc_handle h, int* path, int* handed_over) {
         if (h->last_path == FMPC_PATH_PANEL) {
             if (hipDeviceSynchronize() != hipSuccess) return FMPC_E_HIP;
             if (hipMemcpy(handed_over, h->pn_cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return FMPC_E_HIP;
+        }
+        if (h->last_path == FMPC_PATH_TILED && h->bank_first_dispatch && h->bfm.cnt.p) {      // the bank's first-move form: what its exact path redid
+            if (hipDeviceSynchronize() != hipSuccess) return FMPC_E_HIP;
+            if (hipMemcpy(handed_over, h->bfm.cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return FMPC_E_HIP;
         }
     }
     return FMPC_OK;

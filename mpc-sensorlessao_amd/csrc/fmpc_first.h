@@ -19,6 +19,9 @@ struct FmParams {
     const double* m12t;                 // [2n][T n]: columns of M1, then of M2 (closed-loop prediction matrices)
     const double* dx0T;                 // 2 Qf xbar + qf (n): x entries of r_d at the last stage without nu
     double e0, ep0, normE, norme, normEp, normep, rd2_0;
+    // per-model form of a model bank (fmpc_first_move_bank; behind everything else): K0t .. ep, dx0T are the operands of model 0,
+    // those of model j at + j * bk_stride doubles, its scalars [e0, ep0, normE, norme, normEp, normep, rd2_0, 0] at bk_sc + j * bk_stride
+    const int* model_of; int bk_count; size_t bk_stride; const int* bk_flag; const double* bk_sc;
 };
 
 // A stretch of the loop in ONE launch (fmpc_first_move_run): per realisation the steps start[p] .. steps-1, until one is not
@@ -48,4 +51,7 @@ hipError_t fmpc_launch_walk_gather(const FmCompact& C, hipStream_t stream);
 hipError_t fmpc_launch_walk_scatter(const FmCompact& C, hipStream_t stream);
 
 hipError_t fmpc_launch_first_move(const FmParams& P, int batch, hipStream_t stream);
+hipError_t fmpc_launch_first_move_bank(const FmParams& P, int batch, hipStream_t stream);
+// need[0 .. batch) -> list of the flagged realisations (entry = p | tag), cnt[0] = cnt[1] = its length
+hipError_t fmpc_launch_need_compact(const int* need, int batch, int tag, int* list, int* cnt, hipStream_t stream);
 hipError_t fmpc_launch_first_move_run(const FmParams& P, const FmRun& R, hipStream_t stream);

@@ -119,16 +119,37 @@ __device__ __forceinline__ bool fm_decide(const FmParams& P, double qe, double q
     return fin && (rp2 > 4e-16 || rho2 > 4e-12) && e2 <= 0.5 * rho2;
 }
 
-__global__ void __launch_bounds__(FM_THREADS) fmpc_first_move(FmParams P) {
+// BK: the per-model form of a model bank (fmpc_bank_first_move_device): realisation p reads the operands of model model_of[p] (NULL:
+// model p) at + model * bk_stride and the scalars of the decision from the model's block; x0, x0_pre and w are the bank's
+// loop-input kernel's (x0_given, no w workgroups).  A realisation without a model gets FMPC_E_DIM and nothing else, one whose
+// model is marked goes to the exact path unseen.
+template <bool BK>
+__device__ __forceinline__ void fm_body(const FmParams& P0) {
     __shared__ double sd[2 * FM_NC_MAX + 4];        // d = [x0 ; x0_pre ; B u1 ; B u2], twice in a row (fm_row_fma)
     __shared__ double su[2][160];                   // u1, u2
     __shared__ double sx[2][32];                    // a_k, x0_last
     __shared__ double sred[16];
     __shared__ double spart[FM_THREADS];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int n = P.n, m = P.m, nc = 4 * n, T = P.T, TN = T * n;
     const int p = blockIdx.x;                        // realisation
     const int role = blockIdx.y;                     // 0: first move + decision + x0, x0_pre ; >= 1: rows of w
+    [[maybe_unused]] FmParams Pm;
+    if constexpr (BK) {
+        if (p == 0 && tid == 0 && P0.handed) *P0.handed = 0;
+        const int mi = P0.model_of ? P0.model_of[p] : p;
+        if ((unsigned)mi >= (unsigned)P0.bk_count) {
+            if (tid == 0) { P0.need[p] = 0; if (P0.status) P0.status[p] = FMPC_E_DIM; if (P0.iters) P0.iters[p] = 0; }
+            return;
+        }
+        if (P0.bk_flag[mi] != 0) { if (tid == 0) P0.need[p] = 1; return; }
+        Pm = P0;
+        const size_t mo = (size_t)mi * P0.bk_stride;
+        Pm.K0t += mo; Pm.u0c += mo; Pm.E += mo; Pm.e += mo; Pm.Ep += mo; Pm.ep += mo; Pm.dx0T += mo;
+        const double* sc = P0.bk_sc + mo;
+        Pm.e0 = sc[0]; Pm.ep0 = sc[1]; Pm.normE = sc[2]; Pm.norme = sc[3]; Pm.normEp = sc[4]; Pm.normep = sc[5]; Pm.rd2_0 = sc[6];
+    }
+    const FmParams& P = BK ? Pm : P0;
+    const int n = P.n, m = P.m, nc = 4 * n, T = P.T, TN = T * n;
     // ---- EVERY global load of this thread is requested here, before the first barrier: the kernel is a chain of
     // dependent steps through LDS, and each memory round trip in that chain would cost more than all its arithmetic
     // (12.9 us with the loads where they are used, measured).  Inputs; the B entries of the v = B u products; this
@@ -232,6 +253,8 @@ __global__ void __launch_bounds__(FM_THREADS) fmpc_first_move(FmParams P) {
     }
     FM_TICK(5);
 }
+__global__ void __launch_bounds__(FM_THREADS) fmpc_first_move(FmParams P) { fm_body<false>(P); }
+__global__ void __launch_bounds__(FM_THREADS) fmpc_first_move_bank(FmParams P) { fm_body<true>(P); }
 
 // ------------------------------------------------------------------------------------------------------------------------
 // A recorded stretch of the loop in ONE launch (fmpc_loop_run_device): the workgroup of a realisation keeps its rows of K0, Ec,
@@ -434,5 +457,38 @@ hipError_t fmpc_launch_first_move(const FmParams& P, int batch, hipStream_t stre
     if (P.n != 27 || 4 * P.n > FM_NC_MAX || P.m > 160 || 4 * P.m + 16 * P.n > FM_THREADS) return hipErrorInvalidValue;
     const int wg_w = (P.T * P.n + FM_WROWS - 1) / FM_WROWS;
     hipLaunchKernelGGL(fmpc_first_move, dim3(batch, 1 + wg_w), dim3(FM_THREADS), 0, stream, P);
+    return hipGetLastError();
+}
+
+// the per-model form: role 0 only (w, x0, x0_pre come from fmpc_loop_inputs_bank in front of it)
+hipError_t fmpc_launch_first_move_bank(const FmParams& P, int batch, hipStream_t stream) {
+    if (P.n != 27 || 4 * P.n > FM_NC_MAX || P.m > 160 || 4 * P.m + 16 * P.n > FM_THREADS || !P.x0_given || !P.bk_flag || !P.bk_sc) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fmpc_first_move_bank, dim3(batch, 1), dim3(FM_THREADS), 0, stream, P);
+    return hipGetLastError();
+}
+
+// need[0 .. batch) -> the list of the realisations the exact path redoes from the cold start (entry = p | FT_LIST_HANDED of
+// fmpc_tiled.h), in order; cnt[0] = cnt[1] = its length.  One workgroup: every thread a contiguous stretch, one scan over the threads.
+#define FMC_THREADS 1024
+__global__ void __launch_bounds__(FMC_THREADS) fmpc_need_compact(const int* __restrict__ need, int batch, int tag, int* __restrict__ list, int* __restrict__ cnt) {
+    __shared__ int sc[FMC_THREADS];
+    const int tid = threadIdx.x, per = (batch + FMC_THREADS - 1) / FMC_THREADS;
+    const int p0 = tid * per, p1 = p0 + per < batch ? p0 + per : batch;
+    int mine = 0;
+    for (int p = p0; p < p1; ++p) mine += need[p] != 0 ? 1 : 0;
+    sc[tid] = mine;
+    __syncthreads();
+    for (int o = 1; o < FMC_THREADS; o <<= 1) {
+        const int v = tid >= o ? sc[tid - o] : 0;
+        __syncthreads();
+        sc[tid] += v;
+        __syncthreads();
+    }
+    int at = sc[tid] - mine;
+    for (int p = p0; p < p1; ++p) if (need[p] != 0) list[at++] = p | tag;
+    if (tid == FMC_THREADS - 1) { cnt[0] = sc[tid]; cnt[1] = sc[tid]; }
+}
+hipError_t fmpc_launch_need_compact(const int* need, int batch, int tag, int* list, int* cnt, hipStream_t stream) {
+    hipLaunchKernelGGL(fmpc_need_compact, dim3(1), dim3(FMC_THREADS), 0, stream, need, batch, tag, list, cnt);
     return hipGetLastError();
 }

@@ -1642,6 +1642,233 @@ __global__ void __launch_bounds__(NW * 64, 2) fmpc_bank_prefactor_k(FtParams P) 
     }
 }
 
+// The operands of the per-model first-move form of a bank (fmpc_bank_first_move_device; FbfParams in fmpc_tiled.h): ONE WORKGROUP PER
+// MODEL at a time.  From the cold start nu+ = nuc + J d with d = [x0 ; x0_pre ; B u1 ; B u2] (fmpc_kernel_first.hip), and with
+// b = Pb d + bc (fast_mpc_eq_const.m:39-47; the columns of B u1, B u2 are the model's free response, fmpc_loop_inputs_bank)
+//     J = -Y^-1 Pb ,   nuc = Y^-1 (r_p - C Phi^-1 r_d) at d = 0
+// are 4n + 1 solves with the model's STORED factor: ft_forward / ft_backward, a column at a time, in place in the scratch S that
+// first holds [Pb | cp].  fmpc_host_build_first_move is the specification of what is formed from them.  Both Gram sums run on the
+// fp64 matrix cores as ONE kind of product, S^' S^ over the rows of all stages:
+//     [Ep ep ; ep' ep0] = S^'S^ ,  S^ = [Pb | cp]
+//     [E e ; e' q]      = G^'G^ ,  G^_s = L' [J_s | nuc_s] - [0 | y0] ,  L L' = B diag(a^2) B' ,  L y0 = B (a^2 o cu)   (host, long double)
+// (e0 = q + T (|a o cu|^2 - |y0|^2)).  A Gram sum of K terms in fp64 is off by at most gamma_K sqrt(G_ii G_jj) per entry, so by
+// gamma_K trace(G) in the Frobenius norm, and the rounding of the transform L' J adds gamma_n |L|_F^2 |[J nuc]|_F^2 + T |y0|^2 at most:
+// with K + 2n + 8 <= 4096 both are covered by adding beta = trace + that mass to the norms the decision's rounding guard multiplies
+// by 4096 eps (fm_decide), and 4096 eps beta to e0 (from ep0: subtracted).  DESIGN.md 3.
+template <int NB, int NW>
+__global__ void __launch_bounds__(NW * 64, 2) fmpc_bank_first_build_k(FtParams P, FbfParams Q) {
+    typedef double R;
+    constexpr int NT = NW * 64, NP = 16 * NB, LDN = 16 * NB + 1, NX = 16 * NB;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const FmpcDevModel& M = P.M;
+    const FtModel& V = P.V;
+    const int n = M.n, m = M.m, T = M.T, nb = M.nb;
+    const int s = n + m, Nz = T * s, nbn = nb * n, nc = 4 * n, H = nc / 2 + 1;
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 15, g = lane >> 4;
+    const bool var2 = M.var2 != 0;
+    const FtLds LL = ft_lds_layout(NB, V.mb, NW, (int)sizeof(R), nb, 0);
+    R* sXV = (R*)(smem + LL.xv);
+    R* sPART = (R*)(smem + LL.part);
+    double* red = (double*)(smem + LL.red);
+    double* sNU = (double*)(smem + LL.slot);
+    const int TA = (nb + 15) / 16, NUROWS = 16 * TA + 2, MP = 16 * V.mb;
+    const FtWs L = ft_ws_layout(n, m, T, nb, NB, (int)sizeof(R), 0);
+    double* wsp = P.ws + (size_t)blockIdx.x * P.ws_stride;
+    double* b = wsp + L.b;
+    double* nu = wsp + L.nu;
+    double* winv = wsp + L.winv;
+    double* rdu = wsp + L.rdu;
+    double* rdx = wsp + L.rdx;
+    double* phx = wsp + L.phx;
+    double* rp = wsp + L.rp;
+    double* yv = wsp + L.y;
+    double* zp = P.zout + (size_t)blockIdx.x * Nz;
+    const size_t ld = Q.s_ld;
+    const int NCP = Q.ncp, TG = NCP / 16, KR = (int)ld;              // padded columns (multiple of 16), tiles per side, Gram depth
+    double* S = Q.S + (size_t)blockIdx.x * Q.s_stride;
+    double* G = S + (size_t)NCP * ld;                                // [NCP][NCP]
+    const double* Lt = Q.cst;                                        // [NX][NX]: Lt[r][q] = L[q][r]
+    const double* y0 = Q.cst + NX * NX;
+    const double c0 = Q.cst[NX * NX + NX];                           // T (|a o cu|^2 - |y0|^2)
+    const double lf2 = Q.cst[NX * NX + NX + 1];                      // |L|_F^2
+    const double y02 = Q.cst[NX * NX + NX + 2];                      // T |y0|^2
+    const double ce = 4096.0 * 2.220446049250313e-16;
+    // G = S^'S^ over the first KR rows of every column (rows beyond the live ones are zero), all TG x TG tiles
+    auto gram = [&]() {
+        for (int item = wv; item < TG * TG; item += NW) {
+            const int I = item / TG, J = item - I * TG;
+            const double* xa = S + (size_t)(16 * I + c) * ld;
+            const double* za = S + (size_t)(16 * J + c) * ld;
+            ft_d4 acc = {0, 0, 0, 0};
+            ft_vec_gemm<8>(acc, KR, g, [&](int k) { return xa[k]; }, [&](int k) { return za[k]; });
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) G[(size_t)(16 * I + g + 4 * rr) * NCP + 16 * J + c] = acc[rr];
+        }
+    };
+    // the symmetric nc x nc block of G as the circulant half the application kernel reads, the linear term, and their norms
+    auto emit = [&](double* Mc, double* lin, double& fro, double& lfro, double& tr) {
+        double a2 = 0.0, l2 = 0.0, t1 = 0.0;
+        for (int q = tid; q < H * nc; q += NT) {
+            const int j = q / nc, r = q - j * nc, cc = (r + j) % nc;
+            const double wgt = j == 0 ? 1.0 : ((j == nc / 2 && r >= nc / 2) ? 0.0 : 2.0);
+            Mc[q] = wgt * (0.5 * (G[(size_t)r * NCP + cc] + G[(size_t)cc * NCP + r]));
+        }
+        for (int q = tid; q < nc * nc; q += NT) { const double v = G[(size_t)(q / nc) * NCP + q % nc]; a2 += v * v; }
+        for (int q = tid; q < nc; q += NT) { const double v = G[(size_t)q * NCP + nc]; lin[q] = v; l2 += v * v; t1 += G[(size_t)q * NCP + q]; }
+        fro = sqrt(ft_block_sum<NW>(a2, red)); lfro = sqrt(ft_block_sum<NW>(l2, red)); tr = ft_block_sum<NW>(t1, red);
+    };
+    for (int mi = blockIdx.x; mi < P.bk_count; mi += gridDim.x) {
+        FtSel<true> sel; sel.mi = mi;
+        const size_t mo_plain = (size_t)mi * P.bk_plain, mo_pad = (size_t)mi * P.bk_pad;
+        double* out = Q.out + (size_t)mi * Q.out_stride;
+        double* oK = out + Q.oK; double* ou = out + Q.ou; double* oE = out + Q.oE; double* oe = out + Q.oe;
+        double* oEp = out + Q.oEp; double* oep = out + Q.oep; double* od = out + Q.od; double* osc = out + Q.osc;
+        __syncthreads();
+        bool bad = P.pf_flag[mi] != 0;                               // (uniform) no stored factor: the model never uses the form
+        if (bad) { if (tid == 0) Q.flag[mi] = 1; continue; }
+        const R* sfac = (const R*)P.pf_fac + (size_t)mi * P.pf_stride;
+        for (int idx = tid; idx < Nz; idx += NT) { const int e = idx % s; zp[idx] = e < m ? M.umid[e] : M.xmid[e - m]; }
+        for (int idx = tid; idx < nbn; idx += NT) { nu[idx] = 0.0; b[idx] = idx >= T * n ? M.xf[idx - T * n] : 0.0; }
+        for (size_t q = tid; q < (size_t)NCP * ld; q += NT) S[q] = 0.0;
+        __syncthreads();
+        const FtResid rs = ft_phase_resid<R, NB, NW, false, true>(ft_params(), blockIdx.x, sel);   // r_p = cp, r_d, Phi^-1 at the start, d = 0
+        bad = rs.bad > 0.0 || !(rs.rho2 < INFINITY);
+        if (bad) { if (tid == 0) Q.flag[mi] = 1; continue; }
+        const double rd2_0 = rs.rho2 - rs.rp2;
+        __syncthreads();
+        // ---- S^ = [Pb | cp]
+        const double* A1 = M.A1 + mo_plain; const double* A2 = M.A2 + mo_plain;     // row-major n x n
+        for (int q = tid; q < n * n; q += NT) {
+            const int r = q / n, cc = q - r * n;
+            S[(size_t)cc * ld + r] = A1[q];                                          // stage 0: A1 x0 + A2 x0_pre
+            if (var2) { S[(size_t)(n + cc) * ld + r] = A2[q]; if (T > 1) S[(size_t)cc * ld + n + r] = A2[q]; }   // stage 1: A2 x0
+        }
+        for (int idx = tid; idx < nbn; idx += NT) S[(size_t)nc * ld + idx] = rp[idx];
+        for (int i = 0; i < T; ++i) {                                // free response: W_i = A1 W_{i-1} + A2 W_{i-2}, W_-1 = [I 0], W_-2 = [0 I]; Pb = -W
+            for (int q = tid; q < 2 * n * n; q += NT) {
+                const int cc = q / n, r = q - cc * n;                // column cc of [B u1 | B u2], row r
+                const double* w1 = S + (size_t)(2 * n + cc) * ld + (size_t)(i >= 1 ? i - 1 : 0) * n;
+                const double* w2 = S + (size_t)(2 * n + cc) * ld + (size_t)(i >= 2 ? i - 2 : 0) * n;
+                double acc = 0.0;
+                for (int k = 0; k < n; ++k) {
+                    const double p1 = i >= 1 ? -w1[k] : (k == cc ? 1.0 : 0.0);
+                    acc = fma(A1[r * n + k], p1, acc);
+                    if (var2) {
+                        const double p2 = i >= 2 ? -w2[k] : (i == 1 ? (k == cc ? 1.0 : 0.0) : (k + n == cc ? 1.0 : 0.0));
+                        acc = fma(A2[r * n + k], p2, acc);
+                    }
+                }
+                S[(size_t)(2 * n + cc) * ld + (size_t)i * n + r] = -acc;
+            }
+            __threadfence_block();
+            __syncthreads();
+        }
+        gram();
+        __threadfence_block();
+        __syncthreads();
+        double nEp, nep, trp;
+        emit(oEp, oep, nEp, nep, trp);
+        const double ep0 = G[(size_t)nc * NCP + nc];
+        const double betap = trp + ep0;
+        __syncthreads();
+        // ---- nuc = Y^-1 (r_p - C Phi^-1 r_d): the right-hand side as P2 of fmpc_newton_tiled forms it (diagonal R, Q)
+        for (int item = wv; item < NB * TA; item += NW) {
+            const int Jr = item / TA, A = item - Jr * TA;
+            const int i = 16 * A + c, r = 16 * Jr + c;
+            ft_d4 acc = {0, 0, 0, 0};
+            const size_t iu = (size_t)(i < T ? i : T - 1) * m;
+            const double* ph1 = phx + (size_t)((i >= 1 && i < T) ? i - 1 : 0) * n;
+            const double* ph2 = phx + (size_t)((i >= 2 && i < T) ? i - 2 : 0) * n;
+            const double f1 = (i >= 1 && i < T) ? 1.0 : 0.0, f2 = (i >= 2 && i < T) ? 1.0 : 0.0;
+            ft_vec_gemm<12>(acc, MP, g,
+                        [&](int k) { const int kc = k < m ? k : m - 1; return rdu[iu + kc] * winv[iu + kc]; },
+                        [&](int k) { return V.BtP[(size_t)k * NP + r]; });
+            ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
+                        [&](int k) { return ph1[k < n ? k : n - 1] * f1; },
+                        [&](int k) { return (V.A1tP + mo_pad)[k * NP + r]; });
+            if (var2)
+                ft_vec_gemm<(NP / 4 < 12 ? NP / 4 : 10)>(acc, NP, g,
+                            [&](int k) { return ph2[k < n ? k : n - 1] * f2; },
+                            [&](int k) { return (V.A2tP + mo_pad)[k * NP + r]; });
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int io = 16 * A + g + 4 * rr;
+                if (io < nb && r < n) {
+                    const double cv = io < T ? phx[io * n + r] - acc[rr] : phx[(T - 1) * n + r];
+                    yv[io * n + r] = rp[io * n + r] - cv;
+                }
+            }
+        }
+        // ---- the 4n + 1 sweeps through the stored factor, in place: column nc first (nuc), then J = -Y^-1 Pb
+        for (int col = nc; col >= 0; --col) {
+            double* sc = S + (size_t)col * ld;
+            if (col < nc)
+                for (int idx = tid; idx < nbn; idx += NT) yv[idx] = -sc[idx];
+            __threadfence_block();
+            __syncthreads();
+            ft_forward<R, NB, NW>(sfac, yv, sXV, sPART, n, nb);
+            __syncthreads();
+            ft_backward<R, NB, NW>(sfac, yv, sXV, sPART, sNU, n, nb, NUROWS);
+            __syncthreads();
+            for (int idx = tid; idx < nbn; idx += NT) { const int i = idx / n, r = idx - i * n; sc[idx] = sNU[i * LDN + r]; }
+            __syncthreads();
+        }
+        __threadfence_block();
+        __syncthreads();
+        // ---- u0 = u0c + K0 d: K0 = diag(wc) B' J_0, u0c = ubar + wc o (B' nuc_0 - cu)      (wc, cu: stage 0 of Phi^-1, r_d[u] at nu = 0)
+        for (int q = tid; q < nc * m; q += NT) {
+            const int cc = q / m, j = q - cc * m;
+            double acc = 0.0;
+            for (int r = 0; r < n; ++r) acc = fma(M.Bt[(size_t)j * n + r], S[(size_t)cc * ld + r], acc);
+            oK[q] = winv[j] * acc;
+        }
+        for (int j = tid; j < m; j += NT) {
+            double acc = 0.0;
+            for (int r = 0; r < n; ++r) acc = fma(M.Bt[(size_t)j * n + r], S[(size_t)nc * ld + r], acc);
+            ou[j] = M.umid[j] + winv[j] * (acc - rdu[j]);
+        }
+        for (int r = tid; r < n; r += NT) od[r] = rdx[(T - 1) * n + r];           // x entries of r_d at the last stage without nu
+        double sj = 0.0;
+        for (size_t q = tid; q < (size_t)(nc + 1) * ld; q += NT) sj = fma(S[q], S[q], sj);
+        const double mass = lf2 * ft_block_sum<NW>(sj, red) + y02;
+        // ---- G^_s = L' [J_s | nuc_s] - [0 | y0], in place; the terminal rows carry no input
+        for (int q = tid; q < (nc + 1) * nb; q += NT) {
+            const int col = q / nb, i = q - col * nb;
+            double* v = S + (size_t)col * ld + (size_t)i * n;
+            double x[NX];
+#pragma unroll
+            for (int k = 0; k < NX; ++k) x[k] = k < n ? v[k] : 0.0;
+            for (int r = 0; r < n; ++r) {
+                double acc = 0.0;
+#pragma unroll
+                for (int k = 0; k < NX; ++k) acc = fma(Lt[r * NX + k], x[k], acc);
+                v[r] = i < T ? (col == nc ? acc - y0[r] : acc) : 0.0;
+            }
+        }
+        __threadfence_block();
+        __syncthreads();
+        gram();
+        __threadfence_block();
+        __syncthreads();
+        double nE, ne, tre;
+        emit(oE, oe, nE, ne, tre);
+        const double qq = G[(size_t)nc * NCP + nc];
+        const double beta = tre + qq + mass;
+        if (tid == 0) {
+            osc[0] = qq + c0 + ce * beta; osc[1] = ep0 - ce * betap;
+            osc[2] = nE + beta; osc[3] = ne + beta; osc[4] = nEp + betap; osc[5] = nep + betap;
+            osc[6] = rd2_0; osc[7] = 0.0;
+        }
+        // a model whose operands are not finite never uses the form
+        double chk = 0.0;
+        for (int q = tid; q < nc * m; q += NT) chk += fabs(oK[q]);
+        for (int j = tid; j < m; j += NT) chk += fabs(ou[j]);
+        chk = ft_block_sum<NW>(chk, red) + nE + ne + nEp + nep + fabs(qq) + fabs(ep0) + beta + betap + fabs(rd2_0);
+        if (tid == 0) Q.flag[mi] = chk < INFINITY ? 0 : 1;
+    }
+}
+
 // ---------------------------------------------------------------- host side
 template <bool BK, typename R, int NB, int NW, int NL = -1, bool DR = false>
 static hipError_t ft_launch_pf(const FtParams& P, int grid, size_t lds, hipStream_t stream) {
@@ -1763,4 +1990,16 @@ hipError_t fmpc_launch_tiled(const FtParams& P, int NB, int NW, int is_float, in
     const int denseR = P.V.denseR;
     if (P.bk_count > 0) { FT_DISPATCH(ft_launch, true, P, grid, lds_bytes, stream) }
     FT_DISPATCH(ft_launch, false, P, grid, lds_bytes, stream)
+}
+
+hipError_t fmpc_bank_first_build_prepare(int NB, int NW, size_t lds_bytes) {
+    if (NB == 2 && NW == 2) return hipFuncSetAttribute((const void*)fmpc_bank_first_build_k<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (NB == 2 && NW == 4) return hipFuncSetAttribute((const void*)fmpc_bank_first_build_k<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    return hipErrorInvalidValue;
+}
+hipError_t fmpc_launch_bank_first_build(const FtParams& P, const FbfParams& Q, int NB, int NW, int grid, size_t lds_bytes, hipStream_t stream) {
+    if (NB == 2 && NW == 2) hipLaunchKernelGGL((fmpc_bank_first_build_k<2, 2>), dim3(grid), dim3(NW * 64), lds_bytes, stream, P, Q);
+    else if (NB == 2 && NW == 4) hipLaunchKernelGGL((fmpc_bank_first_build_k<2, 4>), dim3(grid), dim3(NW * 64), lds_bytes, stream, P, Q);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
 }

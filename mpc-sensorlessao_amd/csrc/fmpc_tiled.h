@@ -152,3 +152,25 @@ hipError_t fmpc_launch_tiled(const FtParams& P, int NB, int NW, int is_float, in
 // the build of the stored cold-start factors of a bank (one workgroup per model at a time; P.zout: grid x T (n + m) doubles of scratch)
 hipError_t fmpc_bank_prefactor_prepare(int n, int NB, int NW, int is_float, size_t lds_bytes);
 hipError_t fmpc_launch_bank_prefactor(const FtParams& P, int NB, int NW, int is_float, int grid, size_t lds_bytes, hipStream_t stream);
+
+// The build of the per-model first-move form of a bank (fmpc_bank_first_move_device; fmpc_bank_first_build_k): fp64, n <= 31 (NB = 2).
+// Per workgroup a scratch of ncp columns of s_ld doubles ([Pb | cp], then [J | nuc], a column per right-hand side; ncp = 4n + 1 rounded
+// up to 16, s_ld = nb n rounded up to 4) and the ncp x ncp Gram matrix behind it.  Per model the operands at out + model * out_stride,
+// laid out as FmParams addresses them (oK .. osc: offsets in doubles of K0t, u0c, Ec, e, Epc, ep, dx0T and the 8 scalars
+// [e0, ep0, normE, norme, normEp, normep, rd2_0, 0]); flag[model] != 0: the model has no valid operands.
+// cst: [Lt 32 x 32 | y0 32 | c0, |L|_F^2, T |y0|^2] (fmpc_api.hip).
+struct FbfParams {
+    double* S; size_t s_ld, s_stride; int ncp;
+    double* out; size_t out_stride, oK, ou, oE, oe, oEp, oep, od, osc;
+    int* flag;
+    const double* cst;
+};
+static inline size_t fmpc_bank_first_scratch_doubles(int n, int nb, size_t* s_ld, int* ncp) {
+    const size_t ld = ((size_t)nb * n + 3) & ~(size_t)3;
+    const int cp = (4 * n + 1 + 15) & ~15;
+    if (s_ld) *s_ld = ld;
+    if (ncp) *ncp = cp;
+    return (size_t)cp * ld + (size_t)cp * cp;
+}
+hipError_t fmpc_bank_first_build_prepare(int NB, int NW, size_t lds_bytes);
+hipError_t fmpc_launch_bank_first_build(const FtParams& P, const FbfParams& Q, int NB, int NW, int grid, size_t lds_bytes, hipStream_t stream);

@@ -458,6 +458,30 @@ class FastMPCHandle:
         """True when the last bank solve was handed the stored factors (fmpc_last_bank_stored_factor)."""
         return bool(self._lib.fmpc_last_bank_stored_factor(self._h))
 
+    def first_move_model_bank(self, k=1e-2):
+        """fmpc_bank_first_move_device: build the per-model first-move form of the cold-start loop step for barrier weight k, on
+        torch's current stream (222624 bytes per model at (27, 144)).  Needs prefactor_model_bank(k) with exactly this k first.
+        Bank loop steps with first moves only, one Newton step and this k then take the form."""
+        import torch
+        stream = C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+        rc = self._lib.fmpc_bank_first_move_device(self._h, float(k), stream)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_bank_first_move_device")
+
+    def release_bank_first_move(self):
+        rc = self._lib.fmpc_bank_first_move_release(self._h)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_bank_first_move_release")
+
+    @property
+    def bank_first_move_count(self):
+        """Models of the bank with valid first-move operands (fmpc_bank_first_move_count; 0 = none).  Synchronises the device."""
+        return int(self._lib.fmpc_bank_first_move_count(self._h))
+
+    def last_bank_first_move(self):
+        """True when the last bank loop step took the per-model first-move form (fmpc_last_bank_first_move)."""
+        return bool(self._lib.fmpc_last_bank_first_move(self._h))
+
     def _bank_loop_checks(self, batch, pairs, model_of, status, iters):
         import torch
         for t, shape, name in pairs:
