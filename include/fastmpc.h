@@ -322,10 +322,51 @@ int fmpc_solve_ramp_u0_device(fmpc_handle h, int batch,
  * for `batch` coefficient series at once, on the device (Gram matrices on the fp64 matrix cores, Cholesky solve of the
  * normal equations).  Device pointers; series: per realisation n x num_samples column-major (MATLAB: ad_acc', one
  * n-vector per time step), the first num_train samples are used; A1, A2: per realisation n x n column-major;
- * status (nullable): per realisation 0 or FMPC_E_NOT_PD_SCHUR when AA'AA is not positive definite.  n <= 32.
+ * status (nullable): per realisation 0 or FMPC_E_NOT_PD_SCHUR when AA'AA is not positive definite.  n <= 32
+ * (FMPC_E_UNSUPPORTED above): fmpc_var_fit_device below is the entry for every solver size and for VAR(1).
  */
 int fmpc_var_identify_device(int n, int num_train, int num_samples, int batch, const double* series,
                              double* A1, double* A2, int* status, void* stream);
+
+/*
+ * VAR(PN) identification, PN = order = 1 or 2, at any solver size (reference README.md:116-130):
+ *     AA(i-PN, n(j-1)+1 : nj) = ad_acc(i-j,:), j = 1..PN ;  BB(i-PN,:) = ad_acc(i,:) ;  i = PN+1..num_train
+ *     PARA = (AA'*AA) \ AA'*BB ;  A_j = PARA(n(j-1)+1 : nj, :)'
+ * series, A1, A2, status: the layouts of fmpc_var_identify_device; with order 1, A2 is not touched and may be NULL (the VAR_1
+ * solver variant takes the single A).  A series whose Gram matrix is not positive definite (a zero, negative, NaN or Inf pivot)
+ * gets FMPC_E_NOT_PD_SCHUR in status, its A1, A2 are not written and the other series are unaffected.
+ * Supported: p = order * n <= 224 (VAR(2) up to n = 111, the largest bank size; VAR(1) up to n = 224).  The Gram matrices AA'AA
+ * and AA'BB are 16 x 16 tiles on the fp64 matrix cores, each summed in one fixed order (bitwise reproducible, whatever the slot
+ * or batch position of a series); the normal equations are solved by a blocked Cholesky factorisation with block substitutions.
+ * The entry has no handle: it neither allocates nor synchronises nor reads back, so it can be recorded into a HIP graph.  The
+ * caller owns the workspace (device memory).  A SLOT holds the Gram matrix and right-hand sides of one series;
+ * fmpc_var_fit_workspace_bytes(n, order, batch) is the recommended size -- min(batch, 512) slots: two per compute unit of an
+ * MI355X, more would not run at the same time; p = 222: 0.6 MB per slot, 308 MB at the cap -- and (n, order, 1) the minimum, one
+ * slot.  The call uses as many whole slots as workspace_bytes holds and walks the batch through them; less than one slot is
+ * FMPC_E_DIM.  order 2 with n <= 32 is handed to the kernel of fmpc_var_identify_device (bit for bit its results) and needs no
+ * workspace: fmpc_var_fit_workspace_bytes is 0 there (also for arguments the fit refuses) and workspace may be NULL.
+ * (FMPC_VARFIT_BLOCKED=1 in the environment, read at every call of both functions, sends those sizes through the blocked
+ * kernels too: a measurement switch.)
+ * Before anything is enqueued: FMPC_E_NULL for a NULL series or A1, a NULL A2 at order 2, a NULL workspace where one is needed;
+ * FMPC_E_DIM for order outside {1, 2}, n <= 0, batch < 0, num_train - order < order * n (fewer rows than unknowns),
+ * num_samples < num_train; FMPC_E_UNSUPPORTED for p > 224.  batch == 0 is FMPC_OK.
+ *
+ * fmpc_var_validate_device: the second half of the reference's identification block (README.md:134-153 with first = num_train,
+ * count = num_test): the one-step prediction pred_i = sum_j A_j ad_acc(first+i-j,:)' against ad_acc(first+i,:), i = 1..count
+ * (the reference's 1-based rows: first >= order, first + count <= num_samples, count >= 1; FMPC_E_DIM otherwise) and per mode q
+ *     rmse[b n + q] = sqrt(mean_i (pred_i(q) - actual_i(q))^2),  rrmse[b n + q] = rmse / (max_i actual_i(q) - min_i actual_i(q))
+ * (a plain IEEE division: a constant column gives Inf or NaN, as the reference's expression does).  rrmse may be NULL.  A1, A2:
+ * per series, what the fit writes (A2 NULL or ignored at order 1) -- or any other model, e.g. a bank's after editing: the call is
+ * independent of the fit.  The product is on the matrix cores, the reductions have a fixed order.  Same limit on p and error
+ * conventions as the fit; no workspace.
+ */
+size_t fmpc_var_fit_workspace_bytes(int n, int order, int batch);
+int fmpc_var_fit_device(int n, int order, int num_train, int num_samples, int batch,
+                        const double* series, double* A1, double* A2, int* status,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int fmpc_var_validate_device(int n, int order, int first, int count, int num_samples, int batch,
+                             const double* series, const double* A1, const double* A2,
+                             double* rmse, double* rrmse, void* stream);
 
 /*
  * Model bank: one VAR model (A1, A2) per problem of a batched solve.  In the reference a realisation's model is its own: A1, A2 are

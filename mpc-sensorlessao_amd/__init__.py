@@ -12,10 +12,10 @@ from .sharded import ShardedFastMPC, shard_range
 from .closed_loop import ClosedLoop, AOLoop
 from .lanes import SolveLanes
 from .recorded import RecordedSolves
-from .var_identify import identify_var2_device
+from .var_identify import identify_var2_device, identify_var_device, validate_var_device, var_fit_workspace_bytes
 from .estimator import PhaseDiversityEstimator
 from . import _lib
 
 __all__ = ["FastMPCHandle", "Fast_MPC2", "Fast_MPC2_VAR1", "deinterleave", "FastMPCError",
            "ShardedFastMPC", "shard_range", "ClosedLoop", "AOLoop", "SolveLanes", "RecordedSolves", "PhaseDiversityEstimator", "synthetic", "load", "LIB_PATH",
-           "identify_var2_device"]
+           "identify_var2_device", "identify_var_device", "validate_var_device", "var_fit_workspace_bytes"]

@@ -73,6 +73,9 @@ SIGNATURES = {
     "fmpc_set_refinement": (C.c_int, [_vp, C.c_int]),
     "fmpc_last_refinement": (C.c_int, [_vp]),
     "fmpc_var_identify_device": (C.c_int, [C.c_int] * 4 + [_vp] * 5),
+    "fmpc_var_fit_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "fmpc_var_fit_device": (C.c_int, [C.c_int] * 5 + [_vp] * 5 + [C.c_size_t, _vp]),
+    "fmpc_var_validate_device": (C.c_int, [C.c_int] * 6 + [_vp] * 6),
     "fmpc_solve_ramp": (C.c_int, [_vp, C.c_int] + [_vp] * 6 + [C.c_int, C.c_double] + [_vp] * 5),
     "fmpc_solve_ramp_device": (C.c_int, [_vp, C.c_int] + [_vp] * 6 + [C.c_int, C.c_double] + [_vp] * 5 + [_vp]),
     "fmpc_solve_ramp_u0_device": (C.c_int, [_vp, C.c_int] + [_vp] * 6 + [C.c_int, C.c_double] + [_vp] * 6 + [_vp]),
