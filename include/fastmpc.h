@@ -272,6 +272,53 @@ int fmpc_loop_run_device(fmpc_handle h, int batch, int steps, const double* a, c
                          double* U0, double* X0, int* status, int* iters, void* stream);
 
 /*
+ * Closed-loop records: the tail of the reference's timestep (README.md:576-622) for a batch of realisations, on the device.
+ * The caller's B_conv is blkdiag(B) (the body of MPC_DesignMatrices is not part of the reference
+ * tree), so with M1_i, M2_i the n x n row blocks of M1, M2 and w = b_ref, per problem and stage i = 0 .. stages-1:
+ *     f_i    = M1_i x0 + M2_i x0_pre + w_i            (x0_pre NULL: zeros; w NULL: zeros)
+ *     Xp_i   = f_i + B u_i                            X_predicted, README.md:592; Xp_0 is x_prev (:594, X_acc :621)
+ *     xerr_i = ||Xp_i||_2                             X_err, README.md:603-607; xerr_0 is X_err_low / X_acc_err (:607, :622)
+ *     J      = sum_{i<T-1} Xp_i' Q Xp_i + Xp_{T-1}' Qf Xp_{T-1} + sum_i u_i' R u_i
+ *                                                     = U'HU + r'U + c of README.md:588 (:343, :500-501) for
+ *                                                     H = B_conv' Q~ B_conv + R~, r = 2 B_conv' Q~ f, c = f' Q~ f
+ *     du     = u_0 - u1                               (u1 NULL: u_0)  du_prev, README.md:611-615
+ *     uv_c   = sign(u_0c) (-b + sqrt(b^2 + 4 a |u_0c| unit_change)) / (2 a)
+ *                                                     the rad -> V conversion of README.md:576-585 (a, b: :350), first move only (:585)
+ * The handle's linear terms q, r, qf do not enter J (the reference passes [] for them).  unit_change is used at README.md:579
+ * and never defined there: it is an argument beside coeff_a and coeff_b.  X_err_high (:608, the norm of an empty slice) is
+ * omitted.  Device pointers: x0, x0_pre n per problem, w T n, u_i of problem p at u + p*ldu + i*stage_stride, u1 m; outputs
+ * Xp stages*n, xerr stages, J 1, du m, uv m per problem, each nullable.  With z of a solve as u: ldu = ldz,
+ * stage_stride = n + m, stages = T; with first moves only: u = u0_out, ldu = m, stages = 1.  stages in [1, T].
+ * Before the device is touched: FMPC_E_DIM for J != NULL with stages != T, ldu < (stages-1)*stage_stride + m,
+ * stage_stride < m when stages > 1, uv != NULL with coeff_a <= 0 or a non-finite parameter; FMPC_E_NULL for a NULL h, x0 or u;
+ * FMPC_OK with nothing enqueued when all five outputs are NULL or batch == 0.
+ * n <= 32 with diagonal Q, Qf, R (the reference's configuration): panels of 16 problems on the matrix cores, u read once, the
+ * per-stage costs added in a fixed order (no atomics: two calls give the same bits).  Any other size or dense weights: one
+ * workgroup per problem, the size and weight fallback without a speed claim.  The weights are uploaded on the first call
+ * (FMPC_E_ALLOC while `stream` is being captured and something has to be allocated: call once before a capture).
+ *
+ * fmpc_loop_records_run_device: the stages = 1 records of every step of a recorded stretch in one launch, from X0, U0 as
+ * fmpc_loop_run_device leaves them (n x batch x steps, m x batch x steps) and the state before the stretch (x0_before,
+ * u_before1, u_before2: each nullable = zeros).  Step s has x0 = X0[s], x0_pre = X0[s-1] (x0_before at s = 0), u[s-1], u[s-2]
+ * from U0 (u_before1 / u_before2 where the index is negative) and w_0 = -A1 B u[s-1] - A2 B u[s-2] (README.md:490-497), so
+ *     Xp0[s] = A1 (X0[s] - B u[s-1]) + A2 (x0_pre[s] - B u[s-2]) + B U0[s],  dU[s] = U0[s] - u[s-1],  Uv[s] from U0[s].
+ * Outputs n, 1, m, m per (problem, step), laid out as X0 / U0; each nullable.  VAR(1) handles (A2 absent) work in both calls.
+ */
+int fmpc_loop_records_device(fmpc_handle h, int batch, int stages,
+                             const double* x0, const double* x0_pre, const double* w,
+                             const double* u, long long ldu, int stage_stride,
+                             const double* u1,
+                             double coeff_a, double coeff_b, double unit_change,
+                             double* Xp, double* xerr, double* J, double* du, double* uv,
+                             void* stream);
+int fmpc_loop_records_run_device(fmpc_handle h, int batch, int steps,
+                                 const double* X0, const double* U0,
+                                 const double* x0_before, const double* u_before1, const double* u_before2,
+                                 double coeff_a, double coeff_b, double unit_change,
+                                 double* Xp0, double* xerr0, double* dU, double* Uv,
+                                 void* stream);
+
+/*
  * Ramp-rate rows of the VAR_1 variant (VAR_1/Fast_MPC2.m:26-27 arguments dumin, dumax, u_prev;
  * VAR_1/fast_mpc_ineq_const.m:58-76): per stage j   du_min <= u_j - u_{j-1} <= du_max,  u_{-1} = u_prev.
  * fmpc_set_ramp stores the bounds (m each, du_min < du_max) in the handle; fmpc_solve_ramp[_device] is

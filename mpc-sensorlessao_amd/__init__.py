@@ -11,6 +11,7 @@ from . import synthetic
 from .sharded import ShardedFastMPC, shard_range
 from .closed_loop import ClosedLoop, AOLoop
 from .lanes import SolveLanes
+from .records import LoopRecords
 from .recorded import RecordedSolves
 from .var_identify import identify_var2_device, identify_var_device, validate_var_device, var_fit_workspace_bytes
 from .estimator import PhaseDiversityEstimator
@@ -18,4 +19,4 @@ from . import _lib
 
 __all__ = ["FastMPCHandle", "Fast_MPC2", "Fast_MPC2_VAR1", "deinterleave", "FastMPCError",
            "ShardedFastMPC", "shard_range", "ClosedLoop", "AOLoop", "SolveLanes", "RecordedSolves", "PhaseDiversityEstimator", "synthetic", "load", "LIB_PATH",
-           "identify_var2_device", "identify_var_device", "validate_var_device", "var_fit_workspace_bytes"]
+           "identify_var2_device", "identify_var_device", "validate_var_device", "var_fit_workspace_bytes", "LoopRecords"]

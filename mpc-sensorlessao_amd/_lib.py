@@ -64,6 +64,8 @@ SIGNATURES = {
     "fmpc_loop_step_device": (C.c_int, [_vp, C.c_int] + [_vp] * 8 + [C.c_int, C.c_double] + [_vp] * 6 + [_vp]),
     "fmpc_ao_step_device": (C.c_int, [_vp, C.c_int] + [_vp] * 6 + [C.c_int, C.c_double] + [_vp] * 6 + [_vp]),
     "fmpc_loop_run_device": (C.c_int, [_vp, C.c_int, C.c_int] + [_vp] * 4 + [C.c_int, C.c_int, C.c_double] + [_vp] * 7 + [_vp]),
+    "fmpc_loop_records_device": (C.c_int, [_vp, C.c_int, C.c_int] + [_vp] * 4 + [C.c_longlong, C.c_int, _vp] + [C.c_double] * 3 + [_vp] * 5 + [_vp]),
+    "fmpc_loop_records_run_device": (C.c_int, [_vp, C.c_int, C.c_int] + [_vp] * 5 + [C.c_double] * 3 + [_vp] * 4 + [_vp]),
     "fmpc_solve_u0_device": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [C.c_int, C.c_double] + [_vp] * 6 + [_vp]),
     "fmpc_solve_u0_device_ld": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [C.c_int, C.c_double] + [_vp] * 6 + [C.c_int, _vp]),
     "fmpc_solve_u0": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [C.c_int, C.c_double] + [_vp] * 4),

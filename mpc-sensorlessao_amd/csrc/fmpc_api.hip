@@ -19,6 +19,7 @@
 #include "fmpc_tiled.h"
 #include "fmpc_rampcold.h"
 #include "fmpc_bank.h"
+#include "fmpc_records.h"
 #define FMPC_PRODUCT_MIN_BATCH_DEFAULT 65   // closed-loop steps with first moves only: the product form from this many realisations on
 #include "fmpc_alloc.h"                    // owned, counted buffers (fmpc_alloc_generation), shared with fmpc_est_api.hip
 
@@ -45,6 +46,8 @@ hipError_t fmpc_launch_unpack(int n, int m, int T, int batch, const double* z, d
 hipError_t fmpc_launch_loop_inputs(int n, int m, int T, int batch, const double* Bt, const double* M1, const double* M2,
                                    const double* a, const double* x0_last, const double* u1, const double* u2,
                                    double* x0, double* x0_pre, double* w, hipStream_t stream, double* lv = nullptr);
+// closed-loop records (fmpc_kernel_records.hip)
+hipError_t fmpc_launch_loop_records(const RecParams& P, int panel, hipStream_t stream);
 
 // one-wave-per-problem MFMA kernel (fmpc_kernel_wave.hip)
 size_t fmpc_wave_lds_bytes(int n, int mp);
@@ -198,6 +201,10 @@ struct fmpc_handle_s {
     DevBuf<double> ws;
     // z_out == NULL (first moves only): the working iterate of the problems a kernel has to iterate on lives here
     DevBuf<double> zs;
+    // closed-loop records (fmpc_loop_records_device): Q, Qf, R as the records kernel of this handle reads them, uploaded on first use
+    // (rec_panel: the padded diagonals of the panel kernel; else dense), and the per-stage partial costs of the last call
+    DevBuf<double> rec_w; int rec_ready = 0, rec_panel = 0; size_t rec_oQf = 0, rec_oR = 0;
+    DevBuf<double> rec_j;
     // staging for the host-pointer entry points
     DevBuf<char> stage;
     PinnedBuf<char> pin; void* pin_dev = nullptr;   // pinned host twin of the staging block for small host-pointer solves (fmpc_solve_host)
@@ -2838,6 +2845,92 @@ extern "C" int fmpc_loop_inputs_device(fmpc_handle h, int batch, const double* a
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
     return fmpc_launch_loop_inputs(h->n, h->m, h->T, batch, h->dev.Bt, h->loop_M1, h->loop_M2, a_k, x0_last, u1, u2,
                                    x0, x0_pre, w, (hipStream_t)stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
+}
+
+// Q, Qf, R of the records kernels on the device, once per handle (h->mu held, inside the guard).  n <= 32 with diagonal weights: the
+// panel kernel's zero-padded diagonals; otherwise the dense matrices of the any-size kernel.  The handle keeps 2Q, 2Qf, 2R.
+static int fmpc_ensure_records(fmpc_handle h, hipStream_t stream) {
+    if (h->rec_ready) return FMPC_OK;
+    const int n = h->n, m = h->m;
+    const int panel = n <= REC_NMAX && !h->denseQ && !h->denseR;
+    std::vector<double> v;
+    if (panel) {
+        const int mpad = (m + 15) & ~15;
+        h->rec_oQf = REC_NMAX; h->rec_oR = 2 * REC_NMAX;
+        v.assign(2 * REC_NMAX + (size_t)mpad, 0.0);
+        for (int i = 0; i < n; ++i) { v[i] = 0.5 * h->hm_Q2[i]; v[h->rec_oQf + i] = 0.5 * h->hm_Qf2[i]; }
+        for (int j = 0; j < m; ++j) v[h->rec_oR + j] = 0.5 * h->hm_R2[j];
+    } else {
+        const size_t nn = (size_t)n * n;
+        h->rec_oQf = nn; h->rec_oR = 2 * nn;
+        v.assign(2 * nn + (size_t)m * m, 0.0);
+        for (size_t e = 0; e < nn; ++e) { v[e] = 0.5 * h->hm_q2m[e]; v[nn + e] = 0.5 * h->hm_qf2m[e]; }
+        if (h->denseR) for (size_t e = 0; e < (size_t)m * m; ++e) v[2 * nn + e] = 0.5 * h->hm_r2full[e];
+        else for (int j = 0; j < m; ++j) v[2 * nn + (size_t)j * m + j] = 0.5 * h->hm_R2[j];
+    }
+    const int rc = h->rec_w.assign(v.data(), v.size(), stream);       // (FMPC_E_ALLOC while the stream is being captured)
+    if (rc != FMPC_OK) return rc;
+    h->rec_panel = panel; h->rec_ready = 1;
+    return FMPC_OK;
+}
+
+static int fmpc_records_launch(fmpc_handle h, RecParams& P, hipStream_t stream) {
+    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    std::lock_guard<std::mutex> lock(h->mu);
+    int rc = fmpc_guard_begin(h, stream);
+    if (rc != FMPC_OK) return rc;
+    rc = fmpc_ensure_records(h, stream);
+    if (rc == FMPC_OK && P.J && h->rec_panel) rc = h->rec_j.grow((size_t)P.stages * P.batch, stream);
+    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
+    P.n = h->n; P.m = h->m; P.T = h->T;
+    P.Bt = h->dev.Bt; P.M1 = h->loop_M1; P.M2 = h->loop_M2;
+    P.Q = h->rec_w; P.Qf = h->rec_w + h->rec_oQf; P.R = h->rec_w + h->rec_oR;
+    P.jpart = (P.J && h->rec_panel) ? (double*)h->rec_j : nullptr;
+    const bool ok = fmpc_launch_loop_records(P, h->rec_panel, stream) == hipSuccess;
+    fmpc_guard_end(h, stream);
+    return ok ? FMPC_OK : FMPC_E_HIP;
+}
+
+// The records of a timestep (README.md:576-622; see include/fastmpc.h).  Every argument rule answers before the device is touched.
+extern "C" int fmpc_loop_records_device(fmpc_handle h, int batch, int stages,
+                                        const double* x0, const double* x0_pre, const double* w,
+                                        const double* u, long long ldu, int stage_stride, const double* u1,
+                                        double coeff_a, double coeff_b, double unit_change,
+                                        double* Xp, double* xerr, double* J, double* du, double* uv, void* stream) {
+    if (uv && (!(coeff_a > 0.0) || !isfinite(coeff_a) || !isfinite(coeff_b) || !isfinite(unit_change))) return FMPC_E_DIM;
+    if (batch < 0 || stages < 1) return FMPC_E_DIM;
+    if (!h || !x0 || !u) return FMPC_E_NULL;
+    if (stages > h->T || (J && stages != h->T)) return FMPC_E_DIM;
+    if (stages > 1 && stage_stride < h->m) return FMPC_E_DIM;
+    if (ldu < (long long)(stages - 1) * (stages > 1 ? stage_stride : 0) + h->m) return FMPC_E_DIM;
+    if ((!Xp && !xerr && !J && !du && !uv) || batch == 0) return FMPC_OK;
+    RecParams P;
+    memset(&P, 0, sizeof(P));
+    P.batch = batch; P.steps = 0;
+    P.stages = (Xp || xerr || J) ? stages : 1;                        // (du and uv are the first move's)
+    P.x0 = x0; P.x0_pre = x0_pre; P.w = w; P.u = u; P.ldu = ldu; P.stage_stride = stages > 1 ? stage_stride : 0; P.u1 = u1;
+    P.ca = coeff_a; P.cb = coeff_b; P.uc = unit_change;
+    P.Xp = Xp; P.xerr = xerr; P.J = J; P.du = du; P.uv = uv;
+    return fmpc_records_launch(h, P, (hipStream_t)stream);
+}
+
+// The stage-0 records of every step of a recorded stretch in one launch (see include/fastmpc.h).
+extern "C" int fmpc_loop_records_run_device(fmpc_handle h, int batch, int steps, const double* X0, const double* U0,
+                                            const double* x0_before, const double* u_before1, const double* u_before2,
+                                            double coeff_a, double coeff_b, double unit_change,
+                                            double* Xp0, double* xerr0, double* dU, double* Uv, void* stream) {
+    if (Uv && (!(coeff_a > 0.0) || !isfinite(coeff_a) || !isfinite(coeff_b) || !isfinite(unit_change))) return FMPC_E_DIM;
+    if (batch < 0 || steps < 0) return FMPC_E_DIM;
+    if (!h || !X0 || !U0) return FMPC_E_NULL;
+    if ((!Xp0 && !xerr0 && !dU && !Uv) || batch == 0 || steps == 0) return FMPC_OK;
+    if (steps > 65535) return FMPC_E_DIM;                              // (a grid dimension of the any-size kernel)
+    RecParams P;
+    memset(&P, 0, sizeof(P));
+    P.batch = batch; P.steps = steps; P.stages = 1;
+    P.x0 = X0; P.u = U0; P.ldu = h->m; P.x0_before = x0_before; P.u_before1 = u_before1; P.u_before2 = u_before2;
+    P.ca = coeff_a; P.cb = coeff_b; P.uc = unit_change;
+    P.Xp = Xp0; P.xerr = xerr0; P.du = dU; P.uv = Uv;
+    return fmpc_records_launch(h, P, (hipStream_t)stream);
 }
 
 hipError_t fmpc_launch_phase_residual(int batch, size_t npx, int n, int m, const double* Bt, const double* phase, const double* u,

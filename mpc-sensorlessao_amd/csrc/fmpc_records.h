@@ -1,0 +1,26 @@
+// Closed-loop records (fmpc_loop_records_device / fmpc_loop_records_run_device in include/fastmpc.h): the argument block shared by
+// fmpc_api.hip and fmpc_kernel_records.hip.
+#pragma once
+#include <stddef.h>
+#include <hip/hip_runtime.h>
+
+#define REC_PT 16            // problems of a panel: the columns of a v_mfma_f64_16x16x4_f64 tile
+#define REC_NMAX 32          // the panel kernel's state size: two row tiles
+#define REC_LDB 36           // leading dimension of B' in LDS (rows n..35 zero; 4 * 36 * 8 bytes = 128 mod 256: the four k-groups of a
+                             // wavefront read different banks)
+
+struct RecParams {
+    int n, m, T, batch, stages;
+    int steps;                                       // 0: one timestep, `stages` stages;  > 0: a recorded stretch, stage 0 of every step
+    const double* Bt; const double* M1; const double* M2;          // B' (m x n), M1, M2 ((T n) x n row-major)
+    const double* Q; const double* Qf; const double* R;           // panel kernel: diagonals, zero-padded to 32 / 32 / 16 ceil(m / 16);
+                                                                   // any-size kernel: dense row-major n x n, n x n, m x m
+    // one timestep
+    const double* x0; const double* x0_pre; const double* w;
+    const double* u; long long ldu; int stage_stride;
+    const double* u1;
+    // a stretch: X0 n x batch x steps, U0 m x batch x steps, the state before it (each nullable = zeros)
+    const double* x0_before; const double* u_before1; const double* u_before2;
+    double ca, cb, uc;                               // the rad -> V conversion (README.md:577-583)
+    double* Xp; double* xerr; double* jpart; double* J; double* du; double* uv;    // jpart: stages x batch partial costs (panel kernel)
+};

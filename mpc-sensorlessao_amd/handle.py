@@ -339,6 +339,67 @@ class FastMPCHandle:
         if rc != _lib.FMPC_OK:
             raise FastMPCError(rc, "fmpc_loop_inputs_device")
 
+    def loop_records_device(self, x0, x0_pre, w, u, u1=None, stages=None, ldu=None, stage_stride=None, volts=None,
+                            Xp=None, xerr=None, J=None, du=None, uv=None):
+        """fmpc_loop_records_device: the records of a timestep (README.md:576-622) into the given output tensors (None: not
+        produced).  x0, x0_pre (batch, n), w (batch, T n), u1 (batch, m): contiguous float64 HIP tensors, x0_pre / w / u1 may be
+        None.  u: a solve's z (batch rows ldu apart, stage_stride = n + m, stages = T: the defaults for a 2-D tensor wider than m) or
+        the first moves (batch, m) with stages = 1.  volts = (coeff_a, coeff_b, unit_change), needed with uv."""
+        import torch
+        batch = x0.shape[0]
+        if stages is None:
+            stages = 1 if u.shape[-1] == self.m else self.T
+        if ldu is None:
+            ldu = u.stride(0) if u.dim() == 2 else self.m
+        if stage_stride is None:
+            stage_stride = self.n + self.m
+        stages, ldu, stage_stride = int(stages), int(ldu), int(stage_stride)
+        for t, cols, name in ((x0, self.n, "x0"), (x0_pre, self.n, "x0_pre"), (w, self.T * self.n, "w"), (u1, self.m, "u1"),
+                              (Xp, stages * self.n, "Xp"), (xerr, stages, "xerr"), (J, 1, "J"), (du, self.m, "du"), (uv, self.m, "uv")):
+            if t is None:
+                continue
+            if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != batch * cols:
+                raise FastMPCError(_lib.FMPC_E_DIM, f"{name}: need a contiguous float64 HIP tensor of {(batch, cols)}")
+        if not u.is_cuda or u.dtype != torch.float64 or (u.dim() == 2 and u.stride(1) != 1) or u.dim() > 2:
+            raise FastMPCError(_lib.FMPC_E_DIM, "u: need a float64 HIP tensor with unit stride along its rows")
+        if batch > 0 and (ldu < 0 or stage_stride < 0 or stages < 1
+                          or u.storage_offset() + (batch - 1) * ldu + (stages - 1) * stage_stride + self.m > u.untyped_storage().nbytes() // 8):
+            raise FastMPCError(_lib.FMPC_E_DIM, "u: batch rows of (stages - 1) * stage_stride + m doubles, ldu apart, do not fit the tensor")
+        if uv is not None and volts is None:
+            raise FastMPCError(_lib.FMPC_E_NULL, "uv needs volts = (coeff_a, coeff_b, unit_change)")
+        ca, cb, uc = (1.0, 0.0, 1.0) if volts is None else (float(v) for v in volts)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)
+        rc = self._lib.fmpc_loop_records_device(self._h, batch, stages, p(x0), p(x0_pre), p(w), p(u), ldu, stage_stride, p(u1),
+                                                ca, cb, uc, p(Xp), p(xerr), p(J), p(du), p(uv), stream)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_loop_records_device")
+
+    def loop_records_run_device(self, X0, U0, x0_before=None, u_before1=None, u_before2=None, volts=None,
+                                Xp0=None, xerr0=None, dU=None, Uv=None):
+        """fmpc_loop_records_run_device: the stages = 1 records of every step of a recorded stretch in one launch.  X0 (steps, batch, n),
+        U0 (steps, batch, m) as `ClosedLoop.run_recorded` returns them; x0_before (batch, n), u_before1 / u_before2 (batch, m): the state
+        before the stretch (None: zeros).  Outputs Xp0 (steps, batch, n), xerr0 (steps, batch), dU, Uv (steps, batch, m); None: not produced."""
+        import torch
+        steps, batch = X0.shape[0], X0.shape[1]
+        for t, cnt, name in ((X0, steps * batch * self.n, "X0"), (U0, steps * batch * self.m, "U0"), (x0_before, batch * self.n, "x0_before"),
+                             (u_before1, batch * self.m, "u_before1"), (u_before2, batch * self.m, "u_before2"),
+                             (Xp0, steps * batch * self.n, "Xp0"), (xerr0, steps * batch, "xerr0"), (dU, steps * batch * self.m, "dU"),
+                             (Uv, steps * batch * self.m, "Uv")):
+            if t is None:
+                continue
+            if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != cnt:
+                raise FastMPCError(_lib.FMPC_E_DIM, f"{name}: need a contiguous float64 HIP tensor of {cnt} entries")
+        if Uv is not None and volts is None:
+            raise FastMPCError(_lib.FMPC_E_NULL, "Uv needs volts = (coeff_a, coeff_b, unit_change)")
+        ca, cb, uc = (1.0, 0.0, 1.0) if volts is None else (float(v) for v in volts)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(X0.device).cuda_stream)
+        rc = self._lib.fmpc_loop_records_run_device(self._h, batch, steps, p(X0), p(U0), p(x0_before), p(u_before1), p(u_before2),
+                                                    ca, cb, uc, p(Xp0), p(xerr0), p(dU), p(Uv), stream)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_loop_records_run_device")
+
     # ------------------------------------------------------------------ model bank
     def set_model_bank(self, A1, A2=None):
         """fmpc_bank_set_device: one VAR model per problem.  A1, A2: (count, n, n) float64 HIP tensors, A[b, i, j] = A_b(i, j)
