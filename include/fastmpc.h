@@ -433,8 +433,9 @@ int fmpc_var_validate_device(int n, int order, int first, int count, int num_sam
  * bank as it was.  The bank calls of a handle on different streams are ordered on the device like its solves.
  * fmpc_bank_release frees the bank's memory; it synchronises the device first (a bank solve in flight reads the images), so it must
  * not be called while a stream is being captured -- as fmpc_destroy must not.
- * Every other entry point but fmpc_loop_step_bank_device / fmpc_loop_run_bank_device ignores the bank: fmpc_solve*, the other
- * fmpc_loop_*, fmpc_ao_step_device answer from the fmpc_create model.
+ * Every other entry point but fmpc_loop_step_bank_device / fmpc_loop_run_bank_device / fmpc_loop_records_bank_device /
+ * fmpc_loop_records_run_bank_device ignores the bank: fmpc_solve*, the other fmpc_loop_* (fmpc_loop_records_device and
+ * fmpc_loop_records_run_device among them), fmpc_ao_step_device answer from the fmpc_create model.
  */
 int fmpc_bank_set_device(fmpc_handle h, int count, const double* A1, const double* A2, void* stream);
 int fmpc_bank_count(fmpc_handle h);          /* 0 = no bank (also for a NULL handle) */
@@ -469,6 +470,47 @@ int fmpc_solve_bank_device(fmpc_handle h, int batch, const int* model_of,
 int fmpc_loop_inputs_bank_device(fmpc_handle h, int batch, const int* model_of,
                                  const double* a_k, const double* x0_last, const double* u1,
                                  const double* u2, double* x0, double* x0_pre, double* w, void* stream);
+
+/*
+ * fmpc_loop_records_device / fmpc_loop_records_run_device with the bank's models: the same outputs, layouts, nullable arguments
+ * and argument rules (FMPC_E_DIM, FMPC_E_NULL, FMPC_OK with nothing enqueued when every output is NULL or batch == 0; each
+ * decided before the device is touched), where the prediction of problem p uses model model_of[p] (device int array; NULL = model
+ * p, then batch <= count, else FMPC_E_UNSUPPORTED):
+ *     f_i = M1_i x0 + M2_i x0_pre + w_i   computed as that model's free response  p_i = A1 p_{i-1} + A2 p_{i-2}  from p_-1 = x0,
+ *     p_-2 = x0_pre,  f_i = p_i + w_i  -- exactly how fmpc_loop_inputs_bank_device defines w; no M1, M2 are stored per model
+ *     Xp0[s] = A1_p (X0[s] - B u[s-1]) + A2_p (x0_pre[s] - B u[s-2]) + B U0[s]      (the stretch form)
+ * B, Q, Qf, R stay the handle's.  A1, A2 are read from the bank's fp64 images, which exist whatever arithmetic the bank was built
+ * for: an fp64 bank and an fp32-factor bank give the same bits.  A VAR(1) handle's bank has no A2.
+ * A problem whose index is outside [0, count) is left alone: none of its outputs is written and nothing of a model is read for
+ * it; the other problems are unaffected.  FMPC_E_UNSUPPORTED without a bank.
+ * n <= 32 with diagonal Q, Qf, R: one wavefront per problem walks the chain (its half rows of A1, A2 in registers) into a
+ * workspace of stages * n doubles per problem, then the panel kernel of the shared-model call finishes the stages on the matrix
+ * cores from there; the stretch form is one launch, (problem, 16 steps) per item with the model's A1, A2 as the matrix cores'
+ * A operands.  Any other size where a bank exists, or dense weights: one workgroup per problem, no speed claim.  No atomics:
+ * two calls give the same bits, and a call that asks for one output gives that output's bits.
+ * The calls take the handle's lock and are ordered on the device with the other bank calls.  They do not synchronise, and once
+ * the records weights, the cost scratch and the workspace exist (one call of the same batch and stages) they allocate nothing:
+ * both can be recorded into a HIP graph; FMPC_E_ALLOC under capture otherwise.
+ * WHEN TO USE IT: whenever the loop runs on a bank -- the shared-model calls would predict with the fmpc_create model.
+ * Measured at (27, 144, 30) with one model per realisation (scripts/loop_records_bank_timing.py, one MI355X): the full call (all
+ * stages, all five outputs, u = z) takes 0.050 ms at 256 realisations and 0.077 ms at 2048 -- 1.35 x / 1.20 x the shared-model
+ * call on the same inputs, 3.2 x / 10.3 x faster than the same records from torch.bmm on a stack of per-model M1, M2 (350 KB per
+ * model), and 0.088 / 0.040 of the bank loop step that produced z.  A stretch of 64 steps: 0.051 ms / 0.332 ms (1.02 x / 1.12 x the
+ * shared-model stretch, 3.0 x / 2.5 x faster than torch.bmm with [A1 | A2]).
+ */
+int fmpc_loop_records_bank_device(fmpc_handle h, int batch, const int* model_of, int stages,
+                                  const double* x0, const double* x0_pre, const double* w,
+                                  const double* u, long long ldu, int stage_stride,
+                                  const double* u1,
+                                  double coeff_a, double coeff_b, double unit_change,
+                                  double* Xp, double* xerr, double* J, double* du, double* uv,
+                                  void* stream);
+int fmpc_loop_records_run_bank_device(fmpc_handle h, int batch, int steps, const int* model_of,
+                                      const double* X0, const double* U0,
+                                      const double* x0_before, const double* u_before1, const double* u_before2,
+                                      double coeff_a, double coeff_b, double unit_change,
+                                      double* Xp0, double* xerr0, double* dU, double* Uv,
+                                      void* stream);
 
 /*
  * Stored cold-start factor per model of the bank.  The reference's loop calls the solver from the cold start at every timestep

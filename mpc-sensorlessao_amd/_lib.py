@@ -86,6 +86,8 @@ SIGNATURES = {
     "fmpc_bank_release": (C.c_int, [_vp]),
     "fmpc_solve_bank_device": (C.c_int, [_vp, C.c_int, _vp] + [_vp] * 5 + [C.c_int, C.c_double] + [_vp] * 6 + [_vp]),
     "fmpc_loop_inputs_bank_device": (C.c_int, [_vp, C.c_int, _vp] + [_vp] * 7 + [_vp]),
+    "fmpc_loop_records_bank_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int] + [_vp] * 4 + [C.c_longlong, C.c_int, _vp] + [C.c_double] * 3 + [_vp] * 5 + [_vp]),
+    "fmpc_loop_records_run_bank_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp] + [_vp] * 5 + [C.c_double] * 3 + [_vp] * 4 + [_vp]),
     "fmpc_bank_prefactor_device": (C.c_int, [_vp, C.c_double, _vp]),
     "fmpc_bank_prefactor_count": (C.c_int, [_vp]),
     "fmpc_bank_prefactor_release": (C.c_int, [_vp]),

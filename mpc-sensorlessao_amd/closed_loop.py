@@ -110,30 +110,31 @@ class ClosedLoop:
 
     def records(self, rec):
         """The records of the step just done (README.md:576-622) through `rec` (a `LoopRecords`): the full horizon and J from z with
-        keep_z, stage 0 from the newest first move without.  Returns rec.step's dict of views."""
-        if self.bank:
-            raise ValueError("records: the model bank has no records form (M1, M2 are the handle's)")
+        keep_z, stage 0 from the newest first move without; on the bank, with this loop's model_of.  Returns rec.step's dict of views."""
         if self.steps_done < 1:
             raise ValueError("records: no step has been done")
         s = self.steps_done - 1
         u1 = self.u[(s - 1) % 3] if s >= 1 else None
+        # (a bank loop predicts with its own model_of: fmpc_loop_records_bank_device)
+        step = (lambda *a, **kw: rec.step_bank(*a, model_of=self.model_of, **kw)) if self.bank else rec.step
         if self.z is not None:
-            return rec.step(self.x0, self.x0_pre, self.w, u1, z=self.z)
-        return rec.step(self.x0, self.x0_pre, self.w, u1, u0=self.u[s % 3])
+            return step(self.x0, self.x0_pre, self.w, u1, z=self.z)
+        return step(self.x0, self.x0_pre, self.w, u1, u0=self.u[s % 3])
 
     def run_recorded(self, a, nu0=None, want_x0=True, records=None):
         """The whole stretch a (steps, batch, n) in ONE C call (fmpc_loop_run_device): first moves only, fed back on the device.
         Continues from this object's state.  Returns (U0 (steps, batch, m), X0 (steps, batch, n) or None).
         records (a `LoopRecords`): the stage-0 records of every step of the stretch as well, in one more launch
-        (`LoopRecords.stretch` on U0, X0 and the ring state from before the stretch); returns (U0, X0, dict of records)."""
+        (`LoopRecords.stretch` on U0, X0 and the ring state from before the stretch, with the loop's model_of when it runs on
+        the bank); returns (U0, X0, dict of records)."""
         if records is not None:
-            if self.bank or not want_x0:
-                raise ValueError("run_recorded: records need X0 and have no model-bank form")
+            if not want_x0:
+                raise ValueError("run_recorded: records need X0")
             s0 = self.steps_done
             before = (self.x0.clone() if s0 >= 1 else None, self.u[(s0 - 1) % 3].clone() if s0 >= 1 else None,
                       self.u[(s0 - 2) % 3].clone() if s0 >= 2 else None)
             U0, X0 = self.run_recorded(a, nu0, True)
-            return U0, X0, records.stretch(X0, U0, *before)
+            return U0, X0, records.stretch(X0, U0, *before, model_of=self.model_of, bank=self.bank)
         torch, C = self._torch, self._C
         if not self.bank and (self.ramp or not self.fused):
             raise ValueError("run_recorded: the fused step without ramp rows only")

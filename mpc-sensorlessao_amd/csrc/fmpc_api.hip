@@ -48,6 +48,8 @@ hipError_t fmpc_launch_loop_inputs(int n, int m, int T, int batch, const double*
                                    double* x0, double* x0_pre, double* w, hipStream_t stream, double* lv = nullptr);
 // closed-loop records (fmpc_kernel_records.hip)
 hipError_t fmpc_launch_loop_records(const RecParams& P, int panel, hipStream_t stream);
+// ... with the model bank (fmpc_kernel_records_bank.hip)
+hipError_t fmpc_launch_loop_records_bank(const RecBankParams& K, int panel, hipStream_t stream);
 
 // one-wave-per-problem MFMA kernel (fmpc_kernel_wave.hip)
 size_t fmpc_wave_lds_bytes(int n, int mp);
@@ -205,6 +207,7 @@ struct fmpc_handle_s {
     // (rec_panel: the padded diagonals of the panel kernel; else dense), and the per-stage partial costs of the last call
     DevBuf<double> rec_w; int rec_ready = 0, rec_panel = 0; size_t rec_oQf = 0, rec_oR = 0;
     DevBuf<double> rec_j;
+    DevBuf<double> rec_f;                 // the bank's records (fmpc_loop_records_bank_device): f_i of the last call, stages x n per problem
     // staging for the host-pointer entry points
     DevBuf<char> stage;
     PinnedBuf<char> pin; void* pin_dev = nullptr;   // pinned host twin of the staging block for small host-pointer solves (fmpc_solve_host)
@@ -2891,12 +2894,13 @@ static int fmpc_records_launch(fmpc_handle h, RecParams& P, hipStream_t stream) 
     return ok ? FMPC_OK : FMPC_E_HIP;
 }
 
-// The records of a timestep (README.md:576-622; see include/fastmpc.h).  Every argument rule answers before the device is touched.
-extern "C" int fmpc_loop_records_device(fmpc_handle h, int batch, int stages,
-                                        const double* x0, const double* x0_pre, const double* w,
-                                        const double* u, long long ldu, int stage_stride, const double* u1,
-                                        double coeff_a, double coeff_b, double unit_change,
-                                        double* Xp, double* xerr, double* J, double* du, double* uv, void* stream) {
+// The argument rules and the parameter block of the records of a timestep, for the shared-model call and the bank's: every rule
+// answers before the device is touched.  *todo = 0 with FMPC_OK: nothing to enqueue.
+static int fmpc_records_step_args(fmpc_handle h, int batch, int stages, const double* x0, const double* x0_pre, const double* w,
+                                  const double* u, long long ldu, int stage_stride, const double* u1,
+                                  double coeff_a, double coeff_b, double unit_change,
+                                  double* Xp, double* xerr, double* J, double* du, double* uv, RecParams& P, int* todo) {
+    *todo = 0;
     if (uv && (!(coeff_a > 0.0) || !isfinite(coeff_a) || !isfinite(coeff_b) || !isfinite(unit_change))) return FMPC_E_DIM;
     if (batch < 0 || stages < 1) return FMPC_E_DIM;
     if (!h || !x0 || !u) return FMPC_E_NULL;
@@ -2904,14 +2908,46 @@ extern "C" int fmpc_loop_records_device(fmpc_handle h, int batch, int stages,
     if (stages > 1 && stage_stride < h->m) return FMPC_E_DIM;
     if (ldu < (long long)(stages - 1) * (stages > 1 ? stage_stride : 0) + h->m) return FMPC_E_DIM;
     if ((!Xp && !xerr && !J && !du && !uv) || batch == 0) return FMPC_OK;
-    RecParams P;
     memset(&P, 0, sizeof(P));
     P.batch = batch; P.steps = 0;
     P.stages = (Xp || xerr || J) ? stages : 1;                        // (du and uv are the first move's)
     P.x0 = x0; P.x0_pre = x0_pre; P.w = w; P.u = u; P.ldu = ldu; P.stage_stride = stages > 1 ? stage_stride : 0; P.u1 = u1;
     P.ca = coeff_a; P.cb = coeff_b; P.uc = unit_change;
     P.Xp = Xp; P.xerr = xerr; P.J = J; P.du = du; P.uv = uv;
-    return fmpc_records_launch(h, P, (hipStream_t)stream);
+    *todo = 1;
+    return FMPC_OK;
+}
+// ... of the stage-0 records of a recorded stretch
+static int fmpc_records_run_args(fmpc_handle h, int batch, int steps, const double* X0, const double* U0,
+                                 const double* x0_before, const double* u_before1, const double* u_before2,
+                                 double coeff_a, double coeff_b, double unit_change,
+                                 double* Xp0, double* xerr0, double* dU, double* Uv, RecParams& P, int* todo) {
+    *todo = 0;
+    if (Uv && (!(coeff_a > 0.0) || !isfinite(coeff_a) || !isfinite(coeff_b) || !isfinite(unit_change))) return FMPC_E_DIM;
+    if (batch < 0 || steps < 0) return FMPC_E_DIM;
+    if (!h || !X0 || !U0) return FMPC_E_NULL;
+    if ((!Xp0 && !xerr0 && !dU && !Uv) || batch == 0 || steps == 0) return FMPC_OK;
+    if (steps > 65535) return FMPC_E_DIM;                              // (a grid dimension of the any-size kernel)
+    memset(&P, 0, sizeof(P));
+    P.batch = batch; P.steps = steps; P.stages = 1;
+    P.x0 = X0; P.u = U0; P.ldu = h->m; P.x0_before = x0_before; P.u_before1 = u_before1; P.u_before2 = u_before2;
+    P.ca = coeff_a; P.cb = coeff_b; P.uc = unit_change;
+    P.Xp = Xp0; P.xerr = xerr0; P.du = dU; P.uv = Uv;
+    *todo = 1;
+    return FMPC_OK;
+}
+
+// The records of a timestep (README.md:576-622; see include/fastmpc.h).
+extern "C" int fmpc_loop_records_device(fmpc_handle h, int batch, int stages,
+                                        const double* x0, const double* x0_pre, const double* w,
+                                        const double* u, long long ldu, int stage_stride, const double* u1,
+                                        double coeff_a, double coeff_b, double unit_change,
+                                        double* Xp, double* xerr, double* J, double* du, double* uv, void* stream) {
+    RecParams P;
+    int todo;
+    const int rc = fmpc_records_step_args(h, batch, stages, x0, x0_pre, w, u, ldu, stage_stride, u1, coeff_a, coeff_b, unit_change,
+                                          Xp, xerr, J, du, uv, P, &todo);
+    return todo ? fmpc_records_launch(h, P, (hipStream_t)stream) : rc;
 }
 
 // The stage-0 records of every step of a recorded stretch in one launch (see include/fastmpc.h).
@@ -2919,18 +2955,61 @@ extern "C" int fmpc_loop_records_run_device(fmpc_handle h, int batch, int steps,
                                             const double* x0_before, const double* u_before1, const double* u_before2,
                                             double coeff_a, double coeff_b, double unit_change,
                                             double* Xp0, double* xerr0, double* dU, double* Uv, void* stream) {
-    if (Uv && (!(coeff_a > 0.0) || !isfinite(coeff_a) || !isfinite(coeff_b) || !isfinite(unit_change))) return FMPC_E_DIM;
-    if (batch < 0 || steps < 0) return FMPC_E_DIM;
-    if (!h || !X0 || !U0) return FMPC_E_NULL;
-    if ((!Xp0 && !xerr0 && !dU && !Uv) || batch == 0 || steps == 0) return FMPC_OK;
-    if (steps > 65535) return FMPC_E_DIM;                              // (a grid dimension of the any-size kernel)
     RecParams P;
-    memset(&P, 0, sizeof(P));
-    P.batch = batch; P.steps = steps; P.stages = 1;
-    P.x0 = X0; P.u = U0; P.ldu = h->m; P.x0_before = x0_before; P.u_before1 = u_before1; P.u_before2 = u_before2;
-    P.ca = coeff_a; P.cb = coeff_b; P.uc = unit_change;
-    P.Xp = Xp0; P.xerr = xerr0; P.du = dU; P.uv = Uv;
-    return fmpc_records_launch(h, P, (hipStream_t)stream);
+    int todo;
+    const int rc = fmpc_records_run_args(h, batch, steps, X0, U0, x0_before, u_before1, u_before2, coeff_a, coeff_b, unit_change,
+                                         Xp0, xerr0, dU, Uv, P, &todo);
+    return todo ? fmpc_records_launch(h, P, (hipStream_t)stream) : rc;
+}
+
+// The records with the model of each problem (fmpc_kernel_records_bank.hip): the prediction is the free response of model
+// model_of[p] through the bank's fp64 plain images, whatever arithmetic the bank was built for.  Ordered on the device with the
+// bank calls (fmpc_bank_set_device rewrites the images in place).
+static int fmpc_records_bank_launch(fmpc_handle h, RecBankParams& K, const int* model_of, hipStream_t stream) {
+    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    std::lock_guard<std::mutex> lock(h->mu);
+    const fmpc_handle_s::Bank& B = h->bank;
+    RecParams& P = K.R;
+    if (B.count <= 0 || (!model_of && P.batch > B.count)) return FMPC_E_UNSUPPORTED;
+    int rc = fmpc_guard_begin(h, stream);
+    if (rc != FMPC_OK) return rc;
+    rc = fmpc_ensure_records(h, stream);
+    if (rc == FMPC_OK && P.J && h->rec_panel) rc = h->rec_j.grow((size_t)P.stages * P.batch, stream);
+    if (rc == FMPC_OK && h->rec_panel && P.steps == 0) rc = h->rec_f.grow((size_t)P.stages * P.batch * h->n, stream);
+    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
+    P.n = h->n; P.m = h->m; P.T = h->T;
+    P.Bt = h->dev.Bt;
+    P.Q = h->rec_w; P.Qf = h->rec_w + h->rec_oQf; P.R = h->rec_w + h->rec_oR;
+    P.jpart = (P.J && h->rec_panel) ? (double*)h->rec_j : nullptr;
+    K.plain = B.plain; K.plain_stride = B.plain_stride; K.count = B.count; K.var2 = h->var_order == 2;
+    K.model_of = model_of;
+    K.F = (h->rec_panel && P.steps == 0) ? (double*)h->rec_f : nullptr;
+    const bool ok = fmpc_launch_loop_records_bank(K, h->rec_panel, stream) == hipSuccess;
+    fmpc_guard_end(h, stream);
+    return ok ? FMPC_OK : FMPC_E_HIP;
+}
+
+extern "C" int fmpc_loop_records_bank_device(fmpc_handle h, int batch, const int* model_of, int stages,
+                                             const double* x0, const double* x0_pre, const double* w,
+                                             const double* u, long long ldu, int stage_stride, const double* u1,
+                                             double coeff_a, double coeff_b, double unit_change,
+                                             double* Xp, double* xerr, double* J, double* du, double* uv, void* stream) {
+    RecBankParams K;
+    int todo;
+    const int rc = fmpc_records_step_args(h, batch, stages, x0, x0_pre, w, u, ldu, stage_stride, u1, coeff_a, coeff_b, unit_change,
+                                          Xp, xerr, J, du, uv, K.R, &todo);
+    return todo ? fmpc_records_bank_launch(h, K, model_of, (hipStream_t)stream) : rc;
+}
+
+extern "C" int fmpc_loop_records_run_bank_device(fmpc_handle h, int batch, int steps, const int* model_of, const double* X0,
+                                                 const double* U0, const double* x0_before, const double* u_before1,
+                                                 const double* u_before2, double coeff_a, double coeff_b, double unit_change,
+                                                 double* Xp0, double* xerr0, double* dU, double* Uv, void* stream) {
+    RecBankParams K;
+    int todo;
+    const int rc = fmpc_records_run_args(h, batch, steps, X0, U0, x0_before, u_before1, u_before2, coeff_a, coeff_b, unit_change,
+                                         Xp0, xerr0, dU, Uv, K.R, &todo);
+    return todo ? fmpc_records_bank_launch(h, K, model_of, (hipStream_t)stream) : rc;
 }
 
 hipError_t fmpc_launch_phase_residual(int batch, size_t npx, int n, int m, const double* Bt, const double* phase, const double* u,

@@ -1,5 +1,5 @@
-// Closed-loop records (fmpc_loop_records_device / fmpc_loop_records_run_device in include/fastmpc.h): the argument block shared by
-// fmpc_api.hip and fmpc_kernel_records.hip.
+// Closed-loop records (fmpc_loop_records_device / fmpc_loop_records_run_device and their model-bank forms in include/fastmpc.h):
+// the argument blocks shared by fmpc_api.hip, fmpc_kernel_records.hip and fmpc_kernel_records_bank.hip.
 #pragma once
 #include <stddef.h>
 #include <hip/hip_runtime.h>
@@ -23,4 +23,13 @@ struct RecParams {
     const double* x0_before; const double* u_before1; const double* u_before2;
     double ca, cb, uc;                               // the rad -> V conversion (README.md:577-583)
     double* Xp; double* xerr; double* jpart; double* J; double* du; double* uv;    // jpart: stages x batch partial costs (panel kernel)
+};
+
+// The model-bank forms (fmpc_kernel_records_bank.hip): R as above without M1, M2; problem p predicts with model model_of[p]
+struct RecBankParams {
+    RecParams R;
+    const double* plain; size_t plain_stride;       // FbParams::plain: per model A1 | A2 | A1' | A2' row-major n x n each, fp64
+    int count, var2;                                 // models of the bank; 0: VAR(1), no A2
+    const int* model_of;                             // NULL: model p
+    double* F;                                       // panel kernel, one timestep: the free response p_i, [batch][stages][n]
 };

@@ -345,6 +345,15 @@ class FastMPCHandle:
         produced).  x0, x0_pre (batch, n), w (batch, T n), u1 (batch, m): contiguous float64 HIP tensors, x0_pre / w / u1 may be
         None.  u: a solve's z (batch rows ldu apart, stage_stride = n + m, stages = T: the defaults for a 2-D tensor wider than m) or
         the first moves (batch, m) with stages = 1.  volts = (coeff_a, coeff_b, unit_change), needed with uv."""
+        self._loop_records(False, None, x0, x0_pre, w, u, u1, stages, ldu, stage_stride, volts, Xp, xerr, J, du, uv)
+
+    def loop_records_bank_device(self, x0, x0_pre, w, u, u1=None, stages=None, ldu=None, stage_stride=None, volts=None,
+                                 Xp=None, xerr=None, J=None, du=None, uv=None, model_of=None):
+        """fmpc_loop_records_bank_device: `loop_records_device` where problem p predicts with model model_of[p] of the bank (int32
+        HIP tensor; None: model p).  A problem whose index is outside the bank keeps its outputs as they were."""
+        self._loop_records(True, model_of, x0, x0_pre, w, u, u1, stages, ldu, stage_stride, volts, Xp, xerr, J, du, uv)
+
+    def _loop_records(self, bank, model_of, x0, x0_pre, w, u, u1, stages, ldu, stage_stride, volts, Xp, xerr, J, du, uv):
         import torch
         batch = x0.shape[0]
         if stages is None:
@@ -370,16 +379,36 @@ class FastMPCHandle:
         ca, cb, uc = (1.0, 0.0, 1.0) if volts is None else (float(v) for v in volts)
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         stream = C.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)
-        rc = self._lib.fmpc_loop_records_device(self._h, batch, stages, p(x0), p(x0_pre), p(w), p(u), ldu, stage_stride, p(u1),
-                                                ca, cb, uc, p(Xp), p(xerr), p(J), p(du), p(uv), stream)
+        if bank:
+            self._check_model_of(model_of, batch)
+            rc = self._lib.fmpc_loop_records_bank_device(self._h, batch, p(model_of), stages, p(x0), p(x0_pre), p(w), p(u), ldu, stage_stride,
+                                                         p(u1), ca, cb, uc, p(Xp), p(xerr), p(J), p(du), p(uv), stream)
+        else:
+            rc = self._lib.fmpc_loop_records_device(self._h, batch, stages, p(x0), p(x0_pre), p(w), p(u), ldu, stage_stride, p(u1),
+                                                    ca, cb, uc, p(Xp), p(xerr), p(J), p(du), p(uv), stream)
         if rc != _lib.FMPC_OK:
-            raise FastMPCError(rc, "fmpc_loop_records_device")
+            raise FastMPCError(rc, "fmpc_loop_records_bank_device" if bank else "fmpc_loop_records_device")
+
+    @staticmethod
+    def _check_model_of(model_of, batch):
+        import torch
+        if model_of is not None and not (model_of.is_cuda and model_of.dtype == torch.int32 and model_of.is_contiguous()
+                                         and model_of.numel() == batch):
+            raise FastMPCError(_lib.FMPC_E_DIM, "model_of: need a contiguous int32 HIP tensor of (batch,)")
 
     def loop_records_run_device(self, X0, U0, x0_before=None, u_before1=None, u_before2=None, volts=None,
                                 Xp0=None, xerr0=None, dU=None, Uv=None):
         """fmpc_loop_records_run_device: the stages = 1 records of every step of a recorded stretch in one launch.  X0 (steps, batch, n),
         U0 (steps, batch, m) as `ClosedLoop.run_recorded` returns them; x0_before (batch, n), u_before1 / u_before2 (batch, m): the state
         before the stretch (None: zeros).  Outputs Xp0 (steps, batch, n), xerr0 (steps, batch), dU, Uv (steps, batch, m); None: not produced."""
+        self._loop_records_run(False, None, X0, U0, x0_before, u_before1, u_before2, volts, Xp0, xerr0, dU, Uv)
+
+    def loop_records_run_bank_device(self, X0, U0, x0_before=None, u_before1=None, u_before2=None, volts=None,
+                                     Xp0=None, xerr0=None, dU=None, Uv=None, model_of=None):
+        """fmpc_loop_records_run_bank_device: `loop_records_run_device` with A1, A2 of the bank's model model_of[p] (None: model p)."""
+        self._loop_records_run(True, model_of, X0, U0, x0_before, u_before1, u_before2, volts, Xp0, xerr0, dU, Uv)
+
+    def _loop_records_run(self, bank, model_of, X0, U0, x0_before, u_before1, u_before2, volts, Xp0, xerr0, dU, Uv):
         import torch
         steps, batch = X0.shape[0], X0.shape[1]
         for t, cnt, name in ((X0, steps * batch * self.n, "X0"), (U0, steps * batch * self.m, "U0"), (x0_before, batch * self.n, "x0_before"),
@@ -395,10 +424,15 @@ class FastMPCHandle:
         ca, cb, uc = (1.0, 0.0, 1.0) if volts is None else (float(v) for v in volts)
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         stream = C.c_void_p(torch.cuda.current_stream(X0.device).cuda_stream)
-        rc = self._lib.fmpc_loop_records_run_device(self._h, batch, steps, p(X0), p(U0), p(x0_before), p(u_before1), p(u_before2),
-                                                    ca, cb, uc, p(Xp0), p(xerr0), p(dU), p(Uv), stream)
+        if bank:
+            self._check_model_of(model_of, batch)
+            rc = self._lib.fmpc_loop_records_run_bank_device(self._h, batch, steps, p(model_of), p(X0), p(U0), p(x0_before), p(u_before1),
+                                                             p(u_before2), ca, cb, uc, p(Xp0), p(xerr0), p(dU), p(Uv), stream)
+        else:
+            rc = self._lib.fmpc_loop_records_run_device(self._h, batch, steps, p(X0), p(U0), p(x0_before), p(u_before1), p(u_before2),
+                                                        ca, cb, uc, p(Xp0), p(xerr0), p(dU), p(Uv), stream)
         if rc != _lib.FMPC_OK:
-            raise FastMPCError(rc, "fmpc_loop_records_run_device")
+            raise FastMPCError(rc, "fmpc_loop_records_run_bank_device" if bank else "fmpc_loop_records_run_device")
 
     # ------------------------------------------------------------------ model bank
     def set_model_bank(self, A1, A2=None):
