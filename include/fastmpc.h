@@ -755,6 +755,10 @@ int fmpc_ao_step_device(fmpc_handle h, int batch, const double* x0, const double
  *                   range_min + 1 <= 32.   ndiv <= 3 diversities;  D_re, D_im: ndiv arrays len x len (column-major, MATLAB
  *                   order) = real / imaginary part of pupil.*exp(1i*zd_list(k)*squeeze(Zs(idx2,:,:))).   scale = dx^4*AU.
  *                   A_s: p x nx column-major, b_s: p, p = ndiv d^2 (model_approx.mat of the reference, piston removed).
+ *                   nx is bounded by what one workgroup of the finish kernel serves: nx <= 1024 and
+ *                   (d^2 rounded up to even + 16 nx) * 8 bytes <= 64 KiB, i.e. nx <= 511 for d = 1 and nx <= 448 for d = 32
+ *                   (the reference: 27).  Beyond that FMPC_E_UNSUPPORTED, found before the device is touched (argument
+ *                   errors -- FMPC_E_NULL, FMPC_E_DIM -- come first).
  * fmpc_est_apply[_device]   scrn: batch arrays len x len column-major [rad], |scrn| < 1e6 (a pixel beyond that, or a
  *                   non-finite one, makes that screen's outputs NaN: the kernel reduces the phase by pi/2 itself); noise: batch x p or NULL (Y_M_noise);
  *                   ad_est: batch x nx;  Y_out: batch x p or NULL (Y_M, for Y_M_acc of the reference).

@@ -27,6 +27,7 @@ extern "C" int fmpc_est_create(fmpc_est* out, int len, int first, int d, int ndi
     *out = nullptr;
     if (len < 64 || len % 64 != 0 || d < 1 || d > 32 || first < 0 || first + d > len || ndiv < 1 || ndiv > FE_MAXDIV || nx < 1 ||
         p != ndiv * d * d) return FMPC_E_DIM;
+    if (!fe_finish_serves(d, nx)) return FMPC_E_UNSUPPORTED;         // (before the device is touched and the gain is computed)
     if (hipSetDevice(device) != hipSuccess) return FMPC_E_HIP;
     fmpc_est_s* e = new (std::nothrow) fmpc_est_s();
     if (!e) return FMPC_E_ALLOC;
@@ -92,8 +93,11 @@ extern "C" int fmpc_est_apply_device(fmpc_est e, int batch, const double* scrn, 
         e->part_batch = 0;
         size_t cap = 1;
         while (cap < (size_t)batch) cap *= 2;
-        // (few screens: the PSF kernel may split the columns of a row block over two workgroups -- room for 4 screens x 128 partial windows per diversity)
-        const size_t pw = cap * e->ndiv * (e->len / 16) < (size_t)4 * e->ndiv * 128 ? (size_t)4 * e->ndiv * 128 : cap * e->ndiv * (e->len / 16);
+        // (few screens: the PSF kernel may split the columns of a row block over two workgroups -- room for the FE_SPLIT_MAX
+        //  (screen, diversity) pairs of that shape at 128 partial windows each, whatever ndiv: 4 ndiv x 128 was too little for
+        //  9 to 12 screens of ONE diversity, which then ran without the split)
+        const size_t pw_split = (size_t)FE_SPLIT_MAX * 128;
+        const size_t pw = cap * e->ndiv * (e->len / 16) < pw_split ? pw_split : cap * e->ndiv * (e->len / 16);
         if (e->part.alloc(pw * 2048, (hipStream_t)stream) != FMPC_OK ||
             e->shares.alloc(cap * e->ndiv * 4 * e->nx, (hipStream_t)stream) != FMPC_OK) return FMPC_E_ALLOC;
         e->part_batch = cap;

@@ -20,4 +20,19 @@ struct FeParams {
     double* ad_est; double* Yout;       // [batch][nx], [batch][p] or NULL
 };
 
+#define FE_SPLIT_MAX 12                 // (screens x diversities) up to which the PSF kernel splits the columns of a row block in two
+
+// What the general finish kernel (fmpc_est_finish) needs of a mode count nx: its FE_FINISH_THREADS threads write one entry of the
+// share each (thread j < nx), and its dynamic LDS -- d^2 measurements (padded to even) + nx x 16 partial sums -- has to fit the
+// 64 KiB a workgroup gets without opting in to more (the kernel does not).  fmpc_est_create refuses what fmpc_launch_estimator
+// could not launch: both ask here.
+#define FE_FINISH_THREADS 1024
+#define FE_FINISH_LDS_LIMIT ((size_t)64 * 1024)
+static inline size_t fe_finish_lds_bytes(int d, int nx) {
+    return ((((size_t)d * d + 1) & ~(size_t)1) + (size_t)nx * 16) * sizeof(double);
+}
+static inline bool fe_finish_serves(int d, int nx) {
+    return nx >= 1 && nx <= FE_FINISH_THREADS && fe_finish_lds_bytes(d, nx) <= FE_FINISH_LDS_LIMIT;
+}
+
 hipError_t fmpc_launch_estimator(const FeParams& P, hipStream_t stream);

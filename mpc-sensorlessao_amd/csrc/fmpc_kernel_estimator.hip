@@ -171,7 +171,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) fmpc_est_psf(FeParam
     }
 }
 
-__global__ void __launch_bounds__(1024) fmpc_est_finish(FeParams P) {
+__global__ void __launch_bounds__(FE_FINISH_THREADS) fmpc_est_finish(FeParams P) {
     extern __shared__ double sY[];                           // d^2 measurements of this diversity minus b_s, then nx x 16 partial sums
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int r = blockIdx.x, k = blockIdx.y, d = P.d, nblk = P.len / 16, dd = d * d, p = P.ndiv * dd;
@@ -213,7 +213,7 @@ __global__ void __launch_bounds__(1024) fmpc_est_finish(FeParams P) {
         double acc[FE_ROWB];
 #pragma unroll
         for (int jj = 0; jj < FE_ROWB; ++jj) acc[jj] = 0.0;
-        for (int i = tid; i < dd; i += 1024) {
+        for (int i = tid; i < dd; i += FE_FINISH_THREADS) {
             const double yv = sY[i];
             double gv[FE_ROWB];
 #pragma unroll
@@ -304,6 +304,7 @@ __global__ void __launch_bounds__(256) fmpc_est_combine(FeParams P) {
 
 hipError_t fmpc_launch_estimator(const FeParams& P, hipStream_t stream) {
     if (P.len % 64 != 0 || P.len < 64 || P.d < 1 || P.d > 32 || P.ndiv < 1 || P.ndiv > FE_MAXDIV) return hipErrorInvalidValue;
+    if (!fe_finish_serves(P.d, P.nx)) return hipErrorInvalidValue;      // (fmpc_est_create refuses such a handle)
     // few screens: 8 wavefronts per workgroup so that a lone screen is 256 wavefronts, not 128
     const bool wide = (size_t)P.batch * (P.len / 16) < 512 && P.len % 128 == 0;
     // very few screens of the reference's size: the columns of a row block split over two workgroups as well (a lone screen is
@@ -311,7 +312,7 @@ hipError_t fmpc_launch_estimator(const FeParams& P, hipStream_t stream) {
     int csplit = 1;
     if (P.len == 512 && P.nx <= 27 && P.shares_cap >= (size_t)P.batch * P.ndiv * FE_FQ * P.nx) {
         // (a split of four for ONE screen -- 128 workgroups, four round trips in the finish pass -- measured no faster: 39.6 against 38.1 us)
-        if ((size_t)P.batch * P.ndiv <= 12 && P.part_cap >= (size_t)P.batch * P.ndiv * 64 * 2048) csplit = 2;
+        if ((size_t)P.batch * P.ndiv <= FE_SPLIT_MAX && P.part_cap >= (size_t)P.batch * P.ndiv * 64 * 2048) csplit = 2;
     }
     if (wide) {
         static bool prepared = false;
@@ -331,8 +332,7 @@ hipError_t fmpc_launch_estimator(const FeParams& P, hipStream_t stream) {
         else hipLaunchKernelGGL(fmpc_est_finish_few<1>, dim3(P.batch, P.ndiv, FE_FQ), dim3(256), 0, stream, Q);
     } else {
         Q.nshare = 1;
-        const size_t lds = ((((size_t)P.d * P.d + 1) & ~(size_t)1) + (size_t)P.nx * 16) * sizeof(double);
-        hipLaunchKernelGGL(fmpc_est_finish, dim3(P.batch, P.ndiv), dim3(1024), lds, stream, Q);
+        hipLaunchKernelGGL(fmpc_est_finish, dim3(P.batch, P.ndiv), dim3(FE_FINISH_THREADS), fe_finish_lds_bytes(P.d, P.nx), stream, Q);
     }
     hipLaunchKernelGGL(fmpc_est_combine, dim3((P.batch * P.nx + 255) / 256), dim3(256), 0, stream, Q);
     return hipGetLastError();

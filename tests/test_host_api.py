@@ -95,6 +95,28 @@ def test_create_argument_checks(pkg):
     assert lib.fmpc_last_dispatch(None, None, None) == pkg.FMPC_E_NULL
 
 
+def test_estimator_create_refuses_a_mode_count_the_finish_kernel_cannot_serve(pkg):
+    """fmpc_est_create, include/fastmpc.h: nx <= 1024 (one thread of the finish kernel per mode) and (d^2 + 16 nx) * 8 bytes of LDS
+    <= 64 KiB -- FMPC_E_UNSUPPORTED before the device is touched (this box has none) and before the gain is computed (nx = 2000
+    would be minutes of Jacobi sweeps); argument errors come first."""
+    import time
+    lib = pkg.load()
+    h = C.c_void_p()
+    buf = np.zeros(64 * 64)
+    A = np.ones(2000)
+    p_, a_ = buf.ctypes.data_as(C.c_void_p), A.ctypes.data_as(C.c_void_p)
+    t0 = time.perf_counter()
+    for nx in (2000, 600):                             # d = 1, ndiv = 1, p = 1: 600 modes need 2 + 9600 doubles of LDS
+        h.value = 1
+        assert lib.fmpc_est_create(C.byref(h), 64, 32, 1, 1, p_, p_, 1.0, a_, p_, 1, nx, 0) == pkg.FMPC_E_UNSUPPORTED
+        assert not h.value                             # no handle comes back
+    assert time.perf_counter() - t0 < 1.0              # "at once": nothing was computed
+    assert lib.fmpc_est_create(C.byref(h), 64, 0, 32, 1, p_, p_, 1.0, a_, p_, 1024, 449, 0) == pkg.FMPC_E_UNSUPPORTED   # d = 32: 448 is the last
+    assert lib.fmpc_est_create(C.byref(h), 64, 32, 1, 1, None, p_, 1.0, a_, p_, 1, 2000, 0) == pkg.FMPC_E_NULL
+    assert lib.fmpc_est_create(None, 64, 32, 1, 1, p_, p_, 1.0, a_, p_, 1, 2000, 0) == pkg.FMPC_E_NULL
+    assert lib.fmpc_est_create(C.byref(h), 64, 32, 1, 1, p_, p_, 1.0, a_, p_, 2, 2000, 0) == pkg.FMPC_E_DIM               # p != ndiv d^2
+
+
 def test_fast_mpc2_validation_mirrors_reference_errors(pkg):
     md, data = pkg.synthetic.make_test_problem(8, 5, 10, seed=0)
     mk = lambda **kw: pkg.Fast_MPC2(kw.get("Q", md["Q"]), md["R"], [], md["Qf"], kw.get("q", []), [], [], md["x_min"],
