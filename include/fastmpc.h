@@ -699,6 +699,44 @@ int fmpc_set_dense_form(fmpc_handle h, int enabled, int max_batch_with_w);
 unsigned long long fmpc_alloc_generation(void);
 
 /*
+ * A stretch of cold-start steps in few launches.  Between fmpc_stretch_begin(stream) and fmpc_stretch_end(stream) a
+ * fmpc_solve_device / fmpc_solve_u0_device / fmpc_solve_u0_device_ld call on that stream that takes the affine form of the
+ * cold-start step (n = 27, w == NULL, z_init == NULL, n_newton == 1, the form valid for k) is QUEUED instead of launched, and
+ * consecutive queued calls form a chain that one launch of the product kernel + one launch of the exact path serve: the
+ * per-launch cost of a step (its start, two launch boundaries, about 40 % of a 2000-problem step) is paid once per chain.
+ * Every step computes exactly what its own launches compute (same tile schedule, same stores: z bit for bit).
+ *
+ * A queued call extends the pending chain when it has the same handle, k, batch and output signature (z wanted or not, ldz,
+ * 128-byte alignment of z, nu_out / u0_out / status / iters / step present or not, n_newton) as the chain, the chain has fewer
+ * than FMPC_STRETCH_MAX steps, none of its inputs (x0, x0_pre, nu0) overlaps an output of a pending step and none of its outputs
+ * an input of one, and each of its outputs is either disjoint from all outputs of the pending steps or ALL of them are identical
+ * (base, row distance, extent) to those of one pending step -- that step is then superseded: it is still computed, and this call's
+ * results replace it in program order.  Otherwise the pending chain is launched first and the call starts a new chain.  Any other
+ * call on that stream that takes a solver handle, a call that has to build constants or grow a workspace, fmpc_destroy of the
+ * chain's handle, fmpc_last_dispatch and fmpc_stretch_end launch the pending chain before anything else happens.  (The calls
+ * without a solver handle -- fmpc_var_*, fmpc_est_* -- know nothing of brackets: on a bracketed stream they are foreign work.)
+ *
+ * A handle's workspaces serve one solve at a time, inside a bracket as outside: a solve of the chain's handle on ANOTHER stream
+ * (bracketed or not) launches the pending chain on its own stream first and is ordered behind it through the handle's event, and a
+ * chain waits for a solve of its handle that another stream has enqueued since.  A bracket belongs to one host thread at a time.
+ *
+ * Contract: between begin and end ONLY library calls may be enqueued on the stream; the results of all calls are complete on
+ * the stream after fmpc_stretch_end.  The same holds with and without stream capture.  Under capture, work of anybody else on the
+ * capturing stream while a chain is pending is detected (the graph's node count has moved): the pending chain is dropped --
+ * nothing of it has been enqueued -- and the call that notices returns FMPC_E_UNSUPPORTED.  Outside a capture it cannot be detected.
+ * fmpc_stretch_begin on a stream with an open bracket and fmpc_stretch_end without one return FMPC_E_UNSUPPORTED.
+ *
+ * After a chain, fmpc_last_dispatch / fmpc_last_dual_form read as after a per-step call (handed_over: of the last step that
+ * was not superseded).  fmpc_last_stretch: the steps and launches of the chain of this handle that was launched last (0, 0 before
+ * the first).  Measured at (27, 144, 30), 2000 problems, recorded regions of 20 / 400 steps: 30.1 / 29.2 us of device time per
+ * step against 31.7 / 31.2 us with two launches per step (README.md).
+ */
+#define FMPC_STRETCH_MAX 16
+int fmpc_stretch_begin(void* stream);
+int fmpc_stretch_end(void* stream);
+int fmpc_last_stretch(fmpc_handle h, int* steps, int* launches);
+
+/*
  * Padded output rows for batches on the device: row p of z_out starts at z_out + p * ldz (ldz >= T (n + m); 0 restores the
  * contiguous rows).  A batch is this library's extension of the reference's one-problem call (Fast_MPC2.m:47-60), so the
  * distance between its rows is ours to offer: with ldz a multiple of 16 (128 bytes) and z_out 128-byte aligned every

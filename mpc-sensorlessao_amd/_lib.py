@@ -60,6 +60,9 @@ SIGNATURES = {
     "fmpc_set_small_batch_kernel": (C.c_int, [_vp, C.c_int]),
     "fmpc_set_z_ld": (C.c_int, [_vp, C.c_int]),
     "fmpc_alloc_generation": (C.c_ulonglong, []),
+    "fmpc_stretch_begin": (C.c_int, [_vp]),
+    "fmpc_stretch_end": (C.c_int, [_vp]),
+    "fmpc_last_stretch": (C.c_int, [_vp, _ip, _ip]),
     "fmpc_loop_inputs_device": (C.c_int, [_vp, C.c_int] + [_vp] * 7 + [_vp]),
     "fmpc_loop_step_device": (C.c_int, [_vp, C.c_int] + [_vp] * 8 + [C.c_int, C.c_double] + [_vp] * 6 + [_vp]),
     "fmpc_ao_step_device": (C.c_int, [_vp, C.c_int] + [_vp] * 6 + [C.c_int, C.c_double] + [_vp] * 6 + [_vp]),

@@ -2,6 +2,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "fmpc_host.h"
+#include "../../include/fastmpc.h"
+
+#define FA_N 27                         // states per stage: the only size the kernel is built for (the launcher rejects any other)
+
+// The per-step pointers of a chain of cold-start steps served by ONE launch (fmpc_stretch_begin / fmpc_stretch_end): everything else
+// of FaParams is the same for all steps of a chain.
+struct FaStep {
+    const double* x0; const double* x0p; const double* nu0;
+    double* zout; double* nuout; double* u0out; int* status; int* iters; double* step;
+    int* need;                          // the step's own flag list
+};
 
 struct FaParams {
     int n, m, T, nb, has_xf, batch, rows, tiles, step_ld;
@@ -19,6 +30,10 @@ struct FaParams {
     int* nflag;                         // += 1 per problem flagged in `need` (a running device counter, never reset: the exact-path launch behind
                                         // this kernel compares it with the count it has dealt with and leaves at once when they agree)
     double* dump;                       // 4096 doubles nobody reads: where lanes without a valid target store (no branch around a store)
+    // The kernel reads its per-step pointers from steps[0 .. nsteps).  nsteps = 0 on entry of the launcher: a single step, taken from
+    // the fields x0 .. need above.  All steps of a chain share batch, ldz, step_ld and which of the outputs are present.
+    int nsteps;
+    FaStep steps[FMPC_STRETCH_MAX];
 };
 
 hipError_t fmpc_launch_affine(FaParams P, int num_cu, hipStream_t stream);

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
+#include <map>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -61,6 +63,8 @@ size_t fmpc_wave_ws_doubles(int n, int m, int mp, int T, int nb);
 void fmpc_wave_make_images(int n, const double* blk, double* out);
 hipError_t fmpc_wave_prepare(int n, size_t lds_bytes);
 hipError_t fmpc_launch_wave(const FwParams& P, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t fmpc_launch_wave_chain(const FwParams& base, const FwChainStep* steps, int nsteps, FwParams* table, int grid,
+                                  size_t lds_bytes, hipStream_t stream);
 size_t fmpc_wave_shared_fac_doubles(int n, int nb);
 void fmpc_wave_cold_layout(int n, int mp, int* off9);
 
@@ -89,7 +93,11 @@ struct fmpc_handle_s {
     DevBuf<double> fm_compact;   // compact batch of the stopped realisations of a walk (fmpc_loop_run_walk)
     DevBuf<int> fm_walk_i; size_t fm_walk_cap = 0;   // start / stop step per realisation of a walk
     // affine form of the cold-start step without w (fmpc_kernel_affine.hip), built with the first-move form
-    FaParams fa_P; int fa_valid = 0, fa_disabled = 0; DevBuf<int> fa_need;
+    FaParams fa_P; int fa_valid = 0, fa_disabled = 0;
+    DevBuf<int> fa_need; size_t fa_need_cap = 0;   // FMPC_STRETCH_MAX flag lists of fa_need_cap problems: one per step of a chain (a call outside a stretch: the first)
+    DevBuf<char> fw_chain;               // FMPC_STRETCH_MAX parameter blocks of the flag-mode launch behind a chain (FwParams::chain)
+    struct FmpcStretch* st_cur = nullptr;  // the open bracket of the running solve's stream (fmpc_stretch_begin), or NULL
+    std::atomic<int> st_steps{0}, st_launches{0};   // the chain launched last (fmpc_last_stretch)
     DevBuf<double> ao_scr;               // fmpc_ao_step_device: a zero a[k] and scratch x0 / x0_pre for the loop-input kernel (3 batch n)
     FlParams fs_P; FlStepIn fs_I; int fs_valid = 0, fs_disabled = 0, fs_min_batch = FMPC_PRODUCT_MIN_BATCH_DEFAULT;   // the fused step (fmpc_loop_step27): images in its column order, B's images
     FlParams fl_P; int fl_valid = 0, fl_disabled = 0;   // first-move form as a product: closed-loop steps of > 64 realisations (fmpc_kernel_loopu0.hip)
@@ -196,7 +204,8 @@ struct fmpc_handle_s {
     DevBuf<double> rc_nu; DevBuf<int> rc_si; size_t rc_cap = 0;   // nu / status / iters of the first step when the caller passes none (budgets > 1)
     // A handle's device workspaces serve ONE solve at a time.  Solves enqueued on different streams are ordered on
     // the device: every solve records `ev`, and a solve on another stream than the last one waits for it first.
-    hipEvent_t ev = nullptr; int ev_valid = 0; hipStream_t last_stream = nullptr;
+    hipEvent_t ev = nullptr; std::atomic<int> ev_valid{0}; std::atomic<hipStream_t> last_stream{nullptr};   // (atomic: a chain of this handle may be
+                                         // launched by a call on ANOTHER handle of the same bracketed stream, which does not hold mu)
     // workspace, grown on demand; `mu` serialises the host-side enqueue (a handle may be shared between threads)
     std::mutex mu;
     std::mutex host_mu;          // serialises the host-pointer entry points (shared staging)
@@ -586,6 +595,7 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
                 h->pn_o_aimg = PL.o_aimg; h->pn_o_vec = PL.o_vec; h->pn_o_ucon = PL.o_ucon; h->pn_o_dz = PL.o_dz;
                 h->pn_doubles = PL.pool_doubles;
                 if (h->pn_pool.alloc(o, nullptr) != FMPC_OK || h->pn_cnt.alloc(2, nullptr) != FMPC_OK || h->fa_nflag.alloc(4, nullptr) != FMPC_OK ||
+                    h->fw_chain.alloc((size_t)FMPC_STRETCH_MAX * sizeof(FwParams), nullptr) != FMPC_OK ||
                     h->pn_sched.alloc((size_t)2 * FP_MAX_STEPS(h->nb) * FP_STEP_INTS, nullptr) != FMPC_OK) { fmpc_destroy(h); return FMPC_E_ALLOC; }
                 (void)hipMemset(h->pn_cnt, 0, 2 * sizeof(int));     // [handed over, length of the continuation list]
                 (void)hipMemset(h->fa_nflag, 0, 4 * sizeof(int));
@@ -621,9 +631,11 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
     return FMPC_OK;
 }
 
+static void fmpc_stretch_flush_handle(fmpc_handle h);
 extern "C" int fmpc_destroy(fmpc_handle h) {
     if (!h) return FMPC_E_NULL;
     (void)hipSetDevice(h->device);
+    fmpc_stretch_flush_handle(h);                 // (a pending chain of this handle reads its workspaces)
     delete h;
     return FMPC_OK;
 }
@@ -910,7 +922,223 @@ static bool fmpc_capturing(hipStream_t stream) {            // (declared above f
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     return hipStreamIsCapturing(stream, &st) == hipSuccess && st == hipStreamCaptureStatusActive;
 }
+
+// ---- stretch bracket (include/fastmpc.h, "A stretch of cold-start steps in few launches")
+// Between fmpc_stretch_begin and fmpc_stretch_end the calls that take the affine form are queued per stream and launched as CHAINS:
+// one launch of fmpc_cold_affine over the steps + one flag-mode launch of the exact path with a block row per step.  A queued
+// step keeps everything its launches need BY VALUE (the parameter blocks as they would have been launched), so launching a chain
+// reads no handle state; what the handle reports afterwards (last_path, inv_last) is set when the call is queued.
+struct FmpcChainStep {
+    FaStep a;                            // the product's pointers of the step
+    FwParams w;                          // the flag-mode launch of the step as a call outside a stretch would make it
+    bool superseded;                     // a later step of the chain writes exactly the same outputs: no exact-path redo
+};
+struct FmpcStretch {
+    fmpc_handle h = nullptr;             // the pending chain's handle (nsteps > 0)
+    int nsteps = 0;
+    FaParams A;                          // what the steps share (batch, ldz, step_ld, the handle's constants)
+    double k = 0.0; int n_newton = 0, zld = 0, g3 = 0; bool z_null = false, z_aligned = false;
+    size_t wave_lds = 0, ws_stride = 0; int num_cu = 0;
+    FwParams* table = nullptr;
+    FmpcChainStep st[FMPC_STRETCH_MAX];
+    size_t nodes_seen = 0;               // under capture: nodes of the capturing graph at the library's last look
+};
+static std::mutex fmpc_st_mu;                                   // (taken AFTER a handle's mu, never before it)
+static std::map<hipStream_t, FmpcStretch> fmpc_st_map;          // the open brackets
+static std::atomic<int> fmpc_st_open{0};                        // how many: calls outside any bracket pay one load
+
+// Nodes of the graph `stream` is being captured into; false: not capturing
+static bool fmpc_capture_nodes(hipStream_t stream, size_t* count) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    unsigned long long id = 0; hipGraph_t graph = nullptr; const hipGraphNode_t* deps = nullptr; size_t ndeps = 0;
+    if (hipStreamGetCaptureInfo_v2(stream, &st, &id, &graph, &deps, &ndeps) != hipSuccess || st != hipStreamCaptureStatusActive || !graph)
+        return false;
+    size_t n = 0;
+    if (hipGraphGetNodes(graph, nullptr, &n) != hipSuccess) return false;
+    *count = n;
+    return true;
+}
+static void fmpc_stretch_look(FmpcStretch& S, hipStream_t stream) {
+    size_t n = 0;
+    S.nodes_seen = fmpc_capture_nodes(stream, &n) ? n : 0;
+}
+// Somebody else's work on the capturing stream while a chain is pending: it should have come after steps that are not enqueued
+// yet.  The chain is dropped (nothing of it has been enqueued).  Caller holds fmpc_st_mu.
+static bool fmpc_stretch_foreign(FmpcStretch& S, hipStream_t stream) {
+    size_t n = 0;
+    if (S.nsteps == 0 || !fmpc_capture_nodes(stream, &n) || n == S.nodes_seen) return false;
+    S.nsteps = 0; S.h = nullptr;
+    S.nodes_seen = n;
+    return true;
+}
+
+// Launches the pending chain of a bracket.  Caller holds fmpc_st_mu.
+static int fmpc_stretch_flush(FmpcStretch& S, hipStream_t stream) {
+    if (S.nsteps == 0) return FMPC_OK;
+    const int n = S.nsteps;
+    fmpc_handle h = S.h;
+    S.nsteps = 0; S.h = nullptr;
+    // (the handle's workspaces serve one solve at a time: a solve of this handle enqueued on another stream since the steps were
+    // queued comes first, as fmpc_guard_begin orders unbracketed solves)
+    if (!fmpc_capturing(stream) && h->ev && h->ev_valid && h->last_stream != stream && hipStreamWaitEvent(stream, h->ev, 0) != hipSuccess)
+        return FMPC_E_HIP;
+    FaParams A = S.A;
+    A.nsteps = n;
+    for (int i = 0; i < n; ++i) A.steps[i] = S.st[i].a;
+    if (fmpc_launch_affine(A, S.num_cu, stream) != hipSuccess) return FMPC_E_HIP;
+    int live[FMPC_STRETCH_MAX], nlive = 0;
+    for (int i = 0; i < n; ++i) if (!S.st[i].superseded) live[nlive++] = i;
+    int launches = 1;
+    if (nlive == 1 || S.z_null) {
+        // one flag-mode launch per step, as outside a stretch.  (First moves only: the exact path iterates in ONE scratch z of the
+        // handle, which the block rows of a single launch would share.)  Only the last one counts in `handed` and moves `seen`.
+        for (int j = 0; j < nlive; ++j) {
+            FwParams P = S.st[live[j]].w;
+            if (j + 1 < nlive) { P.handed = nullptr; P.nflag = nullptr; }
+            if (fmpc_launch_wave(P, S.g3, S.wave_lds, stream) != hipSuccess) return FMPC_E_HIP;
+            ++launches;
+        }
+    } else {
+        // a block row per step; the rows share the workspace's num_cu x waves slots
+        int g = S.num_cu / nlive;
+        if (g > S.g3) g = S.g3;
+        if (g < 1) return FMPC_E_UNSUPPORTED;                     // (never: FMPC_STRETCH_MAX <= compute units)
+        FwChainStep T[FMPC_STRETCH_MAX];
+        for (int j = 0; j < nlive; ++j) {
+            const FwParams& P = S.st[live[j]].w;
+            T[j] = {P.x0, P.x0p, P.nu0, P.zout, P.nuout, P.u0out, P.status, P.iters, P.step, P.list,
+                    j + 1 == nlive ? P.handed : nullptr, P.ws + (size_t)j * g * fmpc_wave_waves_per_wg() * S.ws_stride};
+        }
+        if (fmpc_launch_wave_chain(S.st[live[0]].w, T, nlive, S.table, g, S.wave_lds, stream) != hipSuccess) return FMPC_E_HIP;
+        launches += 2;
+    }
+    h->st_steps = n; h->st_launches = launches;
+    if (!fmpc_capturing(stream) && h->ev && hipEventRecord(h->ev, stream) == hipSuccess) { h->ev_valid = 1; h->last_stream = stream; }
+    fmpc_stretch_look(S, stream);
+    return FMPC_OK;
+}
+
+static void fmpc_stretch_flush_handle_locked(fmpc_handle h, bool keep_one, hipStream_t keep);
+// A library call on `stream` that is no step of a chain: what is pending there comes first.
+static int fmpc_stretch_flush_stream(hipStream_t stream, fmpc_handle h = nullptr) {
+    if (fmpc_st_open.load() == 0) return FMPC_OK;
+    std::lock_guard<std::mutex> lk(fmpc_st_mu);
+    if (h) fmpc_stretch_flush_handle_locked(h, true, stream);      // (chains of this handle on OTHER streams)
+    auto it = fmpc_st_map.find(stream);
+    if (it == fmpc_st_map.end()) return FMPC_OK;
+    if (fmpc_stretch_foreign(it->second, stream)) return FMPC_E_UNSUPPORTED;
+    return fmpc_stretch_flush(it->second, stream);
+}
+// The pending chains of handle `h` on every stream but `keep` (NULL handle stream included: pass keep_none).  They use the handle's
+// flag lists, counters, parameter table and workspace slots, which a solve of the same handle on another stream is about to use
+// (or to regrow): they are launched first, and the guard's event then orders that solve behind them.  Caller holds fmpc_st_mu.
+static void fmpc_stretch_flush_handle_locked(fmpc_handle h, bool keep_one, hipStream_t keep) {
+    for (auto& kv : fmpc_st_map)
+        if (kv.second.nsteps && kv.second.h == h && !(keep_one && kv.first == keep) && !fmpc_stretch_foreign(kv.second, kv.first))
+            (void)fmpc_stretch_flush(kv.second, kv.first);
+}
+static void fmpc_stretch_flush_handle(fmpc_handle h) {
+    if (fmpc_st_open.load() == 0) return;
+    std::lock_guard<std::mutex> lk(fmpc_st_mu);
+    fmpc_stretch_flush_handle_locked(h, false, nullptr);
+}
+
+extern "C" int fmpc_stretch_begin(void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    std::lock_guard<std::mutex> lk(fmpc_st_mu);
+    if (fmpc_st_map.count(stream)) return FMPC_E_UNSUPPORTED;      // (brackets do not nest)
+    FmpcStretch& S = fmpc_st_map[stream];
+    fmpc_stretch_look(S, stream);
+    fmpc_st_open.fetch_add(1);
+    return FMPC_OK;
+}
+extern "C" int fmpc_stretch_end(void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    std::lock_guard<std::mutex> lk(fmpc_st_mu);
+    auto it = fmpc_st_map.find(stream);
+    if (it == fmpc_st_map.end()) return FMPC_E_UNSUPPORTED;
+    int rc = FMPC_OK;
+    if (it->second.nsteps) {
+        if (it->second.h && hipSetDevice(it->second.h->device) != hipSuccess) rc = FMPC_E_HIP;
+        else if (fmpc_stretch_foreign(it->second, stream)) rc = FMPC_E_UNSUPPORTED;
+        else rc = fmpc_stretch_flush(it->second, stream);
+    }
+    fmpc_st_map.erase(it);                                         // (the bracket is closed whatever the launch said)
+    fmpc_st_open.fetch_sub(1);
+    return rc;
+}
+extern "C" int fmpc_last_stretch(fmpc_handle h, int* steps, int* launches) {
+    if (!h) return FMPC_E_NULL;
+    if (steps) *steps = h->st_steps.load();
+    if (launches) *launches = h->st_launches.load();
+    return FMPC_OK;
+}
+
+static inline bool fmpc_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    if (!a || !b || !na || !nb) return false;
+    const char* pa = (const char*)a; const char* pb = (const char*)b;
+    return pa < pb + nb && pb < pa + na;
+}
+// The memory a step reads (3 ranges) and writes (6): bytes, empty where the pointer is NULL
+struct FmpcStepRanges { const void* in[3]; size_t nin[3]; const void* out[6]; size_t nout[6]; };
+static FmpcStepRanges fmpc_step_ranges(const FaParams& A, const FaStep& a) {
+    FmpcStepRanges R;
+    const size_t B = (size_t)A.batch, d = sizeof(double);
+    R.in[0] = a.x0; R.nin[0] = B * A.n * d;
+    R.in[1] = a.x0p; R.nin[1] = B * A.n * d;
+    R.in[2] = a.nu0; R.nin[2] = B * A.nb * A.n * d;
+    const size_t ldz = A.ldz > A.rows ? A.ldz : A.rows;
+    R.out[0] = a.zout; R.nout[0] = ((B - 1) * ldz + A.rows) * d;
+    R.out[1] = a.nuout; R.nout[1] = B * A.nb * A.n * d;
+    R.out[2] = a.u0out; R.nout[2] = B * A.m * d;
+    R.out[3] = a.status; R.nout[3] = B * sizeof(int);
+    R.out[4] = a.iters; R.nout[4] = B * sizeof(int);
+    R.out[5] = a.step; R.nout[5] = B * A.step_ld * d;
+    return R;
+}
+// May the step `a` of a call join the pending chain?  `supersedes`: bit i set = its outputs are exactly those of pending step i.
+static bool fmpc_stretch_accepts(const FmpcStretch& S, fmpc_handle h, const FmpcSolve& s, const FaStep& a, int zld, bool z_null, unsigned* supersedes) {
+    *supersedes = 0;
+    if (S.h != h || S.nsteps >= FMPC_STRETCH_MAX || memcmp(&S.k, &s.k, sizeof(double)) != 0 || S.A.batch != s.batch) return false;
+    if (S.n_newton != s.n_newton || S.zld != zld || S.z_null != z_null || S.z_aligned != (((size_t)a.zout & 127) == 0)) return false;
+    const FaStep& f = S.st[0].a;
+    if ((f.nuout == nullptr) != (a.nuout == nullptr) || (f.u0out == nullptr) != (a.u0out == nullptr) || (f.status == nullptr) != (a.status == nullptr) ||
+        (f.iters == nullptr) != (a.iters == nullptr) || (f.step == nullptr) != (a.step == nullptr)) return false;
+    const FmpcStepRanges N = fmpc_step_ranges(S.A, a);
+    for (int i = 0; i < S.nsteps; ++i) {
+        const FaStep& b = S.st[i].a;
+        const FmpcStepRanges O = fmpc_step_ranges(S.A, b);
+        for (int x = 0; x < 3; ++x)
+            for (int y = 0; y < 6; ++y)
+                if (fmpc_overlap(N.in[x], N.nin[x], O.out[y], O.nout[y]) || fmpc_overlap(O.in[x], O.nin[x], N.out[y], N.nout[y])) return false;
+        if (a.zout == b.zout && a.nuout == b.nuout && a.u0out == b.u0out && a.status == b.status && a.iters == b.iters && a.step == b.step) {
+            *supersedes |= 1u << i;
+            continue;
+        }
+        for (int x = 0; x < 6; ++x)
+            for (int y = 0; y < 6; ++y)
+                if (fmpc_overlap(N.out[x], N.nout[x], O.out[y], O.nout[y])) return false;
+    }
+    return true;
+}
+
+// A bracketed solve (h->st_cur, fmpc_solve_device_impl holds fmpc_st_mu) is about to enqueue, build or reallocate something
+// itself instead of joining the pending chain: the chain comes first.  fmpc_solve_device_impl has settled this already from
+// fmpc_affine_ready; this is the backstop at every place where the route leaves the way to the affine form's queue.
+static int fmpc_stretch_settle(fmpc_handle h, hipStream_t stream) {
+    if (!h->st_cur || h->st_cur->nsteps == 0) return FMPC_OK;
+    return fmpc_stretch_flush(*h->st_cur, stream);
+}
+// (fmpc_guard_begin_queued: the same for a solve that may join the pending chain of its stream's bracket)
+static int fmpc_guard_begin_queued(fmpc_handle h, hipStream_t stream) {
+    if (fmpc_capturing(stream)) return FMPC_OK;
+    if (!h->ev && hipEventCreateWithFlags(&h->ev, hipEventDisableTiming) != hipSuccess) return FMPC_E_HIP;
+    if (h->ev_valid && stream != h->last_stream && hipStreamWaitEvent(stream, h->ev, 0) != hipSuccess) return FMPC_E_HIP;
+    return FMPC_OK;
+}
 static int fmpc_guard_begin(fmpc_handle h, hipStream_t stream) {
+    const int rcs = fmpc_stretch_flush_stream(stream, h);       // inside a stretch bracket: the pending chain comes first
+    if (rcs != FMPC_OK) return rcs;
     if (fmpc_capturing(stream)) return FMPC_OK;
     if (!h->ev && hipEventCreateWithFlags(&h->ev, hipEventDisableTiming) != hipSuccess) return FMPC_E_HIP;
     if (h->ev_valid && stream != h->last_stream && hipStreamWaitEvent(stream, h->ev, 0) != hipSuccess) return FMPC_E_HIP;
@@ -1262,16 +1490,20 @@ static int fmpc_path_generic(fmpc_handle h, const FmpcSolve& s) {
 // FMPC_E_UNSUPPORTED: the form does not exist for this k, nothing is enqueued.
 static int fmpc_path_affine(fmpc_handle h, const FmpcSolve& s, size_t stride, int zld, bool z_null) {
     if (!h->fm_valid || h->fm_k != s.k) {
+        { const int rcq = fmpc_stretch_settle(h, s.stream); if (rcq != FMPC_OK) return rcq; }
         if (hipStreamSynchronize(s.stream) != hipSuccess) return FMPC_E_HIP;
         const int rcf = fmpc_build_first_move(h, s.k, s.stream);
         if (rcf != FMPC_OK && rcf != FMPC_E_UNSUPPORTED) return rcf;
     }
     if (!(h->fm_valid && h->fm_k == s.k && h->fa_valid)) return FMPC_E_UNSUPPORTED;
-    if ((size_t)s.batch > h->fa_need.cap) {
+    if ((size_t)s.batch > h->fa_need_cap) {                    // (never with a chain pending: its steps have this batch)
+        { const int rcq = fmpc_stretch_settle(h, s.stream); if (rcq != FMPC_OK) return rcq; }
         size_t cap = 256;
         while (cap < (size_t)s.batch) cap *= 2;
-        const int rc = h->fa_need.alloc(cap, s.stream);
+        h->fa_need_cap = 0;
+        const int rc = h->fa_need.alloc((size_t)FMPC_STRETCH_MAX * cap, s.stream);
         if (rc != FMPC_OK) return rc;
+        h->fa_need_cap = cap;
     }
     FaParams A = h->fa_P;
     A.batch = s.batch; A.step_ld = fmpc_step_ld(s.n_newton);
@@ -1282,9 +1514,36 @@ static int fmpc_path_affine(fmpc_handle h, const FmpcSolve& s, size_t stride, in
     static const bool no_nflag = [] { const char* e = getenv("FMPC_NO_NFLAG"); return e && e[0] == '1'; }();   // A/B switch
     A.nflag = no_nflag ? nullptr : nf;
     A.ldz = zld;                                          // (0: contiguous rows)
-    if (fmpc_launch_affine(A, h->num_cu, s.stream) != hipSuccess) return FMPC_E_HIP;
+    A.nsteps = 0;
     const int grid = fmpc_wave_grid(h, s.batch);
     const int g3 = grid < 64 ? grid : 64;                 // flag mode: the waves walk over the flags, few are set
+    if (h->st_cur) {
+        // inside a stretch bracket: the step joins the pending chain of its stream (fmpc_solve_device_impl has launched a chain
+        // it could not join) or starts one; nothing is enqueued now.  Caller holds fmpc_st_mu.
+        FmpcStretch& S = *h->st_cur;
+        FaStep a = {A.x0, A.x0p, A.nu0, A.zout, A.nuout, A.u0out, A.status, A.iters, A.step, nullptr};
+        unsigned sup = 0;
+        // (fmpc_solve_device_impl has launched a chain this step cannot join; should it not have, the chain is launched here)
+        if (S.nsteps > 0 && !fmpc_stretch_accepts(S, h, s, a, zld, z_null, &sup)) { const int rcq = fmpc_stretch_settle(h, s.stream); if (rcq != FMPC_OK) return rcq; }
+        const int i = S.nsteps;
+        a.need = h->fa_need + (size_t)i * h->fa_need_cap;
+        if (i == 0) {
+            S.h = h; S.A = A; S.k = s.k; S.n_newton = s.n_newton; S.zld = zld; S.z_null = z_null; S.z_aligned = ((size_t)A.zout & 127) == 0;
+            S.g3 = g3; S.wave_lds = h->wave_lds; S.ws_stride = stride; S.num_cu = h->num_cu; S.table = (FwParams*)h->fw_chain.p;
+            fmpc_stretch_look(S, s.stream);
+            sup = 0;
+        }
+        for (int j = 0; j < i; ++j) if (sup & (1u << j)) S.st[j].superseded = true;
+        S.st[i].a = a;
+        S.st[i].superseded = false;
+        FwParams W = fmpc_wave_params(h, s, stride, zld);
+        W.mode = FW_MODE_SHARED; W.handed = h->pn_cnt; W.pphase = 3; W.list = a.need; W.nflag = no_nflag ? nullptr : nf;
+        S.st[i].w = W;
+        S.nsteps = i + 1;
+        h->last_path = FMPC_PATH_PANEL; h->inv_last = 2;
+        return FMPC_OK;
+    }
+    if (fmpc_launch_affine(A, h->num_cu, s.stream) != hipSuccess) return FMPC_E_HIP;
     const int rc = fmpc_launch_flagged(h, s, g3, stride, h->fa_need, no_nflag ? nullptr : nf, zld);
     h->last_path = FMPC_PATH_PANEL; h->inv_last = 2;
     return rc;
@@ -1297,6 +1556,7 @@ static int fmpc_path_panel(fmpc_handle h, const FmpcSolve& s, size_t stride, int
     const int batch = s.batch, max_iter = fmpc_max_iter(s);
     const int npanels = (batch + FP_NP - 1) / FP_NP;
     if ((size_t)batch > h->pn_cap) {
+        { const int rcq = fmpc_stretch_settle(h, s.stream); if (rcq != FMPC_OK) return rcq; }
         h->pn_cap = 0;
         if (h->pn_gate.alloc((size_t)batch * 2, s.stream) != FMPC_OK ||
             h->pn_epsp.alloc((size_t)npanels * h->T * FP_NP, s.stream) != FMPC_OK ||
@@ -1311,6 +1571,7 @@ static int fmpc_path_panel(fmpc_handle h, const FmpcSolve& s, size_t stride, int
     const bool lowrank = h->lp_hint && s.w != nullptr && h->lp_v != nullptr;
     const bool dense_form = h->inv_enabled && (s.w == nullptr || lowrank || batch <= h->inv_max_batch);
     if (dense_form && (!h->inv_valid || h->inv_k != s.k) && !(h->inv_failed && h->inv_failed_k == s.k)) {
+        { const int rcq = fmpc_stretch_settle(h, s.stream); if (rcq != FMPC_OK) return rcq; }
         if (hipStreamSynchronize(s.stream) != hipSuccess) return FMPC_E_HIP;   // earlier solves may still read J
         const int rcb = fmpc_build_inverse(h, s.k, s.stream);
         if (rcb != FMPC_OK) return rcb;
@@ -1323,6 +1584,7 @@ static int fmpc_path_panel(fmpc_handle h, const FmpcSolve& s, size_t stride, int
         if (rca != FMPC_E_UNSUPPORTED) return rca;
     }
     if (zld) return FMPC_E_UNSUPPORTED;                       // (nothing of this solve is enqueued yet)
+    { const int rcq = fmpc_stretch_settle(h, s.stream); if (rcq != FMPC_OK) return rcq; }                      // (the panel kernels below join no chain)
     FpParams Q;
     fmpc_panel_params(h, s.k, Q);
     Q.batch = batch; Q.npanels = npanels; Q.step_ld = fmpc_step_ld(s.n_newton);
@@ -1466,6 +1728,7 @@ static int fmpc_solve_device_inner(fmpc_handle h, FmpcSolve s) {
     // with a budget of 1 does not write z at all (fmpc_cold_dz<.., .., true>).
     const bool z_null = s.z_out == nullptr;
     if (z_null) {
+        if ((size_t)s.batch * h->T * (h->n + h->m) > h->zs.cap) { const int rcq = fmpc_stretch_settle(h, s.stream); if (rcq != FMPC_OK) return rcq; }
         const int rcz = fmpc_scratch_z(h, s.batch, s.stream);
         if (rcz != FMPC_OK) return rcz;
         s.z_out = h->zs;
@@ -1475,21 +1738,29 @@ static int fmpc_solve_device_inner(fmpc_handle h, FmpcSolve s) {
     if (zld && (s.w != nullptr || s.z_init != nullptr || max_iter != 1 || h->prec == FMPC_PREC_F32_MIXED || h->force_tiled || h->denseQ ||
                 h->denseR || !h->use_wave || !h->sh_enabled || !h->pn_enabled)) return FMPC_E_UNSUPPORTED;
     if (h->prec == FMPC_PREC_F32_MIXED || h->force_tiled || ((h->denseQ || h->denseR) && !h->generic_big) ||
-        (!h->use_wave && (!h->generic_ok || h->prefer_tiled)))
+        (!h->use_wave && (!h->generic_ok || h->prefer_tiled))) {
+        { const int rcq = fmpc_stretch_settle(h, s.stream); if (rcq != FMPC_OK) return rcq; }
         return fmpc_path_tiled(h, s);
-    if (!h->use_wave) return fmpc_path_generic(h, s);
+    }
+    if (!h->use_wave) {
+        { const int rcq = fmpc_stretch_settle(h, s.stream); if (rcq != FMPC_OK) return rcq; }
+        return fmpc_path_generic(h, s);
+    }
     size_t stride = 0;
+    if (fmpc_wave_ws_doubles(h->n, h->m, h->wave.mp, h->T, h->nb) * (size_t)h->num_cu * fmpc_wave_waves_per_wg() > h->ws.cap) { const int rcq = fmpc_stretch_settle(h, s.stream); if (rcq != FMPC_OK) return rcq; }
     int rc = fmpc_ensure_wave_ws(h, &stride, s.stream);
     if (rc != FMPC_OK) return rc;
     int mode = FW_MODE_NORMAL;
     if (h->sh_enabled && s.z_init == nullptr) {
         // cold start: the first Newton step of every problem shares one factor (depends on k only)
+        if (!(h->sh_valid && h->sh_k == s.k)) { const int rcq = fmpc_stretch_settle(h, s.stream); if (rcq != FMPC_OK) return rcq; }
         rc = fmpc_ensure_cold(h, s.k, stride, s.stream);
         if (rc != FMPC_OK) return rc;
         mode = FW_MODE_SHARED;
     }
     if (mode == FW_MODE_SHARED && h->pn_enabled && h->pn_valid) return fmpc_path_panel(h, s, stride, zld, z_null);
     if (zld) return FMPC_E_UNSUPPORTED;
+    { const int rcq = fmpc_stretch_settle(h, s.stream); if (rcq != FMPC_OK) return rcq; }                      // (none of the paths below joins a chain)
     if (mode == FW_MODE_NORMAL && h->small_tiled && s.batch <= 1024) {
         rc = fmpc_path_small_tiled(h, s);
         if (rc != FMPC_E_UNSUPPORTED) return rc;
@@ -1501,6 +1772,22 @@ static int fmpc_solve_device_inner(fmpc_handle h, FmpcSolve s) {
     return fmpc_path_wave(h, s, mode, stride);
 }
 
+// Would fmpc_solve_device_inner take this call to the launch of the affine form (fmpc_path_affine) WITHOUT building constants,
+// growing a workspace or enqueuing anything on the way?  The conditions of that route, one by one.  Only such a call may join
+// a pending chain: whatever else a call does on the stream has to come after the chain's launches.
+static bool fmpc_affine_ready(fmpc_handle h, const FmpcSolve& s) {
+    if (s.w || s.z_init || fmpc_max_iter(s) != 1 || s.batch <= 0) return false;
+    const bool z_null = s.z_out == nullptr;
+    const size_t nz = (size_t)h->T * (h->n + h->m);
+    if (z_null && (size_t)s.batch * nz > h->zs.cap) return false;
+    if (h->prec == FMPC_PREC_F32_MIXED || h->force_tiled || h->denseQ || h->denseR || !h->use_wave || !h->sh_enabled || !h->pn_enabled ||
+        !h->pn_valid || h->n != FP_N) return false;
+    if (fmpc_wave_ws_doubles(h->n, h->m, h->wave.mp, h->T, h->nb) * (size_t)h->num_cu * fmpc_wave_waves_per_wg() > h->ws.cap) return false;
+    if (!h->sh_valid || h->sh_k != s.k || (size_t)s.batch > h->pn_cap) return false;
+    if (!h->inv_enabled || !h->inv_valid || h->inv_k != s.k || h->fa_disabled || (s.nu_out != nullptr && z_null)) return false;
+    return h->fm_valid && h->fm_k == s.k && h->fa_valid && (size_t)s.batch <= h->fa_need_cap;
+}
+
 // s.ldz < 0: the handle's fmpc_set_z_ld value applies
 static int fmpc_solve_device_impl(fmpc_handle h, FmpcSolve s) {
     if (!h || !s.x0 || (!s.z_out && !s.u0_out)) return FMPC_E_NULL;
@@ -1509,10 +1796,34 @@ static int fmpc_solve_device_impl(fmpc_handle h, FmpcSolve s) {
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
     std::lock_guard<std::mutex> lk(h->mu);
     if (s.ldz < 0) s.ldz = h->z_ld;
-    int rc = fmpc_guard_begin(h, s.stream);
+    // Inside a stretch bracket of the stream (fmpc_stretch_begin): the call joins the pending chain, or the chain is launched first
+    std::unique_lock<std::mutex> sl(fmpc_st_mu, std::defer_lock);
+    FmpcStretch* S = nullptr;
+    if (fmpc_st_open.load() > 0) {
+        sl.lock();
+        fmpc_stretch_flush_handle_locked(h, true, s.stream);          // (chains of this handle on other streams come first)
+        auto it = fmpc_st_map.find(s.stream);
+        if (it != fmpc_st_map.end()) S = &it->second;
+        else sl.unlock();
+    }
+    if (S && S->nsteps) {
+        if (fmpc_stretch_foreign(*S, s.stream)) return FMPC_E_UNSUPPORTED;
+        const bool z_null = s.z_out == nullptr;
+        const int zld = (!z_null && s.ldz > h->T * (h->n + h->m)) ? s.ldz : 0;
+        const FaStep a = {s.x0, s.x0_pre, s.nu0, s.z_out, s.nu_out, s.u0_out, s.status, s.iters, s.step, nullptr};
+        unsigned sup = 0;
+        if (!(fmpc_affine_ready(h, s) && fmpc_stretch_accepts(*S, h, s, a, zld, z_null, &sup))) {
+            const int rcf = fmpc_stretch_flush(*S, s.stream);
+            if (rcf != FMPC_OK) return rcf;
+        }
+    }
+    int rc = fmpc_guard_begin_queued(h, s.stream);
     if (rc != FMPC_OK) return rc;
+    h->st_cur = S;
     rc = fmpc_solve_device_inner(h, s);
-    fmpc_guard_end(h, s.stream);
+    h->st_cur = nullptr;
+    if (!(S && S->nsteps && S->h == h)) fmpc_guard_end(h, s.stream);      // (a queued step: the chain's launch records the event)
+    else if (!fmpc_capturing(s.stream)) h->last_stream = s.stream;
     return rc;
 }
 
@@ -2426,6 +2737,7 @@ extern "C" int fmpc_last_dispatch(fmpc_handle h, int* path, int* handed_over) {
     if (path) *path = h->last_path;
     if (handed_over) {
         *handed_over = 0;
+        fmpc_stretch_flush_handle(h);                   // (a chain of this handle that is still pending: its count is wanted)
         if (h->last_path == FMPC_PATH_PANEL) {
             if (hipDeviceSynchronize() != hipSuccess) return FMPC_E_HIP;
             if (hipMemcpy(handed_over, h->pn_cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return FMPC_E_HIP;
@@ -2835,6 +3147,7 @@ extern "C" int fmpc_unpack_device(fmpc_handle h, int batch, const double* z, dou
     if (batch < 0) return FMPC_E_DIM;
     if (batch == 0) return FMPC_OK;
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    { const int rcs = fmpc_stretch_flush_stream((hipStream_t)stream); if (rcs != FMPC_OK) return rcs; }   // (z of a pending chain)
     return fmpc_launch_unpack(h->n, h->m, h->T, batch, z, U, X, u0, (hipStream_t)stream) == hipSuccess
                ? FMPC_OK : FMPC_E_HIP;
 }
@@ -2846,6 +3159,7 @@ extern "C" int fmpc_loop_inputs_device(fmpc_handle h, int batch, const double* a
     if (batch < 0) return FMPC_E_DIM;
     if (batch == 0) return FMPC_OK;
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    { const int rcs = fmpc_stretch_flush_stream((hipStream_t)stream); if (rcs != FMPC_OK) return rcs; }
     return fmpc_launch_loop_inputs(h->n, h->m, h->T, batch, h->dev.Bt, h->loop_M1, h->loop_M2, a_k, x0_last, u1, u2,
                                    x0, x0_pre, w, (hipStream_t)stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
@@ -3022,6 +3336,7 @@ extern "C" int fmpc_phase_residual_device(fmpc_handle h, int batch, long long np
     if (batch == 0 || npx == 0) return FMPC_OK;
     if (h->n > 32) return FMPC_E_UNSUPPORTED;
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    { const int rcs = fmpc_stretch_flush_stream((hipStream_t)stream); if (rcs != FMPC_OK) return rcs; }   // (u_prev / Z of a pending chain)
     return fmpc_launch_phase_residual(batch, (size_t)npx, h->n, h->m, h->dev.Bt, phase, u_prev, Z, out, (hipStream_t)stream) == hipSuccess
                ? FMPC_OK : FMPC_E_HIP;
 }

@@ -123,4 +123,17 @@ struct FwParams {
                                     // Nothing depends on the order of host calls, so a recorded graph replays it as it stands
     int u0_done;                    // panel path, first moves only: fmpc_cold_dz has written u0out itself (zout is a scratch
                                     // array that only the problems redone here touch)
+    // Flag mode behind a CHAIN of affine steps (fmpc_launch_wave_chain): block row y of the grid serves step y of the chain and takes
+    // ALL its parameters from chain[y] in device memory instead of the kernel's own (the phases re-read the parameter block through
+    // a pointer, so a block row only needs another one).  NULL: the kernel's argument, as ever.
+    const FwParams* chain;
+};
+
+// What differs between the steps of a chain in the flag-mode launch behind it (fmpc_launch_wave_chain)
+struct FwChainStep {
+    const double* x0; const double* x0p; const double* nu0;
+    double* zout; double* nuout; double* u0out; int* status; int* iters; double* step;
+    int* list;                      // the step's flag list
+    int* handed;                    // the last step of the chain: counts the problems redone; NULL in the others
+    double* ws;                     // the block row's share of the workspace
 };

@@ -44,29 +44,6 @@ typedef double d2a __attribute__((ext_vector_type(2)));
 #define FA_THREADS 256
 #define FA_CT 4                          // column tiles (16 problems each) per task
 
-// The data operand of a tile of 16 problems: lane (g = lane / 16, c = lane % 16) holds d'[p0 + c][4 q + g], d' = [x0 ; x0_pre ; 1 ; 0]
-__device__ __forceinline__ void fa_load_d(double (&D)[FA_KS], const FaParams& P, int p0, int g, int c) {
-    const int n = P.n;
-    const int p = p0 + c < P.batch ? p0 + c : P.batch - 1;
-    const double* x0 = P.x0 + (size_t)p * n;
-    const double* xp = P.x0p ? P.x0p + (size_t)p * n : x0;
-    // one load per entry from an address chosen BEFORE the load, all requested up front; the selects follow (a select right
-    // behind its load makes the compiler wait for each load in turn: one memory round trip per entry)
-    double t[FA_KS];
-#pragma unroll
-    for (int q = 0; q < FA_KS; ++q) {
-        const int k = 4 * q + g;
-        const double* src = k < n ? x0 + k : xp + (k < 2 * n ? k - n : 0);
-        t[q] = *src;
-    }
-#pragma unroll
-    for (int q = 0; q < FA_KS; ++q) {
-        const int k = 4 * q + g;
-        const bool on = k < n || (k < 2 * n && P.x0p != nullptr);
-        D[q] = on ? t[q] : (k == 2 * n ? 1.0 : 0.0);
-    }
-}
-
 __device__ __forceinline__ void fa_load_a(double (&A)[FA_KS], const double* img, int tile, int lane) {
     const double* ip = img + (size_t)tile * FA_KS * 64 + lane;
 #pragma unroll
@@ -132,22 +109,47 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
     __shared__ double sD[FA_KS * FA_CT * 64];
 #define FA_SD(ct, cc, k) sD[((((k) >> 2) * FA_CT + (ct)) * 4 + ((k) & 3)) * 16 + (cc)]
     __shared__ double sF[4][3][16];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, c = lane & 15;
-    const int n = P.n;
+    const int tid0 = threadIdx.x;
+    constexpr int n = FA_N;                                          // (a constant: the staging's idx / n is no run-time division)
     const int wg = (int)blockIdx.x;
     const int gi = wg / P.wgs_per_group, slot = wg - gi * P.wgs_per_group;
     const int tiles = P.tiles_used, rows = P.rows, m = P.m;
     const int tstep = 4 * P.wgs_per_group;
-    int tile = slot * 4 + wv;
-    FA_TICK(0);
-    if (wg == 0 && tid == 0 && P.handed) *P.handed = 0;
+    { const int tid = tid0; FA_TICK(0); (void)tid; }
+    if (wg == 0 && tid0 == 0 && P.handed) *P.handed = 0;
     double A[FA_KS], An[FA_KS];
-    fa_request_a(A, P.img, tile < tiles ? tile : 0, lane);           // in flight while the data are staged
     const int p0 = gi * FA_CT * 16;
+    // The tiles of the product (see below), the same in every step
+    const int rounds = tiles / tstep;
+    const bool forms_wg = P.wgs_per_group >= 8 && rounds >= 2 && slot >= P.wgs_per_group - FA_CT;
+    const int nskip = (P.wgs_per_group >= 8 && rounds >= 2) ? 4 * FA_CT : 0;  // tiles of the last round the forms workgroups leave out
+    const int skip0 = (rounds - 1) * tstep + (P.wgs_per_group - FA_CT) * 4;    // ... a contiguous range
+    const int tfull = (rounds - (forms_wg ? 1 : 0)) * tstep;                 // this wavefront's rounds end here
+    // ================================================================ the steps of a chain (one: a call outside a stretch)
+    // Every step is the whole single-step kernel on its own pointers: same tile schedule, same operand roles, same stores, so z
+    // is bit for bit what one launch per step writes.  What a chain saves is what is paid per LAUNCH (the launch itself, its two
+    // boundaries, the flag-mode launch: 1.3 of the 1.9 us per step measured at 2000 problems); the start of a step is NOT hidden
+    // behind the CU-mate's tiles as one might hope -- the product takes 28.7 us per step of a chain against 29.3 us per launch and
+    // 20.5 us of matrix pipe: the barriers of a step bring the workgroup's wavefronts into step again.
+    for (int s = 0; s < P.nsteps; ++s) {
+    // (the lane's coordinates are taken afresh in every step: everything derived from them -- addresses in LDS, offsets into z --
+    // would otherwise be computed once in front of the loop and held in registers through the product, which has none to spare)
+    int tid = tid0;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, wv = tid >> 6, g = lane >> 4, c = lane & 15;
+    double* dump = P.dump + ((blockIdx.x & 15) * FA_THREADS + tid);          // 16 x 256 doubles: nobody reads them
+    const FaStep& S = P.steps[s];
+    const double* const x0_s = S.x0; const double* const x0p_s = S.x0p; const double* const nu0_s = S.nu0;
+    double* const zout_s = S.zout; double* const nuout_s = S.nuout; double* const u0out_s = S.u0out;
+    int* const status_s = S.status; int* const iters_s = S.iters; double* const step_s = S.step; int* const need_s = S.need;
+    int tile = slot * 4 + wv;
+    // (no wavefront of the workgroup reads sD / sF of the previous step any more when the staging below overwrites them)
+    if (s) __syncthreads();
+    fa_request_a(A, P.img, tile < tiles ? tile : 0, lane);           // in flight while the data are staged
     {
         const int np = P.batch - p0 < FA_CT * 16 ? P.batch - p0 : FA_CT * 16;       // problems of this group
-        const double* s0 = P.x0 + (size_t)p0 * n;
-        const double* s1 = P.x0p ? P.x0p + (size_t)p0 * n : s0;
+        const double* s0 = x0_s + (size_t)p0 * n;
+        const double* s1 = x0p_s ? x0p_s + (size_t)p0 * n : s0;
         double v0[7], v1[7];
 #pragma unroll
         for (int j = 0; j < 7; ++j) {
@@ -161,7 +163,7 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
                 const int pr = idx / n, k = idx - pr * n;
                 const bool on = idx < np * n;
                 FA_SD(pr >> 4, pr & 15, k) = on ? v0[j] : 0.0;
-                FA_SD(pr >> 4, pr & 15, n + k) = (on && P.x0p) ? v1[j] : 0.0;
+                FA_SD(pr >> 4, pr & 15, n + k) = (on && x0p_s) ? v1[j] : 0.0;
             }
         }
         if (tid < FA_CT * 16) { FA_SD(tid >> 4, tid & 15, 2 * n) = 1.0; FA_SD(tid >> 4, tid & 15, 2 * n + 1) = 0.0; }
@@ -179,12 +181,12 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
         const double le = P.elin[k], lp = P.eplin[k];                              // 2 e and -2 ep, zero beyond 2 n (64 entries)
         // lower bound of ||r_d(nu0)||^2: its x entries of the last stage (as the gate of the panel path), lane c: entries c, c + 16
         double rdl[4] = {P.rd2_0, P.rd2_0, P.rd2_0, P.rd2_0};
-        if (P.nu0 && t == 0) {
+        if (nu0_s && t == 0) {
             double xa[4][2];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int pr = p0 + fct * 16 + 4 * r + g < P.batch ? p0 + fct * 16 + 4 * r + g : P.batch - 1;
-                const double* nu = P.nu0 + (size_t)pr * P.nb * n;
+                const double* nu = nu0_s + (size_t)pr * P.nb * n;
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int e = c + 16 * j, ec = e < n ? e : 0;
@@ -223,12 +225,12 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
                     const double sp = (sF[0][1][i] + sF[1][1][i]) + (sF[2][1][i] + sF[3][1][i]);
                     const double sn = (sF[0][2][i] + sF[1][2][i]) + (sF[2][2][i] + sF[3][2][i]);
                     const bool clear = fa_decide(P, se, sp, rdl[r], sn);
-                    P.need[pp] = clear ? 0 : 1;
+                    need_s[pp] = clear ? 0 : 1;
                     if (!clear && P.nflag) atomicAdd(P.nflag, 1);
                     if (clear) {
-                        if (P.status) P.status[pp] = FMPC_OK;
-                        if (P.iters) P.iters[pp] = 1;
-                        if (P.step) for (int q = 0; q < P.step_ld; ++q) P.step[(size_t)pp * P.step_ld + q] = q == 0 ? 1.0 : -1.0;
+                        if (status_s) status_s[pp] = FMPC_OK;
+                        if (iters_s) iters_s[pp] = 1;
+                        if (step_s) for (int q = 0; q < P.step_ld; ++q) step_s[(size_t)pp * P.step_ld + q] = q == 0 ? 1.0 : -1.0;
                     }
                 }
             }
@@ -241,12 +243,6 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
     // the tiles beyond the full rounds (z has 320 full tiles + one of 10 rows at (27, 144, 30): one) are dealt by COLUMN TILE,
     // 14 matrix instructions apiece, to all wavefronts of the group -- a whole extra tile on one wavefront holds up its SIMD for
     // a tile's time, 10 % of the kernel.
-    const int rounds = tiles / tstep;
-    const bool forms_wg = P.wgs_per_group >= 8 && rounds >= 2 && slot >= P.wgs_per_group - FA_CT;
-    const int nskip = (P.wgs_per_group >= 8 && rounds >= 2) ? 4 * FA_CT : 0;  // tiles of the last round the forms workgroups leave out
-    const int skip0 = (rounds - 1) * tstep + (P.wgs_per_group - FA_CT) * 4;    // ... a contiguous range
-    const int tfull = (rounds - (forms_wg ? 1 : 0)) * tstep;                 // this wavefront's rounds end here
-    double* dump = P.dump + ((blockIdx.x & 15) * FA_THREADS + tid);          // 16 x 256 doubles: nobody reads them
     {
         const int wg_w = slot * 4 + wv;                                          // wavefront of the group
         const int nleft = nskip + (tiles - rounds * tstep);
@@ -264,13 +260,15 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int pp = (gi * FA_CT + ct) * 16 + 4 * r + g;
-                if (ZOUT && lt < P.tiles && row < rows && pp < P.batch) P.zout[(size_t)pp * P.ldz + row] = acc[r];
-                if (ZOUT && lt >= P.tiles && row - 16 * P.tiles < P.nu_rows && pp < P.batch) P.nuout[(size_t)pp * P.nu_rows + (row - 16 * P.tiles)] = acc[r];
-                if (P.u0out != nullptr && row < m && pp < P.batch) P.u0out[(size_t)pp * m + row] = acc[r];
+                if (ZOUT && lt < P.tiles && row < rows && pp < P.batch) zout_s[(size_t)pp * P.ldz + row] = acc[r];
+                if (ZOUT && lt >= P.tiles && row - 16 * P.tiles < P.nu_rows && pp < P.batch) nuout_s[(size_t)pp * P.nu_rows + (row - 16 * P.tiles)] = acc[r];
+                if (u0out_s != nullptr && row < m && pp < P.batch) u0out_s[(size_t)pp * m + row] = acc[r];
             }
         }
     }
-    if (tile >= tfull) return;
+    // (before the back-edge of the step loop every load requested by hand has been awaited: here, or by the last tile below,
+    // which requests its own operand once more and waits for it)
+    if (tile >= tfull) { fa_await_a<0>(A); continue; }
     double D[FA_CT][FA_KS];
 #pragma unroll
     for (int ct = 0; ct < FA_CT; ++ct)
@@ -297,7 +295,7 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
             // (tiles beyond those of z are rows of nu+: another base and row count, the same 16 stores)
             const bool isnu = tile >= P.tiles;
             const int rloc = isnu ? row - 16 * P.tiles : row, rcnt = isnu ? P.nu_rows : rows, ld = isnu ? P.nu_rows : P.ldz;
-            double* obase = isnu ? P.nuout : P.zout;
+            double* obase = isnu ? nuout_s : zout_s;
             const unsigned voz = (unsigned)(g * ld + rloc);
             const bool rok = rloc < rcnt;
 #pragma unroll
@@ -314,7 +312,7 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
         // Without z (ZOUT = false) the first moves are the ONLY stores behind the request above: they must not sit under a
         // condition, or a wavefront that skipped them would pass fa_await_a<16> with its 14 loads still in flight (found by
         // tests/test_isa_affine_hazard.py; the launcher only deals the tiles 16 t < m then, and rows >= m go to the dump line).
-        if (!ZOUT || (P.u0out != nullptr && 16 * tile < m)) {    // uniform: the first m rows again, as the first moves
+        if (!ZOUT || (u0out_s != nullptr && 16 * tile < m)) {    // uniform: the first m rows again, as the first moves
             const unsigned vou = (unsigned)(g * m + row);
             const bool rok = row < m;
 #pragma unroll
@@ -322,7 +320,7 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int pb = (gi * FA_CT + ct) * 16 + 4 * r;
-                    double* ub = P.u0out + (size_t)pb * m + vou;
+                    double* ub = u0out_s + (size_t)pb * m + vou;
                     double* dst = (rok && pb + g < P.batch) ? ub : dump;
                     *dst = acc[ct][r];
                 }
@@ -339,16 +337,31 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
 #endif
     }
     FA_TICK(3);
+    }
 }
 
 hipError_t fmpc_launch_affine(FaParams P, int num_cu, hipStream_t stream) {
     if (P.n != 27 || 2 * P.n + 2 > FA_KC || 7 * FA_THREADS < FA_CT * 16 * P.n) return hipErrorInvalidValue;
+    if (P.nsteps < 0 || P.nsteps > FMPC_STRETCH_MAX) return hipErrorInvalidValue;
+    if (P.nsteps == 0) {                                          // a single step: the per-call fields
+        P.nsteps = 1;
+        P.steps[0] = {P.x0, P.x0p, P.nu0, P.zout, P.nuout, P.u0out, P.status, P.iters, P.step, P.need};
+    }
+    // (the steps of a chain share which outputs are present; the kernel's instance is chosen from the first)
+    P.x0 = P.steps[0].x0; P.zout = P.steps[0].zout; P.nuout = P.steps[0].nuout; P.u0out = P.steps[0].u0out;
+    bool aligned = true;
+    for (int s = 0; s < P.nsteps; ++s) {
+        const FaStep& S = P.steps[s];
+        if (!S.x0 || !S.need || (S.zout == nullptr) != (P.zout == nullptr) || (S.nuout == nullptr) != (P.nuout == nullptr) ||
+            (S.u0out == nullptr) != (P.u0out == nullptr)) return hipErrorInvalidValue;
+        aligned = aligned && ((size_t)S.zout & 127) == 0;
+    }
     if (!P.zout && !P.u0out) return hipErrorInvalidValue;         // (fmpc_cold_affine<false> stores the first moves unconditionally)
     const int ncol = (P.batch + 15) / 16, ngroups = (ncol + FA_CT - 1) / FA_CT;
     P.tiles_used = P.zout ? P.tiles + (P.nuout ? P.nu_tiles : 0) : (P.m + 15) / 16;
     if (P.ldz < P.rows) P.ldz = P.rows;
     static const bool no_nt = [] { const char* e = getenv("FMPC_AFFINE_NO_NT"); return e && e[0] == '1'; }();       // A/B switch
-    const bool nt = P.zout && !no_nt && P.ldz % 16 == 0 && ((size_t)P.zout & 127) == 0;
+    const bool nt = P.zout && !no_nt && P.ldz % 16 == 0 && aligned;
     // two workgroups of four wavefronts per CU are resident: that many workgroups share the groups of 64 problems (a workgroup
     // beyond the resident set would start when another ends)
     int wpg = (2 * num_cu) / ngroups;                            // workgroups per group

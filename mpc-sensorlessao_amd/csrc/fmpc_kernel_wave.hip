@@ -2003,7 +2003,10 @@ template <int N, bool EX>
 __global__ void __launch_bounds__(FW_THREADS, 2) fmpc_newton_wave(FwParams Pv) {
     using C = FwCfg<N>;
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    const FwKP P = fw_params();
+    // (a chain of affine steps in flag mode: block row y works with the parameter block of step y, device memory written by
+    // fmpc_wave_chain_table in front of this launch)
+    const FwKP P0 = fw_params();
+    const FwKP P = P0->chain ? (FwKP)(unsigned long long)(P0->chain + blockIdx.y) : P0;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int mp = P->V.mp;
     const int batch = P->batch;
@@ -2037,7 +2040,7 @@ __global__ void __launch_bounds__(FW_THREADS, 2) fmpc_newton_wave(FwParams Pv) {
         if (cnt == seen) return;
         // (rare) the workgroup that draws the last ticket has seen every workgroup read both counts: it brings `seen` up to date
         __syncthreads();
-        if (threadIdx.x == 0 && atomicAdd(P->nflag + 2, 1) == (int)gridDim.x - 1) { P->nflag[1] = cnt; P->nflag[2] = 0; }
+        if (threadIdx.x == 0 && atomicAdd(P->nflag + 2, 1) == (int)(gridDim.x * gridDim.y) - 1) { P->nflag[1] = cnt; P->nflag[2] = 0; }
     }
     if (pphase == 3) {                               // nothing flagged among this workgroup's problems (the usual case): leave
         int any = 0;
@@ -2277,6 +2280,40 @@ hipError_t fmpc_wave_prepare(int n, size_t lds_bytes) {
     const hipError_t e = hipFuncSetAttribute((const void*)fmpc_newton_wave<27, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute((const void*)fmpc_newton_wave<27, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+}
+
+// The parameter blocks of a chain's steps, written where the flag-mode launch behind them reads them (FwParams::chain)
+struct FwChainTable { FwParams base; FwChainStep steps[FMPC_STRETCH_MAX]; int nsteps; FwParams* table; };
+__global__ void __launch_bounds__(64) fmpc_wave_chain_table(FwChainTable A) {
+    const int i = threadIdx.x;
+    if (i >= A.nsteps) return;
+    FwParams* q = A.table + i;
+    *q = A.base;
+    const FwChainStep& S = A.steps[i];
+    q->x0 = S.x0; q->x0p = S.x0p; q->nu0 = S.nu0; q->zout = S.zout; q->nuout = S.nuout; q->u0out = S.u0out;
+    q->status = S.status; q->iters = S.iters; q->step = S.step; q->list = S.list; q->handed = S.handed; q->ws = S.ws;
+    q->chain = nullptr;
+}
+
+// Flag mode behind a chain of affine steps: ONE launch, block row y redoes the flagged problems of steps[y] (each row has its own
+// share of the workspace: `grid` x FW_WAVES slots from steps[y].ws on).  `table`: nsteps parameter blocks of device memory.
+hipError_t fmpc_launch_wave_chain(const FwParams& base, const FwChainStep* steps, int nsteps, FwParams* table, int grid,
+                                  size_t lds_bytes, hipStream_t stream) {
+    if (base.M.n != 27 || base.pphase != 3 || base.mode != FW_MODE_SHARED || nsteps < 1 || nsteps > FMPC_STRETCH_MAX || !table || grid < 1)
+        return hipErrorInvalidValue;
+    static const int env_flags = [] { const char* e = getenv("FMPC_WAVE_FLAGS"); return e && e[0] ? atoi(e) : 0; }();
+    FwChainTable A;
+    A.base = base; A.base.flags = env_flags; A.base.chain = nullptr;
+    for (int i = 0; i < nsteps; ++i) A.steps[i] = steps[i];
+    for (int i = nsteps; i < FMPC_STRETCH_MAX; ++i) A.steps[i] = steps[0];
+    A.nsteps = nsteps; A.table = table;
+    hipLaunchKernelGGL(fmpc_wave_chain_table, dim3(1), dim3(64), 0, stream, A);
+    if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;
+    FwParams P = A.base;
+    P.x0 = steps[0].x0;                                  // (not read: every block row takes its block from the table)
+    P.chain = table;
+    hipLaunchKernelGGL((fmpc_newton_wave<27, false>), dim3(grid, nsteps), dim3(FW_THREADS), lds_bytes, stream, P);
+    return hipGetLastError();
 }
 
 hipError_t fmpc_launch_wave(const FwParams& params, int grid, size_t lds_bytes, hipStream_t stream) {

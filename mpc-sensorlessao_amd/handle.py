@@ -187,6 +187,15 @@ class FastMPCHandle:
             raise FastMPCError(rc, "fmpc_last_dispatch")
         return path.value, cnt.value
 
+    def last_stretch(self):
+        """(steps, launches) of the chain of this handle that was launched last inside a stretch bracket (fmpc_last_stretch;
+        (0, 0) before the first)."""
+        st = C.c_int(); la = C.c_int()
+        rc = self._lib.fmpc_last_stretch(self._h, C.byref(st), C.byref(la))
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_last_stretch")
+        return st.value, la.value
+
     def last_tiled_wavefronts(self):
         """Wavefronts per problem of the last tiled-kernel launch (fmpc_last_tiled_wavefronts; 0 = none yet)."""
         return int(self._lib.fmpc_last_tiled_wavefronts(self._h))
