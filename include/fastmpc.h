@@ -704,7 +704,10 @@ unsigned long long fmpc_alloc_generation(void);
  * cold-start step (n = 27, w == NULL, z_init == NULL, n_newton == 1, the form valid for k) is QUEUED instead of launched, and
  * consecutive queued calls form a chain that one launch of the product kernel + one launch of the exact path serve: the
  * per-launch cost of a step (its start, two launch boundaries, about 40 % of a 2000-problem step) is paid once per chain.
- * Every step computes exactly what its own launches compute (same tile schedule, same stores: z bit for bit).
+ * Every step computes exactly what its own launches compute (same instruction sequence per entry of z: z bit for bit).
+ * The steps of a chain MAY RUN CONCURRENTLY: steps that write different output tuples share no memory (the rules below) and are
+ * dealt to different workgroups of the one launch ("lanes"); the steps that write one and the same tuple stay in one lane, in the
+ * order of the calls.  Nothing a caller can observe depends on it -- the results are complete after fmpc_stretch_end, as before.
  *
  * A queued call extends the pending chain when it has the same handle, k, batch and output signature (z wanted or not, ldz,
  * 128-byte alignment of z, nu_out / u0_out / status / iters / step present or not, n_newton) as the chain, the chain has fewer
@@ -728,8 +731,9 @@ unsigned long long fmpc_alloc_generation(void);
  *
  * After a chain, fmpc_last_dispatch / fmpc_last_dual_form read as after a per-step call (handed_over: of the last step that
  * was not superseded).  fmpc_last_stretch: the steps and launches of the chain of this handle that was launched last (0, 0 before
- * the first).  Measured at (27, 144, 30), 2000 problems, recorded regions of 20 / 400 steps: 30.1 / 29.2 us of device time per
- * step against 31.7 / 31.2 us with two launches per step (README.md).
+ * the first).  Measured at (27, 144, 30), 2000 problems, four buffer sets in rotation, recorded regions of 20 / 400 steps:
+ * 25.5 / 23.9 us of device time per step with the steps of a chain in four lanes, 31.2 / 29.4 us with the steps one after
+ * another, 31.7 / 31.2 us with two launches per step (README.md).
  */
 #define FMPC_STRETCH_MAX 16
 int fmpc_stretch_begin(void* stream);

@@ -34,8 +34,16 @@ struct FaParams {
     // the fields x0 .. need above.  All steps of a chain share batch, ldz, step_ld and which of the outputs are present.
     int nsteps;
     FaStep steps[FMPC_STRETCH_MAX];
+    // The lanes of a chain (fmpc_host_plan_lanes): workgroup blockIdx.x = (lane wgs_per_lane + group wgs_per_group + slot) runs the
+    // steps [lane_begin[lane], lane_begin[lane + 1]) of steps[], which the launcher has put into lane order.  One lane: all steps.
+    int nlanes, wgs_per_lane;
+    int lane_begin[FMPC_STRETCH_MAX + 1];
 };
 
-hipError_t fmpc_launch_affine(FaParams P, int num_cu, hipStream_t stream);
+// The most lanes a chain takes unless FMPC_STRETCH_LANES says otherwise (DESIGN.md section 7 has the measurement behind it)
+#define FMPC_STRETCH_LANES_DEFAULT FMPC_STRETCH_MAX
+// supersedes[j] (a chain, nsteps > 1): bit i set = step j writes exactly the output tuple of step i < j.  Steps that share no tuple
+// are independent (fmpc_stretch_accepts) and may run side by side, in lanes; NULL: one lane, the steps one after another.
+hipError_t fmpc_launch_affine(FaParams P, int num_cu, hipStream_t stream, const unsigned* supersedes = nullptr);
 // The same step as TWO chained products per stage (nu+_s = J_s d, u_s = Bw nu+_s; the x rows directly): 20 % fewer matrix
 // instructions and one task per wavefront.  z_out required, nu_out not served (the caller takes fmpc_launch_affine then).

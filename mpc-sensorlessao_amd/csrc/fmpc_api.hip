@@ -932,6 +932,7 @@ struct FmpcChainStep {
     FaStep a;                            // the product's pointers of the step
     FwParams w;                          // the flag-mode launch of the step as a call outside a stretch would make it
     bool superseded;                     // a later step of the chain writes exactly the same outputs: no exact-path redo
+    unsigned same_outputs;               // bit i: pending step i < this one has exactly this step's outputs (fmpc_stretch_accepts)
 };
 struct FmpcStretch {
     fmpc_handle h = nullptr;             // the pending chain's handle (nsteps > 0)
@@ -985,7 +986,14 @@ static int fmpc_stretch_flush(FmpcStretch& S, hipStream_t stream) {
     FaParams A = S.A;
     A.nsteps = n;
     for (int i = 0; i < n; ++i) A.steps[i] = S.st[i].a;
-    if (fmpc_launch_affine(A, S.num_cu, stream) != hipSuccess) return FMPC_E_HIP;
+    // Steps with different output tuples share nothing (fmpc_stretch_accepts) and may run side by side in the launch; the steps of one
+    // tuple stay in order.  The relation as the launcher wants it, transitive: a step names every earlier step of its tuple.
+    unsigned same[FMPC_STRETCH_MAX];
+    for (int j = 0; j < n; ++j) {
+        same[j] = S.st[j].same_outputs & ((1u << j) - 1u);
+        for (int i = 0; i < j; ++i) if (same[j] >> i & 1u) same[j] |= same[i];
+    }
+    if (fmpc_launch_affine(A, S.num_cu, stream, same) != hipSuccess) return FMPC_E_HIP;
     int live[FMPC_STRETCH_MAX], nlive = 0;
     for (int i = 0; i < n; ++i) if (!S.st[i].superseded) live[nlive++] = i;
     int launches = 1;
@@ -1536,6 +1544,7 @@ static int fmpc_path_affine(fmpc_handle h, const FmpcSolve& s, size_t stride, in
         for (int j = 0; j < i; ++j) if (sup & (1u << j)) S.st[j].superseded = true;
         S.st[i].a = a;
         S.st[i].superseded = false;
+        S.st[i].same_outputs = sup;
         FwParams W = fmpc_wave_params(h, s, stride, zld);
         W.mode = FW_MODE_SHARED; W.handed = h->pn_cnt; W.pphase = 3; W.list = a.need; W.nflag = no_nflag ? nullptr : nf;
         S.st[i].w = W;

@@ -952,3 +952,57 @@ void fmpc_host_estimator_dft_images(int len, int d, int first, std::vector<doubl
             img[base + 64] = (double)sinl(ang);
         }
 }
+
+// ---- lane plan of a chain of affine steps (fmpc_kernel_affine.hip)
+int fmpc_host_plan_lanes(int nsteps, const unsigned* supersedes, int ngroups, int slots, int tiles_used, int cap, int* lane_of_step, int* wpg_out) {
+    if (ngroups < 1) ngroups = 1;
+    const int wpg_max = (tiles_used + 3) / 4 > 0 ? (tiles_used + 3) / 4 : 1;   // one tile per wavefront at least
+    auto wpg_of = [&](int L) { const int w = slots / (ngroups * L); return w < 1 ? 1 : (w > wpg_max ? wpg_max : w); };
+    for (int i = 0; i < nsteps; ++i) lane_of_step[i] = 0;
+    *wpg_out = wpg_of(1);
+    if (nsteps <= 1) return 1;
+    // classes: the steps of one output tuple, in chain order.  A step knows "the same tuple as pending step i" (any such i): the
+    // lowest one it names, followed down to a step that names none, is its class -- the relation made transitive.
+    std::vector<int> cls(nsteps), first, len;
+    for (int j = 0; j < nsteps; ++j) {
+        int rep = j;
+        for (int i = 0; i < j; ++i) if (supersedes[j] >> i & 1u) { rep = first[cls[i]]; break; }
+        if (rep == j) { cls[j] = (int)first.size(); first.push_back(j); len.push_back(1); }
+        else { cls[j] = cls[rep]; ++len[cls[j]]; }
+    }
+    const int nc = (int)first.size();
+    std::vector<int> order(nc);                                                // longest first, ties in chain order
+    for (int c = 0; c < nc; ++c) order[c] = c;
+    for (int a = 1; a < nc; ++a)
+        for (int b = a; b > 0 && len[order[b]] > len[order[b - 1]]; --b) { const int t = order[b]; order[b] = order[b - 1]; order[b - 1] = t; }
+    int Lmax = slots / ngroups < 1 ? 1 : slots / ngroups;
+    if (Lmax > nc) Lmax = nc;
+    if (cap >= 1 && Lmax > cap) Lmax = cap;
+    if (cap < 1) Lmax = 1;
+    int bestL = 1; long best = -1;
+    std::vector<int> lane_of_cls(nc), best_lanes(nc, 0), load;
+    for (int L = 1; L <= Lmax; ++L) {
+        load.assign(L, 0);
+        for (int o = 0; o < nc; ++o) {
+            int to = 0;
+            for (int l = 1; l < L; ++l) if (load[l] < load[to]) to = l;        // the least loaded lane, ties to the lowest
+            lane_of_cls[order[o]] = to; load[to] += len[order[o]];
+        }
+        int H = 0;
+        for (int l = 0; l < L; ++l) if (load[l] > H) H = load[l];
+        const int w = wpg_of(L), R = (tiles_used + 4 * w - 1) / (4 * w);
+        const long cost = (long)H * (R + FMPC_LANE_START_ROUNDS);
+        if (best < 0 || cost < best) { best = cost; bestL = L; best_lanes = lane_of_cls; }
+    }
+    for (int j = 0; j < nsteps; ++j) lane_of_step[j] = best_lanes[cls[j]];
+    *wpg_out = wpg_of(bestL);
+    return bestL;
+}
+
+extern "C" int fmpc_debug_plan_lanes(int nsteps, const unsigned* supersedes, int ngroups, int slots, int tiles_used, int cap, int* lane_of_step,
+                                     int* lanes, int* wpg) {
+    if (nsteps < 0 || nsteps > 32 || (nsteps && (!supersedes || !lane_of_step)) || !lanes || !wpg) return -1;
+    int dummy = 0;
+    *lanes = fmpc_host_plan_lanes(nsteps, supersedes, ngroups, slots, tiles_used, cap, nsteps ? lane_of_step : &dummy, wpg);
+    return 0;
+}

@@ -122,6 +122,19 @@ struct FmpcAffineOut {
     std::vector<double> img;            // matrix-core operand images: [tile][k-step][lane = 16 (k mod 4) + (row mod 16)], z tiles then nu tiles
 };
 void fmpc_host_build_affine(const FmpcAffineIn& In, FmpcAffineOut& Out);
+// Lane plan of a CHAIN of affine steps: which steps of one launch run side by side.  The steps with one output tuple (a class: step j
+// names in supersedes[j] the earlier steps whose outputs are exactly its own, bit i = step i) are ordered and stay together in
+// chain order; different classes are independent (fmpc_stretch_accepts) and may go to different LANES, each lane with its own
+// workgroups: per 64-problem group wpg = slots / (ngroups lanes) of them (1 .. one tile per wavefront), `slots` = resident
+// workgroups of the chip.  For L = 1 .. min(classes, slots / ngroups, cap) lanes the classes are dealt longest first to the least
+// loaded lane; a lane's workgroup then runs H(L) steps (the fullest lane) of R(L) = ceil(tiles / 4 wpg) rounds of tiles, and every
+// step costs a start on top: cost(L) = H (R + FMPC_LANE_START_ROUNDS); the cheapest L, the smaller one on a tie.  One lane is the
+// schedule of a single step.  Returns the lanes; lane_of_step[nsteps], *wpg.  A pure function (tests/test_host_lane_plan.py).
+// FMPC_LANE_START_ROUNDS: what a step costs a workgroup before its rounds run at the matrix pipe's rate, in rounds of 3.05 us
+// (timing build at 2000 problems, docs/DESIGN_HISTORY.md: a start of 7 us -- data through LDS, decision forms, column-tile tasks --
+// and a first round of 6.8 instead of 3.05 us: 10.5 us).
+#define FMPC_LANE_START_ROUNDS 3
+int fmpc_host_plan_lanes(int nsteps, const unsigned* supersedes, int ngroups, int slots, int tiles_used, int cap, int* lane_of_step, int* wpg);
 // operand images [tile][k-step][lane = 16 (k mod 4) + (row mod 16)] of a rows x cols row-major matrix, ks k-steps of 4 columns
 // (rows padded to tiles of 16, columns to 4 ks, with zeros)
 void fmpc_host_mfma_images(const double* M, int rows, int cols, int ks, std::vector<double>& img);

@@ -21,6 +21,13 @@
 // dealt in contiguous ranges to 8 wavefronts per CU (two per SIMD), which keep their 64 problems' data (the B operand, 112
 // registers) across the tasks of a group; the A operand (a 512-byte image per k-step, L2-resident: 2.3 MB in all) is
 // requested one task ahead.  First moves only (z_out = NULL): the first m rows alone.
+//
+// A chain of steps (fmpc_stretch_begin / fmpc_stretch_end) is ONE launch, and its steps run side by side where they may: the steps
+// that write one output tuple are a class and stay in order; classes are independent (the bracket accepts no step that touches what a
+// pending one writes) and are dealt to LANES of the chain (fmpc_host_plan_lanes).  A workgroup = (lane, group of 64 problems, slot)
+// and runs the steps of its lane only, each of them exactly as the single-step kernel does: with L lanes a (step, group) has 1 / L of
+// the workgroups and L times the rounds of tiles behind ONE start -- the 10.5 us of a step's start and slow first round were paid
+// per 5 rounds of 3 us at 2000 problems, in four lanes per 20 (23.5 against 28.9 us per step of a 16-step chain).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -112,7 +119,10 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
     const int tid0 = threadIdx.x;
     constexpr int n = FA_N;                                          // (a constant: the staging's idx / n is no run-time division)
     const int wg = (int)blockIdx.x;
-    const int gi = wg / P.wgs_per_group, slot = wg - gi * P.wgs_per_group;
+    // (lane of the CHAIN -- a set of steps, below -- , group of 64 problems, workgroup of the group); one chain lane: wgs_per_lane = the grid
+    const int ln = wg / P.wgs_per_lane, wl = wg - ln * P.wgs_per_lane;
+    const int gi = wl / P.wgs_per_group, slot = wl - gi * P.wgs_per_group;
+    const int s_begin = P.lane_begin[ln], s_end = P.lane_begin[ln + 1];
     const int tiles = P.tiles_used, rows = P.rows, m = P.m;
     const int tstep = 4 * P.wgs_per_group;
     { const int tid = tid0; FA_TICK(0); (void)tid; }
@@ -129,9 +139,10 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
     // Every step is the whole single-step kernel on its own pointers: same tile schedule, same operand roles, same stores, so z
     // is bit for bit what one launch per step writes.  What a chain saves is what is paid per LAUNCH (the launch itself, its two
     // boundaries, the flag-mode launch: 1.3 of the 1.9 us per step measured at 2000 problems); the start of a step is NOT hidden
-    // behind the CU-mate's tiles as one might hope -- the product takes 28.7 us per step of a chain against 29.3 us per launch and
-    // 20.5 us of matrix pipe: the barriers of a step bring the workgroup's wavefronts into step again.
-    for (int s = 0; s < P.nsteps; ++s) {
+    // behind the CU-mate's tiles as one might hope -- with all workgroups on every step the product takes 28.7 us per step of a
+    // chain against 29.3 us per launch and 20.5 us of matrix pipe: the barriers of a step bring the workgroup's
+    // wavefronts into step again.  Hence the lanes of a chain: this workgroup runs the steps of ITS lane, on a larger share of their tiles.
+    for (int s = s_begin; s < s_end; ++s) {
     // (the lane's coordinates are taken afresh in every step: everything derived from them -- addresses in LDS, offsets into z --
     // would otherwise be computed once in front of the loop and held in registers through the product, which has none to spare)
     int tid = tid0;
@@ -144,7 +155,7 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
     int* const status_s = S.status; int* const iters_s = S.iters; double* const step_s = S.step; int* const need_s = S.need;
     int tile = slot * 4 + wv;
     // (no wavefront of the workgroup reads sD / sF of the previous step any more when the staging below overwrites them)
-    if (s) __syncthreads();
+    if (s != s_begin) __syncthreads();
     fa_request_a(A, P.img, tile < tiles ? tile : 0, lane);           // in flight while the data are staged
     {
         const int np = P.batch - p0 < FA_CT * 16 ? P.batch - p0 : FA_CT * 16;       // problems of this group
@@ -340,7 +351,7 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_affine(FaParams P) {
     }
 }
 
-hipError_t fmpc_launch_affine(FaParams P, int num_cu, hipStream_t stream) {
+hipError_t fmpc_launch_affine(FaParams P, int num_cu, hipStream_t stream, const unsigned* supersedes) {
     if (P.n != 27 || 2 * P.n + 2 > FA_KC || 7 * FA_THREADS < FA_CT * 16 * P.n) return hipErrorInvalidValue;
     if (P.nsteps < 0 || P.nsteps > FMPC_STRETCH_MAX) return hipErrorInvalidValue;
     if (P.nsteps == 0) {                                          // a single step: the per-call fields
@@ -362,14 +373,28 @@ hipError_t fmpc_launch_affine(FaParams P, int num_cu, hipStream_t stream) {
     if (P.ldz < P.rows) P.ldz = P.rows;
     static const bool no_nt = [] { const char* e = getenv("FMPC_AFFINE_NO_NT"); return e && e[0] == '1'; }();       // A/B switch
     const bool nt = P.zout && !no_nt && P.ldz % 16 == 0 && aligned;
-    // two workgroups of four wavefronts per CU are resident: that many workgroups share the groups of 64 problems (a workgroup
-    // beyond the resident set would start when another ends)
-    int wpg = (2 * num_cu) / ngroups;                            // workgroups per group
-    const int wpg_max = (P.tiles_used + 3) / 4;                  // one tile per wavefront at least
-    if (wpg < 1) wpg = 1;
-    if (wpg > wpg_max) wpg = wpg_max;
+    // two workgroups of four wavefronts per CU are resident: that many workgroups share the (chain lane, group of 64 problems)
+    // pairs, one tile per wavefront at least (a workgroup beyond the resident set would start when another ends).  The plan: one
+    // lane for a single step -- wpg = 2 num_cu / ngroups --, for a chain as many as pay (fmpc_host_plan_lanes).
+    // FMPC_STRETCH_LANES: the most lanes a chain may take (a measurement switch, read at every chain; 1 = the steps one after another)
+    int cap = FMPC_STRETCH_LANES_DEFAULT;
+    if (P.nsteps > 1) { const char* e = getenv("FMPC_STRETCH_LANES"); if (e && e[0]) cap = atoi(e); }
+    if (cap < 1 || !supersedes) cap = 1;
+    int lane_of[FMPC_STRETCH_MAX], wpg = 1;
+    P.nlanes = fmpc_host_plan_lanes(P.nsteps, supersedes, ngroups, 2 * num_cu, P.tiles_used, cap, lane_of, &wpg);
     P.wgs_per_group = wpg;
-    const int grid = ngroups * wpg;
+    P.wgs_per_lane = ngroups * wpg;
+    {   // steps[] in lane order, chain order within a lane
+        FaStep in_chain_order[FMPC_STRETCH_MAX];
+        for (int s = 0; s < P.nsteps; ++s) in_chain_order[s] = P.steps[s];
+        int k = 0;
+        for (int l = 0; l < P.nlanes; ++l) {
+            P.lane_begin[l] = k;
+            for (int s = 0; s < P.nsteps; ++s) if (lane_of[s] == l) P.steps[k++] = in_chain_order[s];
+        }
+        for (int l = P.nlanes; l <= FMPC_STRETCH_MAX; ++l) P.lane_begin[l] = k;
+    }
+    const int grid = P.nlanes * ngroups * wpg;
     if (P.zout && nt) hipLaunchKernelGGL((fmpc_cold_affine<true, true>), dim3(grid), dim3(FA_THREADS), 0, stream, P);
     else if (P.zout) hipLaunchKernelGGL((fmpc_cold_affine<true, false>), dim3(grid), dim3(FA_THREADS), 0, stream, P);
     else hipLaunchKernelGGL((fmpc_cold_affine<false, false>), dim3(grid), dim3(FA_THREADS), 0, stream, P);
