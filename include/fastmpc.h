@@ -732,8 +732,9 @@ unsigned long long fmpc_alloc_generation(void);
  * After a chain, fmpc_last_dispatch / fmpc_last_dual_form read as after a per-step call (handed_over: of the last step that
  * was not superseded).  fmpc_last_stretch: the steps and launches of the chain of this handle that was launched last (0, 0 before
  * the first).  Measured at (27, 144, 30), 2000 problems, four buffer sets in rotation, recorded regions of 20 / 400 steps:
- * 25.5 / 23.9 us of device time per step with the steps of a chain in four lanes, 31.2 / 29.4 us with the steps one after
- * another, 31.7 / 31.2 us with two launches per step (README.md).
+ * 21.4 / 21.4 us of device time per step with the steps of a chain in four lanes and the u rows of z through nu+ (24.6 / 24.4 us
+ * with every tile of z as one product over the data, FMPC_AFFINE_DIRECT=1, on the same box), 31.2 / 29.4 us with the steps one after another,
+ * 31.7 / 31.2 us with two launches per step (README.md).
  */
 #define FMPC_STRETCH_MAX 16
 int fmpc_stretch_begin(void* stream);

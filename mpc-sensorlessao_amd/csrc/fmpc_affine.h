@@ -38,6 +38,12 @@ struct FaParams {
     // steps [lane_begin[lane], lane_begin[lane + 1]) of steps[], which the launcher has put into lane order.  One lane: all steps.
     int nlanes, wgs_per_lane;
     int lane_begin[FMPC_STRETCH_MAX + 1];
+    // the u rows through nu+ (fmpc_kernel_affine_nu.hip; fmpc_host_build_affine): img continues behind the nu tiles, from tile jbase on,
+    // with two tiles per stage 1 .. T-1 of the padded [J_j | nuc_j]
+    const double* imgG;                 // [u tile][FA_NU_KS][64]: [diag(wc) B' | umid - wc o cu] per u tile; NULL: not built
+    const int* plan;                    // [T] FmpcNuStage
+    int jbase, nu_work;                 // nu_work: matrix instructions per column tile of all items without nu+ (fmpc_host_nu_parts)
+    int nparts, nitems, swap;           // set by the launcher: parts per stage item; stage items x parts + nu_out items; fmpc_host_nu_swap
 };
 
 // The most lanes a chain takes unless FMPC_STRETCH_LANES says otherwise (DESIGN.md section 7 has the measurement behind it)
@@ -45,5 +51,8 @@ struct FaParams {
 // supersedes[j] (a chain, nsteps > 1): bit i set = step j writes exactly the output tuple of step i < j.  Steps that share no tuple
 // are independent (fmpc_stretch_accepts) and may run side by side, in lanes; NULL: one lane, the steps one after another.
 hipError_t fmpc_launch_affine(FaParams P, int num_cu, hipStream_t stream, const unsigned* supersedes = nullptr);
-// The same step as TWO chained products per stage (nu+_s = J_s d, u_s = Bw nu+_s; the x rows directly): 20 % fewer matrix
-// instructions and one task per wavefront.  z_out required, nu_out not served (the caller takes fmpc_launch_affine then).
+// fmpc_launch_affine hands the calls that write z to this launcher (fmpc_kernel_affine_nu.hip) unless FMPC_AFFINE_DIRECT=1 is set (read
+// at every launch: the A/B switch of measurements and tests): the u tiles of the stages 1 .. T-1 with 7 k-steps from nu+_j, which the
+// wavefront that owns the stage item computes itself; all other tiles, stage 0 among them, exactly as fmpc_cold_affine computes them.
+// P: as fmpc_launch_affine has prepared it (steps in lane order, wgs_per_group, wgs_per_lane, tiles_used, ldz); grid = its workgroups.
+hipError_t fmpc_launch_affine_nu(FaParams P, int grid, bool nt, hipStream_t stream);

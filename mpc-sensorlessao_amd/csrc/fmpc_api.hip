@@ -1324,7 +1324,7 @@ static int fmpc_build_first_move(fmpc_handle h, double k, hipStream_t stream) {
     // affine form of the whole step without w: [Kz | zc] as matrix-core images; the (x0, x0_pre) blocks of E, Ep likewise
     h->fa_valid = 0;
     FmpcAffineOut AO;
-    size_t oA = 0, oAE = 0, oAEp = 0, oAl = 0, oAlp = 0, oAd = 0;
+    size_t oA = 0, oAE = 0, oAEp = 0, oAl = 0, oAlp = 0, oAd = 0, oAG = 0, oAP = 0;
     bool fa_ok = !h->fa_disabled && 2 * n + 2 <= FA_KC;
     if (fa_ok) {
         FmpcAffineIn AI;
@@ -1346,6 +1346,11 @@ static int fmpc_build_first_move(fmpc_handle h, double k, hipStream_t stream) {
         fmpc_host_mfma_a_images(Ep64.data(), 64, imgEp);
         oA = push(AO.img); oAE = push(imgE); oAEp = push(imgEp); oAl = push(el); oAlp = push(epl);
         oAd = push(std::vector<double>(4096, 0.0));
+        if (!AO.imgG.empty()) {                                   // the u rows through nu+: u-tile images, the tile plan (ints, two per double)
+            std::vector<double> planw((AO.plan.size() * sizeof(FmpcNuStage) + sizeof(double) - 1) / sizeof(double), 0.0);
+            memcpy(planw.data(), AO.plan.data(), AO.plan.size() * sizeof(FmpcNuStage));
+            oAG = push(AO.imgG); oAP = push(planw);
+        }
     }
     // the first-move form as a product over many realisations (fmpc_kernel_loopu0.hip): [K0 | u0c], E, Ep as matrix-core images
     // over d -- in the order [x0; x0_pre; B u1; B u2; 1] behind the loop-input kernel, in blocks of 28 with the constant in
@@ -1378,6 +1383,9 @@ static int fmpc_build_first_move(fmpc_handle h, double k, hipStream_t stream) {
         memset(&A, 0, sizeof(A));
         A.n = n; A.m = m; A.T = T; A.nb = h->nb; A.has_xf = h->has_xf; A.rows = AO.rows; A.tiles = AO.tiles; A.nu_rows = AO.nu_rows; A.nu_tiles = AO.nu_tiles;
         A.img = h->fm_pool + oA; A.imgE = h->fm_pool + oAE; A.imgEp = h->fm_pool + oAEp; A.elin = h->fm_pool + oAl; A.eplin = h->fm_pool + oAlp; A.dump = h->fm_pool + oAd;
+        if (!AO.imgG.empty()) {
+            A.imgG = h->fm_pool + oAG; A.plan = (const int*)(h->fm_pool + oAP); A.jbase = AO.jbase; A.nu_work = fmpc_host_nu_work(AO.plan);
+        }
         A.dx0T = P.dx0T; A.e0 = O.e0; A.ep0 = O.ep0; A.normE = O.normE; A.norme = O.norme; A.normEp = O.normEp; A.normep = O.normep; A.rd2_0 = h->pn_rd2_0;
         h->fa_valid = 1;
     }

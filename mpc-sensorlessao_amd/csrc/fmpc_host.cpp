@@ -3,6 +3,7 @@
 #include "fmpc_host.h"
 #include "fmpc_bank.h"
 
+#include <algorithm>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -698,6 +699,107 @@ void fmpc_host_build_affine(const FmpcAffineIn& In, FmpcAffineOut& Out) {
     }
     fmpc_host_mfma_a_images(Jn.data(), Out.nu_rows, imgn);
     Out.img.insert(Out.img.end(), imgn.begin(), imgn.end());
+    // ---- the u rows through nu+ (fmpc_kernel_affine_nu.hip): u_st = G [nu+_st ; 1], nu+_st = [J_st | nuc_st] d
+    // per stage 1 .. T-1 the 32 rows [J_st | nuc_st] (27), the unit row on the constant column of d (entry 27 of the result is 1.0
+    // exactly), four zero rows
+    Out.jbase = Out.tiles + Out.nu_tiles;
+    fmpc_host_plan_nu(m, n, T, Out.plan);
+    if (n != 27) { Out.imgG.clear(); return; }                     // (n + 1 = 28 = 4 FA_NU_KS: the only size the kernel is built for)
+    std::vector<double> Jp((size_t)32 * FA_KC);
+    for (int st = 1; st < T; ++st) {
+        std::fill(Jp.begin(), Jp.end(), 0.0);
+        for (int r = 0; r < n; ++r) {
+            for (int c = 0; c < nd; ++c) Jp[(size_t)r * FA_KC + c] = In.J[((size_t)st * n + r) * ncJ + c];
+            Jp[(size_t)r * FA_KC + nd] = In.nuc[(size_t)st * n + r];
+        }
+        Jp[(size_t)n * FA_KC + nd] = 1.0;
+        fmpc_host_mfma_a_images(Jp.data(), 32, imgn);
+        Out.img.insert(Out.img.end(), imgn.begin(), imgn.end());
+    }
+    // per u tile [diag(wc) B' | umid - wc o cu] of its 16 rows: each entry rounded to double once
+    int nut = 0;
+    for (int st = 0; st < T; ++st) nut += Out.plan[st].nu;
+    Out.imgG.assign((size_t)nut * FA_NU_KS * 64, 0.0);
+    for (int st = 1; st < T; ++st)
+        for (int u = 0; u < Out.plan[st].nu; ++u) {
+            double* im = &Out.imgG[(size_t)(Out.plan[st].ub + u) * FA_NU_KS * 64];
+            for (int r = 0; r < 16; ++r) {
+                const int j = 16 * (Out.plan[st].tb + u) + r - st * s;                  // actuator of the row
+                for (int c = 0; c <= n; ++c) {
+                    const ld v = c < n ? wc[j] * (ld)In.bt[(size_t)j * n + c] : (ld)In.umid[j] - wc[j] * cu[j];
+                    im[(size_t)(c >> 2) * 64 + (c & 3) * 16 + r] = (double)v;
+                }
+            }
+        }
+}
+
+void fmpc_host_plan_nu(int m, int n, int T, std::vector<FmpcNuStage>& plan) {
+    const int s = n + m, tiles = (T * s + 15) / 16;
+    plan.assign(T > 0 ? T : 0, FmpcNuStage{0, 0, 0, 0});
+    int ub = 0;
+    for (int j = 0; j < T; ++j) {
+        const int tb = (s * j + 15) / 16;                            // first tile whose first row lies in stage j
+        int te = (s * (j + 1) + 15) / 16;
+        if (te > tiles) te = tiles;
+        int nu = j >= 1 ? (s * j + m) / 16 - tb : 0;                  // tiles with 16 (t + 1) <= s j + m: a prefix of the item's
+        if (nu < 0) nu = 0;
+        if (nu > te - tb) nu = te - tb;
+        plan[j] = FmpcNuStage{tb, nu, te - tb - nu, ub};
+        ub += nu;
+    }
+}
+
+int fmpc_host_nu_work(const std::vector<FmpcNuStage>& plan) {
+    int work = 0;
+    for (const FmpcNuStage& S : plan) work += 7 * S.nu + 14 * S.nd;
+    return work;
+}
+
+int fmpc_host_nu_parts(int T, int work, int W) {
+    if (T < 1 || W < 1) return 1;
+    int bestP = 1; double best = -1.0;
+    for (int P = 1; P <= 8; ++P) {
+        const double cost = (double)((T * P + W - 1) / W) * (28.0 + (double)work / ((double)T * P));
+        if (best < 0.0 || cost < best) { best = cost; bestP = P; }
+    }
+    return bestP;
+}
+
+int fmpc_host_nu_swap(int T, int parts, int W) {
+    return parts == 1 && W >= 1 && T > W - 1 && T % W != 0 ? W - 1 : 0;
+}
+
+// debug exports (tests/test_host_affine_nu.py): the tile plan; the affine builder on caller-supplied model arrays
+extern "C" int fmpc_debug_plan_nu(int m, int n, int T, int W, int* plan4, int* parts, int* swap) {
+    if (m < 1 || n < 1 || T < 1 || !plan4) return -1;
+    std::vector<FmpcNuStage> plan;
+    fmpc_host_plan_nu(m, n, T, plan);
+    for (int j = 0; j < T; ++j) { plan4[4 * j] = plan[j].tb; plan4[4 * j + 1] = plan[j].nu; plan4[4 * j + 2] = plan[j].nd; plan4[4 * j + 3] = plan[j].ub; }
+    const int np = fmpc_host_nu_parts(T, fmpc_host_nu_work(plan), W);
+    if (parts) *parts = np;
+    if (swap) *swap = fmpc_host_nu_swap(T, np, W);
+    return 0;
+}
+// the tiles [*b, *e) of cnt that part p of `parts` takes (FMPC_NU_CUT, as the kernel applies it)
+extern "C" int fmpc_debug_nu_cut(int cnt, int p, int parts, int* b, int* e) {
+    if (cnt < 0 || parts < 1 || p < 0 || p >= parts || !b || !e) return -1;
+    *b = FMPC_NU_CUT(cnt, p, parts); *e = FMPC_NU_CUT(cnt, p + 1, parts);
+    return 0;
+}
+// arr: bt, umax, umin, umid, xmid, R2, rl, Q2, Qf2, ql, qfl, a1, a2, J (nb n x 2 n), nuc.  Out: Kz [rows][FA_KC], the J images
+// [2 (T - 1)][FA_KS][64], the u-tile images [u tiles][FA_NU_KS][64] (any of them may be NULL).  Returns the u tiles, < 0 on bad arguments.
+extern "C" int fmpc_debug_build_affine_nu(int n, int m, int T, int nb, int has_xf, double k, const double* const* arr, double* Kz, double* imgJ, double* imgG) {
+    if (n != 27 || m < 1 || T < 1 || nb < T || !arr) return -1;
+    FmpcAffineIn In;
+    In.n = n; In.m = m; In.T = T; In.nb = nb; In.has_xf = has_xf; In.ncJ = 2 * n; In.k = k;
+    In.bt = arr[0]; In.umax = arr[1]; In.umin = arr[2]; In.umid = arr[3]; In.xmid = arr[4]; In.R2 = arr[5]; In.rl = arr[6]; In.Q2 = arr[7];
+    In.Qf2 = arr[8]; In.ql = arr[9]; In.qfl = arr[10]; In.a1 = arr[11]; In.a2 = arr[12]; In.J = arr[13]; In.nuc = arr[14];
+    FmpcAffineOut Out;
+    fmpc_host_build_affine(In, Out);
+    if (Kz) std::copy(Out.Kz.begin(), Out.Kz.end(), Kz);
+    if (imgJ) std::copy(Out.img.begin() + (size_t)Out.jbase * FA_KS * 64, Out.img.end(), imgJ);
+    if (imgG) std::copy(Out.imgG.begin(), Out.imgG.end(), imgG);
+    return (int)(Out.imgG.size() / (FA_NU_KS * 64));
 }
 
 // ---- cold-start step with the ramp-rate rows: constants of the Woodbury form (fmpc_host.h)

@@ -115,13 +115,34 @@ struct FmpcAffineIn {
     const double *J, *nuc;
     double k;
 };
+#define FA_NU_KS 7                      // k-steps of a u tile through nu+: n = 27 multipliers of the stage + the constant
+struct FmpcNuStage { int tb, nu, nd, ub; };   // first tile of the item, its u tiles, its direct tiles, index of its first u tile among all u tiles
+#define FMPC_NU_CUT(cnt, p, parts) ((cnt) * (p) / (parts))
 struct FmpcAffineOut {
     int rows, tiles;                    // T (n + m); 16-row tiles
     int nu_rows, nu_tiles;              // nb n rows of nu+ = nuc + J d, as further tiles behind those of z
     std::vector<double> Kz;             // rows x FA_KC row-major (checks)
-    std::vector<double> img;            // matrix-core operand images: [tile][k-step][lane = 16 (k mod 4) + (row mod 16)], z tiles then nu tiles
+    std::vector<double> img;            // matrix-core operand images: [tile][k-step][lane = 16 (k mod 4) + (row mod 16)], z tiles then nu tiles,
+                                        // then from tile jbase on two tiles per stage 1 .. T-1: the padded [J_j | nuc_j] (below)
+    // the u rows through nu+ (fmpc_kernel_affine_nu.hip)
+    int jbase;                          // tiles + nu_tiles
+    std::vector<FmpcNuStage> plan;      // [T]
+    std::vector<double> imgG;           // [u tile][FA_NU_KS][64]: [diag(wc) B' | umid - wc o cu] of the tile's 16 rows, u tiles in row order
 };
 void fmpc_host_build_affine(const FmpcAffineIn& In, FmpcAffineOut& Out);
+// Tile plan of z for the u rows through nu+.  Tiles are the global 16-row tiles of z (rows 16 t ..).  A U TILE of stage j >= 1 lies wholly
+// inside the u rows of stage j; every other tile is DIRECT (all of stage 0, tiles with x rows, tiles across a block boundary, the last
+// partial tile).  Stage item j owns the tiles whose first row lies in stage j: its u tiles come first, its direct tiles behind them.
+// An item splits into `parts` parts: part p takes the u tiles FMPC_NU_CUT(nu, p, parts) .. FMPC_NU_CUT(nu, p + 1, parts) of the item and
+// its direct tiles likewise (every part recomputes nu+ of the stage).  Pure functions (tests/test_host_affine_nu.py).
+void fmpc_host_plan_nu(int m, int n, int T, std::vector<FmpcNuStage>& plan);
+// parts per item for W wavefronts per (lane, group): the smallest makespan ceil(T P / W) (nu+ cost + item cost / P), P = 1 .. 8, in
+// matrix instructions per column tile (nu+: 2 x 14, a u tile 7, a direct tile 14); the smaller P on a tie
+int fmpc_host_nu_work(const std::vector<FmpcNuStage>& plan);   // sum over the items of 7 nu + 14 nd
+int fmpc_host_nu_parts(int T, int work, int W);
+// Stage 0 is the heaviest item (all its tiles are direct).  With one part per item, dealt round-robin to W wavefronts, it changes places
+// with the stage whose wavefront has an item less than the first ones, if there is one: returns that stage, 0 for none
+int fmpc_host_nu_swap(int T, int parts, int W);
 // Lane plan of a CHAIN of affine steps: which steps of one launch run side by side.  The steps with one output tuple (a class: step j
 // names in supersedes[j] the earlier steps whose outputs are exactly its own, bit i = step i) are ordered and stay together in
 // chain order; different classes are independent (fmpc_stretch_accepts) and may go to different LANES, each lane with its own

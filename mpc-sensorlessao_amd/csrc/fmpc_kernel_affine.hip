@@ -92,6 +92,8 @@ __device__ __forceinline__ bool fa_decide(const FaParams& P, double qe, double q
     return fin && (rp2 > 4e-16 || rho2 > 4e-12) && e2 <= 0.5 * rho2;
 }
 
+// (fmpc_affine_dev.h holds a copy of the request / await helpers above, of the staging and of the decision forms below, for
+// fmpc_kernel_affine_nu.hip: a change to the decision here has to be made there as well.)
 // Operand roles: the PROBLEMS are the rows of the matrix instruction (A operand: lane (g, i) holds d'[p0 + i][4 q + g]), the rows
 // of z its columns (B operand: lane (g, j) holds Kz[16 t + j][4 q + g], a 512-byte image per k-step).  Result register r of
 // lane (g, j) is then z[p0 + 4 r + g][16 t + j]: the 16 lanes of a row group hold 16 CONSECUTIVE entries of one problem's z --
@@ -395,6 +397,12 @@ hipError_t fmpc_launch_affine(FaParams P, int num_cu, hipStream_t stream, const 
         for (int l = P.nlanes; l <= FMPC_STRETCH_MAX; ++l) P.lane_begin[l] = k;
     }
     const int grid = P.nlanes * ngroups * wpg;
+    // The calls that write z: the u rows through nu+ (fmpc_kernel_affine_nu.hip), same lanes, groups and workgroups.
+    // FMPC_AFFINE_DIRECT=1: every tile as one product over d, the kernel below (a measurement switch, read at every launch)
+    if (P.zout && P.imgG) {
+        const char* e = getenv("FMPC_AFFINE_DIRECT");
+        if (!(e && e[0] == '1')) return fmpc_launch_affine_nu(P, grid, nt, stream);
+    }
     if (P.zout && nt) hipLaunchKernelGGL((fmpc_cold_affine<true, true>), dim3(grid), dim3(FA_THREADS), 0, stream, P);
     else if (P.zout) hipLaunchKernelGGL((fmpc_cold_affine<true, false>), dim3(grid), dim3(FA_THREADS), 0, stream, P);
     else hipLaunchKernelGGL((fmpc_cold_affine<false, false>), dim3(grid), dim3(FA_THREADS), 0, stream, P);

@@ -19,6 +19,20 @@ for want_z in (True, False):
         h.solve_device(x0, x0p, None, None, nu0, 1, 1e-2, z_out=z if want_z else None, status=st, iters=it, u0_out=u0, want_z=want_z)
         torch.cuda.synchronize()
     out = (C.c_ulonglong * 8192)()
+    if want_z and os.environ.get("FMPC_AFFINE_DIRECT") != "1" and hasattr(lib, "fmpc_debug_affine_nu_trace"):
+        # the calls that write z run fmpc_cold_nu (fmpc_kernel_affine_nu.hip), which has stamps of its own: 0 start, 1 data staged, 2 forms
+        # done, of the wavefront's first item 4 direct tiles done, 5 nu+ done, 6 u tiles done; 3 end
+        lib.fmpc_debug_affine_nu_trace.argtypes = [C.c_void_p]; lib.fmpc_debug_affine_nu_trace(out)
+        t = np.array(out[:], dtype=np.int64).reshape(1024, 8)
+        used = t[:, 0] > 0
+        k = (t[used] - t[used, 0].min()) * 0.01
+        md_ = lambda a: float(np.median(a))
+        print("   u rows through nu+, %d workgroups, medians (us): staged %.1f, forms done %.1f; first item of wavefront 0: (b) %.1f, (a) %.1f, (c) %.1f; end %.1f (%.1f..%.1f)"
+              % (len(k), md_(k[:, 1]), md_(k[:, 2]), md_(k[:, 4] - k[:, 2]), md_(k[:, 5] - k[:, 4]), md_(k[:, 6] - k[:, 5]), md_(k[:, 3]), k[:, 3].min(), k[:, 3].max()))
+        wpg = 16
+        print("   median end by workgroup slot in its group:", " ".join("%.1f" % float(np.median(k[np.arange(len(k)) % wpg == sl, 3])) for sl in range(wpg)))
+        print("   latest end by workgroup slot in its group:", " ".join("%.1f" % float(k[np.arange(len(k)) % wpg == sl, 3].max()) for sl in range(wpg)))
+        continue
     lib.fmpc_debug_affine_trace.argtypes = [C.c_void_p]; lib.fmpc_debug_affine_trace(out)
     t = np.array(out[:], dtype=np.int64).reshape(1024, 8)
     if hasattr(lib, "fmpc_debug_affine_trace_cycles"):
