@@ -513,6 +513,69 @@ int fmpc_loop_records_run_bank_device(fmpc_handle h, int batch, int steps, const
                                       void* stream);
 
 /*
+ * KKT report: how far an iterate (z, nu) of every problem of a batch is from the point the reference iterates to, in the
+ * reference's own terms (inf_newton_solver.m:11-22), on the device.  Conventions of the reference: cost z'Hz + g'z, no 1/2;
+ * H, g of fast_mpc_objective.m WITH the handle's q, r, qf; P, h of fast_mpc_ineq_const.m; C, b of fast_mpc_eq_const.m.  For one
+ * problem with iterate z, multipliers nu (nu_len of fmpc_dims) and barrier weight k:
+ *     s   = h - P z                        slacks: the box rows; plus the ramp rows when they are in force (u_prev below)
+ *     d_i = 1 / s_i
+ *     r_d = 2 H z + g + k P' d + C' nu     inf_newton_solver.m:12, d taken at z
+ *     r_p = C z - b                        inf_newton_solver.m:13 (with xf: the extra n rows x_T - xf)
+ * Report row of problem p, FMPC_KKT_FIELDS doubles at report + p*ldr:
+ *     [FMPC_KKT_RD]        rd         ||r_d||_2
+ *     [FMPC_KKT_RP]        rp         ||r_p||_2                 the reference's n_g (:17)
+ *     [FMPC_KKT_NR]        nr         sqrt(rd^2 + rp^2)         the reference's n_r (:14, :16; the commented fprintf at :18)
+ *     [FMPC_KKT_COST]      cost       z'Hz + g'z
+ *     [FMPC_KKT_BARRIER]   barrier    -sum_i log s_i            NaN when some s_i <= 0
+ *     [FMPC_KKT_MIN_SLACK] min_slack  min_i s_i
+ * flags[p] (int, nullable):
+ *     FMPC_KKT_CONVERGED  (bit 0)  the reference's exit test nr <= 1e-6 && rp <= 1e-8 (:19)
+ *     FMPC_KKT_INFEASIBLE (bit 1)  min_slack <= 0: the iterate is outside the barrier's domain
+ * With bit 1 set, rd, nr and barrier are NaN and bit 0 is clear; rp, cost and min_slack are still valid.  nu == NULL gives the
+ * primal-only report (for the calls that did not ask for nu_out): rd and nr are NaN, bit 0 is clear, the rest is computed.
+ * Device pointers: x0, x0_pre n per problem (x0_pre NULL: zeros; ignored on a VAR(1) handle), w T n (NULL: zeros), z rows ldz
+ * doubles apart (0: contiguous N_z, else >= N_z: the padded rows of fmpc_set_z_ld / fmpc_solve_u0_device_ld are read as they are),
+ * nu nu_len, report rows ldr doubles apart (0: FMPC_KKT_FIELDS, else >= it; nothing between the rows is written).
+ * u_prev (m per problem): non-NULL on a handle with fmpc_set_ramp, the ramp rows of VAR_1/fast_mpc_ineq_const.m:58-76 are part of
+ * P, h; NULL: box rows only; non-NULL without fmpc_set_ramp: FMPC_E_UNSUPPORTED.
+ * Before the device is touched: FMPC_E_DIM for batch < 0, k <= 0 or not finite, ldz < 0 or 0 < ldz < N_z, 0 < ldr <
+ * FMPC_KKT_FIELDS; FMPC_E_NULL for a NULL h, x0, z or report; FMPC_OK with nothing enqueued for batch == 0.
+ * n <= 32 with diagonal Q, Qf, R and no ramp rows (the reference's configuration): panels of 16 problems on the matrix cores
+ * (B u_j, A1 x_j, A2 x_{j-1}, B' nu_j, A1' nu_{j+1}, A2' nu_{j+2} per stage), the slacks, the logarithms and the diagonal terms
+ * formed where u_j and x_{j+1} already are, z read once; the per-stage sums are added in a fixed order (no atomics: the same
+ * inputs give the same bits on every call).  Any other size, dense weights or ramp rows: one workgroup per problem, the fallback
+ * without a speed claim.  The call takes the handle's lock, does not synchronise, and allocates only when the panel kernel's
+ * scratch has to grow (FMPC_E_ALLOC while `stream` is being captured: call once with the same batch before a capture).
+ *
+ * fmpc_kkt_report_bank_device: the same report where A1, A2 of problem p are those of model model_of[p] of the bank (device int
+ * array; NULL = model p, then batch <= count, else FMPC_E_UNSUPPORTED); B, the weights and the bounds stay the handle's.
+ * FMPC_E_UNSUPPORTED without a bank, and with u_prev (the bank has no ramp rows).  A problem whose index is outside [0, count)
+ * gets an all-NaN row and flags 0; nothing of a model is read for it.  One workgroup per problem at every size.
+ * fmpc_kkt_report: host pointers, synchronous, the same rules; z and report with their paddings as given.
+ */
+#define FMPC_KKT_FIELDS     6
+#define FMPC_KKT_RD         0
+#define FMPC_KKT_RP         1
+#define FMPC_KKT_NR         2
+#define FMPC_KKT_COST       3
+#define FMPC_KKT_BARRIER    4
+#define FMPC_KKT_MIN_SLACK  5
+#define FMPC_KKT_CONVERGED  1
+#define FMPC_KKT_INFEASIBLE 2
+int fmpc_kkt_report_device(fmpc_handle h, int batch,
+                           const double* x0, const double* x0_pre, const double* w, const double* u_prev,
+                           const double* z, long long ldz, const double* nu, double k,
+                           double* report, int ldr, int* flags, void* stream);
+int fmpc_kkt_report_bank_device(fmpc_handle h, int batch, const int* model_of,
+                                const double* x0, const double* x0_pre, const double* w, const double* u_prev,
+                                const double* z, long long ldz, const double* nu, double k,
+                                double* report, int ldr, int* flags, void* stream);
+int fmpc_kkt_report(fmpc_handle h, int batch,
+                    const double* x0, const double* x0_pre, const double* w, const double* u_prev,
+                    const double* z, long long ldz, const double* nu, double k,
+                    double* report, int ldr, int* flags);
+
+/*
  * Stored cold-start factor per model of the bank.  The reference's loop calls the solver from the cold start at every timestep
  * (README.md:548-556: x_init = [], n_fix = 1), where z is the mid-box point (fast_mpc_init.m:12-27), so Phi does not depend on the
  * data and Y_j = C_j Phi^-1 C_j' and its block Cholesky factor (inf_newton_solver.m:24-32) depend only on the model j, on k and on

@@ -4,7 +4,9 @@ behind include/fastmpc.h; nothing here solves on the CPU."""
 from ._lib import (FastMPCError, FMPC_OK, FMPC_W_LINESEARCH, FMPC_E_NULL, FMPC_E_DIM,
                    FMPC_E_UNSUPPORTED, FMPC_E_NOT_PD_PHI, FMPC_E_NOT_PD_SCHUR, FMPC_E_HIP,
                    FMPC_E_ALLOC, FMPC_E_NO_DEVICE, FMPC_PATH_GENERIC, FMPC_PATH_WAVE, FMPC_PATH_SHARED,
-                   FMPC_PATH_PANEL, FMPC_PATH_RAMP, FMPC_PATH_RAMP_WS, LIB_PATH, load)
+                   FMPC_PATH_PANEL, FMPC_PATH_RAMP, FMPC_PATH_RAMP_WS, LIB_PATH, load,
+                   FMPC_KKT_FIELDS, FMPC_KKT_RD, FMPC_KKT_RP, FMPC_KKT_NR, FMPC_KKT_COST, FMPC_KKT_BARRIER,
+                   FMPC_KKT_MIN_SLACK, FMPC_KKT_FIELD_NAMES, FMPC_KKT_CONVERGED, FMPC_KKT_INFEASIBLE)
 from .handle import FastMPCHandle
 from .fast_mpc2 import Fast_MPC2, Fast_MPC2_VAR1, deinterleave
 from . import synthetic
@@ -19,4 +21,6 @@ from . import _lib
 
 __all__ = ["FastMPCHandle", "Fast_MPC2", "Fast_MPC2_VAR1", "deinterleave", "FastMPCError",
            "ShardedFastMPC", "shard_range", "ClosedLoop", "AOLoop", "SolveLanes", "RecordedSolves", "PhaseDiversityEstimator", "synthetic", "load", "LIB_PATH",
-           "identify_var2_device", "identify_var_device", "validate_var_device", "var_fit_workspace_bytes", "LoopRecords"]
+           "identify_var2_device", "identify_var_device", "validate_var_device", "var_fit_workspace_bytes", "LoopRecords",
+           "FMPC_KKT_FIELDS", "FMPC_KKT_RD", "FMPC_KKT_RP", "FMPC_KKT_NR", "FMPC_KKT_COST", "FMPC_KKT_BARRIER", "FMPC_KKT_MIN_SLACK",
+           "FMPC_KKT_FIELD_NAMES", "FMPC_KKT_CONVERGED", "FMPC_KKT_INFEASIBLE"]

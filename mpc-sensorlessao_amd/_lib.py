@@ -34,6 +34,12 @@ FMPC_PATH_RAMP_WS = 7
 FMPC_PREC_F64 = 0
 FMPC_PREC_F32_MIXED = 1
 FMPC_MAX_REFINEMENT = 3
+# fmpc_kkt_report*: fields of a report row, flag bits
+FMPC_KKT_FIELDS = 6
+FMPC_KKT_RD, FMPC_KKT_RP, FMPC_KKT_NR, FMPC_KKT_COST, FMPC_KKT_BARRIER, FMPC_KKT_MIN_SLACK = range(6)
+FMPC_KKT_FIELD_NAMES = ("rd", "rp", "nr", "cost", "barrier", "min_slack")
+FMPC_KKT_CONVERGED = 1
+FMPC_KKT_INFEASIBLE = 2
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -90,6 +96,9 @@ SIGNATURES = {
     "fmpc_solve_bank_device": (C.c_int, [_vp, C.c_int, _vp] + [_vp] * 5 + [C.c_int, C.c_double] + [_vp] * 6 + [_vp]),
     "fmpc_loop_inputs_bank_device": (C.c_int, [_vp, C.c_int, _vp] + [_vp] * 7 + [_vp]),
     "fmpc_loop_records_bank_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int] + [_vp] * 4 + [C.c_longlong, C.c_int, _vp] + [C.c_double] * 3 + [_vp] * 5 + [_vp]),
+    "fmpc_kkt_report_device": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [C.c_longlong, _vp, C.c_double, _vp, C.c_int, _vp, _vp]),
+    "fmpc_kkt_report_bank_device": (C.c_int, [_vp, C.c_int, _vp] + [_vp] * 5 + [C.c_longlong, _vp, C.c_double, _vp, C.c_int, _vp, _vp]),
+    "fmpc_kkt_report": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [C.c_longlong, _vp, C.c_double, _vp, C.c_int, _vp]),
     "fmpc_loop_records_run_bank_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp] + [_vp] * 5 + [C.c_double] * 3 + [_vp] * 4 + [_vp]),
     "fmpc_bank_prefactor_device": (C.c_int, [_vp, C.c_double, _vp]),
     "fmpc_bank_prefactor_count": (C.c_int, [_vp]),

@@ -22,6 +22,7 @@
 #include "fmpc_rampcold.h"
 #include "fmpc_bank.h"
 #include "fmpc_records.h"
+#include "fmpc_kkt.h"
 #define FMPC_PRODUCT_MIN_BATCH_DEFAULT 65   // closed-loop steps with first moves only: the product form from this many realisations on
 #include "fmpc_alloc.h"                    // owned, counted buffers (fmpc_alloc_generation), shared with fmpc_est_api.hip
 
@@ -217,6 +218,7 @@ struct fmpc_handle_s {
     DevBuf<double> rec_w; int rec_ready = 0, rec_panel = 0; size_t rec_oQf = 0, rec_oR = 0;
     DevBuf<double> rec_j;
     DevBuf<double> rec_f;                 // the bank's records (fmpc_loop_records_bank_device): f_i of the last call, stages x n per problem
+    DevBuf<double> kkt_part;              // KKT report (fmpc_kkt_report_device): per-(stage, problem) partials of the panel kernel's last call
     // staging for the host-pointer entry points
     DevBuf<char> stage;
     PinnedBuf<char> pin; void* pin_dev = nullptr;   // pinned host twin of the staging block for small host-pointer solves (fmpc_solve_host)
@@ -3341,6 +3343,34 @@ extern "C" int fmpc_loop_records_run_bank_device(fmpc_handle h, int batch, int s
     const int rc = fmpc_records_run_args(h, batch, steps, X0, U0, x0_before, u_before1, u_before2, coeff_a, coeff_b, unit_change,
                                          Xp0, xerr0, dU, Uv, K.R, &todo);
     return todo ? fmpc_records_bank_launch(h, K, model_of, (hipStream_t)stream) : rc;
+}
+
+// KKT report (fmpc_kkt_api.hip has checked the arguments, fmpc_kkt_kernels.hip has the kernels): the rules that need the handle,
+// its lock and stream order, the model's pointers, the launch.  The bank form reads A1, A2 of model model_of[p] from the bank's
+// fp64 plain images and is ordered on the device with the bank calls.
+int fmpc_kkt_set_device(fmpc_handle h) { return hipSetDevice(h->device) == hipSuccess ? FMPC_OK : FMPC_E_HIP; }
+int fmpc_kkt_run(fmpc_handle h, KktParams& P, int bank, const int* model_of, hipStream_t stream) {
+    if (P.u_prev && (bank || !h->ramp_du.p)) return FMPC_E_UNSUPPORTED;
+    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    std::lock_guard<std::mutex> lock(h->mu);
+    const fmpc_handle_s::Bank& B = h->bank;
+    if (bank && (B.count <= 0 || (!model_of && P.batch > B.count))) return FMPC_E_UNSUPPORTED;
+    int rc = fmpc_guard_begin(h, stream);
+    if (rc != FMPC_OK) return rc;
+    const FmpcDevModel& D = h->dev;
+    const int panel = !bank && !P.u_prev && h->n <= KKT_NMAX && !D.denseQ && !D.denseR;
+    if (panel) rc = h->kkt_part.grow((size_t)KKT_PARTS * h->T * P.batch, stream);      // (FMPC_E_ALLOC while the stream is being captured)
+    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
+    P.n = h->n; P.m = h->m; P.T = h->T; P.has_xf = h->has_xf; P.var2 = h->var_order == 2; P.denseQ = D.denseQ; P.denseR = D.denseR;
+    P.A1 = D.A1; P.A2 = D.A2; P.A1t = D.A1t; P.A2t = D.A2t; P.Bt = D.Bt;
+    P.R2 = D.R2; P.Q2 = D.Q2; P.Qf2 = D.Qf2; P.Q2m = D.Q2m; P.Qf2m = D.Qf2m; P.R2m = D.R2m;
+    P.rl = D.rl; P.ql = D.ql; P.qfl = D.qfl; P.umin = D.umin; P.umax = D.umax; P.xf = D.xf;
+    if (P.u_prev) { P.dumin = h->ramp_du; P.dumax = h->ramp_du + h->m; }
+    P.bank = bank; P.count = B.count; P.plain = B.plain; P.plain_stride = B.plain_stride; P.model_of = model_of;
+    P.part = panel ? (double*)h->kkt_part : nullptr;
+    const bool ok = fmpc_launch_kkt(P, panel, stream) == hipSuccess;
+    fmpc_guard_end(h, stream);
+    return ok ? FMPC_OK : FMPC_E_HIP;
 }
 
 hipError_t fmpc_launch_phase_residual(int batch, size_t npx, int n, int m, const double* Bt, const double* phase, const double* u,

@@ -1,0 +1,82 @@
+// KKT report: the entry points of include/fastmpc.h (fmpc_kkt_report_device, fmpc_kkt_report_bank_device, fmpc_kkt_report).
+// The argument rules answer here, before the device is touched; the handle's side is fmpc_kkt_run (fmpc_api.hip), the kernels are
+// in fmpc_kkt_kernels.hip.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <string.h>
+
+#include "../../include/fastmpc.h"
+#include "fmpc_alloc.h"
+#include "fmpc_kkt.h"
+
+// *todo = 0 with FMPC_OK: nothing to enqueue.
+static int fmpc_kkt_args(fmpc_handle h, int batch, const double* x0, const double* x0_pre, const double* w, const double* u_prev,
+                         const double* z, long long ldz, const double* nu, double k, double* report, int ldr, int* flags,
+                         KktParams& P, int* todo) {
+    *todo = 0;
+    if (batch < 0 || !(k > 0.0) || !isfinite(k) || ldz < 0 || (ldr != 0 && ldr < FMPC_KKT_FIELDS)) return FMPC_E_DIM;
+    if (!h || !x0 || !z || !report) return FMPC_E_NULL;
+    if (batch == 0) return FMPC_OK;
+    int nz = 0, nu_len = 0;
+    const int rc = fmpc_dims(h, nullptr, nullptr, nullptr, &nz, &nu_len);
+    if (rc != FMPC_OK) return rc;
+    if (ldz != 0 && ldz < nz) return FMPC_E_DIM;
+    memset(&P, 0, sizeof(P));
+    P.batch = batch; P.nu_len = nu_len;
+    P.x0 = x0; P.x0_pre = x0_pre; P.w = w; P.u_prev = u_prev;
+    P.z = z; P.ldz = ldz ? ldz : nz; P.nu = nu; P.k = k;
+    P.report = report; P.ldr = ldr ? ldr : FMPC_KKT_FIELDS; P.flags = flags;
+    *todo = 1;
+    return FMPC_OK;
+}
+
+extern "C" int fmpc_kkt_report_device(fmpc_handle h, int batch,
+                                      const double* x0, const double* x0_pre, const double* w, const double* u_prev,
+                                      const double* z, long long ldz, const double* nu, double k,
+                                      double* report, int ldr, int* flags, void* stream) {
+    KktParams P;
+    int todo;
+    const int rc = fmpc_kkt_args(h, batch, x0, x0_pre, w, u_prev, z, ldz, nu, k, report, ldr, flags, P, &todo);
+    return todo ? fmpc_kkt_run(h, P, 0, nullptr, (hipStream_t)stream) : rc;
+}
+
+extern "C" int fmpc_kkt_report_bank_device(fmpc_handle h, int batch, const int* model_of,
+                                           const double* x0, const double* x0_pre, const double* w, const double* u_prev,
+                                           const double* z, long long ldz, const double* nu, double k,
+                                           double* report, int ldr, int* flags, void* stream) {
+    KktParams P;
+    int todo;
+    const int rc = fmpc_kkt_args(h, batch, x0, x0_pre, w, u_prev, z, ldz, nu, k, report, ldr, flags, P, &todo);
+    return todo ? fmpc_kkt_run(h, P, 1, model_of, (hipStream_t)stream) : rc;
+}
+
+// Host pointers: the arrays go down, the report and the flags come back, the device is idle on return.
+extern "C" int fmpc_kkt_report(fmpc_handle h, int batch,
+                               const double* x0, const double* x0_pre, const double* w, const double* u_prev,
+                               const double* z, long long ldz, const double* nu, double k,
+                               double* report, int ldr, int* flags) {
+    KktParams P;
+    int todo;
+    int rc = fmpc_kkt_args(h, batch, x0, x0_pre, w, u_prev, z, ldz, nu, k, report, ldr, flags, P, &todo);
+    if (!todo) return rc;
+    int n = 0, m = 0, T = 0, nz = 0;
+    fmpc_dims(h, &n, &m, &T, &nz, nullptr);
+    if (fmpc_kkt_set_device(h) != FMPC_OK) return FMPC_E_HIP;
+    const size_t B = batch;
+    const size_t zlen = (B - 1) * (size_t)P.ldz + nz, rlen = (B - 1) * (size_t)P.ldr + FMPC_KKT_FIELDS;   // (the last row needs no padding)
+    DevBuf<double> dx0, dxp, dw, dup, dz, dnu, drep; DevBuf<int> dfl;   // (released on return)
+    struct In { DevBuf<double>* d; const double* src; size_t len; } in[] = {
+        {&dx0, x0, B * n}, {&dxp, x0_pre, B * n}, {&dw, w, B * T * n}, {&dup, u_prev, B * m}, {&dz, z, zlen}, {&dnu, nu, B * P.nu_len}};
+    for (const In& a : in)
+        if (a.src && a.d->alloc(a.len, nullptr) != FMPC_OK) return FMPC_E_ALLOC;
+    if (drep.alloc(rlen, nullptr) != FMPC_OK || (flags && dfl.alloc(B, nullptr) != FMPC_OK)) return FMPC_E_ALLOC;
+    for (const In& a : in)
+        if (a.src && hipMemcpy(a.d->p, a.src, a.len * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return FMPC_E_HIP;
+    // (a padded report: the caller's padding goes down and comes back as it was)
+    if (P.ldr != FMPC_KKT_FIELDS && hipMemcpy(drep.p, report, rlen * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return FMPC_E_HIP;
+    rc = fmpc_kkt_report_device(h, batch, dx0, dxp, dw, dup, dz, ldz, dnu, k, drep, ldr, dfl, nullptr);
+    if (rc == FMPC_OK && hipDeviceSynchronize() != hipSuccess) rc = FMPC_E_HIP;
+    if (rc == FMPC_OK && hipMemcpy(report, drep.p, rlen * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = FMPC_E_HIP;
+    if (rc == FMPC_OK && flags && hipMemcpy(flags, dfl.p, B * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = FMPC_E_HIP;
+    return rc;
+}

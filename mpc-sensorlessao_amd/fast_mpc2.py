@@ -237,6 +237,19 @@ class Fast_MPC2:
         self.last_info = infos
         return x_opt
 
+    def kkt_report(self, z, nu=None, k=1e-2):
+        """How far (z, nu) is from the point inf_newton_solver iterates to at barrier weight k, computed on the device
+        (fmpc_kkt_report): {'rd': ||r_d||, 'rp': ||r_p|| (n_g), 'nr': n_r (inf_newton_solver.m:12-17), 'cost': z'Hz + g'z,
+        'barrier': -sum log(h - Pz), 'min_slack', 'converged': the exit test of :19, 'infeasible': some slack <= 0}.
+        nu None: rd and nr are NaN.  The VAR_1 class includes its ramp rows (u_prev) when they are on."""
+        h = self._handle()
+        row, fl = h.kkt_report(self.x0, self.x0_pre if self.var_order == 2 else None, self.w, z=_vec(z), nu=_vec(nu), k=float(k),
+                               u_prev=self._u_prev_for_solve())
+        out = {name: float(row[i]) for i, name in enumerate(_lib.FMPC_KKT_FIELD_NAMES)}
+        out["converged"] = bool(fl & _lib.FMPC_KKT_CONVERGED)
+        out["infeasible"] = bool(fl & _lib.FMPC_KKT_INFEASIBLE)
+        return out
+
     # ---------------------------------------------------------------- dense builders of the class (host side)
     # The device never forms H, P, C; these exist because they are public methods of the reference class
     # (VAR_2/Fast_MPC2.m:56-67) that a caller may use for its own purposes (e.g. `fomulate_mpc`).  Written from the

@@ -398,6 +398,85 @@ class FastMPCHandle:
         if rc != _lib.FMPC_OK:
             raise FastMPCError(rc, "fmpc_loop_records_bank_device" if bank else "fmpc_loop_records_device")
 
+    def kkt_report_device(self, x0, x0_pre=None, w=None, z=None, nu=None, k=1e-2, u_prev=None, ldz=None, out=None, flags=None):
+        """fmpc_kkt_report_device: per problem the reference's residual norms (inf_newton_solver.m:12-17), cost, barrier and smallest
+        slack of the iterate (z, nu) at barrier weight k, on torch's current stream.  Returns (report, flags): (batch, 6) float64 with
+        the columns FMPC_KKT_RD .. FMPC_KKT_MIN_SLACK and (batch,) int32 with the bits FMPC_KKT_CONVERGED / FMPC_KKT_INFEASIBLE.
+        x0, x0_pre (batch, n), w (batch, T n), nu (batch, nu_len), u_prev (batch, m): contiguous float64 HIP tensors; x0_pre / w None:
+        zeros; nu None: the primal-only report (rd, nr NaN); u_prev (after `set_ramp`): with the ramp rows.  z: (batch, N_z), rows
+        ldz doubles apart (default: its row stride, so the padded view `solve_device` returns is taken as it is).  out: a float64
+        tensor (batch, ldr) with ldr >= 6 whose first six columns receive the report (the rest is not written); flags: int32 (batch,)."""
+        return self._kkt_report(False, None, x0, x0_pre, w, z, nu, k, u_prev, ldz, out, flags)
+
+    def kkt_report_bank_device(self, x0, x0_pre=None, w=None, z=None, nu=None, k=1e-2, u_prev=None, ldz=None, out=None, flags=None,
+                               model_of=None):
+        """fmpc_kkt_report_bank_device: `kkt_report_device` where A1, A2 of problem p are those of model model_of[p] of the bank
+        (int32 HIP tensor; None: model p).  A problem whose index is outside the bank gets an all-NaN row and flags 0."""
+        return self._kkt_report(True, model_of, x0, x0_pre, w, z, nu, k, u_prev, ldz, out, flags)
+
+    def _kkt_report(self, bank, model_of, x0, x0_pre, w, z, nu, k, u_prev, ldz, out, flags):
+        import torch
+        if z is None:
+            raise FastMPCError(_lib.FMPC_E_NULL, "z")
+        batch = x0.shape[0]
+        for t, cols, name in ((x0, self.n, "x0"), (x0_pre, self.n, "x0_pre"), (w, self.T * self.n, "w"), (nu, self.nu_len, "nu"),
+                              (u_prev, self.m, "u_prev")):
+            if t is None:
+                continue
+            if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != batch * cols:
+                raise FastMPCError(_lib.FMPC_E_DIM, f"{name}: need a contiguous float64 HIP tensor of {(batch, cols)}")
+        if not z.is_cuda or z.dtype != torch.float64 or z.dim() > 2 or (z.dim() == 2 and z.stride(1) != 1) or z.shape[-1] != self.nz:
+            raise FastMPCError(_lib.FMPC_E_DIM, "z: need a float64 HIP tensor (batch, N_z) with unit stride along its rows")
+        if ldz is None:
+            ldz = z.stride(0) if (z.dim() == 2 and batch > 1) else self.nz
+        ldz = int(ldz)
+        if batch > 0 and (ldz < self.nz or z.storage_offset() + (batch - 1) * ldz + self.nz > z.untyped_storage().nbytes() // 8):
+            raise FastMPCError(_lib.FMPC_E_DIM, "z: batch rows of N_z doubles, ldz apart, do not fit the tensor")
+        if out is None:
+            out = torch.empty((batch, _lib.FMPC_KKT_FIELDS), dtype=torch.float64, device=x0.device)
+        if (not out.is_cuda or out.dtype != torch.float64 or out.dim() != 2 or out.shape[0] != batch or out.shape[1] < _lib.FMPC_KKT_FIELDS
+                or out.stride(1) != 1 or (batch > 1 and out.stride(0) < _lib.FMPC_KKT_FIELDS)):
+            raise FastMPCError(_lib.FMPC_E_DIM, "out: need a float64 HIP tensor (batch, >= 6) with unit stride along its rows")
+        ldr = int(out.stride(0)) if batch > 1 else int(out.shape[1])
+        if flags is None:
+            flags = torch.empty(batch, dtype=torch.int32, device=x0.device)
+        if not flags.is_cuda or flags.dtype != torch.int32 or not flags.is_contiguous() or flags.numel() != batch:
+            raise FastMPCError(_lib.FMPC_E_DIM, "flags: need a contiguous int32 HIP tensor of (batch,)")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)
+        if bank:
+            self._check_model_of(model_of, batch)
+            rc = self._lib.fmpc_kkt_report_bank_device(self._h, batch, p(model_of), p(x0), p(x0_pre), p(w), p(u_prev), p(z), ldz, p(nu),
+                                                       float(k), p(out), ldr, p(flags), stream)
+        else:
+            rc = self._lib.fmpc_kkt_report_device(self._h, batch, p(x0), p(x0_pre), p(w), p(u_prev), p(z), ldz, p(nu), float(k),
+                                                  p(out), ldr, p(flags), stream)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_kkt_report_bank_device" if bank else "fmpc_kkt_report_device")
+        return out[:, :_lib.FMPC_KKT_FIELDS], flags
+
+    def kkt_report(self, x0, x0_pre=None, w=None, z=None, nu=None, k=1e-2, u_prev=None):
+        """fmpc_kkt_report (host arrays, synchronous): `kkt_report_device` on numpy arrays.  x0 (batch, n) or (n,); returns
+        (report, flags): (batch, 6) float64 and (batch,) int32, or a row and an int for a single vector input."""
+        if z is None:
+            raise FastMPCError(_lib.FMPC_E_NULL, "z")
+        single = np.asarray(x0).ndim == 1
+        x0 = _f64(x0)
+        batch = 1 if single else x0.shape[0]
+        x0 = _f64(x0, (batch, self.n), "x0")
+        x0_pre = _f64(x0_pre, (batch, self.n), "x0_pre")
+        w = _f64(w, (batch, self.T * self.n), "w")
+        z = _f64(z, (batch, self.nz), "z")
+        nu = _f64(nu, (batch, self.nu_len), "nu")
+        u_prev = _f64(u_prev, (batch, self.m), "u_prev")
+        report = np.empty((batch, _lib.FMPC_KKT_FIELDS))
+        flags = np.zeros(batch, dtype=np.int32)
+        rc = self._lib.fmpc_kkt_report(self._h, batch, _ptr(x0), _ptr(x0_pre), _ptr(w), _ptr(u_prev), _ptr(z), 0, _ptr(nu), float(k),
+                                       _ptr(report), 0, _ptr(flags))
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_kkt_report")
+        return (report[0], int(flags[0])) if single else (report, flags)
+
     @staticmethod
     def _check_model_of(model_of, batch):
         import torch
