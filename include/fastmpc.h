@@ -416,6 +416,59 @@ int fmpc_var_validate_device(int n, int order, int first, int count, int num_sam
                              double* rmse, double* rrmse, void* stream);
 
 /*
+ * Modal fit: the least-squares projection of phase maps onto mode maps, on the device.  The reference's zernmodfit.m:201-213
+ * (c = z \ data(:), the coefficient series ad_acc of README.md:86-93 that the VAR model is identified from and that the
+ * estimator's error is judged against, README.md:479) and README.md:268-271 (B = pinv(Zs'Zs) Zs' B_pupil: the same projection of
+ * the influence functions).  Z: n mode maps of npx pixels, n contiguous rows of npx doubles, the layout fmpc_phase_residual_device
+ * reads; the pixels are either the compressed vectors z(is_in) (npx any count) or full grids whose mode values vanish outside
+ * the support.  For a screen phi:
+ *     G = Z Z' (n x n) = R'R,   s = Z phi,   c = R^-1 R^-T s
+ * which for a full-rank G is z \ data and pinv(Z'Z) Z' data.  Screens must be finite wherever they are read.
+ *
+ * fmpc_modal_factor_device: R (n x n column-major) = the upper Cholesky factor of Z Z', zeros below the diagonal.  status (a
+ * device int, nullable): 0, or FMPC_E_NOT_PD_SCHUR when a pivot is not > 0 or not finite (a rank-deficient or non-finite Z is
+ * an error, not pseudo-inverted); the whole of R is NaN then, so a later fit yields NaN coefficients and nothing has to be read
+ * back to find out.  G comes from the product kernel of the fit with the mode maps as screens: G(i,j) and G(j,i) have the same bits.
+ *
+ * fmpc_modal_fit_device: screen b starts at screens + b * lds (lds = 0: npx; otherwise lds >= npx), its coefficients skip .. n-1
+ * go to coeffs + b * ldc (ldc = 0: n - skip; otherwise ldc >= n - skip; nothing between the rows is written).  skip in [0, n):
+ * the leading coefficients left out -- the reference deletes the piston, ad_acc(:,1) = [], B(1,:) = [], skip = 1.  With batch
+ * index r * num_samples + t, ldc = 0 and skip = 1 the output is the `series` of fmpc_var_fit_device.  A non-finite pixel makes
+ * the coefficients of that screen non-finite; the other screens, those of the same panel included, keep their bits.
+ * The products run on the fp64 matrix cores, 16 modes x 16 screens (a PANEL) per tile, the pixel axis cut into chunks whose
+ * length depends on n alone; a workgroup keeps its chunk of Z on chip and walks over the panels, so each screen is read once.
+ * Every sum has one fixed order and there are no atomics: a screen's coefficients are bitwise the same in repeated calls,
+ * wherever it sits in the batch and however small the workspace is.
+ *
+ * The caller owns the workspace (device memory): one (16 x n_pad) partial per chunk and panel.
+ * fmpc_modal_workspace_bytes(n, npx, batch) is the recommended size -- every panel of the batch up to 64 MiB, and at least 32
+ * panels -- and (n, npx, 1) the minimum, one panel; 0 for arguments the fit refuses.  A call uses as many whole panels as
+ * workspace_bytes holds and walks the batch through them.  Neither entry takes a handle, allocates, synchronises or reads
+ * back: both can be recorded into a HIP graph.
+ * Before the device is touched: FMPC_E_NULL for a NULL Z, R, screens, coeffs or workspace; FMPC_E_DIM for n <= 0, npx < n,
+ * batch < 0, skip outside [0, n), 0 < lds < npx, 0 < ldc < n - skip, a workspace below the minimum; FMPC_E_UNSUPPORTED for
+ * n > 128 (radial order 14, the largest bank size).  batch == 0 is FMPC_OK with nothing enqueued.
+ *
+ * WHEN TO USE IT: whenever the screens (or influence functions) are on the device and their coefficients are wanted there -- the
+ * series for fmpc_var_fit_device, the true coefficients of a closed-loop step, B for fmpc_create.  Measured on one MI355X
+ * (scripts/modal_fit_timing.py, n = 28, skip = 1, medians, five rounds alternating with the torch composition `screens @ Z.T` +
+ * torch.cholesky_solve on a precomputed factor, spread between rounds <= 4 %): 512 x 512 screens, batch 1 / 144 / 256 / 2000:
+ * 0.059 / 0.135 / 0.200 / 1.33 ms against 28.1 ms for the composition at every one of these batch sizes (479 / 207 / 141 / 21 x
+ * faster), 0.17 / 0.42 / 0.47 / 0.51 of the HBM roofline on the compulsory bytes 8 (batch npx + n npx + batch n) at the 6.3 TB/s
+ * copy rate; 32 000 compressed screens of 12 644 pixels: 1.15 ms against 1.48 - 1.54 ms (1.3 x faster), 0.45 of the roofline.
+ * It was not slower than the composition at any size measured.  The partial sums cost a further 25 % of the screen bytes in
+ * workspace traffic at n = 28 (2 n_pad / chunk length).  A single small screen is bound by two launches and the latency of the
+ * finish kernel (0.04 ms), not by bandwidth: for one screen at a time on the host side of a loop, batch the realisations.
+ */
+size_t fmpc_modal_workspace_bytes(int n, long long npx, int batch);
+int fmpc_modal_factor_device(int n, long long npx, const double* Z, double* R, int* status,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int fmpc_modal_fit_device(int n, long long npx, int batch, const double* Z, const double* R,
+                          const double* screens, long long lds, int skip,
+                          double* coeffs, int ldc,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Model bank: one VAR model (A1, A2) per problem of a batched solve.  In the reference a realisation's model is its own: A1, A2 are
  * identified from the training stretch of that realisation's coefficient series (README.md:108-130) and handed to Fast_MPC2
  * (README.md:548-556).  B, the weights, the bounds and T belong to the mirror and the controller and stay the handle's.

@@ -116,6 +116,9 @@ SIGNATURES = {
     "fmpc_est_dims": (C.c_int, [_vp] + [_ip] * 6),
     "fmpc_est_apply": (C.c_int, [_vp, C.c_int] + [_vp] * 4),
     "fmpc_est_apply_device": (C.c_int, [_vp, C.c_int] + [_vp] * 4 + [_vp]),
+    "fmpc_modal_workspace_bytes": (C.c_size_t, [C.c_int, C.c_longlong, C.c_int]),
+    "fmpc_modal_factor_device": (C.c_int, [C.c_int, C.c_longlong, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fmpc_modal_fit_device": (C.c_int, [C.c_int, C.c_longlong, C.c_int, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp]),
 }
 
 _lib = None

@@ -184,9 +184,11 @@ class AOLoop:
     residual screen = phase_valid[k] + sum_j (B u[k-1])_j Z_j (`fmpc_phase_residual_device`), the phase-diversity estimator
     (`PhaseDiversityEstimator`: three PSF windows, ad_est = G (Y_M - b_s)), x0 = ad_est, x0_pre = the previous ad_est,
     b_ref from the last two first moves (`fmpc_loop_inputs_device`), the fastMPC solve, u[k] = U(1:nu).
-    Z: (n, len, len) mode maps indexed [j, row, column] (piston removed).  Screens are handed over indexed [b, row, column]."""
+    Z: (n, len, len) mode maps indexed [j, row, column] (piston removed).  Screens are handed over indexed [b, row, column].
+    modal (optional): a `ModalFit` over the n + 1 mode maps WITH the piston, indexed as the screens are handed over; it gives
+    `true_coefficients`, the reference's ad_acc_valid, and changes nothing else."""
 
-    def __init__(self, handle, estimator, Z, batch, n_newton=1, k=1e-2, one_call=True):
+    def __init__(self, handle, estimator, Z, batch, n_newton=1, k=1e-2, one_call=True, modal=None):
         import ctypes as C
         import numpy as np
         import torch
@@ -207,6 +209,16 @@ class AOLoop:
         self.status = torch.zeros(batch, dtype=torch.int32, device=dev); self.iters = torch.zeros(batch, dtype=torch.int32, device=dev)
         self.steps_done = 0
         self._C, self._torch, self._dev = C, torch, dev
+        if modal is not None and modal.n != n + 1:
+            raise ValueError("modal: need the fit over the n + 1 modes with the piston")
+        self.modal = modal
+
+    def true_coefficients(self, phase_k, workspace=None, out=None):
+        """The modal fit of the incoming screens with the piston dropped (zernmodfit of phase_valid(:,:,k): a row of ad_acc_valid,
+        what X_est_err of README.md:479 is judged against).  phase_k: (batch, ...) over the pixel shape of the `ModalFit`."""
+        if self.modal is None:
+            raise ValueError("true_coefficients: this loop was built without modal=")
+        return self.modal.fit(phase_k, skip=1, workspace=workspace, out=out)
 
     def step(self, phase_k, noise=None, colmajor=False):
         """phase_k: (batch, len, len) float64 HIP tensor indexed [b, row, column] (phase_valid(:,:,k) of every realisation);
