@@ -938,6 +938,68 @@ int fmpc_est_apply(fmpc_est e, int batch, const double* scrn, const double* nois
 int fmpc_est_apply_device(fmpc_est e, int batch, const double* scrn, const double* noise, double* ad_est, double* Y_out,
                           void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Zernike functions on the device: the reference's zernfun.m, in the mode order of zernmodfit.m:195-198 (Zs.mat, which the
+ * reference loads at README.md:266, is not shipped: these calls rebuild it).
+ *
+ * fmpc_zernike_modes   host only.  Returns (N + 1)(N + 2) / 2 and fills the pairs in zernmodfit.m:195-198's order: for each
+ *                   n = 0..N, m = -n, -n + 2, .., n.  NULL outputs just count.  N = 6 gives the reference's 28 modes.
+ * fmpc_zernike_device   the point form.  n, m: HOST arrays of nmode mode numbers (they travel in the kernel arguments: no
+ *                   allocation, no copy that synchronises; the call can be recorded into a graph).  r, theta: device arrays of
+ *                   npx doubles.  Z: nmode rows of npx doubles, row stride ldz >= npx (0 = npx) -- the layout fmpc_modal_* and
+ *                   fmpc_phase_residual_device read.
+ *                       Z[j][p] = R_n^|m|(r_p) * { cos(m theta_p), m > 0 ; sin(|m| theta_p), m < 0 ; 1, m = 0 }
+ *                   with the factorial quotients of zernfun.m:166-170 (exact in a double for n <= 14);  normalized != 0
+ *                   multiplies by sqrt((1 + (m != 0))(n + 1) / pi) (zernfun.m:175-177).  r outside [0, 1] is evaluated as the
+ *                   polynomial: the device cannot raise the error of zernfun.m:107-109.
+ * fmpc_zernike_grid_device   the grid form: the kernel computes the coordinates itself.  Pixel (row y, column x) of a len x len
+ *                   grid is stored at y + len x (MATLAB order, what fmpc_est_create takes for D_re / D_im) and has
+ *                   X = (2 x - N) / N, Y = (2 y - N) / N, N = len - 1, r = hypot(X, Y), theta = atan2(Y, X); the value is 0
+ *                   where r > 1.  (For even len no pixel has r = 1 exactly -- a^2 + b^2 = N^2 has no solution in odd a, b --
+ *                   so the support does not depend on rounding.)
+ * Answered before the device is touched: FMPC_E_NULL for a NULL pointer; FMPC_E_DIM for nmode <= 0, npx <= 0, 0 < ldz < npx,
+ * len <= 0, |m| > n or n - m odd; FMPC_E_UNSUPPORTED for n > 14 or nmode > 128 (the modal fit's limit).
+ */
+int fmpc_zernike_modes(int N, int* n_out, int* m_out);
+int fmpc_zernike_device(int nmode, const int* n, const int* m, long long npx, const double* r, const double* theta, int normalized,
+                        double* Z, long long ldz, void* stream);
+int fmpc_zernike_grid_device(int nmode, const int* n, const int* m, int len, int normalized, double* Z, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * The estimator's first-order image model y = b_s + A_s alpha on the device: what the reference loads from model_approx.mat
+ * (README.md:294) and uses at README.md:478, rebuilt from the optics -- also about a non-zero operating point phi0.
+ * With E = exp(1i*phi0), P_k = E .* D_k and F' . F the d x d window of the centred DFT (as in fmpc_est_apply):
+ *
+ *     I_k = F' P_k F ,    b_s = scale |I_k|^2 ,    A_s(:, j) = 2 scale Re( conj(I_k) .* F' (1i Z_j .* P_k) F )
+ *
+ * fmpc_est_optics_create   len, first, d, ndiv, D_re, D_im, scale: as fmpc_est_create, with the same rules (len a multiple of
+ *                   64, d <= 32, ndiv <= 3, host arrays in MATLAB order; the pin-hole pupil of README.md:383-391 times
+ *                   exp(1i*zd_list(k)*W), scale = dx^4*AU).  The handle owns the device copies of D, the DFT operands and the
+ *                   pupil ranges of the row blocks.
+ * fmpc_est_model_device   Z: nmode <= 128 device maps of len^2 doubles in the pixel order of D (fmpc_zernike_grid_device).
+ *                   phi0: one device screen, |phi0| < 1e6 as for fmpc_est_apply (beyond: NaN outputs), or NULL for zero
+ *                   aberration, the reference's model.  b_s: p = ndiv d^2; A_s: p x nmode column-major; rows in the order of
+ *                   README.md:471 (per diversity, the window column-major).  The workspace is the caller's: no allocation, no
+ *                   synchronisation, no read-back -- the call can be recorded into a graph.  A workspace below the
+ *                   recommended fmpc_est_model_workspace_bytes(o, nmode) walks the modes through it in panels;
+ *                   fmpc_est_model_workspace_bytes(o, 1) is the minimum.  The result is bitwise the same whatever the panel
+ *                   count and on every call (the partial windows are summed in a fixed order).
+ * fmpc_est_create_from_model   runs the model on the optics' device, drops the first `skip` columns (README.md:289 removes the
+ *                   piston: skip = 1) and hands A_s, b_s to fmpc_est_create's path (G on the host, lsqminnorm's rank cut-off).
+ *                   Synchronises.  The result is an ordinary fmpc_est.
+ * Answered before the device is touched: FMPC_E_NULL for NULL o, Z, A_s, b_s or workspace; FMPC_E_DIM for nmode <= 0, skip
+ * outside [0, nmode) or a workspace below the minimum; FMPC_E_UNSUPPORTED for nmode > 128 and, from fmpc_est_create_from_model,
+ * for a mode count nmode - skip that fmpc_est_create refuses.  fmpc_est_model_workspace_bytes is 0 for refused arguments.
+ */
+typedef struct fmpc_est_optics_s* fmpc_est_optics;
+int fmpc_est_optics_create(fmpc_est_optics* out, int len, int first, int d, int ndiv, const double* D_re, const double* D_im,
+                           double scale, int device);
+int fmpc_est_optics_destroy(fmpc_est_optics o);
+size_t fmpc_est_model_workspace_bytes(fmpc_est_optics o, int nmode);
+int fmpc_est_model_device(fmpc_est_optics o, int nmode, const double* Z, const double* phi0, double* A_s, double* b_s,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int fmpc_est_create_from_model(fmpc_est* out, fmpc_est_optics o, int nmode, int skip, const double* Z, const double* phi0);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,9 +18,11 @@ from .recorded import RecordedSolves
 from .var_identify import identify_var2_device, identify_var_device, validate_var_device, var_fit_workspace_bytes
 from .estimator import PhaseDiversityEstimator
 from .modal import ModalFit, modal_workspace_bytes
+from . import optics
+from .optics import zernike_modes, zernike_basis, zernike_grid, EstimatorOptics, reference_optics
 from . import _lib
 
-__all__ = ["FastMPCHandle", "Fast_MPC2", "Fast_MPC2_VAR1", "deinterleave", "FastMPCError",
+__all__ = ["optics", "zernike_modes", "zernike_basis", "zernike_grid", "EstimatorOptics", "reference_optics","FastMPCHandle", "Fast_MPC2", "Fast_MPC2_VAR1", "deinterleave", "FastMPCError",
            "ShardedFastMPC", "shard_range", "ClosedLoop", "AOLoop", "SolveLanes", "RecordedSolves", "PhaseDiversityEstimator", "synthetic", "load", "LIB_PATH",
            "identify_var2_device", "identify_var_device", "validate_var_device", "var_fit_workspace_bytes", "LoopRecords",
            "FMPC_KKT_FIELDS", "FMPC_KKT_RD", "FMPC_KKT_RP", "FMPC_KKT_NR", "FMPC_KKT_COST", "FMPC_KKT_BARRIER", "FMPC_KKT_MIN_SLACK",

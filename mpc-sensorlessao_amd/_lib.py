@@ -119,6 +119,14 @@ SIGNATURES = {
     "fmpc_modal_workspace_bytes": (C.c_size_t, [C.c_int, C.c_longlong, C.c_int]),
     "fmpc_modal_factor_device": (C.c_int, [C.c_int, C.c_longlong, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fmpc_modal_fit_device": (C.c_int, [C.c_int, C.c_longlong, C.c_int, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp]),
+    "fmpc_zernike_modes": (C.c_int, [C.c_int, _ip, _ip]),
+    "fmpc_zernike_device": (C.c_int, [C.c_int, _ip, _ip, C.c_longlong, _vp, _vp, C.c_int, _vp, C.c_longlong, _vp]),
+    "fmpc_zernike_grid_device": (C.c_int, [C.c_int, _ip, _ip, C.c_int, C.c_int, _vp, _vp]),
+    "fmpc_est_optics_create": (C.c_int, [C.POINTER(_vp)] + [C.c_int] * 4 + [_vp, _vp, C.c_double, C.c_int]),
+    "fmpc_est_optics_destroy": (C.c_int, [_vp]),
+    "fmpc_est_model_workspace_bytes": (C.c_size_t, [_vp, C.c_int]),
+    "fmpc_est_model_device": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fmpc_est_create_from_model": (C.c_int, [C.POINTER(_vp), _vp, C.c_int, C.c_int, _vp, _vp]),
 }
 
 _lib = None

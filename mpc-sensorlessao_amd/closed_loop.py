@@ -184,11 +184,12 @@ class AOLoop:
     residual screen = phase_valid[k] + sum_j (B u[k-1])_j Z_j (`fmpc_phase_residual_device`), the phase-diversity estimator
     (`PhaseDiversityEstimator`: three PSF windows, ad_est = G (Y_M - b_s)), x0 = ad_est, x0_pre = the previous ad_est,
     b_ref from the last two first moves (`fmpc_loop_inputs_device`), the fastMPC solve, u[k] = U(1:nu).
-    Z: (n, len, len) mode maps indexed [j, row, column] (piston removed).  Screens are handed over indexed [b, row, column].
+    Z: (n, len, len) mode maps indexed [j, row, column] (piston removed), a host array or a tensor (a HIP tensor is not taken
+    through the host; z_colmajor=True: it is indexed [j, column, row] already, the order of `optics.zernike_grid`).  Screens are handed over indexed [b, row, column].
     modal (optional): a `ModalFit` over the n + 1 mode maps WITH the piston, indexed as the screens are handed over; it gives
     `true_coefficients`, the reference's ad_acc_valid, and changes nothing else."""
 
-    def __init__(self, handle, estimator, Z, batch, n_newton=1, k=1e-2, one_call=True, modal=None):
+    def __init__(self, handle, estimator, Z, batch, n_newton=1, k=1e-2, one_call=True, modal=None, z_colmajor=False):
         import ctypes as C
         import numpy as np
         import torch
@@ -198,7 +199,13 @@ class AOLoop:
         f64 = dict(dtype=torch.float64, device=dev)
         n, m, T = handle.n, handle.m, handle.T
         assert Z.shape[0] == n and Z.shape[1] == estimator.len
-        self.Z = torch.from_numpy(np.ascontiguousarray(np.swapaxes(np.asarray(Z, dtype=np.float64), -1, -2))).to(dev)   # column-major planes
+        if torch.is_tensor(Z):               # a device tensor (optics.zernike_grid) stays on the device
+            Zt = Z.to(device=dev, dtype=torch.float64)
+            self.Z = Zt.contiguous() if z_colmajor else Zt.transpose(-1, -2).contiguous()
+        else:
+            if z_colmajor:
+                raise ValueError("z_colmajor: only for a tensor Z")
+            self.Z = torch.from_numpy(np.ascontiguousarray(np.swapaxes(np.asarray(Z, dtype=np.float64), -1, -2))).to(dev)   # column-major planes
         self.npx = estimator.len ** 2
         self.scrn = torch.empty((batch, estimator.len, estimator.len), **f64)
         self._xb = [torch.zeros((batch, n), **f64) for _ in range(2)]          # ad_est of this and of the previous step, in turn

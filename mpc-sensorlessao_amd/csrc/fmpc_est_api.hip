@@ -25,8 +25,7 @@ extern "C" int fmpc_est_create(fmpc_est* out, int len, int first, int d, int ndi
                                double scale, const double* A_s, const double* b_s, int p, int nx, int device) {
     if (!out || !D_re || !D_im || !A_s || !b_s) return FMPC_E_NULL;
     *out = nullptr;
-    if (len < 64 || len % 64 != 0 || d < 1 || d > 32 || first < 0 || first + d > len || ndiv < 1 || ndiv > FE_MAXDIV || nx < 1 ||
-        p != ndiv * d * d) return FMPC_E_DIM;
+    if (!fe_geometry_ok(len, first, d, ndiv) || nx < 1 || p != ndiv * d * d) return FMPC_E_DIM;
     if (!fe_finish_serves(d, nx)) return FMPC_E_UNSUPPORTED;         // (before the device is touched and the gain is computed)
     if (hipSetDevice(device) != hipSuccess) return FMPC_E_HIP;
     fmpc_est_s* e = new (std::nothrow) fmpc_est_s();
@@ -45,23 +44,8 @@ extern "C" int fmpc_est_create(fmpc_est* out, int len, int first, int d, int ndi
     if (rc != FMPC_OK) { delete e; return rc; }
     // the range of k-steps of every row block that sees the pupil (fmpc_est_psf skips what lies outside)
     {
-        const int nblk = len / 16, nks = len / 4;
-        std::vector<int> qr((size_t)2 * nblk, 0);
-        for (int b = 0; b < nblk; ++b) {
-            int lo = nks, hi = 0;
-            for (int Q = 0; Q < nks; ++Q) {
-                bool any = false;
-                for (int k = 0; k < ndiv && !any; ++k)
-                    for (int x = 4 * Q; x < 4 * Q + 4 && !any; ++x)
-                        for (int y = 16 * b; y < 16 * b + 16; ++y) {
-                            const size_t o = (size_t)k * npx + (size_t)x * len + y;            // column-major: (row y, column x)
-                            if (D_re[o] != 0.0 || D_im[o] != 0.0) { any = true; break; }
-                        }
-                if (any) { if (Q < lo) lo = Q; hi = Q + 1; }
-            }
-            if (hi <= lo) { lo = 0; hi = 0; }
-            qr[2 * b] = lo; qr[2 * b + 1] = hi;
-        }
+        std::vector<int> qr;
+        fmpc_host_estimator_qranges(len, ndiv, D_re, D_im, qr);
         rc = e->qlist.assign(qr.data(), qr.size(), nullptr);
         if (rc != FMPC_OK) { delete e; return rc; }
     }

@@ -35,4 +35,25 @@ static inline bool fe_finish_serves(int d, int nx) {
     return nx >= 1 && nx <= FE_FINISH_THREADS && fe_finish_lds_bytes(d, nx) <= FE_FINISH_LDS_LIMIT;
 }
 
+// The grid and window rules of fmpc_est_create and fmpc_est_optics_create.
+static inline bool fe_geometry_ok(int len, int first, int d, int ndiv) {
+    return len >= 64 && len % 64 == 0 && d >= 1 && d <= 32 && first >= 0 && first + d <= len && ndiv >= 1 && ndiv <= FE_MAXDIV;
+}
+
 hipError_t fmpc_launch_estimator(const FeParams& P, hipStream_t stream);
+
+// The linearised image model (fmpc_kernel_est_model.hip): fields 0 = P_k (the base) and 1 + j = 1i Z_j .* P_k, P_k = E .* D_k.
+#define FEM_MAXMODE 128
+struct FemParams {
+    int len, d, ndiv, nmode;
+    double scale;                       // dx^4 AU
+    const double* phi0;                 // len x len column-major or NULL (E = 1)
+    const double* Z;                    // [nmode][len x len column-major]
+    const double* Dre; const double* Dim; const int* qrange; const double* Fimg;    // as in FeParams
+    double* base;                       // workspace: [ndiv][re, im][32][32] the summed windows I_k of the base field
+    double* part;                       // workspace: [slot][ndiv][len / 16][re, im][32][32] partial windows
+    double* A_s; double* b_s;           // p x nmode column-major, p
+};
+// One pass: the fields f0 .. f0 + nf - 1 through the slots 0 .. nf - 1 of `part` (PSF kernel, then the finish kernel; a pass
+// that holds field 0 finishes it first, the later passes read `base`).
+hipError_t fmpc_launch_est_model_pass(const FemParams& P, int f0, int nf, hipStream_t stream);

@@ -1108,3 +1108,51 @@ extern "C" int fmpc_debug_plan_lanes(int nsteps, const unsigned* supersedes, int
     *lanes = fmpc_host_plan_lanes(nsteps, supersedes, ngroups, slots, tiles_used, cap, nsteps ? lane_of_step : &dummy, wpg);
     return 0;
 }
+
+void fmpc_host_estimator_qranges(int len, int ndiv, const double* D_re, const double* D_im, std::vector<int>& qr) {
+    const int nblk = len / 16, nks = len / 4;
+    const size_t npx = (size_t)len * len;
+    qr.assign((size_t)2 * nblk, 0);
+    for (int b = 0; b < nblk; ++b) {
+        int lo = nks, hi = 0;
+        for (int Q = 0; Q < nks; ++Q) {
+            bool any = false;
+            for (int k = 0; k < ndiv && !any; ++k)
+                for (int x = 4 * Q; x < 4 * Q + 4 && !any; ++x)
+                    for (int y = 16 * b; y < 16 * b + 16; ++y) {
+                        const size_t o = (size_t)k * npx + (size_t)x * len + y;            // column-major: (row y, column x)
+                        if (D_re[o] != 0.0 || D_im[o] != 0.0) { any = true; break; }
+                    }
+            if (any) { if (Q < lo) lo = Q; hi = Q + 1; }
+        }
+        if (hi <= lo) { lo = 0; hi = 0; }
+        qr[2 * b] = lo; qr[2 * b + 1] = hi;
+    }
+}
+
+// ---- Zernike functions (zernfun.m, zernmodfit.m)
+int fmpc_host_zernike_modes(int N, int* n_out, int* m_out) {
+    if (N < 0) return 0;
+    int j = 0;
+    for (int n = 0; n <= N; ++n)
+        for (int m = -n; m <= n; m += 2, ++j) {        // zernmodfit.m:197: [(-x:2:-1) fliplr(x:-2:0)] = -x:2:x
+            if (n_out) n_out[j] = n;
+            if (m_out) m_out[j] = m;
+        }
+    return j;
+}
+
+void fmpc_host_zernike_coefficients(double coef[FMPC_ZERNIKE_NCOEF], unsigned short off[FMPC_ZERNIKE_MAXN + 1][8]) {
+    double fact[FMPC_ZERNIKE_MAXN + 1];
+    fact[0] = 1.0;
+    for (int i = 1; i <= FMPC_ZERNIKE_MAXN; ++i) fact[i] = fact[i - 1] * i;
+    int o = 0;
+    for (int n = 0; n <= FMPC_ZERNIKE_MAXN; ++n) {
+        for (int h = 0; h < 8; ++h) off[n][h] = 0;
+        for (int ma = n & 1; ma <= n; ma += 2) {
+            off[n][ma / 2] = (unsigned short)o;
+            for (int s = 0; s <= (n - ma) / 2; ++s)       // zernfun.m:166-170, the quotients taken in its order (each one an integer)
+                coef[o++] = (1 - 2 * (s & 1)) * fact[n - s] / fact[s] / fact[(n - ma) / 2 - s] / fact[(n + ma) / 2 - s];
+        }
+    }
+}

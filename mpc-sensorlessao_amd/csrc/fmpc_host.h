@@ -214,3 +214,17 @@ int fmpc_host_estimator_gain(const double* A_s, int p, int nx, std::vector<doubl
 // F[y][j] = exp(-2 pi i (first + j - len/2) (y - len/2) / len), as matrix-core operand images [len/4][2 tiles][re, im][64 lanes]
 // (lane = 16 (y mod 4) + (j mod 16); columns j >= d are zero).
 void fmpc_host_estimator_dft_images(int len, int d, int first, std::vector<double>& img);
+// The range of k-steps (4 columns) of every row block of 16 that sees the pupil: qr[2 b], qr[2 b + 1] = [first, last + 1) of
+// the k-steps with a pixel of any D_k != 0 in rows 16 b .. 16 b + 15 (0, 0 for a block that sees none).  D_re, D_im: ndiv arrays
+// len x len column-major.  The PSF kernels of the estimator and of its linearised model skip what lies outside.
+void fmpc_host_estimator_qranges(int len, int ndiv, const double* D_re, const double* D_im, std::vector<int>& qr);
+
+// ---- Zernike functions (zernfun.m, zernmodfit.m)
+#define FMPC_ZERNIKE_MAXN 14            // radial orders whose coefficients are exact in a double (14! < 2^53)
+#define FMPC_ZERNIKE_NCOEF 204          // coefficients of every radial polynomial R_n^|m| with n <= 14
+// The (n, m) pairs of zernmodfit.m:195-198: for n = 0..N, m = -n, -n + 2, .., n.  Returns (N + 1)(N + 2) / 2 (0 for N < 0);
+// n_out, m_out may be NULL (count only).
+int fmpc_host_zernike_modes(int N, int* n_out, int* m_out);
+// The factorial quotients of zernfun.m:166-170 for every (n, |m|) with n <= 14: R_n^|m|(r) = sum_s coef[off[n][|m| / 2] + s]
+// r^(n - 2 s), s = 0 .. (n - |m|) / 2.  Every coefficient is an integer below 2^53: exact.
+void fmpc_host_zernike_coefficients(double coef[FMPC_ZERNIKE_NCOEF], unsigned short off[FMPC_ZERNIKE_MAXN + 1][8]);

@@ -46,6 +46,19 @@ class PhaseDiversityEstimator:
         self._lib.fmpc_est_dims(self._h, None, None, None, None, None, C.byref(rk))
         self.rank = rk.value
 
+    @classmethod
+    def _from_handle(cls, h, device):
+        """An estimator around a handle the library made (fmpc_est_create_from_model); it owns the handle."""
+        self = cls.__new__(cls)
+        self._lib = _lib.load()
+        v = [C.c_int() for _ in range(6)]
+        rc = self._lib.fmpc_est_dims(h, *[C.byref(x) for x in v])
+        if rc != 0:
+            raise FastMPCError(rc, "fmpc_est_dims")
+        self._h, self.device = h, int(device)
+        self.len, self.d, self.ndiv, self.nx, self.p, self.rank = (x.value for x in v)
+        return self
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.fmpc_est_destroy(self._h)

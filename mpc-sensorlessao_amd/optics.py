@@ -1,0 +1,177 @@
+"""The estimator's optics on the device: the Zernike mode maps (the reference's zernfun.m in zernmodfit.m's mode order; its
+Zs.mat is not shipped) and the first-order image model y = b_s + A_s alpha (its model_approx.mat, loaded at README.md:294),
+above `fmpc_zernike_*`, `fmpc_est_optics_*`, `fmpc_est_model_device` and `fmpc_est_create_from_model` (include/fastmpc.h).
+
+    Z = zernike_grid(6, 512)                                   # (28, 512, 512) HIP tensor indexed [j, column, row]
+    opt = reference_optics(512)                                # the README's geometry (README.md:366-396)
+    A_s, b_s = opt.model(opt.Z)                                # (p, 28), (p,): model_approx.mat
+    est = opt.estimator(opt.Z, skip=1)                         # a PhaseDiversityEstimator (piston removed, README.md:289)
+
+PIXEL ORDER.  The maps come out in MATLAB's order: pixel (row y, column x) at y + len x, i.e. a tensor indexed
+[j, column, row] -- what `fmpc_est_create` takes for D, what `PhaseDiversityEstimator.apply_device(colmajor=True)`,
+`AOLoop(z_colmajor=True)` and `AOLoop.step(colmajor=True)` take without a copy.  rowmajor=True gives [j, row, column]
+(a transposed copy on the device)."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import FastMPCError
+from .estimator import PhaseDiversityEstimator
+
+
+def zernike_modes(N):
+    """(n, m) of zernmodfit.m:195-198: for n = 0..N, m = -n, -n + 2, .., n; two int32 arrays of (N + 1)(N + 2) / 2."""
+    lib = _lib.load()
+    cnt = lib.fmpc_zernike_modes(int(N), None, None)
+    n = np.zeros(cnt, dtype=np.int32); m = np.zeros(cnt, dtype=np.int32)
+    lib.fmpc_zernike_modes(int(N), n.ctypes.data_as(_lib._ip), m.ctypes.data_as(_lib._ip))
+    return n, m
+
+
+def _pairs(N_or_pairs):
+    if np.ndim(N_or_pairs) == 0:
+        return zernike_modes(int(N_or_pairs))
+    n, m = N_or_pairs
+    return np.ascontiguousarray(n, dtype=np.int32).reshape(-1), np.ascontiguousarray(m, dtype=np.int32).reshape(-1)
+
+
+def _stream(dev):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def zernike_basis(n, m, r, theta, normalized=False, out=None):
+    """zernfun(n, m, r, theta[, 'norm']) on the device.  r, theta: contiguous float64 HIP tensors of npx points; returns
+    (nmode, npx), or fills out: (nmode, >= npx) with unit column stride (its row stride is passed as ldz).  r outside [0, 1] is
+    evaluated as the polynomial."""
+    import torch
+    n, m = _pairs((n, m))
+    for t in (r, theta):
+        if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+            raise FastMPCError(_lib.FMPC_E_DIM, "r, theta: need contiguous float64 HIP tensors")
+    npx = int(r.numel())
+    if int(theta.numel()) != npx or len(n) != len(m):
+        raise FastMPCError(_lib.FMPC_E_DIM, "r and theta, n and m: equal lengths")
+    Z = torch.empty((len(n), npx), dtype=torch.float64, device=r.device) if out is None else out
+    if not Z.is_cuda or Z.dtype != torch.float64 or Z.dim() != 2 or Z.shape[0] != len(n) or Z.shape[1] < npx or (Z.shape[1] > 1 and Z.stride(1) != 1):
+        raise FastMPCError(_lib.FMPC_E_DIM, "out: need a float64 HIP tensor (nmode, >= npx) with unit column stride")
+    ldz = int(Z.stride(0)) if len(n) > 1 else npx
+    rc = _lib.load().fmpc_zernike_device(len(n), n.ctypes.data_as(_lib._ip), m.ctypes.data_as(_lib._ip), npx, C.c_void_p(r.data_ptr()),
+                                         C.c_void_p(theta.data_ptr()), int(bool(normalized)), C.c_void_p(Z.data_ptr()), ldz, _stream(r.device))
+    if rc != _lib.FMPC_OK:
+        raise FastMPCError(rc, "fmpc_zernike_device")
+    return Z
+
+
+def zernike_grid(N_or_pairs, length, normalized=False, rowmajor=False, device=0):
+    """The modes on the length x length grid x = (-N:2:N)/N, N = length - 1, zero where r > 1: a HIP tensor
+    (nmode, length, length) indexed [j, column, row] (MATLAB's order in memory); rowmajor=True: [j, row, column]."""
+    import torch
+    n, m = _pairs(N_or_pairs)
+    dev = torch.device("cuda", int(device))
+    Z = torch.empty((len(n), int(length), int(length)), dtype=torch.float64, device=dev)
+    rc = _lib.load().fmpc_zernike_grid_device(len(n), n.ctypes.data_as(_lib._ip), m.ctypes.data_as(_lib._ip), int(length),
+                                              int(bool(normalized)), C.c_void_p(Z.data_ptr()), _stream(dev))
+    if rc != _lib.FMPC_OK:
+        raise FastMPCError(rc, "fmpc_zernike_grid_device")
+    return Z.transpose(-1, -2).contiguous() if rowmajor else Z
+
+
+class EstimatorOptics:
+    """pupil, W: (len, len) indexed [row, column], host arrays or tensors; zd_list: the diversities; range_min, range_max: the
+    reference's 1-based window bounds (README.md:378-379).  D_k = pupil .* exp(1i*zd_list(k)*W) is formed here once."""
+
+    def __init__(self, pupil, W, zd_list, dx, range_min, range_max, AU=1e12, device=0):
+        self._lib = _lib.load()
+        to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        pupil = np.asarray(to_np(pupil), dtype=np.float64); W = np.asarray(to_np(W), dtype=np.float64)
+        zd = np.asarray(zd_list, dtype=np.float64).reshape(-1)
+        D = pupil[None] * np.exp(1j * zd[:, None, None] * W[None])           # README.md:464-465 without the screen
+        Dre = np.ascontiguousarray(np.swapaxes(D.real, -1, -2)); Dim = np.ascontiguousarray(np.swapaxes(D.imag, -1, -2))
+        self.len, self.d, self.first, self.ndiv = int(pupil.shape[0]), int(range_max) - int(range_min) + 1, int(range_min) - 1, len(zd)
+        self.p, self.device = self.ndiv * self.d * self.d, int(device)
+        h = C.c_void_p()
+        rc = self._lib.fmpc_est_optics_create(C.byref(h), self.len, self.first, self.d, self.ndiv, Dre.ctypes.data_as(C.c_void_p),
+                                              Dim.ctypes.data_as(C.c_void_p), float(dx) ** 4 * float(AU), self.device)
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_est_optics_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.fmpc_est_optics_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def workspace_bytes(self, nmode=1):
+        """Recommended workspace of `model` in bytes (nmode = 1: the minimum)."""
+        return int(self._lib.fmpc_est_model_workspace_bytes(self._h, int(nmode)))
+
+    def _maps(self, Z, phi0):
+        import torch
+        if not Z.is_cuda or Z.dtype != torch.float64 or not Z.is_contiguous() or tuple(Z.shape[1:]) != (self.len, self.len):
+            raise FastMPCError(_lib.FMPC_E_DIM, "Z: need a contiguous float64 HIP tensor (nmode, len, len) indexed [j, column, row]")
+        if phi0 is not None and (not phi0.is_cuda or phi0.dtype != torch.float64 or not phi0.is_contiguous() or tuple(phi0.shape) != (self.len, self.len)):
+            raise FastMPCError(_lib.FMPC_E_DIM, "phi0: need a contiguous float64 HIP tensor (len, len) indexed [column, row]")
+        return int(Z.shape[0])
+
+    def model(self, Z, phi0=None, workspace=None, out=None):
+        """Z: (nmode, len, len) HIP tensor indexed [j, column, row] (`zernike_grid`); phi0: (len, len) indexed [column, row] or
+        None (zero aberration).  Returns (A_s (p, nmode), b_s (p,)) on torch's current stream; A_s is a view over column-major
+        storage.  workspace: a torch.uint8 HIP tensor of at least `workspace_bytes(1)`; out: (A_s, b_s) of an earlier call."""
+        import torch
+        nmode = self._maps(Z, phi0)
+        if workspace is None:
+            workspace = torch.empty(self.workspace_bytes(nmode), dtype=torch.uint8, device=Z.device)
+        if out is None:
+            At = torch.empty((nmode, self.p), dtype=torch.float64, device=Z.device); b = torch.empty(self.p, dtype=torch.float64, device=Z.device)
+        else:
+            At, b = out[0].t(), out[1]
+            assert At.is_contiguous() and tuple(At.shape) == (nmode, self.p) and b.is_contiguous() and tuple(b.shape) == (self.p,)
+        rc = self._lib.fmpc_est_model_device(self._h, nmode, C.c_void_p(Z.data_ptr()), None if phi0 is None else C.c_void_p(phi0.data_ptr()),
+                                             C.c_void_p(At.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(workspace.data_ptr()),
+                                             workspace.numel(), _stream(Z.device))
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_est_model_device")
+        return At.t(), b
+
+    def estimator(self, Z, skip=1, phi0=None):
+        """The estimator of this model without its first `skip` columns (README.md:289 removes the piston).  Synchronises."""
+        import torch
+        nmode = self._maps(Z, phi0)
+        torch.cuda.current_stream(Z.device).synchronize()                  # (the library runs the model on the null stream)
+        h = C.c_void_p()
+        rc = self._lib.fmpc_est_create_from_model(C.byref(h), self._h, nmode, int(skip), C.c_void_p(Z.data_ptr()),
+                                                  None if phi0 is None else C.c_void_p(phi0.data_ptr()))
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_est_create_from_model")
+        return PhaseDiversityEstimator._from_handle(h, self.device)
+
+
+def reference_optics(length=512, dx=6.5e-6, N=6, zd_dist=3.0, AU=1e12, device=0):
+    """The README's geometry (README.md:366-396): the pin-hole pupil, defocus (mode index 4 of zernmodfit's order, unnormalised)
+    as the diversity, zd_list = [-3 0 3], the window |x| <= 1e-4 m (31 samples on the 512 grid).  Returns an `EstimatorOptics`
+    with `.Z` (the (N + 1)(N + 2) / 2 mode maps on the device, [j, column, row]), `.zd_list`, `.range_min`, `.range_max`
+    (1-based), `.dx`, `.AU` and `.pupil` (host)."""
+    length = int(length)
+    Z = zernike_grid(N, length, device=device)
+    df = 1.0 / (length * dx)
+    fx = np.arange(-length // 2, length // 2) * df
+    FX, FY = np.meshgrid(fx, -fx)
+    pupil = (np.sqrt(FX ** 2 + FY ** 2) <= (length / 2 - 1) * df).astype(np.float64)      # README.md:383-391
+    xaxis = np.arange(-length // 2, length // 2) * dx
+    rmin = int(np.nonzero(np.abs(xaxis + 1.0e-4) < 3e-6)[0][0]) + 1                       # README.md:378-379 (1-based)
+    rmax = int(np.nonzero(np.abs(xaxis - 1.0e-4) < 3e-6)[0][-1]) + 1
+    zd_list = np.array([-zd_dist, 0.0, zd_dist])
+    W = Z[4].t()                                                                          # [row, column]
+    opt = EstimatorOptics(pupil, W, zd_list, dx, rmin, rmax, AU=AU, device=device)
+    opt.Z, opt.zd_list, opt.range_min, opt.range_max, opt.dx, opt.AU, opt.pupil = Z, zd_list, rmin, rmax, dx, AU, pupil
+    return opt
