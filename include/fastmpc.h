@@ -939,6 +939,54 @@ int fmpc_est_apply_device(fmpc_est e, int batch, const double* scrn, const doubl
                           void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
+ * Measurement noise drawn on the device.  The reference's loop adds noise to the PSF windows before it estimates,
+ *     Y_M = Y_M + squeeze(SNR_data(sample,iSimStep,:))            README.md:473-475  ("SNR = 10 [dB]", README.md:295, 348)
+ * from SNR_10.mat, which is not shipped, and no reference code says how it was made.  These calls draw the noise inside the
+ * estimator's finish pass, from a counter: a realisation gets the same noise wherever it sits in a batch, on any rank.
+ *
+ * The draw   g(seed, step, R, i), a standard normal that is a pure function of a 64-bit seed, a 64-bit step, the GLOBAL index R of
+ *            the realisation (0 <= R < 2^32) and the index i of the measurement (0 <= i < p), of nothing else:
+ *              Philox4x32-10 (multipliers D2511F53, CD9E8D57; Weyl constants 9E3779B9, BB67AE85), key = (seed low 32, seed high
+ *              32), counter = (i >> 1, R, step low 32, step high 32), output x0 .. x3;
+ *              u1 = (((x0 >> 6) 2^26 + (x1 >> 6)) + 0.5) 2^-52, u2 likewise from x2, x3: strictly inside (0, 1);
+ *              g = sqrt(-2 ln u1) cos(2 pi u2) for even i, sqrt(-2 ln u1) sin(2 pi u2) for odd i;  |g| <= 8.57.
+ * fmpc_noise mode FMPC_NOISE_SIGMA: sigma_r = value, or sigma_dev[r] (device, batch doubles) when sigma_dev != NULL.
+ *            mode FMPC_NOISE_SNR_MEASURED: sigma_r = sqrt(mean_i(Y0[r][i]^2) 10^(-value / 10)), Y0 = this call's noise-free Y_M --
+ *            the convention of MATLAB's awgn(x, snr, 'measured').  The reference's own convention is UNKNOWN (its samples are not
+ *            shipped); fmpc_est_snr_sigma -- the power of the unaberrated image b_s, one sigma for every screen and step -- is
+ *            the fixed-sigma alternative that a precomputed file would correspond to (use it with FMPC_NOISE_SIGMA).
+ *            seed, step: of the draw.  step_dev: a device counter of one 64-bit word whose value is ADDED to step when the kernel
+ *            runs, or NULL -- a captured graph draws fresh noise on every replay when the caller advances the counter in the same
+ *            capture.  first: the global index of realisation 0 of this call (a rank's or a batch split's offset).
+ * fmpc_est_apply_noisy_device   Y_M[r][i] = Y0[r][i] + fl(sigma_r g(seed, step + *step_dev, first + r, i)): the product and the
+ *            sum rounded once each, never fused, so that this call and "fmpc_noise_normal_device, then fmpc_est_apply_device with
+ *            that array as noise" give the same bits (SIGMA mode).  scrn, ad_est, Y_out (NULL allowed) as in
+ *            fmpc_est_apply_device; sigma_out: batch doubles (device) that receive sigma_r, or NULL.  No batch x p array of noise
+ *            exists in either mode.  Like fmpc_est_apply_device it does not synchronise and, once the handle's workspace has
+ *            served a batch of this size, does not allocate: it can be recorded into a graph.
+ * fmpc_noise_normal_device / _host   out[r ld + i] = fl(sigma_r g), r < batch, i < p; ld >= p (0 = p), the padding is not
+ *            written.  SIGMA mode only.  The host form reads no device pointer: sigma_dev and step_dev must be NULL.
+ * fmpc_est_snr_sigma   host: *sigma = sqrt(mean(b_s^2) 10^(-snr_db / 10)).
+ * fmpc_philox4x32_10   host: one block of the generator (the Random123 known answers hold).
+ * Errors, all found before the device is touched: FMPC_E_NULL for a NULL e, nz, scrn, ad_est / out / sigma; FMPC_E_DIM for a mode
+ * other than the two, batch < 0, first < 0, first + batch > 2^32, a negative or non-finite value in SIGMA mode, a non-finite one
+ * in SNR mode, sigma_dev in SNR mode, p < 1, ld < p.  batch == 0 is FMPC_OK.
+ */
+#define FMPC_NOISE_SIGMA         0
+#define FMPC_NOISE_SNR_MEASURED  1
+typedef struct fmpc_noise_s {
+    int mode; double value; const double* sigma_dev;
+    unsigned long long seed, step; const unsigned long long* step_dev;
+    long long first;
+} fmpc_noise;
+int fmpc_est_apply_noisy_device(fmpc_est e, int batch, const double* scrn, const fmpc_noise* nz,
+                                double* ad_est, double* Y_out, double* sigma_out, void* stream);
+int fmpc_noise_normal_device(double* out, int batch, int p, long long ld, const fmpc_noise* nz, void* stream);
+int fmpc_noise_normal_host(double* out, int batch, int p, long long ld, const fmpc_noise* nz);
+int fmpc_est_snr_sigma(fmpc_est e, double snr_db, double* sigma);
+int fmpc_philox4x32_10(const unsigned int counter[4], const unsigned int key[2], unsigned int out[4]);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
  * Zernike functions on the device: the reference's zernfun.m, in the mode order of zernmodfit.m:195-198 (Zs.mat, which the
  * reference loads at README.md:266, is not shipped: these calls rebuild it).
  *

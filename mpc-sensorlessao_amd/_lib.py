@@ -45,6 +45,16 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p
 
+# fmpc_noise: the noise block of fmpc_est_apply_noisy_device / fmpc_noise_normal_*
+FMPC_NOISE_SIGMA = 0
+FMPC_NOISE_SNR_MEASURED = 1
+
+
+class Noise(C.Structure):
+    _fields_ = [("mode", C.c_int), ("value", C.c_double), ("sigma_dev", _vp), ("seed", C.c_ulonglong), ("step", C.c_ulonglong),
+                ("step_dev", _vp), ("first", C.c_longlong)]
+
+
 # name -> (restype, argtypes); every symbol include/fastmpc.h declares
 SIGNATURES = {
     "fmpc_version": (C.c_int, []),
@@ -116,6 +126,11 @@ SIGNATURES = {
     "fmpc_est_dims": (C.c_int, [_vp] + [_ip] * 6),
     "fmpc_est_apply": (C.c_int, [_vp, C.c_int] + [_vp] * 4),
     "fmpc_est_apply_device": (C.c_int, [_vp, C.c_int] + [_vp] * 4 + [_vp]),
+    "fmpc_est_apply_noisy_device": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(Noise), _vp, _vp, _vp, _vp]),
+    "fmpc_noise_normal_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_longlong, C.POINTER(Noise), _vp]),
+    "fmpc_noise_normal_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_longlong, C.POINTER(Noise)]),
+    "fmpc_est_snr_sigma": (C.c_int, [_vp, C.c_double, _dp]),
+    "fmpc_philox4x32_10": (C.c_int, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "fmpc_modal_workspace_bytes": (C.c_size_t, [C.c_int, C.c_longlong, C.c_int]),
     "fmpc_modal_factor_device": (C.c_int, [C.c_int, C.c_longlong, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fmpc_modal_fit_device": (C.c_int, [C.c_int, C.c_longlong, C.c_int, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp]),

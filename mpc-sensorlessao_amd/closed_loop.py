@@ -230,6 +230,8 @@ class AOLoop:
     def step(self, phase_k, noise=None, colmajor=False):
         """phase_k: (batch, len, len) float64 HIP tensor indexed [b, row, column] (phase_valid(:,:,k) of every realisation);
         colmajor=True: indexed [b, column, row] already -- the order MATLAB keeps phase_valid(:,:,k) in -- and no copy is made.
+        noise: None, the (batch, p) tensor Y_M_noise of this step, or an `EstimatorNoise` that is drawn on the device with
+        `steps_done` as its step (README.md:473-475).
         Returns (u[k] (batch, m), ad_est (batch, n)); both views valid until two further steps / the next step."""
         torch, C = self._torch, self._C
         s = self.steps_done
@@ -246,7 +248,7 @@ class AOLoop:
         self.x0, self.x0_pre = self._xb[s % 2], self._xb[(s + 1) % 2]
         if s == 0:
             self.x0_pre.zero_()
-        self.est.apply_device(self.scrn, noise, colmajor=True, out=self.x0)
+        self.est.apply_device(self.scrn, noise, colmajor=True, out=self.x0, step=s)
         # b_ref = -M1 B u[k-1] - M2 B u[k-2] (README.md:490-497) and the fastMPC step on (x0, x0_pre, b_ref) in one call
         if self.one_call:
             rc = self.h._lib.fmpc_ao_step_device(self.h._h, self.batch, vp(self.x0), vp(self.x0_pre), vp(u1) if s >= 1 else None, vp(u2) if s >= 2 else None,

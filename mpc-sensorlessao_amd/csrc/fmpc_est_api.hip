@@ -8,18 +8,7 @@
 #include "../../include/fastmpc.h"
 #include "fmpc_estimator.h"
 #include "fmpc_host.h"
-#include "fmpc_alloc.h"                    // owned, counted buffers: the estimator's buffers move fmpc_alloc_generation too
-
-struct fmpc_est_s {
-    int device, len, d, first, ndiv, nx, p, rank;
-    double scale;
-    DevBuf<double> pool;                 // D_re | D_im | Fimg | G | b_s
-    size_t oDre, oDim, oF, oG, ob;
-    DevBuf<int> qlist;                   // [len / 16][2]: range of the k-steps inside the pupil per row block
-    DevBuf<double> part; size_t part_batch = 0;        // workspace, grown with the batch
-    DevBuf<double> shares;
-    std::mutex mu;
-};
+#include "fmpc_est_handle.h"               // fmpc_est_s, fe_est_grow, fe_est_params (shared with fmpc_noise_api.hip)
 
 extern "C" int fmpc_est_create(fmpc_est* out, int len, int first, int d, int ndiv, const double* D_re, const double* D_im,
                                double scale, const double* A_s, const double* b_s, int p, int nx, int device) {
@@ -31,6 +20,7 @@ extern "C" int fmpc_est_create(fmpc_est* out, int len, int first, int d, int ndi
     fmpc_est_s* e = new (std::nothrow) fmpc_est_s();
     if (!e) return FMPC_E_ALLOC;
     e->device = device; e->len = len; e->d = d; e->first = first; e->ndiv = ndiv; e->nx = nx; e->p = p; e->scale = scale;
+    e->bs_power = fmpc_host_mean_square(b_s, p);
     std::vector<double> G, Fimg;
     e->rank = fmpc_host_estimator_gain(A_s, p, nx, G);
     fmpc_host_estimator_dft_images(len, d, first, Fimg);
@@ -73,24 +63,8 @@ extern "C" int fmpc_est_apply_device(fmpc_est e, int batch, const double* scrn, 
     if (batch == 0) return FMPC_OK;
     if (hipSetDevice(e->device) != hipSuccess) return FMPC_E_HIP;
     std::lock_guard<std::mutex> lk(e->mu);
-    if ((size_t)batch > e->part_batch) {
-        e->part_batch = 0;
-        size_t cap = 1;
-        while (cap < (size_t)batch) cap *= 2;
-        // (few screens: the PSF kernel may split the columns of a row block over two workgroups -- room for the FE_SPLIT_MAX
-        //  (screen, diversity) pairs of that shape at 128 partial windows each, whatever ndiv: 4 ndiv x 128 was too little for
-        //  9 to 12 screens of ONE diversity, which then ran without the split)
-        const size_t pw_split = (size_t)FE_SPLIT_MAX * 128;
-        const size_t pw = cap * e->ndiv * (e->len / 16) < pw_split ? pw_split : cap * e->ndiv * (e->len / 16);
-        if (e->part.alloc(pw * 2048, (hipStream_t)stream) != FMPC_OK ||
-            e->shares.alloc(cap * e->ndiv * 4 * e->nx, (hipStream_t)stream) != FMPC_OK) return FMPC_E_ALLOC;
-        e->part_batch = cap;
-    }
-    FeParams P;
-    P.len = e->len; P.d = e->d; P.ndiv = e->ndiv; P.nx = e->nx; P.batch = batch; P.scale = e->scale;
-    P.scrn = scrn; P.noise = noise; P.Dre = e->pool + e->oDre; P.Dim = e->pool + e->oDim; P.Fimg = e->pool + e->oF;
-    P.qrange = e->qlist;
-    P.G = e->pool + e->oG; P.bs = e->pool + e->ob; P.part = e->part; P.shares = e->shares; P.shares_cap = e->part_batch * (size_t)e->ndiv * 4 * e->nx; P.nshare = 1; P.part_cap = e->part.cap; P.ad_est = ad_est; P.Yout = Y_out;
+    if (fe_est_grow(e, batch, (hipStream_t)stream) != FMPC_OK) return FMPC_E_ALLOC;
+    const FeParams P = fe_est_params(e, batch, scrn, noise, ad_est, Y_out);
     return fmpc_launch_estimator(P, (hipStream_t)stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 

@@ -18,7 +18,21 @@ struct FeParams {
     size_t shares_cap, part_cap;        // doubles allocated behind `shares` / `part`
     int nshare;                         // set by the launcher: 1, or 4 for the few-screen finish
     double* ad_est; double* Yout;       // [batch][nx], [batch][p] or NULL
+    // ---- noise drawn in the finish pass (fmpc_est_apply_noisy_device; fmpc_noise.h).  Behind everything the noise-free kernels
+    //      read, so that their argument offsets stay where they were; nz_mode = FE_NZ_OFF for fmpc_est_apply[_device].
+    int nz_mode = 0;                    // FE_NZ_*
+    double nz_value = 0.0;              // SIGMA: sigma of every realisation (nz_sigma_dev == NULL); SNR: 10^(-snr_db / 10) / p
+    const double* nz_sigma_dev = nullptr;               // SIGMA: [batch] or NULL
+    unsigned long long nz_seed = 0, nz_step = 0, nz_first = 0;
+    const unsigned long long* nz_step_dev = nullptr;    // device counter added to nz_step, or NULL
+    double* nz_shares = nullptr;        // SNR: [batch][ndiv][nshare][nx] shares of G g for unit noise
+    double* nz_power = nullptr;         // SNR: [batch][ndiv][nshare] partial sums of Y0^2
+    double* nz_sigma = nullptr;         // SNR: [batch] sigma_r, left by the combine pass for the pass over Y_out
+    double* sigma_out = nullptr;        // [batch] or NULL
 };
+#define FE_NZ_OFF   0
+#define FE_NZ_SIGMA 1                   // Y_M += fl(sigma_r g) inside the finish pass
+#define FE_NZ_SNR   2                   // sigma_r from the power of this call's noise-free Y_M: shares of G g, then the combine pass
 
 #define FE_SPLIT_MAX 12                 // (screens x diversities) up to which the PSF kernel splits the columns of a row block in two
 
@@ -41,6 +55,14 @@ static inline bool fe_geometry_ok(int len, int first, int d, int ndiv) {
 }
 
 hipError_t fmpc_launch_estimator(const FeParams& P, hipStream_t stream);
+
+// The stand-alone fill (fmpc_kernel_noise.hip): out[r ld + i] = fl(sigma_r g(seed, step + *step_dev, first + r, i)), i < p.
+struct FnParams {
+    double* out; int batch, p; long long ld;
+    double sigma; const double* sigma_dev;
+    unsigned long long seed, step, first; const unsigned long long* step_dev;
+};
+hipError_t fmpc_launch_noise_fill(const FnParams& P, hipStream_t stream);
 
 // The linearised image model (fmpc_kernel_est_model.hip): fields 0 = P_k (the base) and 1 + j = 1i Z_j .* P_k, P_k = E .* D_k.
 #define FEM_MAXMODE 128

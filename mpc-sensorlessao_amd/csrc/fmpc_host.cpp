@@ -2,6 +2,8 @@
 // sanitizers (tests/host_san).
 #include "fmpc_host.h"
 #include "fmpc_bank.h"
+#include "../../include/fastmpc.h"      // fmpc_noise, the status codes
+#include "fmpc_noise.h"
 
 #include <algorithm>
 #include <math.h>
@@ -1155,4 +1157,43 @@ void fmpc_host_zernike_coefficients(double coef[FMPC_ZERNIKE_NCOEF], unsigned sh
                 coef[o++] = (1 - 2 * (s & 1)) * fact[n - s] / fact[s] / fact[(n - ma) / 2 - s] / fact[(n + ma) / 2 - s];
         }
     }
+}
+
+// ---- measurement noise (fmpc_noise.h): the argument rules of the fmpc_noise block, the draw on the host
+double fmpc_host_mean_square(const double* v, int cnt) {
+    double s = 0.0;
+    for (int i = 0; i < cnt; ++i) s += v[i] * v[i];
+    return cnt > 0 ? s / cnt : 0.0;
+}
+
+int fmpc_host_noise_check(const fmpc_noise* nz, int batch, int sigma_only) {
+    if (!nz) return FMPC_E_NULL;
+    if (nz->mode != FMPC_NOISE_SIGMA && nz->mode != FMPC_NOISE_SNR_MEASURED) return FMPC_E_DIM;
+    if (sigma_only && nz->mode != FMPC_NOISE_SIGMA) return FMPC_E_DIM;
+    if (batch < 0 || nz->first < 0 || nz->first > (1ll << 32) || nz->first + (long long)batch > (1ll << 32)) return FMPC_E_DIM;
+    if (!std::isfinite(nz->value)) return FMPC_E_DIM;
+    if (nz->mode == FMPC_NOISE_SIGMA && nz->value < 0.0) return FMPC_E_DIM;
+    if (nz->mode == FMPC_NOISE_SNR_MEASURED && nz->sigma_dev) return FMPC_E_DIM;
+    return FMPC_OK;
+}
+
+extern "C" int fmpc_philox4x32_10(const unsigned int counter[4], const unsigned int key[2], unsigned int out[4]) {
+    if (!counter || !key || !out) return FMPC_E_NULL;
+    uint32_t c[4] = {counter[0], counter[1], counter[2], counter[3]}, k[2] = {key[0], key[1]}, x[4];
+    fmpc_philox4x32_10_block(c, k, x);
+    for (int i = 0; i < 4; ++i) out[i] = x[i];
+    return FMPC_OK;
+}
+
+extern "C" int fmpc_noise_normal_host(double* out, int batch, int p, long long ld, const fmpc_noise* nz) {
+    if (!out || !nz) return FMPC_E_NULL;
+    const int rc = fmpc_host_noise_check(nz, batch, 1);
+    if (rc != FMPC_OK) return rc;
+    if (p < 1 || (ld != 0 && ld < p)) return FMPC_E_DIM;
+    if (nz->sigma_dev || nz->step_dev) return FMPC_E_DIM;          // device pointers: not readable here
+    if (ld == 0) ld = p;
+    for (int r = 0; r < batch; ++r)
+        for (int i = 0; i < p; ++i)
+            out[(size_t)r * ld + i] = fmpc_noise_scaled(nz->value, fmpc_noise_normal(nz->seed, nz->step, (uint32_t)(nz->first + r), (uint32_t)i));
+    return FMPC_OK;
 }

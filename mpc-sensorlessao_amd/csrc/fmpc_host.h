@@ -219,6 +219,15 @@ void fmpc_host_estimator_dft_images(int len, int d, int first, std::vector<doubl
 // len x len column-major.  The PSF kernels of the estimator and of its linearised model skip what lies outside.
 void fmpc_host_estimator_qranges(int len, int ndiv, const double* D_re, const double* D_im, std::vector<int>& qr);
 
+// ---- measurement noise (include/fastmpc.h: fmpc_noise; the draw itself: fmpc_noise.h)
+// mean(v^2): the power of the unaberrated image b_s behind fmpc_est_snr_sigma
+double fmpc_host_mean_square(const double* v, int cnt);
+// The argument rules of an fmpc_noise block for a call over `batch` realisations: FMPC_E_NULL for nz == NULL; FMPC_E_DIM for an
+// unknown mode (sigma_only: anything but FMPC_NOISE_SIGMA), batch < 0, first < 0, first + batch > 2^32, a non-finite value, a
+// negative sigma, sigma_dev in SNR mode.  No pointer of the block is read.
+struct fmpc_noise_s;
+int fmpc_host_noise_check(const struct fmpc_noise_s* nz, int batch, int sigma_only);
+
 // ---- Zernike functions (zernfun.m, zernmodfit.m)
 #define FMPC_ZERNIKE_MAXN 14            // radial orders whose coefficients are exact in a double (14! < 2^53)
 #define FMPC_ZERNIKE_NCOEF 204          // coefficients of every radial polynomial R_n^|m| with n <= 14

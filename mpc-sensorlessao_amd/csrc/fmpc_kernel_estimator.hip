@@ -28,6 +28,7 @@
 #include "fmpc_device.h"
 #include "fmpc_estimator.h"
 #include "fmpc_est_dev.h"            // d4e, FE_MFMA, FE_TSTRIDE, fe_sincos
+#include "fmpc_noise.h"              // fmpc_noise_normal, fmpc_noise_add: the draw of the noisy forms
 
 template <int NW>
 __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) fmpc_est_psf(FeParams P) {      // (second argument: workgroups per CU here = 2 wavefronts per SIMD either way)
@@ -144,6 +145,65 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) fmpc_est_psf(FeParam
     }
 }
 
+// The noisy forms (NZ = FE_NZ_SIGMA, FE_NZ_SNR; fmpc_est_apply_noisy_device) are further instances of the same bodies: the thread
+// that owns measurement (r, k, il) evaluates one Philox block and takes its branch of the Box-Muller pair (fmpc_noise.h), so no
+// batch x p array of noise exists.  SIGMA: Y_M += fl(sigma_r g) right here.  SNR: sigma_r needs the power of ALL diversities of the
+// screen, which no workgroup of this pass sees -- the estimate is linear in Y_M, so the pass leaves the noise-free share, a second
+// share G_k g_k for unit noise and its partial sum of Y0^2 (fixed orders), and fmpc_est_combine_noisy puts them together.
+__device__ __forceinline__ unsigned long long fe_nz_step(const FeParams& P) { return P.nz_step + (P.nz_step_dev ? *P.nz_step_dev : 0ull); }
+__device__ __forceinline__ double fe_nz_sigma(const FeParams& P, int r) { return P.nz_sigma_dev ? P.nz_sigma_dev[r] : P.nz_value; }
+
+// |O|^2 with the product that is rounded on its own and the one that is fused WRITTEN DOWN (the compiler, left to contract
+// orr * orr + oi * oi, took either one from build to build): the general finish fuses oi * oi, the few-screen finish orr * orr,
+// as they always have, and their noisy instances give the bits of the noise-free ones.
+#define FE_ABS2_GENERAL(orr, oi) __builtin_fma((oi), (oi), (orr) * (orr))
+#define FE_ABS2_FEW(orr, oi) __builtin_fma((orr), (orr), (oi) * (oi))
+
+// SNR form of the general finish, behind the noise-free share: the partial power of this diversity (butterfly per wavefront, then
+// the 16 wavefronts in order), then the same sums over the rows of G for the unit noise g_k in place of Y - b_s.
+__device__ __forceinline__ void fe_finish_snr_tail(const FeParams& P, double* sY, double* sRed, int r, int k, int dd, int p, int il, double gz, double y2) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __syncthreads();                                         // sRed read by the share's writers
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) y2 += __shfl_xor(y2, o, 64);
+    if (lane == 0) sRed[wv] = y2;
+    if (il >= 0) sY[il] = gz;
+    __syncthreads();
+    if (tid == 0) {
+        const double* q = sRed;
+        P.nz_power[(size_t)r * P.ndiv + k] = (((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]))) +
+                                             (((q[8] + q[9]) + (q[10] + q[11])) + ((q[12] + q[13]) + (q[14] + q[15])));
+    }
+    __syncthreads();
+    constexpr int FE_ROWB = 9;
+    for (int j0 = 0; j0 < P.nx; j0 += FE_ROWB) {
+        double acc[FE_ROWB];
+#pragma unroll
+        for (int jj = 0; jj < FE_ROWB; ++jj) acc[jj] = 0.0;
+        for (int i = tid; i < dd; i += FE_FINISH_THREADS) {
+            const double yv = sY[i];
+            double gv[FE_ROWB];
+#pragma unroll
+            for (int jj = 0; jj < FE_ROWB; ++jj) gv[jj] = P.G[(size_t)(j0 + jj < P.nx ? j0 + jj : j0) * p + k * dd + i];
+#pragma unroll
+            for (int jj = 0; jj < FE_ROWB; ++jj) acc[jj] = fma(gv[jj], yv, acc[jj]);
+        }
+#pragma unroll
+        for (int jj = 0; jj < FE_ROWB; ++jj) {
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) acc[jj] += __shfl_xor(acc[jj], o, 64);
+            if (lane == 0 && j0 + jj < P.nx) sRed[(j0 + jj) * 16 + wv] = acc[jj];
+        }
+    }
+    __syncthreads();
+    if (tid < P.nx) {
+        const double* q = sRed + tid * 16;
+        P.nz_shares[((size_t)r * P.ndiv + k) * P.nx + tid] = (((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]))) +
+                                                             (((q[8] + q[9]) + (q[10] + q[11])) + ((q[12] + q[13]) + (q[14] + q[15])));
+    }
+}
+
+template <int NZ>                                            // FE_NZ_OFF: fmpc_est_apply[_device]
 __global__ void __launch_bounds__(FE_FINISH_THREADS) fmpc_est_finish(FeParams P) {
     extern __shared__ double sY[];                           // d^2 measurements of this diversity minus b_s, then nx x 16 partial sums
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -154,6 +214,8 @@ __global__ void __launch_bounds__(FE_FINISH_THREADS) fmpc_est_finish(FeParams P)
                                                              // lines per load and the kernel took 104 us for one screen), row (y frequency)
     // One workgroup per (screen, diversity), which leaves its share of ad_est (fmpc_est_combine adds the shares).  Every load sits in a chain of dependent steps (a lone screen: the reference's loop): loads are
     // issued in batches of 16 (partial windows) and 9 (rows of G) so that a batch costs one memory round trip, not one each.
+    double gz = 0.0, y2 = 0.0;                               // (noisy forms: this thread's unit noise, the square of its Y0)
+    (void)gz; (void)y2;
     if (u < d && v < d) {
         const double* src = P.part + (((size_t)r * P.ndiv + k) * nblk * 2) * 1024 + u * 32 + v;
         double orr = 0.0, oi = 0.0;                        // fixed order (nblk is a multiple of 4)
@@ -173,8 +235,11 @@ __global__ void __launch_bounds__(FE_FINISH_THREADS) fmpc_est_finish(FeParams P)
             oi += (im[0] + im[1]) + (im[2] + im[3]);
         }
         const int il = v * d + u, idx = k * dd + il;       // reshape(v_im(:,:,k), [], 1): column-major
-        double y = (orr * orr + oi * oi) * P.scale;
-        if (P.noise) y += P.noise[(size_t)r * p + idx];
+        double y = FE_ABS2_GENERAL(orr, oi) * P.scale;
+        if constexpr (NZ == FE_NZ_OFF) { if (P.noise) y += P.noise[(size_t)r * p + idx]; }
+        if constexpr (NZ != FE_NZ_OFF) gz = fmpc_noise_normal(P.nz_seed, fe_nz_step(P), (uint32_t)(P.nz_first + (unsigned long long)r), (uint32_t)idx);
+        if constexpr (NZ == FE_NZ_SIGMA) y = fmpc_noise_add(y, fe_nz_sigma(P, r), gz);
+        if constexpr (NZ == FE_NZ_SNR) y2 = y * y;
         if (P.Yout) P.Yout[(size_t)r * p + idx] = y;
         sY[il] = y - P.bs[idx];
     }
@@ -208,6 +273,7 @@ __global__ void __launch_bounds__(FE_FINISH_THREADS) fmpc_est_finish(FeParams P)
         share[tid] = (((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]))) +
                      (((q[8] + q[9]) + (q[10] + q[11])) + ((q[12] + q[13]) + (q[14] + q[15])));
     }
+    if constexpr (NZ == FE_NZ_SNR) fe_finish_snr_tail(P, sY, sRed, r, k, dd, p, u < d && v < d ? v * d + u : -1, gz, y2);
 }
 
 // fmpc_est_finish for a FEW screens (the reference's loop: one): the same sums by four workgroups of 256 threads per (screen,
@@ -218,7 +284,7 @@ __global__ void __launch_bounds__(FE_FINISH_THREADS) fmpc_est_finish(FeParams P)
 #ifndef FE_FEW_MAX
 #define FE_FEW_MAX 64          // (screens x diversities) up to which the finish pass takes this form
 #endif
-template <int NCH>                                           // partial windows per pixel: 32 NCH (column split of the PSF kernel)
+template <int NCH, int NZ>                                   // partial windows per pixel: 32 NCH (column split of the PSF kernel)
 __global__ void __launch_bounds__(256) fmpc_est_finish_few(FeParams P) {
     __shared__ double sRed[4][32];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -246,8 +312,12 @@ __global__ void __launch_bounds__(256) fmpc_est_finish_few(FeParams P) {
             for (int b = 0; b < NB; ++b) { re[b] = src[(size_t)((ch + 1) * NB + b) * 2048]; im[b] = src[(size_t)((ch + 1) * NB + b) * 2048 + 1024]; }
         }
     }
-    double y = (orr * orr + oi * oi) * P.scale;
-    if (own && P.noise) y += P.noise[(size_t)r * p + idx];
+    double y = FE_ABS2_FEW(orr, oi) * P.scale;
+    if constexpr (NZ == FE_NZ_OFF) { if (own && P.noise) y += P.noise[(size_t)r * p + idx]; }
+    double gz = 0.0;                                          // (noisy forms: this thread's unit noise; fmpc_noise.h)
+    (void)gz;
+    if constexpr (NZ != FE_NZ_OFF) gz = fmpc_noise_normal(P.nz_seed, fe_nz_step(P), (uint32_t)(P.nz_first + (unsigned long long)r), (uint32_t)(own ? idx : 0));
+    if constexpr (NZ == FE_NZ_SIGMA) y = fmpc_noise_add(y, fe_nz_sigma(P, r), gz);
     if (own && P.Yout) P.Yout[(size_t)r * p + idx] = y;
     const double yv = own ? y - P.bs[idx] : 0.0;
     double* share = P.shares + (((size_t)r * P.ndiv + k) * FE_FQ + qd) * P.nx;
@@ -260,7 +330,28 @@ __global__ void __launch_bounds__(256) fmpc_est_finish_few(FeParams P) {
     }
     __syncthreads();
     if (tid < P.nx) share[tid] = (sRed[0][tid] + sRed[1][tid]) + (sRed[2][tid] + sRed[3][tid]);
+    if constexpr (NZ == FE_NZ_SNR) {
+        // the same sums of G_k g_k for unit noise, and this quarter's partial power of Y0 (a spare column of sRed: NG < 32)
+        const double gzv = own ? gz : 0.0;
+        double y2 = own ? y * y : 0.0;
+        __syncthreads();                                      // sRed read by the share's writers
+#pragma unroll
+        for (int j = 0; j < NG; ++j) {
+            double a = j < P.nx ? gv[j] * gzv : 0.0;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64);
+            if (lane == 0) sRed[wv][j] = a;
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) y2 += __shfl_xor(y2, o, 64);
+        if (lane == 0) sRed[wv][31] = y2;
+        __syncthreads();
+        const size_t sh = ((size_t)r * P.ndiv + k) * FE_FQ + qd;
+        if (tid < P.nx) P.nz_shares[sh * P.nx + tid] = (sRed[0][tid] + sRed[1][tid]) + (sRed[2][tid] + sRed[3][tid]);
+        if (tid == 31) P.nz_power[sh] = (sRed[0][31] + sRed[1][31]) + (sRed[2][31] + sRed[3][31]);
+    }
 }
+
 
 // ad_est = sum over the diversities of their shares, in a fixed order.  (A launch of its own: the last-arriving workgroup of
 // fmpc_est_finish doing it needs device-scope release fences, which write back an L2 full of partial windows: 35 % slower at
@@ -275,7 +366,48 @@ __global__ void __launch_bounds__(256) fmpc_est_combine(FeParams P) {
     P.ad_est[i] = a;
 }
 
+// The noisy forms' combine.  SIGMA: the same sum as fmpc_est_combine (the noise is in the shares already), and sigma_r for the
+// caller.  SNR: sigma_r = sqrt(mean(Y0^2) 10^(-snr_db / 10)) from the partial powers in their fixed order, then
+// ad_est = sum of the noise-free shares + sigma_r (sum of the unit-noise shares).
+template <int NZ>
+__global__ void __launch_bounds__(256) fmpc_est_combine_noisy(FeParams P) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P.batch * P.nx) return;
+    const int r = i / P.nx, j = i - r * P.nx, ns = P.ndiv * P.nshare;
+    const double* sh = P.shares + (size_t)r * ns * P.nx + j;
+    double a = 0.0;
+    for (int kk = 0; kk < ns; ++kk) a += sh[(size_t)kk * P.nx];
+    double sigma;
+    if constexpr (NZ == FE_NZ_SNR) {
+        const double* pw = P.nz_power + (size_t)r * ns;
+        const double* nh = P.nz_shares + (size_t)r * ns * P.nx + j;
+        double s2 = 0.0, b = 0.0;
+        for (int kk = 0; kk < ns; ++kk) s2 += pw[kk];
+        for (int kk = 0; kk < ns; ++kk) b += nh[(size_t)kk * P.nx];
+        sigma = sqrt(s2 / (double)(P.ndiv * P.d * P.d) * P.nz_value);
+        a = fmpc_noise_add(a, sigma, b);
+        if (j == 0) P.nz_sigma[r] = sigma;
+    } else {
+        sigma = fe_nz_sigma(P, r);
+    }
+    if (j == 0 && P.sigma_out) P.sigma_out[r] = sigma;
+    P.ad_est[i] = a;
+}
+
+// SNR form with Y_out: the finish pass left Y0 there; add fl(sigma_r g), g drawn again (cheaper than keeping it: no array).
+__global__ void __launch_bounds__(256) fmpc_est_noise_yout(FeParams P) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int p = P.ndiv * P.d * P.d;
+    if (i >= (size_t)P.batch * p) return;
+    const size_t r = i / p;
+    const uint32_t idx = (uint32_t)(i - r * p);
+    const double g = fmpc_noise_normal(P.nz_seed, fe_nz_step(P), (uint32_t)(P.nz_first + r), idx);
+    P.Yout[i] = fmpc_noise_add(P.Yout[i], P.nz_sigma[r], g);
+}
+
 hipError_t fmpc_launch_estimator(const FeParams& P, hipStream_t stream) {
+    if (P.nz_mode < FE_NZ_OFF || P.nz_mode > FE_NZ_SNR) return hipErrorInvalidValue;
+    if (P.nz_mode == FE_NZ_SNR && (!P.nz_shares || !P.nz_power || !P.nz_sigma)) return hipErrorInvalidValue;
     if (P.len % 64 != 0 || P.len < 64 || P.d < 1 || P.d > 32 || P.ndiv < 1 || P.ndiv > FE_MAXDIV) return hipErrorInvalidValue;
     if (!fe_finish_serves(P.d, P.nx)) return hipErrorInvalidValue;      // (fmpc_est_create refuses such a handle)
     // few screens: 8 wavefronts per workgroup so that a lone screen is 256 wavefronts, not 128
@@ -301,13 +433,35 @@ hipError_t fmpc_launch_estimator(const FeParams& P, hipStream_t stream) {
     FeParams Q = P;
     if ((size_t)P.batch * P.ndiv <= FE_FEW_MAX && P.len == 512 && P.nx <= 27 && P.shares_cap >= (size_t)P.batch * P.ndiv * FE_FQ * P.nx) {
         Q.nshare = FE_FQ;
-        if (csplit == 2) hipLaunchKernelGGL(fmpc_est_finish_few<2>, dim3(P.batch, P.ndiv, FE_FQ), dim3(256), 0, stream, Q);
-        else hipLaunchKernelGGL(fmpc_est_finish_few<1>, dim3(P.batch, P.ndiv, FE_FQ), dim3(256), 0, stream, Q);
+        const dim3 grid(P.batch, P.ndiv, FE_FQ);
+        if (P.nz_mode == FE_NZ_OFF) {
+            if (csplit == 2) hipLaunchKernelGGL((fmpc_est_finish_few<2, FE_NZ_OFF>), grid, dim3(256), 0, stream, Q);
+            else hipLaunchKernelGGL((fmpc_est_finish_few<1, FE_NZ_OFF>), grid, dim3(256), 0, stream, Q);
+        } else if (P.nz_mode == FE_NZ_SIGMA) {
+            if (csplit == 2) hipLaunchKernelGGL((fmpc_est_finish_few<2, FE_NZ_SIGMA>), grid, dim3(256), 0, stream, Q);
+            else hipLaunchKernelGGL((fmpc_est_finish_few<1, FE_NZ_SIGMA>), grid, dim3(256), 0, stream, Q);
+        } else {
+            if (csplit == 2) hipLaunchKernelGGL((fmpc_est_finish_few<2, FE_NZ_SNR>), grid, dim3(256), 0, stream, Q);
+            else hipLaunchKernelGGL((fmpc_est_finish_few<1, FE_NZ_SNR>), grid, dim3(256), 0, stream, Q);
+        }
     } else {
         Q.nshare = 1;
-        hipLaunchKernelGGL(fmpc_est_finish, dim3(P.batch, P.ndiv), dim3(FE_FINISH_THREADS), fe_finish_lds_bytes(P.d, P.nx), stream, Q);
+        const dim3 grid(P.batch, P.ndiv);
+        const size_t lds = fe_finish_lds_bytes(P.d, P.nx);
+        if (P.nz_mode == FE_NZ_OFF) hipLaunchKernelGGL(fmpc_est_finish<FE_NZ_OFF>, grid, dim3(FE_FINISH_THREADS), lds, stream, Q);
+        else if (P.nz_mode == FE_NZ_SIGMA) hipLaunchKernelGGL(fmpc_est_finish<FE_NZ_SIGMA>, grid, dim3(FE_FINISH_THREADS), lds, stream, Q);
+        else hipLaunchKernelGGL(fmpc_est_finish<FE_NZ_SNR>, grid, dim3(FE_FINISH_THREADS), lds, stream, Q);
     }
-    hipLaunchKernelGGL(fmpc_est_combine, dim3((P.batch * P.nx + 255) / 256), dim3(256), 0, stream, Q);
+    const dim3 cgrid((P.batch * P.nx + 255) / 256);
+    if (P.nz_mode == FE_NZ_OFF) hipLaunchKernelGGL(fmpc_est_combine, cgrid, dim3(256), 0, stream, Q);
+    else if (P.nz_mode == FE_NZ_SIGMA) hipLaunchKernelGGL(fmpc_est_combine_noisy<FE_NZ_SIGMA>, cgrid, dim3(256), 0, stream, Q);
+    else {
+        hipLaunchKernelGGL(fmpc_est_combine_noisy<FE_NZ_SNR>, cgrid, dim3(256), 0, stream, Q);
+        if (P.Yout) {
+            const size_t cnt = (size_t)P.batch * P.ndiv * P.d * P.d;
+            hipLaunchKernelGGL(fmpc_est_noise_yout, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, Q);
+        }
+    }
     return hipGetLastError();
 }
 

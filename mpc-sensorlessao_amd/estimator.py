@@ -4,7 +4,10 @@ simulation loop, README.md:456-480, for a batch of residual phase screens at onc
     est = PhaseDiversityEstimator(pupil, W, zd_list, dx, range_min, range_max, A_s, b_s)   # MATLAB's 1-based range_min/max
     ad_est = est.apply_device(scrn)            # scrn: (batch, len, len) HIP tensor, scrn[b, i, j] = MATLAB's scrn(i, j)
 
-Arrays are handed over as MATLAB has them (column-major); numpy / torch arrays indexed [row, column] are transposed here."""
+Arrays are handed over as MATLAB has them (column-major); numpy / torch arrays indexed [row, column] are transposed here.
+
+Measurement noise (README.md:473-475, "SNR = 10 [dB]") is drawn on the device from a counter (`EstimatorNoise`, include/fastmpc.h:
+fmpc_noise): `est.apply_device(scrn, noise=EstimatorNoise(snr_db=10, seed=1), step=k)`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,6 +22,79 @@ def _colmajor(a):
     """(len, len) or (k, len, len) indexed [.., row, column] -> contiguous column-major planes."""
     a = np.asarray(a, dtype=np.float64)
     return np.ascontiguousarray(np.swapaxes(a, -1, -2))
+
+
+class EstimatorNoise:
+    """Noise drawn inside the estimator's finish pass: Y_M[r][i] += sigma_r g(seed, step, first + r, i), g a standard normal that is
+    a pure function of its four arguments (Philox4x32-10 + Box-Muller, include/fastmpc.h), so a realisation gets the same noise
+    wherever it sits in a batch.  Exactly one of
+        snr_db   sigma_r = sqrt(mean(Y0[r]^2) 10^(-snr_db / 10)) from this call's noise-free Y_M -- MATLAB's awgn(x, snr, 'measured');
+                 the reference's own convention is unknown (SNR_10.mat is not shipped);
+        sigma    a float, or a HIP tensor of batch doubles (`PhaseDiversityEstimator.snr_sigma` gives the fixed sigma of an SNR
+                 against the unaberrated image).
+    first: the global index of realisation 0 of the batches this is used with.  counter: a HIP tensor of one uint64 / int64 whose
+    value is added to the step when the kernel runs (a captured graph: `counter.add_(1)` in the same capture)."""
+
+    def __init__(self, snr_db=None, sigma=None, seed=0, first=0, counter=None):
+        if (snr_db is None) == (sigma is None):
+            raise ValueError("EstimatorNoise: exactly one of snr_db and sigma")
+        self.snr_db = None if snr_db is None else float(snr_db)
+        self.sigma = sigma if hasattr(sigma, "data_ptr") or sigma is None else float(sigma)
+        self.seed, self.first, self.counter = int(seed), int(first), counter
+        if hasattr(self.sigma, "data_ptr"):
+            import torch
+            assert self.sigma.is_cuda and self.sigma.dtype == torch.float64 and self.sigma.is_contiguous()
+        if counter is not None:
+            import torch
+            assert counter.is_cuda and counter.numel() == 1 and counter.dtype in (torch.int64, getattr(torch, "uint64", torch.int64))
+
+    def _block(self, step=0, batch=None):
+        """The fmpc_noise block of a call at `step` (the tensors it points to stay owned by this object)."""
+        nz = _lib.Noise()
+        if self.snr_db is not None:
+            nz.mode, nz.value, nz.sigma_dev = _lib.FMPC_NOISE_SNR_MEASURED, self.snr_db, None
+        elif hasattr(self.sigma, "data_ptr"):
+            if batch is not None and self.sigma.numel() != batch:
+                raise ValueError("EstimatorNoise: sigma tensor needs one entry per realisation of the batch")
+            nz.mode, nz.value, nz.sigma_dev = _lib.FMPC_NOISE_SIGMA, 0.0, self.sigma.data_ptr()
+        else:
+            nz.mode, nz.value, nz.sigma_dev = _lib.FMPC_NOISE_SIGMA, self.sigma, None
+        nz.seed, nz.step = self.seed & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+        nz.step_dev = None if self.counter is None else self.counter.data_ptr()
+        nz.first = self.first
+        return nz
+
+
+def normal_noise(batch, p, noise, step=0, out=None, device=None):
+    """The array sigma_r g(seed, step, first + r, i) that `apply_device(noise=<EstimatorNoise>)` adds, as a (batch, p) HIP tensor on
+    torch's current stream (fmpc_noise_normal_device; `noise` with sigma, not snr_db).  out: a float64 HIP tensor (batch, >= p) with
+    contiguous rows to fill (columns from p on are left alone)."""
+    import torch
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty((batch, p), dtype=torch.float64, device=torch.device("cuda", 0) if device is None else device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.dim() == 2 and out.shape[0] == batch and out.shape[1] >= p
+    assert out.stride(1) == 1 or out.shape[1] == 1
+    ld = out.stride(0) if batch > 1 else max(out.shape[1], p)
+    nz = noise._block(step, batch)
+    rc = lib.fmpc_noise_normal_device(C.c_void_p(out.data_ptr()), batch, p, ld, C.byref(nz), C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream))
+    if rc != 0:
+        raise FastMPCError(rc, "fmpc_noise_normal_device")
+    return out
+
+
+def normal_noise_host(batch, p, noise, step=0, out=None):
+    """The same array from the host restatement of the draw (fmpc_noise_normal_host; no device): a (batch, p) numpy array."""
+    lib = _lib.load()
+    if out is None:
+        out = np.empty((batch, p))
+    assert out.dtype == np.float64 and out.ndim == 2 and out.shape[0] == batch and out.shape[1] >= p and out.strides[1] == 8
+    ld = out.strides[0] // 8 if batch > 1 else max(out.shape[1], p)
+    nz = noise._block(step, batch)
+    rc = lib.fmpc_noise_normal_host(out.ctypes.data_as(C.c_void_p), batch, p, ld, C.byref(nz))
+    if rc != 0:
+        raise FastMPCError(rc, "fmpc_noise_normal_host")
+    return out
 
 
 class PhaseDiversityEstimator:
@@ -70,9 +146,19 @@ class PhaseDiversityEstimator:
         except Exception:
             pass
 
-    def apply_device(self, scrn, noise=None, want_Y=False, colmajor=False, out=None):
+    def snr_sigma(self, snr_db):
+        """sqrt(mean(b_s^2) 10^(-snr_db / 10)): the fixed sigma of an SNR against the unaberrated image (fmpc_est_snr_sigma)."""
+        s = C.c_double()
+        rc = self._lib.fmpc_est_snr_sigma(self._h, float(snr_db), C.byref(s))
+        if rc != 0:
+            raise FastMPCError(rc, "fmpc_est_snr_sigma")
+        return s.value
+
+    def apply_device(self, scrn, noise=None, want_Y=False, colmajor=False, out=None, step=0, want_sigma=False):
         """scrn: (batch, len, len) float64 HIP tensor indexed [b, row, column] (colmajor=True: already [b, column, row], no copy).
-        Returns ad_est (batch, nx) [, Y_M (batch, p)] on torch's current stream; out: a (batch, nx) tensor to write ad_est into."""
+        noise: None, a (batch, p) HIP tensor that is added to Y_M, or an `EstimatorNoise` drawn on the device at `step`.
+        Returns ad_est (batch, nx) [, Y_M (batch, p)] [, sigma (batch): want_sigma, with an EstimatorNoise] on torch's current
+        stream; out: a (batch, nx) tensor to write ad_est into."""
         import torch
         if not colmajor:
             scrn = scrn.transpose(-1, -2).contiguous()
@@ -82,6 +168,18 @@ class PhaseDiversityEstimator:
             assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (batch, self.nx)
         ad = out if out is not None else torch.empty((batch, self.nx), dtype=torch.float64, device=scrn.device)
         Y = torch.empty((batch, self.p), dtype=torch.float64, device=scrn.device) if want_Y else None
+        if isinstance(noise, EstimatorNoise):
+            sig = torch.empty(batch, dtype=torch.float64, device=scrn.device) if want_sigma else None
+            nz = noise._block(step, batch)
+            rc = self._lib.fmpc_est_apply_noisy_device(self._h, batch, C.c_void_p(scrn.data_ptr()), C.byref(nz), C.c_void_p(ad.data_ptr()),
+                                                       None if Y is None else C.c_void_p(Y.data_ptr()), None if sig is None else C.c_void_p(sig.data_ptr()),
+                                                       C.c_void_p(torch.cuda.current_stream(scrn.device).cuda_stream))
+            if rc != 0:
+                raise FastMPCError(rc, "fmpc_est_apply_noisy_device")
+            res = (ad,) + ((Y,) if want_Y else ()) + ((sig,) if want_sigma else ())
+            return res if len(res) > 1 else ad
+        if want_sigma:
+            raise ValueError("want_sigma: only with an EstimatorNoise")
         if noise is not None:
             assert noise.is_cuda and noise.dtype == torch.float64 and noise.is_contiguous() and tuple(noise.shape) == (batch, self.p)
         vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
