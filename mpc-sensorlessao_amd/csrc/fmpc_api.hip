@@ -23,8 +23,8 @@
 #include "fmpc_bank.h"
 #include "fmpc_records.h"
 #include "fmpc_kkt.h"
-#define FMPC_PRODUCT_MIN_BATCH_DEFAULT 65   // closed-loop steps with first moves only: the product form from this many realisations on
-#include "fmpc_alloc.h"                    // owned, counted buffers (fmpc_alloc_generation), shared with fmpc_est_api.hip
+#include "fmpc_estimator.h"
+#include "fmpc_handle.h"
 
 std::atomic<unsigned long long> fmpc_alloc_gen{0};
 extern "C" unsigned long long fmpc_alloc_generation(void) { return fmpc_alloc_gen.load(); }
@@ -49,10 +49,6 @@ hipError_t fmpc_launch_unpack(int n, int m, int T, int batch, const double* z, d
 hipError_t fmpc_launch_loop_inputs(int n, int m, int T, int batch, const double* Bt, const double* M1, const double* M2,
                                    const double* a, const double* x0_last, const double* u1, const double* u2,
                                    double* x0, double* x0_pre, double* w, hipStream_t stream, double* lv = nullptr);
-// closed-loop records (fmpc_kernel_records.hip)
-hipError_t fmpc_launch_loop_records(const RecParams& P, int panel, hipStream_t stream);
-// ... with the model bank (fmpc_kernel_records_bank.hip)
-hipError_t fmpc_launch_loop_records_bank(const RecBankParams& K, int panel, hipStream_t stream);
 
 // one-wave-per-problem MFMA kernel (fmpc_kernel_wave.hip)
 size_t fmpc_wave_lds_bytes(int n, int mp);
@@ -68,175 +64,6 @@ hipError_t fmpc_launch_wave_chain(const FwParams& base, const FwChainStep* steps
                                   size_t lds_bytes, hipStream_t stream);
 size_t fmpc_wave_shared_fac_doubles(int n, int nb);
 void fmpc_wave_cold_layout(int n, int mp, int* off9);
-
-hipError_t fmpc_launch_var_identify(int n, int num_train, int num_samples, int batch, const double* series, double* A1,
-                                    double* A2, int* status, hipStream_t stream);
-size_t fmpc_varfit_slot_doubles(int n, int order);
-hipError_t fmpc_launch_var_fit(int n, int order, int num_train, int num_samples, int batch, const double* series, double* A1,
-                               double* A2, int* status, double* ws, int nslots, hipStream_t stream);
-hipError_t fmpc_launch_var_validate(int n, int order, int first, int count, int num_samples, int batch, const double* series,
-                                    const double* A1, const double* A2, double* rmse, double* rrmse, hipStream_t stream);
-
-#define FMPC_LDS_LIMIT (160 * 1024)
-
-struct fmpc_handle_s {
-    int n, m, T, nb, var_order, has_xf, device;
-    int num_cu;
-    FmpcDevModel dev;            // device pointers into `pool`
-    const double* loop_M1; const double* loop_M2;   // closed-loop prediction matrices (T n) x n, row-major
-    DevBuf<double> pool_d;       // one allocation for all shared doubles
-    DevBuf<int> pool_i;          // and one for the index arrays
-    size_t lds_bytes;
-    int wg_per_cu;
-    // wave kernel (n = 27): used when available unless FMPC_FORCE_GENERIC=1
-    int use_wave = 0;
-    double* fm_forms = nullptr;  // diagnostic: where the one-step first-move kernel leaves the bounds its decision used (fmpc_debug_first_move_forms)
-    DevBuf<double> fm_compact;   // compact batch of the stopped realisations of a walk (fmpc_loop_run_walk)
-    DevBuf<int> fm_walk_i; size_t fm_walk_cap = 0;   // start / stop step per realisation of a walk
-    // affine form of the cold-start step without w (fmpc_kernel_affine.hip), built with the first-move form
-    FaParams fa_P; int fa_valid = 0, fa_disabled = 0;
-    DevBuf<int> fa_need; size_t fa_need_cap = 0;   // FMPC_STRETCH_MAX flag lists of fa_need_cap problems: one per step of a chain (a call outside a stretch: the first)
-    DevBuf<char> fw_chain;               // FMPC_STRETCH_MAX parameter blocks of the flag-mode launch behind a chain (FwParams::chain)
-    struct FmpcStretch* st_cur = nullptr;  // the open bracket of the running solve's stream (fmpc_stretch_begin), or NULL
-    std::atomic<int> st_steps{0}, st_launches{0};   // the chain launched last (fmpc_last_stretch)
-    DevBuf<double> ao_scr;               // fmpc_ao_step_device: a zero a[k] and scratch x0 / x0_pre for the loop-input kernel (3 batch n)
-    FlParams fs_P; FlStepIn fs_I; int fs_valid = 0, fs_disabled = 0, fs_min_batch = FMPC_PRODUCT_MIN_BATCH_DEFAULT;   // the fused step (fmpc_loop_step27): images in its column order, B's images
-    FlParams fl_P; int fl_valid = 0, fl_disabled = 0;   // first-move form as a product: closed-loop steps of > 64 realisations (fmpc_kernel_loopu0.hip)
-    FwModel wave;
-    DevBuf<double> wave_pool_d;
-    DevBuf<int> wave_pool_i;
-    size_t wave_lds = 0;
-    // shared cold-start factor (SURVEY §7.2a regime (ii)): Phi, Y and its Cholesky factor are the
-    // same for every problem in the first Newton step from the mid-box start; it depends only on the
-    // model and on k, so it is computed once per (handle, k) and kept in HBM (L2-resident, 0.5 MB).
-    DevBuf<double> sh_fac, sh_rs; DevBuf<int> sh_ok; DevBuf<double> sh_scratch;
-    double sh_k = 0.0; int sh_valid = 0, sh_enabled = 0;
-    DevBuf<double> cold_d;               // cold-start constants on the device (FwCold layout)
-    // panel kernel (fmpc_kernel_panel.hip): the cold-start step on 16-problem panels, n_newton = 1
-    int pn_enabled = 0, pn_valid = 0, pn_mp = 0;
-    int last_path = 0;
-    size_t pn_lds = 0;
-    DevBuf<double> pn_pool;              // [simg | btimg | aimg | vec | ucon]
-    size_t pn_o_simg, pn_o_limg, pn_o_bt, pn_o_aimg, pn_o_vec, pn_o_ucon, pn_o_dump, pn_doubles;
-    DevBuf<int> pn_cnt;                  // problems the exact path had to solve in the last call (diagnostic)
-    DevBuf<int> gn_list; DevBuf<double> gn_nu; DevBuf<int> gn_cnt; PinnedBuf<int> gn_cnt_host; size_t gn_cap = 0;   // explicit-start batches with a budget > 1: first step / continuation split
-    int gn_split = 1;                                                                                           // (FMPC_NO_GENERAL_SPLIT=1: one launch)
-    DevBuf<int> fa_nflag;                // affine form: [running count of flagged problems | the count the last exact-path launch dealt with | its
-                                         // ticket]: the exact-path launch leaves at once while the two counts agree (FwParams::nflag)
-    size_t pn_cap = 0;                   // per-batch buffers of the panel path, grown together
-    DevBuf<double> pn_gate, pn_epsp, pn_nuws;
-    DevBuf<double> pn_rnp; DevBuf<int> pn_list;   // budgets > 1: next-exit-test partials, compacted list of the problems that go on
-    PinnedBuf<int> pn_cnt_host;          // pinned copy of pn_cnt of an EARLIER call (never waited for): sizes the continuation grid
-    size_t pn_o_dz; int pn_dz_len;
-    size_t pn_dz_lds = 0;
-    double pn_rd2_0 = 0.0, pn_rp2c = 0.0;
-    // dense form of the cold-start dual solve (fmpc_kernel_inv.hip): nu+ = nuc + J d, built per (handle, k) on first use
-    int inv_enabled = 0, inv_valid = 0, inv_jks = 0, inv_max_batch = 768, inv_last = 0; double inv_k = 0.0;
-    int inv_failed = 0; double inv_failed_k = 0.0;               // the build for this k gave a non-finite J: not retried
-    DevBuf<double> inv_jimg, inv_nuc, inv_eimg;
-    DevBuf<double> inv_jst, inv_nucst; int inv_fuse = 0;         // per-stage rows of J_x and nuc: the dual solve fused into d_z (w = NULL, no xf, budget 1)
-    DevBuf<double> inv_jimg2; int inv_jks2 = 0;  // J' = [J_x | -J_w M1 | -J_w M2]: closed-loop steps, w = -M1 B u1 - M2 B u2 (fmpc_loop_step_device)
-    DevBuf<double> lp_v; int lp_hint = 0;                        // [B u1 ; B u2] per problem of the running loop step
-    // first-move form of the closed-loop step (fmpc_kernel_first.hip): host copies of J (columns [x0 | x0_pre | B u1 | B u2]) and
-    // nuc kept by fmpc_build_inverse, the derived matrices on the device per (handle, k), a flag per realisation
-    std::vector<double> hm_J4, hm_nuc; double hm_J4_k = 0.0; int hm_J4_valid = 0;
-    DevBuf<double> fm_pool; int fm_valid = 0, fm_disabled = 0; double fm_k = 0.0; FmParams fm_P; DevBuf<int> fm_need;
-    std::vector<double> hm_m1, hm_m2;
-    std::vector<double> hm_Q2, hm_Qf2, hm_ql, hm_qfl, hm_xf, hm_blocks;
-    std::vector<int> hm_idxD, hm_idx1, hm_idx2;
-    DevBuf<int> pn_sched; int pn_nsf = 0, pn_nsb = 0, pn_limg_cap = 0;
-    std::vector<double> hm_R2, hm_rl, hm_umin, hm_umax, hm_umid, hm_xmid, hm_bt, hm_a1, hm_a2;   // host copies
-    // tiled kernel (fmpc_kernel_tiled.hip): workgroup per problem, any n <= 79; images per arithmetic type, built on first use
-    int generic_ok;                      // the generic kernel's LDS tiles fit (n <= 64), or generic_big
-    int prefer_tiled;                    // the fp64 tiled kernel exists for this size: it is 1.3 (n = 4) to 9 (n = 45) times faster than the
-                                         // generic kernel at every batch size (round 5 measurement): the default; FMPC_FORCE_GENERIC=1: generic
-    int generic_big;                     // sizes no other kernel takes (n > 79 ...), diagonal weights: the generic kernel with its tiles in the workspace
-    int prec = FMPC_PREC_F64;            // FMPC_PREC_F64 / FMPC_PREC_F32_MIXED of the per-problem-factor path
-    int refine = 0;                      // fmpc_set_refinement: sweeps of iterative refinement per Newton step of the fp32 factor
-    int refine_last = 0;                 // ... of the last launch with the fp32 factor (fmpc_last_refinement)
-    int force_tiled = 0;                 // FMPC_TILED=1: route every solve through the tiled kernel (tests, profiles)
-    struct Tiled { int ready = 0, NB = 0, NW = 0; size_t lds = 0; DevBuf<char> pool; DevBuf<int> ipool; DevBuf<double> bm; FtModel V; } tl[2];   // bm: padded fp64 images   // [0] fp64, [1] fp32
-    // model bank (fmpc_bank_set_device): per model the plain and padded images of A1, A2 and the constant Y tiles; one block table
-    // for all models, built from the handle alone and uploaded once
-    struct Bank {
-        int count = 0, t = 0, nblk = 0, table_ready = 0, prepared[2] = {0, 0};
-        size_t plain_stride = 0, pad_stride = 0, yimg_stride = 0;    // doubles, doubles, elements of the factor's type
-        DevBuf<double> plain, pad; DevBuf<char> yimg; DevBuf<int> ipool;   // ipool: [desc | iD | i1 | i2]
-    } bank;
-    // stored cold-start factor per model of the bank (fmpc_bank_prefactor_device): the factor stream of Y_j at the mid-box start for
-    // barrier weight k, count * stride elements of the bank's arithmetic; flag[j] != 0: model j has none
-    struct BankFactor {
-        int valid = 0, count = 0, t = 0, prepared[2] = {0, 0};
-        double k = 0.0; size_t stride = 0;
-        DevBuf<char> fac; DevBuf<int> flag;
-    } bkf;
-    int bank_last_stored = 0;             // the last bank solve was handed the stored factors (fmpc_last_bank_stored_factor)
-    // per-model first-move form of the bank (fmpc_bank_first_move_device): count * stride doubles of operands, its own memory
-    struct BankFirst {
-        int valid = 0, count = 0, disabled = 0, prepared = 0;
-        double k = 0.0, cst_k = 0.0; int cst_valid = 0; size_t stride = 0, oK = 0, ou = 0, oE = 0, oe = 0, oEp = 0, oep = 0, od = 0, osc = 0;
-        DevBuf<double> ops, scratch, cst; DevBuf<int> flag, need, list, cnt;
-    } bfm;
-    int bank_last_first = 0;              // the last bank loop step took the form (fmpc_last_bank_first_move)
-    int bank_first_dispatch = 0;          // the last TILED dispatch was that form's: fmpc_last_dispatch reports its hand-over count
-    DevBuf<double> tl_ws; int tl_prepared = 0;                   // (bit NW: that wavefront count of the fp64 instance is prepared)
-    int tl_last_nw = 0;                   // wavefronts per problem of the last tiled launch (diagnostic)
-    int z_ld = 0;                         // fmpc_set_z_ld: doubles between the z rows of consecutive problems (0: T (n + m))
-    int small_tiled = 1;                  // per-problem-factor solves of few problems go to the tiled kernel (FMPC_NO_SMALL_TILED=1: off)
-    int small_nw = 4;                     // ... with this many wavefronts per problem: 4, the default (round 5), or 2 (FMPC_SMALL_TILED_NW=2 /
-                                          // fmpc_set_small_batch_kernel(h, 2))
-    std::vector<double> hm_b;            // B row-major n x m
-    std::vector<double> hm_a1f, hm_a2f;  // A1, A2 row-major (always kept: the tiled kernel's images)
-    int denseQ;                          // Q or Qf not diagonal: tiled kernel only
-    int denseR;                          // R not diagonal: tiled kernel, fp64
-    std::vector<double> hm_r2full;       // 2R, m x m row-major
-    std::vector<double> hm_q2m, hm_qf2m, hm_xm, hm_xfm;   // 2Q, 2Qf, (2Q)^-1, (2Qf)^-1 row-major
-    // ramp-rate rows (VAR_1): bounds on the device, own workspace (dense Y per workgroup)
-    DevBuf<double> ramp_du;      // [du_min | du_max], 2 m doubles; empty until fmpc_set_ramp
-    DevBuf<double> ramp_ws;
-    // fmpc_newton_ramp (and the cold-start form) take the handle: n <= 64, their LDS fits, diagonal weights (fmpc_set_ramp);
-    // every other ramp solve, and every one after fmpc_set_ramp_workspace(h, 1), runs fmpc_newton_ramp_ws
-    int ramp_lds_ok = 0, ramp_force_ws = 0;
-    // cold-start step with the ramp rows in its Woodbury form (fmpc_ramp_cold): constants per (handle, k, ramp bounds)
-    std::vector<double> hm_dumin, hm_dumax;
-    int rc_disabled = 0, rc_valid = 0, rc_failed = 0, rc_last = 0; double rc_k = 0.0, rc_failed_k = 0.0;
-    DevBuf<double> rc_pool; FrColdParams rc_P;
-    DevBuf<double> rc_ws;
-    DevBuf<double> rc_nu; DevBuf<int> rc_si; size_t rc_cap = 0;   // nu / status / iters of the first step when the caller passes none (budgets > 1)
-    // A handle's device workspaces serve ONE solve at a time.  Solves enqueued on different streams are ordered on
-    // the device: every solve records `ev`, and a solve on another stream than the last one waits for it first.
-    hipEvent_t ev = nullptr; std::atomic<int> ev_valid{0}; std::atomic<hipStream_t> last_stream{nullptr};   // (atomic: a chain of this handle may be
-                                         // launched by a call on ANOTHER handle of the same bracketed stream, which does not hold mu)
-    // workspace, grown on demand; `mu` serialises the host-side enqueue (a handle may be shared between threads)
-    std::mutex mu;
-    std::mutex host_mu;          // serialises the host-pointer entry points (shared staging)
-    DevBuf<double> ws;
-    // z_out == NULL (first moves only): the working iterate of the problems a kernel has to iterate on lives here
-    DevBuf<double> zs;
-    // closed-loop records (fmpc_loop_records_device): Q, Qf, R as the records kernel of this handle reads them, uploaded on first use
-    // (rec_panel: the padded diagonals of the panel kernel; else dense), and the per-stage partial costs of the last call
-    DevBuf<double> rec_w; int rec_ready = 0, rec_panel = 0; size_t rec_oQf = 0, rec_oR = 0;
-    DevBuf<double> rec_j;
-    DevBuf<double> rec_f;                 // the bank's records (fmpc_loop_records_bank_device): f_i of the last call, stages x n per problem
-    DevBuf<double> kkt_part;              // KKT report (fmpc_kkt_report_device): per-(stage, problem) partials of the panel kernel's last call
-    // staging for the host-pointer entry points
-    DevBuf<char> stage;
-    PinnedBuf<char> pin; void* pin_dev = nullptr;   // pinned host twin of the staging block for small host-pointer solves (fmpc_solve_host)
-
-    ~fmpc_handle_s() { if (ev) (void)hipEventDestroy(ev); }
-};
-
-// The arguments of one device solve, as fmpc_solve_device_inner and the path it picks read them
-struct FmpcSolve {
-    int batch;
-    const double* x0; const double* x0_pre; const double* w; const double* z_init; const double* nu0;
-    int n_newton; double k;
-    double* z_out; double* nu_out; int* status; int* iters; double* step;
-    double* u0_out;                      // the first moves, or NULL
-    hipStream_t stream;
-    int ldz;                             // doubles between the z rows of consecutive problems (0: contiguous; -1: the handle's fmpc_set_z_ld value)
-};
-static inline int fmpc_max_iter(const FmpcSolve& s) { return s.n_newton > 0 ? s.n_newton : 1000; }
 
 extern "C" int fmpc_version(void) { return FMPC_VERSION; }
 
@@ -258,65 +85,6 @@ extern "C" const char* fmpc_strerror(int code) {
 
 extern "C" int fmpc_step_ld(int n_newton) { return n_newton > 0 ? n_newton : 1000; }
 
-namespace {
-
-// column-major (MATLAB) element
-inline double cm(const double* M, int rows, int r, int c) { return M[(size_t)r + (size_t)c * rows]; }
-
-bool is_diag(const double* M, int n) {
-    for (int c = 0; c < n; ++c)
-        for (int r = 0; r < n; ++r)
-            if (r != c && cm(M, n, r, c) != 0.0) return false;
-    return true;
-}
-
-// out (row-major n x n) += A diag(x) B'   with A, B row-major n x n
-void add_AxBt(std::vector<double>& out, const std::vector<double>& A, const std::vector<double>& x,
-              const std::vector<double>& B, int n, double sign) {
-    for (int a = 0; a < n; ++a)
-        for (int b = 0; b < n; ++b) {
-            double t = 0.0;
-            for (int c = 0; c < n; ++c) t += A[a * n + c] * x[c] * B[b * n + c];
-            out[a * n + b] += sign * t;
-        }
-}
-
-// inverse of a symmetric positive definite matrix (row-major n x n) by Cholesky in extended precision; false: not PD
-bool spd_inverse(const std::vector<double>& A, int n, std::vector<double>& inv) {
-    typedef long double ld;
-    std::vector<ld> L((size_t)n * n, 0.0L), Li((size_t)n * n, 0.0L);
-    for (int c = 0; c < n; ++c) {
-        ld d = A[c * n + c];
-        for (int k = 0; k < c; ++k) d -= L[c * n + k] * L[c * n + k];
-        if (!(d > 0.0L)) return false;
-        const ld l = sqrtl(d);
-        L[c * n + c] = l;
-        for (int r = c + 1; r < n; ++r) {
-            ld t = A[r * n + c];
-            for (int k = 0; k < c; ++k) t -= L[r * n + k] * L[c * n + k];
-            L[r * n + c] = t / l;
-        }
-    }
-    for (int c = 0; c < n; ++c) {                    // Li = L^-1
-        Li[c * n + c] = 1.0L / L[c * n + c];
-        for (int r = c + 1; r < n; ++r) {
-            ld t = 0.0L;
-            for (int k = c; k < r; ++k) t += L[r * n + k] * Li[k * n + c];
-            Li[r * n + c] = -t / L[r * n + r];
-        }
-    }
-    inv.assign((size_t)n * n, 0.0);
-    for (int a = 0; a < n; ++a)
-        for (int b = 0; b <= a; ++b) {
-            ld t = 0.0L;
-            for (int k = a; k < n; ++k) t += Li[k * n + a] * Li[k * n + b];
-            inv[a * n + b] = inv[b * n + a] = (double)t;
-        }
-    return true;
-}
-
-}  // namespace
-
 extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
                            const double* A1, const double* A2, const double* B,
                            const double* Q, const double* R, const double* Qf,
@@ -332,28 +100,28 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
     if (device < 0) return FMPC_E_NO_DEVICE;
     // dense (symmetric positive definite) R: fast_mpc_objective.m:51-54 takes any square R.  Handled by the tiled kernel in
     // fp64 (a per-stage m x m factorisation in LDS): n <= 47 and m (m + 1) / 2 + m (n + 2) doubles of LDS.
-    const bool denseR = !is_diag(R, m);
+    const bool denseR = !fmpc_host_is_diag(R, m);
     // dense (symmetric positive definite) Q, Qf: fast_mpc_objective.m:52-55 takes any square Q, Qf.  Handled by the
     // tiled kernel only (the other kernels keep the state weights as diagonals).
-    const bool denseQ = !is_diag(Q, n) || !is_diag(Qf, n);
+    const bool denseQ = !fmpc_host_is_diag(Q, n) || !fmpc_host_is_diag(Qf, n);
     for (int i = 0; i < n; ++i)
-        if (!(cm(Q, n, i, i) > 0.0) || !(cm(Qf, n, i, i) > 0.0)) return FMPC_E_NOT_PD_PHI;
+        if (!(fmpc_host_cm(Q, n, i, i) > 0.0) || !(fmpc_host_cm(Qf, n, i, i) > 0.0)) return FMPC_E_NOT_PD_PHI;
     for (int i = 0; i < m; ++i)
-        if (!(cm(R, m, i, i) > 0.0)) return FMPC_E_NOT_PD_PHI;
+        if (!(fmpc_host_cm(R, m, i, i) > 0.0)) return FMPC_E_NOT_PD_PHI;
     if (denseQ)
         for (int a = 0; a < n; ++a)
             for (int b = 0; b < a; ++b)
-                if (cm(Q, n, a, b) != cm(Q, n, b, a) || cm(Qf, n, a, b) != cm(Qf, n, b, a)) return FMPC_E_NOT_PD_PHI;
+                if (fmpc_host_cm(Q, n, a, b) != fmpc_host_cm(Q, n, b, a) || fmpc_host_cm(Qf, n, a, b) != fmpc_host_cm(Qf, n, b, a)) return FMPC_E_NOT_PD_PHI;
     std::vector<double> R2full;
     if (denseR) {
         R2full.assign((size_t)m * m, 0.0);
         for (int a = 0; a < m; ++a)
             for (int b = 0; b < m; ++b) {
-                if (cm(R, m, a, b) != cm(R, m, b, a)) return FMPC_E_NOT_PD_PHI;
-                R2full[(size_t)a * m + b] = 2.0 * cm(R, m, a, b);
+                if (fmpc_host_cm(R, m, a, b) != fmpc_host_cm(R, m, b, a)) return FMPC_E_NOT_PD_PHI;
+                R2full[(size_t)a * m + b] = 2.0 * fmpc_host_cm(R, m, a, b);
             }
         std::vector<double> tmp;
-        if (!spd_inverse(R2full, m, tmp)) return FMPC_E_NOT_PD_PHI;      // (the inverse itself is not used: a positive definiteness test)
+        if (!fmpc_host_spd_inverse(R2full, m, tmp)) return FMPC_E_NOT_PD_PHI;      // (the inverse itself is not used: a positive definiteness test)
     }
     // per-problem-factor paths: the generic kernel (n <= 64 and its tiles fit the LDS), else the tiled kernel in fp64
     // (n <= 47), else the tiled kernel with an fp32 factor (n <= 79: "fp32 mixed precision", BASELINE configs[4])
@@ -417,24 +185,24 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
     std::vector<double> a1(nn), a2(nn, 0.0), a1t(nn), a2t(nn, 0.0), bt((size_t)m * n);
     for (int rr = 0; rr < n; ++rr)
         for (int c = 0; c < n; ++c) {
-            a1[rr * n + c] = cm(A1, n, rr, c);
+            a1[rr * n + c] = fmpc_host_cm(A1, n, rr, c);
             a1t[c * n + rr] = a1[rr * n + c];
             if (var2) {
-                a2[rr * n + c] = cm(A2, n, rr, c);
+                a2[rr * n + c] = fmpc_host_cm(A2, n, rr, c);
                 a2t[c * n + rr] = a2[rr * n + c];
             }
         }
     for (int rr = 0; rr < n; ++rr)
-        for (int c = 0; c < m; ++c) bt[(size_t)c * n + rr] = cm(B, n, rr, c);
+        for (int c = 0; c < m; ++c) bt[(size_t)c * n + rr] = fmpc_host_cm(B, n, rr, c);
     std::vector<double> R2(m), Q2(n), Qf2(n);
-    for (int i = 0; i < m; ++i) R2[i] = 2.0 * cm(R, m, i, i);
-    for (int i = 0; i < n; ++i) { Q2[i] = 2.0 * cm(Q, n, i, i); Qf2[i] = 2.0 * cm(Qf, n, i, i); }
+    for (int i = 0; i < m; ++i) R2[i] = 2.0 * fmpc_host_cm(R, m, i, i);
+    for (int i = 0; i < n; ++i) { Q2[i] = 2.0 * fmpc_host_cm(Q, n, i, i); Qf2[i] = 2.0 * fmpc_host_cm(Qf, n, i, i); }
     // X = (2Q)^-1, Xf = (2Qf)^-1 as dense row-major matrices (diagonal weights: diagonal matrices)
     std::vector<double> Q2m(nn, 0.0), Qf2m(nn, 0.0), X(nn, 0.0), Xf(nn, 0.0);
     for (int a = 0; a < n; ++a)
-        for (int b = 0; b < n; ++b) { Q2m[a * n + b] = 2.0 * cm(Q, n, a, b); Qf2m[a * n + b] = 2.0 * cm(Qf, n, a, b); }
+        for (int b = 0; b < n; ++b) { Q2m[a * n + b] = 2.0 * fmpc_host_cm(Q, n, a, b); Qf2m[a * n + b] = 2.0 * fmpc_host_cm(Qf, n, a, b); }
     if (denseQ) {
-        if (!spd_inverse(Q2m, n, X) || !spd_inverse(Qf2m, n, Xf)) { delete h; return FMPC_E_NOT_PD_PHI; }
+        if (!fmpc_host_spd_inverse(Q2m, n, X) || !fmpc_host_spd_inverse(Qf2m, n, Xf)) { delete h; return FMPC_E_NOT_PD_PHI; }
     } else {
         for (int i = 0; i < n; ++i) { X[i * n + i] = 1.0 / Q2[i]; Xf[i * n + i] = 1.0 / Qf2[i]; }
     }
@@ -536,7 +304,7 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
     h->denseQ = denseQ ? 1 : 0; h->hm_q2m = Q2m; h->hm_qf2m = Qf2m; h->hm_xm = X; h->hm_xfm = Xf;
     h->hm_b.resize((size_t)n * m);
     for (int rr = 0; rr < n; ++rr)
-        for (int c = 0; c < m; ++c) h->hm_b[(size_t)rr * m + c] = cm(B, n, rr, c);
+        for (int c = 0; c < m; ++c) h->hm_b[(size_t)rr * m + c] = fmpc_host_cm(B, n, rr, c);
 
     // ---- wave kernel: MFMA-layout images of the constant blocks (+ a zero block), padded B'
     const char* force = getenv("FMPC_FORCE_GENERIC");
@@ -791,23 +559,24 @@ static int fmpc_tiled_build(fmpc_handle h, int t, hipStream_t stream) {
     return FMPC_OK;
 }
 
+// ... if they are not ready (fmpc_handle.h)
+int fmpc_tiled_ensure(fmpc_handle h, int t, hipStream_t stream) {
+    if (h->tl[t].ready) return FMPC_OK;
+    return t ? fmpc_tiled_build<float>(h, 1, stream) : fmpc_tiled_build<double>(h, 0, stream);
+}
+
 // launches the tiled kernel; caller holds h->mu
 // nw_override: wavefronts per problem other than the handle's default (2 or 4, fp64 without dense R): few problems per CU
 // are solved faster by more wavefronts each (the latency of a problem is what counts then)
-static bool fmpc_capturing(hipStream_t stream);
 __global__ void fmpc_zero_ints(int* p, int n) { if ((int)threadIdx.x < n) p[threadIdx.x] = 0; }
-struct FmpcTiledPlan { int NWu; size_t ldsu; int grid; size_t slot; };
 // Everything a tiled launch needs BEFORE anything is enqueued: the instance is built and prepared, the launch is sized and its
 // workspace exists.  A caller that enqueues another launch first (the first-step / continuation split) plans first and falls
 // back when this fails, so a failure never leaves a half-finished solve.  While `stream` is being captured into a
 // graph nothing is allocated or released (that would end the capture): grid_hint is ignored and the launch is clamped to the
 // slots the workspace already has -- the kernel walks its problems with a workgroup stride, any grid is correct.
-static int fmpc_tiled_plan(fmpc_handle h, int t, int batch, hipStream_t stream, int nw_override, int grid_hint, FmpcTiledPlan* out) {
+int fmpc_tiled_plan(fmpc_handle h, int t, int batch, hipStream_t stream, int nw_override, int grid_hint, FmpcTiledPlan* out) {
     fmpc_handle_s::Tiled& X = h->tl[t];
-    if (!X.ready) {
-        const int rc = t ? fmpc_tiled_build<float>(h, 1, stream) : fmpc_tiled_build<double>(h, 0, stream);
-        if (rc != FMPC_OK) return rc;
-    }
+    { const int rc = fmpc_tiled_ensure(h, t, stream); if (rc != FMPC_OK) return rc; }
     int NWu = X.NW; size_t ldsu = X.lds;
     if (nw_override && nw_override != X.NW && !t && !h->denseR) {
         NWu = nw_override;
@@ -920,7 +689,7 @@ static int fmpc_ensure_ws(fmpc_handle h, int grid, size_t* stride, hipStream_t s
 // (Under stream capture -- the solves of a recorded stretch going into a HIP graph, RecordedSolves in handle.py -- the handle's
 // event is left alone: an event recorded inside a capture cannot be waited for by a stream outside it, and the order of a
 // replay against other work is the order of the stream it is replayed on.)
-static bool fmpc_capturing(hipStream_t stream) {            // (declared above fmpc_tiled_plan)
+bool fmpc_capturing(hipStream_t stream) {                   // (declared in fmpc_handle.h)
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     return hipStreamIsCapturing(stream, &st) == hipSuccess && st == hipStreamCaptureStatusActive;
 }
@@ -1146,7 +915,7 @@ static int fmpc_guard_begin_queued(fmpc_handle h, hipStream_t stream) {
     if (h->ev_valid && stream != h->last_stream && hipStreamWaitEvent(stream, h->ev, 0) != hipSuccess) return FMPC_E_HIP;
     return FMPC_OK;
 }
-static int fmpc_guard_begin(fmpc_handle h, hipStream_t stream) {
+int fmpc_guard_begin(fmpc_handle h, hipStream_t stream) {
     const int rcs = fmpc_stretch_flush_stream(stream, h);       // inside a stretch bracket: the pending chain comes first
     if (rcs != FMPC_OK) return rcs;
     if (fmpc_capturing(stream)) return FMPC_OK;
@@ -1154,7 +923,7 @@ static int fmpc_guard_begin(fmpc_handle h, hipStream_t stream) {
     if (h->ev_valid && stream != h->last_stream && hipStreamWaitEvent(stream, h->ev, 0) != hipSuccess) return FMPC_E_HIP;
     return FMPC_OK;
 }
-static void fmpc_guard_end(fmpc_handle h, hipStream_t stream) {
+void fmpc_guard_end(fmpc_handle h, hipStream_t stream) {
     if (fmpc_capturing(stream)) return;
     if (h->ev && hipEventRecord(h->ev, stream) == hipSuccess) { h->ev_valid = 1; h->last_stream = stream; }
 }
@@ -1181,7 +950,7 @@ static void fmpc_panel_params(fmpc_handle h, double k, FpParams& Q) {
 static int fmpc_build_inverse(fmpc_handle h, double k, hipStream_t stream) {
     const int n = h->n, T = h->T, nb = h->nb, TN = T * n, nrow = nb * n;
     const int ncol = 2 * n + TN, np = 1 + ncol + 2 * n, npanels = (np + FP_NP - 1) / FP_NP;      // + w = -M1 e_j, -M2 e_j
-    const double scale = 1048576.0;
+    const double scale = FMPC_INV_SCALE;
     h->inv_valid = 0;
     std::vector<double> hx0((size_t)np * n, 0.0), hx0p((size_t)np * n, 0.0), hw((size_t)np * TN, 0.0);
     for (int j = 0; j < n; ++j) { hx0[(size_t)(1 + j) * n + j] = scale; hx0p[(size_t)(1 + n + j) * n + j] = scale; }
@@ -1213,90 +982,22 @@ static int fmpc_build_inverse(fmpc_handle h, double k, hipStream_t stream) {
     }
     d.release();
     if (rc != FMPC_OK) return rc;
-    auto at = [&](int p, int row) { return nu[((size_t)(p / FP_NP) * nrow + row) * FP_NP + (p % FP_NP)]; };
-    const int nrt = (nrow + 15) / 16, jks = h->inv_jks, jksp = 16 * ((jks + 15) / 16 + 3);
-    std::vector<double> img((size_t)nrt * jksp * 64, 0.0), nuc((size_t)nrt * 16, 0.0);
-    for (int r = 0; r < nrow; ++r) {
-        nuc[r] = at(0, r);
-        if (!std::isfinite(nuc[r])) return FMPC_OK;                  // the panel path reports what is wrong; this form stays off
-    }
-    const bool var2 = h->var_order == 2;
-    for (int rt = 0; rt < nrt; ++rt)
-        for (int ks = 0; ks < jks; ++ks)
-            for (int l = 0; l < 64; ++l) {
-                const int row = 16 * rt + (l & 15), kk = 4 * ks + (l >> 4);
-                int col = -1;                                        // column of d -> index of the unit-vector problem
-                if (kk < n) col = kk;
-                else if (kk < 2 * n) col = var2 ? kk : -1;           // VAR(1): x0_pre does not enter
-                else if (kk >= 4 * FP_XKS && kk - 4 * FP_XKS < TN) col = 2 * n + (kk - 4 * FP_XKS);
-                if (row < nrow && col >= 0) {
-                    const double v = (at(1 + col, row) - nuc[row]) / scale;
-                    if (!std::isfinite(v)) return FMPC_OK;
-                    img[((size_t)rt * jksp + ks) * 64 + l] = v;
-                }
-            }
-    // per stage: the rows of J_x as two 16-row A tiles (rows beyond n: zero) and nuc padded to 32 (d_z with the dual solve fused in)
-    {
-        std::vector<double> jst((size_t)nb * 2 * FP_XKS * 64, 0.0), ncs((size_t)nb * 32, 0.0);
-        for (int st = 0; st < nb; ++st) {
-            for (int r = 0; r < n; ++r) ncs[(size_t)st * 32 + r] = nuc[(size_t)st * n + r];
-            for (int I = 0; I < 2; ++I)
-                for (int ks = 0; ks < FP_XKS; ++ks)
-                    for (int l = 0; l < 64; ++l) {
-                        const int rl = 16 * I + (l & 15), kk = 4 * ks + (l >> 4);
-                        if (rl >= n) continue;
-                        const int row = st * n + rl;
-                        jst[(((size_t)st * 2 + I) * FP_XKS + ks) * 64 + l] = img[((size_t)(row >> 4) * jksp + ks) * 64 + ((kk & 3) << 4) + (row & 15)];
-                    }
-        }
-        if (hipMemcpy(h->inv_jst, jst.data(), jst.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(h->inv_nucst, ncs.data(), ncs.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return FMPC_E_HIP;
-    }
-    // J' = [J_x | d nu+ / d (B u1) | d nu+ / d (B u2)]
-    const int jks2 = h->inv_jks2, jksp2 = 16 * ((jks2 + 15) / 16 + 3);
-    std::vector<double> img2((size_t)nrt * jksp2 * 64, 0.0);
-    for (int rt = 0; rt < nrt; ++rt)
-        for (int ks = 0; ks < jks2; ++ks)
-            for (int l = 0; l < 64; ++l) {
-                const int row = 16 * rt + (l & 15), kk = 4 * ks + (l >> 4);
-                if (ks < FP_XKS) { img2[((size_t)rt * jksp2 + ks) * 64 + l] = img[((size_t)rt * jksp + ks) * 64 + l]; continue; }
-                const int c = kk - 4 * FP_XKS;
-                if (row < nrow && c < 2 * n) {
-                    const double v = (at(1 + ncol + c, row) - nuc[row]) / scale;
-                    if (!std::isfinite(v)) return FMPC_OK;
-                    img2[((size_t)rt * jksp2 + ks) * 64 + l] = v;
-                }
-            }
+    // the operand images of J, J', E, the per-stage rows and the host copy for the first-move form (fmpc_host_inverse_images), uploaded
+    // in this order.  A value that is not finite leaves this form off (the panel path reports what is wrong); one found as late as in
+    // J' is found after the per-stage images have gone up.
+    std::vector<double> img, nuc, jst, ncs, img2, eimg, J4, nuc4;
+    const bool finite = fmpc_host_inverse_images(n, T, nb, h->var_order == 2, h->inv_jks, h->inv_jks2, h->hm_a1.data(), h->hm_a2.data(), nu,
+                                                 img, nuc, jst, ncs, img2, eimg, J4, nuc4);
+    if (!jst.empty() &&
+        (hipMemcpy(h->inv_jst, jst.data(), jst.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+         hipMemcpy(h->inv_nucst, ncs.data(), ncs.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)) return FMPC_E_HIP;
+    if (!finite) return FMPC_OK;
     if (hipMemcpy(h->inv_jimg2, img2.data(), img2.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return FMPC_E_HIP;
-    // E = [A1 A2 ; A2 0] (fast_mpc_eq_const.m:39-44), rows 0..53, columns [x0 ; x0_pre]
-    std::vector<double> eimg((size_t)4 * FP_XKS * 64, 0.0);
-    for (int I = 0; I < 4; ++I)
-        for (int ks = 0; ks < FP_XKS; ++ks)
-            for (int l = 0; l < 64; ++l) {
-                const int row = 16 * I + (l & 15), kk = 4 * ks + (l >> 4);
-                double v = 0.0;
-                if (row < n && kk < n) v = h->hm_a1[row * n + kk];
-                else if (row < n && kk < 2 * n) v = var2 ? h->hm_a2[row * n + kk - n] : 0.0;
-                else if (row < 2 * n && kk < n) v = var2 ? h->hm_a2[(row - n) * n + kk] : 0.0;
-                eimg[((size_t)I * FP_XKS + ks) * 64 + l] = v;
-            }
     if (hipMemcpy(h->inv_eimg, eimg.data(), eimg.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->inv_jimg, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->inv_nuc, nuc.data(), nuc.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return FMPC_E_HIP;
-    // host copy for the first-move form: J with the columns [x0 | x0_pre | B u1 | B u2], nuc
-    {
-        const int nc = 4 * n;
-        h->hm_J4.assign((size_t)nrow * nc, 0.0); h->hm_nuc.assign(nuc.begin(), nuc.begin() + nrow);
-        for (int r = 0; r < nrow; ++r)
-            for (int c = 0; c < nc; ++c) {
-                int pidx = -1;
-                if (c < n) pidx = 1 + c;
-                else if (c < 2 * n) pidx = var2 ? 1 + c : -1;
-                else pidx = 1 + ncol + (c - 2 * n);
-                if (pidx >= 0) h->hm_J4[(size_t)r * nc + c] = (at(pidx, r) - nuc[r]) / scale;
-            }
-        h->hm_J4_valid = 1; h->hm_J4_k = k; h->fm_valid = 0;
-    }
+    h->hm_J4.swap(J4); h->hm_nuc.swap(nuc4);
+    h->hm_J4_valid = 1; h->hm_J4_k = k; h->fm_valid = 0;
     h->inv_valid = 1; h->inv_k = k;
     return FMPC_OK;
 }
@@ -1471,7 +1172,7 @@ static int fmpc_ensure_cold(fmpc_handle h, double k, size_t stride, hipStream_t 
 }
 
 // z_out == NULL (first moves only): the kernels that iterate on z work in the handle's scratch iterate
-static int fmpc_scratch_z(fmpc_handle h, int batch, hipStream_t stream) {
+int fmpc_scratch_z(fmpc_handle h, int batch, hipStream_t stream) {
     return h->zs.grow((size_t)batch * h->T * (h->n + h->m), stream);
 }
 
@@ -1844,513 +1545,6 @@ static int fmpc_solve_device_impl(fmpc_handle h, FmpcSolve s) {
     if (!(S && S->nsteps && S->h == h)) fmpc_guard_end(h, s.stream);      // (a queued step: the chain's launch records the event)
     else if (!fmpc_capturing(s.stream)) h->last_stream = s.stream;
     return rc;
-}
-
-// ---- model bank (include/fastmpc.h; fmpc_bank.h, fmpc_kernel_bank.hip)
-static int fmpc_bank_unsupported(fmpc_handle h, int t) {
-    if (h->ramp_du.p) return 1;                                        // ramp-rate rows: their kernels have no bank form
-    return fmpc_tiled_supports(h->n, h->m, h->nb, t, nullptr, nullptr, h->denseR) ? 0 : 1;
-}
-extern "C" int fmpc_bank_set_device(fmpc_handle h, int count, const double* A1, const double* A2, void* stream_) {
-    if (!h || !A1) return FMPC_E_NULL;
-    if (h->var_order == 2 && !A2) return FMPC_E_NULL;
-    if (count <= 0) return FMPC_E_DIM;
-    hipStream_t stream = (hipStream_t)stream_;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lk(h->mu);
-    const int t = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
-    if (fmpc_bank_unsupported(h, t)) return FMPC_E_UNSUPPORTED;
-    fmpc_handle_s::Tiled& X = h->tl[t];
-    fmpc_handle_s::Bank& B = h->bank;
-    const bool capturing = fmpc_capturing(stream);
-    if (!X.ready) {
-        if (capturing) return FMPC_E_ALLOC;
-        const int rc = t ? fmpc_tiled_build<float>(h, 1, stream) : fmpc_tiled_build<double>(h, 0, stream);
-        if (rc != FMPC_OK) return rc;
-    }
-    const int n = h->n, nb = h->nb, NB = X.NB, NP = 16 * NB, NQ = NB * NB;
-    if (!B.table_ready) {
-        if (capturing) return FMPC_E_ALLOC;
-        FmpcBankTable tab;
-        const bool xf_is_x = h->hm_xm.size() == h->hm_xfm.size() &&
-                             memcmp(h->hm_xm.data(), h->hm_xfm.data(), h->hm_xm.size() * sizeof(double)) == 0;
-        fmpc_host_bank_table(h->T, h->var_order == 2, h->has_xf != 0, xf_is_x, tab);
-        const int nblk = (int)tab.blocks.size();
-        std::vector<int> ids((size_t)nblk * FB_DESC_INTS, 0);
-        for (int k = 0; k < nblk; ++k) {
-            int* d = ids.data() + (size_t)k * FB_DESC_INTS;
-            d[0] = tab.blocks[k].nterms;
-            for (int q = 0; q < tab.blocks[k].nterms; ++q) {
-                const FmpcBankTerm& tm = tab.blocks[k].t[q];
-                d[1 + 4 * q] = tm.sign; d[2 + 4 * q] = tm.L; d[3 + 4 * q] = tm.X; d[4 + 4 * q] = tm.R;
-            }
-        }
-        for (int i = 0; i < nb; ++i) ids.push_back(tab.idxD[i]);
-        for (int i = 0; i < nb; ++i) ids.push_back(tab.idx1[i] >= 0 ? tab.idx1[i] : nblk);
-        for (int i = 0; i < nb; ++i) ids.push_back(tab.idx2[i] >= 0 ? tab.idx2[i] : nblk);
-        const int rc = B.ipool.assign(ids.data(), ids.size(), stream);
-        if (rc != FMPC_OK) return rc;
-        B.nblk = nblk; B.table_ready = 1;
-    }
-    if (!B.prepared[t]) {
-        if (fmpc_tiled_prepare(n, NB, X.NW, t, X.lds, h->denseR, 1) != hipSuccess) return FMPC_E_HIP;
-        if (fmpc_bank_build_prepare(NB, t) != hipSuccess) return FMPC_E_HIP;
-        B.prepared[t] = 1;
-    }
-    const size_t plain_stride = 4 * (size_t)n * n, pad_stride = 4 * (size_t)NP * NP;
-    const size_t yimg_stride = (size_t)(B.nblk + 1) * NQ * FT_TILE;
-    const size_t ybytes = yimg_stride * (size_t)count * (t ? sizeof(float) : sizeof(double));
-    if (capturing && (plain_stride * (size_t)count > B.plain.cap || pad_stride * (size_t)count > B.pad.cap || ybytes > B.yimg.cap))
-        return FMPC_E_ALLOC;                                           // (the bank that is there stays as it is)
-    B.count = 0;                                                       // (no bank while it is being replaced)
-    h->bkf.valid = 0;                                                  // (and no stored factors of the models that leave)
-    h->bfm.valid = 0;                                                  // (nor their first-move form)
-    int rc = fmpc_guard_begin(h, stream);                             // (an earlier bank solve may still read the old images)
-    if (rc != FMPC_OK) return rc;
-    rc = B.plain.grow(plain_stride * (size_t)count, stream);
-    if (rc == FMPC_OK) rc = B.pad.grow(pad_stride * (size_t)count, stream);
-    if (rc == FMPC_OK) rc = B.yimg.grow(ybytes, stream);
-    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }      // (the handle is left without a bank)
-    FbParams Q;
-    Q.n = n; Q.NB = NB; Q.count = count; Q.nblk = B.nblk; Q.is_float = t;
-    Q.A1 = A1; Q.A2 = h->var_order == 2 ? A2 : nullptr;
-    Q.XP = X.V.XP; Q.XfP = X.V.XfP; Q.desc = B.ipool;
-    Q.plain = B.plain; Q.plain_stride = plain_stride; Q.pad = B.pad; Q.pad_stride = pad_stride;
-    Q.yimg = B.yimg.p; Q.yimg_stride = yimg_stride;
-    const bool launched = fmpc_launch_bank_build(Q, stream) == hipSuccess;
-    fmpc_guard_end(h, stream);
-    if (!launched) return FMPC_E_HIP;
-    B.plain_stride = plain_stride; B.pad_stride = pad_stride; B.yimg_stride = yimg_stride;
-    B.t = t; B.count = count;
-    return FMPC_OK;
-}
-extern "C" int fmpc_bank_count(fmpc_handle h) {
-    if (!h) return 0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return h->bank.count;
-}
-extern "C" int fmpc_bank_release(fmpc_handle h) {
-    if (!h) return FMPC_E_NULL;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lk(h->mu);
-    fmpc_handle_s::Bank& B = h->bank;
-    if (B.plain.p || B.pad.p || B.yimg.p) (void)hipDeviceSynchronize();   // (a bank solve in flight reads them)
-    B.plain.release(); B.pad.release(); B.yimg.release();
-    B.count = 0;
-    h->bkf.valid = 0; h->bkf.fac.release(); h->bkf.flag.release();
-    h->bfm.valid = 0; h->bfm.count = 0; h->bfm.ops.release(); h->bfm.scratch.release(); h->bfm.flag.release();
-    return FMPC_OK;
-}
-
-// The parameter block of a launch over the bank's models (the bank solve, the build of the stored factors): the handle's constants
-// with the model-dependent images replaced by the bank's.  Caller holds h->mu; the per-call fields are the caller's.
-static void fmpc_bank_params(fmpc_handle h, int t, FtParams& P) {
-    const fmpc_handle_s::Bank& B = h->bank;
-    const fmpc_handle_s::Tiled& X = h->tl[t];
-    const int nb = h->nb, NP = 16 * X.NB;
-    const size_t nn = (size_t)h->n * h->n, PP = (size_t)NP * NP;
-    P.M = h->dev; P.V = X.V;
-    P.M.A1 = B.plain; P.M.A2 = B.plain + nn; P.M.A1t = B.plain + 2 * nn; P.M.A2t = B.plain + 3 * nn;
-    P.M.Yblk = nullptr; P.M.idxD = nullptr; P.M.idx1 = nullptr; P.M.idx2 = nullptr;      // (the handle's: not the bank's, and not read)
-    P.V.A1P = B.pad; P.V.A2P = B.pad + PP; P.V.A1tP = B.pad + 2 * PP; P.V.A2tP = B.pad + 3 * PP;
-    P.V.yimg = B.yimg.p; P.V.nblk = B.nblk;
-    const int* tab = B.ipool + (size_t)B.nblk * FB_DESC_INTS;
-    P.V.iD = tab; P.V.i1 = tab + nb; P.V.i2 = tab + 2 * nb;
-    P.list = nullptr; P.nlist = nullptr; P.nuws = nullptr;             // (the continuation lists belong to the shared-factor forms)
-    P.bk_count = B.count;
-    P.bk_plain = B.plain_stride; P.bk_pad = B.pad_stride; P.bk_yimg = B.yimg_stride;
-}
-
-// What a bank solve refuses before anything is enqueued.  Caller holds h->mu.
-static int fmpc_bank_solve_check(fmpc_handle h, int batch, const int* model_of) {
-    const fmpc_handle_s::Bank& B = h->bank;
-    const int t = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
-    if (B.count <= 0 || B.t != t || fmpc_bank_unsupported(h, t) || !h->tl[t].ready) return FMPC_E_UNSUPPORTED;
-    if (h->z_ld > h->T * (h->n + h->m)) return FMPC_E_UNSUPPORTED;
-    if (!model_of && batch > B.count) return FMPC_E_UNSUPPORTED;
-    return FMPC_OK;
-}
-// Everything a bank solve allocates (the scratch iterate of a first-moves-only call, the tiled workspace), before its launch and
-// before a caller's own launch in front of it (the loop inputs of fmpc_loop_step_bank_device).  Caller holds h->mu.
-static int fmpc_bank_solve_plan(fmpc_handle h, FmpcSolve& s, FmpcTiledPlan* plan) {
-    const int t = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
-    if (!s.z_out) {                                                    // first moves only: the iterate lives in the handle's scratch
-        const int rc = fmpc_scratch_z(h, s.batch, s.stream);
-        if (rc != FMPC_OK) return rc;
-        s.z_out = h->zs;
-    }
-    return fmpc_tiled_plan(h, t, s.batch, s.stream, 0, 0, plan);
-}
-static int fmpc_bank_solve_launch(fmpc_handle h, const FmpcSolve& s, const int* model_of, const FmpcTiledPlan& plan,
-                                  const int* list = nullptr, const int* nlist = nullptr) {
-    const int t = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
-    fmpc_handle_s::Tiled& X = h->tl[t];
-    const fmpc_handle_s::BankFactor& F = h->bkf;
-    FtParams P;
-    fmpc_bank_params(h, t, P);
-    P.batch = s.batch;
-    P.x0 = s.x0; P.x0p = s.x0_pre; P.w = s.w; P.zinit = s.z_init; P.nu0 = s.nu0;
-    P.max_iter = fmpc_max_iter(s); P.kbar = s.k;
-    P.zout = s.z_out; P.nuout = s.nu_out; P.status = s.status; P.iters = s.iters; P.step = s.step; P.step_ld = fmpc_step_ld(s.n_newton);
-    P.ws = h->tl_ws; P.ws_stride = plan.slot; P.u0out = s.u0_out;
-    P.refine = t ? h->refine : 0;
-    P.model_of = model_of;
-    P.list = list; P.nlist = nlist;                                    // (the first-move form's hand-over: FT_LIST_HANDED entries)
-    // the stored cold-start factors: from the cold start only, and only for the k they were built for, bit for bit
-    const bool stored = F.valid && F.t == t && F.count == h->bank.count && !h->denseR && !s.z_init && memcmp(&s.k, &F.k, sizeof(double)) == 0;
-    if (stored) { P.pf_fac = F.fac.p; P.pf_flag = F.flag; P.pf_stride = F.stride; }
-    h->bank_last_stored = stored ? 1 : 0;
-    h->tl_last_nw = plan.NWu;
-    if (t) h->refine_last = P.refine;
-    h->last_path = t ? FMPC_PATH_TILED_F32 : FMPC_PATH_TILED;
-    h->bank_first_dispatch = list ? 1 : 0;                             // (a list here is the first-move form's hand-over)
-    return fmpc_launch_tiled(P, X.NB, plan.NWu, t, plan.grid, plan.ldsu, s.stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
-}
-
-extern "C" int fmpc_solve_bank_device(fmpc_handle h, int batch, const int* model_of,
-                                      const double* x0, const double* x0_pre, const double* w,
-                                      const double* z_init, const double* nu0, int n_newton, double k,
-                                      double* z_out, double* nu_out, int* status, int* iters, double* step,
-                                      double* u0_out, void* stream_) {
-    if (!h || !x0 || (!z_out && !u0_out)) return FMPC_E_NULL;
-    if (batch < 0) return FMPC_E_DIM;
-    if (batch == 0) return FMPC_OK;
-    hipStream_t stream = (hipStream_t)stream_;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lk(h->mu);
-    int rc = fmpc_bank_solve_check(h, batch, model_of);
-    if (rc != FMPC_OK) return rc;
-    FmpcSolve s{batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step, u0_out, stream, 0};
-    rc = fmpc_guard_begin(h, stream);
-    if (rc != FMPC_OK) return rc;
-    FmpcTiledPlan plan;
-    rc = fmpc_bank_solve_plan(h, s, &plan);
-    if (rc == FMPC_OK) rc = fmpc_bank_solve_launch(h, s, model_of, plan);
-    fmpc_guard_end(h, stream);
-    return rc;
-}
-
-// ---- stored cold-start factor per model of the bank (include/fastmpc.h)
-extern "C" int fmpc_bank_prefactor_device(fmpc_handle h, double k, void* stream_) {
-    if (!h) return FMPC_E_NULL;
-    hipStream_t stream = (hipStream_t)stream_;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lk(h->mu);
-    fmpc_handle_s::Bank& B = h->bank;
-    fmpc_handle_s::BankFactor& F = h->bkf;
-    const int t = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
-    if (B.count <= 0 || B.t != t || h->denseR || fmpc_bank_unsupported(h, t) || !h->tl[t].ready) return FMPC_E_UNSUPPORTED;
-    fmpc_handle_s::Tiled& X = h->tl[t];
-    const size_t stride = (size_t)h->nb * ft_stage_tiles(X.NB) * FT_TILE;                  // elements of the factor's type per model
-    const size_t bytes = stride * (size_t)B.count * (t ? sizeof(float) : sizeof(double));
-    if (fmpc_capturing(stream) && (bytes > F.fac.cap || (size_t)B.count > F.flag.cap || !F.prepared[t])) return FMPC_E_ALLOC;
-    F.valid = 0;                                                       // (no store while it is being rebuilt)
-    int rc = fmpc_guard_begin(h, stream);                             // (an earlier bank solve may still read the old factors)
-    if (rc != FMPC_OK) return rc;
-    FmpcTiledPlan plan;
-    rc = fmpc_tiled_plan(h, t, B.count, stream, 0, 0, &plan);
-    if (rc == FMPC_OK) rc = fmpc_scratch_z(h, plan.grid, stream);     // the start point, one per workgroup
-    if (rc == FMPC_OK) rc = F.fac.grow(bytes, stream);
-    if (rc == FMPC_OK) rc = F.flag.grow((size_t)B.count, stream);
-    if (rc == FMPC_OK && !F.prepared[t]) {
-        if (fmpc_bank_prefactor_prepare(h->n, X.NB, plan.NWu, t, plan.ldsu) == hipSuccess) F.prepared[t] = 1;
-        else rc = FMPC_E_HIP;
-    }
-    if (rc == FMPC_OK) {
-        FtParams P;
-        fmpc_bank_params(h, t, P);
-        P.batch = B.count;
-        P.x0 = nullptr; P.x0p = nullptr; P.w = nullptr; P.zinit = nullptr; P.nu0 = nullptr;
-        P.max_iter = 1; P.kbar = k;
-        P.zout = h->zs; P.nuout = nullptr; P.status = nullptr; P.iters = nullptr; P.step = nullptr; P.step_ld = 0;
-        P.ws = h->tl_ws; P.ws_stride = plan.slot; P.u0out = nullptr;
-        P.refine = 0; P.model_of = nullptr;
-        P.pf_fac = F.fac.p; P.pf_flag = F.flag; P.pf_stride = stride;
-        if (fmpc_launch_bank_prefactor(P, X.NB, plan.NWu, t, plan.grid, plan.ldsu, stream) != hipSuccess) rc = FMPC_E_HIP;
-    }
-    fmpc_guard_end(h, stream);
-    if (rc != FMPC_OK) return rc;
-    F.valid = 1; F.count = B.count; F.t = t; F.k = k; F.stride = stride;
-    return FMPC_OK;
-}
-extern "C" int fmpc_bank_prefactor_count(fmpc_handle h) {
-    if (!h) return 0;
-    if (hipSetDevice(h->device) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    const fmpc_handle_s::BankFactor& F = h->bkf;
-    if (!F.valid || F.count <= 0) return 0;
-    std::vector<int> fl((size_t)F.count);
-    if (hipDeviceSynchronize() != hipSuccess) return 0;               // (the build may still be running, on any stream)
-    if (hipMemcpy(fl.data(), F.flag, fl.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-    int good = 0;
-    for (int f : fl) good += f == 0 ? 1 : 0;
-    return good;
-}
-extern "C" int fmpc_bank_prefactor_release(fmpc_handle h) {
-    if (!h) return FMPC_E_NULL;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lk(h->mu);
-    fmpc_handle_s::BankFactor& F = h->bkf;
-    if (F.fac.p || F.flag.p) (void)hipDeviceSynchronize();           // (a bank solve in flight reads them)
-    F.valid = 0; F.count = 0;
-    F.fac.release(); F.flag.release();
-    return FMPC_OK;
-}
-extern "C" int fmpc_last_bank_stored_factor(fmpc_handle h) {
-    if (!h) return 0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return h->bank_last_stored;
-}
-
-// ---- per-model first-move form of the bank's cold-start loop step (include/fastmpc.h; fmpc_bank_first_build_k, fmpc_first_move_bank)
-extern "C" int fmpc_bank_first_move_device(fmpc_handle h, double k, void* stream_) {
-    if (!h) return FMPC_E_NULL;
-    hipStream_t stream = (hipStream_t)stream_;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lk(h->mu);
-    fmpc_handle_s::Bank& B = h->bank;
-    const fmpc_handle_s::BankFactor& PF = h->bkf;
-    fmpc_handle_s::BankFirst& F = h->bfm;
-    const int n = h->n, m = h->m, T = h->T, nb = h->nb, nc = 4 * n, Hc = nc / 2 + 1;
-    if (B.count <= 0 || B.t != 0 || h->prec != FMPC_PREC_F64 || h->denseR || h->denseQ || fmpc_bank_unsupported(h, 0) || !h->tl[0].ready)
-        return FMPC_E_UNSUPPORTED;
-    if (!PF.valid || PF.t != 0 || PF.count != B.count || memcmp(&k, &PF.k, sizeof(double)) != 0) return FMPC_E_UNSUPPORTED;
-    // the application kernel's sizes (fmpc_launch_first_move_bank), and the depth the builder's rounding bound is written for
-    // (4 m + 16 n <= 1024 are the slots of the kernel's partial sums: m <= 148 at n = 27)
-    if (n != 27 || m > 160 || 4 * m + 16 * n > 1024 || nb * n + 2 * n + 8 > 4096) return FMPC_E_UNSUPPORTED;
-    fmpc_handle_s::Tiled& X = h->tl[0];
-    auto even = [](size_t v) { return (v + 1) & ~(size_t)1; };
-    size_t o = 0;
-    const size_t oK = o; o += even((size_t)nc * m);
-    const size_t ou = o; o += even(m);
-    const size_t oE = o; o += even((size_t)Hc * nc);
-    const size_t oe = o; o += even(nc);
-    const size_t oEp = o; o += even((size_t)Hc * nc);
-    const size_t oep = o; o += even(nc);
-    const size_t od = o; o += even(n);
-    const size_t osc = o; o += 8;
-    const size_t stride = o;                                           // 27828 doubles = 222624 bytes per model at (27, 144)
-    FmpcTiledPlan plan;
-    const bool capturing = fmpc_capturing(stream);
-    size_t s_ld = 0; int ncp = 0;
-    const size_t sdoubles = fmpc_bank_first_scratch_doubles(n, nb, &s_ld, &ncp);
-    int grid = B.count < h->num_cu ? B.count : h->num_cu;              // (a workgroup's scratch is 0.86 MB: one per CU)
-    if (capturing && (stride * (size_t)B.count > F.ops.cap || (size_t)B.count > F.flag.cap || sdoubles * (size_t)grid > F.scratch.cap ||
-                      !F.cst_valid || memcmp(&k, &F.cst_k, sizeof(double)) != 0 || !F.cnt.p || !F.prepared)) return FMPC_E_ALLOC;
-    // the model-independent constants, in long double: L L' = B diag(a^2) B', L y0 = B (a^2 o cu)   (fmpc_host_build_first_move: Ma2, bg)
-    typedef long double ld;
-    const int NX = 32;
-    std::vector<double> cst((size_t)NX * NX + NX + 8, 0.0);
-    {
-        std::vector<ld> a2(m), cu(m), Ma((size_t)n * n, 0.0L), v0(n, 0.0L), Lm((size_t)n * n, 0.0L), y0(n, 0.0L);
-        ld acu2 = 0.0L;
-        for (int j = 0; j < m; ++j) {
-            const double sp = h->hm_umax[j] - h->hm_umid[j], sm = h->hm_umid[j] - h->hm_umin[j];
-            const double dp = 1.0 / sp, dm = 1.0 / sm;
-            const double hc = k * (dp * dp + dm * dm);
-            cu[j] = (ld)(h->hm_R2[j] * h->hm_umid[j] + h->hm_rl[j] + k * (dp - dm));
-            const double av = hc * (1.0 / (h->hm_R2[j] + hc));
-            a2[j] = (ld)av * (ld)av;
-            acu2 += a2[j] * cu[j] * cu[j];
-        }
-        const double* bt = h->hm_bt.data();
-        for (int r = 0; r < n; ++r) {
-            for (int q = 0; q < n; ++q) { ld t = 0.0L; for (int j = 0; j < m; ++j) t += (ld)bt[(size_t)j * n + r] * a2[j] * (ld)bt[(size_t)j * n + q]; Ma[(size_t)r * n + q] = t; }
-            for (int j = 0; j < m; ++j) v0[r] += (ld)bt[(size_t)j * n + r] * a2[j] * cu[j];
-        }
-        for (int j = 0; j < n; ++j) {                                  // Cholesky; not positive definite: no form for this handle
-            ld d = Ma[(size_t)j * n + j];
-            for (int q = 0; q < j; ++q) d -= Lm[(size_t)j * n + q] * Lm[(size_t)j * n + q];
-            if (!(d > 0.0L) || !std::isfinite((double)d)) return FMPC_E_UNSUPPORTED;
-            const ld dj = sqrtl(d);
-            Lm[(size_t)j * n + j] = dj;
-            for (int i = j + 1; i < n; ++i) {
-                ld t = Ma[(size_t)i * n + j];
-                for (int q = 0; q < j; ++q) t -= Lm[(size_t)i * n + q] * Lm[(size_t)j * n + q];
-                Lm[(size_t)i * n + j] = t / dj;
-            }
-        }
-        ld y2 = 0.0L, lf2 = 0.0L;
-        for (int i = 0; i < n; ++i) {
-            ld t = v0[i];
-            for (int q = 0; q < i; ++q) t -= Lm[(size_t)i * n + q] * y0[q];
-            y0[i] = t / Lm[(size_t)i * n + i];
-            y2 += y0[i] * y0[i];
-        }
-        for (int i = 0; i < n; ++i)
-            for (int q = 0; q <= i; ++q) { cst[(size_t)q * NX + i] = (double)Lm[(size_t)i * n + q]; lf2 += Lm[(size_t)i * n + q] * Lm[(size_t)i * n + q]; }
-        for (int i = 0; i < n; ++i) cst[(size_t)NX * NX + i] = (double)y0[i];
-        const ld c0 = (ld)T * (acu2 - y2);
-        cst[(size_t)NX * NX + NX] = (double)(c0 > 0.0L ? c0 : 0.0L);
-        cst[(size_t)NX * NX + NX + 1] = (double)lf2 * (1.0 + 1e-12);
-        cst[(size_t)NX * NX + NX + 2] = (double)((ld)T * y2) * (1.0 + 1e-12);
-    }
-    F.valid = 0;                                                       // (no form while it is being rebuilt)
-    int rc = fmpc_guard_begin(h, stream);                             // (an earlier loop step may still read the old operands)
-    if (rc != FMPC_OK) return rc;
-    rc = fmpc_tiled_plan(h, 0, grid, stream, 0, 0, &plan);
-    if (rc == FMPC_OK && plan.grid < grid) grid = plan.grid;
-    if (rc == FMPC_OK) rc = fmpc_scratch_z(h, grid, stream);
-    if (rc == FMPC_OK) rc = F.ops.grow(stride * (size_t)B.count, stream);
-    if (rc == FMPC_OK) rc = F.flag.grow((size_t)B.count, stream);
-    if (rc == FMPC_OK) rc = F.scratch.grow(sdoubles * (size_t)grid, stream);
-    if (rc == FMPC_OK) rc = F.cst.grow(cst.size(), stream);
-    if (rc == FMPC_OK && !F.cnt.p) { rc = F.cnt.alloc(2, stream); if (rc == FMPC_OK) (void)hipMemset(F.cnt, 0, 2 * sizeof(int)); }
-    if (rc == FMPC_OK && !F.prepared) {
-        if (fmpc_bank_first_build_prepare(X.NB, plan.NWu, plan.ldsu) == hipSuccess) F.prepared = 1;
-        else rc = FMPC_E_UNSUPPORTED;                                  // (a wavefront count the builder has no instance for)
-    }
-    // (under capture the constants of this k are on the device already: checked above; otherwise a blocking copy)
-    if (rc == FMPC_OK && !capturing) {
-        F.cst_valid = 0;
-        if (hipMemcpy(F.cst, cst.data(), cst.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = FMPC_E_HIP;
-        else { F.cst_valid = 1; F.cst_k = k; }
-    }
-    if (rc == FMPC_OK) {
-        FtParams P;
-        fmpc_bank_params(h, 0, P);
-        P.batch = B.count;
-        P.x0 = nullptr; P.x0p = nullptr; P.w = nullptr; P.zinit = nullptr; P.nu0 = nullptr;
-        P.max_iter = 1; P.kbar = k;
-        P.zout = h->zs; P.nuout = nullptr; P.status = nullptr; P.iters = nullptr; P.step = nullptr; P.step_ld = 0;
-        P.ws = h->tl_ws; P.ws_stride = plan.slot; P.u0out = nullptr;
-        P.refine = 0; P.model_of = nullptr;
-        P.pf_fac = PF.fac.p; P.pf_flag = PF.flag; P.pf_stride = PF.stride;
-        FbfParams Q;
-        Q.S = F.scratch; Q.s_ld = s_ld; Q.s_stride = sdoubles; Q.ncp = ncp;
-        Q.out = F.ops; Q.out_stride = stride; Q.oK = oK; Q.ou = ou; Q.oE = oE; Q.oe = oe; Q.oEp = oEp; Q.oep = oep; Q.od = od; Q.osc = osc;
-        Q.flag = F.flag; Q.cst = F.cst;
-        if (fmpc_launch_bank_first_build(P, Q, X.NB, plan.NWu, grid, plan.ldsu, stream) != hipSuccess) rc = FMPC_E_HIP;
-    }
-    fmpc_guard_end(h, stream);
-    if (rc != FMPC_OK) return rc;
-    F.valid = 1; F.count = B.count; F.k = k; F.stride = stride;
-    F.oK = oK; F.ou = ou; F.oE = oE; F.oe = oe; F.oEp = oEp; F.oep = oep; F.od = od; F.osc = osc;
-    return FMPC_OK;
-}
-extern "C" int fmpc_bank_first_move_count(fmpc_handle h) {
-    if (!h) return 0;
-    if (hipSetDevice(h->device) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    const fmpc_handle_s::BankFirst& F = h->bfm;
-    if (!F.valid || F.count <= 0) return 0;
-    std::vector<int> fl((size_t)F.count);
-    if (hipDeviceSynchronize() != hipSuccess) return 0;               // (the build may still be running, on any stream)
-    if (hipMemcpy(fl.data(), F.flag, fl.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-    int good = 0;
-    for (int f : fl) good += f == 0 ? 1 : 0;
-    return good;
-}
-extern "C" int fmpc_bank_first_move_release(fmpc_handle h) {
-    if (!h) return FMPC_E_NULL;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lk(h->mu);
-    fmpc_handle_s::BankFirst& F = h->bfm;
-    if (F.ops.p || F.scratch.p || F.flag.p) (void)hipDeviceSynchronize();   // (a loop step in flight reads them)
-    F.valid = 0; F.count = 0;
-    F.ops.release(); F.scratch.release(); F.flag.release();            // (need, list, cnt, cst: a few bytes per realisation, kept until fmpc_destroy)
-    return FMPC_OK;
-}
-extern "C" int fmpc_last_bank_first_move(fmpc_handle h) {
-    if (!h) return 0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return h->bank_last_first;
-}
-
-// caller holds h->mu and has checked that a bank exists
-static int fmpc_loop_inputs_bank_launch(fmpc_handle h, int batch, const int* model_of, const double* a_k, const double* x0_last,
-                                        const double* u1, const double* u2, double* x0, double* x0_pre, double* w, hipStream_t stream) {
-    const fmpc_handle_s::Bank& B = h->bank;
-    return fmpc_launch_loop_inputs_bank(h->n, h->m, h->T, h->var_order == 2, batch, h->dev.Bt, B.plain, B.plain_stride, B.count,
-                                        model_of, a_k, x0_last, u1, u2, x0, x0_pre, w, stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
-}
-extern "C" int fmpc_loop_inputs_bank_device(fmpc_handle h, int batch, const int* model_of,
-                                            const double* a_k, const double* x0_last, const double* u1,
-                                            const double* u2, double* x0, double* x0_pre, double* w, void* stream) {
-    if (!h || !a_k || !x0 || !x0_pre || !w) return FMPC_E_NULL;
-    if (batch < 0) return FMPC_E_DIM;
-    if (batch == 0) return FMPC_OK;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lk(h->mu);
-    const fmpc_handle_s::Bank& B = h->bank;
-    if (B.count <= 0 || (!model_of && batch > B.count)) return FMPC_E_UNSUPPORTED;
-    // (the bank's images are rewritten in place by fmpc_bank_set_device: ordered against it like the bank solve)
-    int rc = fmpc_guard_begin(h, (hipStream_t)stream);
-    if (rc != FMPC_OK) return rc;
-    rc = fmpc_loop_inputs_bank_launch(h, batch, model_of, a_k, x0_last, u1, u2, x0, x0_pre, w, (hipStream_t)stream);
-    fmpc_guard_end(h, (hipStream_t)stream);
-    return rc;
-}
-
-// One closed-loop step with the bank's models: fmpc_loop_inputs_bank_device + fmpc_solve_bank_device from the cold start under one
-// lock; everything the solve allocates exists before the loop inputs are enqueued.
-extern "C" int fmpc_loop_step_bank_device(fmpc_handle h, int batch, const int* model_of, const double* a_k, const double* x0_last,
-                                          const double* u1, const double* u2, double* x0, double* x0_pre, double* w,
-                                          const double* nu0, int n_newton, double k,
-                                          double* z_out, double* nu_out, int* status, int* iters, double* step,
-                                          double* u0_out, void* stream_) {
-    if (!h || !a_k || !x0 || !x0_pre || !w || !u0_out) return FMPC_E_NULL;                 // z_out may be NULL: first moves only
-    if (batch < 0) return FMPC_E_DIM;
-    if (batch == 0) return FMPC_OK;
-    hipStream_t stream = (hipStream_t)stream_;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lk(h->mu);
-    int rc = fmpc_bank_solve_check(h, batch, model_of);
-    if (rc != FMPC_OK) return rc;
-    FmpcSolve s{batch, x0, x0_pre, w, nullptr, nu0, n_newton, k, z_out, nu_out, status, iters, step, u0_out, stream, 0};
-    rc = fmpc_guard_begin(h, stream);
-    if (rc != FMPC_OK) return rc;
-    FmpcTiledPlan plan;
-    rc = fmpc_bank_solve_plan(h, s, &plan);
-    // the per-model first-move form: first moves only, one Newton step, the k it was built for bit for bit -- and its per-batch
-    // buffers exist (under capture nothing grows: the call is then the exact path's)
-    fmpc_handle_s::BankFirst& F = h->bfm;
-    bool form = rc == FMPC_OK && F.valid && !F.disabled && F.count == h->bank.count && h->prec == FMPC_PREC_F64 && !z_out && !nu_out &&
-                n_newton == 1 && memcmp(&k, &F.k, sizeof(double)) == 0;
-    if (form && (F.need.grow((size_t)batch, stream) != FMPC_OK || F.list.grow((size_t)batch, stream) != FMPC_OK)) form = false;
-    h->bank_last_first = form ? 1 : 0;
-    if (rc == FMPC_OK) rc = fmpc_loop_inputs_bank_launch(h, batch, model_of, a_k, x0_last, u1, u2, x0, x0_pre, w, stream);
-    if (rc == FMPC_OK && form) {
-        FmParams P;
-        memset(&P, 0, sizeof(P));
-        P.n = h->n; P.m = h->m; P.T = h->T; P.nb = h->nb; P.var2 = h->var_order == 2 ? 1 : 0; P.has_xf = h->has_xf;
-        P.step_ld = fmpc_step_ld(n_newton); P.x0_given = 1;
-        P.a_k = x0; P.x0_last = x0_pre; P.u1 = u1; P.u2 = u2; P.nu0 = nu0;
-        P.x0 = x0; P.x0_pre = x0_pre; P.w = w; P.u0out = u0_out; P.status = status; P.iters = iters; P.step = step;
-        P.need = F.need; P.handed = nullptr; P.bt = h->dev.Bt;
-        P.K0t = F.ops + F.oK; P.u0c = F.ops + F.ou; P.E = F.ops + F.oE; P.e = F.ops + F.oe; P.Ep = F.ops + F.oEp; P.ep = F.ops + F.oep;
-        P.dx0T = F.ops + F.od; P.bk_sc = F.ops + F.osc;
-        P.model_of = model_of; P.bk_count = F.count; P.bk_stride = F.stride; P.bk_flag = F.flag;
-        if (fmpc_launch_first_move_bank(P, batch, stream) != hipSuccess ||
-            fmpc_launch_need_compact(F.need, batch, FT_LIST_HANDED, F.list, F.cnt, stream) != hipSuccess) rc = FMPC_E_HIP;
-        if (rc == FMPC_OK) rc = fmpc_bank_solve_launch(h, s, model_of, plan, F.list, F.cnt + 1);
-    } else if (rc == FMPC_OK) {
-        rc = fmpc_bank_solve_launch(h, s, model_of, plan);
-    }
-    fmpc_guard_end(h, stream);
-    return rc;
-}
-
-// A stretch of the loop with the bank's models in ONE host call: steps consecutive fmpc_loop_step_bank_device calls with the first
-// moves fed back on the device (u[k] = U0[k], u[k-1] = U0[k-1], ...), x0 updated in place.
-extern "C" int fmpc_loop_run_bank_device(fmpc_handle h, int batch, int steps, const int* model_of, const double* a, const double* nu0,
-                                         const double* u_before1, const double* u_before2, int have_x0_last,
-                                         int n_newton, double k, double* x0, double* x0_pre, double* w,
-                                         double* U0, double* X0, int* status, int* iters, void* stream) {
-    if (!h || !a || !x0 || !x0_pre || !w || !U0) return FMPC_E_NULL;
-    if (batch < 0 || steps < 0) return FMPC_E_DIM;
-    if (batch == 0 || steps == 0) return FMPC_OK;
-    const size_t sn = (size_t)batch * h->n, sm = (size_t)batch * h->m, snu = (size_t)batch * h->nb * h->n;
-    for (int s = 0; s < steps; ++s) {
-        const double* u1 = s >= 1 ? U0 + (size_t)(s - 1) * sm : u_before1;
-        const double* u2 = s >= 2 ? U0 + (size_t)(s - 2) * sm : (s == 1 ? u_before1 : u_before2);
-        const int rc = fmpc_loop_step_bank_device(h, batch, model_of, a + (size_t)s * sn, (s >= 1 || have_x0_last) ? x0 : nullptr, u1, u2,
-                                                  x0, x0_pre, w, nu0 ? nu0 + (size_t)s * snu : nullptr, n_newton, k, nullptr, nullptr,
-                                                  status, iters, nullptr, U0 + (size_t)s * sm, stream);
-        if (rc != FMPC_OK) return rc;
-        if (X0 && hipMemcpyAsync(X0 + (size_t)s * sn, x0, sn * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return FMPC_E_HIP;
-    }
-    return FMPC_OK;
 }
 
 extern "C" int fmpc_solve_device(fmpc_handle h, int batch,
@@ -3183,198 +2377,6 @@ extern "C" int fmpc_loop_inputs_device(fmpc_handle h, int batch, const double* a
                                    x0, x0_pre, w, (hipStream_t)stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
-// Q, Qf, R of the records kernels on the device, once per handle (h->mu held, inside the guard).  n <= 32 with diagonal weights: the
-// panel kernel's zero-padded diagonals; otherwise the dense matrices of the any-size kernel.  The handle keeps 2Q, 2Qf, 2R.
-static int fmpc_ensure_records(fmpc_handle h, hipStream_t stream) {
-    if (h->rec_ready) return FMPC_OK;
-    const int n = h->n, m = h->m;
-    const int panel = n <= REC_NMAX && !h->denseQ && !h->denseR;
-    std::vector<double> v;
-    if (panel) {
-        const int mpad = (m + 15) & ~15;
-        h->rec_oQf = REC_NMAX; h->rec_oR = 2 * REC_NMAX;
-        v.assign(2 * REC_NMAX + (size_t)mpad, 0.0);
-        for (int i = 0; i < n; ++i) { v[i] = 0.5 * h->hm_Q2[i]; v[h->rec_oQf + i] = 0.5 * h->hm_Qf2[i]; }
-        for (int j = 0; j < m; ++j) v[h->rec_oR + j] = 0.5 * h->hm_R2[j];
-    } else {
-        const size_t nn = (size_t)n * n;
-        h->rec_oQf = nn; h->rec_oR = 2 * nn;
-        v.assign(2 * nn + (size_t)m * m, 0.0);
-        for (size_t e = 0; e < nn; ++e) { v[e] = 0.5 * h->hm_q2m[e]; v[nn + e] = 0.5 * h->hm_qf2m[e]; }
-        if (h->denseR) for (size_t e = 0; e < (size_t)m * m; ++e) v[2 * nn + e] = 0.5 * h->hm_r2full[e];
-        else for (int j = 0; j < m; ++j) v[2 * nn + (size_t)j * m + j] = 0.5 * h->hm_R2[j];
-    }
-    const int rc = h->rec_w.assign(v.data(), v.size(), stream);       // (FMPC_E_ALLOC while the stream is being captured)
-    if (rc != FMPC_OK) return rc;
-    h->rec_panel = panel; h->rec_ready = 1;
-    return FMPC_OK;
-}
-
-static int fmpc_records_launch(fmpc_handle h, RecParams& P, hipStream_t stream) {
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lock(h->mu);
-    int rc = fmpc_guard_begin(h, stream);
-    if (rc != FMPC_OK) return rc;
-    rc = fmpc_ensure_records(h, stream);
-    if (rc == FMPC_OK && P.J && h->rec_panel) rc = h->rec_j.grow((size_t)P.stages * P.batch, stream);
-    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
-    P.n = h->n; P.m = h->m; P.T = h->T;
-    P.Bt = h->dev.Bt; P.M1 = h->loop_M1; P.M2 = h->loop_M2;
-    P.Q = h->rec_w; P.Qf = h->rec_w + h->rec_oQf; P.R = h->rec_w + h->rec_oR;
-    P.jpart = (P.J && h->rec_panel) ? (double*)h->rec_j : nullptr;
-    const bool ok = fmpc_launch_loop_records(P, h->rec_panel, stream) == hipSuccess;
-    fmpc_guard_end(h, stream);
-    return ok ? FMPC_OK : FMPC_E_HIP;
-}
-
-// The argument rules and the parameter block of the records of a timestep, for the shared-model call and the bank's: every rule
-// answers before the device is touched.  *todo = 0 with FMPC_OK: nothing to enqueue.
-static int fmpc_records_step_args(fmpc_handle h, int batch, int stages, const double* x0, const double* x0_pre, const double* w,
-                                  const double* u, long long ldu, int stage_stride, const double* u1,
-                                  double coeff_a, double coeff_b, double unit_change,
-                                  double* Xp, double* xerr, double* J, double* du, double* uv, RecParams& P, int* todo) {
-    *todo = 0;
-    if (uv && (!(coeff_a > 0.0) || !isfinite(coeff_a) || !isfinite(coeff_b) || !isfinite(unit_change))) return FMPC_E_DIM;
-    if (batch < 0 || stages < 1) return FMPC_E_DIM;
-    if (!h || !x0 || !u) return FMPC_E_NULL;
-    if (stages > h->T || (J && stages != h->T)) return FMPC_E_DIM;
-    if (stages > 1 && stage_stride < h->m) return FMPC_E_DIM;
-    if (ldu < (long long)(stages - 1) * (stages > 1 ? stage_stride : 0) + h->m) return FMPC_E_DIM;
-    if ((!Xp && !xerr && !J && !du && !uv) || batch == 0) return FMPC_OK;
-    memset(&P, 0, sizeof(P));
-    P.batch = batch; P.steps = 0;
-    P.stages = (Xp || xerr || J) ? stages : 1;                        // (du and uv are the first move's)
-    P.x0 = x0; P.x0_pre = x0_pre; P.w = w; P.u = u; P.ldu = ldu; P.stage_stride = stages > 1 ? stage_stride : 0; P.u1 = u1;
-    P.ca = coeff_a; P.cb = coeff_b; P.uc = unit_change;
-    P.Xp = Xp; P.xerr = xerr; P.J = J; P.du = du; P.uv = uv;
-    *todo = 1;
-    return FMPC_OK;
-}
-// ... of the stage-0 records of a recorded stretch
-static int fmpc_records_run_args(fmpc_handle h, int batch, int steps, const double* X0, const double* U0,
-                                 const double* x0_before, const double* u_before1, const double* u_before2,
-                                 double coeff_a, double coeff_b, double unit_change,
-                                 double* Xp0, double* xerr0, double* dU, double* Uv, RecParams& P, int* todo) {
-    *todo = 0;
-    if (Uv && (!(coeff_a > 0.0) || !isfinite(coeff_a) || !isfinite(coeff_b) || !isfinite(unit_change))) return FMPC_E_DIM;
-    if (batch < 0 || steps < 0) return FMPC_E_DIM;
-    if (!h || !X0 || !U0) return FMPC_E_NULL;
-    if ((!Xp0 && !xerr0 && !dU && !Uv) || batch == 0 || steps == 0) return FMPC_OK;
-    if (steps > 65535) return FMPC_E_DIM;                              // (a grid dimension of the any-size kernel)
-    memset(&P, 0, sizeof(P));
-    P.batch = batch; P.steps = steps; P.stages = 1;
-    P.x0 = X0; P.u = U0; P.ldu = h->m; P.x0_before = x0_before; P.u_before1 = u_before1; P.u_before2 = u_before2;
-    P.ca = coeff_a; P.cb = coeff_b; P.uc = unit_change;
-    P.Xp = Xp0; P.xerr = xerr0; P.du = dU; P.uv = Uv;
-    *todo = 1;
-    return FMPC_OK;
-}
-
-// The records of a timestep (README.md:576-622; see include/fastmpc.h).
-extern "C" int fmpc_loop_records_device(fmpc_handle h, int batch, int stages,
-                                        const double* x0, const double* x0_pre, const double* w,
-                                        const double* u, long long ldu, int stage_stride, const double* u1,
-                                        double coeff_a, double coeff_b, double unit_change,
-                                        double* Xp, double* xerr, double* J, double* du, double* uv, void* stream) {
-    RecParams P;
-    int todo;
-    const int rc = fmpc_records_step_args(h, batch, stages, x0, x0_pre, w, u, ldu, stage_stride, u1, coeff_a, coeff_b, unit_change,
-                                          Xp, xerr, J, du, uv, P, &todo);
-    return todo ? fmpc_records_launch(h, P, (hipStream_t)stream) : rc;
-}
-
-// The stage-0 records of every step of a recorded stretch in one launch (see include/fastmpc.h).
-extern "C" int fmpc_loop_records_run_device(fmpc_handle h, int batch, int steps, const double* X0, const double* U0,
-                                            const double* x0_before, const double* u_before1, const double* u_before2,
-                                            double coeff_a, double coeff_b, double unit_change,
-                                            double* Xp0, double* xerr0, double* dU, double* Uv, void* stream) {
-    RecParams P;
-    int todo;
-    const int rc = fmpc_records_run_args(h, batch, steps, X0, U0, x0_before, u_before1, u_before2, coeff_a, coeff_b, unit_change,
-                                         Xp0, xerr0, dU, Uv, P, &todo);
-    return todo ? fmpc_records_launch(h, P, (hipStream_t)stream) : rc;
-}
-
-// The records with the model of each problem (fmpc_kernel_records_bank.hip): the prediction is the free response of model
-// model_of[p] through the bank's fp64 plain images, whatever arithmetic the bank was built for.  Ordered on the device with the
-// bank calls (fmpc_bank_set_device rewrites the images in place).
-static int fmpc_records_bank_launch(fmpc_handle h, RecBankParams& K, const int* model_of, hipStream_t stream) {
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lock(h->mu);
-    const fmpc_handle_s::Bank& B = h->bank;
-    RecParams& P = K.R;
-    if (B.count <= 0 || (!model_of && P.batch > B.count)) return FMPC_E_UNSUPPORTED;
-    int rc = fmpc_guard_begin(h, stream);
-    if (rc != FMPC_OK) return rc;
-    rc = fmpc_ensure_records(h, stream);
-    if (rc == FMPC_OK && P.J && h->rec_panel) rc = h->rec_j.grow((size_t)P.stages * P.batch, stream);
-    if (rc == FMPC_OK && h->rec_panel && P.steps == 0) rc = h->rec_f.grow((size_t)P.stages * P.batch * h->n, stream);
-    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
-    P.n = h->n; P.m = h->m; P.T = h->T;
-    P.Bt = h->dev.Bt;
-    P.Q = h->rec_w; P.Qf = h->rec_w + h->rec_oQf; P.R = h->rec_w + h->rec_oR;
-    P.jpart = (P.J && h->rec_panel) ? (double*)h->rec_j : nullptr;
-    K.plain = B.plain; K.plain_stride = B.plain_stride; K.count = B.count; K.var2 = h->var_order == 2;
-    K.model_of = model_of;
-    K.F = (h->rec_panel && P.steps == 0) ? (double*)h->rec_f : nullptr;
-    const bool ok = fmpc_launch_loop_records_bank(K, h->rec_panel, stream) == hipSuccess;
-    fmpc_guard_end(h, stream);
-    return ok ? FMPC_OK : FMPC_E_HIP;
-}
-
-extern "C" int fmpc_loop_records_bank_device(fmpc_handle h, int batch, const int* model_of, int stages,
-                                             const double* x0, const double* x0_pre, const double* w,
-                                             const double* u, long long ldu, int stage_stride, const double* u1,
-                                             double coeff_a, double coeff_b, double unit_change,
-                                             double* Xp, double* xerr, double* J, double* du, double* uv, void* stream) {
-    RecBankParams K;
-    int todo;
-    const int rc = fmpc_records_step_args(h, batch, stages, x0, x0_pre, w, u, ldu, stage_stride, u1, coeff_a, coeff_b, unit_change,
-                                          Xp, xerr, J, du, uv, K.R, &todo);
-    return todo ? fmpc_records_bank_launch(h, K, model_of, (hipStream_t)stream) : rc;
-}
-
-extern "C" int fmpc_loop_records_run_bank_device(fmpc_handle h, int batch, int steps, const int* model_of, const double* X0,
-                                                 const double* U0, const double* x0_before, const double* u_before1,
-                                                 const double* u_before2, double coeff_a, double coeff_b, double unit_change,
-                                                 double* Xp0, double* xerr0, double* dU, double* Uv, void* stream) {
-    RecBankParams K;
-    int todo;
-    const int rc = fmpc_records_run_args(h, batch, steps, X0, U0, x0_before, u_before1, u_before2, coeff_a, coeff_b, unit_change,
-                                         Xp0, xerr0, dU, Uv, K.R, &todo);
-    return todo ? fmpc_records_bank_launch(h, K, model_of, (hipStream_t)stream) : rc;
-}
-
-// KKT report (fmpc_kkt_api.hip has checked the arguments, fmpc_kkt_kernels.hip has the kernels): the rules that need the handle,
-// its lock and stream order, the model's pointers, the launch.  The bank form reads A1, A2 of model model_of[p] from the bank's
-// fp64 plain images and is ordered on the device with the bank calls.
-int fmpc_kkt_set_device(fmpc_handle h) { return hipSetDevice(h->device) == hipSuccess ? FMPC_OK : FMPC_E_HIP; }
-int fmpc_kkt_run(fmpc_handle h, KktParams& P, int bank, const int* model_of, hipStream_t stream) {
-    if (P.u_prev && (bank || !h->ramp_du.p)) return FMPC_E_UNSUPPORTED;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lock(h->mu);
-    const fmpc_handle_s::Bank& B = h->bank;
-    if (bank && (B.count <= 0 || (!model_of && P.batch > B.count))) return FMPC_E_UNSUPPORTED;
-    int rc = fmpc_guard_begin(h, stream);
-    if (rc != FMPC_OK) return rc;
-    const FmpcDevModel& D = h->dev;
-    const int panel = !bank && !P.u_prev && h->n <= KKT_NMAX && !D.denseQ && !D.denseR;
-    if (panel) rc = h->kkt_part.grow((size_t)KKT_PARTS * h->T * P.batch, stream);      // (FMPC_E_ALLOC while the stream is being captured)
-    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
-    P.n = h->n; P.m = h->m; P.T = h->T; P.has_xf = h->has_xf; P.var2 = h->var_order == 2; P.denseQ = D.denseQ; P.denseR = D.denseR;
-    P.A1 = D.A1; P.A2 = D.A2; P.A1t = D.A1t; P.A2t = D.A2t; P.Bt = D.Bt;
-    P.R2 = D.R2; P.Q2 = D.Q2; P.Qf2 = D.Qf2; P.Q2m = D.Q2m; P.Qf2m = D.Qf2m; P.R2m = D.R2m;
-    P.rl = D.rl; P.ql = D.ql; P.qfl = D.qfl; P.umin = D.umin; P.umax = D.umax; P.xf = D.xf;
-    if (P.u_prev) { P.dumin = h->ramp_du; P.dumax = h->ramp_du + h->m; }
-    P.bank = bank; P.count = B.count; P.plain = B.plain; P.plain_stride = B.plain_stride; P.model_of = model_of;
-    P.part = panel ? (double*)h->kkt_part : nullptr;
-    const bool ok = fmpc_launch_kkt(P, panel, stream) == hipSuccess;
-    fmpc_guard_end(h, stream);
-    return ok ? FMPC_OK : FMPC_E_HIP;
-}
-
-hipError_t fmpc_launch_phase_residual(int batch, size_t npx, int n, int m, const double* Bt, const double* phase, const double* u,
-                                      const double* Z, double* out, hipStream_t stream);
 // Residual phase screens of a timestep: README.md:453, 590-601 (see include/fastmpc.h).
 extern "C" int fmpc_phase_residual_device(fmpc_handle h, int batch, long long npx, const double* phase, const double* u_prev,
                                           const double* Z, double* out, void* stream) {
@@ -3488,67 +2490,4 @@ extern "C" int fmpc_solve_once(int n, int m, int T, int var_order,
         rc = fmpc_solve(ent->h, 1, x0, x0_pre, w, x_init, nu0, nw, k, x_opt, nullptr, &st, iters, nullptr);
     }
     return rc;
-}
-
-// VAR(2) identification (README.md:108-130) on the device; see include/fastmpc.h
-extern "C" int fmpc_var_identify_device(int n, int num_train, int num_samples, int batch, const double* series,
-                                        double* A1, double* A2, int* status, void* stream) {
-    if (!series || !A1 || !A2) return FMPC_E_NULL;
-    if (n <= 0 || batch < 0 || num_train < 2 * n + 2 || num_samples < num_train) return FMPC_E_DIM;   // fewer rows than unknowns: singular
-    if (n > 32) return FMPC_E_UNSUPPORTED;
-    if (batch == 0) return FMPC_OK;
-    return fmpc_launch_var_identify(n, num_train, num_samples, batch, series, A1, A2, status, (hipStream_t)stream) == hipSuccess
-               ? FMPC_OK : FMPC_E_HIP;
-}
-
-// VAR(1) / VAR(2) identification at any solver size and the validation of a model (README.md:116-153); see include/fastmpc.h
-#define FMPC_VARFIT_MAXP 224
-#define FMPC_VARFIT_MAX_SLOTS 512          // recommended workspace: at most two slots per compute unit of an MI355X (256 CUs)
-// order 2 at n <= 32 is the LDS kernel of fmpc_var_identify_device (no workspace); FMPC_VARFIT_BLOCKED=1, read at call time,
-// sends those sizes through the blocked kernels as well (scripts/var_fit_timing.py)
-static bool var_fit_blocked(int n, int order) {
-    if (order != 2 || n > 32) return true;
-    const char* e = getenv("FMPC_VARFIT_BLOCKED");
-    return e && e[0] == '1';
-}
-static int var_fit_dims(int n, int order, int batch) {
-    if ((order != 1 && order != 2) || n <= 0 || batch < 0) return FMPC_E_DIM;
-    if ((long long)order * n > FMPC_VARFIT_MAXP) return FMPC_E_UNSUPPORTED;
-    return FMPC_OK;
-}
-extern "C" size_t fmpc_var_fit_workspace_bytes(int n, int order, int batch) {
-    if (var_fit_dims(n, order, batch) != FMPC_OK || !var_fit_blocked(n, order)) return 0;
-    const int slots = batch < 1 ? 1 : batch > FMPC_VARFIT_MAX_SLOTS ? FMPC_VARFIT_MAX_SLOTS : batch;
-    return (size_t)slots * fmpc_varfit_slot_doubles(n, order) * sizeof(double);
-}
-extern "C" int fmpc_var_fit_device(int n, int order, int num_train, int num_samples, int batch, const double* series,
-                                   double* A1, double* A2, int* status, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!series || !A1 || (order == 2 && !A2)) return FMPC_E_NULL;
-    const int rc = var_fit_dims(n, order, batch);
-    if (rc != FMPC_OK) return rc;
-    if (num_train - order < order * n || num_samples < num_train) return FMPC_E_DIM;      // fewer rows than unknowns: singular
-    hipError_t e;
-    if (!var_fit_blocked(n, order)) {
-        if (batch == 0) return FMPC_OK;
-        e = fmpc_launch_var_identify(n, num_train, num_samples, batch, series, A1, A2, status, (hipStream_t)stream);
-    } else {
-        const size_t slot = fmpc_varfit_slot_doubles(n, order) * sizeof(double);
-        if (!workspace) return FMPC_E_NULL;
-        if (workspace_bytes < slot) return FMPC_E_DIM;
-        if (batch == 0) return FMPC_OK;
-        const size_t nslots = workspace_bytes / slot;
-        e = fmpc_launch_var_fit(n, order, num_train, num_samples, batch, series, A1, A2, status, (double*)workspace,
-                                nslots > (size_t)batch ? batch : (int)nslots, (hipStream_t)stream);
-    }
-    return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
-}
-extern "C" int fmpc_var_validate_device(int n, int order, int first, int count, int num_samples, int batch, const double* series,
-                                        const double* A1, const double* A2, double* rmse, double* rrmse, void* stream) {
-    if (!series || !A1 || (order == 2 && !A2) || !rmse) return FMPC_E_NULL;
-    const int rc = var_fit_dims(n, order, batch);
-    if (rc != FMPC_OK) return rc;
-    if (count <= 0 || first < order || (long long)first + count > num_samples) return FMPC_E_DIM;
-    if (batch == 0) return FMPC_OK;
-    return fmpc_launch_var_validate(n, order, first, count, num_samples, batch, series, A1, A2, rmse, rrmse, (hipStream_t)stream) == hipSuccess
-               ? FMPC_OK : FMPC_E_HIP;
 }

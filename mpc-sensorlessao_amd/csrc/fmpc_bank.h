@@ -1,6 +1,6 @@
 // Model bank: one VAR model (A1, A2) per problem of a batched solve (fmpc_bank_set_device, fmpc_solve_bank_device in
 // include/fastmpc.h).  Shared between the host code that builds the bank's block table (fmpc_host.cpp), the kernels that build
-// a bank's device images and its loop inputs (fmpc_kernel_bank.hip) and the API (fmpc_api.hip).  Internal to the library.
+// a bank's device images and its loop inputs (fmpc_kernel_bank.hip) and the API (fmpc_bank_api.hip).  Internal to the library.
 //
 // The constant blocks of Y = C Phi^-1 C'  are sums of at most three terms  sign * L * X_kind * R'  with
 // L, R in {I, A1, A2} and X_kind in {X = (2Q)^-1, Xf = (2Qf)^-1}.  fmpc_host_y_blocks interns blocks BY CONTENT, so which
@@ -32,6 +32,15 @@ struct FmpcBankTable {
 };
 // xf_is_x: (2Qf)^-1 is (2Q)^-1 byte for byte (a property of the handle, not of a model)
 void fmpc_host_bank_table(int T, bool var2, bool has_xf, bool xf_is_x, FmpcBankTable& out);
+// the table as the device reads it: [desc | iD | i1 | i2] = blocks x FB_DESC_INTS ints, then nb block ids each with "none" (-1)
+// replaced by the number of blocks (the all-zero block behind them)
+void fmpc_host_bank_desc(const FmpcBankTable& tab, int nb, std::vector<int>& ids);
+// The model-independent constants of the bank's first-move builder (fmpc_bank_first_move_device) for barrier weight k, in long
+// double: L L' = B diag(a^2) B', L y0 = B (a^2 o cu) (fmpc_host_build_first_move: Ma2, bg).  cst: NX NX + NX + 8 doubles, NX = 32:
+// L' (cst[q NX + i] = L[i][q], q <= i), y0 at NX NX, then T (sum a^2 cu^2 - |y0|^2) clamped at 0, |L|_F^2 (1 + 1e-12),
+// T |y0|^2 (1 + 1e-12).  bt[c n + r] = B[r][c].  false: B diag(a^2) B' is not positive definite (no form for this handle).
+bool fmpc_host_bank_first_constants(int n, int m, int T, double k, const double* bt, const double* umax, const double* umin,
+                                    const double* umid, const double* R2, const double* rl, std::vector<double>& cst);
 // block k of the table for one model, in long double (checks): out n x n row-major
 void fmpc_host_bank_eval(const FmpcBankBlock& blk, int n, const double* a1, const double* a2, const double* X, const double* Xf,
                          std::vector<long double>& out);

@@ -55,6 +55,9 @@ static inline bool fe_geometry_ok(int len, int first, int d, int ndiv) {
 }
 
 hipError_t fmpc_launch_estimator(const FeParams& P, hipStream_t stream);
+// residual phase screens of a timestep (fmpc_phase_residual_device), n <= 32
+hipError_t fmpc_launch_phase_residual(int batch, size_t npx, int n, int m, const double* Bt, const double* phase, const double* u,
+                                      const double* Z, double* out, hipStream_t stream);
 
 // The stand-alone fill (fmpc_kernel_noise.hip): out[r ld + i] = fl(sigma_r g(seed, step + *step_dev, first + r, i)), i < p.
 struct FnParams {

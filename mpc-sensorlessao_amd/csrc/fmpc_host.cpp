@@ -10,6 +10,46 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+bool fmpc_host_is_diag(const double* M, int n) {
+    for (int c = 0; c < n; ++c)
+        for (int r = 0; r < n; ++r)
+            if (r != c && fmpc_host_cm(M, n, r, c) != 0.0) return false;
+    return true;
+}
+
+bool fmpc_host_spd_inverse(const std::vector<double>& A, int n, std::vector<double>& inv) {
+    typedef long double ld;
+    std::vector<ld> L((size_t)n * n, 0.0L), Li((size_t)n * n, 0.0L);
+    for (int c = 0; c < n; ++c) {
+        ld d = A[c * n + c];
+        for (int k = 0; k < c; ++k) d -= L[c * n + k] * L[c * n + k];
+        if (!(d > 0.0L)) return false;
+        const ld l = sqrtl(d);
+        L[c * n + c] = l;
+        for (int r = c + 1; r < n; ++r) {
+            ld t = A[r * n + c];
+            for (int k = 0; k < c; ++k) t -= L[r * n + k] * L[c * n + k];
+            L[r * n + c] = t / l;
+        }
+    }
+    for (int c = 0; c < n; ++c) {                    // Li = L^-1
+        Li[c * n + c] = 1.0L / L[c * n + c];
+        for (int r = c + 1; r < n; ++r) {
+            ld t = 0.0L;
+            for (int k = c; k < r; ++k) t += L[r * n + k] * Li[k * n + c];
+            Li[r * n + c] = -t / L[r * n + r];
+        }
+    }
+    inv.assign((size_t)n * n, 0.0);
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b <= a; ++b) {
+            ld t = 0.0L;
+            for (int k = a; k < n; ++k) t += Li[k * n + a] * Li[k * n + b];
+            inv[a * n + b] = inv[b * n + a] = (double)t;
+        }
+    return true;
+}
+
 void fmpc_host_add_AXBt(std::vector<double>& out, const std::vector<double>& A, const std::vector<double>& X,
                         const std::vector<double>& B, int n, double sign) {
     std::vector<double> AX((size_t)n * n, 0.0);
@@ -132,6 +172,153 @@ void fmpc_host_bank_eval(const FmpcBankBlock& blk, int n, const double* a1, cons
                 out[(size_t)a * n + b] += tm.sign * v;
             }
     }
+}
+
+void fmpc_host_bank_desc(const FmpcBankTable& tab, int nb, std::vector<int>& ids) {
+    const int nblk = (int)tab.blocks.size();
+    ids.assign((size_t)nblk * FB_DESC_INTS, 0);
+    for (int k = 0; k < nblk; ++k) {
+        int* d = ids.data() + (size_t)k * FB_DESC_INTS;
+        d[0] = tab.blocks[k].nterms;
+        for (int q = 0; q < tab.blocks[k].nterms; ++q) {
+            const FmpcBankTerm& tm = tab.blocks[k].t[q];
+            d[1 + 4 * q] = tm.sign; d[2 + 4 * q] = tm.L; d[3 + 4 * q] = tm.X; d[4 + 4 * q] = tm.R;
+        }
+    }
+    for (int i = 0; i < nb; ++i) ids.push_back(tab.idxD[i]);
+    for (int i = 0; i < nb; ++i) ids.push_back(tab.idx1[i] >= 0 ? tab.idx1[i] : nblk);
+    for (int i = 0; i < nb; ++i) ids.push_back(tab.idx2[i] >= 0 ? tab.idx2[i] : nblk);
+}
+
+bool fmpc_host_bank_first_constants(int n, int m, int T, double k, const double* bt, const double* umax, const double* umin,
+                                    const double* umid, const double* R2, const double* rl, std::vector<double>& cst) {
+    typedef long double ld;
+    const int NX = 32;
+    cst.assign((size_t)NX * NX + NX + 8, 0.0);
+    std::vector<ld> a2(m), cu(m), Ma((size_t)n * n, 0.0L), v0(n, 0.0L), Lm((size_t)n * n, 0.0L), y0(n, 0.0L);
+    ld acu2 = 0.0L;
+    for (int j = 0; j < m; ++j) {
+        const double sp = umax[j] - umid[j], sm = umid[j] - umin[j];
+        const double dp = 1.0 / sp, dm = 1.0 / sm;
+        const double hc = k * (dp * dp + dm * dm);
+        cu[j] = (ld)(R2[j] * umid[j] + rl[j] + k * (dp - dm));
+        const double av = hc * (1.0 / (R2[j] + hc));
+        a2[j] = (ld)av * (ld)av;
+        acu2 += a2[j] * cu[j] * cu[j];
+    }
+    for (int r = 0; r < n; ++r) {
+        for (int q = 0; q < n; ++q) { ld t = 0.0L; for (int j = 0; j < m; ++j) t += (ld)bt[(size_t)j * n + r] * a2[j] * (ld)bt[(size_t)j * n + q]; Ma[(size_t)r * n + q] = t; }
+        for (int j = 0; j < m; ++j) v0[r] += (ld)bt[(size_t)j * n + r] * a2[j] * cu[j];
+    }
+    for (int j = 0; j < n; ++j) {                                  // Cholesky; not positive definite: no form for this handle
+        ld d = Ma[(size_t)j * n + j];
+        for (int q = 0; q < j; ++q) d -= Lm[(size_t)j * n + q] * Lm[(size_t)j * n + q];
+        if (!(d > 0.0L) || !std::isfinite((double)d)) return false;
+        const ld dj = sqrtl(d);
+        Lm[(size_t)j * n + j] = dj;
+        for (int i = j + 1; i < n; ++i) {
+            ld t = Ma[(size_t)i * n + j];
+            for (int q = 0; q < j; ++q) t -= Lm[(size_t)i * n + q] * Lm[(size_t)j * n + q];
+            Lm[(size_t)i * n + j] = t / dj;
+        }
+    }
+    ld y2 = 0.0L, lf2 = 0.0L;
+    for (int i = 0; i < n; ++i) {
+        ld t = v0[i];
+        for (int q = 0; q < i; ++q) t -= Lm[(size_t)i * n + q] * y0[q];
+        y0[i] = t / Lm[(size_t)i * n + i];
+        y2 += y0[i] * y0[i];
+    }
+    for (int i = 0; i < n; ++i)
+        for (int q = 0; q <= i; ++q) { cst[(size_t)q * NX + i] = (double)Lm[(size_t)i * n + q]; lf2 += Lm[(size_t)i * n + q] * Lm[(size_t)i * n + q]; }
+    for (int i = 0; i < n; ++i) cst[(size_t)NX * NX + i] = (double)y0[i];
+    const ld c0 = (ld)T * (acu2 - y2);
+    cst[(size_t)NX * NX + NX] = (double)(c0 > 0.0L ? c0 : 0.0L);
+    cst[(size_t)NX * NX + NX + 1] = (double)lf2 * (1.0 + 1e-12);
+    cst[(size_t)NX * NX + NX + 2] = (double)((ld)T * y2) * (1.0 + 1e-12);
+    return true;
+}
+
+bool fmpc_host_inverse_images(int n, int T, int nb, bool var2, int jks, int jks2, const double* a1, const double* a2,
+                              const std::vector<double>& nu, std::vector<double>& img, std::vector<double>& nuc,
+                              std::vector<double>& jst, std::vector<double>& ncs, std::vector<double>& img2,
+                              std::vector<double>& eimg, std::vector<double>& J4, std::vector<double>& nuc4) {
+    const int TN = T * n, nrow = nb * n, ncol = 2 * n + TN;
+    const double scale = FMPC_INV_SCALE;
+    jst.clear(); ncs.clear();
+    auto at = [&](int p, int row) { return nu[((size_t)(p / FP_NP) * nrow + row) * FP_NP + (p % FP_NP)]; };
+    const int nrt = (nrow + 15) / 16, jksp = 16 * ((jks + 15) / 16 + 3);
+    img.assign((size_t)nrt * jksp * 64, 0.0); nuc.assign((size_t)nrt * 16, 0.0);
+    for (int r = 0; r < nrow; ++r) {
+        nuc[r] = at(0, r);
+        if (!std::isfinite(nuc[r])) return false;                    // the panel path reports what is wrong; this form stays off
+    }
+    for (int rt = 0; rt < nrt; ++rt)
+        for (int ks = 0; ks < jks; ++ks)
+            for (int l = 0; l < 64; ++l) {
+                const int row = 16 * rt + (l & 15), kk = 4 * ks + (l >> 4);
+                int col = -1;                                        // column of d -> index of the unit-vector problem
+                if (kk < n) col = kk;
+                else if (kk < 2 * n) col = var2 ? kk : -1;           // VAR(1): x0_pre does not enter
+                else if (kk >= 4 * FP_XKS && kk - 4 * FP_XKS < TN) col = 2 * n + (kk - 4 * FP_XKS);
+                if (row < nrow && col >= 0) {
+                    const double v = (at(1 + col, row) - nuc[row]) / scale;
+                    if (!std::isfinite(v)) return false;
+                    img[((size_t)rt * jksp + ks) * 64 + l] = v;
+                }
+            }
+    // per stage: the rows of J_x as two 16-row A tiles (rows beyond n: zero) and nuc padded to 32 (d_z with the dual solve fused in)
+    jst.assign((size_t)nb * 2 * FP_XKS * 64, 0.0); ncs.assign((size_t)nb * 32, 0.0);
+    for (int st = 0; st < nb; ++st) {
+        for (int r = 0; r < n; ++r) ncs[(size_t)st * 32 + r] = nuc[(size_t)st * n + r];
+        for (int I = 0; I < 2; ++I)
+            for (int ks = 0; ks < FP_XKS; ++ks)
+                for (int l = 0; l < 64; ++l) {
+                    const int rl = 16 * I + (l & 15), kk = 4 * ks + (l >> 4);
+                    if (rl >= n) continue;
+                    const int row = st * n + rl;
+                    jst[(((size_t)st * 2 + I) * FP_XKS + ks) * 64 + l] = img[((size_t)(row >> 4) * jksp + ks) * 64 + ((kk & 3) << 4) + (row & 15)];
+                }
+    }
+    // J' = [J_x | d nu+ / d (B u1) | d nu+ / d (B u2)]
+    const int jksp2 = 16 * ((jks2 + 15) / 16 + 3);
+    img2.assign((size_t)nrt * jksp2 * 64, 0.0);
+    for (int rt = 0; rt < nrt; ++rt)
+        for (int ks = 0; ks < jks2; ++ks)
+            for (int l = 0; l < 64; ++l) {
+                const int row = 16 * rt + (l & 15), kk = 4 * ks + (l >> 4);
+                if (ks < FP_XKS) { img2[((size_t)rt * jksp2 + ks) * 64 + l] = img[((size_t)rt * jksp + ks) * 64 + l]; continue; }
+                const int c = kk - 4 * FP_XKS;
+                if (row < nrow && c < 2 * n) {
+                    const double v = (at(1 + ncol + c, row) - nuc[row]) / scale;
+                    if (!std::isfinite(v)) return false;
+                    img2[((size_t)rt * jksp2 + ks) * 64 + l] = v;
+                }
+            }
+    // E = [A1 A2 ; A2 0] (fast_mpc_eq_const.m:39-44), rows 0..53, columns [x0 ; x0_pre]
+    eimg.assign((size_t)4 * FP_XKS * 64, 0.0);
+    for (int I = 0; I < 4; ++I)
+        for (int ks = 0; ks < FP_XKS; ++ks)
+            for (int l = 0; l < 64; ++l) {
+                const int row = 16 * I + (l & 15), kk = 4 * ks + (l >> 4);
+                double v = 0.0;
+                if (row < n && kk < n) v = a1[row * n + kk];
+                else if (row < n && kk < 2 * n) v = var2 ? a2[row * n + kk - n] : 0.0;
+                else if (row < 2 * n && kk < n) v = var2 ? a2[(row - n) * n + kk] : 0.0;
+                eimg[((size_t)I * FP_XKS + ks) * 64 + l] = v;
+            }
+    // host copy for the first-move form: J with the columns [x0 | x0_pre | B u1 | B u2], nuc
+    const int nc = 4 * n;
+    J4.assign((size_t)nrow * nc, 0.0); nuc4.assign(nuc.begin(), nuc.begin() + nrow);
+    for (int r = 0; r < nrow; ++r)
+        for (int c = 0; c < nc; ++c) {
+            int pidx = -1;
+            if (c < n) pidx = 1 + c;
+            else if (c < 2 * n) pidx = var2 ? 1 + c : -1;
+            else pidx = 1 + ncol + (c - 2 * n);
+            if (pidx >= 0) J4[(size_t)r * nc + c] = (at(pidx, r) - nuc[r]) / scale;
+        }
+    return true;
 }
 
 void fmpc_host_panel_layout(int n, int m, int T, int nb, int mp, FmpcPanelIn& L, size_t* o_dump, size_t* total, int* dz_len) {

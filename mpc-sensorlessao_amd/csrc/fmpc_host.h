@@ -1,14 +1,22 @@
 // Host-only builders of the library: everything that is computed on the CPU once per handle or per (handle, k) and then
 // uploaded -- the iteration-invariant Y blocks with their de-duplication, the panel path's twisted block factorisation in
 // long double with its operator images and sweep schedules, and the least-recently-used cache of the one-shot entry.
-// No HIP in here: fmpc_api.hip calls these and does the allocation / upload; tests/host_san builds the same file with
-// g++ -fsanitize=address,undefined and checks the factorisation against a dense solve (sanitizers on the CPU build).
+// No HIP in here: the API files (fmpc_api.hip, fmpc_bank_api.hip) call these and keep the allocation, the upload and the launches
+// only; tests/host_san builds the same file with g++ -fsanitize=address,undefined and checks the factorisation against a dense
+// solve, the constants and operand images entry by entry (sanitizers on the CPU build).
 #pragma once
 #include <stddef.h>
 #include <string.h>
 #include <vector>
 
 #include "fmpc_panel_layout.h"
+
+// ---- the model arguments of fmpc_create
+// column-major (MATLAB) element
+inline double fmpc_host_cm(const double* M, int rows, int r, int c) { return M[(size_t)r + (size_t)c * rows]; }
+bool fmpc_host_is_diag(const double* M, int n);                    // M n x n column-major
+// inverse of a symmetric positive definite matrix (row-major n x n) by Cholesky in extended precision; false: not PD
+bool fmpc_host_spd_inverse(const std::vector<double>& A, int n, std::vector<double>& inv);
 
 // out (row-major n x n) += sign * A X B'   with A, B, X row-major n x n (X dense)
 void fmpc_host_add_AXBt(std::vector<double>& out, const std::vector<double>& A, const std::vector<double>& X,
@@ -80,6 +88,26 @@ struct FmpcLru {
     template <class D>
     void clear(D destroy) { for (Entry& e : items) destroy(e.h); items.clear(); }
 };
+
+// ---- dense form of the cold-start dual solve (fmpc_kernel_inv.hip): nu+ = nuc + J d.  fmpc_build_inverse (fmpc_api.hip) has the panel
+// kernel solve for the unit vectors of d scaled by FMPC_INV_SCALE; `nu` is what that launch leaves: problem p, row r at
+// ((p / FP_NP) nb n + r) FP_NP + p % FP_NP, with the problems 0: d = 0 (nuc); 1 + c, c < 2 n + T n: unit vector c of [x0 ; x0_pre ; w];
+// 1 + 2 n + T n + c, c < 2 n: w = -M1 e_c (c < n), -M2 e_(c - n).  From it, all as matrix-core operand images
+// [..][k-step][lane = 16 (k mod 4) + (row mod 16)]:
+//   img  [ceil(nb n / 16)][jksp][64]   J, k-steps [x0 ; x0_pre ; 0 0 | w] (FP_XKS + ceil(T n / 4) = jks of them, rows padded to jksp)
+//   nuc  16 ceil(nb n / 16)
+//   jst  [nb][2][FP_XKS][64], ncs [nb][32]   per stage the rows of J_x as two 16-row tiles and nuc padded to 32
+//   img2 as img with jks2 k-steps: J' = [J_x | d nu+ / d (B u1) | d nu+ / d (B u2)]
+//   eimg [4][FP_XKS][64]               E = [A1 A2 ; A2 0], columns [x0 ; x0_pre]
+//   J4   nb n x 4 n row-major, columns [x0 | x0_pre | B u1 | B u2], and nuc4 = nuc without its padding (the first-move form)
+// VAR(1): the x0_pre columns stay zero.  Returns false as soon as a value is not finite.  The outputs are filled in the order
+// img, (jst, ncs), img2, eimg, (J4, nuc4); jst and ncs are empty unless they are complete, which is what the caller needs to know
+// after a false return (it uploads them before img2 is looked at).
+#define FMPC_INV_SCALE 1048576.0
+bool fmpc_host_inverse_images(int n, int T, int nb, bool var2, int jks, int jks2, const double* a1, const double* a2,
+                              const std::vector<double>& nu, std::vector<double>& img, std::vector<double>& nuc,
+                              std::vector<double>& jst, std::vector<double>& ncs, std::vector<double>& img2,
+                              std::vector<double>& eimg, std::vector<double>& J4, std::vector<double>& nuc4);
 
 // ---- first-move form of the cold-start step (fmpc_kernel_first.hip; closed-loop steps of a few realisations, z_out = NULL)
 // With the data d = [x0 ; x0_pre ; B u1 ; B u2] (4 n numbers; w = -M1 B u1 - M2 B u2, README.md:490-497) the new dual

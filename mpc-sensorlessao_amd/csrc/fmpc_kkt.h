@@ -1,5 +1,5 @@
-// KKT report (fmpc_kkt_report_device and its bank / host forms in include/fastmpc.h): the argument block shared by fmpc_api.hip
-// (which fills the handle's part), fmpc_kkt_api.hip (the entry points) and fmpc_kkt_kernels.hip.
+// KKT report (fmpc_kkt_report_device and its bank / host forms in include/fastmpc.h): the argument block shared by
+// fmpc_kkt_api.hip (the entry points, which fill the handle's part) and fmpc_kkt_kernels.hip.
 #pragma once
 #include <stddef.h>
 #include <hip/hip_runtime.h>
@@ -33,6 +33,3 @@ struct KktParams {
 // panel != 0: the panel kernel and the fold (n <= KKT_NMAX, diagonal weights, no ramp rows, no bank; P.part given);
 // 0: the any-size kernel.
 hipError_t fmpc_launch_kkt(const KktParams& P, int panel, hipStream_t stream);
-// The handle's side (fmpc_api.hip): the rules that need the handle, its lock and stream order, the model pointers, the launch.
-int fmpc_kkt_set_device(struct fmpc_handle_s* h);
-int fmpc_kkt_run(struct fmpc_handle_s* h, KktParams& P, int bank, const int* model_of, hipStream_t stream);

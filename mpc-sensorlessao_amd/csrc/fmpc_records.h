@@ -1,5 +1,5 @@
 // Closed-loop records (fmpc_loop_records_device / fmpc_loop_records_run_device and their model-bank forms in include/fastmpc.h):
-// the argument blocks shared by fmpc_api.hip, fmpc_kernel_records.hip and fmpc_kernel_records_bank.hip.
+// the argument blocks shared by fmpc_records_api.hip, fmpc_kernel_records.hip and fmpc_kernel_records_bank.hip.
 #pragma once
 #include <stddef.h>
 #include <hip/hip_runtime.h>
@@ -33,3 +33,8 @@ struct RecBankParams {
     const int* model_of;                             // NULL: model p
     double* F;                                       // panel kernel, one timestep: the free response p_i, [batch][stages][n]
 };
+
+// closed-loop records (fmpc_kernel_records.hip)
+hipError_t fmpc_launch_loop_records(const RecParams& P, int panel, hipStream_t stream);
+// ... with the model bank (fmpc_kernel_records_bank.hip)
+hipError_t fmpc_launch_loop_records_bank(const RecBankParams& K, int panel, hipStream_t stream);

@@ -37,6 +37,25 @@ def test_host_builders_under_asan_ubsan(san_binary, T, has_xf):
         assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
 
 
+def test_api_host_math_under_asan_ubsan(tmp_path):
+    """The host arithmetic the API files call in fmpc_host.cpp (tests/host_san/api_host_math_test.cpp): the constants of the bank's
+    first-move builder against a long double restatement (L L', L y0 to 32 n 2^-53 of the largest entry; a singular matrix and a
+    zero row of B refused), every entry of the dense form's operand images against the entry of J, A1, A2 its layout names (==, T = 2
+    and 3, VAR(1) and VAR(2); a NaN refused), the bank's packed block descriptors against their table, and fmpc_host_spd_inverse
+    (A inv = I to 64 n 2^-53 cond; a zero pivot refused)."""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    out = str(tmp_path / "api_host_math_test")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+           "-Wall", "-Wextra", os.path.join(ROOT, "tests", "host_san", "api_host_math_test.cpp"), os.path.join(CSRC, "fmpc_host.cpp"), "-o", out]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([out], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
+
+
 @pytest.fixture(scope="module")
 def ramp_cold_binary(tmp_path_factory):
     if shutil.which("g++") is None:
