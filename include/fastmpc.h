@@ -1048,6 +1048,69 @@ int fmpc_est_model_device(fmpc_est_optics o, int nmode, const double* Z, const d
                           void* workspace, size_t workspace_bytes, void* stream);
 int fmpc_est_create_from_model(fmpc_est* out, fmpc_est_optics o, int nmode, int skip, const double* Z, const double* phi0);
 
+/*
+ * Deformable mirror of Gaussian actuators on the device: the reference's section "The influence matrix of Deformable Mirror (DM)
+ * generation" (README.md:184-272) and the surface such a mirror makes.  A mirror is m actuators with centres (cx_t, cy_t), a
+ * coupling in (0, 1) and a pitch d > 0; on a grid whose column c has abscissa x[c] and whose row r has ordinate y[r]
+ *     I_t(r, c) = exp(alpha ((x[c] - cx_t)^2 + (y[r] - cy_t)^2)),   alpha = log(coupling) / d^2        (README.md:226-232)
+ * which is ey_t[r] * ex_t[c] with ex_t[c] = exp(alpha (x[c] - cx_t)^2) and ey_t[r] = exp(alpha (y[r] - cy_t)^2): every entry
+ * evaluates the two factors in double and multiplies them, with alpha formed once on the host in double, so a pixel of a map, of
+ * the operand of B and of a term of the surface is the same number.  x (cols), y (rows), cx, cy (m) are DEVICE arrays of doubles;
+ * centres are per actuator and need lie neither on a grid nor inside the pixel grid (README.md:206-220 puts them on the 677^2
+ * mirror grid, README.md:255-263 crops to the 512^2 pupil: x = xaxis_dm(min_idx:max_idx), y = -x).  Maps are rows x cols with pixel
+ * (r, c) at r + rows * c: MATLAB's order, the order of fmpc_zernike_grid_device and of the screens the estimator takes.
+ *
+ * fmpc_dm_influence_device   the maps of actuators first .. first + count - 1, ldi >= rows * cols doubles apart (map first at I;
+ *                   nothing between the maps is written): B_pupil(:,:,t) of README.md:258-263.
+ * fmpc_dm_matrix_device      B = pinv(Zs'Zs) Zs' B_pupil (README.md:268-271) without the maps ever being in memory.  Z: n contiguous
+ *                   mode maps of rows * cols doubles, R: their factor from fmpc_modal_factor_device.  Result
+ *                   B[(i - skip) + ldb * t], (n - skip) x m column-major (ldb >= n - skip): the layout fmpc_create takes, and what
+ *                   fmpc_modal_fit_device writes for these maps with ldc = ldb (README.md:290 deletes the piston row: skip = 1).
+ *                   The workspace holds the factors ex, ey of every actuator ((rows + cols) * 16 * ceil(m / 16) doubles) and
+ *                   behind them partial sums for as many panels of 16 actuators as fit; a panel takes 16 * n_pad doubles
+ *                   (n_pad = 16 * ceil(n / 16)) per four chunks of the modal fit's pixel axis (a chunk is 256, 128 or 64 pixels
+ *                   for n <= 32, <= 48, beyond), a quarter of what fmpc_modal_fit_device keeps per panel.  The minimum is the
+ *                   tables and one panel; fmpc_dm_matrix_workspace_bytes is the recommended size (the tables and every panel
+ *                   up to 16 MiB; 0 for refused sizes), linear in rows * cols.  The operand of S = Z I' is formed where it is
+ *                   consumed (a lane multiplies the two factors of its four pixels), the product runs on
+ *                   v_mfma_f64_16x16x4_f64 with the pixel-to-lane map of the modal fit, the sum over the partials and the two
+ *                   triangular solves are the modal fit's finish kernel.  Every sum has a fixed order, there are no atomics:
+ *                   the bits of B do not depend on the workspace size.  A non-finite R (a failed factor) gives NaN.
+ * fmpc_dm_surface_device     out[b] = phase[b] + sum_t u[b][t] I_t for a batch of screens ldp / ldo >= rows * cols doubles apart,
+ *                   u[b] at u + b * ldu (ldu >= m): the zonal counterpart of fmpc_phase_residual_device (README.md:590-601 corrects
+ *                   with the modal surface sum_j (B u)_j Z_j, which a mirror of Gaussian actuators cannot make).  phase = NULL
+ *                   gives the surface alone; out == phase is allowed.  Per screen it is the rows x m by m x cols product
+ *                   (Ey o u_b)' Ex on the fp64 matrix cores, the factors of a 64 x 64 tile of pixels taken by the exponential
+ *                   into LDS, 16 actuators at a time; phase is read once and out written once.  The actuators are summed in
+ *                   ascending order: a screen's bits do not depend on its place in the batch or on the batch size.
+ * No entry takes a handle, allocates, synchronises or reads back; all can be recorded into a HIP graph.  Inside a stretch bracket
+ * (fmpc_stretch_begin) they count as foreign calls, as every call without a solver handle does.
+ * Measured on one MI355X (scripts/dm_timing.py; n = 28, m = 144, 512 x 512, medians, five rounds alternating with what is
+ * replaced, spread <= 1 %): fmpc_dm_matrix_device 0.094 ms in 10.6 MB of workspace against 0.199 ms for the maps into 302 MB
+ * followed by fmpc_modal_fit_device (2.1 x faster; 121 ms for numpy on the host), 0.10 of the HBM roofline on the 28 mode maps: it
+ * is bound by three launches and the finish kernel's latency.  fmpc_dm_surface_device on 1 / 256 / 2000 screens: 0.0191 / 0.415 /
+ * 3.13 ms against 0.0158 / 0.863 / 6.71 ms for fmpc_phase_residual_device (27 modes) and 0.0178 / 0.668 / 5.05 ms for one batched
+ * torch.matmul over ex / ey tables: slower than both for ONE screen, 2.1 x and 1.6 x faster from 256 on; 0.43 of the HBM roofline
+ * on one read and one write per pixel and 48.3 TFLOP/s, 0.61 of the fp64 matrix peak, at 2000 screens: 288 flop per pixel make it
+ * arithmetic-bound.
+ * Answered before the device is touched: FMPC_E_NULL for a NULL x, y, cx, cy, I, Z, R, B, workspace, u or out; FMPC_E_DIM for
+ * m, rows, cols, count or batch < 1, first < 0, first + count > m, ldi, ldp (with a phase) or ldo < rows * cols, ldu < m,
+ * a coupling outside (0, 1), a pitch that is not positive and finite, n < 1, rows * cols < n, skip outside [0, n), ldb < n - skip,
+ * a workspace below the minimum; FMPC_E_UNSUPPORTED for n > 128 (FMPC_MODAL_MAXN), for rows * cols or (rows + cols) * 16 *
+ * ceil(m / 16) beyond 2^31 - 1 in the matrix call, and for more than 2^31 - 1 tiles of a grid.
+ */
+int fmpc_dm_influence_device(int m, int rows, int cols, const double* x, const double* y, const double* cx, const double* cy,
+                             double coupling, double pitch, int first, int count, double* I, long long ldi, void* stream);
+size_t fmpc_dm_matrix_workspace_bytes(int n, int m, int rows, int cols);
+int fmpc_dm_matrix_device(int n, int m, int rows, int cols, const double* Z, const double* R,
+                          const double* x, const double* y, const double* cx, const double* cy,
+                          double coupling, double pitch, int skip, double* B, int ldb,
+                          void* ws, size_t ws_bytes, void* stream);
+int fmpc_dm_surface_device(int batch, int m, int rows, int cols, const double* x, const double* y,
+                           const double* cx, const double* cy, double coupling, double pitch,
+                           const double* u, long long ldu, const double* phase, long long ldp,
+                           double* out, long long ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,10 @@ SIGNATURES = {
     "fmpc_est_model_workspace_bytes": (C.c_size_t, [_vp, C.c_int]),
     "fmpc_est_model_device": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fmpc_est_create_from_model": (C.c_int, [C.POINTER(_vp), _vp, C.c_int, C.c_int, _vp, _vp]),
+    "fmpc_dm_influence_device": (C.c_int, [C.c_int] * 3 + [_vp] * 4 + [C.c_double] * 2 + [C.c_int] * 2 + [_vp, C.c_longlong, _vp]),
+    "fmpc_dm_matrix_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "fmpc_dm_matrix_device": (C.c_int, [C.c_int] * 4 + [_vp] * 6 + [C.c_double] * 2 + [C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp]),
+    "fmpc_dm_surface_device": (C.c_int, [C.c_int] * 4 + [_vp] * 4 + [C.c_double] * 2 + [_vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _vp]),
 }
 
 _lib = None

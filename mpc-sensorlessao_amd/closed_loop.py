@@ -187,9 +187,12 @@ class AOLoop:
     Z: (n, len, len) mode maps indexed [j, row, column] (piston removed), a host array or a tensor (a HIP tensor is not taken
     through the host; z_colmajor=True: it is indexed [j, column, row] already, the order of `optics.zernike_grid`).  Screens are handed over indexed [b, row, column].
     modal (optional): a `ModalFit` over the n + 1 mode maps WITH the piston, indexed as the screens are handed over; it gives
-    `true_coefficients`, the reference's ad_acc_valid, and changes nothing else."""
+    `true_coefficients`, the reference's ad_acc_valid, and changes nothing else.
+    dm (optional): a `GaussianDM` on the estimator's grid (rows = cols = len); the residual screen of a step is then
+    phase_valid[k] + sum_t u[k-1]_t I_t, the surface the mirror of Gaussian actuators makes (`fmpc_dm_surface_device`), instead of
+    the modal one; nothing else changes."""
 
-    def __init__(self, handle, estimator, Z, batch, n_newton=1, k=1e-2, one_call=True, modal=None, z_colmajor=False):
+    def __init__(self, handle, estimator, Z, batch, n_newton=1, k=1e-2, one_call=True, modal=None, z_colmajor=False, dm=None):
         import ctypes as C
         import numpy as np
         import torch
@@ -219,6 +222,9 @@ class AOLoop:
         if modal is not None and modal.n != n + 1:
             raise ValueError("modal: need the fit over the n + 1 modes with the piston")
         self.modal = modal
+        if dm is not None and (dm.rows != estimator.len or dm.cols != estimator.len or dm.m != m):
+            raise ValueError("dm: need a GaussianDM of the handle's m actuators on the estimator's len x len grid")
+        self.dm = dm
 
     def true_coefficients(self, phase_k, workspace=None, out=None):
         """The modal fit of the incoming screens with the piston dropped (zernmodfit of phase_valid(:,:,k): a row of ad_acc_valid,
@@ -240,10 +246,16 @@ class AOLoop:
         assert ph.is_contiguous() and ph.dtype == torch.float64
         vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         stream = C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
-        rc = self.h._lib.fmpc_phase_residual_device(self.h._h, self.batch, self.npx, vp(ph), vp(u1) if s >= 1 else None, vp(self.Z), vp(self.scrn), stream)
-        if rc != 0:
-            from ._lib import FastMPCError
-            raise FastMPCError(rc, "fmpc_phase_residual_device")
+        if self.dm is not None:              # the zonal surface of the mirror (no correction before the first move: README.md:447)
+            if s >= 1:
+                self.dm.surface(u1, phase=ph, out=self.scrn)
+            else:
+                self.scrn.copy_(ph)
+        else:
+            rc = self.h._lib.fmpc_phase_residual_device(self.h._h, self.batch, self.npx, vp(ph), vp(u1) if s >= 1 else None, vp(self.Z), vp(self.scrn), stream)
+            if rc != 0:
+                from ._lib import FastMPCError
+                raise FastMPCError(rc, "fmpc_phase_residual_device")
         # x0 = ad_est, x0_pre = the previous ad_est (README.md:482-488): two buffers in turn, the estimator writes into this step's
         self.x0, self.x0_pre = self._xb[s % 2], self._xb[(s + 1) % 2]
         if s == 0:
