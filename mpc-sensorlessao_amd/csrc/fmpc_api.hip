@@ -1260,12 +1260,12 @@ static int fmpc_path_affine(fmpc_handle h, const FmpcSolve& s, size_t stride, in
         W.mode = FW_MODE_SHARED; W.handed = h->pn_cnt; W.pphase = 3; W.list = a.need; W.nflag = no_nflag ? nullptr : nf;
         S.st[i].w = W;
         S.nsteps = i + 1;
-        h->last_path = FMPC_PATH_PANEL; h->inv_last = 2;
+        h->last_path = FMPC_PATH_PANEL; h->pn_split_last = 0; h->inv_last = 2;
         return FMPC_OK;
     }
     if (fmpc_launch_affine(A, h->num_cu, s.stream) != hipSuccess) return FMPC_E_HIP;
     const int rc = fmpc_launch_flagged(h, s, g3, stride, h->fa_need, no_nflag ? nullptr : nf, zld);
-    h->last_path = FMPC_PATH_PANEL; h->inv_last = 2;
+    h->last_path = FMPC_PATH_PANEL; h->pn_split_last = 0; h->inv_last = 2;
     return rc;
 }
 
@@ -1374,7 +1374,7 @@ static int fmpc_path_panel(fmpc_handle h, const FmpcSolve& s, size_t stride, int
     }
     if (split && hipMemcpyAsync(h->pn_cnt_host, h->pn_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, s.stream) != hipSuccess)
         return FMPC_E_HIP;
-    h->last_path = FMPC_PATH_PANEL;
+    h->last_path = FMPC_PATH_PANEL; h->pn_split_last = split;
     return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
@@ -1639,7 +1639,7 @@ static int fmpc_first_move_step(fmpc_handle h, int batch, const double* a_k, con
     const int grid = (batch + wpw - 1) / wpw;
     const FmpcSolve f = {batch, xs, xps, w, nullptr, nu0, 1, k, h->zs, nullptr, status, iters, step, u0_out, stream, 0};
     if (fmpc_launch_flagged(h, f, grid, stride, h->fm_need) != FMPC_OK) return FMPC_E_HIP;
-    h->last_path = FMPC_PATH_PANEL; h->inv_last = 1;
+    h->last_path = FMPC_PATH_PANEL; h->pn_split_last = 0; h->inv_last = 1;
     return FMPC_OK;
 }
 
@@ -1671,7 +1671,7 @@ static int fmpc_loop_u0_step(fmpc_handle h, int batch, const double* a_k, const 
         if (fmpc_launch_loop_step27(L, I, stream) != hipSuccess) return FMPC_E_HIP;
         const FmpcSolve f = {batch, xs, xps, w, nullptr, nu0, 1, k, h->zs, nullptr, status, iters, step, u0_out, stream, 0};
         if (fmpc_launch_flagged(h, f, grid, stride, h->fm_need) != FMPC_OK) return FMPC_E_HIP;
-        h->last_path = FMPC_PATH_PANEL; h->inv_last = 4;
+        h->last_path = FMPC_PATH_PANEL; h->pn_split_last = 0; h->inv_last = 4;
         return FMPC_OK;
     }
     if (given) return FMPC_E_UNSUPPORTED;          // (the caller takes the general route)
@@ -1686,7 +1686,7 @@ static int fmpc_loop_u0_step(fmpc_handle h, int batch, const double* a_k, const 
     if (fmpc_launch_loop_u0(L, stream) != hipSuccess) return FMPC_E_HIP;
     const FmpcSolve f = {batch, x0, x0_pre, w, nullptr, nu0, 1, k, h->zs, nullptr, status, iters, step, u0_out, stream, 0};
     if (fmpc_launch_flagged(h, f, grid, stride, h->fm_need) != FMPC_OK) return FMPC_E_HIP;
-    h->last_path = FMPC_PATH_PANEL; h->inv_last = 3;
+    h->last_path = FMPC_PATH_PANEL; h->pn_split_last = 0; h->inv_last = 3;
     return FMPC_OK;
 }
 
@@ -1820,7 +1820,7 @@ static int fmpc_loop_run_walk(fmpc_handle h, int batch, int steps, int upto, con
             bool ok = hipMemcpyAsync(d_start, start.data(), batch * sizeof(int), hipMemcpyHostToDevice, stream) == hipSuccess;
             ok = ok && fmpc_launch_first_move_run(P, R, stream) == hipSuccess;
             ok = ok && hipMemcpyAsync(stop.data(), d_stop, batch * sizeof(int), hipMemcpyDeviceToHost, stream) == hipSuccess;
-            h->last_path = FMPC_PATH_PANEL; h->inv_last = 1;
+            h->last_path = FMPC_PATH_PANEL; h->pn_split_last = 0; h->inv_last = 1;
             fmpc_guard_end(h, stream);
             if (!ok || hipStreamSynchronize(stream) != hipSuccess) return FMPC_E_HIP;
         }
@@ -1959,6 +1959,21 @@ extern "C" int fmpc_last_dispatch(fmpc_handle h, int* path, int* handed_over) {
             if (hipDeviceSynchronize() != hipSuccess) return FMPC_E_HIP;
             if (hipMemcpy(handed_over, h->bfm.cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return FMPC_E_HIP;
         }
+    }
+    return FMPC_OK;
+}
+
+// Diagnostic (tests; not part of include/fastmpc.h): after a FMPC_PATH_PANEL call with a Newton budget > 1, how many problems the
+// decision launch put on the continuation's list -- the handed-over ones and those whose next exit test the step's own residual
+// sums did not clearly meet; every other problem stopped after its first step.  0 after any other call.  Synchronises the device.
+extern "C" int fmpc_debug_continuation_count(fmpc_handle h, int* count) {
+    if (!h || !count) return FMPC_E_NULL;
+    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *count = 0;
+    if (h->last_path == FMPC_PATH_PANEL && h->pn_split_last) {
+        if (hipDeviceSynchronize() != hipSuccess) return FMPC_E_HIP;
+        if (hipMemcpy(count, h->pn_cnt + 1, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return FMPC_E_HIP;
     }
     return FMPC_OK;
 }

@@ -59,6 +59,7 @@ struct fmpc_handle_s {
     DevBuf<double> pn_pool;              // [simg | btimg | aimg | vec | ucon]
     size_t pn_o_simg, pn_o_limg, pn_o_bt, pn_o_aimg, pn_o_vec, pn_o_ucon, pn_o_dump, pn_doubles;
     DevBuf<int> pn_cnt;                  // problems the exact path had to solve in the last call (diagnostic)
+    int pn_split_last = 0;               // the last panel call ran decide + compacted continuation (budget > 1): pn_cnt[1] is its list length
     DevBuf<int> gn_list; DevBuf<double> gn_nu; DevBuf<int> gn_cnt; PinnedBuf<int> gn_cnt_host; size_t gn_cap = 0;   // explicit-start batches with a budget > 1: first step / continuation split
     int gn_split = 1;                                                                                           // (FMPC_NO_GENERAL_SPLIT=1: one launch)
     DevBuf<int> fa_nflag;                // affine form: [running count of flagged problems | the count the last exact-path launch dealt with | its

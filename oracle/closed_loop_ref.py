@@ -47,7 +47,8 @@ def closed_loop(model, a, n_newton=1, k=1e-2, nu0=None, ramp=None):
     A1, A2, B, T = model["A1"], model["A2"], model["B"], model["T"]
     n, m = B.shape
     solver = BandedFastMPC(A1, A2, B, model["Q"], model["R"], model["Qf"], model["u_min"], model["u_max"],
-                           model["x_min"], model["x_max"], T)
+                           model["x_min"], model["x_max"], T, q=model.get("q"), r=model.get("r"), qf=model.get("qf"),
+                           xf=model.get("xf"))
     if ramp is not None:
         from .dense_ref import DenseFastMPC
         var1 = model.get("var_order", 2) == 1
