@@ -1111,6 +1111,85 @@ int fmpc_dm_surface_device(int batch, int m, int rows, int cols, const double* x
                            const double* u, long long ldu, const double* phase, long long ldp,
                            double* out, long long ldo, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Atmosphere on the device: frozen-flow von Karman phase screens for a batch of realisations, the stage of the reference's
+ * pipeline at README.md:24-75 (OOMAO's layered atmosphere seen by one on-axis source; altitudes do not enter).  OOMAO draws from
+ * MATLAB's randn stream, so its samples cannot be reproduced; what is kept is what it is built on: the von Karman covariance of
+ * phaseStats.m:20-39 and the extrusion of telescopeAbstract.m:335-342, 864-884 (a new line of phase is A z + B xi).
+ *
+ * The process.  Each layer l of each realisation r holds a window of W x W samples on a square lattice of pitch p [m]; rows are y,
+ * columns x, both increasing with the index.  Layers share W, p, r0, L0 and the stencil; layer l has a fraction f_l (it multiplies
+ * the covariance as fractionnalR0 does; the fractions need not sum to 1) and a wind (vx_l, vy_l) = speed_l (cos dir_l, sin dir_l).
+ *   C(rho)     phaseStats.covariance for r0, L0 and a fraction of 1, evaluated on the host (fmpc_atm_covariance_host).
+ *   Extruder   of a stencil s_1 < .. < s_q (1 <= s_j <= W): the new line is the W points (0, i p), the conditioning points are the
+ *              q W points (-s_j p, i p), ordered j-major;  A = ZX' ZZ^-1 (W x q W),  B = chol_lower(XX - A ZX) (W x W), factored
+ *              in long double.  The covariance is isotropic: the same A, B serve rows, columns and both directions.
+ *   Extrusion  line = A z + sqrt(f_l) B xi;  z: the q window lines at distances s_j from the new one;
+ *              xi_i = g(seed, (l << 48) | e, first + r, i) with the draw g of the measurement noise above and e the number of
+ *              extrusions of that layer so far (the start-up's included).  The line at the far side is dropped.
+ *   Start-up   line 0 is sqrt(f_l) B_0 xi, B_0 = chol_lower(XX); line t >= 1 is extruded along x at column t from the columns
+ *              t - s_j with the extruder of the sub-stencil {s_j <= t}, until the window is full (e = W then).  No FFT, no burn-in.
+ *   Time       at step count k a layer is displaced by d = k * (v dt / p) pixels per axis, formed from k in double (the factor
+ *              speed * cos(dir) * dt / p, or sin, is formed once).  floor(|d|) lines have been extruded on that axis, the rest is
+ *              the fraction f in [0, 1) (fmpc_atm_displacement_host).  A step k -> k + 1 extrudes the missing lines on the upwind
+ *              side (index 0 for a positive component, W - 1 for a negative one): all x lines first, then all y lines.  The
+ *              content moves with the wind: phi_l(x, y, t) = phi_l(x - vx t, y - vy t, 0).
+ *   Output     out[r][i][j] = scale * (m_ij * (sum_l b_l(i, j) - mu_r)),  layers ascending.  The out_len x out_len grid spans
+ *              (W - 2) p: output index t of an axis lies at window coordinate c = fl(fl(t h) + s), h = (W - 2) / (out_len - 1),
+ *              s = 1 - f for a positive wind component and f otherwise; i0 = min(floor(c), W - 2), w = c - i0, and
+ *              b = (1 - wy) ((1 - wx) a00 + wx a01) + wy ((1 - wx) a10 + wx a11) over the four samples (i0, i0 + 1) x (j0, j0 + 1).
+ *              m: out_len^2 doubles of 0 / 1 (device) or NULL; mu_r: the mean of sum_l b_l over the mask, summed in a fixed order
+ *              (ngs.meanRmPhase), 0 without a mask or with an empty one.  out is batch x out_len x out_len row-major, the layout
+ *              fmpc_est_apply_device, fmpc_modal_fit_device and fmpc_dm_surface_device read.
+ *
+ * fmpc_atm_covariance_host   out[i] = C(rho[i]), rho >= 0.
+ * fmpc_atm_extruder_host     A (W x q W row-major) and B (W x W row-major, lower, zeros above) of one stencil; stencil = NULL: the
+ *                   default 1, 2, 4, .. (powers of two <= W - 1, at most 8; q is then ignored).  q = 0 with a stencil pointer:
+ *                   B = B_0 = chol_lower(XX), the first line of the start-up; A is not written and may be NULL.  Host only.
+ * fmpc_atm_displacement_host   lines = floor(|k px_per_step|), frac = the rest.
+ * fmpc_atm_create   an opaque handle that owns the operands, the windows and the counters.  layers arrays frac (>= 0), speed
+ *                   [m/s], dir [rad]; dt [s]; batch realisations with the global indices first .. first + batch - 1.  The
+ *                   extruders of every prefix of the stencil are built on the host (one long double Cholesky factor of ZZ serves
+ *                   them all) before the device is touched.  The windows are zero until fmpc_atm_reset_device.
+ * fmpc_atm_reset_device     the start-up of every window in one launch; k = 0.
+ * fmpc_atm_advance_device   k += steps, one launch per step that extrudes anything.
+ * fmpc_atm_screen_device    the output at the current k; it does not advance.  Without a mask one kernel; with one the masked
+ *                   partial sums first (the window samples are then gathered twice, out is written once).
+ * fmpc_atm_get_state / fmpc_atm_set_state   windows: DEVICE array [layer][r][i][j] of layers * batch * W * W doubles (NULL: the
+ *                   counters alone); k and counts[layers] (the e of each layer): HOST.  set_state leaves k >= 0 and counts as given.
+ * fmpc_atm_dims     any pointer may be NULL.
+ * The step count, the extrusion counts and the ring origins live in the handle on the host and travel in the kernel arguments, so
+ * a recorded graph replays the step it recorded.  No call synchronises and none allocates after fmpc_atm_create.  A realisation's
+ * bits do not depend on the batch, on its place in it, or on `first` for the same global index.
+ * Measured on one MI355X (scripts/atm_timing.py; the reference's atmosphere, W = 129, 8 lines, three layers, pupil mask, 20 steps
+ * per window, best of 3 rounds), batch 1 / 256 / 2000, one advance + screen: 0.85 / 0.88 / 1.62 ms at out_len 128, 1.14 / 1.68 /
+ * 7.95 ms at 512; the same arithmetic composed in torch 1.69 / 2.95 / 15.1 and 1.68 / 12.6 / 90.6 ms; the pinned host-to-device copy
+ * of the screens 0.012 / 0.60 / 4.58 and 0.049 / 9.37 / 73.2 ms -- the copy wins for one realisation and at (256, 128).  advance is
+ * latency-bound (about 0.09 ms per line of a layer, one after another; 0.80 ms for 3 workgroups, 0.97 ms for 375), screen is bound
+ * by its gathers (0.60 TB/s of stores at (2000, 512)).  fmpc_atm_create builds the operands in 1.3 s at W = 129 and in 108 s at
+ * W = 512 with 8 lines, the largest q W accepted.
+ * Answered before the device is touched: FMPC_E_NULL for a NULL handle, out, frac, speed, dir, rho, A, B; FMPC_E_DIM for W < 3, a
+ * pitch, r0, L0 that is not positive and finite, layers < 1, a negative or non-finite fraction, a non-finite speed, dir or dt,
+ * q < 1 with a stencil, a stencil not strictly ascending inside [1, W], batch < 0, first < 0, first + batch > 2^32, steps < 0,
+ * out_len < 2, k < 0; FMPC_E_UNSUPPORTED for q > 8, q W > 4096, more than 16 layers, more than 2^31 - 1 (layer, group of 16)
+ * pairs, a wind beyond 2^20 pixels per step, a displacement beyond 2^52 pixels, out_len > 65535, and a Cholesky factor of ZZ or
+ * of XX - A ZX that fails.  batch == 0 is FMPC_OK for every call.
+ */
+typedef struct fmpc_atm_s* fmpc_atm;
+int fmpc_atm_covariance_host(int n, const double* rho, double r0, double L0, double* out);
+int fmpc_atm_extruder_host(int W, double pitch, double r0, double L0, int q, const int* stencil, double* A, double* B);
+int fmpc_atm_displacement_host(long long k, double px_per_step, long long* lines, double* frac);
+int fmpc_atm_create(fmpc_atm* out, int W, double pitch, double r0, double L0, int layers, const double* frac,
+                    const double* speed, const double* dir, double dt, int q, const int* stencil, int batch,
+                    unsigned long long seed, long long first, int device);
+int fmpc_atm_destroy(fmpc_atm a);
+int fmpc_atm_dims(fmpc_atm a, int* W, int* layers, int* batch, int* q, long long* k);
+int fmpc_atm_reset_device(fmpc_atm a, void* stream);
+int fmpc_atm_advance_device(fmpc_atm a, long long steps, void* stream);
+int fmpc_atm_screen_device(fmpc_atm a, int out_len, const double* mask, double scale, double* out, void* stream);
+int fmpc_atm_get_state(fmpc_atm a, double* windows, long long* k, unsigned long long* counts, void* stream);
+int fmpc_atm_set_state(fmpc_atm a, const double* windows, long long k, const unsigned long long* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ from .var_identify import identify_var2_device, identify_var_device, validate_va
 from .estimator import PhaseDiversityEstimator, EstimatorNoise, normal_noise, normal_noise_host
 from .modal import ModalFit, modal_workspace_bytes
 from .dm import GaussianDM, dm_matrix_workspace_bytes, reference_dm_geometry, reference_dm
+from .atmosphere import Atmosphere, reference_atmosphere, atm_covariance, atm_extruder, atm_displacement, atm_default_stencil
 from . import optics
 from .optics import zernike_modes, zernike_basis, zernike_grid, EstimatorOptics, reference_optics
 from . import _lib
@@ -29,4 +30,4 @@ __all__ = ["optics", "zernike_modes", "zernike_basis", "zernike_grid", "Estimato
            "FMPC_KKT_FIELDS", "FMPC_KKT_RD", "FMPC_KKT_RP", "FMPC_KKT_NR", "FMPC_KKT_COST", "FMPC_KKT_BARRIER", "FMPC_KKT_MIN_SLACK",
            "FMPC_KKT_FIELD_NAMES", "FMPC_KKT_CONVERGED", "FMPC_KKT_INFEASIBLE", "ModalFit", "modal_workspace_bytes",
            "EstimatorNoise", "normal_noise", "normal_noise_host", "GaussianDM", "dm_matrix_workspace_bytes", "reference_dm_geometry",
-           "reference_dm"]
+           "reference_dm", "Atmosphere", "reference_atmosphere", "atm_covariance", "atm_extruder", "atm_displacement", "atm_default_stencil"]

@@ -146,6 +146,18 @@ SIGNATURES = {
     "fmpc_dm_matrix_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "fmpc_dm_matrix_device": (C.c_int, [C.c_int] * 4 + [_vp] * 6 + [C.c_double] * 2 + [C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp]),
     "fmpc_dm_surface_device": (C.c_int, [C.c_int] * 4 + [_vp] * 4 + [C.c_double] * 2 + [_vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _vp]),
+    "fmpc_atm_covariance_host": (C.c_int, [C.c_int, _vp, C.c_double, C.c_double, _vp]),
+    "fmpc_atm_extruder_host": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp]),
+    "fmpc_atm_displacement_host": (C.c_int, [C.c_longlong, C.c_double, C.POINTER(C.c_longlong), _dp]),
+    "fmpc_atm_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int, _vp,
+                                  C.c_int, C.c_ulonglong, C.c_longlong, C.c_int]),
+    "fmpc_atm_destroy": (C.c_int, [_vp]),
+    "fmpc_atm_dims": (C.c_int, [_vp, _ip, _ip, _ip, _ip, C.POINTER(C.c_longlong)]),
+    "fmpc_atm_reset_device": (C.c_int, [_vp, _vp]),
+    "fmpc_atm_advance_device": (C.c_int, [_vp, C.c_longlong, _vp]),
+    "fmpc_atm_screen_device": (C.c_int, [_vp, C.c_int, _vp, C.c_double, _vp, _vp]),
+    "fmpc_atm_get_state": (C.c_int, [_vp, _vp, C.POINTER(C.c_longlong), _vp, _vp]),
+    "fmpc_atm_set_state": (C.c_int, [_vp, _vp, C.c_longlong, _vp, _vp]),
 }
 
 _lib = None

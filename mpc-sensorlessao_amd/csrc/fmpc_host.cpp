@@ -4,8 +4,10 @@
 #include "fmpc_bank.h"
 #include "../../include/fastmpc.h"      // fmpc_noise, the status codes
 #include "fmpc_noise.h"
+#include "fmpc_atm.h"
 
 #include <algorithm>
+#include <cmath>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -1382,5 +1384,181 @@ extern "C" int fmpc_noise_normal_host(double* out, int batch, int p, long long l
     for (int r = 0; r < batch; ++r)
         for (int i = 0; i < p; ++i)
             out[(size_t)r * ld + i] = fmpc_noise_scaled(nz->value, fmpc_noise_normal(nz->seed, nz->step, (uint32_t)(nz->first + r), (uint32_t)i));
+    return FMPC_OK;
+}
+
+// ---- atmosphere: von Karman covariance (OOMAO phaseStats.m:20-39), the extruders A = ZX' ZZ^-1, B = chol(XX - A ZX)
+extern "C" int fmpc_atm_covariance_host(int n, const double* rho, double r0, double L0, double* out) {
+    if (!rho || !out) return FMPC_E_NULL;
+    if (n < 0 || !(r0 > 0.0) || !(L0 > 0.0) || !std::isfinite(r0) || !std::isfinite(L0)) return FMPC_E_DIM;
+    const double pi = 3.14159265358979323846;
+    const double ratio = pow(L0 / r0, 5.0 / 3.0), lead = pow(24.0 * tgamma(6.0 / 5.0) / 5.0, 5.0 / 6.0);
+    const double cst = lead * (tgamma(11.0 / 6.0) / (pow(2.0, 5.0 / 6.0) * pow(pi, 8.0 / 3.0))) * ratio;
+    const double var = lead * (tgamma(11.0 / 6.0) * tgamma(5.0 / 6.0) / (2.0 * pow(pi, 8.0 / 3.0))) * ratio;
+    for (int i = 0; i < n; ++i) {
+        if (!(rho[i] >= 0.0) || !std::isfinite(rho[i])) return FMPC_E_DIM;
+        const double u = 2.0 * pi * rho[i] / L0;
+        out[i] = u != 0.0 ? cst * pow(u, 5.0 / 6.0) * std::cyl_bessel_k(5.0 / 6.0, u) : var;
+    }
+    return FMPC_OK;
+}
+
+int fmpc_host_atm_check(int W, double pitch, double r0, double L0, int q, const int* stencil) {
+    if (W < 3 || !(pitch > 0.0) || !(r0 > 0.0) || !(L0 > 0.0) || !std::isfinite(pitch) || !std::isfinite(r0) || !std::isfinite(L0)) return FMPC_E_DIM;
+    if (q < 1) return FMPC_E_DIM;
+    for (int j = 0; j < q && j <= FMPC_ATM_MAXQ; ++j)
+        if (stencil[j] < 1 || stencil[j] > W || (j > 0 && stencil[j] <= stencil[j - 1])) return FMPC_E_DIM;
+    if (q > FMPC_ATM_MAXQ || (long long)q * W > FMPC_ATM_MAXK) return FMPC_E_UNSUPPORTED;
+    return FMPC_OK;
+}
+
+int fmpc_host_atm_default_stencil(int W, int* stencil) {
+    int q = 0;
+    for (int s = 1; s <= W - 1 && q < FMPC_ATM_MAXQ; s *= 2) stencil[q++] = s;
+    return q;
+}
+
+// lower Cholesky factor in place, rows packed (row r at r (r + 1) / 2); false when a pivot is not positive
+static bool atm_chol_packed(std::vector<long double>& L, int N) {
+    for (int r = 0; r < N; ++r) {
+        long double* lr = L.data() + (size_t)r * (r + 1) / 2;
+        for (int c = 0; c <= r; ++c) {
+            const long double* lc = L.data() + (size_t)c * (c + 1) / 2;
+            long double s = lr[c];
+            for (int k = 0; k < c; ++k) s -= lr[k] * lc[k];
+            if (c == r) {
+                if (!(s > 0.0L) || !std::isfinite((double)s)) return false;
+                lr[c] = sqrtl(s);
+            } else {
+                lr[c] = s / lc[c];
+            }
+        }
+    }
+    return true;
+}
+
+int fmpc_host_atm_extruders(int W, double pitch, double r0, double L0, int q, const int* stencil, bool all, FmpcAtmExtruders& out) {
+    const int N = q * W;
+    out.A.assign(q + 1, std::vector<double>());
+    out.B.assign(q + 1, std::vector<double>());
+    // C(pitch hypot(ds, di)) for every line distance ds that occurs: 0, s_a, s_b - s_a
+    std::vector<int> dss(1, 0);
+    for (int a = 0; a < q; ++a) {
+        dss.push_back(stencil[a]);
+        for (int b = a + 1; b < q; ++b) dss.push_back(stencil[b] - stencil[a]);
+    }
+    std::sort(dss.begin(), dss.end());
+    dss.erase(std::unique(dss.begin(), dss.end()), dss.end());
+    std::vector<std::vector<long double>> cov(dss.size(), std::vector<long double>(W));
+    {
+        std::vector<double> rho(W), c(W);
+        for (size_t d = 0; d < dss.size(); ++d) {
+            for (int i = 0; i < W; ++i) rho[i] = pitch * hypot((double)dss[d], (double)i);
+            if (fmpc_atm_covariance_host(W, rho.data(), r0, L0, c.data()) != FMPC_OK) return FMPC_E_UNSUPPORTED;
+            for (int i = 0; i < W; ++i) {
+                if (!std::isfinite(c[i])) return FMPC_E_UNSUPPORTED;
+                cov[d][i] = c[i];
+            }
+        }
+    }
+    auto C = [&](int ds, int di) -> long double {
+        ds = ds < 0 ? -ds : ds; di = di < 0 ? -di : di;
+        return cov[std::lower_bound(dss.begin(), dss.end(), ds) - dss.begin()][di];
+    };
+    // ZZ = L L'
+    std::vector<long double> L((size_t)N * (N + 1) / 2);
+    for (int a = 0; a < q; ++a)
+        for (int i = 0; i < W; ++i) {
+            long double* lr = L.data() + (size_t)(a * W + i) * (a * W + i + 1) / 2;
+            for (int b = 0; b <= a; ++b)
+                for (int k = 0; k < W && b * W + k <= a * W + i; ++k) lr[b * W + k] = C(stencil[a] - stencil[b], i - k);
+        }
+    if (!atm_chol_packed(L, N)) return FMPC_E_UNSUPPORTED;
+    // Y = L^-1 ZX, one right-hand side per point of the new line (stored by right-hand side)
+    std::vector<long double> Y((size_t)W * N);
+    for (int w = 0; w < W; ++w) {
+        long double* y = Y.data() + (size_t)w * N;
+        for (int r = 0; r < N; ++r) {
+            const long double* lr = L.data() + (size_t)r * (r + 1) / 2;
+            long double s = C(stencil[r / W], r % W - w);
+            for (int k = 0; k < r; ++k) s -= lr[k] * y[k];
+            y[r] = s / lr[r];
+        }
+    }
+    std::vector<long double> a(N), S((size_t)W * (W + 1) / 2);
+    for (int j = all ? 0 : q; j <= q; ++j) {
+        const int Nj = j * W;
+        // A_j: row w solves L_j' a = y_w
+        out.A[j].assign((size_t)W * Nj, 0.0);
+        for (int w = 0; w < W; ++w) {
+            for (int r = 0; r < Nj; ++r) a[r] = Y[(size_t)w * N + r];
+            for (int r = Nj - 1; r >= 0; --r) {
+                const long double* lr = L.data() + (size_t)r * (r + 1) / 2;
+                a[r] /= lr[r];
+                for (int k = 0; k < r; ++k) a[k] -= lr[k] * a[r];
+            }
+            for (int r = 0; r < Nj; ++r) out.A[j][(size_t)w * Nj + r] = (double)a[r];
+        }
+        // B_j = chol(XX - A_j ZX_j) = chol(XX - Y_j' Y_j)
+        for (int w = 0; w < W; ++w)
+            for (int v = 0; v <= w; ++v) {
+                long double s = C(0, w - v);
+                const long double *yw = Y.data() + (size_t)w * N, *yv = Y.data() + (size_t)v * N;
+                for (int r = 0; r < Nj; ++r) s -= yw[r] * yv[r];
+                S[(size_t)w * (w + 1) / 2 + v] = s;
+            }
+        if (!atm_chol_packed(S, W)) return FMPC_E_UNSUPPORTED;
+        out.B[j].assign((size_t)W * W, 0.0);
+        for (int w = 0; w < W; ++w)
+            for (int v = 0; v <= w; ++v) out.B[j][(size_t)w * W + v] = (double)S[(size_t)w * (w + 1) / 2 + v];
+    }
+    return FMPC_OK;
+}
+
+void fmpc_host_atm_images(int W, int q, const FmpcAtmExtruders& X, std::vector<double>& img, unsigned long long* off) {
+    const int Wp4 = fmpc_atm_wp4(W), NT = fmpc_atm_tiles(W);
+    size_t total = 0;
+    for (int j = 0; j <= q; ++j) { off[j] = total; total += fmpc_atm_img_doubles(W, j); }
+    img.assign(total, 0.0);
+    for (int j = 0; j <= q; ++j) {
+        const int KS = (j + 1) * (Wp4 / 4);
+        for (int tile = 0; tile < NT; ++tile)
+            for (int ks = 0; ks < KS; ++ks)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int row = 16 * tile + (lane & 15), kk = 4 * ks + (lane >> 4), part = kk / Wp4, i = kk % Wp4;
+                    if (row >= W || i >= W) continue;
+                    img[off[j] + ((size_t)tile * KS + ks) * 64 + lane] =
+                        part < j ? X.A[j][(size_t)row * (j * W) + (size_t)part * W + i] : X.B[j][(size_t)row * W + i];
+                }
+    }
+}
+
+extern "C" int fmpc_atm_extruder_host(int W, double pitch, double r0, double L0, int q, const int* stencil, double* A, double* B) {
+    const bool first_line = stencil && q == 0;            // B_0 = chol(XX) of the start-up's first line: no A
+    if (!B || (!A && !first_line)) return FMPC_E_NULL;
+    int def[FMPC_ATM_MAXQ], one = 1;
+    if (!stencil) {
+        if (W < 3) return FMPC_E_DIM;
+        q = fmpc_host_atm_default_stencil(W, def);
+        stencil = def;
+    }
+    const int rc = first_line ? fmpc_host_atm_check(W, pitch, r0, L0, 1, &one) : fmpc_host_atm_check(W, pitch, r0, L0, q, stencil);
+    if (rc != FMPC_OK) return rc;
+    FmpcAtmExtruders X;
+    const int rb = fmpc_host_atm_extruders(W, pitch, r0, L0, q, stencil, false, X);
+    if (rb != FMPC_OK) return rb;
+    if (!first_line) memcpy(A, X.A[q].data(), X.A[q].size() * sizeof(double));
+    memcpy(B, X.B[q].data(), X.B[q].size() * sizeof(double));
+    return FMPC_OK;
+}
+
+extern "C" int fmpc_atm_displacement_host(long long k, double px_per_step, long long* lines, double* frac) {
+    if (!lines || !frac) return FMPC_E_NULL;
+    if (k < 0 || !std::isfinite(px_per_step)) return FMPC_E_DIM;
+    const double d = fabs((double)k * px_per_step);
+    if (!(d < 4503599627370496.0)) return FMPC_E_UNSUPPORTED;         // 2^52: beyond it a double holds no fraction
+    const double n = floor(d);
+    *lines = (long long)n;
+    *frac = d - n;
     return FMPC_OK;
 }

@@ -265,3 +265,17 @@ int fmpc_host_zernike_modes(int N, int* n_out, int* m_out);
 // The factorial quotients of zernfun.m:166-170 for every (n, |m|) with n <= 14: R_n^|m|(r) = sum_s coef[off[n][|m| / 2] + s]
 // r^(n - 2 s), s = 0 .. (n - |m|) / 2.  Every coefficient is an integer below 2^53: exact.
 void fmpc_host_zernike_coefficients(double coef[FMPC_ZERNIKE_NCOEF], unsigned short off[FMPC_ZERNIKE_MAXN + 1][8]);
+
+// ---- atmosphere (include/fastmpc.h: fmpc_atm; layouts: fmpc_atm.h)
+// The argument rules of a window and a stencil: FMPC_E_DIM for W < 3, a pitch, r0 or L0 that is not positive and finite, q < 1, a
+// stencil that is not strictly ascending inside [1, W]; FMPC_E_UNSUPPORTED for q > 8 or q W > 4096.
+int fmpc_host_atm_check(int W, double pitch, double r0, double L0, int q, const int* stencil);
+// The default stencil 1, 2, 4, .. (powers of two <= W - 1, at most 8 of them); returns q.
+int fmpc_host_atm_default_stencil(int W, int* stencil);
+// The extruders of the prefixes of a stencil, factored in long double: A[j] (W x j W row-major; empty for j = 0) and B[j] (W x W,
+// lower, zeros above the diagonal) of the first j lines, j = 0 .. q -- or, with all = false, j = q alone (the others stay empty).
+// One Cholesky factor of ZZ serves every prefix: ZZ of a prefix is a leading block.  FMPC_E_UNSUPPORTED when a factor fails.
+struct FmpcAtmExtruders { std::vector<std::vector<double>> A, B; };
+int fmpc_host_atm_extruders(int W, double pitch, double r0, double L0, int q, const int* stencil, bool all, FmpcAtmExtruders& out);
+// The operand images of fmpc_atm.h for j = 0 .. q, back to back; off[j]: where image j starts.
+void fmpc_host_atm_images(int W, int q, const FmpcAtmExtruders& X, std::vector<double>& img, unsigned long long* off);
