@@ -56,15 +56,15 @@ def closed_loop(model, a, n_newton=1, k=1e-2, nu0=None, ramp=None):
         class _Dense:
             def solve(self, x0, x0_pre, w, nw, kk, nu0=None):
                 info = {}
-                nu = np.zeros(T * n) if nu0 is None else nu0
+                nu = np.zeros((T + (1 if model.get("xf") is not None else 0)) * n) if nu0 is None else nu0
                 if var1:
-                    d = DenseFastMPC.var1(model["Q"], model["R"], None, model["Qf"], None, None, None, model["x_min"],
+                    d = DenseFastMPC.var1(model["Q"], model["R"], None, model["Qf"], model.get("q"), model.get("r"), model.get("qf"), model["x_min"],
                                           model["x_max"], model["u_min"], model["u_max"], ramp[0], ramp[1], T, x0, self.u_prev,
-                                          A1, B, w, None, None, ramp=True)
+                                          A1, B, w, model.get("xf"), None, ramp=True)
                 else:
-                    d = DenseFastMPC(model["Q"], model["R"], None, model["Qf"], None, None, None, model["x_min"],
+                    d = DenseFastMPC(model["Q"], model["R"], None, model["Qf"], model.get("q"), model.get("r"), model.get("qf"), model["x_min"],
                                      model["x_max"], model["u_min"], model["u_max"], ramp[0], ramp[1], T, x0, x0_pre,
-                                     self.u_prev, A1, A2, B, w, None, None, ramp=True)
+                                     self.u_prev, A1, A2, B, w, model.get("xf"), None, ramp=True)
                 z = d.mpc_fixed_log_newton(nw, kk, nu0=nu, info=info)
                 return z, info["nu"], info["iters"], 0
         solver = _Dense()
