@@ -52,6 +52,35 @@ CASES = [
 ]
 
 
+def one_extrusion(atm, ref, st):
+    """Both sides load the state `st`, take one step and are compared; `ref` is the long double restatement of `atm`."""
+    k0 = st["k"]
+    ref.load_state(st)
+    atm.load_state(st)
+    got0 = _dev_state(atm)
+    assert np.array_equal(got0["windows"], st["windows"]) and got0["k"] == k0 and got0["counts"] == list(st["counts"])
+    ref.clear_tol()
+    ref.advance(1)
+    atm.advance(1)
+    got = _dev_state(atm)
+    assert got["k"] == k0 + 1 and got["counts"] == ref.e
+    new, worst = 0, 0.0
+    for l in range(ref.layers):
+        want, tol = ref.win[l], ref.tol[l]
+        old = tol == 0
+        assert np.array_equal(got["windows"][l][old], np.asarray(want, dtype=np.float64)[old])
+        err = np.abs(got["windows"][l].astype(np.longdouble) - want)
+        assert np.all(err <= tol), float((err - tol).max())
+        if (~old).any():
+            worst = max(worst, float((err[~old] / tol[~old].clip(1e-300)).max()))
+        new += int((~old).sum())
+        nx, ny = (ar.displacement(k0 + 1, v)[0] - ar.displacement(k0, v)[0] for v in (ref.vpx[l], ref.vpy[l]))
+        assert nx <= 1 and ny <= 1 and int((~old[0]).sum()) == (nx + ny) * ref.W - nx * ny
+    assert new > 0
+    print(f"atm W={ref.W} layers={ref.layers} one extrusion: worst error / bound {worst:.3f}")
+    return got
+
+
 @pytest.mark.parametrize("W,stencil,winds,frac,batch,k0", CASES)
 def test_one_extrusion_per_axis_against_long_double(pkg, gpu, W, stencil, winds, frac, batch, k0):
     """set_state from the restatement's start-up, one step, get_state: a new line entry lies within (q + 1) W 2^-52 (sum |A||z| +
@@ -61,26 +90,7 @@ def test_one_extrusion_per_axis_against_long_double(pkg, gpu, W, stencil, winds,
     ref.reset()
     st = ref.state()
     st["k"] = k0
-    ref.load_state(st)
-    atm.load_state(st)
-    got0 = _dev_state(atm)
-    assert np.array_equal(got0["windows"], st["windows"]) and got0["k"] == k0 and got0["counts"] == st["counts"]
-    ref.clear_tol()
-    ref.advance(1)
-    atm.advance(1)
-    got = _dev_state(atm)
-    assert got["k"] == k0 + 1 and got["counts"] == ref.e
-    new = 0
-    for l in range(len(winds)):
-        want, tol = ref.win[l], ref.tol[l]
-        old = tol == 0
-        assert np.array_equal(got["windows"][l][old], np.asarray(want, dtype=np.float64)[old])
-        err = np.abs(got["windows"][l].astype(np.longdouble) - want)
-        assert np.all(err <= tol), float((err - tol).max())
-        new += int((~old).sum())
-        nx, ny = (ar.displacement(k0 + 1, v)[0] - ar.displacement(k0, v)[0] for v in (ref.vpx[l], ref.vpy[l]))
-        assert nx <= 1 and ny <= 1 and int((~old[0]).sum()) == (nx + ny) * W - nx * ny
-    assert new > 0
+    one_extrusion(atm, ref, st)
     atm.close()
 
 
@@ -88,6 +98,10 @@ RUNS = [
     (18, [1, 2, 17], [(0.3, -2.6), (-1.0, 0.3), (0.0, 0.0)], [0.5, 0.3, 0.2], 17),
     (33, None, [(2.6, 1.0), (-0.3, -1.0), (-2.6, 0.3)], [0.028, 0.004, 0.008], 40),
     (129, None, [(1.0, -2.6)], [0.04], 1),
+    # more than twelve row tiles, so that a wavefront takes a second pass over the operands: 14 tiles with W % 4 = 1 and a far
+    # line whose gather wraps the ring, 16 full tiles
+    (209, [1, 2, 208], [(2.6, -1.0), (-1.0, 2.6)], [0.6, 0.4], 3),
+    (256, [1, 2, 255], [(-1.0, -2.6), (2.6, -1.0)], [0.6, 0.4], 3),
 ]
 
 
@@ -101,10 +115,12 @@ def test_start_up_and_forty_steps_against_the_restatement(pkg, gpu, W, stencil, 
         W = 18, 3 layers, 17 realisations:   8.1e-14, 1.3e-13 / 1.8e-13, 8.8e-13   (window rms 14 rad)
         W = 33, 3 layers, 40 realisations:   5.2e-14, 1.2e-13 / 7.1e-14, 2.4e-13   (rms 2.9)
         W = 129, 1 layer, 1 realisation:     6.4e-14, 2.8e-13 / 1.0e-13, 3.2e-13   (rms 4.6; 8 steps)
-    i.e. the device at 1.6 to 4.8 times the spread."""
-    steps = 40 if W < 129 else 8                           # (W = 129 is there for the nine tiles of a line, not for the length)
+        W = 209, 2 layers, 3 realisations:   5.9e-13, 1.1e-12 / 5.3e-13, 1.1e-12   (rms 13.8; 8 steps; lines 1, 2, 208)
+        W = 256, 2 layers, 3 realisations:   9.7e-13, 1.5e-12 / 1.0e-12, 1.5e-12   (rms 13.4; 8 steps; lines 1, 2, 255)
+    i.e. the device at 1.5 to 4.8 times the spread."""
+    steps = 40 if W < 129 else 8                           # (W >= 129 is there for the tiles of a line, not for the length)
     atm, ld = _pair(pkg, W, stencil, winds, frac, batch)
-    _, rv = _pair(pkg, W, stencil, winds, frac, batch, dtype=np.float64, reverse=True, ref=True)
+    rv = ar.AtmRef(W, ld.s, ld.ext, frac, ld.vpx, ld.vpy, batch, ld.xi, dtype=np.float64, reverse=True)
     atm.reset()
     ld.reset(); rv.reset()
     for stage in ("start-up", "run"):
@@ -125,6 +141,34 @@ def _disk(n):
     return (x[:, None] ** 2 + x[None, :] ** 2 <= 1.0).astype(np.float64)
 
 
+def screens_against_the_restatement(atm, ref, sizes, masks=(None, "disk")):
+    """The screens of `atm` at every out_len of `sizes` and every mask (None, "disk" or an array) against `ref`, the long double
+    restatement that holds the device's own windows; the bound of test_output_against_the_restatement.  Returns the worst error
+    over bound."""
+    import torch
+    layers, worst = ref.layers, 0.0
+    for n in sizes:
+        for mask in masks:
+            mask = _disk(n) if isinstance(mask, str) else mask
+            got = atm.screen(n, mask=mask)
+            got4 = atm.screen(n, mask=mask, scale=4.0)
+            torch.cuda.synchronize()
+            got, got4 = got.cpu().numpy(), got4.cpu().numpy()
+            want, ab, S = ref.screen(n, mask=mask, want_abs=True)
+            tol = (8 + layers) * EPS * ab
+            if mask is not None:
+                cnt = mask.sum()
+                tol = tol + cnt * EPS * (np.abs(np.asarray(S, dtype=np.float64)) * mask).sum(axis=(1, 2))[:, None, None] / max(cnt, 1.0)
+                assert np.all(got[:, mask == 0] == 0.0)
+            err = np.abs(got.astype(np.longdouble) - want)
+            assert np.all(err <= tol), (n, mask is not None, float((err / tol.clip(1e-300)).max()))
+            assert np.array_equal(got4, 4.0 * got)
+            if mask is None or mask.sum() > 1:               # (a mask of no pixel or of one gives zeros everywhere)
+                assert np.abs(got).max() > 0
+            worst = max(worst, float((err / tol.clip(1e-300)).max()))
+    return worst
+
+
 @pytest.mark.parametrize("W,stencil,winds,frac,batch,steps", [
     (18, [1, 2], [(0.3, -2.6), (-1.0, 0.3), (0.0, 0.0)], [0.5, 0.3, 0.2], 17, 3),
     (33, None, [(2.6, 1.0)], [1.0], 40, 2),
@@ -135,34 +179,17 @@ def test_output_against_the_restatement(pkg, gpu, W, stencil, winds, frac, batch
     2^-52 sum_l |four samples| -- three products and sums per layer with weights in [0, 1], the layer sum, the mean's
     subtraction and the scale -- plus, with a mask, npix_mask 2^-52 mean|phi| for the mean's sum; masked pixels are exactly
     zero; a power-of-two scale is exact."""
-    import torch
     atm, ref = _pair(pkg, W, stencil, winds, frac, batch, dtype=np.longdouble)
     atm.reset().advance(steps)
-    st = _dev_state(atm)
-    ref.load_state(st)
-    layers = len(winds)
-    for n in (W - 1, 20, 64):
-        for mask in (None, _disk(n)):
-            got = atm.screen(n, mask=mask)
-            got4 = atm.screen(n, mask=mask, scale=4.0)
-            torch.cuda.synchronize()
-            got, got4 = got.cpu().numpy(), got4.cpu().numpy()
-            want, ab, S = ref.screen(n, mask=mask, want_abs=True)
-            tol = (8 + layers) * EPS * ab
-            if mask is not None:
-                cnt = mask.sum()
-                tol = tol + cnt * EPS * (np.abs(np.asarray(S, dtype=np.float64)) * mask).sum(axis=(1, 2))[:, None, None] / cnt
-                assert np.all(got[:, mask == 0] == 0.0)
-            err = np.abs(got.astype(np.longdouble) - want)
-            assert np.all(err <= tol), (n, mask is not None, float((err / tol.clip(1e-300)).max()))
-            assert np.array_equal(got4, 4.0 * got)
-            assert np.abs(got).max() > 0
+    ref.load_state(_dev_state(atm))
+    screens_against_the_restatement(atm, ref, (W - 1, 20, 64))
     atm.close()
 
 
 def test_a_realisation_does_not_depend_on_the_batch_or_on_first(pkg, gpu):
     """Screens of the realisations with the global indices 5 .. 44: in a batch of 40, alone, and in a batch whose `first` differs
-    (so that they sit in other columns of other groups) -- the same bits; another seed gives other screens."""
+    (so that they sit in other columns of other groups), and in batches of exactly one and two groups of 16 -- the same bits;
+    another seed gives other screens."""
     import torch
     W, winds, frac = 33, [(2.6, 1.0), (-0.3, -1.0), (-2.6, 0.3)], [0.028, 0.004, 0.008]
     mask = _disk(20)
@@ -180,6 +207,8 @@ def test_a_realisation_does_not_depend_on_the_batch_or_on_first(pkg, gpu):
     assert np.array_equal(run(1, 5 + 23)[:, 0], a[:, 23])
     b = run(17, 2)                                           # global 5 is column 3 there
     assert np.array_equal(b[:, 3:], a[:, :14])
+    for full in (16, 32):                                    # whole groups of 16: no column of the last group is idle
+        assert np.array_equal(run(full, 5), a[:, :full])
     c = run(40, 5, seed=12)
     assert not np.array_equal(c, a) and np.abs(c - a).max() > 1e-3
 
