@@ -987,6 +987,67 @@ int fmpc_est_snr_sigma(fmpc_est e, double snr_db, double* sigma);
 int fmpc_philox4x32_10(const unsigned int counter[4], const unsigned int key[2], unsigned int out[4]);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
+ * Photon and read-out noise of a detector, drawn on the device.  What a camera does to a PSF window: the variance of a
+ * photo-electron count follows the signal, and a read-out noise that does not depend on it comes on top.  OOMAO's detector.m:315-321:
+ *     image = poissrnd(image + nPhotonBackground) - nPhotonBackground;  image = quantumEfficiency*image;
+ *     image = image + randn(size(image)).*readOutNoise;
+ *
+ * The model   for realisation r and measurement i of a call, Y0 the noise-free Y_M of fmpc_est_apply_device (or the array given):
+ *              lam = gain_r Y0[r][i] + background                       expected photo-electrons
+ *              N   = photon_noise ? K(seed, step, first + r, i; lam) : lam           K ~ Poisson(lam)
+ *              e   = qe (N - background) + read_noise g(seed, step, first + r, i)    g: the normal draw above, the same counter
+ *              Y_M[r][i] = e / gain_r                                   back in the units of A_s, b_s
+ *            Each product, sum and quotient is rounded once, in the order written: gain_r Y0, + background; N - background,
+ *            qe x that, read_noise x g, their sum, / gain_r.  read_noise == 0 draws no g.  With photon_noise = 0, background = 0,
+ *            qe = 1, gain = 1 this is FMPC_NOISE_SIGMA with sigma = read_noise, bit for bit.  qe is applied as OOMAO applies it: it
+ *            SCALES the image (E[Y_M] = qe Y0), so a caller who wants an unbiased estimate folds it into the gain (gain qe
+ *            photo-electrons per unit, qe = 1).
+ *            gain_r: photo-electrons per unit of Y_M: `gain`, or gain_dev[r] (device, batch doubles) when gain_dev != NULL.
+ *            qe > 0, background >= 0, read_noise >= 0 [electrons rms], finite.  seed, step, step_dev, first: as in fmpc_noise.
+ * Domain     lam < 0, non-finite or > 2^31 makes that measurement NaN, with or without photon noise (so does a gain_dev[r] that
+ *            is negative or not finite; gain_dev[r] == 0 divides by zero).  Y0 of the estimator is never negative; the stand-alone
+ *            calls take any array.  At the top of the range K's acceptance test rounds k ln(lam) at 2^-53 of its size: 8e-6
+ *            absolute at lam = 2^31, 2e-9 at 10^6 -- a relative error of that size on a probability.
+ * The draw K   a pure function of (seed, step, R, i, lam), exact in law on 0 <= lam <= 2^31, the same bits on host and device: it
+ *            uses +, -, x, /, sqrt, integer and bit operations only (its own exp and ln, csrc/fmpc_detector.h).
+ *              Uniforms: attempt a = 0, 1, .. takes the Philox4x32-10 block with key = (seed low 32, seed high 32) and counter =
+ *              (i | (a + 1) << 24, R, step low 32, step high 32), u1 and u2 built from x0 .. x3 as for g.  The detector calls
+ *              require p <= 2^24; the normal draw's counter word 0 is i >> 1 < 2^23 there, so no block serves both draws: the
+ *              photon noise and the read-out noise of a measurement are independent.
+ *              lam < 10: inversion by sequential search on u1 of attempt 0, K = the smallest k with u1 <= sum_{j<=k} t_j, t_0 =
+ *              exp(-lam), t_k = t_{k-1} lam / k; the search also stops at the first t_k < 2^-64 (probability < 2^-49) and within
+ *              128 steps.
+ *              lam >= 10: Hoermann's transformed rejection PTRS (1993) with b = 0.931 + 2.53 sqrt(lam), a = -0.059 + 0.02483 b,
+ *              1/alpha = 1.1239 + 1.1328 / (b - 3.4), v_r = 0.9277 - 3.6224 / (b - 2); per attempt U = u1 - 1/2, V = u2, us =
+ *              1/2 - |U|, k = floor((2 a / us + b) U + lam + 0.43); accept if us >= 0.07 and V <= v_r; reject if k < 0 or (us <
+ *              0.013 and V > us); else accept iff ln V + ln(1/alpha) - ln(a / us^2 + b) <= -lam + k ln lam - ln k!  (ln k!: table
+ *              below 16, Stirling's series to 1/k^7 above).  An attempt is accepted with probability >= 0.75; after 64 attempts
+ *              (probability < 1e-38) K = floor(lam + 1/2).
+ * fmpc_est_apply_detector_device   fmpc_est_apply_noisy_device with this model; scrn, ad_est, Y_out (NULL allowed) as there.  No
+ *            batch x p array of noise exists.  It does not synchronise and, once the handle's workspace has served a batch of
+ *            this size, does not allocate: it can be recorded into a graph, and step_dev makes every replay draw afresh.
+ * fmpc_detector_read_device / _host   Y[r ld + i] = the model applied to Y0[r ld + i], r < batch, i < p <= 2^24; Y == Y0 is
+ *            allowed; ld >= p (0 = p), the padding is neither read nor written.  The host form reads no device pointer: gain_dev and
+ *            step_dev must be NULL.  With gain = 1, qe = 1, background = 0, read_noise = 0 they return K(lam = Y0) itself.
+ * fmpc_est_photon_gain   host: *gain = n_photons ndiv / sum_i b_s[i]: with it the unaberrated system puts n_photons
+ *            photo-electrons, on average, into one diversity's window.  FMPC_E_DIM if the sum is not positive or n_photons is not
+ *            positive and finite.
+ * Errors, all found before the device is touched: FMPC_E_NULL for a NULL e, det, scrn, ad_est, Y, Y0 / gain; FMPC_E_DIM for
+ * batch < 0, first < 0, first + batch > 2^32, p < 1, p > 2^24, ld < p, a negative or non-finite gain, background or read_noise,
+ * qe <= 0 or non-finite, gain == 0 without gain_dev.  batch == 0 is FMPC_OK.
+ */
+typedef struct fmpc_detector_s {
+    double gain; const double* gain_dev;
+    double qe, background, read_noise; int photon_noise;
+    unsigned long long seed, step; const unsigned long long* step_dev; long long first;
+} fmpc_detector;
+int fmpc_est_apply_detector_device(fmpc_est e, int batch, const double* scrn, const fmpc_detector* det,
+                                   double* ad_est, double* Y_out, void* stream);
+int fmpc_detector_read_device(double* Y, const double* Y0, int batch, int p, long long ld, const fmpc_detector* det, void* stream);
+int fmpc_detector_read_host(double* Y, const double* Y0, int batch, int p, long long ld, const fmpc_detector* det);
+int fmpc_est_photon_gain(fmpc_est e, double n_photons, double* gain);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
  * Zernike functions on the device: the reference's zernfun.m, in the mode order of zernmodfit.m:195-198 (Zs.mat, which the
  * reference loads at README.md:266, is not shipped: these calls rebuild it).
  *

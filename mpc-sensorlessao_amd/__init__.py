@@ -16,7 +16,7 @@ from .lanes import SolveLanes
 from .records import LoopRecords
 from .recorded import RecordedSolves
 from .var_identify import identify_var2_device, identify_var_device, validate_var_device, var_fit_workspace_bytes
-from .estimator import PhaseDiversityEstimator, EstimatorNoise, normal_noise, normal_noise_host
+from .estimator import PhaseDiversityEstimator, EstimatorNoise, normal_noise, normal_noise_host, DetectorNoise, detector_read, detector_read_host
 from .modal import ModalFit, modal_workspace_bytes
 from .dm import GaussianDM, dm_matrix_workspace_bytes, reference_dm_geometry, reference_dm
 from .atmosphere import Atmosphere, reference_atmosphere, atm_covariance, atm_extruder, atm_displacement, atm_default_stencil
@@ -29,5 +29,5 @@ __all__ = ["optics", "zernike_modes", "zernike_basis", "zernike_grid", "Estimato
            "identify_var2_device", "identify_var_device", "validate_var_device", "var_fit_workspace_bytes", "LoopRecords",
            "FMPC_KKT_FIELDS", "FMPC_KKT_RD", "FMPC_KKT_RP", "FMPC_KKT_NR", "FMPC_KKT_COST", "FMPC_KKT_BARRIER", "FMPC_KKT_MIN_SLACK",
            "FMPC_KKT_FIELD_NAMES", "FMPC_KKT_CONVERGED", "FMPC_KKT_INFEASIBLE", "ModalFit", "modal_workspace_bytes",
-           "EstimatorNoise", "normal_noise", "normal_noise_host", "GaussianDM", "dm_matrix_workspace_bytes", "reference_dm_geometry",
+           "EstimatorNoise", "normal_noise", "normal_noise_host", "DetectorNoise", "detector_read", "detector_read_host", "GaussianDM", "dm_matrix_workspace_bytes", "reference_dm_geometry",
            "reference_dm", "Atmosphere", "reference_atmosphere", "atm_covariance", "atm_extruder", "atm_displacement", "atm_default_stencil"]

@@ -55,6 +55,12 @@ class Noise(C.Structure):
                 ("step_dev", _vp), ("first", C.c_longlong)]
 
 
+# fmpc_detector: the block of fmpc_est_apply_detector_device / fmpc_detector_read_*
+class Detector(C.Structure):
+    _fields_ = [("gain", C.c_double), ("gain_dev", _vp), ("qe", C.c_double), ("background", C.c_double), ("read_noise", C.c_double),
+                ("photon_noise", C.c_int), ("seed", C.c_ulonglong), ("step", C.c_ulonglong), ("step_dev", _vp), ("first", C.c_longlong)]
+
+
 # name -> (restype, argtypes); every symbol include/fastmpc.h declares
 SIGNATURES = {
     "fmpc_version": (C.c_int, []),
@@ -131,6 +137,10 @@ SIGNATURES = {
     "fmpc_noise_normal_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_longlong, C.POINTER(Noise)]),
     "fmpc_est_snr_sigma": (C.c_int, [_vp, C.c_double, _dp]),
     "fmpc_philox4x32_10": (C.c_int, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "fmpc_est_apply_detector_device": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(Detector), _vp, _vp, _vp]),
+    "fmpc_detector_read_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.POINTER(Detector), _vp]),
+    "fmpc_detector_read_host": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.POINTER(Detector)]),
+    "fmpc_est_photon_gain": (C.c_int, [_vp, C.c_double, _dp]),
     "fmpc_modal_workspace_bytes": (C.c_size_t, [C.c_int, C.c_longlong, C.c_int]),
     "fmpc_modal_factor_device": (C.c_int, [C.c_int, C.c_longlong, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fmpc_modal_fit_device": (C.c_int, [C.c_int, C.c_longlong, C.c_int, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp]),

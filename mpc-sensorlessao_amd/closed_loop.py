@@ -236,8 +236,8 @@ class AOLoop:
     def step(self, phase_k, noise=None, colmajor=False):
         """phase_k: (batch, len, len) float64 HIP tensor indexed [b, row, column] (phase_valid(:,:,k) of every realisation);
         colmajor=True: indexed [b, column, row] already -- the order MATLAB keeps phase_valid(:,:,k) in -- and no copy is made.
-        noise: None, the (batch, p) tensor Y_M_noise of this step, or an `EstimatorNoise` that is drawn on the device with
-        `steps_done` as its step (README.md:473-475).
+        noise: None, the (batch, p) tensor Y_M_noise of this step, or an `EstimatorNoise` / a `DetectorNoise` that is drawn on the
+        device with `steps_done` as its step (README.md:473-475).
         Returns (u[k] (batch, m), ad_est (batch, n)); both views valid until two further steps / the next step."""
         torch, C = self._torch, self._C
         s = self.steps_done

@@ -21,6 +21,7 @@ extern "C" int fmpc_est_create(fmpc_est* out, int len, int first, int d, int ndi
     if (!e) return FMPC_E_ALLOC;
     e->device = device; e->len = len; e->d = d; e->first = first; e->ndiv = ndiv; e->nx = nx; e->p = p; e->scale = scale;
     e->bs_power = fmpc_host_mean_square(b_s, p);
+    e->bs_sum = fmpc_host_sum(b_s, p);
     std::vector<double> G, Fimg;
     e->rank = fmpc_host_estimator_gain(A_s, p, nx, G);
     fmpc_host_estimator_dft_images(len, d, first, Fimg);

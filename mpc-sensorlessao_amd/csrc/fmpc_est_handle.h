@@ -11,6 +11,7 @@ struct fmpc_est_s {
     int device, len, d, first, ndiv, nx, p, rank;
     double scale;
     double bs_power;                     // mean(b_s^2): the power of the unaberrated image (fmpc_est_snr_sigma)
+    double bs_sum;                       // sum(b_s): what the unaberrated system puts into its windows (fmpc_est_photon_gain)
     DevBuf<double> pool;                 // D_re | D_im | Fimg | G | b_s
     size_t oDre, oDim, oF, oG, ob;
     DevBuf<int> qlist;                   // [len / 16][2]: range of the k-steps inside the pupil per row block

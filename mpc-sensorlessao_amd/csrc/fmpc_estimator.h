@@ -29,10 +29,16 @@ struct FeParams {
     double* nz_power = nullptr;         // SNR: [batch][ndiv][nshare] partial sums of Y0^2
     double* nz_sigma = nullptr;         // SNR: [batch] sigma_r, left by the combine pass for the pass over Y_out
     double* sigma_out = nullptr;        // [batch] or NULL
+    // ---- detector form (fmpc_est_apply_detector_device; fmpc_detector.h): seed, step, first and the counter are the nz_* ones
+    double det_gain = 1.0;              // photo-electrons per unit of Y_M of every realisation (det_gain_dev == NULL)
+    const double* det_gain_dev = nullptr;               // [batch] or NULL
+    double det_qe = 1.0, det_background = 0.0, det_read_noise = 0.0;
+    int det_photon = 0;
 };
 #define FE_NZ_OFF   0
 #define FE_NZ_SIGMA 1                   // Y_M += fl(sigma_r g) inside the finish pass
 #define FE_NZ_SNR   2                   // sigma_r from the power of this call's noise-free Y_M: shares of G g, then the combine pass
+#define FE_NZ_DET   3                   // Y_M = fmpc_detector_read(Y0): photon and read-out noise inside the finish pass
 
 #define FE_SPLIT_MAX 12                 // (screens x diversities) up to which the PSF kernel splits the columns of a row block in two
 
@@ -66,6 +72,15 @@ struct FnParams {
     unsigned long long seed, step, first; const unsigned long long* step_dev;
 };
 hipError_t fmpc_launch_noise_fill(const FnParams& P, hipStream_t stream);
+
+// The stand-alone detector (fmpc_kernel_detector.hip): Y[r ld + i] = fmpc_detector_read(Y0[r ld + i]; gain_r, ..), i < p; Y == Y0 allowed.
+struct FdParams {
+    double* Y; const double* Y0; int batch, p; long long ld;
+    double gain; const double* gain_dev;
+    double qe, background, read_noise; int photon;
+    unsigned long long seed, step, first; const unsigned long long* step_dev;
+};
+hipError_t fmpc_launch_detector_read(const FdParams& P, hipStream_t stream);
 
 // The linearised image model (fmpc_kernel_est_model.hip): fields 0 = P_k (the base) and 1 + j = 1i Z_j .* P_k, P_k = E .* D_k.
 #define FEM_MAXMODE 128

@@ -4,6 +4,7 @@
 #include "fmpc_bank.h"
 #include "../../include/fastmpc.h"      // fmpc_noise, the status codes
 #include "fmpc_noise.h"
+#include "fmpc_detector.h"
 #include "fmpc_atm.h"
 
 #include <algorithm>
@@ -1384,6 +1385,36 @@ extern "C" int fmpc_noise_normal_host(double* out, int batch, int p, long long l
     for (int r = 0; r < batch; ++r)
         for (int i = 0; i < p; ++i)
             out[(size_t)r * ld + i] = fmpc_noise_scaled(nz->value, fmpc_noise_normal(nz->seed, nz->step, (uint32_t)(nz->first + r), (uint32_t)i));
+    return FMPC_OK;
+}
+
+// ---- detector (fmpc_detector.h): the argument rules of the fmpc_detector block, the read-out on the host
+double fmpc_host_sum(const double* v, int cnt) {
+    double s = 0.0;
+    for (int i = 0; i < cnt; ++i) s += v[i];
+    return s;
+}
+
+int fmpc_host_detector_check(const fmpc_detector* det, int batch) {
+    if (!det) return FMPC_E_NULL;
+    if (batch < 0 || det->first < 0 || det->first > (1ll << 32) || det->first + (long long)batch > (1ll << 32)) return FMPC_E_DIM;
+    if (!std::isfinite(det->gain) || det->gain < 0.0 || (det->gain == 0.0 && !det->gain_dev)) return FMPC_E_DIM;
+    if (!std::isfinite(det->qe) || !(det->qe > 0.0)) return FMPC_E_DIM;
+    if (!std::isfinite(det->background) || det->background < 0.0 || !std::isfinite(det->read_noise) || det->read_noise < 0.0) return FMPC_E_DIM;
+    return FMPC_OK;
+}
+
+extern "C" int fmpc_detector_read_host(double* Y, const double* Y0, int batch, int p, long long ld, const fmpc_detector* det) {
+    if (!Y || !Y0 || !det) return FMPC_E_NULL;
+    const int rc = fmpc_host_detector_check(det, batch);
+    if (rc != FMPC_OK) return rc;
+    if (p < 1 || p > FMPC_DET_MAX_P || (ld != 0 && ld < p)) return FMPC_E_DIM;
+    if (det->gain_dev || det->step_dev) return FMPC_E_DIM;         // device pointers: not readable here
+    if (ld == 0) ld = p;
+    for (int r = 0; r < batch; ++r)
+        for (int i = 0; i < p; ++i)
+            Y[(size_t)r * ld + i] = fmpc_detector_read(Y0[(size_t)r * ld + i], det->gain, det->qe, det->background, det->read_noise, det->photon_noise,
+                                                       det->seed, det->step, (uint32_t)(det->first + r), (uint32_t)i);
     return FMPC_OK;
 }
 

@@ -255,6 +255,14 @@ double fmpc_host_mean_square(const double* v, int cnt);
 // negative sigma, sigma_dev in SNR mode.  No pointer of the block is read.
 struct fmpc_noise_s;
 int fmpc_host_noise_check(const struct fmpc_noise_s* nz, int batch, int sigma_only);
+// ---- detector (include/fastmpc.h: fmpc_detector; the draw and the model: fmpc_detector.h)
+// sum(v): what the unaberrated system puts into its windows, behind fmpc_est_photon_gain
+double fmpc_host_sum(const double* v, int cnt);
+// The argument rules of an fmpc_detector block for a call over `batch` realisations: FMPC_E_NULL for det == NULL; FMPC_E_DIM for
+// batch < 0, first < 0, first + batch > 2^32, a negative or non-finite gain, background or read_noise, qe <= 0 or non-finite,
+// gain == 0 without gain_dev.  No pointer of the block is read.
+struct fmpc_detector_s;
+int fmpc_host_detector_check(const struct fmpc_detector_s* det, int batch);
 
 // ---- Zernike functions (zernfun.m, zernmodfit.m)
 #define FMPC_ZERNIKE_MAXN 14            // radial orders whose coefficients are exact in a double (14! < 2^53)

@@ -29,6 +29,7 @@
 #include "fmpc_estimator.h"
 #include "fmpc_est_dev.h"            // d4e, FE_MFMA, FE_TSTRIDE, fe_sincos
 #include "fmpc_noise.h"              // fmpc_noise_normal, fmpc_noise_add: the draw of the noisy forms
+#include "fmpc_detector.h"           // fmpc_detector_read: the detector form
 
 template <int NW>
 __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) fmpc_est_psf(FeParams P) {      // (second argument: workgroups per CU here = 2 wavefronts per SIMD either way)
@@ -152,6 +153,13 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) fmpc_est_psf(FeParam
 // share G_k g_k for unit noise and its partial sum of Y0^2 (fixed orders), and fmpc_est_combine_noisy puts them together.
 __device__ __forceinline__ unsigned long long fe_nz_step(const FeParams& P) { return P.nz_step + (P.nz_step_dev ? *P.nz_step_dev : 0ull); }
 __device__ __forceinline__ double fe_nz_sigma(const FeParams& P, int r) { return P.nz_sigma_dev ? P.nz_sigma_dev[r] : P.nz_value; }
+// The detector form (NZ = FE_NZ_DET; fmpc_est_apply_detector_device): the owner of a measurement replaces Y0 by its read-out --
+// a Poisson deviate and a normal one, both pure functions of (seed, step, realisation, measurement) (fmpc_detector.h).  The loops
+// of the Poisson draw diverge across lanes; nothing in them waits on another lane.  The shares and the combine are the plain ones.
+__device__ __forceinline__ double fe_det_read(const FeParams& P, int r, int idx, double y0) {
+    return fmpc_detector_read(y0, P.det_gain_dev ? P.det_gain_dev[r] : P.det_gain, P.det_qe, P.det_background, P.det_read_noise, P.det_photon,
+                              P.nz_seed, fe_nz_step(P), (uint32_t)(P.nz_first + (unsigned long long)r), (uint32_t)idx);
+}
 
 // |O|^2 with the product that is rounded on its own and the one that is fused WRITTEN DOWN (the compiler, left to contract
 // orr * orr + oi * oi, took either one from build to build): the general finish fuses oi * oi, the few-screen finish orr * orr,
@@ -237,9 +245,10 @@ __global__ void __launch_bounds__(FE_FINISH_THREADS) fmpc_est_finish(FeParams P)
         const int il = v * d + u, idx = k * dd + il;       // reshape(v_im(:,:,k), [], 1): column-major
         double y = FE_ABS2_GENERAL(orr, oi) * P.scale;
         if constexpr (NZ == FE_NZ_OFF) { if (P.noise) y += P.noise[(size_t)r * p + idx]; }
-        if constexpr (NZ != FE_NZ_OFF) gz = fmpc_noise_normal(P.nz_seed, fe_nz_step(P), (uint32_t)(P.nz_first + (unsigned long long)r), (uint32_t)idx);
+        if constexpr (NZ == FE_NZ_SIGMA || NZ == FE_NZ_SNR) gz = fmpc_noise_normal(P.nz_seed, fe_nz_step(P), (uint32_t)(P.nz_first + (unsigned long long)r), (uint32_t)idx);
         if constexpr (NZ == FE_NZ_SIGMA) y = fmpc_noise_add(y, fe_nz_sigma(P, r), gz);
         if constexpr (NZ == FE_NZ_SNR) y2 = y * y;
+        if constexpr (NZ == FE_NZ_DET) y = fe_det_read(P, r, idx, y);
         if (P.Yout) P.Yout[(size_t)r * p + idx] = y;
         sY[il] = y - P.bs[idx];
     }
@@ -316,8 +325,9 @@ __global__ void __launch_bounds__(256) fmpc_est_finish_few(FeParams P) {
     if constexpr (NZ == FE_NZ_OFF) { if (own && P.noise) y += P.noise[(size_t)r * p + idx]; }
     double gz = 0.0;                                          // (noisy forms: this thread's unit noise; fmpc_noise.h)
     (void)gz;
-    if constexpr (NZ != FE_NZ_OFF) gz = fmpc_noise_normal(P.nz_seed, fe_nz_step(P), (uint32_t)(P.nz_first + (unsigned long long)r), (uint32_t)(own ? idx : 0));
+    if constexpr (NZ == FE_NZ_SIGMA || NZ == FE_NZ_SNR) gz = fmpc_noise_normal(P.nz_seed, fe_nz_step(P), (uint32_t)(P.nz_first + (unsigned long long)r), (uint32_t)(own ? idx : 0));
     if constexpr (NZ == FE_NZ_SIGMA) y = fmpc_noise_add(y, fe_nz_sigma(P, r), gz);
+    if constexpr (NZ == FE_NZ_DET) { if (own) y = fe_det_read(P, r, idx, y); }
     if (own && P.Yout) P.Yout[(size_t)r * p + idx] = y;
     const double yv = own ? y - P.bs[idx] : 0.0;
     double* share = P.shares + (((size_t)r * P.ndiv + k) * FE_FQ + qd) * P.nx;
@@ -406,7 +416,7 @@ __global__ void __launch_bounds__(256) fmpc_est_noise_yout(FeParams P) {
 }
 
 hipError_t fmpc_launch_estimator(const FeParams& P, hipStream_t stream) {
-    if (P.nz_mode < FE_NZ_OFF || P.nz_mode > FE_NZ_SNR) return hipErrorInvalidValue;
+    if (P.nz_mode < FE_NZ_OFF || P.nz_mode > FE_NZ_DET) return hipErrorInvalidValue;
     if (P.nz_mode == FE_NZ_SNR && (!P.nz_shares || !P.nz_power || !P.nz_sigma)) return hipErrorInvalidValue;
     if (P.len % 64 != 0 || P.len < 64 || P.d < 1 || P.d > 32 || P.ndiv < 1 || P.ndiv > FE_MAXDIV) return hipErrorInvalidValue;
     if (!fe_finish_serves(P.d, P.nx)) return hipErrorInvalidValue;      // (fmpc_est_create refuses such a handle)
@@ -440,9 +450,12 @@ hipError_t fmpc_launch_estimator(const FeParams& P, hipStream_t stream) {
         } else if (P.nz_mode == FE_NZ_SIGMA) {
             if (csplit == 2) hipLaunchKernelGGL((fmpc_est_finish_few<2, FE_NZ_SIGMA>), grid, dim3(256), 0, stream, Q);
             else hipLaunchKernelGGL((fmpc_est_finish_few<1, FE_NZ_SIGMA>), grid, dim3(256), 0, stream, Q);
-        } else {
+        } else if (P.nz_mode == FE_NZ_SNR) {
             if (csplit == 2) hipLaunchKernelGGL((fmpc_est_finish_few<2, FE_NZ_SNR>), grid, dim3(256), 0, stream, Q);
             else hipLaunchKernelGGL((fmpc_est_finish_few<1, FE_NZ_SNR>), grid, dim3(256), 0, stream, Q);
+        } else {
+            if (csplit == 2) hipLaunchKernelGGL((fmpc_est_finish_few<2, FE_NZ_DET>), grid, dim3(256), 0, stream, Q);
+            else hipLaunchKernelGGL((fmpc_est_finish_few<1, FE_NZ_DET>), grid, dim3(256), 0, stream, Q);
         }
     } else {
         Q.nshare = 1;
@@ -450,10 +463,11 @@ hipError_t fmpc_launch_estimator(const FeParams& P, hipStream_t stream) {
         const size_t lds = fe_finish_lds_bytes(P.d, P.nx);
         if (P.nz_mode == FE_NZ_OFF) hipLaunchKernelGGL(fmpc_est_finish<FE_NZ_OFF>, grid, dim3(FE_FINISH_THREADS), lds, stream, Q);
         else if (P.nz_mode == FE_NZ_SIGMA) hipLaunchKernelGGL(fmpc_est_finish<FE_NZ_SIGMA>, grid, dim3(FE_FINISH_THREADS), lds, stream, Q);
-        else hipLaunchKernelGGL(fmpc_est_finish<FE_NZ_SNR>, grid, dim3(FE_FINISH_THREADS), lds, stream, Q);
+        else if (P.nz_mode == FE_NZ_SNR) hipLaunchKernelGGL(fmpc_est_finish<FE_NZ_SNR>, grid, dim3(FE_FINISH_THREADS), lds, stream, Q);
+        else hipLaunchKernelGGL(fmpc_est_finish<FE_NZ_DET>, grid, dim3(FE_FINISH_THREADS), lds, stream, Q);
     }
     const dim3 cgrid((P.batch * P.nx + 255) / 256);
-    if (P.nz_mode == FE_NZ_OFF) hipLaunchKernelGGL(fmpc_est_combine, cgrid, dim3(256), 0, stream, Q);
+    if (P.nz_mode == FE_NZ_OFF || P.nz_mode == FE_NZ_DET) hipLaunchKernelGGL(fmpc_est_combine, cgrid, dim3(256), 0, stream, Q);
     else if (P.nz_mode == FE_NZ_SIGMA) hipLaunchKernelGGL(fmpc_est_combine_noisy<FE_NZ_SIGMA>, cgrid, dim3(256), 0, stream, Q);
     else {
         hipLaunchKernelGGL(fmpc_est_combine_noisy<FE_NZ_SNR>, cgrid, dim3(256), 0, stream, Q);

@@ -7,7 +7,8 @@ simulation loop, README.md:456-480, for a batch of residual phase screens at onc
 Arrays are handed over as MATLAB has them (column-major); numpy / torch arrays indexed [row, column] are transposed here.
 
 Measurement noise (README.md:473-475, "SNR = 10 [dB]") is drawn on the device from a counter (`EstimatorNoise`, include/fastmpc.h:
-fmpc_noise): `est.apply_device(scrn, noise=EstimatorNoise(snr_db=10, seed=1), step=k)`."""
+fmpc_noise): `est.apply_device(scrn, noise=EstimatorNoise(snr_db=10, seed=1), step=k)`.  A detector's photon and read-out noise
+(OOMAO detector.m:315-321) likewise: `noise=DetectorNoise(est.photon_gain(1e4), read_noise=2.0, seed=1)`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -97,6 +98,81 @@ def normal_noise_host(batch, p, noise, step=0, out=None):
     return out
 
 
+class DetectorNoise:
+    """Photon and read-out noise of a detector, drawn inside the estimator's finish pass (include/fastmpc.h: fmpc_detector; OOMAO
+    detector.m:315-321): with lam = gain Y0 + background photo-electrons expected in a measurement,
+        Y_M = (qe (N - background) + read_noise g) / gain,   N ~ Poisson(lam) (photon_noise) or N = lam,
+    N and the standard normal g pure functions of (seed, step, first + r, i), exact in law for lam up to 2^31 and the same bits on
+    host and device.  gain: photo-electrons per unit of Y_M, a float or a HIP tensor of batch doubles
+    (`PhaseDiversityEstimator.photon_gain` gives the gain of a flux).  read_noise: electrons rms.  qe scales the image as OOMAO's
+    does: fold it into the gain for an unbiased estimate.  first, counter: as in `EstimatorNoise`."""
+
+    def __init__(self, gain, photon_noise=True, read_noise=0.0, qe=1.0, background=0.0, seed=0, first=0, counter=None):
+        self.gain = gain if hasattr(gain, "data_ptr") else float(gain)
+        self.photon_noise, self.read_noise, self.qe, self.background = bool(photon_noise), float(read_noise), float(qe), float(background)
+        self.seed, self.first, self.counter = int(seed), int(first), counter
+        if hasattr(self.gain, "data_ptr"):
+            import torch
+            assert self.gain.is_cuda and self.gain.dtype == torch.float64 and self.gain.is_contiguous()
+        if counter is not None:
+            import torch
+            assert counter.is_cuda and counter.numel() == 1 and counter.dtype in (torch.int64, getattr(torch, "uint64", torch.int64))
+
+    def _block(self, step=0, batch=None):
+        """The fmpc_detector block of a call at `step` (the tensors it points to stay owned by this object)."""
+        det = _lib.Detector()
+        if hasattr(self.gain, "data_ptr"):
+            if batch is not None and self.gain.numel() != batch:
+                raise ValueError("DetectorNoise: gain tensor needs one entry per realisation of the batch")
+            det.gain, det.gain_dev = 0.0, self.gain.data_ptr()
+        else:
+            det.gain, det.gain_dev = self.gain, None
+        det.qe, det.background, det.read_noise, det.photon_noise = self.qe, self.background, self.read_noise, int(self.photon_noise)
+        det.seed, det.step = self.seed & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+        det.step_dev = None if self.counter is None else self.counter.data_ptr()
+        det.first = self.first
+        return det
+
+
+def detector_read(Y0, det, step=0, out=None):
+    """The detector's read-out of a (batch, p) float64 HIP tensor Y0 with contiguous rows (fmpc_detector_read_device), on torch's
+    current stream: what `apply_device(noise=<DetectorNoise>)` makes of its noise-free Y_M.  out: a tensor of Y0's shape and strides
+    (Y0 itself: in place); columns are the measurements i < p of realisation first + r."""
+    import torch
+    lib = _lib.load()
+    assert Y0.is_cuda and Y0.dtype == torch.float64 and Y0.dim() == 2 and (Y0.stride(1) == 1 or Y0.shape[1] == 1)
+    if out is None:
+        out = torch.empty_strided(tuple(Y0.shape), Y0.stride(), dtype=torch.float64, device=Y0.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.shape == Y0.shape and out.stride() == Y0.stride()
+    batch, p = Y0.shape
+    ld = Y0.stride(0) if batch > 1 else p
+    blk = det._block(step, batch)
+    rc = lib.fmpc_detector_read_device(C.c_void_p(out.data_ptr()), C.c_void_p(Y0.data_ptr()), batch, p, ld, C.byref(blk),
+                                       C.c_void_p(torch.cuda.current_stream(Y0.device).cuda_stream))
+    if rc != 0:
+        raise FastMPCError(rc, "fmpc_detector_read_device")
+    return out
+
+
+def detector_read_host(Y0, det, step=0, out=None):
+    """The same read-out on the host (fmpc_detector_read_host; no device): Y0 a (batch, p) float64 numpy array with contiguous
+    rows; returns an array of its shape (out: one of Y0's shape and strides, Y0 itself for in place)."""
+    lib = _lib.load()
+    Y0 = np.asarray(Y0)
+    if out is None:
+        Y0 = np.ascontiguousarray(Y0, dtype=np.float64)
+        out = np.empty_like(Y0)
+    assert Y0.dtype == np.float64 and Y0.ndim == 2 and Y0.strides[1] == 8
+    assert out.dtype == np.float64 and out.shape == Y0.shape and out.strides == Y0.strides
+    batch, p = Y0.shape
+    ld = Y0.strides[0] // 8 if batch > 1 else p
+    blk = det._block(step, batch)
+    rc = lib.fmpc_detector_read_host(out.ctypes.data_as(C.c_void_p), Y0.ctypes.data_as(C.c_void_p), batch, p, ld, C.byref(blk))
+    if rc != 0:
+        raise FastMPCError(rc, "fmpc_detector_read_host")
+    return out
+
+
 class PhaseDiversityEstimator:
     def __init__(self, pupil, W, zd_list, dx, range_min, range_max, A_s, b_s, AU=1e12, device=0):
         """range_min, range_max: the reference's 1-based window bounds (README.md:378-379); A_s (p, nx), b_s (p)."""
@@ -154,9 +230,19 @@ class PhaseDiversityEstimator:
             raise FastMPCError(rc, "fmpc_est_snr_sigma")
         return s.value
 
+    def photon_gain(self, n_photons):
+        """n_photons ndiv / sum(b_s): the gain [photo-electrons per unit of Y_M] at which the unaberrated system puts n_photons
+        photo-electrons, on average, into one diversity's window (fmpc_est_photon_gain)."""
+        g = C.c_double()
+        rc = self._lib.fmpc_est_photon_gain(self._h, float(n_photons), C.byref(g))
+        if rc != 0:
+            raise FastMPCError(rc, "fmpc_est_photon_gain")
+        return g.value
+
     def apply_device(self, scrn, noise=None, want_Y=False, colmajor=False, out=None, step=0, want_sigma=False):
         """scrn: (batch, len, len) float64 HIP tensor indexed [b, row, column] (colmajor=True: already [b, column, row], no copy).
-        noise: None, a (batch, p) HIP tensor that is added to Y_M, or an `EstimatorNoise` drawn on the device at `step`.
+        noise: None, a (batch, p) HIP tensor that is added to Y_M, an `EstimatorNoise` or a `DetectorNoise` drawn on the device
+        at `step`.
         Returns ad_est (batch, nx) [, Y_M (batch, p)] [, sigma (batch): want_sigma, with an EstimatorNoise] on torch's current
         stream; out: a (batch, nx) tensor to write ad_est into."""
         import torch
@@ -180,6 +266,14 @@ class PhaseDiversityEstimator:
             return res if len(res) > 1 else ad
         if want_sigma:
             raise ValueError("want_sigma: only with an EstimatorNoise")
+        if isinstance(noise, DetectorNoise):
+            det = noise._block(step, batch)
+            rc = self._lib.fmpc_est_apply_detector_device(self._h, batch, C.c_void_p(scrn.data_ptr()), C.byref(det), C.c_void_p(ad.data_ptr()),
+                                                          None if Y is None else C.c_void_p(Y.data_ptr()),
+                                                          C.c_void_p(torch.cuda.current_stream(scrn.device).cuda_stream))
+            if rc != 0:
+                raise FastMPCError(rc, "fmpc_est_apply_detector_device")
+            return (ad, Y) if want_Y else ad
         if noise is not None:
             assert noise.is_cuda and noise.dtype == torch.float64 and noise.is_contiguous() and tuple(noise.shape) == (batch, self.p)
         vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
