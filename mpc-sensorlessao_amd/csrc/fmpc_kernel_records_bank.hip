@@ -85,21 +85,7 @@ fmpc_records_bank_panel(RecBankParams K, int items, int ipw) {
     const int n = P.n, m = P.m, T = P.T, batch = P.batch, mpad = (m + 15) & ~15;
     double* sBt = sh; double* sR = sBt + (size_t)mpad * REC_LDB; double* sQ = sR + mpad; double* sQf = sQ + REC_NMAX;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, lk = lane >> 4;
-    for (int base = 0; base < mpad * REC_LDB; base += 8 * 256) {
-        double t[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int idx = base + k * 256 + tid, c = idx / REC_LDB, q = idx - c * REC_LDB;
-            const bool ok = c < m && q < n;
-            const double v = P.Bt[ok ? (size_t)c * n + q : 0];
-            t[k] = ok ? v : 0.0;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { const int idx = base + k * 256 + tid; if (idx < mpad * REC_LDB) sBt[idx] = t[k]; }
-    }
-    for (int c = tid; c < mpad; c += 256) sR[c] = P.R[c];
-    if (tid < REC_NMAX) { sQ[tid] = P.Q[tid]; sQf[tid] = P.Qf[tid]; }
-    __syncthreads();
+    rc_stage_lds(P.Bt, P.R, P.Q, P.Qf, n, m, sBt, sR, sQ, sQf, mpad, tid);
 
     const int cols = STRETCH ? (P.steps + REC_PT - 1) / REC_PT : (batch + REC_PT - 1) / REC_PT;     // step tiles of a problem / panels
     const int it1 = (blockIdx.x + 1) * ipw < items ? (blockIdx.x + 1) * ipw : items;
@@ -117,14 +103,9 @@ fmpc_records_bank_panel(RecBankParams K, int items, int ipw) {
             A2 = K.var2 ? A1 + (size_t)n * n : A1;
             const int s0 = REC_PT * st + li;
             pok = s0 < P.steps;
-            const size_t s = pok ? s0 : P.steps - 1, sb = s * batch;   // (a ragged tile: the idle columns repeat the last step)
-            x0p = P.x0 + (sb + p) * n;
-            xpp = s > 0 ? P.x0 + (sb - batch + p) * n : (P.x0_before ? P.x0_before + p * n : nullptr);
-            up = P.u + (sb + p) * m;
-            u1p = s > 0 ? P.u + (sb - batch + p) * m : (P.u_before1 ? P.u_before1 + p * m : nullptr);
-            ub2 = s > 1 ? P.u + (sb - 2 * (size_t)batch + p) * m
-                        : (s == 1 ? (P.u_before1 ? P.u_before1 + p * m : nullptr) : (P.u_before2 ? P.u_before2 + p * m : nullptr));
-            xo = sb + p;
+            // (a ragged tile: the idle columns repeat the last step)
+            rc_stretch_ptrs(P.x0, P.u, P.x0_before, P.u_before1, P.u_before2, n, m, batch, pok ? s0 : P.steps - 1, p, x0p, xpp, up, u1p,
+                            ub2, xo);
         } else {
             const int pn = it / P.stages;
             i = it - pn * P.stages;
@@ -141,16 +122,10 @@ fmpc_records_bank_panel(RecBankParams K, int items, int ipw) {
         rc_d4 acc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
         if (STRETCH) {
             // ---- the corrected states X0[s] - B u[s-1], x0_pre[s] - B u[s-2] as B operands: k-step ks holds entry 4 ks + lk.  The
-            // matrix-core products run in every lane: a column without u[s-1] / u[s-2] takes u[s] and drops the result.
+            // matrix-core products run in every lane: a column without u[s-1] / u[s-2] takes u[s] and drops the result
+            // (fmpc_records_panel branches round them: its step is uniform.  Two forms on purpose, not one behind a flag).
             double xb[8], pb[8];
-            const double* xq = xpp ? xpp : x0p;
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const int q = 4 * ks + lk, qc = q < n ? q : 0;
-                const double t0 = x0p[qc], t1 = xq[qc];
-                xb[ks] = q < n ? t0 : 0.0;
-                pb[ks] = (xpp && q < n) ? t1 : 0.0;
-            }
+            rc_load_xb(x0p, xpp, n, lk, xb, pb);
             rc_d4 b0 = {0, 0, 0, 0}, b1 = {0, 0, 0, 0};
             rc_bu<false, 2>(sBt, sR, u1p ? u1p : up, m, lk, li, b0, b1, false, nullptr, nullptr, nullptr, pok, 0, 0, 0);
 #pragma unroll
@@ -159,27 +134,8 @@ fmpc_records_bank_panel(RecBankParams K, int items, int ipw) {
             rc_bu<false, 2>(sBt, sR, ub2 ? ub2 : up, m, lk, li, b0, b1, false, nullptr, nullptr, nullptr, pok, 0, 0, 0);
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks) pb[ks] -= ub2 ? (ks < 4 ? b0[ks & 3] : b1[ks & 3]) : 0.0;
-            // ---- rows of the model's A1, A2 as A operands (zero factors beyond n), requested together, then the products
-#pragma unroll
-            for (int I = 0; I < 2; ++I) {
-                if (I == 1 && n <= 16) break;
-                const int qr = 16 * I + li;
-                const bool rok = qr < n;
-                const size_t rb = (size_t)(rok ? qr : 0) * n;
-                double a1[8], a2[8];
-#pragma unroll
-                for (int ks = 0; ks < 8; ++ks) {
-                    const int kc = 4 * ks + lk;
-                    const bool ok = rok && kc < n;
-                    const double t1 = A1[rb + (kc < n ? kc : 0)], t2 = A2[rb + (kc < n ? kc : 0)];
-                    a1[ks] = ok ? t1 : 0.0; a2[ks] = (ok && K.var2) ? t2 : 0.0;
-                }
-#pragma unroll
-                for (int ks = 0; ks < 8; ++ks) {
-                    acc[I] = RC_MFMA(a1[ks], xb[ks], acc[I]);
-                    acc[I] = RC_MFMA(a2[ks], pb[ks], acc[I]);
-                }
-            }
+            // ---- the rows of the model's A1, A2 (a VAR(1) bank: A2 = 0) times the corrected states
+            rc_ax(A1, A2, 0, K.var2 != 0, n, li, lk, xb, pb, acc);
         } else {
             // ---- the accumulators start at f_i = p_i + w_i
             const double* wq = xpp ? xpp : x0p;
@@ -196,39 +152,8 @@ fmpc_records_bank_panel(RecBankParams K, int items, int ipw) {
         double ur = rc_bu<true, STRETCH ? 2 : RC_GFULL>(sBt, sR, up, m, lk, li, acc[0], acc[1], i == 0 && (P.du || P.uv), u1p,
                                 P.du ? P.du + (STRETCH ? xo : p) * m : nullptr, P.uv ? P.uv + (STRETCH ? xo : p) * m : nullptr,
                                 pok, P.ca, P.cb, P.uc);
-        // ---- Xp from the accumulators; its norm and weighted norm per column: over the lane's 8 rows, then over the four k-groups
-        const double* qw = i == T - 1 ? sQf : sQ;
-        double se = 0.0, sq = 0.0;
-#pragma unroll
-        for (int I = 0; I < 2; ++I)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int q = 16 * I + 4 * r + lk;
-                const double v = acc[I][r];
-                if (P.Xp && pok && q < n) P.Xp[xo * n + q] = v;
-                se += v * v; sq += qw[q] * v * v;
-            }
-        se += __shfl_xor(se, 16); se += __shfl_xor(se, 32);
-        sq += __shfl_xor(sq, 16); sq += __shfl_xor(sq, 32);
-        ur += __shfl_xor(ur, 16); ur += __shfl_xor(ur, 32);
-        if (lk == 0 && pok) {
-            if (P.xerr) P.xerr[xo] = sqrt(se);
-            if (!STRETCH && P.jpart) P.jpart[(size_t)i * batch + p] = sq + ur;
-        }
+        rc_finish(P.Xp, P.xerr, STRETCH ? nullptr : P.jpart, (size_t)i * batch + p, acc, i == T - 1 ? sQf : sQ, ur, xo, pok, n, lk);
     }
-}
-
-// J of a problem with a model: its stages in order (no atomics)
-__global__ void __launch_bounds__(256)
-fmpc_records_bank_jsum(const double* __restrict__ jpart, double* __restrict__ J, int batch, int stages, const int* __restrict__ model_of,
-                       int count) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= batch) return;
-    const int mi = model_of ? model_of[p] : p;
-    if ((unsigned)mi >= (unsigned)count) return;
-    double s = 0.0;
-    for (int i = 0; i < stages; ++i) s += jpart[(size_t)i * batch + p];
-    J[p] = s;
 }
 
 // Any size (a bank exists up to n = 111), dense Q, Qf, R: fmpc_records_any with the free response in place of M1, M2 -- one workgroup
@@ -239,45 +164,26 @@ __global__ void __launch_bounds__(256)
 fmpc_records_bank_any(RecBankParams K) {
     extern __shared__ double sh[];                       // p_{i-1}, p_{i-2}, p_i, Xp_i (n each), u_i (m), three sums per thread
     const RecParams& P = K.R;
-    const int n = P.n, m = P.m, T = P.T, batch = P.batch, tid = threadIdx.x;
+    const int n = P.n, m = P.m, T = P.T, tid = threadIdx.x;
     double* p1 = sh; double* p2 = sh + n; double* pc = sh + 2 * n; double* sxp = sh + 3 * n; double* su = sh + 4 * n; double* red = su + m;
     const size_t p = blockIdx.x, s = STRETCH ? blockIdx.y : 0;
     const int mi = K.model_of ? K.model_of[p] : (int)p;
     if ((unsigned)mi >= (unsigned)K.count) return;                 // (uniform: no model, nothing read or written for this problem)
     const double* A1t = K.plain + (size_t)mi * K.plain_stride + 2 * (size_t)n * n;
     const double* A2t = A1t + (size_t)n * n;
-    const double* x0p; const double* xpp; const double* u1p; const double* ub2 = nullptr;
+    const double* x0p; const double* xpp; const double* us = nullptr; const double* u1p; const double* ub2 = nullptr;
     size_t xo0;
-    if (STRETCH) {
-        const size_t sb = s * batch;
-        x0p = P.x0 + (sb + p) * n;
-        xpp = s > 0 ? P.x0 + (sb - batch + p) * n : (P.x0_before ? P.x0_before + p * n : nullptr);
-        u1p = s > 0 ? P.u + (sb - batch + p) * m : (P.u_before1 ? P.u_before1 + p * m : nullptr);
-        ub2 = s > 1 ? P.u + (sb - 2 * (size_t)batch + p) * m
-                    : (s == 1 ? (P.u_before1 ? P.u_before1 + p * m : nullptr) : (P.u_before2 ? P.u_before2 + p * m : nullptr));
-        xo0 = sb + p;
-    } else {
+    if (STRETCH) rc_stretch_ptrs(P.x0, P.u, P.x0_before, P.u_before1, P.u_before2, n, m, P.batch, s, p, x0p, xpp, us, u1p, ub2, xo0);
+    else {
         x0p = P.x0 + p * n;
         xpp = P.x0_pre ? P.x0_pre + p * n : nullptr;
         u1p = P.u1 ? P.u1 + p * m : nullptr;
         xo0 = p * P.stages;
     }
-    for (int r = tid; r < n; r += 256) {
-        double a = x0p[r], b = xpp ? xpp[r] : 0.0;
-        if (STRETCH) {
-            double s1 = 0.0, s2 = 0.0;
-            for (int c = 0; c < m; ++c) {
-                const double bv = P.Bt[(size_t)c * n + r];
-                if (u1p) s1 += bv * u1p[c];
-                if (ub2) s2 += bv * ub2[c];
-            }
-            a -= s1; b -= s2;
-        }
-        p1[r] = a; p2[r] = b;
-    }
+    rc_any_sub_bu(P, STRETCH, x0p, xpp, u1p, ub2, p1, p2, tid);
     double Jacc = 0.0;
     for (int i = 0; i < P.stages; ++i) {
-        const double* up = STRETCH ? P.u + xo0 * m : P.u + p * (size_t)P.ldu + (size_t)i * P.stage_stride;
+        const double* up = STRETCH ? us : P.u + p * (size_t)P.ldu + (size_t)i * P.stage_stride;
         const double* wp = (!STRETCH && P.w) ? P.w + (p * T + i) * n : nullptr;
         __syncthreads();                                 // (p1, p2 written; the previous stage's su, sxp, red read)
         for (int c = tid; c < m; c += 256) su[c] = up[c];
@@ -293,38 +199,7 @@ fmpc_records_bank_any(RecBankParams K) {
             sxp[r] = f;
             if (P.Xp) P.Xp[(xo0 + i) * n + r] = f;
         }
-        __syncthreads();
-        double se = 0.0, sq = 0.0, sr = 0.0;
-        for (int r = tid; r < n; r += 256) se += sxp[r] * sxp[r];
-        if (P.J) {
-            const double* Qm = i == T - 1 ? P.Qf : P.Q;
-            for (int r = tid; r < n; r += 256) {
-                double t = 0.0;
-                for (int q = 0; q < n; ++q) t += Qm[(size_t)r * n + q] * sxp[q];
-                sq += sxp[r] * t;
-            }
-            for (int c = tid; c < m; c += 256) {
-                double t = 0.0;
-                for (int d = 0; d < m; ++d) t += P.R[(size_t)c * m + d] * su[d];
-                sr += su[c] * t;
-            }
-        }
-        red[tid] = se; red[256 + tid] = sq; red[512 + tid] = sr;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (tid < o) { red[tid] += red[tid + o]; red[256 + tid] += red[256 + tid + o]; red[512 + tid] += red[512 + tid + o]; }
-            __syncthreads();
-        }
-        if (tid == 0) {
-            if (P.xerr) P.xerr[xo0 + i] = sqrt(red[0]);
-            Jacc += red[256] + red[512];
-        }
-        if (i == 0)
-            for (int c = tid; c < m; c += 256) {
-                const size_t o = (STRETCH ? xo0 : p) * m + c;
-                if (P.du) P.du[o] = su[c] - (u1p ? u1p[c] : 0.0);
-                if (P.uv) P.uv[o] = rc_volts(su[c], P.ca, P.cb, P.uc);
-            }
+        rc_any_stage_tail(P, sxp, su, red, i, xo0, STRETCH ? xo0 : p, u1p, Jacc, tid);
         double* t = p2; p2 = p1; p1 = pc; pc = t;        // (the next stage writes the old p_{i-2} behind its first barrier)
     }
     if (tid == 0 && P.J) P.J[p] = Jacc;
@@ -337,39 +212,28 @@ hipError_t fmpc_launch_loop_records_bank(const RecBankParams& K, int panel, hipS
     const int stretch = P.steps > 0;
     if (!panel) {
         const size_t lds = (4 * (size_t)P.n + P.m + 3 * 256) * sizeof(double);
+        // (a known difference: fmpc_launch_loop_records goes to 160 KB with hipFuncAttributeMaxDynamicSharedMemorySize, this form
+        // stops at the 64 KB a kernel has without it)
         if (lds > 64 * 1024) return hipErrorInvalidValue;
         if (stretch) hipLaunchKernelGGL(fmpc_records_bank_any<true>, dim3(P.batch, P.steps), dim3(256), lds, stream, K);
         else hipLaunchKernelGGL(fmpc_records_bank_any<false>, dim3(P.batch), dim3(256), lds, stream, K);
         return hipGetLastError();
     }
-    if (P.n > REC_NMAX || (!stretch && !K.F)) return hipErrorInvalidValue;
-    const int mpad = (P.m + 15) & ~15;
-    const size_t lds = ((size_t)mpad * REC_LDB + mpad + 2 * REC_NMAX) * sizeof(double);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (!stretch && !K.F) return hipErrorInvalidValue;
     const long long items = stretch ? (long long)P.batch * ((P.steps + REC_PT - 1) / REC_PT)
                                     : (long long)((P.batch + REC_PT - 1) / REC_PT) * P.stages;
-    if (items > 0x7fffffffLL) return hipErrorInvalidValue;
-    const int ipw = items >= 8192 ? 16 : (items >= 2048 ? 8 : 4);      // (as fmpc_launch_loop_records: B' is loaded once per workgroup)
-    const unsigned grid = (unsigned)((items + ipw - 1) / ipw);
-    const void* kern = stretch ? (const void*)fmpc_records_bank_panel<true> : (const void*)fmpc_records_bank_panel<false>;
-    if (lds > 64 * 1024) {
-        hipError_t ea = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return ea;
-    }
+    RecPanelPlan L;
+    hipError_t e = fmpc_records_panel_plan(P, items, stretch ? (const void*)fmpc_records_bank_panel<true>
+                                                             : (const void*)fmpc_records_bank_panel<false>, L);
+    if (e != hipSuccess) return e;
     if (stretch) {
-        hipLaunchKernelGGL(fmpc_records_bank_panel<true>, dim3(grid), dim3(256), lds, stream, K, (int)items, ipw);
+        hipLaunchKernelGGL(fmpc_records_bank_panel<true>, dim3(L.grid), dim3(256), L.lds, stream, K, L.items, L.ipw);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(fmpc_records_bank_chain, dim3((P.batch + RCB_CW - 1) / RCB_CW), dim3(64 * RCB_CW), 0, stream, K);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fmpc_records_bank_panel<false>, dim3(grid), dim3(256), lds, stream, K, (int)items, ipw);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (P.J && P.jpart) {
-        hipLaunchKernelGGL(fmpc_records_bank_jsum, dim3((P.batch + 255) / 256), dim3(256), 0, stream, P.jpart, P.J, P.batch, P.stages,
-                           K.model_of, K.count);
-        e = hipGetLastError();
-    }
-    return e;
+    hipLaunchKernelGGL(fmpc_records_bank_panel<false>, dim3(L.grid), dim3(256), L.lds, stream, K, L.items, L.ipw);
+    e = hipGetLastError();
+    return e != hipSuccess ? e : fmpc_records_jsum_launch(P, K.model_of, K.count, stream);
 }

@@ -34,6 +34,14 @@ struct RecBankParams {
     double* F;                                       // panel kernel, one timestep: the free response p_i, [batch][stages][n]
 };
 
+// The launch of a panel kernel `kern` (fmpc_records_panel / fmpc_records_bank_panel) over `items` items: the LDS of B' and the
+// weights (allowed beyond 64 KB on kern, up to 160 KB), `ipw` items per workgroup and the grid.  In fmpc_kernel_records.hip.
+struct RecPanelPlan { size_t lds; int items, ipw; unsigned grid; };
+hipError_t fmpc_records_panel_plan(const RecParams& P, long long items, const void* kern, RecPanelPlan& L);
+// J[p] = the stages of jpart in order, for the problems with a model (model_of, count as in RecBankParams; the shared model:
+// NULL, batch -- every problem has one).  In fmpc_kernel_records.hip.
+hipError_t fmpc_records_jsum_launch(const RecParams& P, const int* model_of, int count, hipStream_t stream);
+
 // closed-loop records (fmpc_kernel_records.hip)
 hipError_t fmpc_launch_loop_records(const RecParams& P, int panel, hipStream_t stream);
 // ... with the model bank (fmpc_kernel_records_bank.hip)

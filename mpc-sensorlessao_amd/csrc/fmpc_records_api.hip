@@ -38,18 +38,27 @@ static int fmpc_ensure_records(fmpc_handle h, hipStream_t stream) {
     return FMPC_OK;
 }
 
+// What both forms need between fmpc_guard_begin and the launch (h->mu held): the weights, the partial-cost scratch of the panel
+// kernel, and the handle's part of the parameter block.
+static int fmpc_records_prepare(fmpc_handle h, RecParams& P, hipStream_t stream) {
+    int rc = fmpc_ensure_records(h, stream);
+    if (rc == FMPC_OK && P.J && h->rec_panel) rc = h->rec_j.grow((size_t)P.stages * P.batch, stream);
+    if (rc != FMPC_OK) return rc;
+    P.n = h->n; P.m = h->m; P.T = h->T;
+    P.Bt = h->dev.Bt;
+    P.Q = h->rec_w; P.Qf = h->rec_w + h->rec_oQf; P.R = h->rec_w + h->rec_oR;
+    P.jpart = (P.J && h->rec_panel) ? (double*)h->rec_j : nullptr;
+    return FMPC_OK;
+}
+
 static int fmpc_records_launch(fmpc_handle h, RecParams& P, hipStream_t stream) {
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
     std::lock_guard<std::mutex> lock(h->mu);
     int rc = fmpc_guard_begin(h, stream);
     if (rc != FMPC_OK) return rc;
-    rc = fmpc_ensure_records(h, stream);
-    if (rc == FMPC_OK && P.J && h->rec_panel) rc = h->rec_j.grow((size_t)P.stages * P.batch, stream);
+    rc = fmpc_records_prepare(h, P, stream);
     if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
-    P.n = h->n; P.m = h->m; P.T = h->T;
-    P.Bt = h->dev.Bt; P.M1 = h->loop_M1; P.M2 = h->loop_M2;
-    P.Q = h->rec_w; P.Qf = h->rec_w + h->rec_oQf; P.R = h->rec_w + h->rec_oR;
-    P.jpart = (P.J && h->rec_panel) ? (double*)h->rec_j : nullptr;
+    P.M1 = h->loop_M1; P.M2 = h->loop_M2;
     const bool ok = fmpc_launch_loop_records(P, h->rec_panel, stream) == hipSuccess;
     fmpc_guard_end(h, stream);
     return ok ? FMPC_OK : FMPC_E_HIP;
@@ -134,14 +143,9 @@ static int fmpc_records_bank_launch(fmpc_handle h, RecBankParams& K, const int* 
     if (B.count <= 0 || (!model_of && P.batch > B.count)) return FMPC_E_UNSUPPORTED;
     int rc = fmpc_guard_begin(h, stream);
     if (rc != FMPC_OK) return rc;
-    rc = fmpc_ensure_records(h, stream);
-    if (rc == FMPC_OK && P.J && h->rec_panel) rc = h->rec_j.grow((size_t)P.stages * P.batch, stream);
+    rc = fmpc_records_prepare(h, P, stream);
     if (rc == FMPC_OK && h->rec_panel && P.steps == 0) rc = h->rec_f.grow((size_t)P.stages * P.batch * h->n, stream);
     if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
-    P.n = h->n; P.m = h->m; P.T = h->T;
-    P.Bt = h->dev.Bt;
-    P.Q = h->rec_w; P.Qf = h->rec_w + h->rec_oQf; P.R = h->rec_w + h->rec_oR;
-    P.jpart = (P.J && h->rec_panel) ? (double*)h->rec_j : nullptr;
     K.plain = B.plain; K.plain_stride = B.plain_stride; K.count = B.count; K.var2 = h->var_order == 2;
     K.model_of = model_of;
     K.F = (h->rec_panel && P.steps == 0) ? (double*)h->rec_f : nullptr;

@@ -160,6 +160,9 @@ CASES = [
     pytest.param(8, 5, 6, 2, False, 1, 0, id="panel-n-below-16-one-problem"),
     pytest.param(8, 5, 6, 2, False, 17, 0, id="panel-n-below-16"),
     pytest.param(8, 5, 6, 1, False, 3, 0, id="panel-var1"),
+    pytest.param(16, 5, 3, 2, False, 17, 0, id="panel-n-16-one-row-tile"),
+    pytest.param(17, 5, 3, 2, False, 17, 0, id="panel-n-17-second-row-tile"),
+    pytest.param(32, 20, 3, 2, False, 3, 0, id="panel-n-32-the-limit"),
     pytest.param(8, 5, 6, 2, True, 3, 0, id="any-size-dense-weights"),
     pytest.param(40, 30, 4, 2, False, 3, 0, id="any-size-n-above-32"),
 ]
@@ -253,7 +256,7 @@ def stretch_ref(md, X0, U0, x0_before=None, ub1=None, ub2=None):
     return Xp0, np.linalg.norm(Xp0, axis=2), dU, volts_ref(U0)
 
 
-@pytest.mark.parametrize("n,m,T,R,steps", [(27, 144, 10, 3, 5), (8, 5, 6, 2, 4)])
+@pytest.mark.parametrize("n,m,T,R,steps", [(27, 144, 10, 3, 5), (8, 5, 6, 2, 4), (17, 5, 3, 3, 19)])
 def test_stretch_against_steps_and_numpy(pkg, gpu, models, n, m, T, R, steps):
     """ClosedLoop.run_recorded(a, records=rec) against per-step ClosedLoop.step + records(rec) on a second loop with keep_z=True
     (stage 0 of its full-horizon call), both against numpy on that run's X0, U0; a stretch continued from a non-empty state.
@@ -291,7 +294,7 @@ def test_stretch_against_steps_and_numpy(pkg, gpu, models, n, m, T, R, steps):
         e1, e2, e3 = rel_err(one[k], st[k]), rel_err(one[k], ref[k]), rel_err(st[k], ref[k])
         print(f"  {k}: stretch vs steps {e1:.2e}, stretch vs numpy {e2:.2e}, steps vs numpy {e3:.2e}")
         assert e1 <= TOL and e2 <= TOL and e3 <= TOL, (k, e1, e2, e3)
-    # two steps, then three from the state they leave
+    # two steps, then the others from the state they leave
     loop3 = pkg.ClosedLoop(h, R, n_newton=1, k=1e-2, keep_z=False)
     rec3 = pkg.LoopRecords(h, R, volts=VOLTS)
     first = {k: v.clone() for k, v in loop3.run_recorded(ta[:2].contiguous(), records=rec3)[2].items()}
@@ -300,7 +303,7 @@ def test_stretch_against_steps_and_numpy(pkg, gpu, models, n, m, T, R, steps):
     for k in keys:
         both = torch.cat([first[k], second[k]]).cpu().numpy()
         e = rel_err(both, one[k])
-        print(f"  {k}: 2 + 3 steps vs 5: {e:.2e}")
+        print(f"  {k}: 2 + {steps - 2} steps vs {steps}: {e:.2e}")
         assert e <= TOL, (k, e)
 
 

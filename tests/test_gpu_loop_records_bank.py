@@ -214,6 +214,10 @@ CASES = [
     pytest.param(8, 5, 6, 3, 2, False, 1, 0, True, id="panel-n-below-16-one-problem"),
     pytest.param(8, 5, 6, 3, 2, False, 17, 0, True, id="panel-n-below-16"),
     pytest.param(8, 5, 6, 3, 1, False, 3, 0, True, id="panel-var1-no-A2"),
+    pytest.param(16, 5, 3, 3, 2, False, 17, 0, True, id="panel-n-16-one-row-tile"),
+    pytest.param(17, 5, 3, 3, 2, False, 17, 0, True, id="panel-n-17-second-row-tile"),
+    pytest.param(32, 20, 3, 3, 2, False, 3, 0, True, id="panel-n-32-the-limit"),
+    pytest.param(32, 20, 3, 3, 1, False, 3, 0, True, id="panel-n-32-var1-no-A2"),
     pytest.param(8, 5, 6, 3, 2, True, 3, 0, True, id="any-size-dense-weights"),
     pytest.param(40, 30, 4, 3, 2, False, 3, 0, True, id="any-size-n-above-32"),
     pytest.param(27, 144, 30, 5, 2, False, 5, 0, False, id="model-of-null-batch-equals-count"),
@@ -370,6 +374,8 @@ STRETCH = [
     pytest.param(8, 5, 6, 3, 2, 3, 19, False, id="panel-ragged-second-tile-null-before"),
     pytest.param(8, 5, 6, 3, 2, 3, 19, True, id="panel-ragged-second-tile"),
     pytest.param(8, 5, 6, 3, 1, 2, 3, True, id="panel-var1-no-A2"),
+    pytest.param(17, 5, 3, 3, 2, 3, 19, True, id="panel-n-17-ragged-second-tile"),
+    pytest.param(32, 20, 3, 3, 2, 2, 3, False, id="panel-n-32-null-before"),
     pytest.param(40, 30, 4, 3, 2, 2, 3, False, id="any-size-null-before"),
     pytest.param(40, 30, 4, 3, 2, 2, 3, True, id="any-size"),
 ]
