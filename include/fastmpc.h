@@ -1251,6 +1251,82 @@ int fmpc_atm_screen_device(fmpc_atm a, int out_len, const double* mask, double s
 int fmpc_atm_get_state(fmpc_atm a, double* windows, long long* k, unsigned long long* counts, void* stream);
 int fmpc_atm_set_state(fmpc_atm a, const double* windows, long long k, const unsigned long long* counts, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Science camera on the device: the in-focus PSF of a batch of residual screens, accumulated over an exposure, and the wavefront
+ * statistics of every screen.  The reference sends phi_res = phi_distort + phi_cor "onto a scientific camera ... to measure the
+ * PSF" (README.md:10 of the reference); OOMAO's imager.m:92-133 is that camera: it accumulates frames over an exposure and
+ * reports a Strehl ratio, the accumulated frame's central value over that of a reference frame (imager.m:115).
+ *
+ * Definitions.  For a screen phi (len x len, column-major, radians) and a real pupil amplitude A >= 0 (len x len, column-major):
+ *   I[u,v]   = sum_{y,x} A[y,x] e^{i phi[y,x]} exp(-2 pi i ((u - d/2)(y - len/2) + (v - d/2)(x - len/2)) / (s len))
+ *   psf[u,v] = scale |I[u,v]|^2, stored column-major d x d (element (u, v) at u + d v, the order of the estimator's Y_M blocks).
+ *   s >= 1 is the sampling: samples per 1 / len cycles per pixel.
+ *   s = 1 is the reference's fftshift(fft2(fftshift(P))) (README.md:468-470): with the README's pin-hole pupil, scale = dx^4 AU,
+ *   len 512, d = 32 and phi = 0, psf[1:,1:] is the zero-diversity block of the reference's b_s.  An integer s > 1 is the window
+ *   around the centre of the DFT of the pupil field zero-padded ABOUT ITS CENTRE to s len.  It is NOT the reference's literal
+ *   fft2(fftshift(P), res, res) with res > len: that expression pads after the shift, which scrambles the field (0.52 of the
+ *   norm apart).  A window of a centred DFT is a partial DFT, so the sampling is a property of the table F alone and any real
+ *   s >= 1 costs the same two small matrix products.
+ * Quality of a screen, with weights a = A over the pixels A != 0 (FMPC_SCI_FIELDS doubles per screen):
+ *   FMPC_SCI_MEAN      mu = sum a phi / sum a
+ *   FMPC_SCI_RMS       sigma = sqrt(sum a (phi - mu)^2 / sum a)
+ *   FMPC_SCI_STREHL    |sum a e^{i phi}|^2 / (sum a)^2: the central sample over the unaberrated one, what imager.m:115 measures;
+ *                      with amplitude weights 1 - S = sigma^2 + O(sigma^4)
+ *   FMPC_SCI_MARECHAL  exp(-sigma^2)
+ *   FMPC_SCI_MIN, FMPC_SCI_MAX   of phi over the pupil
+ *   The variance comes from (weight, mean, M2) triples merged pairwise in a fixed order (Welford within a lane, Chan's merge above
+ *   it), never from sum a phi^2 - (sum a phi)^2 / sum a.
+ *
+ * fmpc_sci_create   len a multiple of 64 (as the estimator), d in {16, 32, 48, 64}, sampling >= 1 and finite, pupil: HOST array.
+ *                   Built on the host in long double before the device is touched: the len x d table, per row block of 16 the
+ *                   range of k-steps (4 columns) that see the pupil, sum A, sum A^2 and I0 = scale (sum A)^2.
+ * fmpc_sci_dims     any pointer may be NULL.
+ * fmpc_sci_workspace_bytes   the recommended workspace for a batch (batch <= 1: the minimum, one screen's slot; 0 for a NULL
+ *                   camera or batch < 0).  A slot holds T = P F of a screen for both halves of the few-screens form, 32 len d
+ *                   bytes, and its quality partials, 32 len bytes; a call walks over the batch in chunks of the slots it is given.
+ * fmpc_sci_expose_device   device pointers only.  scrn: batch x len x len.  image: batch x d x d or NULL; accumulate = 0 writes
+ *                   fl(scale |I|^2), accumulate = 1 writes image + fl(scale |I|^2), |I|^2 = fma(Im, Im, fl(Re Re)): each rounded
+ *                   once.  quality: batch rows of FMPC_SCI_FIELDS doubles, ldq doubles apart (0: FMPC_SCI_FIELDS), or NULL; what
+ *                   lies between the rows is left alone.  workspace: 8-byte aligned, at least fmpc_sci_workspace_bytes(cam, 1).
+ *                   A pupil pixel (A != 0) that is not finite or has |phi| >= 1e6 makes that screen's image and quality NaN and no
+ *                   other screen's; pixels with A = 0 never enter any arithmetic.  With image = NULL no matrix instruction is
+ *                   issued and the table is not read.  A realisation's bits do not depend on the batch, on its place in it, on
+ *                   the workspace or on which of image and quality are asked for.
+ * fmpc_sci_last_form   1: the last chunk ran one workgroup of 8 wavefronts per (screen, 16 rows); 2: the few-screens form, two
+ *                   workgroups of 4 (chunks of at most 256 (screen, 16 rows) pairs); 0: no call yet.  Same bits either way.
+ * fmpc_sci_summary_device   of an image accumulated over `frames` exposures, per realisation 2 + nrad doubles (nrad <= d / 2):
+ *                   out[0] = image[d/2, d/2] / (frames I0), the long-exposure Strehl ratio;
+ *                   out[1] = sum image / (frames scale (s len)^2 sum A^2), the share of the energy inside the window (Parseval);
+ *                   out[2 + rho] = the same quotient over the disc (u - d/2)^2 + (v - d/2)^2 <= rho^2: the encircled energy.
+ * fmpc_sci_tables_host   the host tables of fmpc_sci_create without a device: F_re, F_im (len x d row-major: F[y][j]), qrange
+ *                   (2 len / 16 ints), sums (sum A, sum A^2, I0); any output may be NULL.
+ * No call allocates or synchronises after fmpc_sci_create: every call can be recorded into a HIP graph.
+ * Answered before the device is touched, in this order: FMPC_E_NULL for a NULL out, pupil, camera, scrn, workspace, summary image
+ * or out, and for image and quality both NULL; FMPC_E_DIM for len < 1, d < 1, a sampling that is not finite or below 1, a scale
+ * that is not finite; FMPC_E_UNSUPPORTED for a len that is no multiple of 64 or above 8192 and a d outside {16, 32, 48, 64};
+ * FMPC_E_DIM for a negative or non-finite pupil value, a pupil without a pixel A > 0, batch < 0, accumulate outside {0, 1},
+ * ldq < 0 or 0 < ldq < FMPC_SCI_FIELDS, a workspace below one slot or not 8-byte aligned, frames < 1, nrad outside [0, d / 2].
+ * batch == 0 is FMPC_OK.
+ */
+#define FMPC_SCI_FIELDS    6
+#define FMPC_SCI_MEAN      0
+#define FMPC_SCI_RMS       1
+#define FMPC_SCI_STREHL    2
+#define FMPC_SCI_MARECHAL  3
+#define FMPC_SCI_MIN       4
+#define FMPC_SCI_MAX       5
+typedef struct fmpc_sci_s* fmpc_sci;
+int fmpc_sci_create(fmpc_sci* out, int len, int d, double sampling, const double* pupil, double scale, int device);
+int fmpc_sci_destroy(fmpc_sci cam);
+int fmpc_sci_dims(fmpc_sci cam, int* len, int* d, double* sampling, double* sumA, double* sumA2, double* I0);
+size_t fmpc_sci_workspace_bytes(fmpc_sci cam, int batch);
+int fmpc_sci_expose_device(fmpc_sci cam, int batch, const double* scrn, double* image, int accumulate, double* quality,
+                           long long ldq, void* workspace, size_t workspace_bytes, void* stream);
+int fmpc_sci_last_form(fmpc_sci cam);
+int fmpc_sci_summary_device(fmpc_sci cam, int batch, const double* image, int frames, int nrad, double* out, void* stream);
+int fmpc_sci_tables_host(int len, int d, double sampling, const double* pupil, double scale, double* F_re, double* F_im,
+                         int* qrange, double* sums);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,10 @@ from .modal import ModalFit, modal_workspace_bytes
 from .dm import GaussianDM, dm_matrix_workspace_bytes, reference_dm_geometry, reference_dm
 from .atmosphere import Atmosphere, reference_atmosphere, atm_covariance, atm_extruder, atm_displacement, atm_default_stencil
 from . import optics
-from .optics import zernike_modes, zernike_basis, zernike_grid, EstimatorOptics, reference_optics
+from .optics import zernike_modes, zernike_basis, zernike_grid, EstimatorOptics, reference_optics, reference_pupil, reference_science_camera
+from . import science
+from .science import (ScienceCamera, sci_tables_host, FMPC_SCI_FIELDS, FMPC_SCI_MEAN, FMPC_SCI_RMS, FMPC_SCI_STREHL, FMPC_SCI_MARECHAL,
+                      FMPC_SCI_MIN, FMPC_SCI_MAX, FMPC_SCI_FIELD_NAMES, FMPC_SCI_FORM_STANDARD, FMPC_SCI_FORM_FEW)
 from . import _lib
 
 __all__ = ["optics", "zernike_modes", "zernike_basis", "zernike_grid", "EstimatorOptics", "reference_optics","FastMPCHandle", "Fast_MPC2", "Fast_MPC2_VAR1", "deinterleave", "FastMPCError",
@@ -30,4 +33,6 @@ __all__ = ["optics", "zernike_modes", "zernike_basis", "zernike_grid", "Estimato
            "FMPC_KKT_FIELDS", "FMPC_KKT_RD", "FMPC_KKT_RP", "FMPC_KKT_NR", "FMPC_KKT_COST", "FMPC_KKT_BARRIER", "FMPC_KKT_MIN_SLACK",
            "FMPC_KKT_FIELD_NAMES", "FMPC_KKT_CONVERGED", "FMPC_KKT_INFEASIBLE", "ModalFit", "modal_workspace_bytes",
            "EstimatorNoise", "normal_noise", "normal_noise_host", "DetectorNoise", "detector_read", "detector_read_host", "GaussianDM", "dm_matrix_workspace_bytes", "reference_dm_geometry",
-           "reference_dm", "Atmosphere", "reference_atmosphere", "atm_covariance", "atm_extruder", "atm_displacement", "atm_default_stencil"]
+           "reference_dm", "science", "ScienceCamera", "sci_tables_host", "reference_pupil", "reference_science_camera", "FMPC_SCI_FIELDS", "FMPC_SCI_MEAN",
+           "FMPC_SCI_RMS", "FMPC_SCI_STREHL", "FMPC_SCI_MARECHAL", "FMPC_SCI_MIN", "FMPC_SCI_MAX", "FMPC_SCI_FIELD_NAMES", "FMPC_SCI_FORM_STANDARD",
+           "FMPC_SCI_FORM_FEW", "Atmosphere", "reference_atmosphere", "atm_covariance", "atm_extruder", "atm_displacement", "atm_default_stencil"]

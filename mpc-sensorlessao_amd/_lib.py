@@ -168,6 +168,14 @@ SIGNATURES = {
     "fmpc_atm_screen_device": (C.c_int, [_vp, C.c_int, _vp, C.c_double, _vp, _vp]),
     "fmpc_atm_get_state": (C.c_int, [_vp, _vp, C.POINTER(C.c_longlong), _vp, _vp]),
     "fmpc_atm_set_state": (C.c_int, [_vp, _vp, C.c_longlong, _vp, _vp]),
+    "fmpc_sci_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_double, _vp, C.c_double, C.c_int]),
+    "fmpc_sci_destroy": (C.c_int, [_vp]),
+    "fmpc_sci_dims": (C.c_int, [_vp, _ip, _ip, _dp, _dp, _dp, _dp]),
+    "fmpc_sci_workspace_bytes": (C.c_size_t, [_vp, C.c_int]),
+    "fmpc_sci_expose_device": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_longlong, _vp, C.c_size_t, _vp]),
+    "fmpc_sci_last_form": (C.c_int, [_vp]),
+    "fmpc_sci_summary_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "fmpc_sci_tables_host": (C.c_int, [C.c_int, C.c_int, C.c_double, _vp, C.c_double, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -190,9 +190,12 @@ class AOLoop:
     `true_coefficients`, the reference's ad_acc_valid, and changes nothing else.
     dm (optional): a `GaussianDM` on the estimator's grid (rows = cols = len); the residual screen of a step is then
     phase_valid[k] + sum_t u[k-1]_t I_t, the surface the mirror of Gaussian actuators makes (`fmpc_dm_surface_device`), instead of
-    the modal one; nothing else changes."""
+    the modal one; nothing else changes.
+    science (optional): a `ScienceCamera` on the estimator's grid; every step exposes the residual screen it has just formed
+    (`scrn`, column-major, no copy): `science_quality` (batch, FMPC_SCI_FIELDS) holds this step's rows, `science_image` (batch, d, d)
+    the exposure accumulated over `science_frames` steps since the last `science_reset()`; nothing else changes."""
 
-    def __init__(self, handle, estimator, Z, batch, n_newton=1, k=1e-2, one_call=True, modal=None, z_colmajor=False, dm=None):
+    def __init__(self, handle, estimator, Z, batch, n_newton=1, k=1e-2, one_call=True, modal=None, z_colmajor=False, science=None, dm=None):
         import ctypes as C
         import numpy as np
         import torch
@@ -225,6 +228,30 @@ class AOLoop:
         if dm is not None and (dm.rows != estimator.len or dm.cols != estimator.len or dm.m != m):
             raise ValueError("dm: need a GaussianDM of the handle's m actuators on the estimator's len x len grid")
         self.dm = dm
+        if science is not None and science.len != estimator.len:
+            raise ValueError("science: need a ScienceCamera on the estimator's len x len grid")
+        self.science = science
+        if science is not None:
+            from .science import FMPC_SCI_FIELDS
+            self.science_image = torch.zeros((batch, science.d, science.d), **f64)
+            self.science_quality = torch.zeros((batch, FMPC_SCI_FIELDS), **f64)
+            self.science_frames = 0
+            self._science_ws = torch.empty(science.workspace_bytes(batch), dtype=torch.uint8, device=dev)
+
+    def science_reset(self):
+        """Start a new exposure: the accumulated image and the frame count go back to zero (after the uncorrected first step, say)."""
+        if self.science is None:
+            raise ValueError("science_reset: this loop was built without science=")
+        self.science_image.zero_()
+        self.science_frames = 0
+
+    def science_summary(self, nrad=None):
+        """`ScienceCamera.summary` of the current exposure: long-exposure Strehl, window energy, encircled energy."""
+        if self.science is None:
+            raise ValueError("science_summary: this loop was built without science=")
+        if self.science_frames < 1:
+            raise ValueError("science_summary: no frame since the last science_reset")
+        return self.science.summary(self.science_image, self.science_frames, nrad)
 
     def true_coefficients(self, phase_k, workspace=None, out=None):
         """The modal fit of the incoming screens with the piston dropped (zernmodfit of phase_valid(:,:,k): a row of ad_acc_valid,
@@ -256,6 +283,10 @@ class AOLoop:
             if rc != 0:
                 from ._lib import FastMPCError
                 raise FastMPCError(rc, "fmpc_phase_residual_device")
+        if self.science is not None:         # the camera sees the residual wavefront the estimator sees
+            self.science.expose(self.scrn, image=self.science_image, accumulate=True, quality=self.science_quality, colmajor=True,
+                                workspace=self._science_ws)
+            self.science_frames += 1
         # x0 = ad_est, x0_pre = the previous ad_est (README.md:482-488): two buffers in turn, the estimator writes into this step's
         self.x0, self.x0_pre = self._xb[s % 2], self._xb[(s + 1) % 2]
         if s == 0:

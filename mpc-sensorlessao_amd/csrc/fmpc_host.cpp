@@ -1593,3 +1593,64 @@ extern "C" int fmpc_atm_displacement_host(long long k, double px_per_step, long 
     *frac = d - n;
     return FMPC_OK;
 }
+
+// ---- science camera (include/fastmpc.h: fmpc_sci; layouts: fmpc_science.h)
+int fmpc_host_sci_check(int len, int d, double sampling, double scale) {
+    if (len < 1 || d < 1 || !std::isfinite(sampling) || sampling < 1.0 || !std::isfinite(scale)) return FMPC_E_DIM;
+    if (len % 64 != 0 || len > FMPC_SCI_MAXLEN || (d != 16 && d != 32 && d != 48 && d != 64)) return FMPC_E_UNSUPPORTED;
+    return FMPC_OK;
+}
+
+int fmpc_host_sci_tables(int len, int d, double sampling, const double* pupil, double scale, FmpcSciTables& out) {
+    typedef long double ld;
+    const int rc = fmpc_host_sci_check(len, d, sampling, scale);
+    if (rc != FMPC_OK) return rc;
+    const size_t npx = (size_t)len * len;
+    ld sa = 0.0L, sa2 = 0.0L;
+    for (size_t i = 0; i < npx; ++i) {
+        if (!std::isfinite(pupil[i]) || pupil[i] < 0.0) return FMPC_E_DIM;
+        sa += (ld)pupil[i]; sa2 += (ld)pupil[i] * (ld)pupil[i];
+    }
+    if (!(sa > 0.0L)) return FMPC_E_DIM;                                  // an all-zero pupil has no Strehl ratio
+    out.sumA = (double)sa; out.sumA2 = (double)sa2; out.I0 = (double)((ld)scale * sa * sa);
+    // F[y][j] = exp(-2 pi i (j - d/2)(y - len/2) / (s len)) as operand images [len / 4][d / 16][re, im][64 lanes],
+    // lane = 16 (y mod 4) + (j mod 16).  The turn count n / (s len) is reduced to [-1/2, 1/2] before it meets 2 pi: in integers
+    // where s len is one, in long double otherwise (|n| <= 32 len / 2: the quotient is good to 1e-18 of a turn).
+    const ld two_pi = 6.283185307179586476925286766559L;
+    const ld period = (ld)sampling * (ld)len;
+    const bool whole = period == floorl(period) && period < 1.0e15L;
+    const long long M = whole ? (long long)period : 0;
+    const int nt = d / 16;
+    out.Fimg.assign((size_t)(len / 4) * nt * 2 * 64, 0.0);
+    for (int y = 0; y < len; ++y)
+        for (int j = 0; j < d; ++j) {
+            const long long n = (long long)(j - d / 2) * (long long)(y - len / 2);
+            ld turn;
+            if (whole) turn = (ld)(((n % M) + M) % M) / (ld)M;
+            else { turn = (ld)n / period; turn -= roundl(turn); }
+            const ld ang = -two_pi * turn;
+            const size_t base = (((size_t)(y / 4) * nt + (j / 16)) * 2) * 64 + (size_t)(y % 4) * 16 + (j % 16);
+            out.Fimg[base] = (double)cosl(ang);
+            out.Fimg[base + 64] = (double)sinl(ang);
+        }
+    fmpc_host_estimator_qranges(len, 1, pupil, pupil, out.qr);           // (the k-steps with a pixel A != 0)
+    return FMPC_OK;
+}
+
+extern "C" int fmpc_sci_tables_host(int len, int d, double sampling, const double* pupil, double scale, double* F_re, double* F_im,
+                                    int* qrange, double* sums) {
+    if (!pupil) return FMPC_E_NULL;
+    FmpcSciTables t;
+    const int rc = fmpc_host_sci_tables(len, d, sampling, pupil, scale, t);
+    if (rc != FMPC_OK) return rc;
+    const int nt = d / 16;
+    for (int y = 0; y < len && (F_re || F_im); ++y)
+        for (int j = 0; j < d; ++j) {
+            const size_t base = (((size_t)(y / 4) * nt + (j / 16)) * 2) * 64 + (size_t)(y % 4) * 16 + (j % 16);
+            if (F_re) F_re[(size_t)y * d + j] = t.Fimg[base];
+            if (F_im) F_im[(size_t)y * d + j] = t.Fimg[base + 64];
+        }
+    if (qrange) memcpy(qrange, t.qr.data(), t.qr.size() * sizeof(int));
+    if (sums) { sums[0] = t.sumA; sums[1] = t.sumA2; sums[2] = t.I0; }
+    return FMPC_OK;
+}

@@ -264,8 +264,20 @@ double fmpc_host_sum(const double* v, int cnt);
 struct fmpc_detector_s;
 int fmpc_host_detector_check(const struct fmpc_detector_s* det, int batch);
 
+// ---- science camera (include/fastmpc.h: fmpc_sci; layouts: fmpc_science.h)
+#define FMPC_SCI_MAXLEN 8192
+// The argument rules of a camera: FMPC_E_DIM for len < 1, d < 1, a sampling that is not finite or below 1, a scale that is not
+// finite; FMPC_E_UNSUPPORTED for a len that is no multiple of 64 or beyond FMPC_SCI_MAXLEN and a d outside {16, 32, 48, 64}.
+int fmpc_host_sci_check(int len, int d, double sampling, double scale);
+// The constant operands of a camera, in long double: the len x d DFT factors F[y][j] = exp(-2 pi i (j - d/2)(y - len/2) / (s len))
+// as operand images [len / 4][d / 16][re, im][64 lanes] (lane = 16 (y mod 4) + (j mod 16)); qr as fmpc_host_estimator_qranges for
+// the pixels A != 0; sum A, sum A^2 and I0 = scale (sum A)^2.  pupil: len x len column-major.  The rules above, then FMPC_E_DIM
+// for a negative or non-finite pupil value and for a pupil without a pixel A > 0.
+struct FmpcSciTables { std::vector<double> Fimg; std::vector<int> qr; double sumA = 0.0, sumA2 = 0.0, I0 = 0.0; };
+int fmpc_host_sci_tables(int len, int d, double sampling, const double* pupil, double scale, FmpcSciTables& out);
+
 // ---- Zernike functions (zernfun.m, zernmodfit.m)
-#define FMPC_ZERNIKE_MAXN 14            // radial orders whose coefficients are exact in a double (14! < 2^53)
+#define FMPC_ZERNIKE_MAXN 14           // radial orders whose coefficients are exact in a double (14! < 2^53)
 #define FMPC_ZERNIKE_NCOEF 204          // coefficients of every radial polynomial R_n^|m| with n <= 14
 // The (n, m) pairs of zernmodfit.m:195-198: for n = 0..N, m = -n, -n + 2, .., n.  Returns (N + 1)(N + 2) / 2 (0 for N < 0);
 // n_out, m_out may be NULL (count only).

@@ -156,6 +156,23 @@ class EstimatorOptics:
         return PhaseDiversityEstimator._from_handle(h, self.device)
 
 
+def reference_pupil(length=512, dx=6.5e-6):
+    """The README's pin-hole pupil (README.md:383-391): 1 where the spatial frequency is within (length / 2 - 1) df of the centre,
+    a host array (length, length) indexed [row, column]."""
+    length = int(length)
+    df = 1.0 / (length * dx)
+    fx = np.arange(-length // 2, length // 2) * df
+    FX, FY = np.meshgrid(fx, -fx)
+    return (np.sqrt(FX ** 2 + FY ** 2) <= (length / 2 - 1) * df).astype(np.float64)
+
+
+def reference_science_camera(d=32, sampling=1.0, length=512, device=0):
+    """A `ScienceCamera` behind the README's pin-hole pupil with its dx = 6.5e-6 and AU = 1e12: at sampling 1 and d = 32 the
+    image of a zero screen is the zero-diversity block of the reference's b_s (its first row and column apart)."""
+    from .science import ScienceCamera
+    return ScienceCamera(reference_pupil(length, 6.5e-6), d=d, sampling=sampling, dx=6.5e-6, AU=1e12, device=device)
+
+
 def reference_optics(length=512, dx=6.5e-6, N=6, zd_dist=3.0, AU=1e12, device=0):
     """The README's geometry (README.md:366-396): the pin-hole pupil, defocus (mode index 4 of zernmodfit's order, unnormalised)
     as the diversity, zd_list = [-3 0 3], the window |x| <= 1e-4 m (31 samples on the 512 grid).  Returns an `EstimatorOptics`
@@ -163,10 +180,7 @@ def reference_optics(length=512, dx=6.5e-6, N=6, zd_dist=3.0, AU=1e12, device=0)
     (1-based), `.dx`, `.AU` and `.pupil` (host)."""
     length = int(length)
     Z = zernike_grid(N, length, device=device)
-    df = 1.0 / (length * dx)
-    fx = np.arange(-length // 2, length // 2) * df
-    FX, FY = np.meshgrid(fx, -fx)
-    pupil = (np.sqrt(FX ** 2 + FY ** 2) <= (length / 2 - 1) * df).astype(np.float64)      # README.md:383-391
+    pupil = reference_pupil(length, dx)
     xaxis = np.arange(-length // 2, length // 2) * dx
     rmin = int(np.nonzero(np.abs(xaxis + 1.0e-4) < 3e-6)[0][0]) + 1                       # README.md:378-379 (1-based)
     rmax = int(np.nonzero(np.abs(xaxis - 1.0e-4) < 3e-6)[0][-1]) + 1
