@@ -85,6 +85,183 @@ extern "C" const char* fmpc_strerror(int code) {
 
 extern "C" int fmpc_step_ld(int n_newton) { return n_newton > 0 ? n_newton : 1000; }
 
+// Environment switches: NAME=1 (first character `c`) switches on, a number is read with atoi (unset or empty: the default)
+static bool fmpc_env_on(const char* name, char c = '1') { const char* e = getenv(name); return e && e[0] == c; }
+static int fmpc_env_int(const char* name, int dflt) { const char* e = getenv(name); return e && e[0] ? atoi(e) : dflt; }
+
+// ---- fmpc_create in stages.  Every stage returns an FMPC code; fmpc_create destroys the handle when one fails.
+// Which kernels of the per-problem-factor path take the model: the generic kernel (n <= 64 and its tiles fit the LDS), else the
+// tiled kernel in fp64 (n <= 47), else the tiled kernel with an fp32 factor (n <= 79: "fp32 mixed precision", BASELINE configs[4])
+struct FmpcPaths { bool generic_ok, generic_big, tiled64_any; size_t lds; };
+static int fmpc_pick_paths(int n, int m, int nb, bool denseQ, bool denseR, FmpcPaths& P) {
+    P.lds = fmpc_generic_lds_bytes(n, m);
+    P.generic_ok = !denseQ && !denseR && n <= 64 && P.lds <= FMPC_LDS_LIMIT;
+    // (fp64 tiled instances of 4 and 5 blocks of 16, 47 < n <= 79: round 5)
+    int NB64 = 0;
+    P.tiled64_any = fmpc_tiled_supports(n, m, nb, 0, &NB64, nullptr, denseR);
+    // (likewise the fp32-factor instances of 6 and 7 blocks, 79 < n <= 111: on request; the default beyond n = 79 is the exact fp64 fallback)
+    int NB32 = 0;
+    const bool tiled32_any = fmpc_tiled_supports(n, m, nb, 1, &NB32, nullptr, denseR);
+    const bool tiled64 = P.tiled64_any && NB64 <= 3, tiled32 = tiled32_any && NB32 <= 5;
+    // Any other size with diagonal weights (the reference checks shapes only, fast_mpc_objective.m:17-47): the generic kernel
+    // with its tiles in the HBM workspace ("big": a size fallback, fp64, no speed claim).  FMPC_GENERIC_BIG=1 forces it (tests).
+    P.generic_big = false;
+    if ((!P.generic_ok && !tiled64 && !tiled32) || fmpc_env_on("FMPC_GENERIC_BIG"))
+        P.generic_big = fmpc_generic_big_lds_bytes(n, m) <= FMPC_LDS_LIMIT;     // (dense Q, Qf, R: taken)
+    if (P.generic_big) { P.generic_ok = true; P.lds = fmpc_generic_big_lds_bytes(n, m); }
+    if (!P.generic_ok && !tiled64 && !tiled32) return FMPC_E_UNSUPPORTED;
+    if (!P.generic_ok) P.lds = 0;
+    return FMPC_OK;
+}
+
+static void fmpc_read_switches(fmpc_handle h) {
+    h->rc_disabled = fmpc_env_on("FMPC_NO_RAMP_COLD");
+    if (fmpc_env_on("FMPC_FORCE_GENERIC")) h->prefer_tiled = 0;
+    h->force_tiled = fmpc_env_on("FMPC_TILED");
+    h->small_tiled = !fmpc_env_on("FMPC_NO_SMALL_TILED");
+    h->small_nw = fmpc_env_on("FMPC_SMALL_TILED_NW", '2') ? 2 : 4;      // (four: the default again, round 5)
+    h->fa_disabled = fmpc_env_on("FMPC_NO_AFFINE");
+    h->fl_disabled = fmpc_env_on("FMPC_NO_LOOP_U0");
+    h->fs_disabled = fmpc_env_on("FMPC_NO_LOOP_FUSE");
+    h->fs_min_batch = fmpc_env_int("FMPC_PRODUCT_MIN_BATCH", FMPC_PRODUCT_MIN_BATCH_DEFAULT);
+    if (h->fs_min_batch < 1) h->fs_min_batch = FMPC_PRODUCT_MIN_BATCH_DEFAULT;
+    h->fm_disabled = fmpc_env_on("FMPC_NO_FIRST_MOVE");
+    h->bfm.disabled = fmpc_env_on("FMPC_NO_BANK_FIRST_MOVE");
+    h->gn_split = !fmpc_env_on("FMPC_NO_GENERAL_SPLIT");
+}
+
+static int fmpc_query_device(fmpc_handle h) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) return FMPC_E_HIP;
+    h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    h->wg_per_cu = h->lds_bytes ? std::max(1, std::min(8, (int)(FMPC_LDS_LIMIT / h->lds_bytes))) : 1;
+    if (h->generic_big && h->wg_per_cu > 2) h->wg_per_cu = 2;      // (a workspace slot holds the whole factor: nb 3 n (n + 1) doubles)
+    return FMPC_OK;
+}
+
+// The model on the device: one pool of doubles, one of block ids, and the FmpcDevModel pointers into them
+static int fmpc_upload_model(fmpc_handle h) {
+    const FmpcHostModel& M = h->hm;
+    const int n = h->n, m = h->m, nn = n * n;
+    std::vector<double> a1t(nn), a2t(nn);
+    for (int rr = 0; rr < n; ++rr)
+        for (int c = 0; c < n; ++c) { a1t[c * n + rr] = M.a1[rr * n + c]; a2t[c * n + rr] = M.a2[rr * n + c]; }
+    FmpcDevModel& D = h->dev;
+    D.n = n; D.m = m; D.T = h->T; D.nb = h->nb; D.has_xf = h->has_xf; D.var2 = M.var2; D.denseQ = M.denseQ; D.denseR = M.denseR;
+    // the pool in this order, every array on a 16-byte boundary; `dst` gets its address once the pool is on the device
+    std::vector<double> pool;
+    std::vector<std::pair<const double**, size_t>> where;
+    auto push = [&](const double*& dst, const std::vector<double>& v) {
+        where.push_back({&dst, pool.size()});
+        pool.insert(pool.end(), v.begin(), v.end());
+        while (pool.size() % 2) pool.push_back(0.0);
+    };
+    push(D.A1, M.a1); push(D.A2, M.a2); push(D.A1t, a1t); push(D.A2t, a2t); push(D.Bt, M.bt);
+    push(D.R2, M.R2); push(D.Q2, M.Q2); push(D.Qf2, M.Qf2); push(D.rl, M.rl); push(D.ql, M.ql); push(D.qfl, M.qfl);
+    push(D.umin, M.umin); push(D.umax, M.umax); push(D.umid, M.umid); push(D.xmid, M.xmid);
+    push(D.xf, M.has_xf ? M.xf : std::vector<double>(n, 0.0));
+    push(D.Q2m, M.q2m); push(D.Qf2m, M.qf2m); push(D.Xm, M.xm); push(D.Xfm, M.xfm);      // (dense Q, Qf: the generic kernel's workspace instance)
+    D.R2m = nullptr;
+    if (M.denseR) push(D.R2m, M.r2full);
+    push(h->loop_M1, M.m1); push(h->loop_M2, M.m2); push(D.Yblk, M.blocks);
+    std::vector<int> ipool(M.idxD);
+    ipool.insert(ipool.end(), M.idx1.begin(), M.idx1.end());
+    ipool.insert(ipool.end(), M.idx2.begin(), M.idx2.end());
+    int rc = h->pool_d.assign(pool.data(), pool.size(), nullptr);
+    if (rc == FMPC_OK) rc = h->pool_i.assign(ipool.data(), ipool.size(), nullptr);
+    if (rc != FMPC_OK) return rc;
+    for (auto& w : where) *w.first = h->pool_d + w.second;
+    D.idxD = h->pool_i; D.idx1 = h->pool_i + h->nb; D.idx2 = h->pool_i + 2 * h->nb;
+    return FMPC_OK;
+}
+
+// Wave kernel: MFMA-layout images of the constant blocks (+ a zero block), padded B'
+static int fmpc_setup_wave(fmpc_handle h) {
+    const FmpcHostModel& M = h->hm;
+    const int n = h->n, m = h->m, mp = fmpc_wave_mp(m);
+    if (M.denseQ || M.denseR || !fmpc_wave_supports(n) || fmpc_env_on("FMPC_FORCE_GENERIC") ||
+        fmpc_wave_lds_bytes(n, mp) > FMPC_LDS_LIMIT) return FMPC_OK;
+    const int stride = fmpc_wave_img_stride(n);
+    const int nblk = (int)(M.blocks.size() / ((size_t)n * n));
+    std::vector<double> wpool((size_t)(nblk + 1) * stride, 0.0);      // last = zero block
+    for (int k = 0; k < nblk; ++k) fmpc_wave_make_images(n, M.blocks.data() + (size_t)k * n * n, wpool.data() + (size_t)k * stride);
+    const size_t oBtP = wpool.size();
+    wpool.resize(oBtP + (size_t)mp * 33, 0.0);
+    for (int c = 0; c < m; ++c)
+        for (int rr = 0; rr < n; ++rr) wpool[oBtP + (size_t)c * 33 + rr] = M.bt[(size_t)c * n + rr];
+    std::vector<int> wi;
+    for (int i = 0; i < h->nb; ++i) wi.push_back(M.idxD[i]);
+    for (int i = 0; i < h->nb; ++i) wi.push_back(M.idx1[i] >= 0 ? M.idx1[i] : nblk);
+    for (int i = 0; i < h->nb; ++i) wi.push_back(M.idx2[i] >= 0 ? M.idx2[i] : nblk);
+    int rc = h->wave_pool_d.assign(wpool.data(), wpool.size(), nullptr);
+    if (rc == FMPC_OK) rc = h->wave_pool_i.assign(wi.data(), wi.size(), nullptr);
+    if (rc != FMPC_OK) return rc;
+    h->wave.mp = mp; h->wave.img = h->wave_pool_d; h->wave.BtP = h->wave_pool_d + oBtP;
+    h->wave.iD = h->wave_pool_i; h->wave.i1 = h->wave_pool_i + h->nb; h->wave.i2 = h->wave_pool_i + 2 * h->nb;
+    h->wave_lds = fmpc_wave_lds_bytes(n, mp);
+    if (fmpc_wave_prepare(n, h->wave_lds) != hipSuccess) return FMPC_E_HIP;
+    h->use_wave = 1;
+    return FMPC_OK;
+}
+
+// Shared cold-start factor of the wave path (fmpc_handle_s::sh_fac): its buffers and the buffer of the cold-start constants (fmpc_upload_cold)
+static int fmpc_setup_shared_cold(fmpc_handle h) {
+    const int n = h->n, m = h->m, T = h->T;
+    if (!h->use_wave || fmpc_env_on("FMPC_NO_SHARED") || h->nb * n > 840) return FMPC_OK;     // the cold path keeps rhs/y/d_nu in an 840-double LDS vector
+    const size_t nf = fmpc_wave_shared_fac_doubles(n, h->nb);
+    const size_t nscr = (size_t)T * (n + m) + 64 + (size_t)n;      // zero state + z of the export solve
+    if (h->sh_fac.alloc(nf, nullptr) != FMPC_OK || h->sh_rs.alloc((size_t)h->nb * 32, nullptr) != FMPC_OK ||
+        h->sh_ok.alloc(1, nullptr) != FMPC_OK || h->sh_scratch.alloc(nscr, nullptr) != FMPC_OK) return FMPC_E_ALLOC;
+    (void)hipMemset(h->sh_ok, 0, sizeof(int));
+    (void)hipMemset(h->sh_scratch, 0, nscr * sizeof(double));
+    int off9[14];
+    fmpc_wave_cold_layout(n, h->wave.mp, off9);
+    if (h->cold_d.alloc((size_t)off9[8], nullptr) != FMPC_OK) return FMPC_E_ALLOC;
+    h->sh_enabled = 1;
+    return FMPC_OK;
+}
+
+// Panel kernel: needs the panel + images in LDS
+static int fmpc_setup_panel(fmpc_handle h) {
+    const int n = h->n, m = h->m, T = h->T;
+    const int pmp = (m + 15) & ~15;
+    const size_t plds = fmpc_panel_lds_bytes(h->nb, pmp);
+    if (!h->sh_enabled || n != FP_N || fmpc_env_on("FMPC_NO_PANEL") || plds > FMPC_LDS_LIMIT) return FMPC_OK;
+    h->pn_in.mp = pmp;
+    size_t o = 0;
+    fmpc_host_panel_layout(n, m, T, h->nb, pmp, h->pn_in, &h->pn_o_dump, &o, &h->pn_dz_len);      // pool layout (fmpc_host.cpp)
+    if (h->pn_pool.alloc(o, nullptr) != FMPC_OK || h->pn_cnt.alloc(2, nullptr) != FMPC_OK || h->fa_nflag.alloc(4, nullptr) != FMPC_OK ||
+        h->fw_chain.alloc((size_t)FMPC_STRETCH_MAX * sizeof(FwParams), nullptr) != FMPC_OK ||
+        h->pn_sched.alloc((size_t)2 * FP_MAX_STEPS(h->nb) * FP_STEP_INTS, nullptr) != FMPC_OK) return FMPC_E_ALLOC;
+    (void)hipMemset(h->pn_cnt, 0, 2 * sizeof(int));     // [handed over, length of the continuation list]
+    (void)hipMemset(h->fa_nflag, 0, 4 * sizeof(int));
+    if (h->pn_cnt_host.alloc(2, nullptr) != FMPC_OK) return FMPC_E_ALLOC;
+    h->pn_cnt_host[0] = -1; h->pn_cnt_host[1] = -1;   // nothing known yet
+    h->pn_dz_lds = fmpc_dz_lds_bytes(pmp, 1);
+    if (fmpc_panel_prepare(plds) != hipSuccess || fmpc_dz_prepare(pmp) != hipSuccess) return FMPC_E_HIP;
+    h->pn_mp = pmp; h->pn_lds = plds; h->pn_enabled = 1;
+    return FMPC_OK;
+}
+
+// Dense form of the cold-start dual solve: FMPC_NO_INV=1 switches it off, FMPC_INV_MAX_BATCH bounds its use when w is given
+static int fmpc_setup_inverse(fmpc_handle h) {
+    const int n = h->n, T = h->T;
+    if (!h->pn_enabled) return FMPC_OK;
+    h->inv_enabled = !fmpc_env_on("FMPC_NO_INV");
+    h->inv_fuse = fmpc_env_on("FMPC_FUSE_DZ");                    // (measured slower: DESIGN.md §7; off unless asked for)
+    h->inv_max_batch = fmpc_env_int("FMPC_INV_MAX_BATCH", h->inv_max_batch);
+    h->inv_jks = FP_XKS + (T * n + 3) / 4;
+    h->inv_jks2 = 2 * FP_XKS;                       // [x0 ; x0_pre ; 0 0 ; B u1 ; B u2 ; 0 0]
+    const size_t nrt = ((size_t)h->nb * n + 15) / 16;
+    if (h->inv_enabled && (h->inv_jimg.alloc(nrt * (size_t)(16 * ((h->inv_jks + 15) / 16 + 3)) * 64, nullptr) != FMPC_OK ||
+                           h->inv_nuc.alloc(nrt * 16, nullptr) != FMPC_OK ||
+                           h->inv_eimg.alloc(4 * FP_XKS * 64, nullptr) != FMPC_OK ||
+                           h->inv_jst.alloc((size_t)h->nb * 2 * FP_XKS * 64, nullptr) != FMPC_OK ||
+                           h->inv_nucst.alloc((size_t)h->nb * 32, nullptr) != FMPC_OK ||
+                           h->inv_jimg2.alloc(nrt * (size_t)(16 * ((2 * FP_XKS + 15) / 16 + 3)) * 64, nullptr) != FMPC_OK)) return FMPC_E_ALLOC;
+    return FMPC_OK;
+}
+
 extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
                            const double* A1, const double* A2, const double* B,
                            const double* Q, const double* R, const double* Qf,
@@ -98,305 +275,37 @@ extern "C" int fmpc_create(fmpc_handle* out, int n, int m, int T, int var_order,
     if (!A1 || !B || (var_order == 2 && !A2)) return FMPC_E_NULL;   // fast_mpc_eq_const.m:19-25
     if (!Q || !R || !Qf || !x_min || !x_max || !u_min || !u_max) return FMPC_E_NULL;
     if (device < 0) return FMPC_E_NO_DEVICE;
-    // dense (symmetric positive definite) R: fast_mpc_objective.m:51-54 takes any square R.  Handled by the tiled kernel in
-    // fp64 (a per-stage m x m factorisation in LDS): n <= 47 and m (m + 1) / 2 + m (n + 2) doubles of LDS.
-    const bool denseR = !fmpc_host_is_diag(R, m);
-    // dense (symmetric positive definite) Q, Qf: fast_mpc_objective.m:52-55 takes any square Q, Qf.  Handled by the
-    // tiled kernel only (the other kernels keep the state weights as diagonals).
-    const bool denseQ = !fmpc_host_is_diag(Q, n) || !fmpc_host_is_diag(Qf, n);
-    for (int i = 0; i < n; ++i)
-        if (!(fmpc_host_cm(Q, n, i, i) > 0.0) || !(fmpc_host_cm(Qf, n, i, i) > 0.0)) return FMPC_E_NOT_PD_PHI;
-    for (int i = 0; i < m; ++i)
-        if (!(fmpc_host_cm(R, m, i, i) > 0.0)) return FMPC_E_NOT_PD_PHI;
-    if (denseQ)
-        for (int a = 0; a < n; ++a)
-            for (int b = 0; b < a; ++b)
-                if (fmpc_host_cm(Q, n, a, b) != fmpc_host_cm(Q, n, b, a) || fmpc_host_cm(Qf, n, a, b) != fmpc_host_cm(Qf, n, b, a)) return FMPC_E_NOT_PD_PHI;
-    std::vector<double> R2full;
-    if (denseR) {
-        R2full.assign((size_t)m * m, 0.0);
-        for (int a = 0; a < m; ++a)
-            for (int b = 0; b < m; ++b) {
-                if (fmpc_host_cm(R, m, a, b) != fmpc_host_cm(R, m, b, a)) return FMPC_E_NOT_PD_PHI;
-                R2full[(size_t)a * m + b] = 2.0 * fmpc_host_cm(R, m, a, b);
-            }
-        std::vector<double> tmp;
-        if (!fmpc_host_spd_inverse(R2full, m, tmp)) return FMPC_E_NOT_PD_PHI;      // (the inverse itself is not used: a positive definiteness test)
-    }
-    // per-problem-factor paths: the generic kernel (n <= 64 and its tiles fit the LDS), else the tiled kernel in fp64
-    // (n <= 47), else the tiled kernel with an fp32 factor (n <= 79: "fp32 mixed precision", BASELINE configs[4])
-    size_t lds = fmpc_generic_lds_bytes(n, m);
-    bool generic_ok = !denseQ && !denseR && n <= 64 && lds <= FMPC_LDS_LIMIT;
-    const int nb_ = T + (xf ? 1 : 0);
-    // (fp64 tiled instances of 4 and 5 blocks of 16, 47 < n <= 79: round 5)
-    int NB64 = 0;
-    const bool tiled64_any = fmpc_tiled_supports(n, m, nb_, 0, &NB64, nullptr, denseR);
-    // (likewise the fp32-factor instances of 6 and 7 blocks, 79 < n <= 111: on request; the default beyond n = 79 is the exact fp64 fallback)
-    int NB32 = 0;
-    const bool tiled32_any = fmpc_tiled_supports(n, m, nb_, 1, &NB32, nullptr, denseR);
-    const bool tiled64 = tiled64_any && NB64 <= 3, tiled32 = tiled32_any && NB32 <= 5;
-    // Any other size with diagonal weights (the reference checks shapes only, fast_mpc_objective.m:17-47): the generic kernel
-    // with its tiles in the HBM workspace ("big": a size fallback, fp64, no speed claim).  FMPC_GENERIC_BIG=1 forces it (tests).
-    bool generic_big = false;
-    { const char* fb = getenv("FMPC_GENERIC_BIG");
-      if ((!generic_ok && !tiled64 && !tiled32) || (fb && fb[0] == '1'))
-          generic_big = fmpc_generic_big_lds_bytes(n, m) <= FMPC_LDS_LIMIT; }   // (dense Q, Qf, R: taken)
-    if (generic_big) { generic_ok = true; lds = fmpc_generic_big_lds_bytes(n, m); }
-    if (!generic_ok && !tiled64 && !tiled32) return FMPC_E_UNSUPPORTED;
-    if (!generic_ok) lds = 0;
+    FmpcHostModel hm;
+    int rc = fmpc_host_model_classify(n, m, Q, R, Qf, hm);        // (fmpc_host.cpp)
+    if (rc != FMPC_OK) return rc;
+    FmpcPaths paths;
+    rc = fmpc_pick_paths(n, m, T + (xf ? 1 : 0), hm.denseQ, hm.denseR, paths);
+    if (rc != FMPC_OK) return rc;
 
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return FMPC_E_NO_DEVICE;
-    if (device >= ndev) return FMPC_E_NO_DEVICE;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device >= ndev) return FMPC_E_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return FMPC_E_HIP;
 
     fmpc_handle h = new (std::nothrow) fmpc_handle_s();
     if (!h) return FMPC_E_ALLOC;
     h->n = n; h->m = m; h->T = T; h->var_order = var_order; h->has_xf = xf ? 1 : 0;
-    h->nb = T + h->has_xf; h->device = device;
-    h->lds_bytes = lds;
-    { const char* e = getenv("FMPC_NO_RAMP_COLD"); h->rc_disabled = (e && e[0] == '1') ? 1 : 0; }
-    h->generic_ok = generic_ok ? 1 : 0; h->generic_big = generic_big ? 1 : 0;
-    { const char* fg = getenv("FMPC_FORCE_GENERIC"); h->prefer_tiled = (tiled64_any && !generic_big && !(fg && fg[0] == '1')) ? 1 : 0; }
+    h->nb = T + h->has_xf; h->device = device; h->lds_bytes = paths.lds;
+    h->generic_ok = paths.generic_ok ? 1 : 0; h->generic_big = paths.generic_big ? 1 : 0;
+    h->prefer_tiled = (paths.tiled64_any && !paths.generic_big) ? 1 : 0;      // (FMPC_FORCE_GENERIC=1: off, fmpc_read_switches)
     // fp64 wherever an fp64 kernel on the matrix cores (or the generic kernel) exists -- the reference is fp64 throughout and the literal
     // drop-in call (fmpc_solve_once) has no precision argument; the fp32 factor (BASELINE configs[4]) is a request since round 5
-    h->prec = (generic_ok || tiled64_any) ? FMPC_PREC_F64 : FMPC_PREC_F32_MIXED;
-    { const char* ft = getenv("FMPC_TILED"); h->force_tiled = (ft && ft[0] == '1') ? 1 : 0; }
-    { const char* ns = getenv("FMPC_NO_SMALL_TILED"); h->small_tiled = (ns && ns[0] == '1') ? 0 : 1; }
-    { const char* nw = getenv("FMPC_SMALL_TILED_NW"); h->small_nw = (nw && nw[0] == '2') ? 2 : 4; }      // (four: the default again, round 5)
-    { const char* na = getenv("FMPC_NO_AFFINE"); h->fa_disabled = (na && na[0] == '1') ? 1 : 0; }
-    { const char* na = getenv("FMPC_NO_LOOP_U0"); h->fl_disabled = (na && na[0] == '1') ? 1 : 0; }
-    { const char* na = getenv("FMPC_NO_LOOP_FUSE"); h->fs_disabled = (na && na[0] == '1') ? 1 : 0; }
-    { const char* na = getenv("FMPC_PRODUCT_MIN_BATCH"); h->fs_min_batch = (na && atoi(na) >= 1) ? atoi(na) : FMPC_PRODUCT_MIN_BATCH_DEFAULT; }
-    { const char* nf = getenv("FMPC_NO_FIRST_MOVE"); h->fm_disabled = (nf && nf[0] == '1') ? 1 : 0; }
-    { const char* nf = getenv("FMPC_NO_BANK_FIRST_MOVE"); h->bfm.disabled = (nf && nf[0] == '1') ? 1 : 0; }
-    { const char* gs = getenv("FMPC_NO_GENERAL_SPLIT"); h->gn_split = (gs && gs[0] == '1') ? 0 : 1; }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { delete h; return FMPC_E_HIP; }
-    h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    h->wg_per_cu = lds ? (int)(FMPC_LDS_LIMIT / lds) : 1;
-    if (h->wg_per_cu < 1) h->wg_per_cu = 1;
-    if (h->wg_per_cu > 8) h->wg_per_cu = 8;
-    if (generic_big && h->wg_per_cu > 2) h->wg_per_cu = 2;         // (a workspace slot holds the whole factor: nb 3 n (n + 1) doubles)
-
-    const bool var2 = var_order == 2;
-    const int nn = n * n;
-    // ---- row-major copies
-    std::vector<double> a1(nn), a2(nn, 0.0), a1t(nn), a2t(nn, 0.0), bt((size_t)m * n);
-    for (int rr = 0; rr < n; ++rr)
-        for (int c = 0; c < n; ++c) {
-            a1[rr * n + c] = fmpc_host_cm(A1, n, rr, c);
-            a1t[c * n + rr] = a1[rr * n + c];
-            if (var2) {
-                a2[rr * n + c] = fmpc_host_cm(A2, n, rr, c);
-                a2t[c * n + rr] = a2[rr * n + c];
-            }
-        }
-    for (int rr = 0; rr < n; ++rr)
-        for (int c = 0; c < m; ++c) bt[(size_t)c * n + rr] = fmpc_host_cm(B, n, rr, c);
-    std::vector<double> R2(m), Q2(n), Qf2(n);
-    for (int i = 0; i < m; ++i) R2[i] = 2.0 * fmpc_host_cm(R, m, i, i);
-    for (int i = 0; i < n; ++i) { Q2[i] = 2.0 * fmpc_host_cm(Q, n, i, i); Qf2[i] = 2.0 * fmpc_host_cm(Qf, n, i, i); }
-    // X = (2Q)^-1, Xf = (2Qf)^-1 as dense row-major matrices (diagonal weights: diagonal matrices)
-    std::vector<double> Q2m(nn, 0.0), Qf2m(nn, 0.0), X(nn, 0.0), Xf(nn, 0.0);
-    for (int a = 0; a < n; ++a)
-        for (int b = 0; b < n; ++b) { Q2m[a * n + b] = 2.0 * fmpc_host_cm(Q, n, a, b); Qf2m[a * n + b] = 2.0 * fmpc_host_cm(Qf, n, a, b); }
-    if (denseQ) {
-        if (!fmpc_host_spd_inverse(Q2m, n, X) || !fmpc_host_spd_inverse(Qf2m, n, Xf)) { delete h; return FMPC_E_NOT_PD_PHI; }
-    } else {
-        for (int i = 0; i < n; ++i) { X[i * n + i] = 1.0 / Q2[i]; Xf[i * n + i] = 1.0 / Qf2[i]; }
-    }
-    // ---- iteration-invariant Y blocks, deduplicated
-    //   Yd_i = X_{i+1} + [i>=1] A1 X_i A1' + [i>=2] A2 X_{i-1} A2'
-    //   Y1_i = -X_{i+1} A1' + [i>=1] A1 X_i A2'      (rows i, i+1 < T)
-    //   Y2_i = -X_{i+1} A2'                          (rows i, i+2 < T)
-    //   xf:   Yd_T = Xf, Y1_{T-1} = Xf
-    std::vector<std::vector<double>> blocks;
-    std::vector<int> idxD, idx1, idx2;
-    fmpc_host_y_blocks(n, T, var2, xf != nullptr, a1, a2, X, Xf, blocks, idxD, idx1, idx2);      // (fmpc_host.cpp)
-    // ---- pack the pool
-    std::vector<double> pool;
-    auto push = [&](const double* p, size_t cnt) {
-        size_t off = pool.size();
-        pool.insert(pool.end(), p, p + cnt);
-        while (pool.size() % 2) pool.push_back(0.0);   // keep 16-byte alignment
-        return off;
-    };
-    auto push_opt = [&](const double* p, size_t cnt) {
-        std::vector<double> z(cnt, 0.0);
-        return push(p ? p : z.data(), cnt);
-    };
-    const size_t oA1 = push(a1.data(), nn), oA2 = push(a2.data(), nn);
-    const size_t oA1t = push(a1t.data(), nn), oA2t = push(a2t.data(), nn);
-    const size_t oBt = push(bt.data(), bt.size());
-    const size_t oR2 = push(R2.data(), m), oQ2 = push(Q2.data(), n), oQf2 = push(Qf2.data(), n);
-    const size_t orl = push_opt(r, m), oql = push_opt(q, n), oqfl = push_opt(qf, n);
-    const size_t oumin = push(u_min, m), oumax = push(u_max, m);
-    std::vector<double> umid(m), xmid(n);
-    for (int i = 0; i < m; ++i) umid[i] = (u_min[i] + u_max[i]) / 2;    // fast_mpc_init.m:19-20
-    for (int i = 0; i < n; ++i) xmid[i] = (x_min[i] + x_max[i]) / 2;
-    const size_t oumid = push(umid.data(), m), oxmid = push(xmid.data(), n);
-    const size_t oxf = push_opt(xf, n);
-    // dense Q, Qf for the generic kernel's workspace instance: 2Q, 2Qf and their inverses
-    const size_t oQ2m = push(Q2m.data(), nn), oQf2m = push(Qf2m.data(), nn), oXm = push(X.data(), nn), oXfm = push(Xf.data(), nn);
-    const size_t oR2m = denseR ? push(R2full.data(), R2full.size()) : 0;
-    // closed-loop prediction matrices (main.mlx, MPC_DesignMatrices): M1_0 = A1, M2_0 = A2, M1_1 = A1^2 + A2,
-    // M2_1 = A1 A2, M1_i = A1 M1_{i-1} + A2 M1_{i-2}, M2_i = M1_{i-1} A2
-    std::vector<double> lm1((size_t)T * nn, 0.0), lm2((size_t)T * nn, 0.0);
-    {
-        auto mul = [&](const double* X, const double* Y, double* Z, double beta) {     // Z = beta Z + X Y (n x n row-major)
-            for (int rr = 0; rr < n; ++rr)
-                for (int c = 0; c < n; ++c) {
-                    double t = 0.0;
-                    for (int qq = 0; qq < n; ++qq) t += X[rr * n + qq] * Y[qq * n + c];
-                    Z[rr * n + c] = beta * Z[rr * n + c] + t;
-                }
-        };
-        for (int i = 0; i < T; ++i) {
-            double* m1 = lm1.data() + (size_t)i * nn; double* m2 = lm2.data() + (size_t)i * nn;
-            if (i == 0) { for (int e = 0; e < nn; ++e) { m1[e] = a1[e]; m2[e] = a2[e]; } }
-            else if (i == 1) { for (int e = 0; e < nn; ++e) m1[e] = a2[e]; mul(a1.data(), a1.data(), m1, 1.0); mul(a1.data(), a2.data(), m2, 0.0); }
-            else {
-                mul(a1.data(), m1 - nn, m1, 0.0); mul(a2.data(), m1 - 2 * nn, m1, 1.0);
-                mul(m1 - nn, a2.data(), m2, 0.0);
-            }
-        }
-    }
-    const size_t oM1 = push(lm1.data(), lm1.size()), oM2 = push(lm2.data(), lm2.size());
-    h->hm_m1 = lm1; h->hm_m2 = lm2;
-    // blocks are indexed as Yblk + idx*n*n by the kernels: pack them without padding
-    std::vector<double> yall;
-    for (auto& bk : blocks) yall.insert(yall.end(), bk.begin(), bk.end());
-    const size_t oY = push(yall.data(), yall.size());
-
-    std::vector<int> ipool;
-    ipool.insert(ipool.end(), idxD.begin(), idxD.end());
-    ipool.insert(ipool.end(), idx1.begin(), idx1.end());
-    ipool.insert(ipool.end(), idx2.begin(), idx2.end());
-
-    int rc = h->pool_d.assign(pool.data(), pool.size(), nullptr);
-    if (rc == FMPC_OK) rc = h->pool_i.assign(ipool.data(), ipool.size(), nullptr);
+    h->prec = (paths.generic_ok || paths.tiled64_any) ? FMPC_PREC_F64 : FMPC_PREC_F32_MIXED;
+    h->hm = std::move(hm);
+    fmpc_read_switches(h);
+    rc = fmpc_query_device(h);
+    if (rc == FMPC_OK) rc = fmpc_host_build_model(n, m, T, var_order, A1, A2, B, Q, R, Qf, q, r, qf, x_min, x_max, u_min, u_max, xf, h->hm);
+    if (rc == FMPC_OK) rc = fmpc_upload_model(h);
+    if (rc == FMPC_OK && h->generic_ok && fmpc_generic_prepare(h->lds_bytes, h->generic_big) != hipSuccess) rc = FMPC_E_HIP;
+    if (rc == FMPC_OK) rc = fmpc_setup_wave(h);
+    if (rc == FMPC_OK) rc = fmpc_setup_shared_cold(h);
+    if (rc == FMPC_OK) rc = fmpc_setup_panel(h);
+    if (rc == FMPC_OK) rc = fmpc_setup_inverse(h);
     if (rc != FMPC_OK) { fmpc_destroy(h); return rc; }
-    FmpcDevModel& D = h->dev;
-    D.n = n; D.m = m; D.T = T; D.nb = h->nb; D.has_xf = h->has_xf; D.var2 = var2 ? 1 : 0;
-    D.A1 = h->pool_d + oA1; D.A2 = h->pool_d + oA2; D.A1t = h->pool_d + oA1t; D.A2t = h->pool_d + oA2t;
-    D.Bt = h->pool_d + oBt; D.R2 = h->pool_d + oR2; D.Q2 = h->pool_d + oQ2; D.Qf2 = h->pool_d + oQf2;
-    D.rl = h->pool_d + orl; D.ql = h->pool_d + oql; D.qfl = h->pool_d + oqfl;
-    D.umin = h->pool_d + oumin; D.umax = h->pool_d + oumax; D.umid = h->pool_d + oumid;
-    D.xmid = h->pool_d + oxmid; D.xf = h->pool_d + oxf; D.Yblk = h->pool_d + oY;
-    D.idxD = h->pool_i; D.idx1 = h->pool_i + h->nb; D.idx2 = h->pool_i + 2 * h->nb;
-    D.denseR = denseR ? 1 : 0; D.R2m = denseR ? h->pool_d + oR2m : nullptr;
-    D.denseQ = denseQ ? 1 : 0; D.Q2m = h->pool_d + oQ2m; D.Qf2m = h->pool_d + oQf2m; D.Xm = h->pool_d + oXm; D.Xfm = h->pool_d + oXfm;
-    h->loop_M1 = h->pool_d + oM1; h->loop_M2 = h->pool_d + oM2;
-
-    if (generic_ok && fmpc_generic_prepare(lds, generic_big ? 1 : 0) != hipSuccess) { fmpc_destroy(h); return FMPC_E_HIP; }
-    // host copies the tiled kernel's images are built from (on first use of an arithmetic type)
-    h->hm_blocks = yall; h->hm_idxD = idxD; h->hm_idx1 = idx1; h->hm_idx2 = idx2; h->hm_bt = bt;
-    h->hm_a1f = a1; h->hm_a2f = a2;
-    // (always kept: the cold-start form of the ramp path is built from them for any n, fmpc_ensure_ramp_cold)
-    h->hm_R2 = R2; h->hm_rl.assign(m, 0.0); if (r) h->hm_rl.assign(r, r + m);
-    h->hm_umin.assign(u_min, u_min + m); h->hm_umax.assign(u_max, u_max + m); h->hm_umid = umid; h->hm_xmid = xmid;
-    h->hm_Q2 = Q2; h->hm_Qf2 = Qf2;
-    h->hm_ql.assign(n, 0.0); if (q) h->hm_ql.assign(q, q + n);
-    h->hm_qfl.assign(n, 0.0); if (qf) h->hm_qfl.assign(qf, qf + n);
-    h->hm_xf.clear(); if (xf) h->hm_xf.assign(xf, xf + n);
-    h->denseR = denseR ? 1 : 0; h->hm_r2full = R2full;
-    h->denseQ = denseQ ? 1 : 0; h->hm_q2m = Q2m; h->hm_qf2m = Qf2m; h->hm_xm = X; h->hm_xfm = Xf;
-    h->hm_b.resize((size_t)n * m);
-    for (int rr = 0; rr < n; ++rr)
-        for (int c = 0; c < m; ++c) h->hm_b[(size_t)rr * m + c] = fmpc_host_cm(B, n, rr, c);
-
-    // ---- wave kernel: MFMA-layout images of the constant blocks (+ a zero block), padded B'
-    const char* force = getenv("FMPC_FORCE_GENERIC");
-    const int mp = fmpc_wave_mp(m);
-    if (!denseQ && !denseR && fmpc_wave_supports(n) && !(force && force[0] == '1') &&
-        fmpc_wave_lds_bytes(n, mp) <= FMPC_LDS_LIMIT) {
-        const int stride = fmpc_wave_img_stride(n);
-        const int nblk = (int)blocks.size();
-        std::vector<double> wpool((size_t)(nblk + 1) * stride, 0.0);      // last = zero block
-        for (int k = 0; k < nblk; ++k) fmpc_wave_make_images(n, blocks[k].data(), wpool.data() + (size_t)k * stride);
-        const size_t oBtP = wpool.size();
-        wpool.resize(oBtP + (size_t)mp * 33, 0.0);
-        for (int c = 0; c < m; ++c)
-            for (int rr = 0; rr < n; ++rr) wpool[oBtP + (size_t)c * 33 + rr] = bt[(size_t)c * n + rr];
-        std::vector<int> wi;
-        for (int i = 0; i < h->nb; ++i) wi.push_back(idxD[i]);
-        for (int i = 0; i < h->nb; ++i) wi.push_back(idx1[i] >= 0 ? idx1[i] : nblk);
-        for (int i = 0; i < h->nb; ++i) wi.push_back(idx2[i] >= 0 ? idx2[i] : nblk);
-        rc = h->wave_pool_d.assign(wpool.data(), wpool.size(), nullptr);
-        if (rc == FMPC_OK) rc = h->wave_pool_i.assign(wi.data(), wi.size(), nullptr);
-        if (rc != FMPC_OK) { fmpc_destroy(h); return rc; }
-        h->wave.mp = mp;
-        h->wave.img = h->wave_pool_d;
-        h->wave.BtP = h->wave_pool_d + oBtP;
-        h->wave.iD = h->wave_pool_i;
-        h->wave.i1 = h->wave_pool_i + h->nb;
-        h->wave.i2 = h->wave_pool_i + 2 * h->nb;
-        h->wave_lds = fmpc_wave_lds_bytes(n, mp);
-        if (fmpc_wave_prepare(n, h->wave_lds) != hipSuccess) { fmpc_destroy(h); return FMPC_E_HIP; }
-        h->use_wave = 1;
-        const char* nosh = getenv("FMPC_NO_SHARED");
-        if (!(nosh && nosh[0] == '1') && h->nb * n <= 840) {     // the cold path keeps rhs/y/d_nu in an 840-double LDS vector
-            const size_t nf = fmpc_wave_shared_fac_doubles(n, h->nb);
-            const size_t nscr = (size_t)T * (n + m) + 64 + (size_t)n;      // zero state + z of the export solve
-            if (h->sh_fac.alloc(nf, nullptr) != FMPC_OK || h->sh_rs.alloc((size_t)h->nb * 32, nullptr) != FMPC_OK ||
-                h->sh_ok.alloc(1, nullptr) != FMPC_OK || h->sh_scratch.alloc(nscr, nullptr) != FMPC_OK) {
-                fmpc_destroy(h);
-                return FMPC_E_ALLOC;
-            }
-            (void)hipMemset(h->sh_ok, 0, sizeof(int));
-            (void)hipMemset(h->sh_scratch, 0, nscr * sizeof(double));
-            int off9[14];
-            fmpc_wave_cold_layout(n, mp, off9);
-            if (h->cold_d.alloc((size_t)off9[8], nullptr) != FMPC_OK) { fmpc_destroy(h); return FMPC_E_ALLOC; }
-            h->hm_R2 = R2; h->hm_rl.assign(m, 0.0); if (r) h->hm_rl.assign(r, r + m);
-            h->hm_umin.assign(u_min, u_min + m); h->hm_umax.assign(u_max, u_max + m);
-            h->hm_umid = umid; h->hm_xmid = xmid; h->hm_bt = bt; h->hm_a1 = a1; h->hm_a2 = a2;
-            h->sh_enabled = 1;
-            // panel kernel: needs the panel + images in LDS
-            const char* nopn = getenv("FMPC_NO_PANEL");
-            const int pmp = (m + 15) & ~15;
-            const size_t plds = fmpc_panel_lds_bytes(h->nb, pmp);
-            if (n == FP_N && !(nopn && nopn[0] == '1') && plds <= FMPC_LDS_LIMIT) {
-                FmpcPanelIn PL;                                     // pool layout: fmpc_host_panel_layout (fmpc_host.cpp)
-                size_t o = 0;
-                fmpc_host_panel_layout(n, m, T, h->nb, pmp, PL, &h->pn_o_dump, &o, &h->pn_dz_len);
-                h->pn_o_simg = PL.o_simg; h->pn_limg_cap = PL.limg_cap; h->pn_o_limg = PL.o_limg; h->pn_o_bt = PL.o_bt;
-                h->pn_o_aimg = PL.o_aimg; h->pn_o_vec = PL.o_vec; h->pn_o_ucon = PL.o_ucon; h->pn_o_dz = PL.o_dz;
-                h->pn_doubles = PL.pool_doubles;
-                if (h->pn_pool.alloc(o, nullptr) != FMPC_OK || h->pn_cnt.alloc(2, nullptr) != FMPC_OK || h->fa_nflag.alloc(4, nullptr) != FMPC_OK ||
-                    h->fw_chain.alloc((size_t)FMPC_STRETCH_MAX * sizeof(FwParams), nullptr) != FMPC_OK ||
-                    h->pn_sched.alloc((size_t)2 * FP_MAX_STEPS(h->nb) * FP_STEP_INTS, nullptr) != FMPC_OK) { fmpc_destroy(h); return FMPC_E_ALLOC; }
-                (void)hipMemset(h->pn_cnt, 0, 2 * sizeof(int));     // [handed over, length of the continuation list]
-                (void)hipMemset(h->fa_nflag, 0, 4 * sizeof(int));
-                if (h->pn_cnt_host.alloc(2, nullptr) != FMPC_OK) { fmpc_destroy(h); return FMPC_E_ALLOC; }
-                h->pn_cnt_host[0] = -1; h->pn_cnt_host[1] = -1;   // nothing known yet
-                h->pn_dz_lds = fmpc_dz_lds_bytes(pmp, 1);
-                if (fmpc_panel_prepare(plds) != hipSuccess || fmpc_dz_prepare(pmp) != hipSuccess) { fmpc_destroy(h); return FMPC_E_HIP; }
-                h->hm_Q2 = Q2; h->hm_Qf2 = Qf2; h->hm_blocks = yall; h->hm_idxD = idxD; h->hm_idx1 = idx1; h->hm_idx2 = idx2;
-                h->hm_ql.assign(n, 0.0); if (q) h->hm_ql.assign(q, q + n);
-                h->hm_qfl.assign(n, 0.0); if (qf) h->hm_qfl.assign(qf, qf + n);
-                if (xf) h->hm_xf.assign(xf, xf + n);
-                h->pn_mp = pmp; h->pn_lds = plds; h->pn_enabled = 1;
-                {   // the dense form: FMPC_NO_INV=1 switches it off, FMPC_INV_MAX_BATCH bounds its use when w is given
-                    const char* noinv = getenv("FMPC_NO_INV");
-                    const char* mb = getenv("FMPC_INV_MAX_BATCH");
-                    h->inv_enabled = !(noinv && noinv[0] == '1');
-                    { const char* nf = getenv("FMPC_FUSE_DZ"); h->inv_fuse = nf && nf[0] == '1'; }    // (measured slower: DESIGN.md §7; off unless asked for)
-                    if (mb && mb[0]) h->inv_max_batch = atoi(mb);
-                    h->inv_jks = FP_XKS + (T * n + 3) / 4;
-                    h->inv_jks2 = 2 * FP_XKS;                       // [x0 ; x0_pre ; 0 0 ; B u1 ; B u2 ; 0 0]
-                    const size_t nrt = ((size_t)h->nb * n + 15) / 16;
-                    if (h->inv_enabled && (h->inv_jimg.alloc(nrt * (size_t)(16 * ((h->inv_jks + 15) / 16 + 3)) * 64, nullptr) != FMPC_OK ||
-                                           h->inv_nuc.alloc(nrt * 16, nullptr) != FMPC_OK ||
-                                           h->inv_eimg.alloc(4 * FP_XKS * 64, nullptr) != FMPC_OK ||
-                                           h->inv_jst.alloc((size_t)h->nb * 2 * FP_XKS * 64, nullptr) != FMPC_OK ||
-                                           h->inv_nucst.alloc((size_t)h->nb * 32, nullptr) != FMPC_OK ||
-                                           h->inv_jimg2.alloc(nrt * (size_t)(16 * ((2 * FP_XKS + 15) / 16 + 3)) * 64, nullptr) != FMPC_OK)) { fmpc_destroy(h); return FMPC_E_ALLOC; }
-                }
-            }
-        }
-    }
     *out = h;
     return FMPC_OK;
 }
@@ -420,55 +329,12 @@ extern "C" int fmpc_dims(fmpc_handle h, int* n, int* m, int* T, int* nz, int* nu
     return FMPC_OK;
 }
 
-// Cold-start constants for barrier weight k (see FwCold in fmpc_kernel_wave.hip): the first Newton
-// step from u = ubar, x = xbar only needs these k-dependent vectors and the 27 x 27 matrix G.
+// Cold-start constants of the wave kernel for barrier weight k (FwCold in fmpc_kernel_wave.hip), built by fmpc_host_wave_cold
 static int fmpc_upload_cold(fmpc_handle h, double k, hipStream_t stream) {
-    const int n = h->n, m = h->m, mp = h->wave.mp;
     int o[14];
-    fmpc_wave_cold_layout(n, mp, o);
-    std::vector<double> c((size_t)o[8], 0.0);
-    for (int j = 0; j < m; ++j) {
-        const double sp = h->hm_umax[j] - h->hm_umid[j], sm = h->hm_umid[j] - h->hm_umin[j];
-        const double dp = 1.0 / sp, dm = 1.0 / sm;
-        const double hc = k * (dp * dp + dm * dm);
-        c[o[0] + j] = h->hm_R2[j] * h->hm_umid[j] + h->hm_rl[j] + k * (dp - dm);
-        c[o[1] + j] = hc;
-        c[o[2] + j] = 1.0 / (h->hm_R2[j] + hc);
-    }
-    const double* bt = h->hm_bt.data();                         // bt[c*n + r] = B[r][c]
-    for (int a = 0; a < n; ++a) {
-        double cbu = 0.0, bu = 0.0;
-        for (int j = 0; j < m; ++j) {
-            cbu += bt[(size_t)j * n + a] * c[o[2] + j] * c[o[0] + j];
-            bu += bt[(size_t)j * n + a] * h->hm_umid[j];
-        }
-        c[o[4] + a] = cbu;
-        double a1x = 0.0, a2x = 0.0;
-        for (int q = 0; q < n; ++q) { a1x += h->hm_a1[a * n + q] * h->hm_xmid[q]; a2x += h->hm_a2[a * n + q] * h->hm_xmid[q]; }
-        c[o[5] + a] = h->hm_xmid[a] - bu;
-        c[o[6] + a] = h->hm_xmid[a] - bu - a1x;
-        c[o[7] + a] = h->hm_xmid[a] - bu - a1x - a2x;
-        double va = 0.0, va2 = 0.0;
-        for (int j = 0; j < m; ++j) {
-            const double aj = c[o[1] + j] * c[o[2] + j];
-            va += bt[(size_t)j * n + a] * aj * c[o[0] + j];
-            va2 += bt[(size_t)j * n + a] * aj * aj * c[o[0] + j];
-        }
-        c[o[11] + a] = va; c[o[12] + a] = va2;
-        for (int b = 0; b < n; ++b) {
-            double g = 0.0, ma = 0.0, ma2 = 0.0;
-            for (int j = 0; j < m; ++j) {
-                const double bb = bt[(size_t)j * n + a] * bt[(size_t)j * n + b];
-                const double aj = c[o[1] + j] * c[o[2] + j];
-                g += bb * c[o[2] + j]; ma += bb * aj; ma2 += bb * aj * aj;
-            }
-            c[o[3] + a * n + b] = g; c[o[9] + a * n + b] = ma; c[o[10] + a * n + b] = ma2;
-        }
-    }
-    for (int j = 0; j < m; ++j) {
-        const double aj = c[o[1] + j] * c[o[2] + j], cu = c[o[0] + j];
-        c[o[13]] += aj * cu * cu; c[o[13] + 1] += aj * aj * cu * cu;
-    }
+    fmpc_wave_cold_layout(h->n, h->wave.mp, o);
+    std::vector<double> c;
+    fmpc_host_wave_cold(h->hm, k, o, c);
     return hipMemcpyAsync(h->cold_d, c.data(), c.size() * sizeof(double), hipMemcpyHostToDevice, stream) == hipSuccess
                ? FMPC_OK : FMPC_E_HIP;
 }
@@ -478,16 +344,8 @@ static int fmpc_upload_cold(fmpc_handle h, double k, hipStream_t stream) {
 static int fmpc_upload_panel(fmpc_handle h, double k, hipStream_t stream) {
     (void)stream;
     h->pn_valid = 0;
-    FmpcPanelIn In;
-    In.n = h->n; In.m = h->m; In.T = h->T; In.nb = h->nb; In.mp = h->pn_mp; In.var_order = h->var_order;
-    In.pool_doubles = h->pn_doubles; In.o_simg = h->pn_o_simg; In.o_limg = h->pn_o_limg; In.o_bt = h->pn_o_bt;
-    In.o_aimg = h->pn_o_aimg; In.o_vec = h->pn_o_vec; In.o_ucon = h->pn_o_ucon; In.o_dz = h->pn_o_dz; In.limg_cap = h->pn_limg_cap;
-    In.umax = h->hm_umax.data(); In.umin = h->hm_umin.data(); In.umid = h->hm_umid.data(); In.xmid = h->hm_xmid.data();
-    In.R2 = h->hm_R2.data(); In.rl = h->hm_rl.data(); In.Q2 = h->hm_Q2.data(); In.Qf2 = h->hm_Qf2.data();
-    In.ql = h->hm_ql.data(); In.qfl = h->hm_qfl.data(); In.xf = h->hm_xf.data();
-    In.bt = h->hm_bt.data(); In.a1 = h->hm_a1.data(); In.a2 = h->hm_a2.data(); In.blocks = h->hm_blocks.data();
-    In.idxD = h->hm_idxD.data(); In.idx1 = h->hm_idx1.data(); In.idx2 = h->hm_idx2.data();
     FmpcPanelOut Out;
+    FmpcPanelIn In = h->pn_in; In.M = &h->hm;                      // (pn_in: mp and the pool layout)
     fmpc_host_build_panel(In, k, Out);
     if (!Out.valid) return FMPC_OK;                                // not PD at the start point: the exact path reports it
     h->pn_nsf = Out.nsf; h->pn_nsb = Out.nsb; h->pn_rp2c = Out.rp2c; h->pn_rd2_0 = Out.rd2_0;
@@ -504,57 +362,57 @@ static int fmpc_tiled_build(fmpc_handle h, int t, hipStream_t stream) {
     fmpc_handle_s::Tiled& X = h->tl[t];
     const int n = h->n, m = h->m, nb = h->nb, nn = n * n;
     int NB = 0, NW = 0;
-    if (!fmpc_tiled_supports(n, m, nb, t, &NB, &NW, h->denseR)) return FMPC_E_UNSUPPORTED;
+    if (!fmpc_tiled_supports(n, m, nb, t, &NB, &NW, h->hm.denseR)) return FMPC_E_UNSUPPORTED;
     const int mb = (m + 15) / 16, NQ = NB * NB;
-    const int nblk = (int)(h->hm_blocks.size() / nn);
+    const int nblk = (int)(h->hm.blocks.size() / nn);
     std::vector<R> img((size_t)(nblk + 1) * NQ * FT_TILE + (size_t)mb * NB * FT_TILE, (R)0);
     for (int k = 0; k < nblk; ++k)
         for (int a = 0; a < n; ++a)
             for (int b = 0; b < n; ++b)
-                img[((size_t)k * NQ + (a / 16) * NB + b / 16) * FT_TILE + (a % 16) * 16 + b % 16] = (R)h->hm_blocks[(size_t)k * nn + a * n + b];
+                img[((size_t)k * NQ + (a / 16) * NB + b / 16) * FT_TILE + (a % 16) * 16 + b % 16] = (R)h->hm.blocks[(size_t)k * nn + a * n + b];
     const size_t obt = (size_t)(nblk + 1) * NQ * FT_TILE;
     for (int c = 0; c < m; ++c)
         for (int r = 0; r < n; ++r)
-            img[obt + ((size_t)(c / 16) * NB + r / 16) * FT_TILE + (c % 16) * 16 + r % 16] = (R)h->hm_bt[(size_t)c * n + r];
+            img[obt + ((size_t)(c / 16) * NB + r / 16) * FT_TILE + (c % 16) * 16 + r % 16] = (R)h->hm.bt[(size_t)c * n + r];
     std::vector<int> ids;
-    for (int i = 0; i < nb; ++i) ids.push_back(h->hm_idxD[i]);
-    for (int i = 0; i < nb; ++i) ids.push_back(h->hm_idx1[i] >= 0 ? h->hm_idx1[i] : nblk);
-    for (int i = 0; i < nb; ++i) ids.push_back(h->hm_idx2[i] >= 0 ? h->hm_idx2[i] : nblk);
+    for (int i = 0; i < nb; ++i) ids.push_back(h->hm.idxD[i]);
+    for (int i = 0; i < nb; ++i) ids.push_back(h->hm.idx1[i] >= 0 ? h->hm.idx1[i] : nblk);
+    for (int i = 0; i < nb; ++i) ids.push_back(h->hm.idx2[i] >= 0 ? h->hm.idx2[i] : nblk);
     // zero-padded fp64 images of B', B, A1, A2, A1', A2' for the residual GEMMs
     const int NP = 16 * NB, MP = 16 * mb;
     const size_t oBt = 0, oBm = oBt + (size_t)MP * NP, oA1 = oBm + (size_t)NP * MP, oA2 = oA1 + (size_t)NP * NP,
                  oA1t = oA2 + (size_t)NP * NP, oA2t = oA1t + (size_t)NP * NP, oQ2 = oA2t + (size_t)NP * NP,
                  oQf2 = oQ2 + (size_t)NP * NP, oX = oQf2 + (size_t)NP * NP, oXf = oX + (size_t)NP * NP, oR2 = oXf + (size_t)NP * NP,
-                 ptot = oR2 + (h->denseR ? (size_t)MP * MP : 0);
+                 ptot = oR2 + (h->hm.denseR ? (size_t)MP * MP : 0);
     std::vector<double> pad(ptot, 0.0);
     for (int c = 0; c < m; ++c)
         for (int r = 0; r < n; ++r) {
-            pad[oBt + (size_t)c * NP + r] = h->hm_bt[(size_t)c * n + r];
-            pad[oBm + (size_t)r * MP + c] = h->hm_bt[(size_t)c * n + r];
+            pad[oBt + (size_t)c * NP + r] = h->hm.bt[(size_t)c * n + r];
+            pad[oBm + (size_t)r * MP + c] = h->hm.bt[(size_t)c * n + r];
         }
     for (int a = 0; a < n; ++a)
         for (int b = 0; b < n; ++b) {
-            pad[oA1 + (size_t)a * NP + b] = h->hm_a1f[(size_t)a * n + b]; pad[oA1t + (size_t)b * NP + a] = h->hm_a1f[(size_t)a * n + b];
-            pad[oA2 + (size_t)a * NP + b] = h->hm_a2f[(size_t)a * n + b]; pad[oA2t + (size_t)b * NP + a] = h->hm_a2f[(size_t)a * n + b];
-            pad[oQ2 + (size_t)a * NP + b] = h->hm_q2m[(size_t)a * n + b]; pad[oQf2 + (size_t)a * NP + b] = h->hm_qf2m[(size_t)a * n + b];
-            pad[oX + (size_t)a * NP + b] = h->hm_xm[(size_t)a * n + b]; pad[oXf + (size_t)a * NP + b] = h->hm_xfm[(size_t)a * n + b];
+            pad[oA1 + (size_t)a * NP + b] = h->hm.a1[(size_t)a * n + b]; pad[oA1t + (size_t)b * NP + a] = h->hm.a1[(size_t)a * n + b];
+            pad[oA2 + (size_t)a * NP + b] = h->hm.a2[(size_t)a * n + b]; pad[oA2t + (size_t)b * NP + a] = h->hm.a2[(size_t)a * n + b];
+            pad[oQ2 + (size_t)a * NP + b] = h->hm.q2m[(size_t)a * n + b]; pad[oQf2 + (size_t)a * NP + b] = h->hm.qf2m[(size_t)a * n + b];
+            pad[oX + (size_t)a * NP + b] = h->hm.xm[(size_t)a * n + b]; pad[oXf + (size_t)a * NP + b] = h->hm.xfm[(size_t)a * n + b];
         }
-    if (h->denseR)
+    if (h->hm.denseR)
         for (int a = 0; a < m; ++a)
-            for (int b = 0; b < m; ++b) pad[oR2 + (size_t)a * MP + b] = h->hm_r2full[(size_t)a * m + b];
+            for (int b = 0; b < m; ++b) pad[oR2 + (size_t)a * MP + b] = h->hm.r2full[(size_t)a * m + b];
     int rc = X.pool.assign((const char*)img.data(), img.size() * sizeof(R), stream);
     if (rc == FMPC_OK) rc = X.ipool.assign(ids.data(), ids.size(), stream);
     if (rc == FMPC_OK) rc = X.bm.assign(pad.data(), pad.size(), stream);
     if (rc != FMPC_OK) return rc;
     X.NB = NB; X.NW = NW;
-    X.lds = fmpc_tiled_lds_bytes(NB, mb, NW, t, nb, h->denseR ? ft_pr_doubles(n, m) : 0);
-    if (fmpc_tiled_prepare(n, NB, NW, t, X.lds, h->denseR) != hipSuccess) return FMPC_E_HIP;
+    X.lds = fmpc_tiled_lds_bytes(NB, mb, NW, t, nb, h->hm.denseR ? ft_pr_doubles(n, m) : 0);
+    if (fmpc_tiled_prepare(n, NB, NW, t, X.lds, h->hm.denseR) != hipSuccess) return FMPC_E_HIP;
     X.V.NB = NB; X.V.mb = mb; X.V.cn = n / 16; X.V.nl = n % 16; X.V.nblk = nblk;
     X.V.yimg = X.pool; X.V.btimg = (const R*)X.pool.p + obt;
     X.V.iD = X.ipool; X.V.i1 = X.ipool + nb; X.V.i2 = X.ipool + 2 * nb;
     X.V.BtP = X.bm + oBt; X.V.BmP = X.bm + oBm; X.V.A1P = X.bm + oA1; X.V.A2P = X.bm + oA2; X.V.A1tP = X.bm + oA1t; X.V.A2tP = X.bm + oA2t;
-    X.V.denseR = h->denseR; X.V.R2P = h->denseR ? X.bm + oR2 : nullptr;
-    X.V.denseQ = h->denseQ; X.V.Q2P = X.bm + oQ2; X.V.Qf2P = X.bm + oQf2; X.V.XP = X.bm + oX; X.V.XfP = X.bm + oXf;
+    X.V.denseR = h->hm.denseR; X.V.R2P = h->hm.denseR ? X.bm + oR2 : nullptr;
+    X.V.denseQ = h->hm.denseQ; X.V.Q2P = X.bm + oQ2; X.V.Qf2P = X.bm + oQf2; X.V.XP = X.bm + oX; X.V.XfP = X.bm + oXf;
     X.ready = 1;
     return FMPC_OK;
 }
@@ -578,7 +436,7 @@ int fmpc_tiled_plan(fmpc_handle h, int t, int batch, hipStream_t stream, int nw_
     fmpc_handle_s::Tiled& X = h->tl[t];
     { const int rc = fmpc_tiled_ensure(h, t, stream); if (rc != FMPC_OK) return rc; }
     int NWu = X.NW; size_t ldsu = X.lds;
-    if (nw_override && nw_override != X.NW && !t && !h->denseR) {
+    if (nw_override && nw_override != X.NW && !t && !h->hm.denseR) {
         NWu = nw_override;
         ldsu = fmpc_tiled_lds_bytes(X.NB, X.V.mb, NWu, t, h->nb, 0);
         if (!(h->tl_prepared & (1 << NWu))) {
@@ -595,7 +453,7 @@ int fmpc_tiled_plan(fmpc_handle h, int t, int batch, hipStream_t stream, int nw_
     if (!capturing && grid_hint > 0 && grid_hint < grid) grid = grid_hint;   // (a list: as many workgroups as it is expected to be long)
     // (refinement of the fp32 solve keeps three more vectors per slot, behind everything else: a handle that never asks for it
     // allocates and addresses what it always did)
-    const FtWs L = ft_ws_layout(h->n, h->m, h->T, h->nb, X.NB, t ? 4 : 8, h->denseR, (t && h->refine > 0) ? 1 : 0);
+    const FtWs L = ft_ws_layout(h->n, h->m, h->T, h->nb, X.NB, t ? 4 : 8, h->hm.denseR, (t && h->refine > 0) ? 1 : 0);
     // one workspace slot per LAUNCHED workgroup (not per workgroup the chip could hold: a warm start of one problem or a
     // continuation list of 200 would otherwise allocate 0.5-1.4 GB per handle); grown geometrically up to the full grid,
     // so that a growing sequence of batch sizes reallocates (and synchronises) a logarithmic number of times
@@ -643,9 +501,9 @@ static int fmpc_solve_tiled(fmpc_handle h, int t, const FmpcSolve& s, int nw_ove
 extern "C" int fmpc_set_precision(fmpc_handle h, int mode) {
     if (!h) return FMPC_E_NULL;
     if (mode != FMPC_PREC_F64 && mode != FMPC_PREC_F32_MIXED) return FMPC_E_DIM;
-    if (mode == FMPC_PREC_F32_MIXED && !fmpc_tiled_supports(h->n, h->m, h->nb, 1, nullptr, nullptr, h->denseR)) return FMPC_E_UNSUPPORTED;
+    if (mode == FMPC_PREC_F32_MIXED && !fmpc_tiled_supports(h->n, h->m, h->nb, 1, nullptr, nullptr, h->hm.denseR)) return FMPC_E_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (mode == FMPC_PREC_F64 && !h->generic_ok && !fmpc_tiled_supports(h->n, h->m, h->nb, 0, nullptr, nullptr, h->denseR)) {
+    if (mode == FMPC_PREC_F64 && !h->generic_ok && !fmpc_tiled_supports(h->n, h->m, h->nb, 0, nullptr, nullptr, h->hm.denseR)) {
         // no fp64 tiled instance (a dense R beyond n = 47, B too large for the fp64 tiles): fp64 on request through the generic
         // kernel with its tiles in the workspace (slow, exact)
         const size_t lds = fmpc_generic_big_lds_bytes(h->n, h->m);
@@ -679,7 +537,7 @@ static int fmpc_grid_for(fmpc_handle h, int batch) {
 
 // grows the per-workgroup workspace; caller holds h->mu
 static int fmpc_ensure_ws(fmpc_handle h, int grid, size_t* stride, hipStream_t stream) {
-    const FmpcWsLayout L = fmpc_ws_layout(h->n, h->m, h->T, h->nb, h->generic_big != 0, h->denseR != 0);
+    const FmpcWsLayout L = fmpc_ws_layout(h->n, h->m, h->T, h->nb, h->generic_big != 0, h->hm.denseR != 0);
     *stride = L.total;
     return h->ws.grow(L.total * (size_t)grid, stream);
 }
@@ -932,12 +790,12 @@ void fmpc_guard_end(fmpc_handle h, hipStream_t stream) {
 static void fmpc_panel_params(fmpc_handle h, double k, FpParams& Q) {
     memset(&Q, 0, sizeof(Q));
     Q.m = h->m; Q.mp = h->pn_mp; Q.T = h->T; Q.nb = h->nb; Q.has_xf = h->has_xf; Q.var2 = h->var_order == 2 ? 1 : 0;
-    Q.simg = h->pn_pool + h->pn_o_simg; Q.limg = h->pn_pool + h->pn_o_limg;
+    Q.simg = h->pn_pool + h->pn_in.o_simg; Q.limg = h->pn_pool + h->pn_in.o_limg;
     Q.sched_f = h->pn_sched; Q.sched_b = h->pn_sched + (size_t)FP_MAX_STEPS(h->nb) * FP_STEP_INTS; Q.nsf = h->pn_nsf; Q.nsb = h->pn_nsb;
-    Q.btimg = h->pn_pool + h->pn_o_bt; Q.aimg = h->pn_pool + h->pn_o_aimg;
-    Q.vec = h->pn_pool + h->pn_o_vec; Q.ucon = h->pn_pool + h->pn_o_ucon;
+    Q.btimg = h->pn_pool + h->pn_in.o_bt; Q.aimg = h->pn_pool + h->pn_in.o_aimg;
+    Q.vec = h->pn_pool + h->pn_in.o_vec; Q.ucon = h->pn_pool + h->pn_in.o_ucon;
     Q.rd2_0 = h->pn_rd2_0; Q.rp2c = h->pn_rp2c; Q.dump = h->pn_pool + h->pn_o_dump;
-    Q.dzimg = h->pn_pool + h->pn_o_dz; Q.dzimg_len = h->pn_dz_len;
+    Q.dzimg = h->pn_pool + h->pn_in.o_dz; Q.dzimg_len = h->pn_dz_len;
     Q.kbar = k;
     Q.jimg = h->inv_jimg; Q.nuc = h->inv_nuc; Q.jks = h->inv_jks; Q.jksp = 16 * ((h->inv_jks + 15) / 16 + 3); Q.eimg = h->inv_eimg;
     Q.jst = h->inv_jst; Q.nucst = h->inv_nucst; Q.gate_only = 0;
@@ -957,8 +815,8 @@ static int fmpc_build_inverse(fmpc_handle h, double k, hipStream_t stream) {
     for (int j = 0; j < TN; ++j) hw[(size_t)(1 + 2 * n + j) * TN + j] = scale;
     for (int j = 0; j < n; ++j)                                       // w = -M1 (B u1) - M2 (B u2): the columns of [B u1 ; B u2]
         for (int e = 0; e < TN; ++e) {
-            hw[(size_t)(1 + ncol + j) * TN + e] = -scale * h->hm_m1[(size_t)e * n + j];
-            hw[(size_t)(1 + ncol + n + j) * TN + e] = -scale * h->hm_m2[(size_t)e * n + j];
+            hw[(size_t)(1 + ncol + j) * TN + e] = -scale * h->hm.m1[(size_t)e * n + j];
+            hw[(size_t)(1 + ncol + n + j) * TN + e] = -scale * h->hm.m2[(size_t)e * n + j];
         }
     DevBuf<double> d;                                                 // (released on return)
     const size_t o_x0 = 0, o_x0p = o_x0 + hx0.size(), o_w = o_x0p + hx0p.size(), o_gate = o_w + hw.size(),
@@ -986,7 +844,7 @@ static int fmpc_build_inverse(fmpc_handle h, double k, hipStream_t stream) {
     // in this order.  A value that is not finite leaves this form off (the panel path reports what is wrong); one found as late as in
     // J' is found after the per-stage images have gone up.
     std::vector<double> img, nuc, jst, ncs, img2, eimg, J4, nuc4;
-    const bool finite = fmpc_host_inverse_images(n, T, nb, h->var_order == 2, h->inv_jks, h->inv_jks2, h->hm_a1.data(), h->hm_a2.data(), nu,
+    const bool finite = fmpc_host_inverse_images(n, T, nb, h->var_order == 2, h->inv_jks, h->inv_jks2, h->hm.a1.data(), h->hm.a2.data(), nu,
                                                  img, nuc, jst, ncs, img2, eimg, J4, nuc4);
     if (!jst.empty() &&
         (hipMemcpy(h->inv_jst, jst.data(), jst.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
@@ -1008,11 +866,7 @@ static int fmpc_build_first_move(fmpc_handle h, double k, hipStream_t stream) {
     if (!h->hm_J4_valid || h->hm_J4_k != k) return FMPC_E_UNSUPPORTED;
     const int n = h->n, m = h->m, T = h->T, TN = T * n;
     FmpcFirstIn In;
-    In.n = n; In.m = m; In.T = T; In.nb = h->nb; In.var2 = h->var_order == 2 ? 1 : 0; In.has_xf = h->has_xf;
-    In.bt = h->hm_bt.data(); In.umax = h->hm_umax.data(); In.umin = h->hm_umin.data(); In.umid = h->hm_umid.data();
-    In.xmid = h->hm_xmid.data(); In.R2 = h->hm_R2.data(); In.rl = h->hm_rl.data(); In.a1 = h->hm_a1.data(); In.a2 = h->hm_a2.data();
-    In.m1 = h->hm_m1.data(); In.m2 = h->hm_m2.data(); In.xf = h->hm_xf.empty() ? h->hm_xmid.data() : h->hm_xf.data();
-    In.J = h->hm_J4.data(); In.nuc = h->hm_nuc.data(); In.k = k;
+    In.M = &h->hm; In.J = h->hm_J4.data(); In.nuc = h->hm_nuc.data(); In.k = k;
     FmpcFirstOut O;
     fmpc_host_build_first_move(In, O);
     for (double v : O.K0t) if (!std::isfinite(v)) return FMPC_E_UNSUPPORTED;
@@ -1021,8 +875,8 @@ static int fmpc_build_first_move(fmpc_handle h, double k, hipStream_t stream) {
     auto push = [&](const std::vector<double>& v) { const size_t o = pool.size(); pool.insert(pool.end(), v.begin(), v.end()); while (pool.size() % 2) pool.push_back(0.0); return o; };
     std::vector<double> m12t((size_t)2 * n * TN), dx0T(n);
     for (int e = 0; e < TN; ++e)
-        for (int q = 0; q < n; ++q) { m12t[(size_t)q * TN + e] = h->hm_m1[(size_t)e * n + q]; m12t[(size_t)(n + q) * TN + e] = h->hm_m2[(size_t)e * n + q]; }
-    for (int r = 0; r < n; ++r) dx0T[r] = h->hm_Qf2[r] * h->hm_xmid[r] + h->hm_qfl[r];
+        for (int q = 0; q < n; ++q) { m12t[(size_t)q * TN + e] = h->hm.m1[(size_t)e * n + q]; m12t[(size_t)(n + q) * TN + e] = h->hm.m2[(size_t)e * n + q]; }
+    for (int r = 0; r < n; ++r) dx0T[r] = h->hm.Qf2[r] * h->hm.xmid[r] + h->hm.qfl[r];
     const size_t oK = push(O.K0t), ou = push(O.u0c), oE = push(O.Ec), oe = push(O.e), oEp = push(O.Epc), oep = push(O.ep), om = push(m12t), od = push(dx0T);
     // affine form of the whole step without w: [Kz | zc] as matrix-core images; the (x0, x0_pre) blocks of E, Ep likewise
     h->fa_valid = 0;
@@ -1031,10 +885,7 @@ static int fmpc_build_first_move(fmpc_handle h, double k, hipStream_t stream) {
     bool fa_ok = !h->fa_disabled && 2 * n + 2 <= FA_KC;
     if (fa_ok) {
         FmpcAffineIn AI;
-        AI.n = n; AI.m = m; AI.T = T; AI.nb = h->nb; AI.has_xf = h->has_xf; AI.ncJ = 4 * n;
-        AI.bt = In.bt; AI.umax = In.umax; AI.umin = In.umin; AI.umid = In.umid; AI.xmid = In.xmid; AI.R2 = In.R2; AI.rl = In.rl;
-        AI.Q2 = h->hm_Q2.data(); AI.Qf2 = h->hm_Qf2.data(); AI.ql = h->hm_ql.data(); AI.qfl = h->hm_qfl.data(); AI.a1 = In.a1; AI.a2 = In.a2;
-        AI.J = In.J; AI.nuc = In.nuc; AI.k = k;
+        AI.M = &h->hm; AI.ncJ = 4 * n; AI.J = In.J; AI.nuc = In.nuc; AI.k = k;
         fmpc_host_build_affine(AI, AO);
         for (double v : AO.img) if (!std::isfinite(v)) { fa_ok = false; break; }
     }
@@ -1069,14 +920,14 @@ static int fmpc_build_first_move(fmpc_handle h, double k, hipStream_t stream) {
     }
     if (fs_ok) {
         FmpcLoopImages LI;
-        fmpc_host_build_loop_images(O, n, m, FL_KS, true, In.bt, LI);
+        fmpc_host_build_loop_images(O, n, m, FL_KS, true, h->hm.bt.data(), LI);
         oSU = push(LI.imgU); oSE = push(LI.imgE); oSEp = push(LI.imgEp); oSB = push(LI.imgB);
     }
     const int rc = h->fm_pool.assign(pool.data(), pool.size(), stream);
     if (rc != FMPC_OK) return rc;
     FmParams& P = h->fm_P;
     memset(&P, 0, sizeof(P));
-    P.n = n; P.m = m; P.T = T; P.nb = h->nb; P.var2 = In.var2; P.has_xf = h->has_xf;
+    P.n = n; P.m = m; P.T = T; P.nb = h->nb; P.var2 = h->hm.var2; P.has_xf = h->has_xf;
     P.bt = h->dev.Bt; P.K0t = h->fm_pool + oK; P.u0c = h->fm_pool + ou; P.E = h->fm_pool + oE; P.e = h->fm_pool + oe;
     P.Ep = h->fm_pool + oEp; P.ep = h->fm_pool + oep; P.m12t = h->fm_pool + om; P.dx0T = h->fm_pool + od;
     P.e0 = O.e0; P.ep0 = O.ep0; P.normE = O.normE; P.norme = O.norme; P.normEp = O.normEp; P.normep = O.normep; P.rd2_0 = h->pn_rd2_0;
@@ -1095,7 +946,7 @@ static int fmpc_build_first_move(fmpc_handle h, double k, hipStream_t stream) {
     if (fl_ok) {
         FlParams& L = h->fl_P;
         memset(&L, 0, sizeof(L));
-        L.n = n; L.m = m; L.T = T; L.nb = h->nb; L.has_xf = h->has_xf; L.var2 = In.var2;
+        L.n = n; L.m = m; L.T = T; L.nb = h->nb; L.has_xf = h->has_xf; L.var2 = h->hm.var2;
         L.imgU = h->fm_pool + oLU; L.imgE = h->fm_pool + oLE; L.imgEp = h->fm_pool + oLEp;
         L.dx0T = P.dx0T; L.e0 = O.e0; L.ep0 = O.ep0; L.normE = O.normE; L.norme = O.norme; L.normEp = O.normEp; L.normep = O.normep; L.rd2_0 = h->pn_rd2_0;
         h->fl_valid = 1;
@@ -1184,7 +1035,7 @@ static int fmpc_path_tiled(fmpc_handle h, const FmpcSolve& s) {
     // time up to 256 problems, 20 to 60 % MORE at 2048 (round 5 sweep, n = 8 .. 31).  (n = 27 has its own dispatch below; a size
     // that reaches this point with the wave kernel switched off keeps the handle's setting.)
     const int t_ = h->prec == FMPC_PREC_F32_MIXED ? 1 : 0;
-    const int few = (!t_ && !h->denseR && h->n <= 31 && h->n != FP_N && s.batch <= 512 && !h->force_tiled) ? 4 : 0;
+    const int few = (!t_ && !h->hm.denseR && h->n <= 31 && h->n != FP_N && s.batch <= 512 && !h->force_tiled) ? 4 : 0;
     return fmpc_solve_tiled(h, t_, s, few);
 }
 
@@ -1230,7 +1081,7 @@ static int fmpc_path_affine(fmpc_handle h, const FmpcSolve& s, size_t stride, in
     A.status = s.status; A.iters = s.iters; A.step = s.step; A.need = h->fa_need; A.handed = h->pn_cnt;
     int* const nf = h->fa_nflag;                          // [running count of flagged problems | count dealt with | ticket]: device
                                                           // state only, the same in an eager call and in a recorded graph
-    static const bool no_nflag = [] { const char* e = getenv("FMPC_NO_NFLAG"); return e && e[0] == '1'; }();   // A/B switch
+    static const bool no_nflag = fmpc_env_on("FMPC_NO_NFLAG");   // A/B switch
     A.nflag = no_nflag ? nullptr : nf;
     A.ldz = zld;                                          // (0: contiguous rows)
     A.nsteps = 0;
@@ -1455,9 +1306,9 @@ static int fmpc_solve_device_inner(fmpc_handle h, FmpcSolve s) {
     }
     // Padded z rows (fmpc_set_z_ld): the affine form of the cold-start step and its exact path honour them, nothing else does
     const int zld = (!z_null && s.ldz > h->T * (h->n + h->m)) ? s.ldz : 0;
-    if (zld && (s.w != nullptr || s.z_init != nullptr || max_iter != 1 || h->prec == FMPC_PREC_F32_MIXED || h->force_tiled || h->denseQ ||
-                h->denseR || !h->use_wave || !h->sh_enabled || !h->pn_enabled)) return FMPC_E_UNSUPPORTED;
-    if (h->prec == FMPC_PREC_F32_MIXED || h->force_tiled || ((h->denseQ || h->denseR) && !h->generic_big) ||
+    if (zld && (s.w != nullptr || s.z_init != nullptr || max_iter != 1 || h->prec == FMPC_PREC_F32_MIXED || h->force_tiled || h->hm.denseQ ||
+                h->hm.denseR || !h->use_wave || !h->sh_enabled || !h->pn_enabled)) return FMPC_E_UNSUPPORTED;
+    if (h->prec == FMPC_PREC_F32_MIXED || h->force_tiled || ((h->hm.denseQ || h->hm.denseR) && !h->generic_big) ||
         (!h->use_wave && (!h->generic_ok || h->prefer_tiled))) {
         { const int rcq = fmpc_stretch_settle(h, s.stream); if (rcq != FMPC_OK) return rcq; }
         return fmpc_path_tiled(h, s);
@@ -1500,7 +1351,7 @@ static bool fmpc_affine_ready(fmpc_handle h, const FmpcSolve& s) {
     const bool z_null = s.z_out == nullptr;
     const size_t nz = (size_t)h->T * (h->n + h->m);
     if (z_null && (size_t)s.batch * nz > h->zs.cap) return false;
-    if (h->prec == FMPC_PREC_F32_MIXED || h->force_tiled || h->denseQ || h->denseR || !h->use_wave || !h->sh_enabled || !h->pn_enabled ||
+    if (h->prec == FMPC_PREC_F32_MIXED || h->force_tiled || h->hm.denseQ || h->hm.denseR || !h->use_wave || !h->sh_enabled || !h->pn_enabled ||
         !h->pn_valid || h->n != FP_N) return false;
     if (fmpc_wave_ws_doubles(h->n, h->m, h->wave.mp, h->T, h->nb) * (size_t)h->num_cu * fmpc_wave_waves_per_wg() > h->ws.cap) return false;
     if (!h->sh_valid || h->sh_k != s.k || (size_t)s.batch > h->pn_cap) return false;
@@ -1780,7 +1631,7 @@ static int fmpc_loop_run_walk(fmpc_handle h, int batch, int steps, int upto, con
     // behind take one step through the one-step call (a compact batch, as for a stopped step) until all have arrived -- at most
     // `upto` such calls, none of them synchronises.
     int max_restarts = 8, restarts = 0;
-    { const char* e = getenv("FMPC_WALK_MAX_RESTARTS"); if (e && e[0] >= '0' && e[0] <= '9') max_restarts = atoi(e); }
+    { const int v = fmpc_env_int("FMPC_WALK_MAX_RESTARTS", -1); if (v >= 0) max_restarts = v; }
     bool stepwise = false;
     for (;;) {
         if (stepwise) {
@@ -1996,9 +1847,9 @@ extern "C" int fmpc_set_ramp(fmpc_handle h, const double* du_min, const double* 
         if (!(du_min[c] < du_max[c])) return FMPC_E_DIM;
     // fmpc_newton_ramp: n <= 64, B' and its tiles in LDS, diagonal weights.  Everything else: fmpc_newton_ramp_ws, whose LDS
     // grows only with the 16 NTl doubles of the substitution vector and whose workspace (one problem) must fit the budget.
-    const bool lds_ok = h->n <= 64 && fmpc_ramp_lds_admit_bytes(h->n, h->m, h->nb * h->n) <= FMPC_LDS_LIMIT && !h->denseQ && !h->denseR;
+    const bool lds_ok = h->n <= 64 && fmpc_ramp_lds_admit_bytes(h->n, h->m, h->nb * h->n) <= FMPC_LDS_LIMIT && !h->hm.denseQ && !h->hm.denseR;
     const size_t lds_ws = fmpc_ramp_lds_bytes(h->n, h->m, h->nb, 1);
-    const bool ws_ok = lds_ws <= FMPC_LDS_LIMIT && fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb, 1, h->denseR) <= FMPC_RAMP_WS_BUDGET;
+    const bool ws_ok = lds_ws <= FMPC_LDS_LIMIT && fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb, 1, h->hm.denseR) <= FMPC_RAMP_WS_BUDGET;
     if (!lds_ok && !ws_ok) return FMPC_E_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(h->mu);
     if (!h->ramp_du) {
@@ -2022,7 +1873,7 @@ extern "C" int fmpc_set_ramp_workspace(fmpc_handle h, int enabled) {
     std::lock_guard<std::mutex> lk(h->mu);
     if (enabled) {
         const size_t lds_ws = fmpc_ramp_lds_bytes(h->n, h->m, h->nb, 1);
-        if (lds_ws > FMPC_LDS_LIMIT || fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb, 1, h->denseR) > FMPC_RAMP_WS_BUDGET) return FMPC_E_UNSUPPORTED;
+        if (lds_ws > FMPC_LDS_LIMIT || fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb, 1, h->hm.denseR) > FMPC_RAMP_WS_BUDGET) return FMPC_E_UNSUPPORTED;
         if (hipSetDevice(h->device) != hipSuccess || fmpc_ramp_prepare(1, lds_ws) != hipSuccess) return FMPC_E_HIP;
     }
     h->ramp_force_ws = enabled ? 1 : 0;
@@ -2037,14 +1888,10 @@ static int fmpc_ensure_ramp_cold(fmpc_handle h, double k, hipStream_t stream) {
     if (h->rc_valid && h->rc_k == k) return FMPC_OK;
     if (h->rc_failed && h->rc_failed_k == k) return FMPC_E_UNSUPPORTED;
     const size_t lds = fmpc_ramp_cold_lds_bytes(h->n, h->m, h->T, h->nb);
-    // (the constants are built from the DIAGONALS hm_Q2, hm_Qf2, hm_R2: never for dense weights)
-    if (lds > FMPC_LDS_LIMIT || h->n > 64 || h->denseQ || h->denseR) return FMPC_E_UNSUPPORTED;
+    // (the constants are built from the DIAGONALS hm.Q2, hm.Qf2, hm.R2: never for dense weights)
+    if (lds > FMPC_LDS_LIMIT || h->n > 64 || h->hm.denseQ || h->hm.denseR) return FMPC_E_UNSUPPORTED;
     FmpcRampColdIn In;
-    In.n = h->n; In.m = h->m; In.T = h->T; In.nb = h->nb; In.var2 = h->var_order == 2 ? 1 : 0; In.has_xf = h->has_xf;
-    In.bt = h->hm_bt.data(); In.a1 = h->hm_a1f.data(); In.a2 = h->hm_a2f.data();
-    In.umax = h->hm_umax.data(); In.umin = h->hm_umin.data(); In.umid = h->hm_umid.data(); In.xmid = h->hm_xmid.data();
-    In.R2 = h->hm_R2.data(); In.rl = h->hm_rl.data(); In.Q2 = h->hm_Q2.data(); In.Qf2 = h->hm_Qf2.data(); In.ql = h->hm_ql.data();
-    In.qfl = h->hm_qfl.data(); In.xf = h->hm_xf.data(); In.dumin = h->hm_dumin.data(); In.dumax = h->hm_dumax.data(); In.k = k;
+    In.M = &h->hm; In.dumin = h->hm_dumin.data(); In.dumax = h->hm_dumax.data(); In.k = k;
     FmpcRampColdOut O;
     fmpc_host_build_ramp_cold(In, O);
     if (!O.valid) { h->rc_failed = 1; h->rc_failed_k = k; return FMPC_E_UNSUPPORTED; }
@@ -2056,8 +1903,8 @@ static int fmpc_ensure_ramp_cold(fmpc_handle h, double k, hipStream_t stream) {
     size_t o_ik, o_ib;
     {
         std::vector<double> ik, ib;
-        fmpc_host_mfma_images(h->hm_bt.data(), h->m, h->n, (h->n + 3) / 4, ik);
-        fmpc_host_mfma_images(h->hm_b.data(), h->n, h->m, (h->m + 3) / 4, ib);
+        fmpc_host_mfma_images(h->hm.bt.data(), h->m, h->n, (h->n + 3) / 4, ik);
+        fmpc_host_mfma_images(h->hm.b.data(), h->n, h->m, (h->m + 3) / 4, ib);
         o_ik = push(ik); o_ib = push(ib);
     }
     size_t o_Gt;
@@ -2167,7 +2014,7 @@ static int fmpc_solve_ramp_device_inner(fmpc_handle h, FmpcSolve& s, const doubl
         s.z_out = h->zs;
     }
     // one workgroup per problem in flight, at most one per CU; the workspace of all of them within the budget
-    const size_t stride = fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb, ws, h->denseR);
+    const size_t stride = fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb, ws, h->hm.denseR);
     int cap = h->num_cu;
     if ((size_t)cap * stride > FMPC_RAMP_WS_BUDGET) cap = (int)(FMPC_RAMP_WS_BUDGET / stride);
     if (cap < 1) return FMPC_E_ALLOC;
@@ -2283,7 +2130,7 @@ static int fmpc_solve_host(fmpc_handle h, int batch,
     // inputs straight from the pinned block (it is device-accessible) -- no copy up -- and, when the iterate is written once
     // (cold start, Newton budget 1: no kernel uses z as its working storage except for a flagged problem), write the outputs
     // straight into it -- no copy down.  FMPC_NO_ZEROCOPY=1: the copies as before (A/B).
-    static const bool no_zc = [] { const char* e = getenv("FMPC_NO_ZEROCOPY"); return e && e[0] == '1'; }();
+    static const bool no_zc = fmpc_env_on("FMPC_NO_ZEROCOPY");
     const bool zc_in = pin != nullptr && pin_dev != nullptr && !no_zc && off <= FMPC_ZC_LIMIT;
     const bool zc_out = zc_in && n_newton == 1 && z_init == nullptr && u_prev == nullptr;
     char* const base_in = zc_in ? pin_dev : base;

@@ -14,7 +14,7 @@
 // ---- model bank (include/fastmpc.h; fmpc_bank.h, fmpc_kernel_bank.hip)
 static int fmpc_bank_unsupported(fmpc_handle h, int t) {
     if (h->ramp_du.p) return 1;                                        // ramp-rate rows: their kernels have no bank form
-    return fmpc_tiled_supports(h->n, h->m, h->nb, t, nullptr, nullptr, h->denseR) ? 0 : 1;
+    return fmpc_tiled_supports(h->n, h->m, h->nb, t, nullptr, nullptr, h->hm.denseR) ? 0 : 1;
 }
 extern "C" int fmpc_bank_set_device(fmpc_handle h, int count, const double* A1, const double* A2, void* stream_) {
     if (!h || !A1) return FMPC_E_NULL;
@@ -37,8 +37,8 @@ extern "C" int fmpc_bank_set_device(fmpc_handle h, int count, const double* A1, 
     if (!B.table_ready) {
         if (capturing) return FMPC_E_ALLOC;
         FmpcBankTable tab;
-        const bool xf_is_x = h->hm_xm.size() == h->hm_xfm.size() &&
-                             memcmp(h->hm_xm.data(), h->hm_xfm.data(), h->hm_xm.size() * sizeof(double)) == 0;
+        const bool xf_is_x = h->hm.xm.size() == h->hm.xfm.size() &&
+                             memcmp(h->hm.xm.data(), h->hm.xfm.data(), h->hm.xm.size() * sizeof(double)) == 0;
         fmpc_host_bank_table(h->T, h->var_order == 2, h->has_xf != 0, xf_is_x, tab);
         const int nblk = (int)tab.blocks.size();
         std::vector<int> ids;
@@ -48,7 +48,7 @@ extern "C" int fmpc_bank_set_device(fmpc_handle h, int count, const double* A1, 
         B.nblk = nblk; B.table_ready = 1;
     }
     if (!B.prepared[t]) {
-        if (fmpc_tiled_prepare(n, NB, X.NW, t, X.lds, h->denseR, 1) != hipSuccess) return FMPC_E_HIP;
+        if (fmpc_tiled_prepare(n, NB, X.NW, t, X.lds, h->hm.denseR, 1) != hipSuccess) return FMPC_E_HIP;
         if (fmpc_bank_build_prepare(NB, t) != hipSuccess) return FMPC_E_HIP;
         B.prepared[t] = 1;
     }
@@ -172,7 +172,7 @@ static int fmpc_bank_solve_launch(fmpc_handle h, const FmpcSolve& s, const int* 
     P.model_of = model_of;
     P.list = list; P.nlist = nlist;                                    // (the first-move form's hand-over: FT_LIST_HANDED entries)
     // the stored cold-start factors: from the cold start only, and only for the k they were built for, bit for bit
-    const bool stored = F.valid && F.t == t && F.count == h->bank.count && !h->denseR && !s.z_init && memcmp(&s.k, &F.k, sizeof(double)) == 0;
+    const bool stored = F.valid && F.t == t && F.count == h->bank.count && !h->hm.denseR && !s.z_init && memcmp(&s.k, &F.k, sizeof(double)) == 0;
     if (stored) { P.pf_fac = F.fac.p; P.pf_flag = F.flag; P.pf_stride = F.stride; }
     h->bank_last_stored = stored ? 1 : 0;
     h->tl_last_nw = plan.NWu;
@@ -214,7 +214,7 @@ extern "C" int fmpc_bank_prefactor_device(fmpc_handle h, double k, void* stream_
     fmpc_handle_s::Bank& B = h->bank;
     fmpc_handle_s::BankFactor& F = h->bkf;
     const int t = fmpc_prec_t(h);
-    if (B.count <= 0 || B.t != t || h->denseR || fmpc_bank_unsupported(h, t) || !h->tl[t].ready) return FMPC_E_UNSUPPORTED;
+    if (B.count <= 0 || B.t != t || h->hm.denseR || fmpc_bank_unsupported(h, t) || !h->tl[t].ready) return FMPC_E_UNSUPPORTED;
     fmpc_handle_s::Tiled& X = h->tl[t];
     const size_t stride = (size_t)h->nb * ft_stage_tiles(X.NB) * FT_TILE;                  // elements of the factor's type per model
     const size_t bytes = stride * (size_t)B.count * (t ? sizeof(float) : sizeof(double));
@@ -276,7 +276,7 @@ extern "C" int fmpc_bank_first_move_device(fmpc_handle h, double k, void* stream
     const fmpc_handle_s::BankFactor& PF = h->bkf;
     fmpc_handle_s::BankFirst& F = h->bfm;
     const int n = h->n, m = h->m, T = h->T, nb = h->nb, nc = 4 * n, Hc = nc / 2 + 1;
-    if (B.count <= 0 || B.t != 0 || h->prec != FMPC_PREC_F64 || h->denseR || h->denseQ || fmpc_bank_unsupported(h, 0) || !h->tl[0].ready)
+    if (B.count <= 0 || B.t != 0 || h->prec != FMPC_PREC_F64 || h->hm.denseR || h->hm.denseQ || fmpc_bank_unsupported(h, 0) || !h->tl[0].ready)
         return FMPC_E_UNSUPPORTED;
     if (!PF.valid || PF.t != 0 || PF.count != B.count || memcmp(&k, &PF.k, sizeof(double)) != 0) return FMPC_E_UNSUPPORTED;
     // the application kernel's sizes (fmpc_launch_first_move_bank), and the depth the builder's rounding bound is written for
@@ -303,8 +303,8 @@ extern "C" int fmpc_bank_first_move_device(fmpc_handle h, double k, void* stream
                       !F.cst_valid || memcmp(&k, &F.cst_k, sizeof(double)) != 0 || !F.cnt.p || !F.prepared)) return FMPC_E_ALLOC;
     // the model-independent constants, in long double: L L' = B diag(a^2) B', L y0 = B (a^2 o cu)   (fmpc_host_bank_first_constants)
     std::vector<double> cst;
-    if (!fmpc_host_bank_first_constants(n, m, T, k, h->hm_bt.data(), h->hm_umax.data(), h->hm_umin.data(), h->hm_umid.data(),
-                                        h->hm_R2.data(), h->hm_rl.data(), cst)) return FMPC_E_UNSUPPORTED;
+    if (!fmpc_host_bank_first_constants(n, m, T, k, h->hm.bt.data(), h->hm.umax.data(), h->hm.umin.data(), h->hm.umid.data(),
+                                        h->hm.R2.data(), h->hm.rl.data(), cst)) return FMPC_E_UNSUPPORTED;
     F.valid = 0;                                                       // (no form while it is being rebuilt)
     int rc = fmpc_guard_begin(h, stream);                             // (an earlier loop step may still read the old operands)
     if (rc != FMPC_OK) return rc;

@@ -9,6 +9,7 @@
 
 #include "../../include/fastmpc.h"
 #include "fmpc_device.h"
+#include "fmpc_host.h"
 #include "fmpc_first.h"
 #include "fmpc_affine.h"
 #include "fmpc_loopu0.h"
@@ -22,6 +23,7 @@
 struct fmpc_handle_s {
     int n, m, T, nb, var_order, has_xf, device;
     int num_cu;
+    FmpcHostModel hm;            // the model on the host (fmpc_host.h); hm.denseQ: tiled kernel only, hm.denseR: tiled kernel, fp64
     FmpcDevModel dev;            // device pointers into `pool`
     const double* loop_M1; const double* loop_M2;   // closed-loop prediction matrices (T n) x n, row-major
     DevBuf<double> pool_d;       // one allocation for all shared doubles
@@ -57,7 +59,7 @@ struct fmpc_handle_s {
     int last_path = 0;
     size_t pn_lds = 0;
     DevBuf<double> pn_pool;              // [simg | btimg | aimg | vec | ucon]
-    size_t pn_o_simg, pn_o_limg, pn_o_bt, pn_o_aimg, pn_o_vec, pn_o_ucon, pn_o_dump, pn_doubles;
+    FmpcPanelIn pn_in; size_t pn_o_dump; // mp and the layout of pn_pool (o_*) as fmpc_host_build_panel reads them (M is set per call); then the dump area
     DevBuf<int> pn_cnt;                  // problems the exact path had to solve in the last call (diagnostic)
     int pn_split_last = 0;               // the last panel call ran decide + compacted continuation (budget > 1): pn_cnt[1] is its list length
     DevBuf<int> gn_list; DevBuf<double> gn_nu; DevBuf<int> gn_cnt; PinnedBuf<int> gn_cnt_host; size_t gn_cap = 0;   // explicit-start batches with a budget > 1: first step / continuation split
@@ -68,7 +70,7 @@ struct fmpc_handle_s {
     DevBuf<double> pn_gate, pn_epsp, pn_nuws;
     DevBuf<double> pn_rnp; DevBuf<int> pn_list;   // budgets > 1: next-exit-test partials, compacted list of the problems that go on
     PinnedBuf<int> pn_cnt_host;          // pinned copy of pn_cnt of an EARLIER call (never waited for): sizes the continuation grid
-    size_t pn_o_dz; int pn_dz_len;
+    int pn_dz_len;
     size_t pn_dz_lds = 0;
     double pn_rd2_0 = 0.0, pn_rp2c = 0.0;
     // dense form of the cold-start dual solve (fmpc_kernel_inv.hip): nu+ = nuc + J d, built per (handle, k) on first use
@@ -82,11 +84,7 @@ struct fmpc_handle_s {
     // nuc kept by fmpc_build_inverse, the derived matrices on the device per (handle, k), a flag per realisation
     std::vector<double> hm_J4, hm_nuc; double hm_J4_k = 0.0; int hm_J4_valid = 0;
     DevBuf<double> fm_pool; int fm_valid = 0, fm_disabled = 0; double fm_k = 0.0; FmParams fm_P; DevBuf<int> fm_need;
-    std::vector<double> hm_m1, hm_m2;
-    std::vector<double> hm_Q2, hm_Qf2, hm_ql, hm_qfl, hm_xf, hm_blocks;
-    std::vector<int> hm_idxD, hm_idx1, hm_idx2;
-    DevBuf<int> pn_sched; int pn_nsf = 0, pn_nsb = 0, pn_limg_cap = 0;
-    std::vector<double> hm_R2, hm_rl, hm_umin, hm_umax, hm_umid, hm_xmid, hm_bt, hm_a1, hm_a2;   // host copies
+    DevBuf<int> pn_sched; int pn_nsf = 0, pn_nsb = 0;
     // tiled kernel (fmpc_kernel_tiled.hip): workgroup per problem, any n <= 79; images per arithmetic type, built on first use
     int generic_ok;                      // the generic kernel's LDS tiles fit (n <= 64), or generic_big
     int prefer_tiled;                    // the fp64 tiled kernel exists for this size: it is 1.3 (n = 4) to 9 (n = 45) times faster than the
@@ -126,12 +124,6 @@ struct fmpc_handle_s {
     int small_tiled = 1;                  // per-problem-factor solves of few problems go to the tiled kernel (FMPC_NO_SMALL_TILED=1: off)
     int small_nw = 4;                     // ... with this many wavefronts per problem: 4, the default (round 5), or 2 (FMPC_SMALL_TILED_NW=2 /
                                           // fmpc_set_small_batch_kernel(h, 2))
-    std::vector<double> hm_b;            // B row-major n x m
-    std::vector<double> hm_a1f, hm_a2f;  // A1, A2 row-major (always kept: the tiled kernel's images)
-    int denseQ;                          // Q or Qf not diagonal: tiled kernel only
-    int denseR;                          // R not diagonal: tiled kernel, fp64
-    std::vector<double> hm_r2full;       // 2R, m x m row-major
-    std::vector<double> hm_q2m, hm_qf2m, hm_xm, hm_xfm;   // 2Q, 2Qf, (2Q)^-1, (2Qf)^-1 row-major
     // ramp-rate rows (VAR_1): bounds on the device, own workspace (dense Y per workgroup)
     DevBuf<double> ramp_du;      // [du_min | du_max], 2 m doubles; empty until fmpc_set_ramp
     DevBuf<double> ramp_ws;

@@ -108,6 +108,137 @@ void fmpc_host_y_blocks(int n, int T, bool var2, bool has_xf, const std::vector<
     }
 }
 
+int fmpc_host_model_classify(int n, int m, const double* Q, const double* R, const double* Qf, FmpcHostModel& M) {
+    // dense (symmetric positive definite) Q, Qf, R: fast_mpc_objective.m:51-55 takes any square matrices (the tiled kernel's part)
+    const bool denseR = !fmpc_host_is_diag(R, m), denseQ = !fmpc_host_is_diag(Q, n) || !fmpc_host_is_diag(Qf, n);
+    std::vector<double>& R2full = M.r2full;
+    M.denseQ = denseQ ? 1 : 0; M.denseR = denseR ? 1 : 0; R2full.clear();
+    for (int i = 0; i < n; ++i)
+        if (!(fmpc_host_cm(Q, n, i, i) > 0.0) || !(fmpc_host_cm(Qf, n, i, i) > 0.0)) return FMPC_E_NOT_PD_PHI;
+    for (int i = 0; i < m; ++i)
+        if (!(fmpc_host_cm(R, m, i, i) > 0.0)) return FMPC_E_NOT_PD_PHI;
+    if (denseQ)
+        for (int a = 0; a < n; ++a)
+            for (int b = 0; b < a; ++b)
+                if (fmpc_host_cm(Q, n, a, b) != fmpc_host_cm(Q, n, b, a) || fmpc_host_cm(Qf, n, a, b) != fmpc_host_cm(Qf, n, b, a)) return FMPC_E_NOT_PD_PHI;
+    if (denseR) {
+        R2full.assign((size_t)m * m, 0.0);
+        for (int a = 0; a < m; ++a)
+            for (int b = 0; b < m; ++b) {
+                if (fmpc_host_cm(R, m, a, b) != fmpc_host_cm(R, m, b, a)) return FMPC_E_NOT_PD_PHI;
+                R2full[(size_t)a * m + b] = 2.0 * fmpc_host_cm(R, m, a, b);
+            }
+        std::vector<double> tmp;
+        if (!fmpc_host_spd_inverse(R2full, m, tmp)) return FMPC_E_NOT_PD_PHI;      // (the inverse itself is not used: a positive definiteness test)
+    }
+    return FMPC_OK;
+}
+
+int fmpc_host_build_model(int n, int m, int T, int var_order, const double* A1, const double* A2, const double* B,
+                          const double* Q, const double* R, const double* Qf, const double* q, const double* r, const double* qf,
+                          const double* x_min, const double* x_max, const double* u_min, const double* u_max, const double* xf,
+                          FmpcHostModel& M) {
+    const bool var2 = var_order == 2;
+    const int nn = n * n;
+    M.n = n; M.m = m; M.T = T; M.has_xf = xf ? 1 : 0; M.nb = T + M.has_xf; M.var2 = var2 ? 1 : 0;
+    // ---- row-major copies
+    M.a1.assign(nn, 0.0); M.a2.assign(nn, 0.0); M.bt.assign((size_t)m * n, 0.0); M.b.assign((size_t)n * m, 0.0);
+    for (int rr = 0; rr < n; ++rr)
+        for (int c = 0; c < n; ++c) {
+            M.a1[rr * n + c] = fmpc_host_cm(A1, n, rr, c);
+            if (var2) M.a2[rr * n + c] = fmpc_host_cm(A2, n, rr, c);
+        }
+    for (int rr = 0; rr < n; ++rr)
+        for (int c = 0; c < m; ++c) M.bt[(size_t)c * n + rr] = M.b[(size_t)rr * m + c] = fmpc_host_cm(B, n, rr, c);
+    M.R2.resize(m); M.Q2.resize(n); M.Qf2.resize(n);
+    for (int i = 0; i < m; ++i) M.R2[i] = 2.0 * fmpc_host_cm(R, m, i, i);
+    for (int i = 0; i < n; ++i) { M.Q2[i] = 2.0 * fmpc_host_cm(Q, n, i, i); M.Qf2[i] = 2.0 * fmpc_host_cm(Qf, n, i, i); }
+    M.rl.assign(m, 0.0); if (r) M.rl.assign(r, r + m);
+    M.ql.assign(n, 0.0); if (q) M.ql.assign(q, q + n);
+    M.qfl.assign(n, 0.0); if (qf) M.qfl.assign(qf, qf + n);
+    M.umin.assign(u_min, u_min + m); M.umax.assign(u_max, u_max + m);
+    M.umid.resize(m); M.xmid.resize(n);
+    for (int i = 0; i < m; ++i) M.umid[i] = (u_min[i] + u_max[i]) / 2;    // fast_mpc_init.m:19-20
+    for (int i = 0; i < n; ++i) M.xmid[i] = (x_min[i] + x_max[i]) / 2;
+    M.xf.clear(); if (xf) M.xf.assign(xf, xf + n);
+    // X = (2Q)^-1, Xf = (2Qf)^-1 as dense row-major matrices (diagonal weights: diagonal matrices)
+    M.q2m.assign(nn, 0.0); M.qf2m.assign(nn, 0.0); M.xm.assign(nn, 0.0); M.xfm.assign(nn, 0.0);
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b < n; ++b) { M.q2m[a * n + b] = 2.0 * fmpc_host_cm(Q, n, a, b); M.qf2m[a * n + b] = 2.0 * fmpc_host_cm(Qf, n, a, b); }
+    if (M.denseQ) {
+        if (!fmpc_host_spd_inverse(M.q2m, n, M.xm) || !fmpc_host_spd_inverse(M.qf2m, n, M.xfm)) return FMPC_E_NOT_PD_PHI;
+    } else {
+        for (int i = 0; i < n; ++i) { M.xm[i * n + i] = 1.0 / M.Q2[i]; M.xfm[i * n + i] = 1.0 / M.Qf2[i]; }
+    }
+    // ---- iteration-invariant Y blocks, deduplicated; the kernels index them as Yblk + idx*n*n: no padding
+    std::vector<std::vector<double>> blocks;
+    fmpc_host_y_blocks(n, T, var2, xf != nullptr, M.a1, M.a2, M.xm, M.xfm, blocks, M.idxD, M.idx1, M.idx2);
+    M.blocks.clear();
+    for (auto& bk : blocks) M.blocks.insert(M.blocks.end(), bk.begin(), bk.end());
+    // closed-loop prediction matrices (main.mlx, MPC_DesignMatrices): M1_0 = A1, M2_0 = A2, M1_1 = A1^2 + A2,
+    // M2_1 = A1 A2, M1_i = A1 M1_{i-1} + A2 M1_{i-2}, M2_i = M1_{i-1} A2
+    M.m1.assign((size_t)T * nn, 0.0); M.m2.assign((size_t)T * nn, 0.0);
+    auto mul = [&](const double* X, const double* Y, double* Z, double beta) {     // Z = beta Z + X Y (n x n row-major)
+        for (int rr = 0; rr < n; ++rr)
+            for (int c = 0; c < n; ++c) {
+                double t = 0.0;
+                for (int qq = 0; qq < n; ++qq) t += X[rr * n + qq] * Y[qq * n + c];
+                Z[rr * n + c] = beta * Z[rr * n + c] + t;
+            }
+    };
+    const double* a1 = M.a1.data(); const double* a2 = M.a2.data();
+    for (int i = 0; i < T; ++i) {
+        double* m1 = M.m1.data() + (size_t)i * nn; double* m2 = M.m2.data() + (size_t)i * nn;
+        if (i == 0) { for (int e = 0; e < nn; ++e) { m1[e] = a1[e]; m2[e] = a2[e]; } }
+        else if (i == 1) { for (int e = 0; e < nn; ++e) m1[e] = a2[e]; mul(a1, a1, m1, 1.0); mul(a1, a2, m2, 0.0); }
+        else {
+            mul(a1, m1 - nn, m1, 0.0); mul(a2, m1 - 2 * nn, m1, 1.0);
+            mul(m1 - nn, a2, m2, 0.0);
+        }
+    }
+    return FMPC_OK;
+}
+
+void fmpc_host_wave_cold(const FmpcHostModel& M, double k, const int o[14], std::vector<double>& c) {
+    const int n = M.n, m = M.m;
+    c.assign((size_t)o[8], 0.0);
+    for (int j = 0; j < m; ++j) { const FmpcHostModel::Box b = M.box(j, k); c[o[0] + j] = b.cu; c[o[1] + j] = b.hc; c[o[2] + j] = b.wc; }
+    const double* bt = M.bt.data();                               // bt[c*n + r] = B[r][c]
+    for (int a = 0; a < n; ++a) {
+        double cbu = 0.0, bu = 0.0;
+        for (int j = 0; j < m; ++j) {
+            cbu += bt[(size_t)j * n + a] * c[o[2] + j] * c[o[0] + j];
+            bu += bt[(size_t)j * n + a] * M.umid[j];
+        }
+        c[o[4] + a] = cbu;
+        double a1x = 0.0, a2x = 0.0;
+        for (int q = 0; q < n; ++q) { a1x += M.a1[a * n + q] * M.xmid[q]; a2x += M.a2[a * n + q] * M.xmid[q]; }
+        c[o[5] + a] = M.xmid[a] - bu;
+        c[o[6] + a] = M.xmid[a] - bu - a1x;
+        c[o[7] + a] = M.xmid[a] - bu - a1x - a2x;
+        double va = 0.0, va2 = 0.0;
+        for (int j = 0; j < m; ++j) {
+            const double aj = c[o[1] + j] * c[o[2] + j];
+            va += bt[(size_t)j * n + a] * aj * c[o[0] + j];
+            va2 += bt[(size_t)j * n + a] * aj * aj * c[o[0] + j];
+        }
+        c[o[11] + a] = va; c[o[12] + a] = va2;
+        for (int b = 0; b < n; ++b) {
+            double g = 0.0, ma = 0.0, ma2 = 0.0;
+            for (int j = 0; j < m; ++j) {
+                const double bb = bt[(size_t)j * n + a] * bt[(size_t)j * n + b];
+                const double aj = c[o[1] + j] * c[o[2] + j];
+                g += bb * c[o[2] + j]; ma += bb * aj; ma2 += bb * aj * aj;
+            }
+            c[o[3] + a * n + b] = g; c[o[9] + a * n + b] = ma; c[o[10] + a * n + b] = ma2;
+        }
+    }
+    for (int j = 0; j < m; ++j) {
+        const double aj = c[o[1] + j] * c[o[2] + j], cu = c[o[0] + j];
+        c[o[13]] += aj * cu * cu; c[o[13] + 1] += aj * aj * cu * cu;
+    }
+}
+
 // The block table of a model bank (fmpc_bank.h): the walk of fmpc_host_y_blocks above with term lists in place of numbers.
 void fmpc_host_bank_table(int T, bool var2, bool has_xf, bool xf_is_x, FmpcBankTable& out) {
     const int nb = T + (has_xf ? 1 : 0);
@@ -347,7 +478,8 @@ void fmpc_host_panel_layout(int n, int m, int T, int nb, int mp, FmpcPanelIn& L,
 // two sweeps into steps.  30 stages x 27^3: microseconds.
 int fmpc_host_build_panel(const FmpcPanelIn& In, double k, FmpcPanelOut& Out) {
     typedef long double ld;
-    const int n = In.n, m = In.m, T = In.T, nb = In.nb, mp = In.mp;
+    const FmpcHostModel& hm = *In.M;
+    const int n = hm.n, m = hm.m, T = hm.T, nb = hm.nb, mp = In.mp;
     const int nn = n * n;
     Out.valid = 0; Out.nsf = 0; Out.nsb = 0;
     std::vector<double>& pool = Out.pool;
@@ -372,14 +504,11 @@ int fmpc_host_build_panel(const FmpcPanelIn& In, double k, FmpcPanelOut& Out) {
     double* uc = pool.data() + In.o_ucon;
     double sa_cu = 0.0;
     for (int j = 0; j < m; ++j) {
-        const double sp = In.umax[j] - In.umid[j], sm = In.umid[j] - In.umin[j];
-        const double dp = 1.0 / sp, dm = 1.0 / sm;
-        const double hc = k * (dp * dp + dm * dm);
-        const double cu = In.R2[j] * In.umid[j] + In.rl[j] + k * (dp - dm);
-        uc[j] = cu; uc[mp + j] = 1.0 / (In.R2[j] + hc); uc[2 * mp + j] = hc; uc[3 * mp + j] = In.umid[j];
-        sa_cu += cu * cu;
+        const FmpcHostModel::Box b = hm.box(j, k);
+        uc[j] = b.cu; uc[mp + j] = b.wc; uc[2 * mp + j] = b.hc; uc[3 * mp + j] = hm.umid[j];
+        sa_cu += b.cu * b.cu;
     }
-    const double* bt = In.bt;                           // bt[c*n + r] = B[r][c]
+    const double* bt = hm.bt.data();                           // bt[c*n + r] = B[r][c]
     // ---- Y = C Phi^-1 C' at the cold start, block by block: Y_ii = const + G (i < T), Y_{i,i+1}, Y_{i,i+2}
     std::vector<ld> G(nn, 0.0L);
     for (int a = 0; a < n; ++a)
@@ -401,9 +530,9 @@ int fmpc_host_build_panel(const FmpcPanelIn& In, double k, FmpcPanelOut& Out) {
         out.assign(nn, 0.0L);
         const int lo = i < j ? i : j, d = i < j ? j - i : i - j;
         int id = -1;
-        if (d == 0) id = In.idxD[lo]; else if (d == 1) id = In.idx1[lo]; else if (d == 2) id = In.idx2[lo];
+        if (d == 0) id = hm.idxD[lo]; else if (d == 1) id = hm.idx1[lo]; else if (d == 2) id = hm.idx2[lo];
         if (d > 2 || id < 0) return false;
-        const double* src = In.blocks + (size_t)id * nn;
+        const double* src = hm.blocks.data() + (size_t)id * nn;
         for (int r = 0; r < n; ++r) for (int c = 0; c < n; ++c) out[r * n + c] = i <= j ? (ld)src[r * n + c] : (ld)src[c * n + r];
         if (d == 0 && i < T) for (int q = 0; q < nn; ++q) out[q] += G[q];
         return true;
@@ -549,9 +678,9 @@ int fmpc_host_build_panel(const FmpcPanelIn& In, double k, FmpcPanelOut& Out) {
                 M[r * n + c] = a;
             }
         };
-        prod(Linv[rank[0]], In.a1); image(M, -1.0, dst);
-        prod(Linv[rank[0]], In.a2); image(M, -1.0, dst + FP_IMG);
-        if (nb > 1) { prod(Linv[rank[1]], In.a2); image(M, -1.0, dst + 2 * FP_IMG); }
+        prod(Linv[rank[0]], hm.a1.data()); image(M, -1.0, dst);
+        prod(Linv[rank[0]], hm.a2.data()); image(M, -1.0, dst + FP_IMG);
+        if (nb > 1) { prod(Linv[rank[1]], hm.a2.data()); image(M, -1.0, dst + 2 * FP_IMG); }
     }
     // ---- model images
     {
@@ -564,11 +693,11 @@ int fmpc_host_build_panel(const FmpcPanelIn& In, double k, FmpcPanelOut& Out) {
                 }
         double* a = pool.data() + In.o_aimg;
         std::vector<ld> A(nn);
-        for (int i = 0; i < nn; ++i) A[i] = In.a1[i];
+        for (int i = 0; i < nn; ++i) A[i] = hm.a1[i];
         image(A, 1.0, a + FP_AIMG_A1 * FP_IMG);
         for (int r = 0; r < n; ++r) for (int c = 0; c < n; ++c) M[r * n + c] = A[c * n + r];
         image(M, 1.0, a + FP_AIMG_A1T * FP_IMG);
-        for (int i = 0; i < nn; ++i) A[i] = In.a2[i];
+        for (int i = 0; i < nn; ++i) A[i] = hm.a2[i];
         image(A, 1.0, a + FP_AIMG_A2 * FP_IMG);
         for (int r = 0; r < n; ++r) for (int c = 0; c < n; ++c) M[r * n + c] = A[c * n + r];
         image(M, 1.0, a + FP_AIMG_A2T * FP_IMG);
@@ -587,12 +716,12 @@ int fmpc_host_build_panel(const FmpcPanelIn& In, double k, FmpcPanelOut& Out) {
         double t0 = 0.0, t1 = 0.0, t2 = 0.0;
         for (int j = 0; j < m; ++j) {
             t0 += bt[(size_t)j * n + a] * uc[mp + j] * uc[j];
-            t1 += bt[(size_t)j * n + a] * In.umid[j];
+            t1 += bt[(size_t)j * n + a] * hm.umid[j];
             t2 += bt[(size_t)j * n + a] * uc[j];
         }
         cbu[a] = t0; bu[a] = t1; vec[V.bcu + a] = t2;
         double s1 = 0.0, s2 = 0.0;
-        for (int q = 0; q < n; ++q) { s1 += In.a1[a * n + q] * In.xmid[q]; s2 += In.a2[a * n + q] * In.xmid[q]; }
+        for (int q = 0; q < n; ++q) { s1 += hm.a1[a * n + q] * hm.xmid[q]; s2 += hm.a2[a * n + q] * hm.xmid[q]; }
         a1x[a] = s1; a2x[a] = s2;
     }
     std::vector<double> phx((size_t)T * n);
@@ -600,25 +729,25 @@ int fmpc_host_build_panel(const FmpcPanelIn& In, double k, FmpcPanelOut& Out) {
     for (int j = 0; j < T; ++j)
         for (int r = 0; r < n; ++r) {
             const bool last = j + 1 == T;
-            const double q2 = last ? In.Qf2[r] : In.Q2[r];
-            const double d0 = q2 * In.xmid[r] + (last ? In.qfl[r] : In.ql[r]);
+            const double q2 = last ? hm.Qf2[r] : hm.Q2[r];
+            const double d0 = q2 * hm.xmid[r] + (last ? hm.qfl[r] : hm.ql[r]);
             vec[V.dx0 + j * 32 + r] = d0;
             vec[V.iq + j * 32 + r] = 1.0 / q2;
             phx[(size_t)j * n + r] = d0 / q2;
-            vec[V.xc + j * 32 + r] = In.xmid[r] - d0 / q2;
+            vec[V.xc + j * 32 + r] = hm.xmid[r] - d0 / q2;
             rd2_0 += d0 * d0;
         }
-    const bool var2 = In.var_order == 2;
+    const bool var2 = hm.var2 != 0;
     for (int i = 0; i < nb; ++i)
         for (int r = 0; r < n; ++r) {
             double cp, c0;
             if (i < T) {
-                cp = In.xmid[r] - bu[r] - (i >= 1 ? a1x[r] : 0.0) - (i >= 2 ? a2x[r] : 0.0);
+                cp = hm.xmid[r] - bu[r] - (i >= 1 ? a1x[r] : 0.0) - (i >= 2 ? a2x[r] : 0.0);
                 c0 = phx[(size_t)i * n + r] - cbu[r];
-                if (i >= 1) for (int q = 0; q < n; ++q) c0 -= In.a1[r * n + q] * phx[(size_t)(i - 1) * n + q];
-                if (i >= 2 && var2) for (int q = 0; q < n; ++q) c0 -= In.a2[r * n + q] * phx[(size_t)(i - 2) * n + q];
+                if (i >= 1) for (int q = 0; q < n; ++q) c0 -= hm.a1[r * n + q] * phx[(size_t)(i - 1) * n + q];
+                if (i >= 2 && var2) for (int q = 0; q < n; ++q) c0 -= hm.a2[r * n + q] * phx[(size_t)(i - 2) * n + q];
             } else {
-                cp = In.xmid[r] - In.xf[r];
+                cp = hm.xmid[r] - hm.xf[r];
                 c0 = phx[(size_t)(T - 1) * n + r];
             }
             vec[V.cp + i * 32 + r] = cp;
@@ -647,10 +776,10 @@ int fmpc_host_build_panel(const FmpcPanelIn& In, double k, FmpcPanelOut& Out) {
         }
         for (int j = 0; j < mp; ++j) {                               // [c2 | 2R | hp | hm] for the next-exit-test variant
             const bool in = j < m;
-            dz[D.UX + j] = in ? In.R2[j] * In.umid[j] + In.rl[j] : 0.0;
-            dz[D.UX + mp + j] = in ? In.R2[j] : 0.0;
-            dz[D.UX + 2 * mp + j] = in ? In.umax[j] - In.umid[j] : 1.0;
-            dz[D.UX + 3 * mp + j] = in ? In.umid[j] - In.umin[j] : 1.0;
+            dz[D.UX + j] = in ? hm.R2[j] * hm.umid[j] + hm.rl[j] : 0.0;
+            dz[D.UX + mp + j] = in ? hm.R2[j] : 0.0;
+            dz[D.UX + 2 * mp + j] = in ? hm.umax[j] - hm.umid[j] : 1.0;
+            dz[D.UX + 3 * mp + j] = in ? hm.umid[j] - hm.umin[j] : 1.0;
         }
         for (int r = 0; r < 32; ++r) {
             dz[D.XQ + r] = vec[V.xc + r]; dz[D.XQ + 32 + r] = vec[V.xc + (T - 1) * 32 + r];
@@ -665,25 +794,20 @@ int fmpc_host_build_panel(const FmpcPanelIn& In, double k, FmpcPanelOut& Out) {
 
 void fmpc_host_build_first_move(const FmpcFirstIn& In, FmpcFirstOut& Out) {
     typedef long double ld;
-    const int n = In.n, m = In.m, T = In.T, nb = In.nb, nc = 4 * n;
-    const bool var2 = In.var2 != 0;
+    const FmpcHostModel& hm = *In.M;
+    const int n = hm.n, m = hm.m, T = hm.T, nb = hm.nb, nc = 4 * n;
+    const bool var2 = hm.var2 != 0;
+    const double* xf = hm.xf_or_xmid();
     Out.nc = nc;
     std::vector<double> cu(m), wc(m), av(m);
-    for (int j = 0; j < m; ++j) {
-        const double sp = In.umax[j] - In.umid[j], sm = In.umid[j] - In.umin[j];
-        const double dp = 1.0 / sp, dm = 1.0 / sm;
-        const double hc = In.k * (dp * dp + dm * dm);
-        cu[j] = In.R2[j] * In.umid[j] + In.rl[j] + In.k * (dp - dm);
-        wc[j] = 1.0 / (In.R2[j] + hc);
-        av[j] = hc * wc[j];
-    }
-    const double* bt = In.bt;                                     // bt[c*n + r] = B[r][c]
+    for (int j = 0; j < m; ++j) { const FmpcHostModel::Box b = hm.box(j, In.k); cu[j] = b.cu; wc[j] = b.wc; av[j] = b.hc * b.wc; }
+    const double* bt = hm.bt.data();                                     // bt[c*n + r] = B[r][c]
     // ---- u0 = u0c + K0 d
     Out.K0t.assign((size_t)nc * m, 0.0); Out.u0c.assign(m, 0.0);
     for (int j = 0; j < m; ++j) {
         ld t = 0.0L;
         for (int r = 0; r < n; ++r) t += (ld)bt[(size_t)j * n + r] * (ld)In.nuc[r];
-        Out.u0c[j] = (double)((ld)In.umid[j] + (ld)wc[j] * (t - (ld)cu[j]));
+        Out.u0c[j] = (double)((ld)hm.umid[j] + (ld)wc[j] * (t - (ld)cu[j]));
         for (int c = 0; c < nc; ++c) {
             ld s = 0.0L;
             for (int r = 0; r < n; ++r) s += (ld)bt[(size_t)j * n + r] * (ld)In.J[(size_t)r * nc + c];
@@ -737,23 +861,23 @@ void fmpc_host_build_first_move(const FmpcFirstIn& In, FmpcFirstOut& Out) {
     ld ep0 = 0.0L;
     std::vector<ld> bu(n, 0.0L), a1x(n, 0.0L), a2x(n, 0.0L);
     for (int r = 0; r < n; ++r) {
-        for (int j = 0; j < m; ++j) bu[r] += (ld)bt[(size_t)j * n + r] * (ld)In.umid[j];
-        for (int q = 0; q < n; ++q) { a1x[r] += (ld)In.a1[r * n + q] * (ld)In.xmid[q]; a2x[r] += (ld)In.a2[r * n + q] * (ld)In.xmid[q]; }
+        for (int j = 0; j < m; ++j) bu[r] += (ld)bt[(size_t)j * n + r] * (ld)hm.umid[j];
+        for (int q = 0; q < n; ++q) { a1x[r] += (ld)hm.a1[r * n + q] * (ld)hm.xmid[q]; a2x[r] += (ld)hm.a2[r * n + q] * (ld)hm.xmid[q]; }
     }
     for (int i = 0; i < nb; ++i)
         for (int r = 0; r < n; ++r) {
             ld cp;
             for (int c = 0; c < nc; ++c) row[c] = 0.0L;
             if (i < T) {
-                cp = (ld)In.xmid[r] - bu[r] - (i >= 1 ? a1x[r] : 0.0L) - (i >= 2 ? a2x[r] : 0.0L);
-                if (i == 0) for (int q = 0; q < n; ++q) { row[q] = In.a1[r * n + q]; row[n + q] = var2 ? (ld)In.a2[r * n + q] : 0.0L; }
-                if (i == 1 && var2) for (int q = 0; q < n; ++q) row[q] = In.a2[r * n + q];
+                cp = (ld)hm.xmid[r] - bu[r] - (i >= 1 ? a1x[r] : 0.0L) - (i >= 2 ? a2x[r] : 0.0L);
+                if (i == 0) for (int q = 0; q < n; ++q) { row[q] = hm.a1[r * n + q]; row[n + q] = var2 ? (ld)hm.a2[r * n + q] : 0.0L; }
+                if (i == 1 && var2) for (int q = 0; q < n; ++q) row[q] = hm.a2[r * n + q];
                 for (int q = 0; q < n; ++q) {
-                    row[2 * n + q] = -(ld)In.m1[((size_t)i * n + r) * n + q];
-                    row[3 * n + q] = -(ld)In.m2[((size_t)i * n + r) * n + q];
+                    row[2 * n + q] = -(ld)hm.m1[((size_t)i * n + r) * n + q];
+                    row[3 * n + q] = -(ld)hm.m2[((size_t)i * n + r) * n + q];
                 }
             } else {
-                cp = (ld)In.xmid[r] - (ld)In.xf[r];
+                cp = (ld)hm.xmid[r] - (ld)xf[r];
             }
             ep0 += cp * cp;
             for (int c1 = 0; c1 < nc; ++c1) {
@@ -842,15 +966,16 @@ void fmpc_host_mfma_a_images(const double* M, int rows, std::vector<double>& img
 //   x_j+   = xmid + X_j (-(2 Q_j xmid + q_j) - nu+_{j-1} + A1' nu+_j + A2' nu+_{j+1} [- nu+_T])   j = 1..T, X_j = (2 Q_j)^-1
 void fmpc_host_build_affine(const FmpcAffineIn& In, FmpcAffineOut& Out) {
     typedef long double ld;
-    const int n = In.n, m = In.m, T = In.T, s = n + m, nd = 2 * n, ncJ = In.ncJ;
+    const FmpcHostModel& hm = *In.M;
+    const int n = hm.n, m = hm.m, T = hm.T, s = n + m, nd = 2 * n, ncJ = In.ncJ;
     Out.rows = T * s; Out.tiles = (Out.rows + 15) / 16;
     Out.Kz.assign((size_t)Out.rows * FA_KC, 0.0);
     std::vector<ld> cu(m), wc(m);
     for (int j = 0; j < m; ++j) {
-        const ld sp = (ld)In.umax[j] - (ld)In.umid[j], sm = (ld)In.umid[j] - (ld)In.umin[j];
+        const ld sp = (ld)hm.umax[j] - (ld)hm.umid[j], sm = (ld)hm.umid[j] - (ld)hm.umin[j];
         const ld dp = 1.0L / sp, dm = 1.0L / sm;
-        cu[j] = (ld)In.R2[j] * (ld)In.umid[j] + (ld)In.rl[j] + (ld)In.k * (dp - dm);
-        wc[j] = 1.0L / ((ld)In.R2[j] + (ld)In.k * (dp * dp + dm * dm));
+        cu[j] = (ld)hm.R2[j] * (ld)hm.umid[j] + (ld)hm.rl[j] + (ld)In.k * (dp - dm);
+        wc[j] = 1.0L / ((ld)hm.R2[j] + (ld)In.k * (dp * dp + dm * dm));
     }
     // nu+ as an affine function of d: column c < nd of J, column nd = nuc
     auto nuv = [&](int blk, int r, int c) -> ld {
@@ -861,8 +986,8 @@ void fmpc_host_build_affine(const FmpcAffineIn& In, FmpcAffineOut& Out) {
             double* row = &Out.Kz[((size_t)st * s + j) * FA_KC];
             for (int c = 0; c <= nd; ++c) {
                 ld t = 0.0L;
-                for (int r = 0; r < n; ++r) t += (ld)In.bt[(size_t)j * n + r] * nuv(st, r, c);
-                if (c == nd) t = (ld)In.umid[j] + wc[j] * (t - cu[j]); else t *= wc[j];
+                for (int r = 0; r < n; ++r) t += (ld)hm.bt[(size_t)j * n + r] * nuv(st, r, c);
+                if (c == nd) t = (ld)hm.umid[j] + wc[j] * (t - cu[j]); else t *= wc[j];
                 row[c] = (double)t;
             }
         }
@@ -870,20 +995,20 @@ void fmpc_host_build_affine(const FmpcAffineIn& In, FmpcAffineOut& Out) {
         const bool last = jx == T;
         for (int r = 0; r < n; ++r) {
             double* row = &Out.Kz[((size_t)st * s + m + r) * FA_KC];
-            const ld q2 = last ? (ld)In.Qf2[r] : (ld)In.Q2[r], ql = last ? (ld)In.qfl[r] : (ld)In.ql[r];
+            const ld q2 = last ? (ld)hm.Qf2[r] : (ld)hm.Q2[r], ql = last ? (ld)hm.qfl[r] : (ld)hm.ql[r];
             for (int c = 0; c <= nd; ++c) {
                 ld v = -nuv(jx - 1, r, c);
-                if (jx < T) for (int q = 0; q < n; ++q) v += (ld)In.a1[q * n + r] * nuv(jx, q, c);
-                if (jx + 1 < T) for (int q = 0; q < n; ++q) v += (ld)In.a2[q * n + r] * nuv(jx + 1, q, c);
-                if (last && In.has_xf) v -= nuv(T, r, c);
-                if (c == nd) v = (ld)In.xmid[r] + (v - (q2 * (ld)In.xmid[r] + ql)) / q2; else v /= q2;
+                if (jx < T) for (int q = 0; q < n; ++q) v += (ld)hm.a1[q * n + r] * nuv(jx, q, c);
+                if (jx + 1 < T) for (int q = 0; q < n; ++q) v += (ld)hm.a2[q * n + r] * nuv(jx + 1, q, c);
+                if (last && hm.has_xf) v -= nuv(T, r, c);
+                if (c == nd) v = (ld)hm.xmid[r] + (v - (q2 * (ld)hm.xmid[r] + ql)) / q2; else v /= q2;
                 row[c] = (double)v;
             }
         }
     }
     fmpc_host_mfma_a_images(Out.Kz.data(), Out.rows, Out.img);
     // nu+ = nuc + J d as further rows (requested by callers that want the multipliers)
-    Out.nu_rows = In.nb * n; Out.nu_tiles = (Out.nu_rows + 15) / 16;
+    Out.nu_rows = hm.nb * n; Out.nu_tiles = (Out.nu_rows + 15) / 16;
     std::vector<double> Jn((size_t)Out.nu_rows * FA_KC, 0.0), imgn;
     for (int r = 0; r < Out.nu_rows; ++r) {
         for (int c = 0; c < nd; ++c) Jn[(size_t)r * FA_KC + c] = In.J[(size_t)r * ncJ + c];
@@ -918,7 +1043,7 @@ void fmpc_host_build_affine(const FmpcAffineIn& In, FmpcAffineOut& Out) {
             for (int r = 0; r < 16; ++r) {
                 const int j = 16 * (Out.plan[st].tb + u) + r - st * s;                  // actuator of the row
                 for (int c = 0; c <= n; ++c) {
-                    const ld v = c < n ? wc[j] * (ld)In.bt[(size_t)j * n + c] : (ld)In.umid[j] - wc[j] * cu[j];
+                    const ld v = c < n ? wc[j] * (ld)hm.bt[(size_t)j * n + c] : (ld)hm.umid[j] - wc[j] * cu[j];
                     im[(size_t)(c >> 2) * 64 + (c & 3) * 16 + r] = (double)v;
                 }
             }
@@ -982,10 +1107,13 @@ extern "C" int fmpc_debug_nu_cut(int cnt, int p, int parts, int* b, int* e) {
 // [2 (T - 1)][FA_KS][64], the u-tile images [u tiles][FA_NU_KS][64] (any of them may be NULL).  Returns the u tiles, < 0 on bad arguments.
 extern "C" int fmpc_debug_build_affine_nu(int n, int m, int T, int nb, int has_xf, double k, const double* const* arr, double* Kz, double* imgJ, double* imgG) {
     if (n != 27 || m < 1 || T < 1 || nb < T || !arr) return -1;
+    FmpcHostModel M;
+    M.n = n; M.m = m; M.T = T; M.nb = nb; M.has_xf = has_xf;
+    auto vec = [&](int i, int cnt) { return std::vector<double>(arr[i], arr[i] + cnt); };
+    M.bt = vec(0, m * n); M.umax = vec(1, m); M.umin = vec(2, m); M.umid = vec(3, m); M.xmid = vec(4, n); M.R2 = vec(5, m); M.rl = vec(6, m);
+    M.Q2 = vec(7, n); M.Qf2 = vec(8, n); M.ql = vec(9, n); M.qfl = vec(10, n); M.a1 = vec(11, n * n); M.a2 = vec(12, n * n);
     FmpcAffineIn In;
-    In.n = n; In.m = m; In.T = T; In.nb = nb; In.has_xf = has_xf; In.ncJ = 2 * n; In.k = k;
-    In.bt = arr[0]; In.umax = arr[1]; In.umin = arr[2]; In.umid = arr[3]; In.xmid = arr[4]; In.R2 = arr[5]; In.rl = arr[6]; In.Q2 = arr[7];
-    In.Qf2 = arr[8]; In.ql = arr[9]; In.qfl = arr[10]; In.a1 = arr[11]; In.a2 = arr[12]; In.J = arr[13]; In.nuc = arr[14];
+    In.M = &M; In.ncJ = 2 * n; In.k = k; In.J = arr[13]; In.nuc = arr[14];
     FmpcAffineOut Out;
     fmpc_host_build_affine(In, Out);
     if (Kz) std::copy(Out.Kz.begin(), Out.Kz.end(), Kz);
@@ -997,13 +1125,14 @@ extern "C" int fmpc_debug_build_affine_nu(int n, int m, int T, int nb, int has_x
 // ---- cold-start step with the ramp-rate rows: constants of the Woodbury form (fmpc_host.h)
 void fmpc_host_build_ramp_cold(const FmpcRampColdIn& In, FmpcRampColdOut& Out) {
     typedef long double ld;
-    const int n = In.n, m = In.m, T = In.T, nb = In.nb, s = n + m, Nz = T * s, nbn = nb * n;
-    const bool var2 = In.var2 != 0, has_xf = In.has_xf != 0;
+    const FmpcHostModel& hm = *In.M;
+    const int n = hm.n, m = hm.m, T = hm.T, nb = hm.nb, s = n + m, Nz = T * s, nbn = nb * n;
+    const bool var2 = hm.var2 != 0, has_xf = hm.has_xf != 0;
     Out.valid = 0;
     // ---- per actuator: box and ramp terms at the start point, the tridiagonal and its inverse
     std::vector<ld> hb(m), gb(m), erb(m), grb(m);
     for (int c = 0; c < m; ++c) {
-        const ld dp = 1.0L / ((ld)In.umax[c] - (ld)In.umid[c]), dm = 1.0L / ((ld)In.umid[c] - (ld)In.umin[c]);
+        const ld dp = 1.0L / ((ld)hm.umax[c] - (ld)hm.umid[c]), dm = 1.0L / ((ld)hm.umid[c] - (ld)hm.umin[c]);
         hb[c] = (ld)In.k * (dp * dp + dm * dm); gb[c] = (ld)In.k * (dp - dm);
         const ld rp = 1.0L / (ld)In.dumax[c], rm = 1.0L / (-(ld)In.dumin[c]);       // slacks of u_j - u_{j-1} = 0
         erb[c] = (ld)In.k * (rp * rp + rm * rm); grb[c] = (ld)In.k * (rp - rm);
@@ -1018,7 +1147,7 @@ void fmpc_host_build_ramp_cold(const FmpcRampColdIn& In, FmpcRampColdOut& Out) {
         for (int j = 0; j < T; ++j) {
             const ld hdj = hb[c] + (j >= 1 ? erb[c] : 0.0L) + (j + 1 < T ? erb[c] : 0.0L);
             Out.hd[(size_t)j * m + c] = (double)hdj;
-            ld d = (ld)In.R2[c] + hdj;
+            ld d = (ld)hm.R2[c] + hdj;
             if (j > 0) d -= lo[j - 1] * lo[j - 1] * dg[j - 1];
             if (!(d > 0.0L) || !std::isfinite((double)d)) return;
             dg[j] = d;
@@ -1041,17 +1170,17 @@ void fmpc_host_build_ramp_cold(const FmpcRampColdIn& In, FmpcRampColdOut& Out) {
         for (int j = 0; j < T; ++j) Out.g0[(size_t)j * m + c] = Out.Gf[((size_t)j * T + 0) * m + c];
     }
     for (size_t i = 0; i < Gl.size(); ++i) Gl[i] = (ld)Out.Gf[i];   // (the device applies the rounded values: keep the algebra consistent)
-    auto qinv = [&](int jx, int r) -> ld { return 1.0L / (jx == T ? (ld)In.Qf2[r] : (ld)In.Q2[r]); };   // x_jx, jx = 1..T
+    auto qinv = [&](int jx, int r) -> ld { return 1.0L / (jx == T ? (ld)hm.Qf2[r] : (ld)hm.Q2[r]); };   // x_jx, jx = 1..T
     // ---- gbar, phibar = Phibar^-1 (-gbar)
     Out.gbar_u.assign((size_t)T * m, 0.0); Out.gbar_x.assign((size_t)T * n, 0.0);
     Out.phib_u.assign((size_t)T * m, 0.0); Out.phib_x.assign((size_t)T * n, 0.0);
     std::vector<ld> gu((size_t)T * m), gx((size_t)T * n), pu((size_t)T * m), px((size_t)T * n);
     for (int j = 0; j < T; ++j) {
         for (int c = 0; c < m; ++c)
-            gu[(size_t)j * m + c] = (ld)In.R2[c] * (ld)In.umid[c] + (ld)In.rl[c] + gb[c] + (j >= 1 ? grb[c] : 0.0L) - (j + 1 < T ? grb[c] : 0.0L);
+            gu[(size_t)j * m + c] = (ld)hm.R2[c] * (ld)hm.umid[c] + (ld)hm.rl[c] + gb[c] + (j >= 1 ? grb[c] : 0.0L) - (j + 1 < T ? grb[c] : 0.0L);
         for (int r = 0; r < n; ++r) {
             const bool last = j + 1 == T;
-            gx[(size_t)j * n + r] = last ? (ld)In.Qf2[r] * (ld)In.xmid[r] + (ld)In.qfl[r] : (ld)In.Q2[r] * (ld)In.xmid[r] + (ld)In.ql[r];
+            gx[(size_t)j * n + r] = last ? (ld)hm.Qf2[r] * (ld)hm.xmid[r] + (ld)hm.qfl[r] : (ld)hm.Q2[r] * (ld)hm.xmid[r] + (ld)hm.ql[r];
         }
     }
     for (int j = 0; j < T; ++j) {
@@ -1071,12 +1200,12 @@ void fmpc_host_build_ramp_cold(const FmpcRampColdIn& In, FmpcRampColdOut& Out) {
         for (int r = 0; r < n; ++r) {
             std::vector<Ent>& row = Cr[(size_t)i * n + r];
             row.push_back({i * s + m + r, 1.0L});
-            for (int c = 0; c < m; ++c) row.push_back({i * s + c, -(ld)In.bt[(size_t)c * n + r]});
-            if (i >= 1) for (int q = 0; q < n; ++q) row.push_back({(i - 1) * s + m + q, -(ld)In.a1[(size_t)r * n + q]});
-            if (var2 && i >= 2) for (int q = 0; q < n; ++q) row.push_back({(i - 2) * s + m + q, -(ld)In.a2[(size_t)r * n + q]});
+            for (int c = 0; c < m; ++c) row.push_back({i * s + c, -(ld)hm.bt[(size_t)c * n + r]});
+            if (i >= 1) for (int q = 0; q < n; ++q) row.push_back({(i - 1) * s + m + q, -(ld)hm.a1[(size_t)r * n + q]});
+            if (var2 && i >= 2) for (int q = 0; q < n; ++q) row.push_back({(i - 2) * s + m + q, -(ld)hm.a2[(size_t)r * n + q]});
         }
     if (has_xf) for (int r = 0; r < n; ++r) Cr[(size_t)T * n + r].push_back({(T - 1) * s + m + r, 1.0L});
-    auto zstart = [&](int col) -> ld { const int e = col % s; return e < m ? (ld)In.umid[e] : (ld)In.xmid[e - m]; };
+    auto zstart = [&](int col) -> ld { const int e = col % s; return e < m ? (ld)hm.umid[e] : (ld)hm.xmid[e - m]; };
     // cpb = C z0 (- xf on the terminal rows), betab = C phibar + cpb
     Out.cpb.assign(nbn, 0.0); Out.betab.assign(nbn, 0.0);
     auto phib_at = [&](int col) -> ld { const int j = col / s, e = col % s; return e < m ? pu[(size_t)j * m + e] : px[(size_t)j * n + (e - m)]; };
@@ -1084,7 +1213,7 @@ void fmpc_host_build_ramp_cold(const FmpcRampColdIn& In, FmpcRampColdOut& Out) {
     for (int a = 0; a < nbn; ++a) {
         ld cz = 0.0L, cp = 0.0L;
         for (const Ent& e : Cr[a]) { cz += e.v * zstart(e.col); cp += e.v * phib_at(e.col); }
-        if (a >= T * n) cz -= (ld)In.xf[a - T * n];
+        if (a >= T * n) cz -= (ld)hm.xf[a - T * n];
         cpl[a] = cz; betal[a] = cp + cz;
         Out.cpb[a] = (double)cz; Out.betab[a] = (double)(cp + cz);
     }

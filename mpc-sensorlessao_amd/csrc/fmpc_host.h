@@ -1,5 +1,7 @@
 // Host-only builders of the library: everything that is computed on the CPU once per handle or per (handle, k) and then
-// uploaded -- the iteration-invariant Y blocks with their de-duplication, the panel path's twisted block factorisation in
+// uploaded -- the host model of a handle (FmpcHostModel: the arguments of fmpc_create row-major with everything derived from them,
+// which every builder below reads), the iteration-invariant Y blocks with their de-duplication, the cold-start constants of the
+// wave kernel, the panel path's twisted block factorisation in
 // long double with its operator images and sweep schedules, and the least-recently-used cache of the one-shot entry.
 // No HIP in here: the API files (fmpc_api.hip, fmpc_bank_api.hip) call these and keep the allocation, the upload and the launches
 // only; tests/host_san builds the same file with g++ -fsanitize=address,undefined and checks the factorisation against a dense
@@ -29,16 +31,46 @@ void fmpc_host_y_blocks(int n, int T, bool var2, bool has_xf, const std::vector<
                         const std::vector<double>& X, const std::vector<double>& Xf,
                         std::vector<std::vector<double>>& blocks, std::vector<int>& idxD, std::vector<int>& idx1, std::vector<int>& idx2);
 
-// Inputs of the panel-path builder: host copies of the model (row-major) and the layout of the constant pool.
+// ---- the host model of a handle: what fmpc_create is given, row-major, and what is derived from it once.  Each stored once;
+// the builders below read it through `const FmpcHostModel* M` of their inputs.
+struct FmpcHostModel {
+    int n = 0, m = 0, T = 0, nb = 0, var2 = 0, has_xf = 0, denseQ = 0, denseR = 0;      // nb = T + has_xf block rows
+    std::vector<double> a1, a2, b, bt;  // row-major: a1, a2 n x n (a2: zeros for VAR(1)); b[r*m + c] = bt[c*n + r] = B[r][c]
+    std::vector<double> R2, Q2, Qf2, rl, ql, qfl;   // the diagonals of 2R, 2Q, 2Qf; linear terms r, q, qf (zeros for a NULL argument)
+    std::vector<double> umin, umax, umid, xmid;     // box of u, midpoints of both boxes (fast_mpc_init.m:19-20)
+    std::vector<double> xf;             // terminal state; empty when there is none
+    std::vector<double> q2m, qf2m, xm, xfm, r2full; // dense row-major: 2Q, 2Qf, (2Q)^-1, (2Qf)^-1 n x n; 2R m x m (dense R only, else empty)
+    std::vector<double> blocks;         // the unique Y blocks (fmpc_host_y_blocks) back to back, n x n row-major each
+    std::vector<int> idxD, idx1, idx2;  // [nb]: block id or -1 (none)
+    std::vector<double> m1, m2;         // closed-loop prediction matrices (T n) x n row-major (main.mlx, MPC_DesignMatrices)
+    const double* xf_or_xmid() const { return xf.empty() ? xmid.data() : xf.data(); }
+    // Box terms of actuator j at the mid-box start for barrier weight k, as the cold-start builders share them (in double):
+    // cu = 2R ubar + r + k (1/s+ - 1/s-), hc = k (1/s+^2 + 1/s-^2), wc = 1 / (2R + hc)
+    struct Box { double cu, hc, wc; };
+    Box box(int j, double k) const {
+        const double sp = umax[j] - umid[j], sm = umid[j] - umin[j], dp = 1.0 / sp, dm = 1.0 / sm, hc = k * (dp * dp + dm * dm);
+        return {R2[j] * umid[j] + rl[j] + k * (dp - dm), hc, 1.0 / (R2[j] + hc)};
+    }
+};
+// The weight checks of fmpc_create (Q, Qf n x n, R m x m, column-major): positive diagonals, dense Q / Qf / R symmetric, dense 2R
+// positive definite.  FMPC_OK or FMPC_E_NOT_PD_PHI; sets M.denseQ (Q or Qf is not diagonal), M.denseR and M.r2full.
+int fmpc_host_model_classify(int n, int m, const double* Q, const double* R, const double* Qf, FmpcHostModel& M);
+// The rest of M from the (checked, column-major) arguments of fmpc_create, after the classification: copies, doubled weights,
+// inverses, Y blocks, M1 / M2.  FMPC_E_NOT_PD_PHI when dense 2Q or 2Qf is not positive definite.
+int fmpc_host_build_model(int n, int m, int T, int var_order, const double* A1, const double* A2, const double* B,
+                          const double* Q, const double* R, const double* Qf, const double* q, const double* r, const double* qf,
+                          const double* x_min, const double* x_max, const double* u_min, const double* u_max, const double* xf,
+                          FmpcHostModel& M);
+// Cold-start constants of the wave kernel for barrier weight k (FwCold in fmpc_kernel_wave.hip): k-dependent vectors and the
+// n x n matrices G, Ma, Ma2.  off: fmpc_wave_cold_layout (off[8] = length of c).
+void fmpc_host_wave_cold(const FmpcHostModel& M, double k, const int off[14], std::vector<double>& c);
+
+// Inputs of the panel-path builder: the model and the layout of the constant pool.
 struct FmpcPanelIn {
-    int n, m, T, nb, mp, var_order;
+    const FmpcHostModel* M;
+    int mp;
     size_t pool_doubles, o_simg, o_limg, o_bt, o_aimg, o_vec, o_ucon, o_dz;
     int limg_cap;
-    const double *umax, *umin, *umid, *xmid, *R2, *rl, *Q2, *Qf2, *ql, *qfl, *xf;
-    const double *bt;                   // bt[c*n + r] = B[r][c]
-    const double *a1, *a2;              // n x n row-major
-    const double *blocks;               // unique Y blocks, n x n row-major each
-    const int *idxD, *idx1, *idx2;
 };
 struct FmpcPanelOut {
     std::vector<double> pool;           // [simg | limg | btimg | aimg | vec | ucon | dump | dzimg] per the offsets above
@@ -119,9 +151,8 @@ bool fmpc_host_inverse_images(int n, int T, int nb, bool var2, int jks, int jks2
 // Matrices are stored [column][row] (consecutive threads = consecutive rows of a product).
 #define FM_NC_MAX 108
 struct FmpcFirstIn {
-    int n, m, T, nb, var2, has_xf;
-    const double *bt, *umax, *umin, *umid, *xmid, *R2, *rl, *a1, *a2, *m1, *m2, *xf;
-    const double *J;                    // nb n x 4n row-major: columns [x0 | x0_pre | B u1 | B u2]
+    const FmpcHostModel* M;
+    const double *J;                   // nb n x 4n row-major: columns [x0 | x0_pre | B u1 | B u2]
     const double *nuc;                  // nb n
     double k;
 };
@@ -138,8 +169,8 @@ void fmpc_host_build_first_move(const FmpcFirstIn& In, FmpcFirstOut& Out);
 #define FA_KS 14                        // k-steps of 4: 2 n = 54 data columns, column 54 = the constant zc (times 1), column 55 = 0
 #define FA_KC (4 * FA_KS)
 struct FmpcAffineIn {
-    int n, m, T, nb, has_xf, ncJ;       // J: nb n rows x ncJ columns row-major, the first 2 n columns are used
-    const double *bt, *umax, *umin, *umid, *xmid, *R2, *rl, *Q2, *Qf2, *ql, *qfl, *a1, *a2;
+    const FmpcHostModel* M;
+    int ncJ;                            // J: nb n rows x ncJ columns row-major, the first 2 n columns are used
     const double *J, *nuc;
     double k;
 };
@@ -212,9 +243,8 @@ void fmpc_host_mfma_a_images(const double* M, int rows, std::vector<double>& img
 //     phi = Phibar^-1 f_z ,  nu = Ybar^-1 (C phi - f_nu) ,  z = phi - Phibar^-1 C' nu ,   Ybar = C Phibar^-1 C'
 // with Phibar^-1 = per actuator the inverse Gf of its T x T tridiagonal, per state entry 1 / (2Q).
 struct FmpcRampColdIn {
-    int n, m, T, nb, var2, has_xf;
-    const double *bt, *a1, *a2;         // bt[c*n + r] = B[r][c]; a1, a2 row-major n x n
-    const double *umax, *umin, *umid, *xmid, *R2, *rl, *Q2, *Qf2, *ql, *qfl, *xf, *dumin, *dumax;
+    const FmpcHostModel* M;             // (its diagonals Q2, Qf2, R2 are read: never for dense weights)
+    const double *dumin, *dumax;        // ramp bounds, m each
     double k;
 };
 struct FmpcRampColdOut {

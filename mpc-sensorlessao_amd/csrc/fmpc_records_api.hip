@@ -16,21 +16,21 @@
 static int fmpc_ensure_records(fmpc_handle h, hipStream_t stream) {
     if (h->rec_ready) return FMPC_OK;
     const int n = h->n, m = h->m;
-    const int panel = n <= REC_NMAX && !h->denseQ && !h->denseR;
+    const int panel = n <= REC_NMAX && !h->hm.denseQ && !h->hm.denseR;
     std::vector<double> v;
     if (panel) {
         const int mpad = (m + 15) & ~15;
         h->rec_oQf = REC_NMAX; h->rec_oR = 2 * REC_NMAX;
         v.assign(2 * REC_NMAX + (size_t)mpad, 0.0);
-        for (int i = 0; i < n; ++i) { v[i] = 0.5 * h->hm_Q2[i]; v[h->rec_oQf + i] = 0.5 * h->hm_Qf2[i]; }
-        for (int j = 0; j < m; ++j) v[h->rec_oR + j] = 0.5 * h->hm_R2[j];
+        for (int i = 0; i < n; ++i) { v[i] = 0.5 * h->hm.Q2[i]; v[h->rec_oQf + i] = 0.5 * h->hm.Qf2[i]; }
+        for (int j = 0; j < m; ++j) v[h->rec_oR + j] = 0.5 * h->hm.R2[j];
     } else {
         const size_t nn = (size_t)n * n;
         h->rec_oQf = nn; h->rec_oR = 2 * nn;
         v.assign(2 * nn + (size_t)m * m, 0.0);
-        for (size_t e = 0; e < nn; ++e) { v[e] = 0.5 * h->hm_q2m[e]; v[nn + e] = 0.5 * h->hm_qf2m[e]; }
-        if (h->denseR) for (size_t e = 0; e < (size_t)m * m; ++e) v[2 * nn + e] = 0.5 * h->hm_r2full[e];
-        else for (int j = 0; j < m; ++j) v[2 * nn + (size_t)j * m + j] = 0.5 * h->hm_R2[j];
+        for (size_t e = 0; e < nn; ++e) { v[e] = 0.5 * h->hm.q2m[e]; v[nn + e] = 0.5 * h->hm.qf2m[e]; }
+        if (h->hm.denseR) for (size_t e = 0; e < (size_t)m * m; ++e) v[2 * nn + e] = 0.5 * h->hm.r2full[e];
+        else for (int j = 0; j < m; ++j) v[2 * nn + (size_t)j * m + j] = 0.5 * h->hm.R2[j];
     }
     const int rc = h->rec_w.assign(v.data(), v.size(), stream);       // (FMPC_E_ALLOC while the stream is being captured)
     if (rc != FMPC_OK) return rc;

@@ -59,15 +59,17 @@ int main(int argc, char** argv) {
     for (auto& b : blocks) yall.insert(yall.end(), b.begin(), b.end());
 
     // ---- panel-path builder
+    FmpcHostModel HM;
+    HM.n = n; HM.m = m; HM.T = T; HM.nb = nb; HM.var2 = var2 ? 1 : 0; HM.has_xf = has_xf;
+    HM.umax = umax; HM.umin = umin; HM.umid = umid; HM.xmid = xmid; HM.R2 = R2; HM.rl = rl;
+    HM.Q2 = Q2; HM.Qf2 = Qf2; HM.ql = ql; HM.qfl = qfl; if (has_xf) HM.xf = xf;
+    HM.bt = bt; HM.a1 = a1; HM.a2 = a2; HM.blocks = yall;
+    HM.idxD = idxD; HM.idx1 = idx1; HM.idx2 = idx2;
     FmpcPanelIn In;
-    In.n = n; In.m = m; In.T = T; In.nb = nb; In.mp = mp; In.var_order = var_order;
+    In.M = &HM; In.mp = mp;
     size_t o_dump = 0, total = 0; int dz_len = 0;
     fmpc_host_panel_layout(n, m, T, nb, mp, In, &o_dump, &total, &dz_len);
     if (!(In.pool_doubles == o_dump && total > o_dump && dz_len > 0)) return fail("pool layout");
-    In.umax = umax.data(); In.umin = umin.data(); In.umid = umid.data(); In.xmid = xmid.data(); In.R2 = R2.data(); In.rl = rl.data();
-    In.Q2 = Q2.data(); In.Qf2 = Qf2.data(); In.ql = ql.data(); In.qfl = qfl.data(); In.xf = xf.data();
-    In.bt = bt.data(); In.a1 = a1.data(); In.a2 = a2.data(); In.blocks = yall.data();
-    In.idxD = idxD.data(); In.idx1 = idx1.data(); In.idx2 = idx2.data();
     const double k = 1e-2;
     FmpcPanelOut Out;
     if (fmpc_host_build_panel(In, k, Out) != 0 || !Out.valid) return fail("panel builder did not produce a valid result");
@@ -190,10 +192,9 @@ int main(int argc, char** argv) {
         for (auto& v : nuc) v = 0.1 * N01(rng);
         for (auto& v : m1) v = 0.3 * N01(rng);
         for (auto& v : m2) v = 0.3 * N01(rng);
+        HM.m1 = m1; HM.m2 = m2;
         FmpcFirstIn Fi;
-        Fi.n = n; Fi.m = m; Fi.T = T; Fi.nb = nb; Fi.var2 = var2 ? 1 : 0; Fi.has_xf = has_xf;
-        Fi.bt = bt.data(); Fi.umax = umax.data(); Fi.umin = umin.data(); Fi.umid = umid.data(); Fi.xmid = xmid.data(); Fi.R2 = R2.data(); Fi.rl = rl.data();
-        Fi.a1 = a1.data(); Fi.a2 = a2.data(); Fi.m1 = m1.data(); Fi.m2 = m2.data(); Fi.xf = xf.data(); Fi.J = J.data(); Fi.nuc = nuc.data(); Fi.k = k;
+        Fi.M = &HM; Fi.J = J.data(); Fi.nuc = nuc.data(); Fi.k = k;
         FmpcFirstOut Fo;
         fmpc_host_build_first_move(Fi, Fo);
         if (Fo.nc != nc || Fo.K0t.size() != (size_t)nc * m || Fo.u0c.size() != (size_t)m || Fo.E.size() != (size_t)nc * nc || Fo.Ep.size() != (size_t)nc * nc ||

@@ -61,11 +61,12 @@ int main(int argc, char** argv) {
     }
     for (int r = 0; r < n; ++r) { Q2[r] = 2.0 * (1.0 + 0.5 * U01(rng)); Qf2[r] = 50.0 * Q2[r]; ql[r] = 0.1 * N01(rng); qfl[r] = 0.1 * N01(rng); xmid[r] = 0.01 * N01(rng); xf[r] = 0.1 * N01(rng); }
 
+    FmpcHostModel HM;
+    HM.n = n; HM.m = m; HM.T = T; HM.nb = nb; HM.var2 = var2 ? 1 : 0; HM.has_xf = has_xf;
+    HM.bt = bt; HM.a1 = a1; HM.a2 = a2; HM.umax = umax; HM.umin = umin; HM.umid = umid; HM.xmid = xmid;
+    HM.R2 = R2; HM.rl = rl; HM.Q2 = Q2; HM.Qf2 = Qf2; HM.ql = ql; HM.qfl = qfl; if (has_xf) HM.xf = xf;
     FmpcRampColdIn In;
-    In.n = n; In.m = m; In.T = T; In.nb = nb; In.var2 = var2 ? 1 : 0; In.has_xf = has_xf;
-    In.bt = bt.data(); In.a1 = a1.data(); In.a2 = a2.data(); In.umax = umax.data(); In.umin = umin.data(); In.umid = umid.data(); In.xmid = xmid.data();
-    In.R2 = R2.data(); In.rl = rl.data(); In.Q2 = Q2.data(); In.Qf2 = Qf2.data(); In.ql = ql.data(); In.qfl = qfl.data(); In.xf = xf.data();
-    In.dumin = dumin.data(); In.dumax = dumax.data(); In.k = k;
+    In.M = &HM; In.dumin = dumin.data(); In.dumax = dumax.data(); In.k = k;
     FmpcRampColdOut O;
     fmpc_host_build_ramp_cold(In, O);
     if (!O.valid) return fail("builder reports invalid");

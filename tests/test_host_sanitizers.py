@@ -56,6 +56,25 @@ def test_api_host_math_under_asan_ubsan(tmp_path):
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
 
 
+def test_host_model_under_asan_ubsan(tmp_path):
+    """The host model of a handle (tests/host_san/model_build_test.cpp): fmpc_host_build_model on an integer-valued model (n = 3,
+    m = 2, T = 4, VAR(1) and VAR(2), with and without xf and linear terms) -- transposes, doubled weights, midpoints, zeros for NULL
+    q / r / qf, M1 / M2 against their recurrence, the presence pattern of the Y blocks, all by ==; fmpc_host_model_classify and
+    the build refuse what fmpc_create refuses with FMPC_E_NOT_PD_PHI; fmpc_host_wave_cold at n = 27, m = 5 fills its layout with
+    finite values and exactly symmetric G, Ma, Ma2."""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    out = str(tmp_path / "model_build_test")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+           "-Wall", "-Wextra", os.path.join(ROOT, "tests", "host_san", "model_build_test.cpp"), os.path.join(CSRC, "fmpc_host.cpp"), "-o", out]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([out], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
+
+
 @pytest.fixture(scope="module")
 def ramp_cold_binary(tmp_path_factory):
     if shutil.which("g++") is None:
