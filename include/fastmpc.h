@@ -1327,6 +1327,73 @@ int fmpc_sci_summary_device(fmpc_sci cam, int batch, const double* image, int fr
 int fmpc_sci_tables_host(int len, int d, double sampling, const double* pupil, double scale, double* F_re, double* F_im,
                          int* qrange, double* sums);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Shack-Hartmann sensor on the device: the spots of a lenslet array behind a batch of screens, their centres of gravity and a
+ * modal estimate.  What a wavefront sensor would have measured on the residual screen the sensorless estimator sees: OOMAO's
+ * lensletArray.propagateThrough (even branch) and shackHartmann.setValidLenslet / dataProcessing (centroiding branch).
+ *
+ * Geometry.  A screen is len x len, column-major, radians; npl in {16, 32} pixels per lenslet, len = nL npl; lenslet (i, j) covers
+ *   rows i npl .. and columns j npl ..; the amplitude is a real len x len array >= 0.  pad in {1, 2, 3, 4} is the spot sampling:
+ *   nOut = pad npl (OOMAO's nyquistSampling = 1 is pad = 2).  The spot window is s x s, s even, 2 <= s <= min(32, nOut) (OOMAO's
+ *   default field stop is s = npl).
+ * Spot.  With E = amplitude exp(i phi) on the lenslet's pixels, kappa_a = a - (s - 1) / 2 and F[x, a] = exp(-2 pi i x kappa_a / nOut):
+ *       I = scale |F' E F|^2 / nOut^2          indexed [row frequency, column frequency]
+ *   (F' the plain transpose): val / nOutWavePx, the half-pixel phasor of setPhasor, the zero-padded FFT and the crop about
+ *   centerIndex, as one partial DFT.  The spot is centred between pixels.  |.|^2 = fma(Im, Im, fl(Re Re)), then x fl(scale / nOut^2).
+ * Frame.  (nL s)^2 doubles per screen, column-major, lenslet (i, j) at rows i s .. and columns j s ..; lenslets without light
+ *   (no pixel with amplitude > 0) are zeros and do no work.
+ * Valid lenslets.  mean(amplitude^2) over the lenslet >= min_light_ratio; the valid list is in the column-major order of the
+ *   nL x nL grid (validLenslet(:)).  fmpc_sh_create takes the caller's own mask instead (nL^2 bytes, column-major, non-zero: valid).
+ * Slopes, per valid lenslet:  b = the spot;  with a threshold b <- max(b - t, 0), t = floor (mode 1) or max(floor, frac max(b))
+ *   (mode 2, the two-element framePixelThreshold);  x = sum b col / sum b, y = sum b row / sum b with col, row = 0 .. s - 1;
+ *   slopes = ([x; y] - reference) slopes_units: all x first, then all y (2 nvalid doubles per screen).  A lenslet with
+ *   sum b <= 0 gives 0 for both entries and is counted in dark[screen] (OOMAO keeps its previous slopes there; this library
+ *   holds no such state).  The three sums are taken in a fixed order; there are no atomics.
+ * Modal estimate.  coef = R slopes, R nmode x 2 nvalid column-major, nmode <= 128, nmode doubles per screen.
+ * Bad input.  A pixel in the light (amplitude != 0) that is not finite or has |phi| >= 1e6 makes that screen's frame, slopes and
+ *   coef NaN, its dark count -1, and leaves the other screens alone (the rule of fmpc_est_apply_device); pixels without light
+ *   never enter any arithmetic.  A frame value that is not finite inside a valid lenslet does the same to fmpc_sh_slopes_device.
+ *
+ * fmpc_sh_valid_host   host only, no device: valid (nL^2 bytes, column-major) and / or *nvalid.
+ * fmpc_sh_create       amplitude: HOST array; valid: HOST mask or NULL (from min_light_ratio); scale > 0.  The handle owns the
+ *                      operands and a fixed scratch area (at most 32 MiB); a sensor without a valid lenslet is FMPC_E_DIM.
+ * fmpc_sh_dims         any pointer may be NULL; nmode = 0 without a reconstructor.
+ * fmpc_sh_set_threshold   host state, read by the next measuring call: mode 0 none, 1 floor, 2 floor and fraction.
+ * fmpc_sh_set_reference_device   ref: DEVICE array of 2 nvalid doubles in pixels (NULL: zeros), copied on the stream.
+ * fmpc_sh_set_reconstructor_device   R: DEVICE array (NULL: none), copied on the stream; may allocate.
+ * fmpc_sh_measure_device   device pointers only.  scrn: batch x len x len.  Any of frame, slopes, coef, dark may be NULL (not
+ *                      all).  Without a frame a spot never leaves registers.
+ * fmpc_sh_slopes_device    the slopes, coef and dark of stored frames, ld doubles apart (0: (nL s)^2): the same device function
+ *                      for threshold and centroid as the fused path, so measure(frame) followed by this call gives the bits of
+ *                      measure(slopes); with fmpc_detector_read_device on the frame in between, a noisy sensor.
+ * The measuring calls do not allocate, synchronise or read back: they can be recorded into a HIP graph.  A handle's calls belong
+ * on one stream at a time (they share its scratch area).  A screen's bits do not depend on the batch, on its place in it or on
+ * which outputs are asked for.
+ * Answered before the device is touched: FMPC_E_NULL for a NULL out, amplitude, handle, scrn or frame, for fmpc_sh_valid_host
+ * without an output and for a measuring call without one; FMPC_E_DIM for len, npl, pad or s below 1, a scale that is not finite
+ * and positive, a min_light_ratio that is not finite, a negative or non-finite amplitude, a mask without a valid lenslet,
+ * batch < 0, 0 < ld < (nL s)^2 or ld < 0, a threshold mode outside {0, 1, 2}, a negative or non-finite floor or frac, a
+ * slopes_units that is not finite, nmode < 1; FMPC_E_UNSUPPORTED for npl outside {16, 32}, a len that is no multiple of npl or
+ * above 8192, pad > 4, s odd or above min(32, nOut), nmode > 128, and for coef != NULL without a reconstructor.  batch == 0 is
+ * FMPC_OK.
+ */
+#define FMPC_SH_THRESHOLD_NONE      0
+#define FMPC_SH_THRESHOLD_FLOOR     1
+#define FMPC_SH_THRESHOLD_FRACTION  2
+typedef struct fmpc_sh_s* fmpc_sh;
+int fmpc_sh_valid_host(int len, int npl, const double* amplitude, double min_light_ratio, unsigned char* valid, int* nvalid);
+int fmpc_sh_create(fmpc_sh* out, int len, int npl, int pad, int s, const double* amplitude, const unsigned char* valid,
+                   double min_light_ratio, double scale, int device);
+int fmpc_sh_destroy(fmpc_sh sh);
+int fmpc_sh_dims(fmpc_sh sh, int* len, int* nL, int* npl, int* pad, int* s, int* nvalid, int* nmode);
+int fmpc_sh_set_threshold(fmpc_sh sh, int mode, double floor, double frac);
+int fmpc_sh_set_reference_device(fmpc_sh sh, const double* ref, double slopes_units, void* stream);
+int fmpc_sh_set_reconstructor_device(fmpc_sh sh, int nmode, const double* R, void* stream);
+int fmpc_sh_measure_device(fmpc_sh sh, int batch, const double* scrn, double* frame, double* slopes, double* coef, int* dark,
+                           void* stream);
+int fmpc_sh_slopes_device(fmpc_sh sh, int batch, const double* frame, long long ld, double* slopes, double* coef, int* dark,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,8 @@ from .optics import zernike_modes, zernike_basis, zernike_grid, EstimatorOptics,
 from . import science
 from .science import (ScienceCamera, sci_tables_host, FMPC_SCI_FIELDS, FMPC_SCI_MEAN, FMPC_SCI_RMS, FMPC_SCI_STREHL, FMPC_SCI_MARECHAL,
                       FMPC_SCI_MIN, FMPC_SCI_MAX, FMPC_SCI_FIELD_NAMES, FMPC_SCI_FORM_STANDARD, FMPC_SCI_FORM_FEW)
+from . import shwfs
+from .shwfs import ShackHartmann, sh_valid_host, FMPC_SH_THRESHOLD_NONE, FMPC_SH_THRESHOLD_FLOOR, FMPC_SH_THRESHOLD_FRACTION
 from . import _lib
 
 __all__ = ["optics", "zernike_modes", "zernike_basis", "zernike_grid", "EstimatorOptics", "reference_optics","FastMPCHandle", "Fast_MPC2", "Fast_MPC2_VAR1", "deinterleave", "FastMPCError",
@@ -35,4 +37,5 @@ __all__ = ["optics", "zernike_modes", "zernike_basis", "zernike_grid", "Estimato
            "EstimatorNoise", "normal_noise", "normal_noise_host", "DetectorNoise", "detector_read", "detector_read_host", "GaussianDM", "dm_matrix_workspace_bytes", "reference_dm_geometry",
            "reference_dm", "science", "ScienceCamera", "sci_tables_host", "reference_pupil", "reference_science_camera", "FMPC_SCI_FIELDS", "FMPC_SCI_MEAN",
            "FMPC_SCI_RMS", "FMPC_SCI_STREHL", "FMPC_SCI_MARECHAL", "FMPC_SCI_MIN", "FMPC_SCI_MAX", "FMPC_SCI_FIELD_NAMES", "FMPC_SCI_FORM_STANDARD",
-           "FMPC_SCI_FORM_FEW", "Atmosphere", "reference_atmosphere", "atm_covariance", "atm_extruder", "atm_displacement", "atm_default_stencil"]
+           "FMPC_SCI_FORM_FEW", "Atmosphere", "reference_atmosphere", "atm_covariance", "atm_extruder", "atm_displacement", "atm_default_stencil",
+           "shwfs", "ShackHartmann", "sh_valid_host", "FMPC_SH_THRESHOLD_NONE", "FMPC_SH_THRESHOLD_FLOOR", "FMPC_SH_THRESHOLD_FRACTION"]

@@ -176,6 +176,15 @@ SIGNATURES = {
     "fmpc_sci_last_form": (C.c_int, [_vp]),
     "fmpc_sci_summary_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
     "fmpc_sci_tables_host": (C.c_int, [C.c_int, C.c_int, C.c_double, _vp, C.c_double, _vp, _vp, _vp, _vp]),
+    "fmpc_sh_valid_host": (C.c_int, [C.c_int, C.c_int, _vp, C.c_double, _vp, _ip]),
+    "fmpc_sh_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_int]),
+    "fmpc_sh_destroy": (C.c_int, [_vp]),
+    "fmpc_sh_dims": (C.c_int, [_vp] + [_ip] * 7),
+    "fmpc_sh_set_threshold": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double]),
+    "fmpc_sh_set_reference_device": (C.c_int, [_vp, _vp, C.c_double, _vp]),
+    "fmpc_sh_set_reconstructor_device": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "fmpc_sh_measure_device": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fmpc_sh_slopes_device": (C.c_int, [_vp, C.c_int, _vp, C.c_longlong, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -193,9 +193,14 @@ class AOLoop:
     the modal one; nothing else changes.
     science (optional): a `ScienceCamera` on the estimator's grid; every step exposes the residual screen it has just formed
     (`scrn`, column-major, no copy): `science_quality` (batch, FMPC_SCI_FIELDS) holds this step's rows, `science_image` (batch, d, d)
-    the exposure accumulated over `science_frames` steps since the last `science_reset()`; nothing else changes."""
+    the exposure accumulated over `science_frames` steps since the last `science_reset()`; nothing else changes.
+    sensor (optional): a calibrated `ShackHartmann` on the estimator's grid with the handle's n modes; x0 of a step is then
+    `sensor.coefficients(scrn)` instead of the estimator's ad_est, and `noise` of `step` may be None or a `DetectorNoise`, which is
+    applied to the sensor's frame (measure the frame, `detector_read` on it, slopes and coefficients from what was read) with
+    `steps_done` as its step; nothing else changes."""
 
-    def __init__(self, handle, estimator, Z, batch, n_newton=1, k=1e-2, one_call=True, modal=None, z_colmajor=False, science=None, dm=None):
+    def __init__(self, handle, estimator, Z, batch, n_newton=1, k=1e-2, one_call=True, modal=None, z_colmajor=False, science=None, sensor=None,
+                 dm=None):
         import ctypes as C
         import numpy as np
         import torch
@@ -237,6 +242,12 @@ class AOLoop:
             self.science_quality = torch.zeros((batch, FMPC_SCI_FIELDS), **f64)
             self.science_frames = 0
             self._science_ws = torch.empty(science.workspace_bytes(batch), dtype=torch.uint8, device=dev)
+        if sensor is not None and (sensor.len != estimator.len or sensor.nmode != n):
+            raise ValueError("sensor: need a ShackHartmann on the estimator's len x len grid, calibrated for the handle's n modes")
+        self.sensor = sensor
+        if sensor is not None:
+            self._sensor_frame = torch.empty((batch, sensor.frame_len, sensor.frame_len), **f64)
+            self._sensor_slopes = torch.empty((batch, 2 * sensor.nvalid), **f64)
 
     def science_reset(self):
         """Start a new exposure: the accumulated image and the frame count go back to zero (after the uncorrected first step, say)."""
@@ -291,7 +302,18 @@ class AOLoop:
         self.x0, self.x0_pre = self._xb[s % 2], self._xb[(s + 1) % 2]
         if s == 0:
             self.x0_pre.zero_()
-        self.est.apply_device(self.scrn, noise, colmajor=True, out=self.x0, step=s)
+        if self.sensor is None:
+            self.est.apply_device(self.scrn, noise, colmajor=True, out=self.x0, step=s)
+        elif noise is None:                  # what a wavefront sensor measures on the same residual screen
+            self.sensor.coefficients(self.scrn, out=self.x0, colmajor=True)
+        else:
+            from .estimator import DetectorNoise, detector_read
+            if not isinstance(noise, DetectorNoise):
+                raise TypeError("step: with sensor= the noise is None or a DetectorNoise")
+            self.sensor.measure(self.scrn, want_coef=False, want_slopes=False, colmajor=True, out=dict(frame=self._sensor_frame))
+            fr = self._sensor_frame.view(self.batch, -1)
+            detector_read(fr, noise, step=s, out=fr)
+            self.sensor.slopes_from_frame(fr, out=dict(slopes=self._sensor_slopes, coef=self.x0))
         # b_ref = -M1 B u[k-1] - M2 B u[k-2] (README.md:490-497) and the fastMPC step on (x0, x0_pre, b_ref) in one call
         if self.one_call:
             rc = self.h._lib.fmpc_ao_step_device(self.h._h, self.batch, vp(self.x0), vp(self.x0_pre), vp(u1) if s >= 1 else None, vp(u2) if s >= 2 else None,

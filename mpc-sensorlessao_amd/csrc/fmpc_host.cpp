@@ -1783,3 +1783,70 @@ extern "C" int fmpc_sci_tables_host(int len, int d, double sampling, const doubl
     if (sums) { sums[0] = t.sumA; sums[1] = t.sumA2; sums[2] = t.I0; }
     return FMPC_OK;
 }
+
+// ---- Shack-Hartmann sensor
+int fmpc_host_sh_check(int len, int npl, int pad, int s) {
+    if (len < 1 || npl < 1 || pad < 1 || s < 1) return FMPC_E_DIM;
+    if (npl != 16 && npl != 32) return FMPC_E_UNSUPPORTED;
+    if (len % npl != 0 || len > FMPC_SH_MAXLEN || pad > 4) return FMPC_E_UNSUPPORTED;
+    const int nout = pad * npl;
+    if (s % 2 != 0 || s > 32 || s > nout) return FMPC_E_UNSUPPORTED;
+    return FMPC_OK;
+}
+
+int fmpc_host_sh_amplitude_check(int len, const double* amplitude) {
+    const size_t npx = (size_t)len * len;
+    for (size_t i = 0; i < npx; ++i)
+        if (!std::isfinite(amplitude[i]) || amplitude[i] < 0.0) return FMPC_E_DIM;
+    return FMPC_OK;
+}
+
+void fmpc_host_sh_lit(int len, int npl, const double* amplitude, std::vector<unsigned char>& lit) {
+    const int nL = len / npl;
+    lit.assign((size_t)nL * nL, 0);
+    for (int x = 0; x < len; ++x)
+        for (int y = 0; y < len; ++y)
+            if (amplitude[(size_t)x * len + y] > 0.0) lit[(size_t)(y / npl) + (size_t)nL * (x / npl)] = 1;
+}
+
+void fmpc_host_sh_factors(int npl, int pad, int s, std::vector<double>& Fimg) {
+    typedef long double ld;
+    const ld pi = 3.141592653589793238462643383279503L;
+    const int nt = s > 16 ? 2 : 1, nout = pad * npl, M = 2 * nout;
+    Fimg.assign((size_t)(npl / 4) * nt * 2 * 64, 0.0);
+    for (int x = 0; x < npl; ++x)
+        for (int a = 0; a < s; ++a) {
+            // x (a - (s - 1) / 2) / nOut turns = x (2 a - s + 1) / (2 nOut): reduced in integers before it meets pi
+            const int n = ((x * (2 * a - s + 1)) % M + M) % M;
+            const ld ang = -pi * (ld)n / (ld)nout;
+            const size_t base = (((size_t)(x / 4) * nt + (a / 16)) * 2) * 64 + (size_t)(x % 4) * 16 + (a % 16);
+            Fimg[base] = (double)cosl(ang);
+            Fimg[base + 64] = (double)sinl(ang);
+        }
+}
+
+extern "C" int fmpc_sh_valid_host(int len, int npl, const double* amplitude, double min_light_ratio, unsigned char* valid, int* nvalid) {
+    typedef long double ld;
+    if (!amplitude || (!valid && !nvalid)) return FMPC_E_NULL;
+    int rc = fmpc_host_sh_check(len, npl, 1, 2);                          // (the size rules of len and npl alone)
+    if (rc != FMPC_OK) return rc;
+    if (!std::isfinite(min_light_ratio)) return FMPC_E_DIM;
+    rc = fmpc_host_sh_amplitude_check(len, amplitude);
+    if (rc != FMPC_OK) return rc;
+    const int nL = len / npl;
+    int count = 0;
+    for (int j = 0; j < nL; ++j)
+        for (int i = 0; i < nL; ++i) {
+            ld sum = 0.0L;
+            for (int x = 0; x < npl; ++x)
+                for (int y = 0; y < npl; ++y) {
+                    const ld a = (ld)amplitude[(size_t)(j * npl + x) * len + (size_t)(i * npl + y)];
+                    sum += a * a;
+                }
+            const bool ok = (double)(sum / (ld)(npl * npl)) >= min_light_ratio;
+            if (valid) valid[(size_t)i + (size_t)nL * j] = ok ? 1 : 0;
+            count += ok ? 1 : 0;
+        }
+    if (nvalid) *nvalid = count;
+    return FMPC_OK;
+}

@@ -306,6 +306,19 @@ int fmpc_host_sci_check(int len, int d, double sampling, double scale);
 struct FmpcSciTables { std::vector<double> Fimg; std::vector<int> qr; double sumA = 0.0, sumA2 = 0.0, I0 = 0.0; };
 int fmpc_host_sci_tables(int len, int d, double sampling, const double* pupil, double scale, FmpcSciTables& out);
 
+// ---- Shack-Hartmann sensor (include/fastmpc.h: fmpc_sh; layouts: fmpc_shwfs.h)
+#define FMPC_SH_MAXLEN 8192
+// The argument rules of a sensor's geometry: FMPC_E_DIM for len < 1, npl < 1, pad < 1, s < 1; FMPC_E_UNSUPPORTED for npl outside
+// {16, 32}, a len that is no multiple of npl or beyond FMPC_SH_MAXLEN, pad > 4, s odd or beyond min(32, pad npl).
+int fmpc_host_sh_check(int len, int npl, int pad, int s);
+// FMPC_E_DIM for a negative or non-finite amplitude (len x len), else FMPC_OK.
+int fmpc_host_sh_amplitude_check(int len, const double* amplitude);
+// The lenslets (column-major over the nL x nL grid) with a pixel of amplitude > 0.
+void fmpc_host_sh_lit(int len, int npl, const double* amplitude, std::vector<unsigned char>& lit);
+// F[x][a] = exp(-2 pi i x (a - (s - 1) / 2) / (pad npl)), x < npl, a < s, in long double with the turn count reduced in integers, as
+// operand images [npl / 4][NT][re, im][64 lanes], NT = 1 (s <= 16) or 2, lane = 16 (x mod 4) + (a mod 16), zero for a >= s.
+void fmpc_host_sh_factors(int npl, int pad, int s, std::vector<double>& Fimg);
+
 // ---- Zernike functions (zernfun.m, zernmodfit.m)
 #define FMPC_ZERNIKE_MAXN 14           // radial orders whose coefficients are exact in a double (14! < 2^53)
 #define FMPC_ZERNIKE_NCOEF 204          // coefficients of every radial polynomial R_n^|m| with n <= 14
