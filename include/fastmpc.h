@@ -1172,6 +1172,90 @@ int fmpc_dm_surface_device(int batch, int m, int rows, int cols, const double* x
                            const double* u, long long ldu, const double* phase, long long ldp,
                            double* out, long long ldo, void* stream);
 
+/*
+ * Deformable mirror of spline actuators on the device: the influence function OOMAO's deformableMirror is built on
+ * (influenceFunction.m:96-118 the curve, influenceFunction.m:253-362 the maps), used separably as there:
+ *     I_t(r, c) = fy_t[r] * fx_t[c],   fx_t[c] = f((x[c] - cx_t) / pitch),   fy_t[r] = f((y[r] - cy_t) / pitch)
+ * with pixel (r, c) at r + rows * c and x (cols), y (rows), cx, cy (m) DEVICE arrays as for the Gaussian mirror above.  The
+ * profile f is a piecewise cubic in pitch units: `pieces` pieces (1 .. 4096), strictly ascending breaks[0 .. pieces],
+ *     f(d) = sum_k coef[4 i + k] (d - breaks[i])^k   for breaks[i] <= d < breaks[i + 1]   (the last piece closed on the right),
+ *     f(d) = 0 exactly for d < breaks[0] or d > breaks[pieces]     (influenceFunction.m:274: u >= -bezier(end,1) & u <= bezier(end,1))
+ * It need not be symmetric.  Each factor is evaluated once in double (bisection over the breaks, three fused Horner steps) and
+ * every pixel is the product of two table entries: a pixel of a map, of the operand of B and of a term of the surface is the
+ * same number.
+ *
+ * fmpc_dm_profile_oomao_host   host only: OOMAO's curve (influenceFunction.m:96-118) as such a profile.  Control points P1 = (0, 1),
+ *                   P2 = (p2x, 1), P3, P4, P5 = -P3 / ratio + (1 + 1 / ratio) P4, P6 = (p6x, 0), P7 = (2, 0); the cubic Bezier
+ *                   segments (P1..P4) and (P4..P7) at t = 0, 0.01, .., 1 (the second without t = 0): 201 points (bx, by); xScale =
+ *                   the not-a-knot spline through (by -> bx) at `mech`, bx /= xScale; the not-a-knot spline through the mirrored
+ *                   points: 401 knots, *pieces = 400, support [-bx[end], bx[end]].  cap: the pieces breaks (cap + 1 doubles) and
+ *                   coef (4 cap doubles) hold.  OOMAO's 'monotonic' is (0.2, (0.4, 0.7), (0.6, 0.4), 1, 1).  FMPC_E_DIM when by is
+ *                   not strictly monotone (the y -> x spline is then undefined: 'overshoot' is such a curve; pass pp arrays of
+ *                   your own), when mech is outside (0, 1), when cap < 400, when an argument is not finite or ratio is 0.
+ * fmpc_dm_profile_eval_host    host only: out[i] = f(d[i]), i < count, by the code the device runs: the same bits.  FMPC_E_DIM for
+ *                   pieces outside [1, 4096], breaks that do not ascend strictly, a coefficient that is not finite.
+ * fmpc_dm_spline_prepare_device   writes the PREPARED MIRROR into the caller's workspace ws (fmpc_dm_spline_workspace_bytes(m, rows,
+ *                   cols) bytes, 8-byte aligned; 0 for refused sizes); breaks and coef are DEVICE arrays and are not kept.  It holds
+ *                   the factor tables actuator-minor (the layout of the Gaussian matrix call), the same pixel-minor with the axes
+ *                   padded to whole tiles, and per FMPC_DM_TILE x FMPC_DM_TILE tile of pixels (tile (tr, tc) at tr + ntr * tc) the
+ *                   count and the ascending list of the actuators for which SOME column of the tile and SOME row of the tile lie
+ *                   inside the support -- pixels are tested, not intervals: x and y need not be monotone.  Every byte is written
+ *                   and nothing depends on timing: two calls leave the same bytes.  Call it again after the centres change.
+ *                   The breaks are not checked on the device: they must ascend strictly (fmpc_dm_profile_eval_host checks).
+ * fmpc_dm_spline_influence_device   the maps of actuators first .. first + count - 1 from the prepared tables, ldi >= rows * cols
+ *                   doubles apart.
+ * fmpc_dm_spline_matrix_device      B = pinv(Zs'Zs) Zs' I as fmpc_dm_matrix_device: the same product and finish kernels on the
+ *                   prepared tables, the same panels and passes, the same result layout, n <= 128.  ws2 holds the partial sums
+ *                   only: at least one panel (16 * n_pad doubles per four chunks of the modal fit's pixel axis);
+ *                   fmpc_dm_spline_matrix_workspace_bytes is the recommended size (every panel up to 16 MiB; 0 for refused
+ *                   sizes).  The bits of B do not depend on the workspace size.  A non-finite R gives NaN.
+ * fmpc_dm_spline_surface_device     out[b] = phase[b] + sum_t u[b][t] I_t, arguments as fmpc_dm_surface_device.  The tile mapping
+ *                   and matrix-core layout of the Gaussian kernel; a stage is 16 actuators of the TILE'S LIST, their slices read
+ *                   from the pixel-minor table (no transcendental in the loop), a ragged last stage zero-filled: the work per
+ *                   pixel follows the support, not m.  flags & FMPC_DM_DENSE walks all m actuators instead (for A / B timing
+ *                   and tests); any other bit is refused.  A tile with an empty list writes phase (or zeros).  Contract: the sum
+ *                   runs in ascending actuator order over the tile's list; a screen's bits do not depend on the batch size, on
+ *                   its place in the batch or on the screens a workgroup takes together; a NaN u[b][t] makes NaN exactly the
+ *                   pixels of screen b in the tiles on actuator t's list, with FMPC_DM_DENSE every pixel (an infinite one makes
+ *                   them NaN or infinite); u of an actuator off a tile's list is not read for that tile.
+ * Limits: one profile per mirror, the same along both axes; one pitch; no mirror per realisation; no bank, sharded or MATLAB
+ * forms; 'overshoot' only through pp arrays of the caller.
+ * No device entry takes a handle, allocates, synchronises or reads back; all can be recorded into a HIP graph.
+ * Measured on one MI355X (scripts/dm_spline_timing.py, profiles/dm_spline_timing.json; 512 x 512, medians of 30 windows, five
+ * rounds alternating, spread <= 2.4 % for one screen and <= 0.8 % from 256 on).  The reference's 12 x 12 actuators (pitch 61.5 px)
+ * at coupling 0.1, 25 actuators on every tile's list, 0.22 of the dense matrix instructions: 1 / 256 / 2000 screens in 0.0110 /
+ * 0.216 / 1.615 ms against 0.0194 / 0.419 / 3.136 ms for fmpc_dm_surface_device with the same centres (1.76 / 1.94 / 1.94 x) and
+ * 0.0135 / 0.397 / 2.98 ms for its own FMPC_DM_DENSE walk; 0.82 of the HBM roofline on one read and one write per pixel at 2000:
+ * it is memory-bound now (the matrix instructions alone would take 0.26 of the time).  At coupling 0.3 (36 - 49 per tile, 0.40):
+ * 0.0159 / 0.250 / 1.791 ms (1.22 / 1.69 / 1.76 x the Gaussian call).  32 x 32 actuators on the same grid (pitch 21.8 px, 49
+ * per tile): 0.0157 / 0.247 / 1.793 ms, 1.43 / 1.14 / 1.11 x the 12 x 12 mirror's time with twice its stages, against 0.115 / 2.63 /
+ * 20.1 ms for the Gaussian call at m = 1024.  fmpc_dm_spline_prepare_device: 0.060 ms (m = 144), 0.271 ms (m = 1024).
+ * fmpc_dm_spline_matrix_device: 0.096 / 0.092 ms (coupling 0.1 / 0.3) against 0.095 ms for fmpc_dm_matrix_device, which makes its
+ * tables in the call: the same product and finish kernels, no gain.
+ * Answered before the device is touched: FMPC_E_NULL for a NULL x, y, cx, cy, breaks, coef, ws, I, Z, R, B, ws2, u or out;
+ * FMPC_E_DIM for m, rows, cols, count or batch < 1, a pitch that is not positive and finite, pieces outside [1, 4096], a ws below
+ * fmpc_dm_spline_workspace_bytes or not 8-byte aligned, first < 0, first + count > m, ldi, ldp (with a phase) or ldo < rows * cols,
+ * ldu < m, n < 1, rows * cols < n, skip outside [0, n), ldb < n - skip, a ws2 below one panel, an unknown flag bit;
+ * FMPC_E_UNSUPPORTED for n > 128, for (rows + cols) * 16 * ceil(m / 16) or tiles * (1 + 16 * ceil(m / 16)) beyond 2^31 - 1, and
+ * for rows * cols beyond 2^31 - 1 in the matrix call.
+ */
+#define FMPC_DM_TILE 64
+#define FMPC_DM_DENSE 1u
+int fmpc_dm_profile_oomao_host(double p2x, const double* p3, const double* p4, double ratio, double p6x, double mech, int cap,
+                               double* breaks, double* coef, int* pieces);
+int fmpc_dm_profile_eval_host(int pieces, const double* breaks, const double* coef, long long count, const double* d, double* out);
+size_t fmpc_dm_spline_workspace_bytes(int m, int rows, int cols);
+int fmpc_dm_spline_prepare_device(int m, int rows, int cols, const double* x, const double* y, const double* cx, const double* cy,
+                                  double pitch, int pieces, const double* breaks, const double* coef, void* ws, size_t ws_bytes,
+                                  void* stream);
+int fmpc_dm_spline_influence_device(int m, int rows, int cols, const void* ws, int first, int count, double* I, long long ldi,
+                                    void* stream);
+size_t fmpc_dm_spline_matrix_workspace_bytes(int n, int m, int rows, int cols);
+int fmpc_dm_spline_matrix_device(int n, int m, int rows, int cols, const double* Z, const double* R, const void* ws, int skip,
+                                 double* B, int ldb, void* ws2, size_t ws2_bytes, void* stream);
+int fmpc_dm_spline_surface_device(int batch, int m, int rows, int cols, const void* ws, const double* u, long long ldu,
+                                  const double* phase, long long ldp, double* out, long long ldo, unsigned flags, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------------
  * Atmosphere on the device: frozen-flow von Karman phase screens for a batch of realisations, the stage of the reference's
  * pipeline at README.md:24-75 (OOMAO's layered atmosphere seen by one on-axis source; altitudes do not enter).  OOMAO draws from

@@ -19,6 +19,8 @@ from .var_identify import identify_var2_device, identify_var_device, validate_va
 from .estimator import PhaseDiversityEstimator, EstimatorNoise, normal_noise, normal_noise_host, DetectorNoise, detector_read, detector_read_host
 from .modal import ModalFit, modal_workspace_bytes
 from .dm import GaussianDM, dm_matrix_workspace_bytes, reference_dm_geometry, reference_dm
+from .dm_spline import (DMProfile, SplineDM, oomao_profile, oomao_dm_geometry, oomao_dm, dm_spline_matrix_workspace_bytes, FMPC_DM_TILE,
+                        FMPC_DM_DENSE)
 from .atmosphere import Atmosphere, reference_atmosphere, atm_covariance, atm_extruder, atm_displacement, atm_default_stencil
 from . import optics
 from .optics import zernike_modes, zernike_basis, zernike_grid, EstimatorOptics, reference_optics, reference_pupil, reference_science_camera
@@ -38,4 +40,6 @@ __all__ = ["optics", "zernike_modes", "zernike_basis", "zernike_grid", "Estimato
            "reference_dm", "science", "ScienceCamera", "sci_tables_host", "reference_pupil", "reference_science_camera", "FMPC_SCI_FIELDS", "FMPC_SCI_MEAN",
            "FMPC_SCI_RMS", "FMPC_SCI_STREHL", "FMPC_SCI_MARECHAL", "FMPC_SCI_MIN", "FMPC_SCI_MAX", "FMPC_SCI_FIELD_NAMES", "FMPC_SCI_FORM_STANDARD",
            "FMPC_SCI_FORM_FEW", "Atmosphere", "reference_atmosphere", "atm_covariance", "atm_extruder", "atm_displacement", "atm_default_stencil",
-           "shwfs", "ShackHartmann", "sh_valid_host", "FMPC_SH_THRESHOLD_NONE", "FMPC_SH_THRESHOLD_FLOOR", "FMPC_SH_THRESHOLD_FRACTION"]
+           "shwfs", "ShackHartmann", "sh_valid_host", "FMPC_SH_THRESHOLD_NONE", "FMPC_SH_THRESHOLD_FLOOR", "FMPC_SH_THRESHOLD_FRACTION",
+           "DMProfile", "SplineDM", "oomao_profile", "oomao_dm_geometry", "oomao_dm", "dm_spline_matrix_workspace_bytes", "FMPC_DM_TILE",
+           "FMPC_DM_DENSE"]

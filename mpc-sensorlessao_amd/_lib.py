@@ -156,6 +156,14 @@ SIGNATURES = {
     "fmpc_dm_matrix_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "fmpc_dm_matrix_device": (C.c_int, [C.c_int] * 4 + [_vp] * 6 + [C.c_double] * 2 + [C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp]),
     "fmpc_dm_surface_device": (C.c_int, [C.c_int] * 4 + [_vp] * 4 + [C.c_double] * 2 + [_vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _vp]),
+    "fmpc_dm_profile_oomao_host": (C.c_int, [C.c_double, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _ip]),
+    "fmpc_dm_profile_eval_host": (C.c_int, [C.c_int, _vp, _vp, C.c_longlong, _vp, _vp]),
+    "fmpc_dm_spline_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "fmpc_dm_spline_prepare_device": (C.c_int, [C.c_int] * 3 + [_vp] * 4 + [C.c_double, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fmpc_dm_spline_influence_device": (C.c_int, [C.c_int] * 3 + [_vp, C.c_int, C.c_int, _vp, C.c_longlong, _vp]),
+    "fmpc_dm_spline_matrix_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "fmpc_dm_spline_matrix_device": (C.c_int, [C.c_int] * 4 + [_vp] * 3 + [C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp]),
+    "fmpc_dm_spline_surface_device": (C.c_int, [C.c_int] * 4 + [_vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, C.c_uint, _vp]),
     "fmpc_atm_covariance_host": (C.c_int, [C.c_int, _vp, C.c_double, C.c_double, _vp]),
     "fmpc_atm_extruder_host": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp]),
     "fmpc_atm_displacement_host": (C.c_int, [C.c_longlong, C.c_double, C.POINTER(C.c_longlong), _dp]),

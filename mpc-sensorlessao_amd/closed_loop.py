@@ -190,7 +190,7 @@ class AOLoop:
     `true_coefficients`, the reference's ad_acc_valid, and changes nothing else.
     dm (optional): a `GaussianDM` on the estimator's grid (rows = cols = len); the residual screen of a step is then
     phase_valid[k] + sum_t u[k-1]_t I_t, the surface the mirror of Gaussian actuators makes (`fmpc_dm_surface_device`), instead of
-    the modal one; nothing else changes.
+    the modal one; nothing else changes.  A `SplineDM` (dm_spline.py) has the same rows, cols, m and surface() and goes in alike.
     science (optional): a `ScienceCamera` on the estimator's grid; every step exposes the residual screen it has just formed
     (`scrn`, column-major, no copy): `science_quality` (batch, FMPC_SCI_FIELDS) holds this step's rows, `science_image` (batch, d, d)
     the exposure accumulated over `science_frames` steps since the last `science_reset()`; nothing else changes.

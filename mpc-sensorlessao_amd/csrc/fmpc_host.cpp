@@ -1850,3 +1850,119 @@ extern "C" int fmpc_sh_valid_host(int len, int npl, const double* amplitude, dou
     if (nvalid) *nvalid = count;
     return FMPC_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- spline mirror
+// MATLAB's spline(x, y) for n >= 4 ascending sites: the not-a-knot cubic through them, by its slopes.  The system is tridiagonal
+// (the two not-a-knot rows touch two unknowns each) and is solved by elimination without pivoting, in long double.
+static bool dmsp_slopes(const std::vector<long double>& x, const std::vector<long double>& y, std::vector<long double>& s) {
+    typedef long double ld;
+    const size_t n = x.size();
+    if (n < 4 || y.size() != n) return false;
+    std::vector<ld> h(n - 1), dl(n - 1), lo(n, 0.0L), di(n), up(n, 0.0L), b(n);
+    for (size_t i = 0; i + 1 < n; ++i) {
+        h[i] = x[i + 1] - x[i];
+        if (!(h[i] > 0.0L)) return false;
+        dl[i] = (y[i + 1] - y[i]) / h[i];
+    }
+    const ld d0 = x[2] - x[0], d1 = x[n - 1] - x[n - 3];
+    di[0] = h[1]; up[0] = d0;
+    b[0] = ((h[0] + 2.0L * d0) * h[1] * dl[0] + h[0] * h[0] * dl[1]) / d0;
+    for (size_t i = 1; i + 1 < n; ++i) {
+        lo[i] = h[i]; di[i] = 2.0L * (h[i - 1] + h[i]); up[i] = h[i - 1];
+        b[i] = 3.0L * (h[i] * dl[i - 1] + h[i - 1] * dl[i]);
+    }
+    lo[n - 1] = d1; di[n - 1] = h[n - 3];
+    b[n - 1] = (h[n - 2] * h[n - 2] * dl[n - 3] + (2.0L * d1 + h[n - 2]) * h[n - 3] * dl[n - 2]) / d1;
+    for (size_t i = 1; i < n; ++i) {
+        const ld w = lo[i] / di[i - 1];
+        di[i] -= w * up[i - 1];
+        b[i] -= w * b[i - 1];
+    }
+    s.assign(n, 0.0L);
+    s[n - 1] = b[n - 1] / di[n - 1];
+    for (size_t i = n - 1; i-- > 0;) s[i] = (b[i] - up[i] * s[i + 1]) / di[i];
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite((double)s[i])) return false;
+    return true;
+}
+
+// the four coefficients of piece i in powers of (x - x[i])
+static void dmsp_piece(const std::vector<long double>& x, const std::vector<long double>& y, const std::vector<long double>& s, size_t i,
+                       long double c[4]) {
+    const long double h = x[i + 1] - x[i], dl = (y[i + 1] - y[i]) / h;
+    c[0] = y[i]; c[1] = s[i];
+    c[2] = (3.0L * dl - 2.0L * s[i] - s[i + 1]) / h;
+    c[3] = (s[i] + s[i + 1] - 2.0L * dl) / (h * h);
+}
+
+extern "C" int fmpc_dm_profile_oomao_host(double p2x, const double* p3, const double* p4, double ratio, double p6x, double mech, int cap,
+                                          double* breaks, double* coef, int* pieces) {
+    typedef long double ld;
+    if (!p3 || !p4 || !breaks || !coef || !pieces) return FMPC_E_NULL;
+    const int NS = 101, NP = 2 * NS - 1, NK = 2 * NP - 1;                 // samples per segment, points of the half curve, knots
+    if (cap < NK - 1) return FMPC_E_DIM;
+    const double in[] = {p2x, p3[0], p3[1], p4[0], p4[1], ratio, p6x, mech};
+    for (double v : in)
+        if (!std::isfinite(v)) return FMPC_E_DIM;
+    if (!(mech > 0.0 && mech < 1.0) || ratio == 0.0) return FMPC_E_DIM;
+    ld P[7][2] = {{0.0L, 1.0L}, {p2x, 1.0L}, {p3[0], p3[1]}, {p4[0], p4[1]}, {0.0L, 0.0L}, {p6x, 0.0L}, {2.0L, 0.0L}};
+    for (int k = 0; k < 2; ++k) P[4][k] = -P[2][k] / (ld)ratio + (1.0L + 1.0L / (ld)ratio) * P[3][k];
+    // the two Bezier segments at t = 0, 1/100, .., 1 (the second without its t = 0), rounded to double as the reference holds them
+    std::vector<ld> bx(NP), by(NP);
+    for (int seg = 0; seg < 2; ++seg)
+        for (int j = seg; j < NS; ++j) {
+            const ld t = (ld)j / (ld)(NS - 1), q = 1.0L - t;
+            const ld w[4] = {q * q * q, 3.0L * q * q * t, 3.0L * q * t * t, t * t * t};
+            ld px = 0.0L, py = 0.0L;
+            for (int k = 0; k < 4; ++k) { px += w[k] * P[3 * seg + k][0]; py += w[k] * P[3 * seg + k][1]; }
+            const int at = seg * (NS - 1) + j;
+            bx[at] = (ld)(double)px; by[at] = (ld)(double)py;
+            if (!std::isfinite((double)px) || !std::isfinite((double)py)) return FMPC_E_DIM;
+        }
+    // x as a spline of y needs strictly monotone y
+    bool down = true, upw = true;
+    for (int i = 0; i + 1 < NP; ++i) { down = down && by[i + 1] < by[i]; upw = upw && by[i + 1] > by[i]; }
+    if (!down && !upw) return FMPC_E_DIM;
+    std::vector<ld> sy(by), sx(bx), s;
+    if (down) { std::reverse(sy.begin(), sy.end()); std::reverse(sx.begin(), sx.end()); }
+    if (!dmsp_slopes(sy, sx, s)) return FMPC_E_DIM;
+    if (!((ld)mech >= sy.front() && (ld)mech <= sy.back())) return FMPC_E_DIM;
+    size_t at = (size_t)(std::upper_bound(sy.begin(), sy.end(), (ld)mech) - sy.begin());
+    at = at == 0 ? 0 : at - 1;
+    if (at > sy.size() - 2) at = sy.size() - 2;
+    ld c[4];
+    dmsp_piece(sy, sx, s, at, c);
+    const ld tm = (ld)mech - sy[at];
+    const ld scale = ((c[3] * tm + c[2]) * tm + c[1]) * tm + c[0];
+    if (!std::isfinite((double)scale) || !(scale > 0.0L)) return FMPC_E_DIM;
+    // the mirrored knots, as doubles; the spline through them
+    std::vector<ld> u(NK), v(NK);
+    for (int i = 0; i < NP; ++i) {
+        const ld xs = (ld)(double)(bx[i] / scale);
+        u[NP - 1 + i] = xs; v[NP - 1 + i] = by[i];
+        u[NP - 1 - i] = -xs; v[NP - 1 - i] = by[i];
+    }
+    u[NP - 1] = 0.0L + bx[0] / scale;
+    if (!dmsp_slopes(u, v, s)) return FMPC_E_DIM;                          // (false as well when the knots do not ascend)
+    for (int i = 0; i < NK; ++i) breaks[i] = (double)u[i];
+    for (int i = 0; i + 1 < NK; ++i) {
+        dmsp_piece(u, v, s, (size_t)i, c);
+        for (int k = 0; k < 4; ++k) {
+            coef[4 * i + k] = (double)c[k];
+            if (!std::isfinite(coef[4 * i + k])) return FMPC_E_DIM;
+        }
+    }
+    *pieces = NK - 1;
+    return FMPC_OK;
+}
+
+extern "C" int fmpc_dm_profile_eval_host(int pieces, const double* breaks, const double* coef, long long count, const double* d, double* out) {
+    if (!breaks || !coef || !d || !out) return FMPC_E_NULL;
+    if (pieces < 1 || pieces > FMPC_DM_MAX_PIECES || count < 0) return FMPC_E_DIM;
+    for (int i = 0; i < pieces; ++i)
+        if (!(breaks[i] < breaks[i + 1])) return FMPC_E_DIM;
+    for (int i = 0; i < 4 * pieces; ++i)
+        if (!std::isfinite(coef[i])) return FMPC_E_DIM;
+    for (long long i = 0; i < count; ++i) out[i] = fmpc_dm_profile_eval(pieces, breaks, coef, d[i]);
+    return FMPC_OK;
+}

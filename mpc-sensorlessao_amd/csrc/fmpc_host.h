@@ -319,6 +319,12 @@ void fmpc_host_sh_lit(int len, int npl, const double* amplitude, std::vector<uns
 // operand images [npl / 4][NT][re, im][64 lanes], NT = 1 (s <= 16) or 2, lane = 16 (x mod 4) + (a mod 16), zero for a >= s.
 void fmpc_host_sh_factors(int npl, int pad, int s, std::vector<double>& Fimg);
 
+// ---- mirror of spline actuators (include/fastmpc.h: fmpc_dm_profile_oomao_host, fmpc_dm_profile_eval_host)
+// The profile is a piecewise cubic in pitch units; fmpc_dm_profile.h holds the one evaluation the host and the device share.
+// fmpc_dm_profile_oomao_host builds OOMAO's curve (influenceFunction.m:96-118) in long double: the Bezier samples rounded to double,
+// the y -> x not-a-knot spline for the scale, the mirrored knots rounded to double, the not-a-knot spline through them.
+#include "fmpc_dm_profile.h"
+
 // ---- Zernike functions (zernfun.m, zernmodfit.m)
 #define FMPC_ZERNIKE_MAXN 14           // radial orders whose coefficients are exact in a double (14! < 2^53)
 #define FMPC_ZERNIKE_NCOEF 204          // coefficients of every radial polynomial R_n^|m| with n <= 14
