@@ -1,5 +1,9 @@
-// C-ABI of the MI355X fastMPC solver (include/fastmpc.h): handle, host-side assembly of the
-// iteration-invariant blocks, launches.  No CPU solve path exists in this library.
+// C-ABI of the MI355X fastMPC solver (include/fastmpc.h), the dispatcher: fmpc_create in stages and fmpc_destroy, the stretch
+// bracket, the builders of the cold-start forms per (handle, k), the paths of a device solve (fmpc_path_*) and the choice between
+// them, the device solve entries, the small setters and queries.  No CPU solve path exists in this library.
+// The other entry points on a solver handle: fmpc_ramp_api.hip (ramp-rate rows), fmpc_loop_api.hip (closed loop),
+// fmpc_hostcall_api.hip (host pointers, fmpc_solve_once), fmpc_bank_api.hip, fmpc_records_api.hip, fmpc_kkt_api.hip; what they
+// share with this file is declared in fmpc_handle.h.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -30,32 +34,21 @@ std::atomic<unsigned long long> fmpc_alloc_gen{0};
 extern "C" unsigned long long fmpc_alloc_generation(void) { return fmpc_alloc_gen.load(); }
 
 
-// kernels / launchers (fmpc_kernel_generic.hip)
+// kernels / launchers (fmpc_kernel_generic.hip; fmpc_launch_unpack: fmpc_handle.h)
 size_t fmpc_generic_lds_bytes(int n, int m);
 size_t fmpc_generic_big_lds_bytes(int n, int m);
 hipError_t fmpc_generic_prepare(size_t lds_bytes, int big);
-// fmpc_kernel_ramp.hip (ws = 0: fmpc_newton_ramp, 1: fmpc_newton_ramp_ws)
-size_t fmpc_ramp_lds_bytes(int n, int m, int nb, int ws);
-size_t fmpc_ramp_ws_doubles(int n, int m, int T, int nb, int ws, int dense_r);
-hipError_t fmpc_ramp_prepare(int ws, size_t lds_bytes);
-hipError_t fmpc_launch_ramp(const FrParams& P, int grid, hipStream_t stream);
 hipError_t fmpc_launch_generic(const FmpcDevModel& M, int batch, int grid, const double* x0,
                                const double* x0p, const double* w, const double* zinit,
                                const double* nu0, int max_iter, double kbar, double* zout,
                                double* nuout, int* status, int* iters, double* step, int step_ld,
                                double* ws, size_t ws_stride, hipStream_t stream, int big);
-hipError_t fmpc_launch_unpack(int n, int m, int T, int batch, const double* z, double* U,
-                              double* X, double* u0, hipStream_t stream);
-hipError_t fmpc_launch_loop_inputs(int n, int m, int T, int batch, const double* Bt, const double* M1, const double* M2,
-                                   const double* a, const double* x0_last, const double* u1, const double* u2,
-                                   double* x0, double* x0_pre, double* w, hipStream_t stream, double* lv = nullptr);
 
-// one-wave-per-problem MFMA kernel (fmpc_kernel_wave.hip)
+// one-wave-per-problem MFMA kernel (fmpc_kernel_wave.hip; fmpc_wave_waves_per_wg: fmpc_handle.h)
 size_t fmpc_wave_lds_bytes(int n, int mp);
 bool fmpc_wave_supports(int n);
 int fmpc_wave_img_stride(int n);
 int fmpc_wave_mp(int m);
-int fmpc_wave_waves_per_wg();
 size_t fmpc_wave_ws_doubles(int n, int m, int mp, int T, int nb);
 void fmpc_wave_make_images(int n, const double* blk, double* out);
 hipError_t fmpc_wave_prepare(int n, size_t lds_bytes);
@@ -85,10 +78,6 @@ extern "C" const char* fmpc_strerror(int code) {
 
 extern "C" int fmpc_step_ld(int n_newton) { return n_newton > 0 ? n_newton : 1000; }
 
-// Environment switches: NAME=1 (first character `c`) switches on, a number is read with atoi (unset or empty: the default)
-static bool fmpc_env_on(const char* name, char c = '1') { const char* e = getenv(name); return e && e[0] == c; }
-static int fmpc_env_int(const char* name, int dflt) { const char* e = getenv(name); return e && e[0] ? atoi(e) : dflt; }
-
 // ---- fmpc_create in stages.  Every stage returns an FMPC code; fmpc_create destroys the handle when one fails.
 // Which kernels of the per-problem-factor path take the model: the generic kernel (n <= 64 and its tiles fit the LDS), else the
 // tiled kernel in fp64 (n <= 47), else the tiled kernel with an fp32 factor (n <= 79: "fp32 mixed precision", BASELINE configs[4])
@@ -115,7 +104,7 @@ static int fmpc_pick_paths(int n, int m, int nb, bool denseQ, bool denseR, FmpcP
 }
 
 static void fmpc_read_switches(fmpc_handle h) {
-    h->rc_disabled = fmpc_env_on("FMPC_NO_RAMP_COLD");
+    h->ramp.cold.disabled = fmpc_env_on("FMPC_NO_RAMP_COLD");
     if (fmpc_env_on("FMPC_FORCE_GENERIC")) h->prefer_tiled = 0;
     h->force_tiled = fmpc_env_on("FMPC_TILED");
     h->small_tiled = !fmpc_env_on("FMPC_NO_SMALL_TILED");
@@ -656,8 +645,8 @@ static int fmpc_stretch_flush(FmpcStretch& S, hipStream_t stream) {
 }
 
 static void fmpc_stretch_flush_handle_locked(fmpc_handle h, bool keep_one, hipStream_t keep);
-// A library call on `stream` that is no step of a chain: what is pending there comes first.
-static int fmpc_stretch_flush_stream(hipStream_t stream, fmpc_handle h = nullptr) {
+// A library call on `stream` that is no step of a chain: what is pending there comes first.  (fmpc_handle.h)
+int fmpc_stretch_flush_stream(hipStream_t stream, fmpc_handle h) {
     if (fmpc_st_open.load() == 0) return FMPC_OK;
     std::lock_guard<std::mutex> lk(fmpc_st_mu);
     if (h) fmpc_stretch_flush_handle_locked(h, true, stream);      // (chains of this handle on OTHER streams)
@@ -804,8 +793,8 @@ static void fmpc_panel_params(fmpc_handle h, double k, FpParams& Q) {
 
 // J and nuc of the dense form (fmpc_kernel_inv.hip) for barrier weight k: the panel kernel itself solves for the unit
 // vectors of d = [x0 ; x0_pre ; w] (scaled by 2^20: the constant part of the right-hand side then costs no digits), so
-// both forms of the dual solve rest on one factorisation.  Once per (handle, k), ~5 ms; synchronises the stream.
-static int fmpc_build_inverse(fmpc_handle h, double k, hipStream_t stream) {
+// both forms of the dual solve rest on one factorisation.  Once per (handle, k), ~5 ms; synchronises the stream.  (fmpc_handle.h)
+int fmpc_build_inverse(fmpc_handle h, double k, hipStream_t stream) {
     const int n = h->n, T = h->T, nb = h->nb, TN = T * n, nrow = nb * n;
     const int ncol = 2 * n + TN, np = 1 + ncol + 2 * n, npanels = (np + FP_NP - 1) / FP_NP;      // + w = -M1 e_j, -M2 e_j
     const double scale = FMPC_INV_SCALE;
@@ -860,8 +849,8 @@ static int fmpc_build_inverse(fmpc_handle h, double k, hipStream_t stream) {
     return FMPC_OK;
 }
 
-// Matrices of the first-move form for barrier weight k (fmpc_host_build_first_move), uploaded as one pool.
-static int fmpc_build_first_move(fmpc_handle h, double k, hipStream_t stream) {
+// Matrices of the first-move form for barrier weight k (fmpc_host_build_first_move), uploaded as one pool.  (fmpc_handle.h)
+int fmpc_build_first_move(fmpc_handle h, double k, hipStream_t stream) {
     h->fm_valid = 0;
     if (!h->hm_J4_valid || h->hm_J4_k != k) return FMPC_E_UNSUPPORTED;
     const int n = h->n, m = h->m, T = h->T, TN = T * n;
@@ -963,8 +952,8 @@ static int fmpc_build_first_move(fmpc_handle h, double k, hipStream_t stream) {
     return FMPC_OK;
 }
 
-// The wave kernel's workspace: one slot per resident wavefront of the whole chip.  Caller holds h->mu.
-static int fmpc_ensure_wave_ws(fmpc_handle h, size_t* stride_out, hipStream_t stream) {
+// The wave kernel's workspace: one slot per resident wavefront of the whole chip.  Caller holds h->mu.  (fmpc_handle.h)
+int fmpc_ensure_wave_ws(fmpc_handle h, size_t* stride_out, hipStream_t stream) {
     const int wpw = fmpc_wave_waves_per_wg();
     const size_t stride = fmpc_wave_ws_doubles(h->n, h->m, h->wave.mp, h->T, h->nb);
     const int rc = h->ws.grow(stride * (size_t)h->num_cu * wpw, stream);
@@ -997,15 +986,16 @@ static int fmpc_wave_grid(fmpc_handle h, int batch) {
 
 // The exact path in flag mode behind a kernel that has decided the step of every problem (the affine, first-move and loop
 // forms): from the cold start with the shared factor, it redoes the problems flagged in `need` and counts them in pn_cnt
-static int fmpc_launch_flagged(fmpc_handle h, const FmpcSolve& s, int grid, size_t stride, int* need, int* nflag = nullptr, int zld = 0) {
+// (fmpc_handle.h)
+int fmpc_launch_flagged(fmpc_handle h, const FmpcSolve& s, int grid, size_t stride, int* need, int* nflag, int zld) {
     FwParams P = fmpc_wave_params(h, s, stride, zld);
     P.mode = FW_MODE_SHARED; P.handed = h->pn_cnt; P.pphase = 3; P.list = need; P.nflag = nflag;
     return fmpc_launch_wave(P, grid, h->wave_lds, s.stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
 // Cold-start constants of barrier weight k: the shared factor (an export launch of the wave kernel on one problem), the
-// k-dependent constants of the exact path and of the panel path.  Once per (handle, k).  Caller holds h->mu.
-static int fmpc_ensure_cold(fmpc_handle h, double k, size_t stride, hipStream_t stream) {
+// k-dependent constants of the exact path and of the panel path.  Once per (handle, k).  Caller holds h->mu.  (fmpc_handle.h)
+int fmpc_ensure_cold(fmpc_handle h, double k, size_t stride, hipStream_t stream) {
     if (h->sh_valid && h->sh_k == k) return FMPC_OK;
     // earlier solves (ordered before this point on `stream` by the guard) may still read the constants of
     // the previous k, which the blocking uploads below overwrite
@@ -1288,8 +1278,8 @@ static int fmpc_path_wave(fmpc_handle h, const FmpcSolve& s, int mode, size_t st
 
 // fmpc_solve_device (u0_out == NULL) / fmpc_solve_u0_device: the first moves are written by the solve's last kernel
 // where that kernel visits every problem anyway (the wave kernel), by the unpack kernel otherwise.  Picks the path in a fixed
-// order; a path that does not apply returns before it enqueues anything.  Caller holds h->mu; s.ldz >= 0.
-static int fmpc_solve_device_inner(fmpc_handle h, FmpcSolve s) {
+// order; a path that does not apply returns before it enqueues anything.  Caller holds h->mu; s.ldz >= 0.  (fmpc_handle.h)
+int fmpc_solve_device_inner(fmpc_handle h, FmpcSolve s) {
     if (!h || !s.x0 || (!s.z_out && !s.u0_out)) return FMPC_E_NULL;
     if (s.batch < 0) return FMPC_E_DIM;
     if (s.batch == 0) return FMPC_OK;
@@ -1359,8 +1349,8 @@ static bool fmpc_affine_ready(fmpc_handle h, const FmpcSolve& s) {
     return h->fm_valid && h->fm_k == s.k && h->fa_valid && (size_t)s.batch <= h->fa_need_cap;
 }
 
-// s.ldz < 0: the handle's fmpc_set_z_ld value applies
-static int fmpc_solve_device_impl(fmpc_handle h, FmpcSolve s) {
+// s.ldz < 0: the handle's fmpc_set_z_ld value applies  (fmpc_handle.h)
+int fmpc_solve_device_impl(fmpc_handle h, FmpcSolve s) {
     if (!h || !s.x0 || (!s.z_out && !s.u0_out)) return FMPC_E_NULL;
     if (s.batch < 0) return FMPC_E_DIM;
     if (s.batch == 0) return FMPC_OK;
@@ -1388,13 +1378,15 @@ static int fmpc_solve_device_impl(fmpc_handle h, FmpcSolve s) {
             if (rcf != FMPC_OK) return rcf;
         }
     }
-    int rc = fmpc_guard_begin_queued(h, s.stream);
-    if (rc != FMPC_OK) return rc;
+    FmpcGuard guard(h, s.stream, fmpc_guard_begin_queued(h, s.stream));
+    if (guard.rc != FMPC_OK) return guard.rc;
     h->st_cur = S;
-    rc = fmpc_solve_device_inner(h, s);
+    const int rc = fmpc_solve_device_inner(h, s);
     h->st_cur = nullptr;
-    if (!(S && S->nsteps && S->h == h)) fmpc_guard_end(h, s.stream);      // (a queued step: the chain's launch records the event)
-    else if (!fmpc_capturing(s.stream)) h->last_stream = s.stream;
+    if (S && S->nsteps && S->h == h) {                                    // (a queued step: the chain's launch records the event)
+        guard.dismiss();
+        if (!fmpc_capturing(s.stream)) h->last_stream = s.stream;
+    }
     return rc;
 }
 
@@ -1434,332 +1426,6 @@ extern "C" int fmpc_solve_u0_device_ld(fmpc_handle h, int batch,
                                       u0_out, (hipStream_t)stream, ldz});
 }
 
-// Closed-loop step of a few realisations in the first-move form (fmpc_kernel_first.hip): ONE launch computes the loop inputs,
-// the first moves and the step-length decision; a second one (the exact path in flag mode) returns at once unless a
-// realisation was not clear-cut.  FMPC_E_UNSUPPORTED: the caller takes the four-launch path.  Caller holds h->mu.
-#define FMPC_FIRST_MOVE_MAX_BATCH 64
-#define FMPC_WALK_MAX_BATCH 4096          // realisations of a one-launch walk (fmpc_loop_run_walk): one workgroup each
-static int fmpc_first_move_ensure(fmpc_handle h, int batch, double k, hipStream_t stream, size_t* stride_out, int max_batch = FMPC_FIRST_MOVE_MAX_BATCH) {
-    if (h->fm_disabled || !h->use_wave || !h->sh_enabled || !h->pn_enabled || !h->inv_enabled || h->n != FP_N || batch > max_batch)
-        return FMPC_E_UNSUPPORTED;
-    size_t stride = 0;
-    int rc = fmpc_ensure_wave_ws(h, &stride, stream);
-    if (rc != FMPC_OK) return rc;
-    rc = fmpc_ensure_cold(h, k, stride, stream);
-    if (rc != FMPC_OK) return rc;
-    if (!h->pn_valid) return FMPC_E_UNSUPPORTED;
-    if (!h->inv_valid || h->inv_k != k) {
-        if (h->inv_failed && h->inv_failed_k == k) return FMPC_E_UNSUPPORTED;
-        if (hipStreamSynchronize(stream) != hipSuccess) return FMPC_E_HIP;
-        rc = fmpc_build_inverse(h, k, stream);
-        if (rc != FMPC_OK) return rc;
-        h->inv_failed = h->inv_valid ? 0 : 1; h->inv_failed_k = k;
-        if (!h->inv_valid) return FMPC_E_UNSUPPORTED;
-    }
-    if (!h->fm_valid || h->fm_k != k) {
-        if (hipStreamSynchronize(stream) != hipSuccess) return FMPC_E_HIP;
-        rc = fmpc_build_first_move(h, k, stream);
-        if (rc != FMPC_OK) return rc;
-    }
-    // scratch iterate for realisations the exact path redoes, one flag per realisation
-    rc = fmpc_scratch_z(h, batch, stream);
-    if (rc != FMPC_OK) return rc;
-    rc = h->fm_need.grow(batch > FMPC_FIRST_MOVE_MAX_BATCH ? (size_t)batch : (size_t)FMPC_FIRST_MOVE_MAX_BATCH, stream);
-    if (rc != FMPC_OK) return rc;
-    *stride_out = stride;
-    return FMPC_OK;
-}
-
-static int fmpc_first_move_step(fmpc_handle h, int batch, const double* a_k, const double* x0_last, const double* u1, const double* u2,
-                                double* x0, double* x0_pre, double* w, const double* nu0, double k,
-                                int* status, int* iters, double* step, double* u0_out, hipStream_t stream, int given = 0) {
-    size_t stride = 0;
-    int rc = fmpc_first_move_ensure(h, batch, k, stream, &stride);
-    if (rc != FMPC_OK) return rc;
-    FmParams P = h->fm_P;
-    P.step_ld = fmpc_step_ld(1);
-    P.x0_given = given;                            // (a_k IS x0, x0_last IS x0_pre: nothing is written to x0 / x0_pre)
-    const double* xs = given ? a_k : x0; const double* xps = given ? x0_last : x0_pre;
-    P.a_k = a_k; P.x0_last = x0_last; P.u1 = u1; P.u2 = u2; P.nu0 = nu0;
-    P.x0 = x0; P.x0_pre = x0_pre; P.w = w; P.u0out = u0_out; P.status = status; P.iters = iters; P.step = step; P.need = h->fm_need;
-    P.forms = h->fm_forms;
-    P.handed = h->pn_cnt;                          // zeroed by the kernel; the exact path (next launch) counts what it redoes
-    if (fmpc_launch_first_move(P, batch, stream) != hipSuccess) return FMPC_E_HIP;
-    // the exact path for flagged realisations (cold start with the shared factor), first moves from its own z
-    const int wpw = fmpc_wave_waves_per_wg();
-    const int grid = (batch + wpw - 1) / wpw;
-    const FmpcSolve f = {batch, xs, xps, w, nullptr, nu0, 1, k, h->zs, nullptr, status, iters, step, u0_out, stream, 0};
-    if (fmpc_launch_flagged(h, f, grid, stride, h->fm_need) != FMPC_OK) return FMPC_E_HIP;
-    h->last_path = FMPC_PATH_PANEL; h->pn_split_last = 0; h->inv_last = 1;
-    return FMPC_OK;
-}
-
-// Closed-loop step of MANY realisations with first moves only: the loop-input kernel, the first-move form as a product over the
-// batch (fmpc_kernel_loopu0.hip), the exact path in flag mode -- three launches, none of them over the T stages.
-#define FMPC_LOOP_U0_MAX_BATCH 65536
-static int fmpc_loop_u0_step(fmpc_handle h, int batch, const double* a_k, const double* x0_last, const double* u1, const double* u2,
-                             double* x0, double* x0_pre, double* w, const double* nu0, double k,
-                             int* status, int* iters, double* step, double* u0_out, hipStream_t stream, int given = 0) {
-    if (h->fl_disabled) return FMPC_E_UNSUPPORTED;
-    size_t stride = 0;
-    int rc = fmpc_first_move_ensure(h, batch, k, stream, &stride, FMPC_LOOP_U0_MAX_BATCH);
-    if (rc != FMPC_OK) return rc;
-    if (!h->fl_valid) return FMPC_E_UNSUPPORTED;
-    const int wpw = fmpc_wave_waves_per_wg();
-    int grid = (batch + wpw - 1) / wpw;
-    if (grid > 64) grid = 64;                      // flagged realisations are few: the list is walked by a small grid (as after the affine kernel)
-    // ONE launch for the loop inputs, the first moves and the decision -- when the other workgroups may read x0_last while
-    // x0 and x0_pre are written, i.e. when the caller does not update x0 in place
-    if (h->fs_valid && h->loop_M1 && (given || x0_last == nullptr || (x0_last != x0 && x0_last != x0_pre))) {
-        FlParams L = h->fs_P;
-        FlStepIn I = h->fs_I;
-        I.x0_given = given;
-        const double* xs = given ? a_k : x0; const double* xps = given ? x0_last : x0_pre;
-        L.batch = batch; L.step_ld = fmpc_step_ld(1);
-        L.nu0 = nu0; L.u0out = u0_out; L.status = status; L.iters = iters; L.step = step; L.need = h->fm_need; L.handed = h->pn_cnt;
-        L.x0w = x0; L.x0pw = x0_pre;
-        I.a = a_k; I.x0_last = x0_last; I.u1 = u1; I.u2 = u2; I.w = w;
-        if (fmpc_launch_loop_step27(L, I, stream) != hipSuccess) return FMPC_E_HIP;
-        const FmpcSolve f = {batch, xs, xps, w, nullptr, nu0, 1, k, h->zs, nullptr, status, iters, step, u0_out, stream, 0};
-        if (fmpc_launch_flagged(h, f, grid, stride, h->fm_need) != FMPC_OK) return FMPC_E_HIP;
-        h->last_path = FMPC_PATH_PANEL; h->pn_split_last = 0; h->inv_last = 4;
-        return FMPC_OK;
-    }
-    if (given) return FMPC_E_UNSUPPORTED;          // (the caller takes the general route)
-    rc = h->lp_v.grow((size_t)batch * 2 * h->n, stream);
-    if (rc != FMPC_OK) return rc;
-    if (fmpc_launch_loop_inputs(h->n, h->m, h->T, batch, h->dev.Bt, h->loop_M1, h->loop_M2, a_k, x0_last, u1, u2,
-                                x0, x0_pre, w, stream, h->lp_v) != hipSuccess) return FMPC_E_HIP;
-    FlParams L = h->fl_P;
-    L.batch = batch; L.step_ld = fmpc_step_ld(1);
-    L.x0 = x0; L.x0_pre = x0_pre; L.v = h->lp_v; L.nu0 = nu0;
-    L.u0out = u0_out; L.status = status; L.iters = iters; L.step = step; L.need = h->fm_need; L.handed = h->pn_cnt;
-    if (fmpc_launch_loop_u0(L, stream) != hipSuccess) return FMPC_E_HIP;
-    const FmpcSolve f = {batch, x0, x0_pre, w, nullptr, nu0, 1, k, h->zs, nullptr, status, iters, step, u0_out, stream, 0};
-    if (fmpc_launch_flagged(h, f, grid, stride, h->fm_need) != FMPC_OK) return FMPC_E_HIP;
-    h->last_path = FMPC_PATH_PANEL; h->pn_split_last = 0; h->inv_last = 3;
-    return FMPC_OK;
-}
-
-// One closed-loop step: fmpc_loop_inputs_device + fmpc_solve_u0_device under one lock, with the knowledge that
-// w = -M1 (B u1) - M2 (B u2) has only 2 n degrees of freedom.
-// given = 1 (fmpc_ao_step_device): a_k IS x0 and x0_last IS x0_pre -- the loop with its estimator, where the solver's x0 is the
-// estimated residual and not a[k] + B u[k-1] (README.md:482-497); x0 / x0_pre are not written (may be NULL).
-static int fmpc_loop_step_impl(fmpc_handle h, int batch, const double* a_k, const double* x0_last,
-                               const double* u1, const double* u2, double* x0, double* x0_pre, double* w,
-                               const double* nu0, int n_newton, double k,
-                               double* z_out, double* nu_out, int* status, int* iters, double* step,
-                               double* u0_out, void* stream, int given) {
-    if (!h || !a_k || (!given && (!x0 || !x0_pre)) || !w || !u0_out) return FMPC_E_NULL;       // z_out may be NULL: first moves only
-    if (given && !x0_last && h->var_order == 2) return FMPC_E_NULL;             // (x0_pre of a VAR(2) model: zeros at the first step, not NULL)
-    if (batch < 0) return FMPC_E_DIM;
-    if (batch == 0) return FMPC_OK;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lk(h->mu);
-    int rc = fmpc_guard_begin(h, (hipStream_t)stream);
-    if (rc != FMPC_OK) return rc;
-    const bool lr = h->inv_enabled && h->inv_jimg2 != nullptr && h->n == FP_N;
-    // (a handle switched to the fp32 factor or to FMPC_TILED=1 takes the kernel it was switched to, whatever outputs are asked for)
-    if (lr && !z_out && !nu_out && n_newton == 1 && h->prec == FMPC_PREC_F64 && !h->force_tiled) {
-        // first moves only, a few realisations: one launch instead of four (falls through when the form does not apply)
-        // few realisations: a workgroup per realisation (fmpc_first_move); from fs_min_batch on (default 65, FMPC_PRODUCT_MIN_BATCH)
-        // the product form, whose 16 workgroups per 16 realisations spread the constants over as many CUs
-        rc = FMPC_E_UNSUPPORTED;
-        if (batch >= h->fs_min_batch)
-            rc = fmpc_loop_u0_step(h, batch, a_k, x0_last, u1, u2, x0, x0_pre, w, nu0, k, status, iters, step, u0_out, (hipStream_t)stream, given);
-        if (rc == FMPC_E_UNSUPPORTED)
-            rc = fmpc_first_move_step(h, batch, a_k, x0_last, u1, u2, x0, x0_pre, w, nu0, k, status, iters, step, u0_out, (hipStream_t)stream, given);
-        if (rc == FMPC_E_UNSUPPORTED && batch > FMPC_FIRST_MOVE_MAX_BATCH && batch < h->fs_min_batch)
-            rc = fmpc_loop_u0_step(h, batch, a_k, x0_last, u1, u2, x0, x0_pre, w, nu0, k, status, iters, step, u0_out, (hipStream_t)stream, given);
-        if (rc != FMPC_E_UNSUPPORTED) { fmpc_guard_end(h, (hipStream_t)stream); return rc; }
-        rc = FMPC_OK;
-    }
-    if (lr && (rc = h->lp_v.grow((size_t)batch * 2 * h->n, (hipStream_t)stream)) != FMPC_OK) { fmpc_guard_end(h, (hipStream_t)stream); return rc; }
-    const double* a_in = a_k; const double* xl_in = x0_last; double* x0_o = x0; double* x0p_o = x0_pre;
-    if (given) {
-        // the loop-input kernel only has to produce w: a = 0, its x0 / x0_pre go to scratch (3 batch n doubles of the handle)
-        if ((size_t)batch * 3 * h->n > h->ao_scr.cap) {
-            if ((rc = h->ao_scr.alloc((size_t)3 * batch * h->n, (hipStream_t)stream)) != FMPC_OK) { fmpc_guard_end(h, (hipStream_t)stream); return rc; }
-            if (hipMemsetAsync(h->ao_scr, 0, (size_t)batch * h->n * sizeof(double), (hipStream_t)stream) != hipSuccess) { fmpc_guard_end(h, (hipStream_t)stream); return FMPC_E_HIP; }
-        }
-        const size_t cap = h->ao_scr.cap / (3 * h->n);          // (problems the scratch was sized for: the offsets of its thirds)
-        a_in = h->ao_scr; xl_in = nullptr; x0_o = h->ao_scr + cap * h->n; x0p_o = h->ao_scr + 2 * cap * h->n;
-    }
-    if (fmpc_launch_loop_inputs(h->n, h->m, h->T, batch, h->dev.Bt, h->loop_M1, h->loop_M2, a_in, xl_in, u1, u2,
-                                x0_o, x0p_o, w, (hipStream_t)stream, lr ? h->lp_v : nullptr) != hipSuccess) rc = FMPC_E_HIP;
-    if (rc == FMPC_OK) {
-        h->lp_hint = lr ? 1 : 0;
-        rc = fmpc_solve_device_inner(h, {batch, given ? a_k : x0, given ? x0_last : x0_pre, w, nullptr, nu0, n_newton, k, z_out, nu_out,
-                                         status, iters, step, u0_out, (hipStream_t)stream, h->z_ld});
-        h->lp_hint = 0;
-    }
-    fmpc_guard_end(h, (hipStream_t)stream);
-    return rc;
-}
-
-extern "C" int fmpc_loop_step_device(fmpc_handle h, int batch, const double* a_k, const double* x0_last,
-                                     const double* u1, const double* u2, double* x0, double* x0_pre, double* w,
-                                     const double* nu0, int n_newton, double k,
-                                     double* z_out, double* nu_out, int* status, int* iters, double* step,
-                                     double* u0_out, void* stream) {
-    return fmpc_loop_step_impl(h, batch, a_k, x0_last, u1, u2, x0, x0_pre, w, nu0, n_newton, k, z_out, nu_out, status, iters, step, u0_out, stream, 0);
-}
-
-// The MPC part of one timestep of the loop WITH its estimator (README.md:482-497,548-556,589): x0 = ad_est[k], x0_pre = ad_est[k-1]
-// come from the estimator, b_ref = -M1 B u[k-1] - M2 B u[k-2] from the moves applied.  See include/fastmpc.h.
-extern "C" int fmpc_ao_step_device(fmpc_handle h, int batch, const double* x0, const double* x0_pre,
-                                   const double* u1, const double* u2, double* w,
-                                   const double* nu0, int n_newton, double k,
-                                   double* z_out, double* nu_out, int* status, int* iters, double* step,
-                                   double* u0_out, void* stream) {
-    return fmpc_loop_step_impl(h, batch, x0, x0_pre, u1, u2, nullptr, nullptr, w, nu0, n_newton, k, z_out, nu_out, status, iters, step, u0_out, stream, 1);
-}
-
-// A recorded stretch of the loop in ONE host call: steps consecutive fmpc_loop_step_device calls with the first moves fed back
-// on the device (u[k] = U0[k], u[k-1] = U0[k-1], ...).  See include/fastmpc.h.
-// The steps [0, upto) of a recorded stretch as ONE launch per walk (fmpc_first_move_run): every realisation walks until a step
-// is not clear-cut; the host has that step redone by the one-step call (its exact path) and starts the walk again behind it.
-// Synchronises the stream once per walk (it has to see where the walks stopped).  FMPC_E_UNSUPPORTED: not applicable, nothing done.
-static int fmpc_loop_run_walk(fmpc_handle h, int batch, int steps, int upto, const double* a, const double* nu0,
-                              const double* ub1, const double* ub2, int have_x0_last, double k,
-                              double* x0, double* x0_pre, double* w, double* U0, double* X0, int* status, int* iters, hipStream_t stream) {
-    std::vector<int> start(batch, 0), stop(batch, 0), idx, stp;      // (host sides of asynchronous copies: alive until the function returns)
-    std::vector<std::vector<int>> keep;                              // index lists of the stepwise mode (no synchronisation between its copies)
-    // Every walk costs a synchronisation, and every stop a gather + one-step call + scatter + a new batch-wide launch: on a stretch
-    // where many steps are not clear-cut that is slower than one call per step.  After `max_restarts` walks, or when more than a
-    // tenth of the realisations stop in one walk, the rest of the stretch is done STEPWISE: the realisations that are furthest
-    // behind take one step through the one-step call (a compact batch, as for a stopped step) until all have arrived -- at most
-    // `upto` such calls, none of them synchronises.
-    int max_restarts = 8, restarts = 0;
-    { const int v = fmpc_env_int("FMPC_WALK_MAX_RESTARTS", -1); if (v >= 0) max_restarts = v; }
-    bool stepwise = false;
-    for (;;) {
-        if (stepwise) {
-            int smin = upto;
-            for (int p = 0; p < batch; ++p) smin = start[p] < smin ? start[p] : smin;
-            if (smin >= upto) return FMPC_OK;
-            keep.emplace_back(); keep.emplace_back();
-            std::vector<int>& ki = keep[keep.size() - 2];
-            std::vector<int>& ks = keep[keep.size() - 1];
-            for (int p = 0; p < batch; ++p)
-                if (start[p] == smin) { ki.push_back(p); ks.push_back(smin); start[p] = smin + 1; }
-            idx = ki; stp = ks;
-        } else {
-            if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-            std::lock_guard<std::mutex> lk(h->mu);
-            int rc = fmpc_guard_begin(h, stream);
-            if (rc != FMPC_OK) return rc;
-            size_t stride = 0;
-            rc = fmpc_first_move_ensure(h, 1, k, stream, &stride);
-            if (rc == FMPC_OK && (size_t)batch > h->fm_walk_cap) {
-                h->fm_walk_cap = 0;
-                size_t cap = 64;
-                while (cap < (size_t)batch) cap *= 2;
-                const size_t nd = fmpc_compact_doubles(h->n, h->m, h->T, h->nb, (int)cap);
-                if (h->fm_walk_i.alloc(2 * cap, stream) != FMPC_OK || h->fm_compact.alloc(nd, stream) != FMPC_OK) rc = FMPC_E_ALLOC;
-                else h->fm_walk_cap = cap;
-            }
-            if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
-            int* d_start = h->fm_walk_i;
-            int* d_stop = h->fm_walk_i + h->fm_walk_cap;
-            FmParams P = h->fm_P;
-            P.step_ld = fmpc_step_ld(1);
-            P.x0 = x0; P.x0_pre = x0_pre; P.status = status; P.iters = iters; P.handed = h->pn_cnt; P.forms = nullptr;
-            FmRun R;
-            R.steps = upto; R.batch = batch; R.have_x0_last = have_x0_last; R.start = d_start; R.stop = d_stop;
-            R.a = a; R.nu0 = nu0; R.U0 = U0; R.X0 = X0; R.ub1 = ub1; R.ub2 = ub2;
-            bool ok = hipMemcpyAsync(d_start, start.data(), batch * sizeof(int), hipMemcpyHostToDevice, stream) == hipSuccess;
-            ok = ok && fmpc_launch_first_move_run(P, R, stream) == hipSuccess;
-            ok = ok && hipMemcpyAsync(stop.data(), d_stop, batch * sizeof(int), hipMemcpyDeviceToHost, stream) == hipSuccess;
-            h->last_path = FMPC_PATH_PANEL; h->pn_split_last = 0; h->inv_last = 1;
-            fmpc_guard_end(h, stream);
-            if (!ok || hipStreamSynchronize(stream) != hipSuccess) return FMPC_E_HIP;
-        }
-        // the stopped realisations, each at its own step, as ONE compact batch through the one-step call (its exact path redoes
-        // them), results scattered back; then the walks go on behind those steps
-        if (!stepwise) {
-            idx.clear(); stp.clear();
-            for (int p = 0; p < batch; ++p) {
-                if (stop[p] >= upto) { start[p] = upto; continue; }
-                idx.push_back(p); stp.push_back(stop[p]);
-                start[p] = stop[p] + 1;
-            }
-        }
-        const bool done = idx.empty();
-        if (!done) {
-            const int cnt = (int)idx.size();
-            const int* hidx = stepwise ? keep[keep.size() - 2].data() : idx.data();
-            const int* hstp = stepwise ? keep[keep.size() - 1].data() : stp.data();
-            FmCompact C;
-            C.cnt = cnt; C.n = h->n; C.m = h->m; C.T = h->T; C.nb = h->nb; C.batch = batch; C.have_x0_last = have_x0_last;
-            C.a = a; C.nu0 = nu0; C.U0 = U0; C.X0 = X0; C.ub1 = ub1; C.ub2 = ub2;
-            C.x0 = x0; C.x0_pre = x0_pre; C.w = w; C.status = status; C.iters = iters;
-            {
-                std::lock_guard<std::mutex> lk(h->mu);
-                int* d_idx = h->fm_walk_i;                                     // start / stop slots: free between walks
-                int* d_stp = h->fm_walk_i + h->fm_walk_cap;
-                fmpc_compact_carve(C, h->fm_compact, (int)h->fm_walk_cap);
-                C.idx = d_idx; C.stp = d_stp;
-                if (hipMemcpyAsync(d_idx, hidx, cnt * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess ||
-                    hipMemcpyAsync(d_stp, hstp, cnt * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess ||
-                    fmpc_launch_walk_gather(C, stream) != hipSuccess) return FMPC_E_HIP;
-            }
-            const int rc = fmpc_loop_step_device(h, cnt, C.ca, C.cx0, C.cu1, C.cu2, C.cx0, C.cx0p, C.cw, nu0 ? C.cnu : nullptr, 1, k,
-                                                 nullptr, nullptr, C.cst, C.cit, nullptr, C.cu0, stream);
-            if (rc != FMPC_OK) return rc;
-            if (fmpc_launch_walk_scatter(C, stream) != hipSuccess) return FMPC_E_HIP;
-        }
-        if (getenv("FMPC_DEBUG_WALK")) {
-            if (stepwise) fprintf(stderr, "[fastmpc] stepwise: %d realisations take step %d\n", (int)idx.size(), stp.empty() ? -1 : stp[0]);
-            else {
-                int nstop = 0;
-                for (int p = 0; p < batch; ++p) nstop += stop[p] < upto ? 1 : 0;
-                fprintf(stderr, "[fastmpc] walk over %d realisations up to step %d: %d stopped\n", batch, upto, nstop);
-            }
-        }
-        if (done) return FMPC_OK;                    // (a restarted walk begins at a step >= 1 of the stretch: x0 holds its predecessor's residual)
-        if (!stepwise && (++restarts >= max_restarts || idx.size() * 10 > (size_t)batch)) stepwise = true;
-    }
-}
-
-extern "C" int fmpc_loop_run_device(fmpc_handle h, int batch, int steps, const double* a, const double* nu0,
-                                    const double* u_before1, const double* u_before2, int have_x0_last,
-                                    int n_newton, double k, double* x0, double* x0_pre, double* w,
-                                    double* U0, double* X0, int* status, int* iters, void* stream) {
-    if (!h || !a || !x0 || !x0_pre || !w || !U0) return FMPC_E_NULL;
-    if (batch < 0 || steps < 0) return FMPC_E_DIM;
-    if (batch == 0 || steps == 0) return FMPC_OK;
-    const size_t sn = (size_t)batch * h->n, sm = (size_t)batch * h->m, snu = (size_t)batch * h->nb * h->n;
-    int s_begin = 0;
-    if (n_newton == 1 && steps >= 3 && batch <= FMPC_WALK_MAX_BATCH && h->n == FP_N && h->inv_jimg2 != nullptr) {
-        // all steps but the last in one launch; the last one by the one-step call, which leaves x0, x0_pre, w, status and
-        // iters exactly as a step-by-step run does
-        const int rc = fmpc_loop_run_walk(h, batch, steps, steps - 1, a, nu0, u_before1, u_before2, have_x0_last, k, x0, x0_pre, w, U0, X0,
-                                          status, iters, (hipStream_t)stream);
-        if (rc == FMPC_OK) s_begin = steps - 1;
-        else if (rc != FMPC_E_UNSUPPORTED) return rc;
-    }
-    for (int s = s_begin; s < steps; ++s) {
-        const double* u1 = s >= 1 ? U0 + (size_t)(s - 1) * sm : u_before1;
-        const double* u2 = s >= 2 ? U0 + (size_t)(s - 2) * sm : (s == 1 ? u_before1 : u_before2);
-        const int rc = fmpc_loop_step_device(h, batch, a + (size_t)s * sn, (s >= 1 || have_x0_last) ? x0 : nullptr, u1, u2, x0, x0_pre, w,
-                                             nu0 ? nu0 + (size_t)s * snu : nullptr, n_newton, k, nullptr, nullptr, status, iters, nullptr,
-                                             U0 + (size_t)s * sm, stream);
-        if (rc != FMPC_OK) return rc;
-        if (X0 && hipMemcpyAsync(X0 + (size_t)s * sn, x0, sn * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return FMPC_E_HIP;
-    }
-    return FMPC_OK;
-}
-
-// Diagnostic (tests): the one-step first-move kernel writes, per realisation, the bounds its decision used -- upper bound of
-// ||e||^2, lower bounds of ||r_p||^2 and of rho^2 -- to dev_forms[3 p ..] (device memory, NULL: off).
-extern "C" int fmpc_debug_first_move_forms(fmpc_handle h, double* dev_forms) {
-    if (!h) return FMPC_E_NULL;
-    std::lock_guard<std::mutex> lk(h->mu);
-    h->fm_forms = dev_forms;
-    return FMPC_OK;
-}
-
 extern "C" int fmpc_set_z_ld(fmpc_handle h, int ldz) {
     if (!h) return FMPC_E_NULL;
     if (ldz != 0 && ldz < h->T * (h->n + h->m)) return FMPC_E_DIM;
@@ -1779,7 +1445,7 @@ extern "C" int fmpc_set_small_batch_kernel(fmpc_handle h, int tiled) {
 extern "C" int fmpc_last_dual_form(fmpc_handle h) {
     if (!h) return FMPC_E_NULL;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->last_path == FMPC_PATH_RAMP) return h->rc_last ? 5 : 0;     // 5: the cold-start step with ramp rows in its Woodbury form
+    if (h->last_path == FMPC_PATH_RAMP) return h->ramp.cold.last ? 5 : 0;    // 5: the cold-start step with ramp rows in its Woodbury form
     return h->last_path == FMPC_PATH_PANEL ? h->inv_last : 0;
 }
 
@@ -1829,393 +1495,6 @@ extern "C" int fmpc_debug_continuation_count(fmpc_handle h, int* count) {
     return FMPC_OK;
 }
 
-// doubles (16 GB) of ramp workspace for all workgroups together
-#define FMPC_RAMP_WS_BUDGET ((size_t)2 << 30)
-
-// The historical LDS bound that admits a handle to fmpc_newton_ramp (it still counts a 1024-thread variant and LDS scratch the
-// kernel no longer has); kept as it is so that every (n, m, T) stays on the path it has always taken.
-static size_t fmpc_ramp_lds_admit_bytes(int n, int m, int nbn) {
-    const size_t ntl = ((size_t)nbn + 1 + 15) / 16;
-    const size_t d = (size_t)m * n + 2 * (size_t)n * (n + 1) + 2 * (size_t)n + 16 * 64 + 16 + (16 * 17 + 16 * ntl + 16 * 16 + 16);
-    return d * sizeof(double);
-}
-
-extern "C" int fmpc_set_ramp(fmpc_handle h, const double* du_min, const double* du_max) {
-    if (!h || !du_min || !du_max) return FMPC_E_NULL;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    for (int c = 0; c < h->m; ++c)
-        if (!(du_min[c] < du_max[c])) return FMPC_E_DIM;
-    // fmpc_newton_ramp: n <= 64, B' and its tiles in LDS, diagonal weights.  Everything else: fmpc_newton_ramp_ws, whose LDS
-    // grows only with the 16 NTl doubles of the substitution vector and whose workspace (one problem) must fit the budget.
-    const bool lds_ok = h->n <= 64 && fmpc_ramp_lds_admit_bytes(h->n, h->m, h->nb * h->n) <= FMPC_LDS_LIMIT && !h->hm.denseQ && !h->hm.denseR;
-    const size_t lds_ws = fmpc_ramp_lds_bytes(h->n, h->m, h->nb, 1);
-    const bool ws_ok = lds_ws <= FMPC_LDS_LIMIT && fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb, 1, h->hm.denseR) <= FMPC_RAMP_WS_BUDGET;
-    if (!lds_ok && !ws_ok) return FMPC_E_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->ramp_du) {
-        if (h->ramp_du.alloc(2 * (size_t)h->m, nullptr) != FMPC_OK) return FMPC_E_ALLOC;
-        if (lds_ok && fmpc_ramp_prepare(0, fmpc_ramp_lds_bytes(h->n, h->m, h->nb, 0)) != hipSuccess) return FMPC_E_HIP;
-        if (ws_ok && fmpc_ramp_prepare(1, lds_ws) != hipSuccess) return FMPC_E_HIP;
-        h->ramp_lds_ok = lds_ok ? 1 : 0;
-        if (!ws_ok) h->ramp_force_ws = 0;
-    } else if (hipDeviceSynchronize() != hipSuccess) {
-        return FMPC_E_HIP;
-    }
-    if (hipMemcpy(h->ramp_du, du_min, h->m * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(h->ramp_du + h->m, du_max, h->m * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return FMPC_E_HIP;
-    h->hm_dumin.assign(du_min, du_min + h->m); h->hm_dumax.assign(du_max, du_max + h->m);
-    h->rc_valid = 0; h->rc_failed = 0;                              // (the constants of the cold-start form depend on the bounds)
-    return FMPC_OK;
-}
-
-extern "C" int fmpc_set_ramp_workspace(fmpc_handle h, int enabled) {
-    if (!h) return FMPC_E_NULL;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (enabled) {
-        const size_t lds_ws = fmpc_ramp_lds_bytes(h->n, h->m, h->nb, 1);
-        if (lds_ws > FMPC_LDS_LIMIT || fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb, 1, h->hm.denseR) > FMPC_RAMP_WS_BUDGET) return FMPC_E_UNSUPPORTED;
-        if (hipSetDevice(h->device) != hipSuccess || fmpc_ramp_prepare(1, lds_ws) != hipSuccess) return FMPC_E_HIP;
-    }
-    h->ramp_force_ws = enabled ? 1 : 0;
-    return FMPC_OK;
-}
-
-// Constants of the cold-start step's Woodbury form for barrier weight k (fmpc_host_build_ramp_cold): built on the host in long
-// double on first use of a k, uploaded as one pool.  FMPC_E_UNSUPPORTED: the general path takes the solve (LDS, a start point
-// at which Phibar or Ybar is not positive definite, FMPC_NO_RAMP_COLD=1).  Caller holds h->mu.
-static int fmpc_ensure_ramp_cold(fmpc_handle h, double k, hipStream_t stream) {
-    if (h->rc_disabled) return FMPC_E_UNSUPPORTED;
-    if (h->rc_valid && h->rc_k == k) return FMPC_OK;
-    if (h->rc_failed && h->rc_failed_k == k) return FMPC_E_UNSUPPORTED;
-    const size_t lds = fmpc_ramp_cold_lds_bytes(h->n, h->m, h->T, h->nb);
-    // (the constants are built from the DIAGONALS hm.Q2, hm.Qf2, hm.R2: never for dense weights)
-    if (lds > FMPC_LDS_LIMIT || h->n > 64 || h->hm.denseQ || h->hm.denseR) return FMPC_E_UNSUPPORTED;
-    FmpcRampColdIn In;
-    In.M = &h->hm; In.dumin = h->hm_dumin.data(); In.dumax = h->hm_dumax.data(); In.k = k;
-    FmpcRampColdOut O;
-    fmpc_host_build_ramp_cold(In, O);
-    if (!O.valid) { h->rc_failed = 1; h->rc_failed_k = k; return FMPC_E_UNSUPPORTED; }
-    std::vector<double> pool;
-    auto push = [&](const std::vector<double>& v) { const size_t o = pool.size(); pool.insert(pool.end(), v.begin(), v.end()); if (pool.size() & 1) pool.push_back(0.0); return o; };
-    const size_t o_g0 = push(O.g0), o_Gf = push(O.Gf), o_pu = push(O.phib_u), o_px = push(O.phib_x), o_gu = push(O.gbar_u), o_gx = push(O.gbar_x),
-                 o_hd = push(O.hd), o_er = push(O.erb), o_cp = push(O.cpb), o_bb = push(O.betab), o_Yi = push(O.Yinv), o_G = push(O.G),
-                 o_Xi = push(O.Xiu0t), o_y0 = push(O.y0c);
-    size_t o_ik, o_ib;
-    {
-        std::vector<double> ik, ib;
-        fmpc_host_mfma_images(h->hm.bt.data(), h->m, h->n, (h->n + 3) / 4, ik);
-        fmpc_host_mfma_images(h->hm.b.data(), h->n, h->m, (h->m + 3) / 4, ib);
-        o_ik = push(ik); o_ib = push(ib);
-    }
-    size_t o_Gt;
-    {   // G in the LDS tile layout of fr_tile_cholesky_lds: upper tile triangle of [G | rhs] packed, 16 x 16 row-major, zero padded
-        const int m_ = h->m, NTm = (m_ + 15) / 16, NT1 = NTm + 1;
-        std::vector<double> Gt;
-        for (int I = 0; I < NTm; ++I)
-            for (int J = I; J < NT1; ++J)
-                for (int e = 0; e < 256; ++e) {
-                    const int row = 16 * I + (e >> 4), col = 16 * J + (e & 15);
-                    Gt.push_back(row < m_ && col < m_ ? O.G[(size_t)row * ((m_ + 1) & ~1) + col] : 0.0);
-                }
-        o_Gt = push(Gt);
-    }
-    h->rc_valid = 0;
-    const int rc = h->rc_pool.assign(pool.data(), pool.size(), stream);
-    if (rc != FMPC_OK) return rc;
-    if (fmpc_ramp_cold_prepare(lds) != hipSuccess) return FMPC_E_HIP;
-    FrColdParams& P = h->rc_P;
-    memset(&P, 0, sizeof(P));
-    P.M = h->dev; P.dumin = h->ramp_du; P.dumax = h->ramp_du + h->m; P.kbar = k;
-    P.g0 = h->rc_pool + o_g0; P.Gf = h->rc_pool + o_Gf; P.phib_u = h->rc_pool + o_pu; P.phib_x = h->rc_pool + o_px; P.gbar_u = h->rc_pool + o_gu;
-    P.gbar_x = h->rc_pool + o_gx; P.hd = h->rc_pool + o_hd; P.erb = h->rc_pool + o_er; P.cpb = h->rc_pool + o_cp; P.betab = h->rc_pool + o_bb;
-    P.Yinv = h->rc_pool + o_Yi; P.G = h->rc_pool + o_G; P.Gt = h->rc_pool + o_Gt; P.imgBk = h->rc_pool + o_ik; P.imgBb = h->rc_pool + o_ib; P.Xiu0t = h->rc_pool + o_Xi; P.y0c = h->rc_pool + o_y0;
-    h->rc_valid = 1; h->rc_k = k;
-    return FMPC_OK;
-}
-
-// The launch parameters of a ramp solve s (u_prev: the previous moves); form ws, workspace stride per workgroup.
-static FrParams fmpc_ramp_params(fmpc_handle h, const FmpcSolve& s, const double* u_prev, bool ws, size_t stride) {
-    FrParams P;
-    P.M = h->dev; P.dumin = h->ramp_du; P.dumax = h->ramp_du + h->m;
-    P.batch = s.batch; P.max_iter = fmpc_max_iter(s); P.step_ld = fmpc_step_ld(s.n_newton); P.ws = ws ? 1 : 0; P.it0 = 0; P.kbar = s.k;
-    P.x0 = s.x0; P.x0p = s.x0_pre; P.w = s.w; P.uprev = u_prev; P.zinit = s.z_init; P.nu0 = s.nu0;
-    P.zout = s.z_out; P.nuout = s.nu_out; P.status = s.status; P.iters = s.iters; P.step = s.step;
-    P.ws_buf = h->ramp_ws; P.ws_stride = stride;
-    return P;
-}
-
-// One launch of fmpc_newton_ramp (ws = false) or fmpc_newton_ramp_ws from s.z_init or the mid-box start, then the first moves
-// by the unpack kernel if they are asked for.
-static int fmpc_ramp_path_newton(fmpc_handle h, const FmpcSolve& s, const double* u_prev, bool ws, size_t stride, int grid) {
-    { const int rw = h->ramp_ws.grow(stride * (size_t)grid, s.stream); if (rw != FMPC_OK) return rw; }
-    h->last_path = ws ? FMPC_PATH_RAMP_WS : FMPC_PATH_RAMP;
-    h->rc_last = 0;
-    hipError_t e = fmpc_launch_ramp(fmpc_ramp_params(h, s, u_prev, ws, stride), grid, s.stream);
-    if (e == hipSuccess && s.u0_out)
-        e = fmpc_launch_unpack(h->n, h->m, h->T, s.batch, s.z_out, nullptr, nullptr, s.u0_out, s.stream);
-    return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
-}
-
-// Cold start on fmpc_newton_ramp's domain: the first Newton step in its Woodbury form (fmpc_ramp_cold, one m x m factorisation
-// per problem); a budget > 1 continues with fmpc_newton_ramp from the iterate that step leaves (it0 = 1).  The first moves come
-// from the cold-start kernel itself when it takes the whole solve (budget 1; s.z_out may then be NULL), from the unpack kernel
-// otherwise.  FMPC_E_UNSUPPORTED: the form is not available, nothing is enqueued.
-static int fmpc_ramp_path_cold(fmpc_handle h, const FmpcSolve& s, const double* u_prev, size_t stride, int grid) {
-    const int rcc = fmpc_ensure_ramp_cold(h, s.k, s.stream);
-    if (rcc != FMPC_OK) return rcc;
-    const int batch = s.batch, max_iter = fmpc_max_iter(s);
-    const size_t cstride = fmpc_ramp_cold_ws_doubles(h->m);
-    const int cgrid = batch < h->num_cu ? batch : h->num_cu;
-    if (cstride * (size_t)cgrid > h->rc_ws.cap) {
-        size_t want = cstride * (size_t)(batch < h->num_cu ? (batch < 16 ? 16 : batch) : h->num_cu);
-        if (want > cstride * (size_t)h->num_cu) want = cstride * (size_t)h->num_cu;
-        const int rcw = h->rc_ws.alloc(want, s.stream);
-        if (rcw != FMPC_OK) return rcw;
-    }
-    // the continuation reads nu, status and iters of the first step: scratch arrays where the caller passes none
-    double* nu_first = s.nu_out;
-    int* st_first = s.status; int* it_first = s.iters;
-    if (max_iter > 1 && (!s.nu_out || !s.status || !s.iters)) {
-        if ((size_t)batch > h->rc_cap) {
-            h->rc_cap = 0;
-            if (h->rc_nu.alloc((size_t)batch * h->nb * h->n, s.stream) != FMPC_OK ||
-                h->rc_si.alloc(2 * (size_t)batch, s.stream) != FMPC_OK) return FMPC_E_ALLOC;
-            h->rc_cap = batch;
-        }
-        if (!s.nu_out) nu_first = h->rc_nu;
-        if (!s.status) st_first = h->rc_si;
-        if (!s.iters) it_first = h->rc_si + batch;
-    }
-    if (max_iter > 1) { const int rw = h->ramp_ws.grow(stride * (size_t)grid, s.stream); if (rw != FMPC_OK) return rw; }
-    FrColdParams P = h->rc_P;
-    P.batch = batch; P.x0 = s.x0; P.x0p = s.x0_pre; P.w = s.w; P.uprev = u_prev; P.nu0 = s.nu0;
-    P.zout = s.z_out; P.nuout = nu_first; P.u0out = max_iter == 1 ? s.u0_out : nullptr; P.status = st_first; P.iters = it_first; P.step = s.step;
-    P.step_ld = fmpc_step_ld(s.n_newton); P.ws = h->rc_ws; P.ws_stride = cstride;
-    hipError_t e = fmpc_launch_ramp_cold(P, cgrid, s.stream);
-    h->rc_last = 1;
-    if (e == hipSuccess && max_iter > 1) {
-        FrParams Q = fmpc_ramp_params(h, s, u_prev, false, stride);
-        Q.zinit = s.z_out; Q.nu0 = nu_first; Q.status = st_first; Q.iters = it_first; Q.it0 = 1;
-        e = fmpc_launch_ramp(Q, grid, s.stream);
-    }
-    if (e == hipSuccess && max_iter > 1 && s.u0_out)
-        e = fmpc_launch_unpack(h->n, h->m, h->T, batch, s.z_out, nullptr, nullptr, s.u0_out, s.stream);
-    return e == hipSuccess ? FMPC_OK : FMPC_E_HIP;
-}
-
-// Selects the ramp path: fmpc_newton_ramp on its domain (n <= 64, its LDS fits, diagonal weights; cold start: the Woodbury form
-// first), fmpc_newton_ramp_ws for everything else and after fmpc_set_ramp_workspace(h, 1).  Caller holds h->mu.
-static int fmpc_solve_ramp_device_inner(fmpc_handle h, FmpcSolve& s, const double* u_prev) {
-    const bool ws = !h->ramp_lds_ok || h->ramp_force_ws;
-    const bool cold_only = !ws && !s.z_init && fmpc_max_iter(s) == 1 && !h->rc_disabled;   // (the cold-start kernel then needs no z array at all)
-    if (!s.z_out && !cold_only) {                                   // first moves only: the iterate goes to a scratch array
-        const int rcz = fmpc_scratch_z(h, s.batch, s.stream);
-        if (rcz != FMPC_OK) return rcz;
-        s.z_out = h->zs;
-    }
-    // one workgroup per problem in flight, at most one per CU; the workspace of all of them within the budget
-    const size_t stride = fmpc_ramp_ws_doubles(h->n, h->m, h->T, h->nb, ws, h->hm.denseR);
-    int cap = h->num_cu;
-    if ((size_t)cap * stride > FMPC_RAMP_WS_BUDGET) cap = (int)(FMPC_RAMP_WS_BUDGET / stride);
-    if (cap < 1) return FMPC_E_ALLOC;
-    const int grid = s.batch < cap ? s.batch : cap;
-    if (!ws) {
-        h->last_path = FMPC_PATH_RAMP;
-        h->rc_last = 0;
-        if (!s.z_init) {
-            const int rc = fmpc_ramp_path_cold(h, s, u_prev, stride, grid);
-            if (rc != FMPC_E_UNSUPPORTED) return rc;
-            if (!s.z_out) {                                         // the cold-start form is not available after all: scratch iterate
-                const int rcz = fmpc_scratch_z(h, s.batch, s.stream);
-                if (rcz != FMPC_OK) return rcz;
-                s.z_out = h->zs;
-            }
-        }
-    }
-    return fmpc_ramp_path_newton(h, s, u_prev, ws, stride, grid);
-}
-
-// fmpc_solve_ramp_device (u0_out == NULL) / fmpc_solve_ramp_u0_device; z_out == NULL: first moves only
-// (s.ldz < 0: the handle's fmpc_set_z_ld value applies)
-static int fmpc_solve_ramp_device_impl(fmpc_handle h, FmpcSolve s, const double* u_prev) {
-    if (!h || !s.x0 || (!s.z_out && !s.u0_out) || !u_prev) return FMPC_E_NULL;
-    if (!h->ramp_du) return FMPC_E_UNSUPPORTED;                    // fmpc_set_ramp first
-    if ((s.ldz < 0 ? h->z_ld : s.ldz) > h->T * (h->n + h->m)) return FMPC_E_UNSUPPORTED;   // padded z rows: the cold-start affine step only
-    if (s.batch < 0) return FMPC_E_DIM;
-    if (s.batch == 0) return FMPC_OK;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> lk(h->mu);
-    int rc = fmpc_guard_begin(h, s.stream);
-    if (rc != FMPC_OK) return rc;
-    rc = fmpc_solve_ramp_device_inner(h, s, u_prev);
-    fmpc_guard_end(h, s.stream);
-    return rc;
-}
-
-extern "C" int fmpc_solve_ramp_device(fmpc_handle h, int batch,
-                                      const double* x0, const double* x0_pre, const double* w, const double* u_prev,
-                                      const double* z_init, const double* nu0, int n_newton, double k,
-                                      double* z_out, double* nu_out, int* status, int* iters, double* step,
-                                      void* stream) {
-    if (!z_out) return FMPC_E_NULL;
-    return fmpc_solve_ramp_device_impl(h, {batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step, nullptr,
-                                           (hipStream_t)stream, -1}, u_prev);
-}
-
-extern "C" int fmpc_solve_ramp_u0_device(fmpc_handle h, int batch,
-                                         const double* x0, const double* x0_pre, const double* w, const double* u_prev,
-                                         const double* z_init, const double* nu0, int n_newton, double k,
-                                         double* z_out, double* nu_out, int* status, int* iters, double* step,
-                                         double* u0_out, void* stream) {
-    if (!u0_out) return FMPC_E_NULL;
-    return fmpc_solve_ramp_device_impl(h, {batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step, u0_out,
-                                           (hipStream_t)stream, -1}, u_prev);
-}
-
-// host-pointer solve; u_prev != NULL selects the ramp-rate path
-// Host-pointer entries (fmpc_solve, fmpc_solve_ramp, fmpc_solve_once): stage in, solve, stage out.
-// One device block holds the inputs that are present, then the outputs that are asked for.  Up to FMPC_PIN_LIMIT bytes (the
-// literal drop-in call: ONE problem per timestep, README.md:548-556) the block has a PINNED host twin kept by the handle: the
-// inputs are packed into it and go up in ONE asynchronous copy, the outputs come back in ONE, and the call waits once -- two
-// transfers and one synchronisation where round 3 issued up to six blocking hipMemcpy each way (163 us per call).  Larger
-// batches are bandwidth-bound and copy straight between the caller's arrays and the device block.
-#define FMPC_PIN_LIMIT ((size_t)1 << 20)
-#define FMPC_ZC_LIMIT ((size_t)128 << 10)      /* calls this small skip the copies: the kernels work on the pinned block itself */
-static int fmpc_solve_host(fmpc_handle h, int batch,
-                           const double* x0, const double* x0_pre, const double* w, const double* u_prev,
-                           const double* z_init, const double* nu0,
-                           int n_newton, double k,
-                           double* z_out, double* nu_out, int* status, int* iters, double* step, double* u0_out = nullptr) {
-    if (!h || !x0 || (!z_out && !u0_out)) return FMPC_E_NULL;
-    if (u0_out && u_prev) return FMPC_E_UNSUPPORTED;                // (first-move output: not with the ramp-rate rows)
-    if (batch < 0) return FMPC_E_DIM;
-    if (batch == 0) return FMPC_OK;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    std::lock_guard<std::mutex> host_lk(h->host_mu);
-    const size_t n = h->n, Nz = (size_t)h->T * (h->n + h->m), nbn = (size_t)h->nb * h->n;
-    const size_t Tn = (size_t)h->T * h->n, sld = fmpc_step_ld(n_newton), B = batch;
-    size_t off = 0;
-    auto take = [&](bool present, size_t bytes) { if (!present) return (size_t)0; size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_x0 = take(true, n * B * 8), o_x0p = take(x0_pre != nullptr, n * B * 8), o_w = take(w != nullptr, Tn * B * 8);
-    const size_t o_zi = take(z_init != nullptr, Nz * B * 8), o_nu0 = take(nu0 != nullptr, nbn * B * 8);
-    const size_t o_up = take(u_prev != nullptr, (size_t)h->m * B * 8);
-    const size_t in_bytes = off;
-    const size_t o_out = off;                                       // outputs from here on: one copy down
-    const size_t o_z = take(z_out != nullptr, Nz * B * 8), o_nu = take(nu_out != nullptr, nbn * B * 8);
-    const size_t o_u0 = take(u0_out != nullptr, (size_t)h->m * B * 8);
-    const size_t o_st = take(true, B * 4), o_it = take(true, B * 4), o_step = take(step != nullptr, sld * B * 8);
-    const bool pinned = off <= FMPC_PIN_LIMIT;
-    char* base;
-    char* pin = nullptr;
-    char* pin_dev = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        const int rcs = h->stage.grow(off, nullptr);
-        if (rcs != FMPC_OK) return rcs;
-        base = h->stage;
-        if (pinned) {
-            if (off > h->pin.cap) {
-                size_t want = 64 * 1024;
-                while (want < off) want *= 2;
-                h->pin_dev = nullptr;
-                if (h->pin.alloc(want, nullptr) == FMPC_OK &&                       // (no pinned memory: the blocking copies below still work)
-                    hipHostGetDevicePointer(&h->pin_dev, h->pin, 0) != hipSuccess) h->pin_dev = nullptr;   // (the block as the kernels see it)
-            }
-            pin = h->pin;
-            pin_dev = (char*)h->pin_dev;
-        }
-    }
-    // A call of a few problems (the reference's per-timestep call is ONE) is all latency: the two copies and their
-    // synchronisation are 23 of its 54 us (round 5, scripts/once_latency.py).  Up to FMPC_ZC_LIMIT bytes the kernels read the
-    // inputs straight from the pinned block (it is device-accessible) -- no copy up -- and, when the iterate is written once
-    // (cold start, Newton budget 1: no kernel uses z as its working storage except for a flagged problem), write the outputs
-    // straight into it -- no copy down.  FMPC_NO_ZEROCOPY=1: the copies as before (A/B).
-    static const bool no_zc = fmpc_env_on("FMPC_NO_ZEROCOPY");
-    const bool zc_in = pin != nullptr && pin_dev != nullptr && !no_zc && off <= FMPC_ZC_LIMIT;
-    const bool zc_out = zc_in && n_newton == 1 && z_init == nullptr && u_prev == nullptr;
-    char* const base_in = zc_in ? pin_dev : base;
-    char* const base_o = zc_out ? pin_dev : base;
-    auto dptr = [&](const void* src, size_t o) -> const double* { return src ? (const double*)(base_in + o) : nullptr; };
-    if (pin) {
-        auto pack = [&](size_t o, const double* src, size_t cnt) { if (src) memcpy(pin + o, src, cnt * 8); };
-        pack(o_x0, x0, n * B); pack(o_x0p, x0_pre, n * B); pack(o_w, w, Tn * B); pack(o_zi, z_init, Nz * B); pack(o_nu0, nu0, nbn * B);
-        pack(o_up, u_prev, (size_t)h->m * B);
-        if (!zc_in && hipMemcpyAsync(base, pin, in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return FMPC_E_HIP;
-    } else {
-        auto up = [&](size_t o, const double* src, size_t cnt) { return !src || hipMemcpy(base + o, src, cnt * 8, hipMemcpyHostToDevice) == hipSuccess; };
-        if (!up(o_x0, x0, n * B) || !up(o_x0p, x0_pre, n * B) || !up(o_w, w, Tn * B) || !up(o_zi, z_init, Nz * B) || !up(o_nu0, nu0, nbn * B) ||
-            !up(o_up, u_prev, (size_t)h->m * B)) return FMPC_E_HIP;
-    }
-    int* d_st = (int*)(base_o + o_st);
-    int* d_it = (int*)(base_o + o_it);
-    double* d_nu = nu_out ? (double*)(base_o + o_nu) : nullptr;
-    double* d_step = step ? (double*)(base_o + o_step) : nullptr;
-    double* d_z = z_out ? (double*)(base_o + o_z) : nullptr;
-    double* d_u0 = u0_out ? (double*)(base_o + o_u0) : nullptr;
-    // (ldz 0: the staging block's rows are contiguous, fmpc_set_z_ld is for device batches)
-    const FmpcSolve s = {batch, dptr(x0, o_x0), dptr(x0_pre, o_x0p), dptr(w, o_w), dptr(z_init, o_zi), dptr(nu0, o_nu0), n_newton, k,
-                         d_z, d_nu, d_st, d_it, d_step, d_u0, nullptr, 0};
-    int rc = u_prev ? fmpc_solve_ramp_device_impl(h, s, dptr(u_prev, o_up)) : fmpc_solve_device_impl(h, s);
-    if (rc != FMPC_OK) { (void)hipDeviceSynchronize(); return rc; }
-    std::vector<int> stv;
-    const int* st;
-    if (pin) {
-        if (!zc_out && hipMemcpyAsync(pin + o_out, base + o_out, off - o_out, hipMemcpyDeviceToHost, nullptr) != hipSuccess) return FMPC_E_HIP;
-        if (hipStreamSynchronize(nullptr) != hipSuccess) return FMPC_E_HIP;
-        if (z_out) memcpy(z_out, pin + o_z, Nz * B * 8);
-        if (u0_out) memcpy(u0_out, pin + o_u0, (size_t)h->m * B * 8);
-        if (nu_out) memcpy(nu_out, pin + o_nu, nbn * B * 8);
-        if (iters) memcpy(iters, pin + o_it, B * 4);
-        if (step) memcpy(step, pin + o_step, sld * B * 8);
-        st = (const int*)(pin + o_st);
-    } else {
-        if (hipDeviceSynchronize() != hipSuccess) return FMPC_E_HIP;
-        stv.resize(B);
-        if (z_out && hipMemcpy(z_out, base + o_z, Nz * B * 8, hipMemcpyDeviceToHost) != hipSuccess) return FMPC_E_HIP;
-        if (u0_out && hipMemcpy(u0_out, base + o_u0, (size_t)h->m * B * 8, hipMemcpyDeviceToHost) != hipSuccess) return FMPC_E_HIP;
-        if (nu_out && hipMemcpy(nu_out, base + o_nu, nbn * B * 8, hipMemcpyDeviceToHost) != hipSuccess) return FMPC_E_HIP;
-        if (hipMemcpy(stv.data(), d_st, B * 4, hipMemcpyDeviceToHost) != hipSuccess) return FMPC_E_HIP;
-        if (iters && hipMemcpy(iters, d_it, B * 4, hipMemcpyDeviceToHost) != hipSuccess) return FMPC_E_HIP;
-        if (step && hipMemcpy(step, base + o_step, sld * B * 8, hipMemcpyDeviceToHost) != hipSuccess) return FMPC_E_HIP;
-        st = stv.data();
-    }
-    int worst = FMPC_OK;
-    for (size_t i = 0; i < B; ++i) {
-        if (status) status[i] = st[i];
-        if (st[i] < 0) { if (worst >= 0 || st[i] < worst) worst = st[i]; }
-        else if (worst >= 0 && st[i] > worst) worst = st[i];
-    }
-    return worst;
-}
-
-extern "C" int fmpc_solve(fmpc_handle h, int batch,
-                          const double* x0, const double* x0_pre, const double* w,
-                          const double* z_init, const double* nu0,
-                          int n_newton, double k,
-                          double* z_out, double* nu_out, int* status, int* iters, double* step) {
-    return fmpc_solve_host(h, batch, x0, x0_pre, w, nullptr, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step);
-}
-
-// fmpc_solve with HOST pointers that returns the first moves u0 = z(1:m) (README.md:589: the caller applies U(1:nu) only): m x batch
-// doubles come back instead of N_z x batch (2.3 MB instead of 82 MB per 2000 problems at (27,144,30)); z_out may be given as well.
-extern "C" int fmpc_solve_u0(fmpc_handle h, int batch,
-                             const double* x0, const double* x0_pre, const double* w,
-                             const double* z_init, const double* nu0,
-                             int n_newton, double k,
-                             double* z_out, double* u0_out, int* status, int* iters) {
-    if (!u0_out) return FMPC_E_NULL;
-    return fmpc_solve_host(h, batch, x0, x0_pre, w, nullptr, z_init, nu0, n_newton, k, z_out, nullptr, status, iters, nullptr, u0_out);
-}
-
-extern "C" int fmpc_solve_ramp(fmpc_handle h, int batch,
-                               const double* x0, const double* x0_pre, const double* w, const double* u_prev,
-                               const double* z_init, const double* nu0,
-                               int n_newton, double k,
-                               double* z_out, double* nu_out, int* status, int* iters, double* step) {
-    if (!u_prev) return FMPC_E_NULL;
-    return fmpc_solve_host(h, batch, x0, x0_pre, w, u_prev, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step);
-}
-
 extern "C" int fmpc_unpack_device(fmpc_handle h, int batch, const double* z, double* U, double* X,
                                   double* u0, void* stream) {
     if (!h || !z) return FMPC_E_NULL;
@@ -2225,18 +1504,6 @@ extern "C" int fmpc_unpack_device(fmpc_handle h, int batch, const double* z, dou
     { const int rcs = fmpc_stretch_flush_stream((hipStream_t)stream); if (rcs != FMPC_OK) return rcs; }   // (z of a pending chain)
     return fmpc_launch_unpack(h->n, h->m, h->T, batch, z, U, X, u0, (hipStream_t)stream) == hipSuccess
                ? FMPC_OK : FMPC_E_HIP;
-}
-
-extern "C" int fmpc_loop_inputs_device(fmpc_handle h, int batch, const double* a_k, const double* x0_last,
-                                       const double* u1, const double* u2,
-                                       double* x0, double* x0_pre, double* w, void* stream) {
-    if (!h || !a_k || !x0 || !x0_pre || !w) return FMPC_E_NULL;
-    if (batch < 0) return FMPC_E_DIM;
-    if (batch == 0) return FMPC_OK;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    { const int rcs = fmpc_stretch_flush_stream((hipStream_t)stream); if (rcs != FMPC_OK) return rcs; }
-    return fmpc_launch_loop_inputs(h->n, h->m, h->T, batch, h->dev.Bt, h->loop_M1, h->loop_M2, a_k, x0_last, u1, u2,
-                                   x0, x0_pre, w, (hipStream_t)stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
 // Residual phase screens of a timestep: README.md:453, 590-601 (see include/fastmpc.h).
@@ -2250,106 +1517,4 @@ extern "C" int fmpc_phase_residual_device(fmpc_handle h, int batch, long long np
     { const int rcs = fmpc_stretch_flush_stream((hipStream_t)stream); if (rcs != FMPC_OK) return rcs; }   // (u_prev / Z of a pending chain)
     return fmpc_launch_phase_residual(batch, (size_t)npx, h->n, h->m, h->dev.Bt, phase, u_prev, Z, out, (hipStream_t)stream) == hipSuccess
                ? FMPC_OK : FMPC_E_HIP;
-}
-
-extern "C" int fmpc_unpack(fmpc_handle h, int batch, const double* z, double* U, double* X, double* u0) {
-    if (!h || !z) return FMPC_E_NULL;
-    if (batch < 0) return FMPC_E_DIM;
-    if (batch == 0) return FMPC_OK;
-    if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
-    const size_t B = batch, Nz = (size_t)h->T * (h->n + h->m), Tm = (size_t)h->T * h->m, Tn = (size_t)h->T * h->n;
-    DevBuf<double> dz, dU, dX, du0;                               // (released on return)
-    int rc = FMPC_OK;
-    if (dz.alloc(Nz * B, nullptr) != FMPC_OK) return FMPC_E_ALLOC;
-    if ((U && dU.alloc(Tm * B, nullptr) != FMPC_OK) ||
-        (X && dX.alloc(Tn * B, nullptr) != FMPC_OK) ||
-        (u0 && du0.alloc(h->m * B, nullptr) != FMPC_OK)) rc = FMPC_E_ALLOC;
-    if (rc == FMPC_OK && hipMemcpy(dz, z, Nz * B * 8, hipMemcpyHostToDevice) != hipSuccess) rc = FMPC_E_HIP;
-    if (rc == FMPC_OK) rc = fmpc_unpack_device(h, batch, dz, dU, dX, du0, nullptr);
-    if (rc == FMPC_OK && hipDeviceSynchronize() != hipSuccess) rc = FMPC_E_HIP;
-    if (rc == FMPC_OK && U && hipMemcpy(U, dU, Tm * B * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = FMPC_E_HIP;
-    if (rc == FMPC_OK && X && hipMemcpy(X, dX, Tn * B * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = FMPC_E_HIP;
-    if (rc == FMPC_OK && u0 && hipMemcpy(u0, du0, h->m * B * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = FMPC_E_HIP;
-    return rc;
-}
-
-// The reference rebuilds its (value-class) object at every timestep (README.md:548) with the same model; doing the same
-// here would allocate, upload and -- on the panel path -- factor again at every call.  fmpc_solve_once therefore keeps
-// the handles of the last few models it has seen, keyed on the exact bytes of every model argument.
-namespace {
-std::mutex once_mu;
-FmpcLru<fmpc_handle> once_cache(4);                            // (fmpc_host.h) the last 4 distinct models
-}  // namespace
-
-extern "C" int fmpc_solve_once_cache_clear(void) {
-    std::lock_guard<std::mutex> lk(once_mu);
-    once_cache.clear([](fmpc_handle hh) { fmpc_destroy(hh); });
-    return FMPC_OK;
-}
-
-extern "C" int fmpc_solve_once(int n, int m, int T, int var_order,
-                               const double* Q, const double* R, const double* S, const double* Qf,
-                               const double* q, const double* r, const double* qf,
-                               const double* x_min, const double* x_max,
-                               const double* u_min, const double* u_max,
-                               const double* du_min, const double* du_max,
-                               const double* x0, const double* x0_pre, const double* u_prev,
-                               const double* A1, const double* A2, const double* B,
-                               const double* w, const double* xf, const double* x_init,
-                               const double* nu0, int nw, double k, int device,
-                               double* x_opt, int* iters) {
-    (void)S;                                                  // stored, never used (Fast_MPC2.m:33)
-    // VAR_2 ignores du_min, du_max, u_prev (its ramp rows are commented out, D8); VAR_1 builds ramp rows from them
-    // (VAR_1/fast_mpc_ineq_const.m:58-76)
-    const bool ramp = var_order == 1 && du_min && du_max && u_prev;
-    if (!x0 || (var_order == 2 && !x0_pre)) return FMPC_E_DIM;   // fast_mpc_eq_const.m:27-30
-    if (n <= 0 || m <= 0 || T <= 0 || (var_order != 1 && var_order != 2)) return FMPC_E_DIM;
-    if (!A1 || !B || (var_order == 2 && !A2)) return FMPC_E_NULL;
-    if (!Q || !R || !Qf || !x_min || !x_max || !u_min || !u_max) return FMPC_E_NULL;
-    std::lock_guard<std::mutex> lk(once_mu);                  // (also keeps an entry alive while it is in use)
-    // The model of a call is compared IN PLACE against the stored keys (same record format as fmpc_host_key_push: a count or -1,
-    // then the values): a hit -- every call but the first of a simulation -- builds no key (round 3 copied ~220 KB per call,
-    // most of it the m x m matrix R, before comparing it).
-    const double dims[5] = {(double)n, (double)m, (double)T, (double)var_order, (double)device};
-    const size_t nn = (size_t)n * n;
-    struct Seg { const double* p; size_t cnt; };
-    const Seg segs[15] = {{dims, 5}, {A1, nn}, {var_order == 2 ? A2 : nullptr, nn}, {B, (size_t)n * m}, {Q, nn}, {R, (size_t)m * m}, {Qf, nn},
-                          {q, (size_t)n}, {r, (size_t)m}, {qf, (size_t)n}, {x_min, (size_t)n}, {x_max, (size_t)n}, {u_min, (size_t)m},
-                          {u_max, (size_t)m}, {xf, (size_t)n}};
-    size_t key_len = 0;
-    for (const Seg& sg : segs) key_len += 1 + (sg.p ? sg.cnt : 0);
-    FmpcLru<fmpc_handle>::Entry* ent = nullptr;
-    for (auto& e : once_cache.items) {
-        if (e.key.size() != key_len) continue;
-        const double* kp = e.key.data();
-        bool same = true;
-        for (const Seg& sg : segs) {
-            if (*kp++ != (sg.p ? (double)sg.cnt : -1.0)) { same = false; break; }
-            if (sg.p) { if (memcmp(kp, sg.p, sg.cnt * sizeof(double)) != 0) { same = false; break; } kp += sg.cnt; }
-        }
-        if (same) { ent = &e; break; }
-    }
-    int rc;
-    if (!ent) {
-        std::vector<double> key;
-        key.reserve(key_len);
-        for (const Seg& sg : segs) fmpc_host_key_push(key, sg.p, sg.cnt);
-        fmpc_handle h = nullptr;
-        rc = fmpc_create(&h, n, m, T, var_order, A1, A2, B, Q, R, Qf, q, r, qf, x_min, x_max, u_min, u_max, xf, device);
-        if (rc != FMPC_OK) return rc;
-        ent = once_cache.insert(std::move(key), h, [](fmpc_handle hh) { fmpc_destroy(hh); });   // evicts the least recently used model
-    }
-    once_cache.touch(ent);
-    int st = 0;
-    if (ramp) {
-        // (the README shifts du_min/du_max by u_prev at every step, README.md:543-544: the bounds are per-call data)
-        std::vector<double> rb(du_min, du_min + m);
-        rb.insert(rb.end(), du_max, du_max + m);
-        rc = FMPC_OK;
-        if (rb != ent->ramp) { rc = fmpc_set_ramp(ent->h, du_min, du_max); if (rc == FMPC_OK) ent->ramp = rb; }
-        if (rc == FMPC_OK) rc = fmpc_solve_ramp(ent->h, 1, x0, x0_pre, w, u_prev, x_init, nu0, nw, k, x_opt, nullptr, &st, iters, nullptr);
-    } else {
-        rc = fmpc_solve(ent->h, 1, x0, x0_pre, w, x_init, nu0, nw, k, x_opt, nullptr, &st, iters, nullptr);
-    }
-    return rc;
 }

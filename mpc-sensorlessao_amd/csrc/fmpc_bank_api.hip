@@ -13,7 +13,7 @@
 
 // ---- model bank (include/fastmpc.h; fmpc_bank.h, fmpc_kernel_bank.hip)
 static int fmpc_bank_unsupported(fmpc_handle h, int t) {
-    if (h->ramp_du.p) return 1;                                        // ramp-rate rows: their kernels have no bank form
+    if (h->ramp.du.p) return 1;                                       // ramp-rate rows: their kernels have no bank form
     return fmpc_tiled_supports(h->n, h->m, h->nb, t, nullptr, nullptr, h->hm.denseR) ? 0 : 1;
 }
 extern "C" int fmpc_bank_set_device(fmpc_handle h, int count, const double* A1, const double* A2, void* stream_) {
@@ -60,12 +60,12 @@ extern "C" int fmpc_bank_set_device(fmpc_handle h, int count, const double* A1, 
     B.count = 0;                                                       // (no bank while it is being replaced)
     h->bkf.valid = 0;                                                  // (and no stored factors of the models that leave)
     h->bfm.valid = 0;                                                  // (nor their first-move form)
-    int rc = fmpc_guard_begin(h, stream);                             // (an earlier bank solve may still read the old images)
-    if (rc != FMPC_OK) return rc;
-    rc = B.plain.grow(plain_stride * (size_t)count, stream);
+    FmpcGuard guard(h, stream);                                        // (an earlier bank solve may still read the old images)
+    if (guard.rc != FMPC_OK) return guard.rc;
+    int rc = B.plain.grow(plain_stride * (size_t)count, stream);
     if (rc == FMPC_OK) rc = B.pad.grow(pad_stride * (size_t)count, stream);
     if (rc == FMPC_OK) rc = B.yimg.grow(ybytes, stream);
-    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }      // (the handle is left without a bank)
+    if (rc != FMPC_OK) return rc;                                      // (the handle is left without a bank)
     FbParams Q;
     Q.n = n; Q.NB = NB; Q.count = count; Q.nblk = B.nblk; Q.is_float = t;
     Q.A1 = A1; Q.A2 = h->var_order == 2 ? A2 : nullptr;
@@ -73,7 +73,7 @@ extern "C" int fmpc_bank_set_device(fmpc_handle h, int count, const double* A1, 
     Q.plain = B.plain; Q.plain_stride = plain_stride; Q.pad = B.pad; Q.pad_stride = pad_stride;
     Q.yimg = B.yimg.p; Q.yimg_stride = yimg_stride;
     const bool launched = fmpc_launch_bank_build(Q, stream) == hipSuccess;
-    fmpc_guard_end(h, stream);
+    guard.end();
     if (!launched) return FMPC_E_HIP;
     B.plain_stride = plain_stride; B.pad_stride = pad_stride; B.yimg_stride = yimg_stride;
     B.t = t; B.count = count;
@@ -196,12 +196,11 @@ extern "C" int fmpc_solve_bank_device(fmpc_handle h, int batch, const int* model
     int rc = fmpc_bank_solve_check(h, batch, model_of);
     if (rc != FMPC_OK) return rc;
     FmpcSolve s{batch, x0, x0_pre, w, z_init, nu0, n_newton, k, z_out, nu_out, status, iters, step, u0_out, stream, 0};
-    rc = fmpc_guard_begin(h, stream);
-    if (rc != FMPC_OK) return rc;
+    FmpcGuard guard(h, stream);
+    if (guard.rc != FMPC_OK) return guard.rc;
     FmpcTiledPlan plan;
     rc = fmpc_bank_solve_plan(h, s, &plan);
     if (rc == FMPC_OK) rc = fmpc_bank_solve_launch(h, s, model_of, plan);
-    fmpc_guard_end(h, stream);
     return rc;
 }
 
@@ -220,10 +219,10 @@ extern "C" int fmpc_bank_prefactor_device(fmpc_handle h, double k, void* stream_
     const size_t bytes = stride * (size_t)B.count * (t ? sizeof(float) : sizeof(double));
     if (fmpc_capturing(stream) && (bytes > F.fac.cap || (size_t)B.count > F.flag.cap || !F.prepared[t])) return FMPC_E_ALLOC;
     F.valid = 0;                                                       // (no store while it is being rebuilt)
-    int rc = fmpc_guard_begin(h, stream);                             // (an earlier bank solve may still read the old factors)
-    if (rc != FMPC_OK) return rc;
+    FmpcGuard guard(h, stream);                                        // (an earlier bank solve may still read the old factors)
+    if (guard.rc != FMPC_OK) return guard.rc;
     FmpcTiledPlan plan;
-    rc = fmpc_tiled_plan(h, t, B.count, stream, 0, 0, &plan);
+    int rc = fmpc_tiled_plan(h, t, B.count, stream, 0, 0, &plan);
     if (rc == FMPC_OK) rc = fmpc_scratch_z(h, plan.grid, stream);     // the start point, one per workgroup
     if (rc == FMPC_OK) rc = F.fac.grow(bytes, stream);
     if (rc == FMPC_OK) rc = F.flag.grow((size_t)B.count, stream);
@@ -237,7 +236,6 @@ extern "C" int fmpc_bank_prefactor_device(fmpc_handle h, double k, void* stream_
         P.pf_fac = F.fac.p; P.pf_flag = F.flag; P.pf_stride = stride;
         if (fmpc_launch_bank_prefactor(P, X.NB, plan.NWu, t, plan.grid, plan.ldsu, stream) != hipSuccess) rc = FMPC_E_HIP;
     }
-    fmpc_guard_end(h, stream);
     if (rc != FMPC_OK) return rc;
     F.valid = 1; F.count = B.count; F.t = t; F.k = k; F.stride = stride;
     return FMPC_OK;
@@ -306,9 +304,9 @@ extern "C" int fmpc_bank_first_move_device(fmpc_handle h, double k, void* stream
     if (!fmpc_host_bank_first_constants(n, m, T, k, h->hm.bt.data(), h->hm.umax.data(), h->hm.umin.data(), h->hm.umid.data(),
                                         h->hm.R2.data(), h->hm.rl.data(), cst)) return FMPC_E_UNSUPPORTED;
     F.valid = 0;                                                       // (no form while it is being rebuilt)
-    int rc = fmpc_guard_begin(h, stream);                             // (an earlier loop step may still read the old operands)
-    if (rc != FMPC_OK) return rc;
-    rc = fmpc_tiled_plan(h, 0, grid, stream, 0, 0, &plan);
+    FmpcGuard guard(h, stream);                                        // (an earlier loop step may still read the old operands)
+    if (guard.rc != FMPC_OK) return guard.rc;
+    int rc = fmpc_tiled_plan(h, 0, grid, stream, 0, 0, &plan);
     if (rc == FMPC_OK && plan.grid < grid) grid = plan.grid;
     if (rc == FMPC_OK) rc = fmpc_scratch_z(h, grid, stream);
     if (rc == FMPC_OK) rc = F.ops.grow(stride * (size_t)B.count, stream);
@@ -336,7 +334,6 @@ extern "C" int fmpc_bank_first_move_device(fmpc_handle h, double k, void* stream
         Q.flag = F.flag; Q.cst = F.cst;
         if (fmpc_launch_bank_first_build(P, Q, X.NB, plan.NWu, grid, plan.ldsu, stream) != hipSuccess) rc = FMPC_E_HIP;
     }
-    fmpc_guard_end(h, stream);
     if (rc != FMPC_OK) return rc;
     F.valid = 1; F.count = B.count; F.k = k; F.stride = stride;
     F.oK = oK; F.ou = ou; F.oE = oE; F.oe = oe; F.oEp = oEp; F.oep = oep; F.od = od; F.osc = osc;
@@ -384,11 +381,9 @@ extern "C" int fmpc_loop_inputs_bank_device(fmpc_handle h, int batch, const int*
     const fmpc_handle_s::Bank& B = h->bank;
     if (B.count <= 0 || (!model_of && batch > B.count)) return FMPC_E_UNSUPPORTED;
     // (the bank's images are rewritten in place by fmpc_bank_set_device: ordered against it like the bank solve)
-    int rc = fmpc_guard_begin(h, (hipStream_t)stream);
-    if (rc != FMPC_OK) return rc;
-    rc = fmpc_loop_inputs_bank_launch(h, batch, model_of, a_k, x0_last, u1, u2, x0, x0_pre, w, (hipStream_t)stream);
-    fmpc_guard_end(h, (hipStream_t)stream);
-    return rc;
+    FmpcGuard guard(h, (hipStream_t)stream);
+    if (guard.rc != FMPC_OK) return guard.rc;
+    return fmpc_loop_inputs_bank_launch(h, batch, model_of, a_k, x0_last, u1, u2, x0, x0_pre, w, (hipStream_t)stream);
 }
 
 // One closed-loop step with the bank's models: fmpc_loop_inputs_bank_device + fmpc_solve_bank_device from the cold start under one
@@ -407,8 +402,8 @@ extern "C" int fmpc_loop_step_bank_device(fmpc_handle h, int batch, const int* m
     int rc = fmpc_bank_solve_check(h, batch, model_of);
     if (rc != FMPC_OK) return rc;
     FmpcSolve s{batch, x0, x0_pre, w, nullptr, nu0, n_newton, k, z_out, nu_out, status, iters, step, u0_out, stream, 0};
-    rc = fmpc_guard_begin(h, stream);
-    if (rc != FMPC_OK) return rc;
+    FmpcGuard guard(h, stream);
+    if (guard.rc != FMPC_OK) return guard.rc;
     FmpcTiledPlan plan;
     rc = fmpc_bank_solve_plan(h, s, &plan);
     // the per-model first-move form: first moves only, one Newton step, the k it was built for bit for bit -- and its per-batch
@@ -436,7 +431,6 @@ extern "C" int fmpc_loop_step_bank_device(fmpc_handle h, int batch, const int* m
     } else if (rc == FMPC_OK) {
         rc = fmpc_bank_solve_launch(h, s, model_of, plan);
     }
-    fmpc_guard_end(h, stream);
     return rc;
 }
 
@@ -449,15 +443,9 @@ extern "C" int fmpc_loop_run_bank_device(fmpc_handle h, int batch, int steps, co
     if (!h || !a || !x0 || !x0_pre || !w || !U0) return FMPC_E_NULL;
     if (batch < 0 || steps < 0) return FMPC_E_DIM;
     if (batch == 0 || steps == 0) return FMPC_OK;
-    const size_t sn = (size_t)batch * h->n, sm = (size_t)batch * h->m, snu = (size_t)batch * h->nb * h->n;
-    for (int s = 0; s < steps; ++s) {
-        const double* u1 = s >= 1 ? U0 + (size_t)(s - 1) * sm : u_before1;
-        const double* u2 = s >= 2 ? U0 + (size_t)(s - 2) * sm : (s == 1 ? u_before1 : u_before2);
-        const int rc = fmpc_loop_step_bank_device(h, batch, model_of, a + (size_t)s * sn, (s >= 1 || have_x0_last) ? x0 : nullptr, u1, u2,
-                                                  x0, x0_pre, w, nu0 ? nu0 + (size_t)s * snu : nullptr, n_newton, k, nullptr, nullptr,
-                                                  status, iters, nullptr, U0 + (size_t)s * sm, stream);
-        if (rc != FMPC_OK) return rc;
-        if (X0 && hipMemcpyAsync(X0 + (size_t)s * sn, x0, sn * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return FMPC_E_HIP;
-    }
-    return FMPC_OK;
+    return fmpc_loop_feedback(h, batch, 0, steps, a, nu0, u_before1, u_before2, have_x0_last, x0, U0, X0, (hipStream_t)stream,
+                              [&](const double* a_s, const double* x0_last, const double* u1, const double* u2, const double* nu0_s, double* u0_s) {
+                                  return fmpc_loop_step_bank_device(h, batch, model_of, a_s, x0_last, u1, u2, x0, x0_pre, w, nu0_s, n_newton, k,
+                                                                    nullptr, nullptr, status, iters, nullptr, u0_s, stream);
+                              });
 }

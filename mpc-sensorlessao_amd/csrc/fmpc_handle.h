@@ -1,8 +1,10 @@
 // The solver handle (fmpc_handle of include/fastmpc.h) and what the API files share around it: the arguments of a device solve,
-// the plan of a tiled launch, and the few helpers of fmpc_api.hip that the other API files call (fmpc_bank_api.hip,
-// fmpc_records_api.hip, fmpc_kkt_api.hip).  Internal to the library.
+// the plan of a tiled launch, the scoped guard of a solve's stream order, the feedback loop of a recorded stretch, and the
+// helpers of fmpc_api.hip (the dispatcher) that the other API files call: fmpc_ramp_api.hip, fmpc_loop_api.hip,
+// fmpc_hostcall_api.hip, fmpc_bank_api.hip, fmpc_records_api.hip, fmpc_kkt_api.hip.  Internal to the library.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdlib.h>
 #include <atomic>
 #include <mutex>
 #include <vector>
@@ -124,25 +126,28 @@ struct fmpc_handle_s {
     int small_tiled = 1;                  // per-problem-factor solves of few problems go to the tiled kernel (FMPC_NO_SMALL_TILED=1: off)
     int small_nw = 4;                     // ... with this many wavefronts per problem: 4, the default (round 5), or 2 (FMPC_SMALL_TILED_NW=2 /
                                           // fmpc_set_small_batch_kernel(h, 2))
-    // ramp-rate rows (VAR_1): bounds on the device, own workspace (dense Y per workgroup)
-    DevBuf<double> ramp_du;      // [du_min | du_max], 2 m doubles; empty until fmpc_set_ramp
-    DevBuf<double> ramp_ws;
-    // fmpc_newton_ramp (and the cold-start form) take the handle: n <= 64, their LDS fits, diagonal weights (fmpc_set_ramp);
-    // every other ramp solve, and every one after fmpc_set_ramp_workspace(h, 1), runs fmpc_newton_ramp_ws
-    int ramp_lds_ok = 0, ramp_force_ws = 0;
-    // cold-start step with the ramp rows in its Woodbury form (fmpc_ramp_cold): constants per (handle, k, ramp bounds)
-    std::vector<double> hm_dumin, hm_dumax;
-    int rc_disabled = 0, rc_valid = 0, rc_failed = 0, rc_last = 0; double rc_k = 0.0, rc_failed_k = 0.0;
-    DevBuf<double> rc_pool; FrColdParams rc_P;
-    DevBuf<double> rc_ws;
-    DevBuf<double> rc_nu; DevBuf<int> rc_si; size_t rc_cap = 0;   // nu / status / iters of the first step when the caller passes none (budgets > 1)
+    // ramp-rate rows (VAR_1, fmpc_ramp_api.hip): bounds on the device, own workspace (dense Y per workgroup)
+    struct Ramp {
+        DevBuf<double> du;       // [du_min | du_max], 2 m doubles; empty until fmpc_set_ramp
+        DevBuf<double> ws;
+        // fmpc_newton_ramp (and the cold-start form) take the handle: n <= 64, their LDS fits, diagonal weights (fmpc_set_ramp);
+        // every other ramp solve, and every one after fmpc_set_ramp_workspace(h, 1), runs fmpc_newton_ramp_ws
+        int lds_ok = 0, force_ws = 0;
+        std::vector<double> dumin, dumax;    // the bounds on the host: the cold-start form's constants are built from them
+        // cold-start step with the ramp rows in its Woodbury form (fmpc_ramp_cold): constants per (handle, k, ramp bounds)
+        struct Cold {
+            int disabled = 0, valid = 0, failed = 0, last = 0; double k = 0.0, failed_k = 0.0;   // disabled: FMPC_NO_RAMP_COLD=1
+            DevBuf<double> pool; FrColdParams P;
+            DevBuf<double> ws;
+            DevBuf<double> nu; DevBuf<int> si; size_t cap = 0;   // nu / status / iters of the first step when the caller passes none (budgets > 1)
+        } cold;
+    } ramp;
     // A handle's device workspaces serve ONE solve at a time.  Solves enqueued on different streams are ordered on
     // the device: every solve records `ev`, and a solve on another stream than the last one waits for it first.
     hipEvent_t ev = nullptr; std::atomic<int> ev_valid{0}; std::atomic<hipStream_t> last_stream{nullptr};   // (atomic: a chain of this handle may be
                                          // launched by a call on ANOTHER handle of the same bracketed stream, which does not hold mu)
     // workspace, grown on demand; `mu` serialises the host-side enqueue (a handle may be shared between threads)
     std::mutex mu;
-    std::mutex host_mu;          // serialises the host-pointer entry points (shared staging)
     DevBuf<double> ws;
     // z_out == NULL (first moves only): the working iterate of the problems a kernel has to iterate on lives here
     DevBuf<double> zs;
@@ -152,9 +157,12 @@ struct fmpc_handle_s {
     DevBuf<double> rec_j;
     DevBuf<double> rec_f;                 // the bank's records (fmpc_loop_records_bank_device): f_i of the last call, stages x n per problem
     DevBuf<double> kkt_part;              // KKT report (fmpc_kkt_report_device): per-(stage, problem) partials of the panel kernel's last call
-    // staging for the host-pointer entry points
-    DevBuf<char> stage;
-    PinnedBuf<char> pin; void* pin_dev = nullptr;   // pinned host twin of the staging block for small host-pointer solves (fmpc_solve_host)
+    // staging for the host-pointer entry points (fmpc_hostcall_api.hip)
+    struct HostStage {
+        std::mutex mu;                                  // serialises the host-pointer entry points (shared staging)
+        DevBuf<char> stage;                             // the device block: inputs, then outputs
+        PinnedBuf<char> pin; void* pin_dev = nullptr;   // its pinned host twin for small solves, and that twin as the kernels see it (fmpc_solve_host)
+    } host;
 
     ~fmpc_handle_s() { if (ev) (void)hipEventDestroy(ev); }
 };
@@ -177,6 +185,15 @@ static inline int fmpc_max_iter(const FmpcSolve& s) { return s.n_newton > 0 ? s.
 // What fmpc_tiled_plan settles before anything is enqueued: wavefronts per problem, LDS bytes, grid, workspace doubles per slot
 struct FmpcTiledPlan { int NWu; size_t ldsu; int grid; size_t slot; };
 
+// Environment switches: NAME=1 (first character `c`) switches on, a number is read with atoi (unset or empty: the default)
+static inline bool fmpc_env_on(const char* name, char c = '1') { const char* e = getenv(name); return e && e[0] == c; }
+static inline int fmpc_env_int(const char* name, int dflt) { const char* e = getenv(name); return e && e[0] ? atoi(e) : dflt; }
+
+// Launchers of kernels without a header of their own that more than one API file calls (fmpc_kernel_generic.hip, fmpc_kernel_wave.hip)
+hipError_t fmpc_launch_unpack(int n, int m, int T, int batch, const double* z, double* U,
+                              double* X, double* u0, hipStream_t stream);
+int fmpc_wave_waves_per_wg();
+
 // fmpc_api.hip; the caller holds h->mu
 int fmpc_guard_begin(fmpc_handle h, hipStream_t stream);
 void fmpc_guard_end(fmpc_handle h, hipStream_t stream);
@@ -184,3 +201,52 @@ bool fmpc_capturing(hipStream_t stream);
 int fmpc_scratch_z(fmpc_handle h, int batch, hipStream_t stream);
 int fmpc_tiled_ensure(fmpc_handle h, int t, hipStream_t stream);   // the tiled images of arithmetic t, built if they are not ready
 int fmpc_tiled_plan(fmpc_handle h, int t, int batch, hipStream_t stream, int nw_override, int grid_hint, FmpcTiledPlan* out);
+// ... what the closed-loop calls (fmpc_loop_api.hip) use of the dispatcher: the wave kernel's workspace, the cold-start constants
+// of a k, the builders of the dense dual form and of the first-move form, the exact path in flag mode, the dispatch itself
+int fmpc_ensure_wave_ws(fmpc_handle h, size_t* stride_out, hipStream_t stream);
+int fmpc_ensure_cold(fmpc_handle h, double k, size_t stride, hipStream_t stream);
+int fmpc_build_inverse(fmpc_handle h, double k, hipStream_t stream);
+int fmpc_build_first_move(fmpc_handle h, double k, hipStream_t stream);
+int fmpc_launch_flagged(fmpc_handle h, const FmpcSolve& s, int grid, size_t stride, int* need, int* nflag = nullptr, int zld = 0);
+int fmpc_solve_device_inner(fmpc_handle h, FmpcSolve s);           // s.ldz >= 0
+// fmpc_api.hip, fmpc_ramp_api.hip; they take h->mu themselves (the host-pointer entries of fmpc_hostcall_api.hip end in them)
+int fmpc_solve_device_impl(fmpc_handle h, FmpcSolve s);
+int fmpc_solve_ramp_device_impl(fmpc_handle h, FmpcSolve s, const double* u_prev);
+// fmpc_api.hip; no lock needed.  A library call on `stream` that is no step of a chain: what is pending there comes first
+int fmpc_stretch_flush_stream(hipStream_t stream, fmpc_handle h = nullptr);
+
+// The stream order of one solve as a scope: fmpc_guard_begin when it is made, fmpc_guard_end when it goes (or at end()) if and only
+// if the begin succeeded -- no error path leaves the handle's event unrecorded.  Declare it AFTER the std::lock_guard on h->mu, so
+// that it ends first.  (begin_rc: a begin the caller has made itself; dismiss(): the event is recorded by somebody else.)
+class FmpcGuard {
+public:
+    const int rc;                                                      // what the begin said
+    FmpcGuard(fmpc_handle h, hipStream_t stream) : FmpcGuard(h, stream, fmpc_guard_begin(h, stream)) {}
+    FmpcGuard(fmpc_handle h, hipStream_t stream, int begin_rc) : rc(begin_rc), h_(h), stream_(stream), open_(begin_rc == FMPC_OK) {}
+    FmpcGuard(const FmpcGuard&) = delete;
+    FmpcGuard& operator=(const FmpcGuard&) = delete;
+    ~FmpcGuard() { end(); }
+    void end() { if (open_) { open_ = false; fmpc_guard_end(h_, stream_); } }
+    void dismiss() { open_ = false; }
+private:
+    fmpc_handle h_; hipStream_t stream_; bool open_;
+};
+
+// The feedback loop of a recorded stretch, steps [s_begin, steps): u[k-1], u[k-2] from U0 (before the stretch: the u_before
+// arrays), x0 of the step before as x0_last from step 1 on, nu0 per step, x0 copied to X0 after each step.  `step` is the one-step
+// call: step(a_s, x0_last, u1, u2, nu0_s, u0_s) -> FMPC code.
+template <typename Step>
+static inline int fmpc_loop_feedback(fmpc_handle h, int batch, int s_begin, int steps, const double* a, const double* nu0,
+                                     const double* u_before1, const double* u_before2, int have_x0_last,
+                                     const double* x0, double* U0, double* X0, hipStream_t stream, Step step) {
+    const size_t sn = (size_t)batch * h->n, sm = (size_t)batch * h->m, snu = (size_t)batch * h->nb * h->n;
+    for (int s = s_begin; s < steps; ++s) {
+        const double* u1 = s >= 1 ? U0 + (size_t)(s - 1) * sm : u_before1;
+        const double* u2 = s >= 2 ? U0 + (size_t)(s - 2) * sm : (s == 1 ? u_before1 : u_before2);
+        const int rc = step(a + (size_t)s * sn, (s >= 1 || have_x0_last) ? x0 : nullptr, u1, u2, nu0 ? nu0 + (size_t)s * snu : nullptr,
+                            U0 + (size_t)s * sm);
+        if (rc != FMPC_OK) return rc;
+        if (X0 && hipMemcpyAsync(X0 + (size_t)s * sn, x0, sn * sizeof(double), hipMemcpyDeviceToDevice, stream) != hipSuccess) return FMPC_E_HIP;
+    }
+    return FMPC_OK;
+}

@@ -35,27 +35,26 @@ static int fmpc_kkt_args(fmpc_handle h, int batch, const double* x0, const doubl
 // its lock and stream order, the model's pointers, the launch.  The bank form reads A1, A2 of model model_of[p] from the bank's
 // fp64 plain images and is ordered on the device with the bank calls.
 static int fmpc_kkt_run(fmpc_handle h, KktParams& P, int bank, const int* model_of, hipStream_t stream) {
-    if (P.u_prev && (bank || !h->ramp_du.p)) return FMPC_E_UNSUPPORTED;
+    if (P.u_prev && (bank || !h->ramp.du.p)) return FMPC_E_UNSUPPORTED;
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
     std::lock_guard<std::mutex> lock(h->mu);
     const fmpc_handle_s::Bank& B = h->bank;
     if (bank && (B.count <= 0 || (!model_of && P.batch > B.count))) return FMPC_E_UNSUPPORTED;
-    int rc = fmpc_guard_begin(h, stream);
-    if (rc != FMPC_OK) return rc;
+    FmpcGuard guard(h, stream);
+    if (guard.rc != FMPC_OK) return guard.rc;
+    int rc = FMPC_OK;
     const FmpcDevModel& D = h->dev;
     const int panel = !bank && !P.u_prev && h->n <= KKT_NMAX && !D.denseQ && !D.denseR;
     if (panel) rc = h->kkt_part.grow((size_t)KKT_PARTS * h->T * P.batch, stream);      // (FMPC_E_ALLOC while the stream is being captured)
-    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
+    if (rc != FMPC_OK) return rc;
     P.n = h->n; P.m = h->m; P.T = h->T; P.has_xf = h->has_xf; P.var2 = h->var_order == 2; P.denseQ = D.denseQ; P.denseR = D.denseR;
     P.A1 = D.A1; P.A2 = D.A2; P.A1t = D.A1t; P.A2t = D.A2t; P.Bt = D.Bt;
     P.R2 = D.R2; P.Q2 = D.Q2; P.Qf2 = D.Qf2; P.Q2m = D.Q2m; P.Qf2m = D.Qf2m; P.R2m = D.R2m;
     P.rl = D.rl; P.ql = D.ql; P.qfl = D.qfl; P.umin = D.umin; P.umax = D.umax; P.xf = D.xf;
-    if (P.u_prev) { P.dumin = h->ramp_du; P.dumax = h->ramp_du + h->m; }
+    if (P.u_prev) { P.dumin = h->ramp.du; P.dumax = h->ramp.du + h->m; }
     P.bank = bank; P.count = B.count; P.plain = B.plain; P.plain_stride = B.plain_stride; P.model_of = model_of;
     P.part = panel ? (double*)h->kkt_part : nullptr;
-    const bool ok = fmpc_launch_kkt(P, panel, stream) == hipSuccess;
-    fmpc_guard_end(h, stream);
-    return ok ? FMPC_OK : FMPC_E_HIP;
+    return fmpc_launch_kkt(P, panel, stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
 extern "C" int fmpc_kkt_report_device(fmpc_handle h, int batch,

@@ -1,8 +1,15 @@
-// Cold-start Newton step WITH the ramp-rate rows in its Woodbury form (fmpc_ramp_cold, fmpc_kernel_ramp.hip; constants built by
-// fmpc_host_build_ramp_cold, fmpc_host.h).  Internal to the library.
+// Launchers of the ramp-rate kernels (fmpc_kernel_ramp.hip): the Newton kernels (FrParams, fmpc_device.h) and the cold-start Newton
+// step WITH the ramp-rate rows in its Woodbury form (fmpc_ramp_cold; constants built by fmpc_host_build_ramp_cold, fmpc_host.h).
+// Internal to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "fmpc_device.h"
+
+// ws = 0: fmpc_newton_ramp, 1: fmpc_newton_ramp_ws
+size_t fmpc_ramp_lds_bytes(int n, int m, int nb, int ws);
+size_t fmpc_ramp_ws_doubles(int n, int m, int T, int nb, int ws, int dense_r);
+hipError_t fmpc_ramp_prepare(int ws, size_t lds_bytes);
+hipError_t fmpc_launch_ramp(const FrParams& P, int grid, hipStream_t stream);
 
 struct FrColdParams {
     FmpcDevModel M;

@@ -38,7 +38,7 @@ static int fmpc_ensure_records(fmpc_handle h, hipStream_t stream) {
     return FMPC_OK;
 }
 
-// What both forms need between fmpc_guard_begin and the launch (h->mu held): the weights, the partial-cost scratch of the panel
+// What both forms need between the guard's begin and the launch (h->mu held): the weights, the partial-cost scratch of the panel
 // kernel, and the handle's part of the parameter block.
 static int fmpc_records_prepare(fmpc_handle h, RecParams& P, hipStream_t stream) {
     int rc = fmpc_ensure_records(h, stream);
@@ -54,14 +54,12 @@ static int fmpc_records_prepare(fmpc_handle h, RecParams& P, hipStream_t stream)
 static int fmpc_records_launch(fmpc_handle h, RecParams& P, hipStream_t stream) {
     if (hipSetDevice(h->device) != hipSuccess) return FMPC_E_HIP;
     std::lock_guard<std::mutex> lock(h->mu);
-    int rc = fmpc_guard_begin(h, stream);
+    FmpcGuard guard(h, stream);
+    if (guard.rc != FMPC_OK) return guard.rc;
+    const int rc = fmpc_records_prepare(h, P, stream);
     if (rc != FMPC_OK) return rc;
-    rc = fmpc_records_prepare(h, P, stream);
-    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
     P.M1 = h->loop_M1; P.M2 = h->loop_M2;
-    const bool ok = fmpc_launch_loop_records(P, h->rec_panel, stream) == hipSuccess;
-    fmpc_guard_end(h, stream);
-    return ok ? FMPC_OK : FMPC_E_HIP;
+    return fmpc_launch_loop_records(P, h->rec_panel, stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
 // The argument rules and the parameter block of the records of a timestep, for the shared-model call and the bank's: every rule
@@ -141,17 +139,15 @@ static int fmpc_records_bank_launch(fmpc_handle h, RecBankParams& K, const int* 
     const fmpc_handle_s::Bank& B = h->bank;
     RecParams& P = K.R;
     if (B.count <= 0 || (!model_of && P.batch > B.count)) return FMPC_E_UNSUPPORTED;
-    int rc = fmpc_guard_begin(h, stream);
-    if (rc != FMPC_OK) return rc;
-    rc = fmpc_records_prepare(h, P, stream);
+    FmpcGuard guard(h, stream);
+    if (guard.rc != FMPC_OK) return guard.rc;
+    int rc = fmpc_records_prepare(h, P, stream);
     if (rc == FMPC_OK && h->rec_panel && P.steps == 0) rc = h->rec_f.grow((size_t)P.stages * P.batch * h->n, stream);
-    if (rc != FMPC_OK) { fmpc_guard_end(h, stream); return rc; }
+    if (rc != FMPC_OK) return rc;
     K.plain = B.plain; K.plain_stride = B.plain_stride; K.count = B.count; K.var2 = h->var_order == 2;
     K.model_of = model_of;
     K.F = (h->rec_panel && P.steps == 0) ? (double*)h->rec_f : nullptr;
-    const bool ok = fmpc_launch_loop_records_bank(K, h->rec_panel, stream) == hipSuccess;
-    fmpc_guard_end(h, stream);
-    return ok ? FMPC_OK : FMPC_E_HIP;
+    return fmpc_launch_loop_records_bank(K, h->rec_panel, stream) == hipSuccess ? FMPC_OK : FMPC_E_HIP;
 }
 
 extern "C" int fmpc_loop_records_bank_device(fmpc_handle h, int batch, const int* model_of, int stages,

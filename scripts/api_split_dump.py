@@ -1,6 +1,6 @@
 """The calls whose host-built constants or entry points moved out of csrc/fmpc_api.hip (fmpc_handle.h, fmpc_bank_api.hip,
-fmpc_records_api.hip, fmpc_kkt_api.hip, the host arithmetic in fmpc_host.cpp), dumped so that two builds of the library can be
-compared BITWISE:
+fmpc_records_api.hip, fmpc_kkt_api.hip, fmpc_ramp_api.hip, fmpc_hostcall_api.hip, fmpc_loop_api.hip, the host arithmetic in
+fmpc_host.cpp), dumped so that two builds of the library can be compared BITWISE:
 
     FMPC_LIB=/path/to/older/libfastmpc.so python scripts/api_split_dump.py dump old.npz
     python scripts/api_split_dump.py dump new.npz
@@ -14,6 +14,18 @@ Cases, at the smallest sizes that reach the code, on seeded inputs:
      solve; the two counts and fmpc_last_bank_first_move go into the dump
   3  (8,5,6) VAR(2) and VAR(1), batch 17, dense Q, Qf, R: fmpc_solve_device (fmpc_host_spd_inverse, fmpc_host_is_diag)
   4  (8,5,6): the records of a timestep and a KKT report, with the shared model and with a bank
+  5  (8,5,6) VAR(1) batch 17 with ramp rows, in the LDS form and after fmpc_set_ramp_workspace(h, 1): cold start and z_init, budgets
+     1 and 3, through fmpc_solve_ramp_device and through fmpc_solve_ramp_u0_device with z_out = NULL
+  6  (27,144,2) VAR(1) batch 3 with ramp rows: the cold-start step in its Woodbury form, budgets 1 and 3 without nu_out, status and
+     iters (the handle's scratch arrays), then at a second k (the constants are rebuilt)
+  7  (8,5,6) host pointers: fmpc_solve, fmpc_solve_u0, fmpc_solve_ramp at batch 3 (the kernels work on the pinned block), 512 (pinned
+     staging) and 2048 (blocking copies), budget 1 cold and budget 3 from a z_init with one problem outside its box, and with a NaN
+     state in one problem (its status < 0 comes back as the call's); fmpc_unpack
+  8  fmpc_solve_once: the same model twice (miss, hit), five more models (the first leaves the cache), the first again; VAR(1) with
+     two sets of ramp bounds; fmpc_solve_once_cache_clear
+  9  (27,144,2): fmpc_ao_step_device at batch 3; fmpc_loop_step_device with first moves only at batch 80 (the product form: one
+     launch, and three when x0_last is x0); fmpc_loop_run_device over 4 steps at batch 3 with budget 1 (the walk) and 2 (step by
+     step); fmpc_loop_run_bank_device over 4 steps on a bank of 3 models
 One MI355X.  Every dump is a fresh process."""
 import importlib
 import os
@@ -135,6 +147,153 @@ def dump(path):
     keep("kkt", report=rep, flags=fl)
     rep, fl = h.kkt_report_bank_device(x0, x0p, w, z=z, nu=nu, k=K, model_of=model_of)
     keep("kkt_bank", report=rep, flags=fl)
+    h.close()
+
+    import ctypes as C
+    lib = pkg.load()
+    vp = lambda v: None if v is None else C.c_void_p(v.data_ptr())
+    hp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    stream = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    K2 = 3e-2
+
+    def ramp_problem(n, m, T, R, seed):
+        """VAR(1) model with symmetric ramp bounds, a batch of R problems and previous moves inside the box"""
+        md = pkg.synthetic.make_model(n, m, T, var_order=1)
+        rng = np.random.default_rng(seed)
+        du = 0.25 * (md["u_max"] - md["u_min"])
+        x0, w, nu0 = (rng.standard_normal(s) for s in ((R, n), (R, T * n), (R, T * n)))
+        return md, du, x0, 0.1 * w, np.abs(nu0), 0.2 * du * rng.uniform(-1.0, 1.0, (R, m))
+
+    # ---- 5: ramp rows, the LDS form and the workspace form (fmpc_ramp_api.hip)
+    n, m, T, R = 8, 5, 6, 17
+    md, du, x0, w, nu0, up = ramp_problem(n, m, T, R, 60)
+    x0, w, nu0, up = t(x0), t(w), t(nu0), t(up)
+    h = handle_from_model(pkg, md)
+    h.set_ramp(-du, du)
+    z_first = None
+    for form in ("lds", "ws"):
+        if form == "ws":
+            h.set_ramp_workspace(True)
+        for start in ("cold", "warm"):
+            for nn in (1, 3):
+                st, it, nuo = ints(R), ints(R), empty(R, T * n)
+                z, _, _ = h.solve_device(x0, None, w, z_first if start == "warm" else None, nu0, nn, K, nu_out=nuo, status=st, iters=it, u_prev=up)
+                keep(f"ramp_{form}_{start}{nn}", z=z, nu=nuo, status=st, iters=it, dispatch=h.last_dispatch(), dual=h.last_dual_form())
+                if z_first is None:
+                    z_first = z.clone()
+                u0, st, it = empty(R, m), ints(R), ints(R)
+                h.solve_device(x0, None, w, z_first if start == "warm" else None, nu0, nn, K, status=st, iters=it, u_prev=up, u0_out=u0, want_z=False)
+                keep(f"ramp_{form}_{start}{nn}_u0", u0=u0, status=st, iters=it, dispatch=h.last_dispatch(), dual=h.last_dual_form())
+    h.close()
+
+    # ---- 6: ramp rows, the cold-start step in its Woodbury form at configs[0]'s width; budget 3 without nu_out / status / iters
+    n, m, T, R = 27, 144, 2, 3
+    md, du, x0, w, nu0, up = ramp_problem(n, m, T, R, 61)
+    x0, w, nu0, up = t(x0), t(w), t(nu0), t(up)
+    h = handle_from_model(pkg, md)
+    h.set_ramp(-du, du)
+    for kk, ktag in ((K, "k1"), (K2, "k2")):
+        for nn in (1, 3):
+            z, u0 = empty(R, T * (n + m)), empty(R, m)
+            rc = lib.fmpc_solve_ramp_u0_device(h._h, R, vp(x0), None, vp(w), vp(up), None, vp(nu0), nn, kk, vp(z), None, None, None, None, vp(u0), stream())
+            keep(f"rampcold_{ktag}_n{nn}", rc=rc, z=z, u0=u0, dispatch=h.last_dispatch(), dual=h.last_dual_form())
+    h.close()
+
+    # ---- 7: host-pointer calls (fmpc_hostcall_api.hip): zero-copy, pinned and unpinned staging; fmpc_unpack
+    n, m, T = 8, 5, 6
+    md2 = pkg.synthetic.make_model(n, m, T)
+    md1, du, *_ = ramp_problem(n, m, T, 1, 62)
+    h2, h1 = handle_from_model(pkg, md2), handle_from_model(pkg, md1)
+    h1.set_ramp(-du, du)
+    for R in (3, 512, 2048):
+        rng = np.random.default_rng(70 + R)
+        x0, x0p, w, nu0 = (rng.standard_normal(s) for s in ((R, n), (R, n), (R, T * n), (R, T * n)))
+        w *= 0.1
+        up = 0.2 * du * rng.uniform(-1.0, 1.0, (R, m))
+        z_cold, info = h2.solve(x0, x0p, w, nu0=nu0, n_newton=1, k=K, return_info=True, check=False)
+        out.update({f"host{R}_cold_{k}": np.asarray(v) for k, v in info.items()})
+        keep(f"host{R}_cold", z=z_cold, dispatch=h2.last_dispatch(), dual=h2.last_dual_form())
+        if R == 3:
+            U, X, u0 = h2.unpack(z_cold)
+            keep("host_unpack", U=U, X=X, u0=u0)
+        zi = z_cold.copy()
+        zi[1, 0] = 2.0 * md2["u_max"][0]                                # one problem started outside its box: worst status is not FMPC_OK
+        z, info = h2.solve(x0, x0p, w, z_init=zi, nu0=nu0, n_newton=3, k=K, return_info=True, check=False)
+        out.update({f"host{R}_warm_{k}": np.asarray(v) for k, v in info.items()})
+        keep(f"host{R}_warm", z=z, dispatch=h2.last_dispatch())
+        xn = x0.copy()
+        xn[1, 2] = np.nan                                               # (that start is still solved: a NaN state makes a status < 0 for certain)
+        z, info = h2.solve(xn, x0p, w, nu0=nu0, n_newton=2, k=K, return_info=True, check=False)
+        out.update({f"host{R}_nan_{k}": np.asarray(v) for k, v in info.items()})
+        keep(f"host{R}_nan", z=z, dispatch=h2.last_dispatch())
+        for nn, zin in ((1, None), (3, zi)):
+            u0, info = h2.solve_u0(x0, x0p, w, z_init=zin, nu0=nu0, n_newton=nn, k=K, return_info=True, check=False)
+            out.update({f"host{R}_u0_n{nn}_{k}": np.asarray(v) for k, v in info.items()})
+            keep(f"host{R}_u0_n{nn}", u0=u0, dispatch=h2.last_dispatch())
+            z, info = h1.solve(x0, None, w, z_init=zin, nu0=nu0, n_newton=nn, k=K, return_info=True, check=False, u_prev=up)
+            out.update({f"host{R}_ramp_n{nn}_{k}": np.asarray(v) for k, v in info.items()})
+            keep(f"host{R}_ramp_n{nn}", z=z, dispatch=h1.last_dispatch(), dual=h1.last_dual_form())
+    h2.close(); h1.close()
+
+    # ---- 8: fmpc_solve_once: miss, hit, five more models (the first is evicted), the first again; VAR(1) with two sets of ramp bounds
+    F = lambda M: np.asfortranarray(M).ravel(order="K").copy()
+    lib.fmpc_solve_once_cache_clear()
+    rng = np.random.default_rng(80)
+    x0, x0p, w, nu0 = (rng.standard_normal(s) for s in ((n,), (n,), (T * n,), (T * n,)))
+    w *= 0.1
+
+    def once(tag, md, var, du_min=None, du_max=None, u_prev=None):
+        z = np.full(T * (n + m), np.nan); it = C.c_int(-7)
+        a = [F(md["Q"]), F(md["R"]), F(md["Qf"]), md["x_min"], md["x_max"], md["u_min"], md["u_max"], F(md["A1"]), F(md["A2"]), F(md["B"])]
+        rc = lib.fmpc_solve_once(n, m, T, var, hp(a[0]), hp(a[1]), None, hp(a[2]), None, None, None, hp(a[3]), hp(a[4]), hp(a[5]), hp(a[6]),
+                                 hp(du_min), hp(du_max), hp(x0), hp(x0p), hp(u_prev), hp(a[7]), hp(a[8]) if var == 2 else None, hp(a[9]),
+                                 hp(w), None, None, hp(nu0), 3, K, 0, hp(z), C.byref(it))
+        keep(tag, rc=rc, z=z, iters=it.value)
+
+    for call, i in enumerate((0, 0, 1, 2, 3, 4, 5, 0)):
+        mdi = dict(md2)
+        mdi["A1"] = md2["A1"] * (1.0 - 0.01 * i)
+        once(f"once_v2_call{call}_model{i}", mdi, 2)
+    up1 = 0.2 * du * rng.uniform(-1.0, 1.0, m)
+    once("once_v1_a", md1, 1, -du, du, up1)
+    once("once_v1_b", md1, 1, -0.5 * du, 0.75 * du, up1)
+    lib.fmpc_solve_once_cache_clear()
+
+    # ---- 9: closed loop (fmpc_loop_api.hip): the step with the estimator's x0, the product forms, recorded stretches, the bank's stretch
+    n, m, T = 27, 144, 2
+    md = pkg.synthetic.make_model(n, m, T)
+    h = handle_from_model(pkg, md)
+    R = 3
+    rng = np.random.default_rng(90)
+    x0, x0p, u1, u2 = (t(rng.standard_normal(s)) for s in ((R, n), (R, n), (R, m), (R, m)))
+    nu0 = t(rng.uniform(0.0, 1.0, (R, T * n)))
+    for tag, want_z in (("ao_u0", False), ("ao_z", True)):
+        lw, u0, st, it = empty(R, T * n), empty(R, m), ints(R), ints(R)
+        zl = empty(R, T * (n + m)) if want_z else None
+        rc = lib.fmpc_ao_step_device(h._h, R, vp(x0), vp(x0p), vp(u1), vp(u2), vp(lw), vp(nu0), 1, K, vp(zl), None, vp(st), vp(it), None, vp(u0), stream())
+        keep(tag, rc=rc, w=lw, u0=u0, status=st, iters=it, dispatch=h.last_dispatch(), dual=h.last_dual_form(), **({"z": zl} if want_z else {}))
+    R = 80                                                               # >= fs_min_batch 65: the product form
+    a_k, xl, u1, u2 = (t(rng.standard_normal(s)) for s in ((R, n), (R, n), (R, m), (R, m)))
+    nu0 = t(rng.uniform(0.0, 1.0, (R, T * n)))
+    for tag, alias in (("loop80_fused", False), ("loop80_inplace", True)):
+        lx0, lx0p, lw, u0, st, it = xl.clone(), empty(R, n), empty(R, T * n), empty(R, m), ints(R), ints(R)
+        h.loop_step_device(a_k, lx0 if alias else xl, u1, u2, lx0, lx0p, lw, nu0=nu0, n_newton=1, k=K, status=st, iters=it, u0_out=u0)
+        keep(tag, x0=lx0, x0_pre=lx0p, w=lw, u0=u0, status=st, iters=it, dispatch=h.last_dispatch(), dual=h.last_dual_form())
+    R, S = 3, 4
+    a = t(0.3 * rng.standard_normal((S, R, n)))
+    nu0 = t(rng.uniform(0.0, 1.0, (S, R, T * n)))
+    ub1, ub2 = t(0.1 * rng.standard_normal((R, m))), t(0.1 * rng.standard_normal((R, m)))
+    for tag, nn in (("run_walk", 1), ("run_stepwise", 2)):
+        lx0, lx0p, lw, U0, X0, st, it = empty(R, n), empty(R, n), empty(R, T * n), empty(S, R, m), empty(S, R, n), ints(R), ints(R)
+        rc = lib.fmpc_loop_run_device(h._h, R, S, vp(a), vp(nu0), vp(ub1), vp(ub2), 0, nn, K, vp(lx0), vp(lx0p), vp(lw), vp(U0), vp(X0),
+                                      vp(st), vp(it), stream())
+        keep(tag, rc=rc, U0=U0, X0=X0, x0=lx0, x0_pre=lx0p, w=lw, status=st, iters=it, dispatch=h.last_dispatch(), dual=h.last_dual_form())
+    A1, A2 = bank_models(md, 3)
+    h.set_model_bank(t(A1), t(A2))
+    model_of = t(np.arange(R) % 3, np.int32)
+    lx0, lx0p, lw, U0, X0, st, it = empty(R, n), empty(R, n), empty(R, T * n), empty(S, R, m), empty(S, R, n), ints(R), ints(R)
+    h.loop_run_bank(a, lx0, lx0p, lw, U0, X0, nu0, ub1, ub2, False, 1, K, model_of=model_of, status=st, iters=it)
+    keep("run_bank", U0=U0, X0=X0, x0=lx0, x0_pre=lx0p, w=lw, status=st, iters=it, dispatch=h.last_dispatch(), dual=h.last_dual_form())
     h.close()
 
     np.savez(path, **out)
