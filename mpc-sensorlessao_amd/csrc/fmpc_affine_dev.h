@@ -1,9 +1,7 @@
-// Device code of the affine cold-start step as fmpc_kernel_affine_nu.hip uses it: operand requests with counted waits, the staging of
-// a group's data, the decision forms.  A COPY of what fmpc_kernel_affine.hip does inline, with one difference: fa_stage makes its
-// zero per step (see there).  That file keeps its own text: its instances serve the first-moves-only calls and
-// FMPC_AFFINE_DIRECT=1, and taking these functions from here changes their register allocation (214 against 213 VGPRs), which the
-// measurements in DESIGN.md section 7 are pinned to.  The decision (fa_forms, fa_decide) must stay the same in both: whoever edits
-// one edits the other; tests/test_gpu_affine_nu.py compares status, iterations and step lengths of the two kernels.
+// Device code that the two kernels of the affine cold-start step share (fmpc_cold_affine in fmpc_kernel_affine.hip, fmpc_cold_nu in
+// fmpc_kernel_affine_nu.hip): operand requests with counted waits, the staging of a group's data in operand order, the decision
+// forms and the exit / step-length decision with its rounding guard.  tests/test_gpu_affine_nu.py compares status, iterations and
+// step lengths of the two kernels.
 // Internal to the library; include from a .hip file only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -76,6 +74,8 @@ __device__ __forceinline__ bool fa_decide(const FaParams& P, double qe, double q
 // entry (problem 16 ct + cc, k) of the group's data in OPERAND order (fa_stage)
 #define FA_SD(ct, cc, k) sD[((((k) >> 2) * FA_CT + (ct)) * 4 + ((k) & 3)) * 16 + (cc)]
 // The group's data (x0, x0_pre of the problems p0 .. p0 + 63, the constant 1) into sD[FA_KS FA_CT 64]; the caller puts a barrier behind it
+// FRESH_ZERO keeps each kernel's code as it was: fmpc_cold_nu makes the zero of the last column per step, fmpc_cold_affine takes a plain 0.0
+template <bool FRESH_ZERO>
 __device__ __forceinline__ void fa_stage(double* sD, const FaParams& P, const double* x0_s, const double* x0p_s, int p0, int tid) {
     constexpr int n = FA_N;                                          // (a constant: the staging's idx / n is no run-time division)
     const int np = P.batch - p0 < FA_CT * 16 ? P.batch - p0 : FA_CT * 16;       // problems of this group
@@ -97,9 +97,9 @@ __device__ __forceinline__ void fa_stage(double* sD, const FaParams& P, const do
             FA_SD(pr >> 4, pr & 15, n + k) = (on && x0p_s) ? v1[j] : 0.0;
         }
     }
-    // (the zero is made here: taken from a register pair set up in front of the step loop it is held through the whole product)
+    // (FRESH_ZERO: the zero is made here; taken from a register pair set up in front of the step loop it is held through the whole product)
     double zero = 0.0;
-    asm volatile("" : "+v"(zero));
+    if constexpr (FRESH_ZERO) asm volatile("" : "+v"(zero));
     if (tid < FA_CT * 16) { FA_SD(tid >> 4, tid & 15, 2 * n) = 1.0; FA_SD(tid >> 4, tid & 15, 2 * n + 1) = zero; }
 }
 

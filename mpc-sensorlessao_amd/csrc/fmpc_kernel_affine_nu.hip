@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(FA_THREADS, 2) fmpc_cold_nu(FaParams P) {
     int* const status_s = S.status; int* const iters_s = S.iters; double* const step_s = S.step; int* const need_s = S.need;
     // (no wavefront of the workgroup reads sD / sF of the previous step any more when the staging below overwrites them)
     if (s != s_begin) __syncthreads();
-    fa_stage(sD, P, x0_s, x0p_s, p0, tid);
+    fa_stage<true>(sD, P, x0_s, x0p_s, p0, tid);
     __syncthreads();
     FA_TICK(1);
     fa_forms(sD, sF, P, slot, wv, tid & 63, p0, nu0_s, need_s, status_s, iters_s, step_s);

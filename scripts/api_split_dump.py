@@ -26,6 +26,9 @@ Cases, at the smallest sizes that reach the code, on seeded inputs:
   9  (27,144,2): fmpc_ao_step_device at batch 3; fmpc_loop_step_device with first moves only at batch 80 (the product form: one
      launch, and three when x0_last is x0); fmpc_loop_run_device over 4 steps at batch 3 with budget 1 (the walk) and 2 (step by
      step); fmpc_loop_run_bank_device over 4 steps on a bank of 3 models
+ 10  (27,144,2) batch 70 and (27,144,30) batch 90, the affine cold-start step on fmpc_cold_affine (csrc/fmpc_kernel_affine.hip and the
+     device code it shares with fmpc_cold_nu, fmpc_affine_dev.h): z + u0 with FMPC_AFFINE_DIRECT=1 on contiguous and on padded rows
+     (fmpc_set_z_ld), the same with nu_out, first moves only, and a recorded stretch of 5 steps; the whole padded buffers go into the dump
 One MI355X.  Every dump is a fresh process."""
 import importlib
 import os
@@ -295,6 +298,46 @@ def dump(path):
     h.loop_run_bank(a, lx0, lx0p, lw, U0, X0, nu0, ub1, ub2, False, 1, K, model_of=model_of, status=st, iters=it)
     keep("run_bank", U0=U0, X0=X0, x0=lx0, x0_pre=lx0p, w=lw, status=st, iters=it, dispatch=h.last_dispatch(), dual=h.last_dual_form())
     h.close()
+
+    # ---- 10: the affine cold-start step on fmpc_cold_affine (FMPC_AFFINE_DIRECT=1 is read at every launch; first moves only run it anyway)
+    n, m = 27, 144
+    for T, R in ((2, 70), (30, 90)):
+        md = pkg.synthetic.make_model(n, m, T)
+        d = pkg.synthetic.make_replay_batch(md, r=95, steps=R)
+        x0, x0p, nu0 = t(d["x0"]), t(d["x0_pre"]), t(d["nu0"])
+        h = handle_from_model(pkg, md)
+        ldp = (h.nz + 15) // 16 * 16
+
+        def rows(padded):
+            big = torch.full((R, ldp if padded else h.nz), -7.0, dtype=torch.float64, device=dev)
+            return big, big[:, :h.nz]
+
+        os.environ["FMPC_AFFINE_DIRECT"] = "1"
+        for padded in (False, True):
+            for want_nu in (False, True):
+                big, z = rows(padded)
+                u0, st, it, stp = empty(R, m), ints(R), ints(R), empty(R, 1)
+                nuo = empty(R, h.nu_len) if want_nu else None
+                h.solve_device(x0, x0p, None, None, nu0, 1, K, z_out=z, nu_out=nuo, status=st, iters=it, step=stp, u0_out=u0)
+                keep(f"aff_T{T}_direct_pad{int(padded)}_nu{int(want_nu)}", big=big, u0=u0, status=st, iters=it, step=stp, dispatch=h.last_dispatch(),
+                     dual=h.last_dual_form(), **({"nu": nuo} if want_nu else {}))
+        u0, st, it, stp = empty(R, m), ints(R), ints(R), empty(R, 1)
+        h.solve_device(x0, x0p, None, None, nu0, 1, K, status=st, iters=it, step=stp, u0_out=u0, want_z=False)
+        keep(f"aff_T{T}_u0_only", u0=u0, status=st, iters=it, step=stp, dispatch=h.last_dispatch(), dual=h.last_dual_form())
+        sets = []
+        for i in range(5):                                               # a recorded stretch of 5 steps on distinct padded buffers
+            di = pkg.synthetic.make_replay_batch(md, r=96 + i, steps=R)
+            big, z = rows(True)
+            sets.append(dict(x0=t(di["x0"]), x0p=t(di["x0_pre"]), nu0=t(di["nu0"]), big=big, z=z, u0=empty(R, m), st=ints(R), it=ints(R), stp=empty(R, 1)))
+        assert lib.fmpc_stretch_begin(stream()) == pkg._lib.FMPC_OK
+        for s in sets:
+            h.solve_device(s["x0"], s["x0p"], None, None, s["nu0"], 1, K, z_out=s["z"], status=s["st"], iters=s["it"], step=s["stp"], u0_out=s["u0"])
+        assert lib.fmpc_stretch_end(stream()) == pkg._lib.FMPC_OK
+        for i, s in enumerate(sets):
+            keep(f"aff_T{T}_stretch{i}", big=s["big"], u0=s["u0"], status=s["st"], iters=s["it"], step=s["stp"])
+        keep(f"aff_T{T}_stretch", last=h.last_stretch())
+        del os.environ["FMPC_AFFINE_DIRECT"]
+        h.close()
 
     np.savez(path, **out)
     print("dumped", len(out), "arrays to", path, "from", pkg._lib.LIB_PATH)

@@ -10,7 +10,8 @@ the block boundary on both sides); T = 30 once at batch 90 (the other residues, 
 (one column tile), 90 (a full group and a partial one: both store paths of the u tiles) and 2000 once (two parts per item); terminal
 row on and off, VAR(1), nu_out on and off, padded and contiguous rows.  Between themselves the forms of the new kernel are bit for
 bit equal: a chain of 1, 2, 5, 16 steps and per-step calls, 4 lanes and one, padded and contiguous rows, with and without nu_out,
-the first-moves-only call and z[:, :m]."""
+the first-moves-only call and z[:, :m].  T = 2 at batch 8256 once: at most 3 workgroups per group, where a workgroup evaluates the
+decision forms of two column tiles in turn."""
 import numpy as np
 import pytest
 
@@ -87,6 +88,48 @@ def test_u_rows_through_nu_match_the_direct_product(pkg, gpu, monkeypatch, T, ba
             assert np.array_equal(b["nu"], dn["nu"])
     uo = _run(h, t, batch, gpu, want_z=False)
     assert np.array_equal(uo["u0"], a["u0"]) and np.array_equal(uo["st"], a["st"]) and np.array_equal(uo["it"], a["it"])
+    h.close()
+
+
+def test_a_workgroup_with_two_column_tiles_of_decision_forms(pkg, gpu, monkeypatch):
+    """At most 3 workgroups per group: one workgroup evaluates the decision forms of two column tiles in turn (fa_forms walks
+    fct = wpg - 1 - slot, += wpg) and reuses sF behind the barrier -- in a call that WRITES z through fmpc_cold_affine<true, .>.
+    (27, 144, 2) at batch 8256: 129 groups on the 512 workgroup slots of 256 compute units.  Both kernels decide alike; z within
+    the bar of test_u_rows_through_nu_match_the_direct_product; the first-moves-only call is bit for bit the direct call's z[:, :m].
+    Measured on an MI355X: no problem handed to the exact path, worst rel_err of z 9.3e-16."""
+    import torch
+    from tests.test_host_lane_plan import plan
+    T, batch = 2, 8256
+    md = pkg.synthetic.make_model(27, 144, T)
+    h = handle_from_model(pkg, md)
+    ngroups = (batch + 63) // 64
+    slots = 2 * torch.cuda.get_device_properties(gpu).multi_processor_count
+    for tiles in ((h.nz + 15) // 16, (h.m + 15) // 16):               # the call that writes z, the first-moves-only call
+        lanes, wpg, _ = plan([0], ngroups, slots, tiles, cap=1)
+        assert lanes == 1 and wpg <= 3, (lanes, wpg, slots)
+    data = pkg.synthetic.make_replay_batch(md, r=7, steps=batch)
+    scale = np.linspace(0.5, 50.0, batch)[:, None]                  # (measured: every problem is accepted at t = 1, z is the affine kernels')
+    data["x0"] = data["x0"] * scale; data["x0_pre"] = data["x0_pre"] * scale
+    data["w"] = None
+    t = {k: (None if v is None else torch.from_numpy(np.ascontiguousarray(v)).to(gpu)) for k, v in data.items()}
+    monkeypatch.delenv("FMPC_AFFINE_DIRECT", raising=False)
+    a = _run(h, t, batch, gpu)
+    handed = h.last_dispatch()[1]
+    monkeypatch.setenv("FMPC_AFFINE_DIRECT", "1")
+    d = _run(h, t, batch, gpu)
+    assert h.last_dispatch()[1] == handed
+    uo = _run(h, t, batch, gpu, want_z=False)
+    assert h.last_dispatch()[1] == handed
+    monkeypatch.delenv("FMPC_AFFINE_DIRECT")
+    print("batch %d: %d problems handed to the exact path" % (batch, handed))
+    assert handed < batch, "every problem was redone by the exact path: z of the affine kernels is not compared"
+    for key in ("st", "it", "stp"):
+        assert np.array_equal(a[key], d[key]) and np.array_equal(uo[key], d[key]), key
+    assert np.all(np.isfinite(a["z"])) and np.all(np.isfinite(d["z"]))
+    worst = float(np.max(np.linalg.norm(a["z"] - d["z"], axis=1) / np.linalg.norm(d["z"], axis=1)))      # rel_err per problem
+    print("worst rel_err of z against the direct product %.3e" % worst)
+    assert worst <= 1e-11
+    assert np.array_equal(d["u0"], d["z"][:, :144]) and np.array_equal(uo["u0"], d["z"][:, :144])
     h.close()
 
 
