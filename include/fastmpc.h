@@ -1109,6 +1109,53 @@ int fmpc_est_model_device(fmpc_est_optics o, int nmode, const double* Z, const d
                           void* workspace, size_t workspace_bytes, void* stream);
 int fmpc_est_create_from_model(fmpc_est* out, fmpc_est_optics o, int nmode, int skip, const double* Z, const double* phi0);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Gauss-Newton refinement of the estimate from the images: the exact model above, re-linearised about the current estimate of
+ * every realisation of a batch.  ad_est = G (Y_M - b_s) (README.md:478) is the first-order model about zero aberration; with
+ * phi_b = sum_j alpha_{b,j} Z_j, y(alpha) = scale |F' (D_k .* exp(1i*phi_b)) F|^2 and J_b = dy/dalpha (A_s about phi_b) a step is
+ *
+ *     r = Y_b - y(alpha_b) ,   H = J_b' J_b ,  H_ii <- H_ii (1 + damping) ,   alpha_b <- alpha_b + H \ (J_b' r)
+ *
+ * fmpc_est_refine_device   Z: nmode <= 64 device maps as for fmpc_est_model_device; every map is an unknown (hand over the
+ *                   maps without the piston).  Y: batch device rows of p = ndiv d^2 measured values (Y_M, noise included) in the
+ *                   row order of README.md:471, row b at Y + b ldY.  alpha: batch x nmode on the device, in: the start, out:
+ *                   the refined coefficients.  iters steps with a fixed damping >= 0; no line search and no step rejection.
+ *                   tol > 0: a realisation whose step has ||delta|| <= tol (1 + ||alpha_b||) (alpha_b after the step) is marked
+ *                   converged on the device and takes no further step; tol = 0: every realisation takes iters steps.
+ *                   info (batch x FMPC_REFINE_FIELDS) and status (batch) on the device; either may be NULL:
+ *                       FMPC_REFINE_COST0  ||Y_b - y(alpha_in)||^2        FMPC_REFINE_STEP   ||delta|| of the last step taken
+ *                       FMPC_REFINE_COST   the same at alpha_out          FMPC_REFINE_ITERS  steps taken
+ *                   status bits: FMPC_REFINE_CONVERGED (by tol); FMPC_REFINE_FACTOR_FAILED: a pivot of the Cholesky factor of H
+ *                   was not positive and finite (a map that vanishes in the pupil, say) -- alpha_b stays at its last value and
+ *                   the realisation takes no further step; FMPC_REFINE_BAD_INPUT: the cost is not finite -- a pixel of phi_b with
+ *                   |phi_b| >= 1e6 or not finite (the phase rule of fmpc_est_apply), a value of Y_b or alpha_b that is not
+ *                   finite -- the costs of that row are NaN and, for iters > 0, so is alpha_b; the other rows are not touched and
+ *                   nothing faults.  iters = 0 writes COST0 = COST and leaves alpha alone.
+ *                   The workspace is the caller's: no allocation, no synchronisation, no read-back (the host never reads a
+ *                   flag: the workgroups of a stopped realisation leave at once) -- the call can be recorded into a graph.
+ *                   fmpc_est_refine_workspace_bytes(o, nmode, batch) is the recommended size (every field of up to 16
+ *                   realisations at a time); the minimum is fmpc_est_refine_workspace_bytes(o, nmode, 1) less nmode field slots
+ *                   of ndiv (len / 16) 16384 bytes each.  A smaller workspace walks the realisations, and below the size of
+ *                   one the fields, through it in panels.  A realisation's alpha, info and status are bitwise the same whatever
+ *                   the batch, its place in it and the workspace, and on every call.
+ * Answered before the device is touched, in this order: FMPC_E_NULL for NULL o, Z, Y, alpha or workspace; FMPC_E_DIM for
+ * nmode <= 0, batch < 0, iters < 0, damping or tol negative or not finite; FMPC_E_UNSUPPORTED for nmode > 64 (H is held in 32 KB
+ * of LDS); then, with o's dimensions, FMPC_E_DIM for ldY < p or a workspace below the minimum.  batch = 0 is valid and does
+ * nothing.  fmpc_est_refine_workspace_bytes is 0 for refused arguments.
+ */
+#define FMPC_REFINE_FIELDS 4
+#define FMPC_REFINE_COST0 0
+#define FMPC_REFINE_COST 1
+#define FMPC_REFINE_STEP 2
+#define FMPC_REFINE_ITERS 3
+#define FMPC_REFINE_CONVERGED 1
+#define FMPC_REFINE_FACTOR_FAILED 2
+#define FMPC_REFINE_BAD_INPUT 4
+size_t fmpc_est_refine_workspace_bytes(fmpc_est_optics o, int nmode, int batch);
+int fmpc_est_refine_device(fmpc_est_optics o, int nmode, const double* Z, int batch, const double* Y, long long ldY, double* alpha,
+                           int iters, double damping, double tol, double* info, int* status, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /*
  * Deformable mirror of Gaussian actuators on the device: the reference's section "The influence matrix of Deformable Mirror (DM)
  * generation" (README.md:184-272) and the surface such a mirror makes.  A mirror is m actuators with centres (cx_t, cy_t), a

@@ -24,6 +24,8 @@ from .dm_spline import (DMProfile, SplineDM, oomao_profile, oomao_dm_geometry, o
 from .atmosphere import Atmosphere, reference_atmosphere, atm_covariance, atm_extruder, atm_displacement, atm_default_stencil
 from . import optics
 from .optics import zernike_modes, zernike_basis, zernike_grid, EstimatorOptics, reference_optics, reference_pupil, reference_science_camera
+from ._lib import (FMPC_REFINE_FIELDS, FMPC_REFINE_COST0, FMPC_REFINE_COST, FMPC_REFINE_STEP, FMPC_REFINE_ITERS, FMPC_REFINE_FIELD_NAMES,
+                   FMPC_REFINE_CONVERGED, FMPC_REFINE_FACTOR_FAILED, FMPC_REFINE_BAD_INPUT)
 from . import science
 from .science import (ScienceCamera, sci_tables_host, FMPC_SCI_FIELDS, FMPC_SCI_MEAN, FMPC_SCI_RMS, FMPC_SCI_STREHL, FMPC_SCI_MARECHAL,
                       FMPC_SCI_MIN, FMPC_SCI_MAX, FMPC_SCI_FIELD_NAMES, FMPC_SCI_FORM_STANDARD, FMPC_SCI_FORM_FEW)
@@ -42,4 +44,5 @@ __all__ = ["optics", "zernike_modes", "zernike_basis", "zernike_grid", "Estimato
            "FMPC_SCI_FORM_FEW", "Atmosphere", "reference_atmosphere", "atm_covariance", "atm_extruder", "atm_displacement", "atm_default_stencil",
            "shwfs", "ShackHartmann", "sh_valid_host", "FMPC_SH_THRESHOLD_NONE", "FMPC_SH_THRESHOLD_FLOOR", "FMPC_SH_THRESHOLD_FRACTION",
            "DMProfile", "SplineDM", "oomao_profile", "oomao_dm_geometry", "oomao_dm", "dm_spline_matrix_workspace_bytes", "FMPC_DM_TILE",
-           "FMPC_DM_DENSE"]
+           "FMPC_DM_DENSE", "FMPC_REFINE_FIELDS", "FMPC_REFINE_COST0", "FMPC_REFINE_COST", "FMPC_REFINE_STEP", "FMPC_REFINE_ITERS",
+           "FMPC_REFINE_FIELD_NAMES", "FMPC_REFINE_CONVERGED", "FMPC_REFINE_FACTOR_FAILED", "FMPC_REFINE_BAD_INPUT"]

@@ -41,6 +41,14 @@ FMPC_KKT_FIELD_NAMES = ("rd", "rp", "nr", "cost", "barrier", "min_slack")
 FMPC_KKT_CONVERGED = 1
 FMPC_KKT_INFEASIBLE = 2
 
+# fmpc_est_refine_device: fields of an info row, status bits
+FMPC_REFINE_FIELDS = 4
+FMPC_REFINE_COST0, FMPC_REFINE_COST, FMPC_REFINE_STEP, FMPC_REFINE_ITERS = range(4)
+FMPC_REFINE_FIELD_NAMES = ("cost0", "cost", "step", "iters")
+FMPC_REFINE_CONVERGED = 1
+FMPC_REFINE_FACTOR_FAILED = 2
+FMPC_REFINE_BAD_INPUT = 4
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p
@@ -152,6 +160,9 @@ SIGNATURES = {
     "fmpc_est_model_workspace_bytes": (C.c_size_t, [_vp, C.c_int]),
     "fmpc_est_model_device": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fmpc_est_create_from_model": (C.c_int, [C.POINTER(_vp), _vp, C.c_int, C.c_int, _vp, _vp]),
+    "fmpc_est_refine_workspace_bytes": (C.c_size_t, [_vp, C.c_int, C.c_int]),
+    "fmpc_est_refine_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_longlong, _vp, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp,
+                                         C.c_size_t, _vp]),
     "fmpc_dm_influence_device": (C.c_int, [C.c_int] * 3 + [_vp] * 4 + [C.c_double] * 2 + [C.c_int] * 2 + [_vp, C.c_longlong, _vp]),
     "fmpc_dm_matrix_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "fmpc_dm_matrix_device": (C.c_int, [C.c_int] * 4 + [_vp] * 6 + [C.c_double] * 2 + [C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp]),

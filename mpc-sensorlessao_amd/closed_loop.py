@@ -197,10 +197,14 @@ class AOLoop:
     sensor (optional): a calibrated `ShackHartmann` on the estimator's grid with the handle's n modes; x0 of a step is then
     `sensor.coefficients(scrn)` instead of the estimator's ad_est, and `noise` of `step` may be None or a `DetectorNoise`, which is
     applied to the sensor's frame (measure the frame, `detector_read` on it, slopes and coefficients from what was read) with
-    `steps_done` as its step; nothing else changes."""
+    `steps_done` as its step; nothing else changes.
+    refine (optional): dict(optics=an `EstimatorOptics` of the estimator's geometry, iters=3, damping=0.0, tol=0.0); a step then
+    takes Y_M of `apply_device` (noise of any kind included) and refines x0 in place from it with the exact image model
+    (`EstimatorOptics.refine` over the loop's own Z, the start the linear estimate) before the solve; `refine_info`
+    (batch, FMPC_REFINE_FIELDS) and `refine_status` (batch,) hold the last call's rows; nothing else changes.  Not with sensor=."""
 
     def __init__(self, handle, estimator, Z, batch, n_newton=1, k=1e-2, one_call=True, modal=None, z_colmajor=False, science=None, sensor=None,
-                 dm=None):
+                 refine=None, dm=None):
         import ctypes as C
         import numpy as np
         import torch
@@ -248,6 +252,21 @@ class AOLoop:
         if sensor is not None:
             self._sensor_frame = torch.empty((batch, sensor.frame_len, sensor.frame_len), **f64)
             self._sensor_slopes = torch.empty((batch, 2 * sensor.nvalid), **f64)
+        self.refine = None
+        if refine is not None:
+            if sensor is not None:
+                raise ValueError("refine: the refinement works on the estimator's images; not together with sensor=")
+            unknown = set(refine) - {"optics", "iters", "damping", "tol"}
+            if unknown or "optics" not in refine:
+                raise ValueError("refine: need dict(optics=, iters=, damping=, tol=)")
+            opt = refine["optics"]
+            if (opt.len, opt.p) != (estimator.len, estimator.p):
+                raise ValueError("refine: need an EstimatorOptics of the estimator's grid, window and diversities")
+            from ._lib import FMPC_REFINE_FIELDS
+            self.refine = dict(optics=opt, iters=int(refine.get("iters", 3)), damping=float(refine.get("damping", 0.0)), tol=float(refine.get("tol", 0.0)))
+            self.refine_info = torch.zeros((batch, FMPC_REFINE_FIELDS), **f64)
+            self.refine_status = torch.zeros(batch, dtype=torch.int32, device=dev)
+            self._refine_ws = torch.empty(opt.refine_workspace_bytes(n, batch), dtype=torch.uint8, device=dev)
 
     def science_reset(self):
         """Start a new exposure: the accumulated image and the frame count go back to zero (after the uncorrected first step, say)."""
@@ -302,7 +321,12 @@ class AOLoop:
         self.x0, self.x0_pre = self._xb[s % 2], self._xb[(s + 1) % 2]
         if s == 0:
             self.x0_pre.zero_()
-        if self.sensor is None:
+        if self.refine is not None:          # the linear estimate, then Gauss-Newton on the images it was made from
+            Y = self.est.apply_device(self.scrn, noise, want_Y=True, colmajor=True, out=self.x0, step=s)[1]
+            rf = self.refine
+            rf["optics"].refine(self.Z, Y, alpha0=self.x0, out=self.x0, iters=rf["iters"], damping=rf["damping"], tol=rf["tol"],
+                                info=self.refine_info, status=self.refine_status, workspace=self._refine_ws)
+        elif self.sensor is None:
             self.est.apply_device(self.scrn, noise, colmajor=True, out=self.x0, step=s)
         elif noise is None:                  # what a wavefront sensor measures on the same residual screen
             self.sensor.coefficients(self.scrn, out=self.x0, colmajor=True)

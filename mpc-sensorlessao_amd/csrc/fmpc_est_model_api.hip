@@ -8,15 +8,7 @@
 #include "fmpc_estimator.h"
 #include "fmpc_host.h"
 #include "fmpc_alloc.h"
-
-struct fmpc_est_optics_s {
-    int device, len, d, first, ndiv;
-    double scale;
-    std::vector<double> hDre, hDim;      // the host arrays, for fmpc_est_create_from_model (fmpc_est_create takes host arrays)
-    DevBuf<double> pool;                 // D_re | D_im | Fimg
-    size_t oDre, oDim, oF;
-    DevBuf<int> qlist;                   // [len / 16][2]: range of the k-steps inside the pupil per row block
-};
+#include "fmpc_est_optics_handle.h"
 
 extern "C" int fmpc_est_optics_create(fmpc_est_optics* out, int len, int first, int d, int ndiv, const double* D_re,
                                       const double* D_im, double scale, int device) {
@@ -51,13 +43,9 @@ extern "C" int fmpc_est_optics_destroy(fmpc_est_optics o) {
     return FMPC_OK;
 }
 
-// Workspace: the summed base windows [ndiv][2][32][32], then one slot [ndiv][len / 16][2][32][32] per field held.
-static size_t model_base_doubles(const fmpc_est_optics_s* o) { return (size_t)o->ndiv * 2048; }
-static size_t model_slot_doubles(const fmpc_est_optics_s* o) { return (size_t)o->ndiv * (o->len / 16) * 2048; }
-
 extern "C" size_t fmpc_est_model_workspace_bytes(fmpc_est_optics o, int nmode) {
     if (!o || nmode <= 0 || nmode > FEM_MAXMODE) return 0;
-    return (model_base_doubles(o) + ((size_t)nmode + 1) * model_slot_doubles(o)) * sizeof(double);
+    return (fem_base_doubles(o) + ((size_t)nmode + 1) * fem_slot_doubles(o)) * sizeof(double);
 }
 
 extern "C" int fmpc_est_model_device(fmpc_est_optics o, int nmode, const double* Z, const double* phi0, double* A_s, double* b_s,
@@ -70,9 +58,9 @@ extern "C" int fmpc_est_model_device(fmpc_est_optics o, int nmode, const double*
     FemParams P;
     P.len = o->len; P.d = o->d; P.ndiv = o->ndiv; P.nmode = nmode; P.scale = o->scale; P.phi0 = phi0; P.Z = Z;
     P.Dre = o->pool + o->oDre; P.Dim = o->pool + o->oDim; P.Fimg = o->pool + o->oF; P.qrange = o->qlist;
-    P.base = (double*)workspace; P.part = (double*)workspace + model_base_doubles(o); P.A_s = A_s; P.b_s = b_s;
+    P.base = (double*)workspace; P.part = (double*)workspace + fem_base_doubles(o); P.A_s = A_s; P.b_s = b_s;
     // the fields (the base, then the modes) through the slots the workspace holds
-    const size_t held_ws = (workspace_bytes / sizeof(double) - model_base_doubles(o)) / model_slot_doubles(o);
+    const size_t held_ws = (workspace_bytes / sizeof(double) - fem_base_doubles(o)) / fem_slot_doubles(o);
     const int total = nmode + 1, held = held_ws < (size_t)total ? (int)held_ws : total;
     for (int f0 = 0; f0 < total; f0 += held) {
         const int nf = total - f0 < held ? total - f0 : held;

@@ -1,0 +1,77 @@
+// C ABI of the estimator's Gauss-Newton refinement (include/fastmpc.h: fmpc_est_refine_*).  The argument rules answer here,
+// before the device is touched; the call only records launches: no allocation, no synchronisation, no read-back.
+// Kernels: fmpc_kernel_est_refine.hip.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "../../include/fastmpc.h"
+#include "fmpc_estimator.h"
+#include "fmpc_est_optics_handle.h"
+
+#define FER_PANEL 16                     // realisations the recommended workspace holds at a time
+#define FER_PANEL_MAX 4096               // .. and any workspace (a grid dimension)
+
+// A realisation's block without its field slots, and with `slots` of them, in doubles.
+static size_t refine_fixed_doubles(const fmpc_est_optics_s* o, int nmode) {
+    const size_t p = (size_t)o->ndiv * o->d * o->d;
+    return FER_HDR + (size_t)o->len * o->len + fem_base_doubles(o) + p + p * nmode;
+}
+static size_t refine_block_doubles(const fmpc_est_optics_s* o, int nmode, int slots) {
+    return refine_fixed_doubles(o, nmode) + (size_t)slots * fem_slot_doubles(o);
+}
+
+extern "C" size_t fmpc_est_refine_workspace_bytes(fmpc_est_optics o, int nmode, int batch) {
+    if (!o || nmode <= 0 || nmode > FER_MAXMODE || batch < 0) return 0;
+    const int held = batch < 1 ? 1 : batch < FER_PANEL ? batch : FER_PANEL;
+    return refine_block_doubles(o, nmode, nmode + 1) * held * sizeof(double);
+}
+
+extern "C" int fmpc_est_refine_device(fmpc_est_optics o, int nmode, const double* Z, int batch, const double* Y, long long ldY,
+                                      double* alpha, int iters, double damping, double tol, double* info, int* status,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    if (!o || !Z || !Y || !alpha || !workspace) return FMPC_E_NULL;
+    if (nmode <= 0 || batch < 0 || iters < 0 || !(damping >= 0.0) || !(tol >= 0.0) || isinf(damping) || isinf(tol)) return FMPC_E_DIM;
+    if (nmode > FER_MAXMODE) return FMPC_E_UNSUPPORTED;
+    const int p = o->ndiv * o->d * o->d;
+    const size_t have = workspace_bytes / sizeof(double);
+    if (ldY < p || have < refine_block_doubles(o, nmode, 1)) return FMPC_E_DIM;
+    if (batch == 0) return FMPC_OK;
+    if (hipSetDevice(o->device) != hipSuccess) return FMPC_E_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    // the plan: every field of as many realisations as the workspace holds, or one realisation and the fields in panels
+    const int total = nmode + 1;
+    const size_t full = refine_block_doubles(o, nmode, total);
+    int held_r = 1, held_f = total;
+    if (have >= full) {
+        const size_t fit = have / full;
+        held_r = fit < (size_t)FER_PANEL_MAX ? (int)fit : FER_PANEL_MAX;
+        if (held_r > batch) held_r = batch;
+    } else {
+        held_f = (int)((have - refine_fixed_doubles(o, nmode)) / fem_slot_doubles(o));
+    }
+    FerParams P;
+    P.M.len = o->len; P.M.d = o->d; P.M.ndiv = o->ndiv; P.M.nmode = nmode; P.M.scale = o->scale; P.M.Z = Z;
+    P.M.Dre = o->pool + o->oDre; P.M.Dim = o->pool + o->oDim; P.M.Fimg = o->pool + o->oF; P.M.qrange = o->qlist;
+    P.M.phi0 = nullptr; P.M.base = nullptr; P.M.part = nullptr; P.M.A_s = nullptr; P.M.b_s = nullptr;
+    P.ws = (double*)workspace; P.stride = refine_block_doubles(o, nmode, held_f);
+    P.oPhi = FER_HDR; P.oBase = P.oPhi + (size_t)o->len * o->len; P.oY = P.oBase + fem_base_doubles(o); P.oJ = P.oY + p;
+    P.oPart = P.oJ + (size_t)p * nmode;
+    P.p = p; P.ldY = ldY; P.damping = damping; P.tol = tol;
+    for (int r0 = 0; r0 < batch; r0 += held_r) {
+        P.count = batch - r0 < held_r ? batch - r0 : held_r;
+        P.Y = Y + (size_t)r0 * ldY; P.alpha = alpha + (size_t)r0 * nmode;
+        P.info = info ? info + (size_t)r0 * FMPC_REFINE_FIELDS : nullptr; P.status = status ? status + r0 : nullptr;
+        if (fmpc_launch_refine_init(P, st) != hipSuccess) return FMPC_E_HIP;
+        for (int it = 0; it < iters; ++it) {
+            if (fmpc_launch_refine_phi(P, 0, st) != hipSuccess) return FMPC_E_HIP;
+            for (int f0 = 0; f0 < total; f0 += held_f) {
+                const int nf = total - f0 < held_f ? total - f0 : held_f;
+                if (fmpc_launch_refine_pass(P, f0, nf, 0, st) != hipSuccess) return FMPC_E_HIP;
+            }
+            if (fmpc_launch_refine_step(P, it, st) != hipSuccess) return FMPC_E_HIP;
+        }
+        // the cost at alpha_out: field 0 alone, for every realisation of the panel
+        if (fmpc_launch_refine_phi(P, 1, st) != hipSuccess || fmpc_launch_refine_pass(P, 0, 1, 1, st) != hipSuccess ||
+            fmpc_launch_refine_final(P, iters, st) != hipSuccess) return FMPC_E_HIP;
+    }
+    return FMPC_OK;
+}

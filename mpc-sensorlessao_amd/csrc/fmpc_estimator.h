@@ -97,3 +97,26 @@ struct FemParams {
 // One pass: the fields f0 .. f0 + nf - 1 through the slots 0 .. nf - 1 of `part` (PSF kernel, then the finish kernel; a pass
 // that holds field 0 finishes it first, the later passes read `base`).
 hipError_t fmpc_launch_est_model_pass(const FemParams& P, int f0, int nf, hipStream_t stream);
+
+// The Gauss-Newton refinement of a batch (fmpc_kernel_est_refine.hip): the model about phi_b = sum_j alpha_{b,j} Z_j of every
+// realisation of a panel, the normal equations and the step.  A realisation owns one block of the workspace:
+//     [FER_HDR doubles: info[FMPC_REFINE_FIELDS] | flags (an int)] [phi: len^2] [base] [y: p] [J: p x nmode] [part: slots]
+#define FER_MAXMODE 64
+#define FER_HDR 8
+#define FER_FLAG 4                      // the double of the header that holds the status bits as an int
+struct FerParams {
+    FemParams M;                        // the shared operands; phi0, base, part, A_s (J) and b_s (y) are set per realisation
+    double* ws; size_t stride;          // the panel's blocks and their distance in doubles
+    size_t oPhi, oBase, oY, oJ, oPart;  // offsets inside a block, in doubles
+    int p, count;                       // rows of Y, realisations of the panel
+    const double* Y; long long ldY;     // the panel's first row of Y
+    double* alpha;                      // the panel's first row, count x nmode
+    double damping, tol;
+    double* info; int* status;          // the panel's first rows, or NULL
+};
+hipError_t fmpc_launch_refine_init(const FerParams& P, hipStream_t stream);
+// phi_b into the blocks; then as fmpc_launch_est_model_pass for every realisation.  final: the frozen realisations too.
+hipError_t fmpc_launch_refine_phi(const FerParams& P, int final, hipStream_t stream);
+hipError_t fmpc_launch_refine_pass(const FerParams& P, int f0, int nf, int final, hipStream_t stream);
+hipError_t fmpc_launch_refine_step(const FerParams& P, int it, hipStream_t stream);
+hipError_t fmpc_launch_refine_final(const FerParams& P, int iters, hipStream_t stream);

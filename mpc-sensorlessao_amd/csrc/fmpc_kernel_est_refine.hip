@@ -1,0 +1,261 @@
+// CDNA4 Gauss-Newton refinement of the phase-diversity estimate from the images: per realisation b of a batch
+//     phi_b = sum_j alpha_{b,j} Z_j ;  (J_b, y_b) = the exact first-order model about phi_b (fmpc_est_model_psf.inc, fmpc_est_model_finish.inc) ;
+//     r = Y_b - y_b ;  H = J_b' J_b, H_ii <- H_ii (1 + damping) ;  g = J_b' r ;  alpha_b <- alpha_b + H \ g
+// A realisation owns one block of the caller's workspace (fmpc_estimator.h: FerParams) and is worked on by its own workgroups
+// alone, in a fixed order: its bits depend on nothing but its own inputs.
+//
+// fer_phi:    phi_b into the block, one thread per pixel, the modes in ascending order.
+// fer_psf, fer_finish: the bodies of fmpc_est_model_psf<true> / fmpc_est_model_finish with the realisation as grid.z.
+// fer_step:   one workgroup of 4 wavefronts per realisation.  [J r]' [J r] restricted to the tiles on and above the diagonal
+//             (row tiles of J', column tiles of [J r]: g is the column nmode) with v_mfma_f64_16x16x4_f64, the p rows the k
+//             index, zero-padded to a multiple of 4 and split over the wavefronts; the partial sums meet in LDS in the order of
+//             the wavefronts.  Then an elimination without square roots on the upper triangle carrying the column g
+//             (H = U' D U: the pivots are those of the Cholesky factor, squared), a back substitution, and the update.
+// fer_final:  the cost at alpha_out from field 0 alone, and the rows of info and status.
+// The status bits of a realisation live in its block; a workgroup of any of these kernels leaves at once when they are set.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "fmpc_device.h"
+#include "../../include/fastmpc.h"
+#include "fmpc_estimator.h"
+#include "fmpc_est_dev.h"
+
+#define FEM_NW 4
+
+#define FER_SH 65                        // row stride of H in LDS: 64 columns and g
+
+__device__ __forceinline__ double* fer_block(const FerParams& P, int r) { return P.ws + (size_t)r * P.stride; }
+__device__ __forceinline__ int fer_flags(const double* blk) { return *(const int*)(blk + FER_FLAG); }
+
+__global__ void fer_init(FerParams P) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= P.count) return;
+    double* blk = fer_block(P, r);
+    for (int i = 0; i < FER_HDR; ++i) blk[i] = 0.0;          // (flags: the int 0 is the double 0's low word)
+}
+
+__global__ void __launch_bounds__(256) fer_phi(FerParams P, int final) {
+    const int r = blockIdx.y;
+    double* blk = fer_block(P, r);
+    if (!final && fer_flags(blk)) return;
+    const size_t npx = (size_t)P.M.len * P.M.len, px = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (px >= npx) return;
+    const double* a = P.alpha + (size_t)r * P.M.nmode;
+    double s = 0.0;
+    for (int j = 0; j < P.M.nmode; ++j) s = fma(a[j], P.M.Z[(size_t)j * npx + px], s);
+    blk[P.oPhi + px] = s;
+}
+
+__device__ __forceinline__ FemParams fer_model(const FerParams& P, double* blk) {
+    FemParams M = P.M;
+    M.phi0 = blk + P.oPhi; M.base = blk + P.oBase; M.b_s = blk + P.oY; M.A_s = blk + P.oJ; M.part = blk + P.oPart;
+    return M;
+}
+
+__global__ void __launch_bounds__(FEM_NW * 64, 2) fer_psf(FerParams R, int f0, int final) {
+    double* rblk = fer_block(R, blockIdx.z);
+    if (!final && fer_flags(rblk)) return;                   // (uniform over the workgroup)
+    const FemParams P = fer_model(R, rblk);
+    constexpr bool PHI = true;
+    const int slot = blockIdx.x, f = f0 + slot, blk = blockIdx.y, nblk = gridDim.y;
+#include "fmpc_est_model_psf.inc"
+}
+
+__global__ void __launch_bounds__(1024) fer_finish(FerParams R, int f0, int slot0, int final) {
+    double* rblk = fer_block(R, blockIdx.z);
+    if (!final && fer_flags(rblk)) return;
+    const FemParams P = fer_model(R, rblk);
+    const int slot = slot0 + blockIdx.x, f = f0 + blockIdx.x, k = blockIdx.y;
+#include "fmpc_est_model_finish.inc"
+}
+
+// ||Y - y||^2 of a realisation by the 256 threads of a workgroup: thread t the rows t, t + 256, .., then a tree in LDS.
+__device__ __forceinline__ double fer_cost(const double* Yb, const double* y, int p, double* sRed) {
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    for (int k = tid; k < p; k += 256) { const double r = Yb[k] - y[k]; s = fma(r, r, s); }
+    sRed[tid] = s;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (tid < w) sRed[tid] += sRed[tid + w];
+        __syncthreads();
+    }
+    const double c = sRed[0];
+    __syncthreads();
+    return c;
+}
+
+__device__ __forceinline__ bool fer_finite(double x) { return fabs(x) <= 1.79769313486231570815e+308; }
+
+__global__ void __launch_bounds__(256) fer_step(FerParams P, int it) {
+    __shared__ double sH[64 * FER_SH];
+    __shared__ double sRed[256];
+    __shared__ double sD[64];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, c = lane & 15;
+    double* blk = fer_block(P, r);
+    if (fer_flags(blk)) return;
+    const int n = P.M.nmode, p = P.p;
+    const double* Yb = P.Y + (size_t)r * P.ldY;
+    const double* y = blk + P.oY;
+    const double* J = blk + P.oJ;
+    double* a = P.alpha + (size_t)r * n;
+    int* flags = (int*)(blk + FER_FLAG);
+
+    const double cost = fer_cost(Yb, y, p, sRed);
+    if (it == 0 && tid == 0) blk[FMPC_REFINE_COST0] = cost;
+    if (!fer_finite(cost)) {                                 // a phase beyond the range, a NaN in Y or in alpha: the row is NaN
+        if (tid < n) a[tid] = __builtin_nan("");
+        if (tid == 0) *flags |= FMPC_REFINE_BAD_INPUT;
+        return;
+    }
+
+    // ---- [J r]' [J r], the tiles (rt, ct), ct >= rt: lane (g, c) holds entry (k-row 4 q + g, column 16 t + c) of [J r],
+    //      which is the A operand of row tile t (J' read by columns) and the B operand of column tile t
+    const int ntr = (n + 15) >> 4, ntc = (n >> 4) + 1;       // row tiles over J, column tiles over [J r]
+    d4e acc[4][5];
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 5; ++ct) acc[rt][ct] = (d4e){0, 0, 0, 0};
+    const int kq = (p + 3) >> 2;
+    const int q0 = (int)((long long)kq * wv / 4), q1 = (int)((long long)kq * (wv + 1) / 4);
+    for (int q = q0; q < q1; ++q) {
+        const int k = 4 * q + g;
+        double v[5];
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            const int jj = 16 * t + c;
+            double x = 0.0;
+            if (t < ntc && k < p) {
+                if (jj < n) x = J[(size_t)jj * p + k];
+                else if (jj == n) x = Yb[k] - y[k];
+            }
+            v[t] = x;
+        }
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+            for (int ct = 0; ct < 5; ++ct)
+                if (ct >= rt && rt < ntr && ct < ntc) acc[rt][ct] = FE_MFMA(v[rt], v[ct], acc[rt][ct]);      // (uniform)
+    }
+    // ---- the wavefronts' partial sums meet in LDS in their order: ((w0 + w1) + w2) + w3
+    for (int w = 0; w < 4; ++w) {
+        if (wv == w) {
+#pragma unroll
+            for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < 5; ++ct)
+                    if (ct >= rt && rt < ntr && ct < ntc) {
+#pragma unroll
+                        for (int rr = 0; rr < 4; ++rr) {      // register rr <-> row 16 rt + 4 rr + g, column 16 ct + c
+                            const int i = 16 * rt + 4 * rr + g, j = 16 * ct + c;
+                            if (j < FER_SH) sH[i * FER_SH + j] = w == 0 ? acc[rt][ct][rr] : sH[i * FER_SH + j] + acc[rt][ct][rr];
+                        }
+                    }
+        }
+        __syncthreads();
+    }
+    if (tid < n) sH[tid * FER_SH + tid] *= 1.0 + P.damping;
+    __syncthreads();
+    // ---- elimination on the upper triangle, the column n (g) carried along; row kk is final after step kk
+    bool ok = true;
+    for (int kk = 0; kk < n; ++kk) {
+        const double piv = sH[kk * FER_SH + kk];
+        if (!(piv > 0.0) || !fer_finite(piv)) { ok = false; break; }                  // (uniform: every thread reads the same)
+        const int rows = n - 1 - kk, cols = n - kk;          // rows kk + 1 .. n - 1, columns kk + 1 .. n
+        for (int idx = tid; idx < rows * cols; idx += 256) {
+            const int i = kk + 1 + idx / cols, j = kk + 1 + idx % cols;
+            if (j >= i) sH[i * FER_SH + j] -= sH[kk * FER_SH + i] * (sH[kk * FER_SH + j] / piv);
+        }
+        __syncthreads();
+    }
+    if (!ok) {                                               // alpha stays at its last value
+        if (tid == 0) *flags |= FMPC_REFINE_FACTOR_FAILED;
+        return;
+    }
+    // ---- back substitution: delta_k = (g_k - sum_{j > k} U_kj delta_j) / U_kk, by columns
+    for (int kk = n - 1; kk >= 0; --kk) {
+        const double x = sH[kk * FER_SH + n] / sH[kk * FER_SH + kk];
+        if (tid < kk) sH[tid * FER_SH + n] -= sH[tid * FER_SH + kk] * x;
+        if (tid == kk) sD[kk] = x;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double dd = 0.0, aa = 0.0;
+        for (int j = 0; j < n; ++j) {
+            const double an = a[j] + sD[j];
+            dd = fma(sD[j], sD[j], dd); aa = fma(an, an, aa);
+            a[j] = an;
+        }
+        const double step = sqrt(dd);
+        blk[FMPC_REFINE_STEP] = step;
+        blk[FMPC_REFINE_ITERS] += 1.0;
+        if (P.tol > 0.0 && step <= P.tol * (1.0 + sqrt(aa))) *flags |= FMPC_REFINE_CONVERGED;
+    }
+}
+
+__global__ void __launch_bounds__(256) fer_final(FerParams P, int iters) {
+    __shared__ double sRed[256];
+    const int r = blockIdx.x, tid = threadIdx.x, n = P.M.nmode;
+    double* blk = fer_block(P, r);
+    int fl = fer_flags(blk);
+    double cost = fer_cost(P.Y + (size_t)r * P.ldY, blk + P.oY, P.p, sRed);
+    const bool bad = (fl & FMPC_REFINE_BAD_INPUT) || !fer_finite(cost);
+    if (bad) {
+        fl |= FMPC_REFINE_BAD_INPUT;
+        cost = __builtin_nan("");
+        if (iters > 0 && tid < n) P.alpha[(size_t)r * n + tid] = cost;
+    }
+    if (tid == 0) {
+        if (P.info) {
+            double* o = P.info + (size_t)r * FMPC_REFINE_FIELDS;
+            o[FMPC_REFINE_COST0] = bad || iters == 0 ? cost : blk[FMPC_REFINE_COST0];
+            o[FMPC_REFINE_COST] = cost;
+            o[FMPC_REFINE_STEP] = blk[FMPC_REFINE_STEP];
+            o[FMPC_REFINE_ITERS] = blk[FMPC_REFINE_ITERS];
+        }
+        if (P.status) P.status[r] = fl;
+    }
+}
+
+static bool fer_params_ok(const FerParams& P) {
+    return fe_geometry_ok(P.M.len, 0, P.M.d, P.M.ndiv) && P.M.nmode >= 1 && P.M.nmode <= FER_MAXMODE && P.count >= 1 && P.count <= 65535 &&
+           P.p == P.M.ndiv * P.M.d * P.M.d;
+}
+
+hipError_t fmpc_launch_refine_init(const FerParams& P, hipStream_t stream) {
+    if (!fer_params_ok(P)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fer_init, dim3((P.count + 63) / 64), dim3(64), 0, stream, P);
+    return hipGetLastError();
+}
+
+hipError_t fmpc_launch_refine_phi(const FerParams& P, int final, hipStream_t stream) {
+    if (!fer_params_ok(P)) return hipErrorInvalidValue;
+    const size_t npx = (size_t)P.M.len * P.M.len;
+    hipLaunchKernelGGL(fer_phi, dim3((unsigned)((npx + 255) / 256), P.count), dim3(256), 0, stream, P, final);
+    return hipGetLastError();
+}
+
+hipError_t fmpc_launch_refine_pass(const FerParams& P, int f0, int nf, int final, hipStream_t stream) {
+    if (!fer_params_ok(P) || f0 < 0 || nf < 1 || f0 + nf > P.M.nmode + 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fer_psf, dim3(nf, P.M.len / 16, P.count), dim3(FEM_NW * 64), 0, stream, P, f0, final);
+    int first = 0;
+    if (f0 == 0) {                                           // the base field first: the modes of this pass read I_k
+        hipLaunchKernelGGL(fer_finish, dim3(1, P.M.ndiv, P.count), dim3(1024), 0, stream, P, 0, 0, final);
+        first = 1;
+    }
+    if (nf > first) hipLaunchKernelGGL(fer_finish, dim3(nf - first, P.M.ndiv, P.count), dim3(1024), 0, stream, P, f0 + first, first, final);
+    return hipGetLastError();
+}
+
+hipError_t fmpc_launch_refine_step(const FerParams& P, int it, hipStream_t stream) {
+    if (!fer_params_ok(P)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fer_step, dim3(P.count), dim3(256), 0, stream, P, it);
+    return hipGetLastError();
+}
+
+hipError_t fmpc_launch_refine_final(const FerParams& P, int iters, hipStream_t stream) {
+    if (!fer_params_ok(P)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fer_final, dim3(P.count), dim3(256), 0, stream, P, iters);
+    return hipGetLastError();
+}

@@ -143,6 +143,51 @@ class EstimatorOptics:
             raise FastMPCError(rc, "fmpc_est_model_device")
         return At.t(), b
 
+    def refine_workspace_bytes(self, nmode, batch=1, minimum=False):
+        """Recommended workspace of `refine` in bytes (every field of up to 16 realisations at a time); minimum=True: the
+        smallest it takes (one realisation, one field at a time), whatever the batch."""
+        full = int(self._lib.fmpc_est_refine_workspace_bytes(self._h, int(nmode), int(batch)))
+        if not minimum or full == 0:
+            return full
+        one = int(self._lib.fmpc_est_refine_workspace_bytes(self._h, int(nmode), 1))
+        return one - int(nmode) * self.ndiv * (self.len // 16) * 16384
+
+    def refine(self, Z, Y, alpha0=None, iters=3, damping=0.0, tol=0.0, workspace=None, out=None, info=None, status=None):
+        """Gauss-Newton on ||Y_b - y(alpha_b)||^2 with the exact image model (`fmpc_est_refine_device`).  Z: (nmode <= 64, len, len)
+        HIP tensor indexed [j, column, row], every map an unknown (no piston); Y: (batch, p) measured images, unit column stride;
+        alpha0: (batch, nmode) start, None: zero.  Returns alpha (batch, nmode) on torch's current stream: `out` if given
+        (out may be alpha0 itself: refined in place), else a new tensor.  info: (batch, FMPC_REFINE_FIELDS) float64 and
+        status: (batch,) int32 tensors to fill, or None.  workspace: a torch.uint8 HIP tensor of at least
+        `refine_workspace_bytes(nmode, minimum=True)`."""
+        import torch
+        nmode = self._maps(Z, None)
+        if not Y.is_cuda or Y.dtype != torch.float64 or Y.dim() != 2 or Y.shape[1] != self.p or (self.p > 1 and Y.stride(1) != 1):
+            raise FastMPCError(_lib.FMPC_E_DIM, "Y: need a float64 HIP tensor (batch, p) with unit column stride")
+        batch = int(Y.shape[0])
+        ldY = int(Y.stride(0)) if batch > 1 else self.p
+        alpha = out if out is not None else torch.empty((batch, nmode), dtype=torch.float64, device=Z.device)
+        if not alpha.is_cuda or alpha.dtype != torch.float64 or not alpha.is_contiguous() or tuple(alpha.shape) != (batch, nmode):
+            raise FastMPCError(_lib.FMPC_E_DIM, "out: need a contiguous float64 HIP tensor (batch, nmode)")
+        if alpha0 is None:
+            alpha.zero_()
+        elif alpha0 is not alpha:
+            alpha.copy_(alpha0)
+        if info is not None and (not info.is_cuda or info.dtype != torch.float64 or not info.is_contiguous() or
+                                 tuple(info.shape) != (batch, _lib.FMPC_REFINE_FIELDS)):
+            raise FastMPCError(_lib.FMPC_E_DIM, "info: need a contiguous float64 HIP tensor (batch, FMPC_REFINE_FIELDS)")
+        if status is not None and (not status.is_cuda or status.dtype != torch.int32 or not status.is_contiguous() or tuple(status.shape) != (batch,)):
+            raise FastMPCError(_lib.FMPC_E_DIM, "status: need a contiguous int32 HIP tensor (batch,)")
+        if batch == 0:                       # (an empty tensor has no pointer to hand over; the library takes batch = 0 and does nothing)
+            return alpha
+        if workspace is None:
+            workspace = torch.empty(self.refine_workspace_bytes(nmode, batch), dtype=torch.uint8, device=Z.device)
+        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        rc = self._lib.fmpc_est_refine_device(self._h, nmode, vp(Z), batch, vp(Y), ldY, vp(alpha), int(iters), float(damping), float(tol),
+                                              vp(info), vp(status), vp(workspace), workspace.numel(), _stream(Z.device))
+        if rc != _lib.FMPC_OK:
+            raise FastMPCError(rc, "fmpc_est_refine_device")
+        return alpha
+
     def estimator(self, Z, skip=1, phi0=None):
         """The estimator of this model without its first `skip` columns (README.md:289 removes the piston).  Synchronises."""
         import torch
