@@ -1156,6 +1156,53 @@ int fmpc_est_refine_device(fmpc_est_optics o, int nmode, const double* Z, int ba
                            int iters, double damping, double tol, double* info, int* status, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * The refinement with a held Jacobian, and without one.  An iteration of fmpc_est_refine_device evaluates nmode + 1 fields per
+ * realisation and nmode of them only rebuild J; the residual needs field 0 alone.  fmpc_est_refine_hold_device is that call with
+ * a schedule `refresh` for J; Z, Y, alpha, iters, damping, tol, info, status, the workspace and the stream are as above.
+ *
+ * refresh >= 1     iteration it (0, 1, ..) is FULL when it % refresh == 0: all nmode + 1 fields about the current alpha_b, as
+ *                  above.  Otherwise it is HELD: field 0 alone about the current alpha_b gives y(alpha_b); r = Y_b - y(alpha_b),
+ *                  g = J'r and H = J'J with H_ii (1 + damping) come from the J of the last full iteration, which is still in
+ *                  the realisation's block (H is formed again from it: J is read once).  The elimination, the update, the tol
+ *                  rule, the freeze rules, info and status are those above.  refresh = 1 is fmpc_est_refine_device: the same
+ *                  launches, the same bits.  refresh >= iters builds J once.  G is ignored and may be NULL.
+ * refresh == 0     the gain form: no Jacobian and no factorisation, alpha_b <- alpha_b + G (Y_b - y(alpha_b)) per iteration.  G:
+ *                  device matrix nmode x p, row j at G + j ldG, ldG >= p: the estimator's gain about zero aberration,
+ *                  pinv(A_s) of fmpc_est_model_device without the piston row (README.md:478).  damping must be 0.
+ *                  FMPC_REFINE_FACTOR_FAILED cannot occur; the tol rule and FMPC_REFINE_BAD_INPUT are those above.  A
+ *                  realisation's block holds no J and one field slot (about 4 MB instead of 47 MB at len 512, 27 modes).
+ * FMPC_REFINE_ITERS counts full, held and gain steps alike; FMPC_REFINE_COST0 is the cost at alpha_in in every form.
+ *
+ * When to use which.  Worst relative error ||alpha_hat - alpha|| / ||alpha|| of 6 draws after iterations 1 2 3 4 (len 64, window
+ * 31, diversities -3 / 0 / 3, 27 modes, noise-free, start the linear estimate; tests/test_est_refine_hold_ref.py):
+ *     ||alpha||  start    refresh = 1 (Gauss-Newton)     J once (refresh >= iters)       refresh = 0 (gain form)
+ *     0.3        2.9e-2   3.8e-4 4.8e-8 1.3e-14 -        3.8e-4 6.7e-6 1.2e-7 2.0e-9     2.5e-3 2.2e-4 1.9e-5 1.6e-6
+ *     1.0        1.7e-1   1.3e-2 8.9e-5 4.4e-9  -        1.3e-2 1.4e-3 1.4e-4 1.3e-5     6.5e-2 3.2e-2 1.7e-2 9.5e-3
+ *     1.5        3.9e-1   1.7e-1 1.5e-2 1.1e-4 7.3e-9    1.7e-1 4.7e-2 1.1e-2 2.6e-3     stalls at 1e-1
+ *     2.0        6.7e-1   3.3e-1 4.6e-2 9.9e-4 4.0e-7    3.3e-1 1.2e-1 9.2e-2 7.6e-2     diverges (0.61 .. 0.81 after 9)
+ * refresh = 3 at ||alpha|| = 2: 3.3e-1 1.2e-1 9.2e-2 4.5e-3 1.9e-4 1.1e-5 4.8e-11 after iterations 1 .. 7; 9.0e-9 after 4 at 1.
+ * A held iteration gains about a digit at <= 1 rad for one field instead of nmode + 1; at 0.3 rad, the residual of a converged
+ * loop, two gain steps (two fields, no J) are as good as one Gauss-Newton iteration.  Above 1 rad the gain form stalls or
+ * diverges and a held J is slow: use refresh <= 3 there.  Nothing detects a schedule that does not converge, apart from
+ * FMPC_REFINE_COST against FMPC_REFINE_COST0.  There is no host-pointer, bank, sharded or MATLAB form of this call.
+ *
+ * fmpc_est_refine_hold_workspace_bytes(o, nmode, batch, refresh) is the recommended size: for refresh >= 1 that of
+ * fmpc_est_refine_workspace_bytes, with the same minimum; for refresh = 0 the blocks of up to 128 realisations, always below
+ * the refresh >= 1 value of the same nmode and batch, and the minimum is its value for batch = 1.  A smaller workspace walks
+ * the realisations through it in panels; with refresh >= 2 and a batch larger than the blocks that fit, a block gets 4 field
+ * slots instead of nmode + 1 and the workspace holds that many more realisations at a time (a held iteration needs one slot).  A realisation's alpha, info and status are bitwise the same whatever the batch, its
+ * place in it and the workspace, and on every call; no allocation, no synchronisation, no read-back: graph-recordable.
+ * Answered before the device is touched, in this order: FMPC_E_NULL as above, and for refresh = 0 with G NULL; FMPC_E_DIM as
+ * above, and for refresh < 0 and for refresh = 0 with damping != 0; FMPC_E_UNSUPPORTED for nmode > 64; then, with o's
+ * dimensions, FMPC_E_DIM for ldY < p, for refresh = 0 with ldG < p, or a workspace below the minimum.  batch = 0 does nothing.
+ * fmpc_est_refine_hold_workspace_bytes is 0 for refused arguments.
+ */
+size_t fmpc_est_refine_hold_workspace_bytes(fmpc_est_optics o, int nmode, int batch, int refresh);
+int fmpc_est_refine_hold_device(fmpc_est_optics o, int nmode, const double* Z, int batch, const double* Y, long long ldY, double* alpha,
+                                int iters, int refresh, const double* G, long long ldG, double damping, double tol, double* info,
+                                int* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /*
  * Deformable mirror of Gaussian actuators on the device: the reference's section "The influence matrix of Deformable Mirror (DM)
  * generation" (README.md:184-272) and the surface such a mirror makes.  A mirror is m actuators with centres (cx_t, cy_t), a

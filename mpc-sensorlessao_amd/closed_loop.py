@@ -201,7 +201,9 @@ class AOLoop:
     refine (optional): dict(optics=an `EstimatorOptics` of the estimator's geometry, iters=3, damping=0.0, tol=0.0); a step then
     takes Y_M of `apply_device` (noise of any kind included) and refines x0 in place from it with the exact image model
     (`EstimatorOptics.refine` over the loop's own Z, the start the linear estimate) before the solve; `refine_info`
-    (batch, FMPC_REFINE_FIELDS) and `refine_status` (batch,) hold the last call's rows; nothing else changes.  Not with sensor=."""
+    (batch, FMPC_REFINE_FIELDS) and `refine_status` (batch,) hold the last call's rows; nothing else changes.  Not with sensor=.
+    Two further keys are optional: refresh (1: J every iteration; r > 1: every r-th, held in between; 0: the gain form without a
+    Jacobian, damping 0) and G, the gain form's (n, p) matrix (None: `optics.gain(Z)`, computed once here)."""
 
     def __init__(self, handle, estimator, Z, batch, n_newton=1, k=1e-2, one_call=True, modal=None, z_colmajor=False, science=None, sensor=None,
                  refine=None, dm=None):
@@ -256,17 +258,24 @@ class AOLoop:
         if refine is not None:
             if sensor is not None:
                 raise ValueError("refine: the refinement works on the estimator's images; not together with sensor=")
-            unknown = set(refine) - {"optics", "iters", "damping", "tol"}
+            unknown = set(refine) - {"optics", "iters", "damping", "tol", "refresh", "G"}
             if unknown or "optics" not in refine:
-                raise ValueError("refine: need dict(optics=, iters=, damping=, tol=)")
+                raise ValueError("refine: need dict(optics=, iters=, damping=, tol=[, refresh=, G=])")
             opt = refine["optics"]
             if (opt.len, opt.p) != (estimator.len, estimator.p):
                 raise ValueError("refine: need an EstimatorOptics of the estimator's grid, window and diversities")
             from ._lib import FMPC_REFINE_FIELDS
-            self.refine = dict(optics=opt, iters=int(refine.get("iters", 3)), damping=float(refine.get("damping", 0.0)), tol=float(refine.get("tol", 0.0)))
+            refresh = int(refine.get("refresh", 1))
+            if refresh < 0:
+                raise ValueError("refine: refresh >= 0")
+            G = refine.get("G")
+            if refresh == 0 and G is None:   # the gain about zero aberration, once (it synchronises)
+                G = opt.gain(self.Z)
+            self.refine = dict(optics=opt, iters=int(refine.get("iters", 3)), damping=float(refine.get("damping", 0.0)), tol=float(refine.get("tol", 0.0)),
+                               refresh=refresh, G=G if refresh == 0 else None)
             self.refine_info = torch.zeros((batch, FMPC_REFINE_FIELDS), **f64)
             self.refine_status = torch.zeros(batch, dtype=torch.int32, device=dev)
-            self._refine_ws = torch.empty(opt.refine_workspace_bytes(n, batch), dtype=torch.uint8, device=dev)
+            self._refine_ws = torch.empty(opt.refine_workspace_bytes(n, batch, refresh=refresh), dtype=torch.uint8, device=dev)
 
     def science_reset(self):
         """Start a new exposure: the accumulated image and the frame count go back to zero (after the uncorrected first step, say)."""
@@ -325,7 +334,7 @@ class AOLoop:
             Y = self.est.apply_device(self.scrn, noise, want_Y=True, colmajor=True, out=self.x0, step=s)[1]
             rf = self.refine
             rf["optics"].refine(self.Z, Y, alpha0=self.x0, out=self.x0, iters=rf["iters"], damping=rf["damping"], tol=rf["tol"],
-                                info=self.refine_info, status=self.refine_status, workspace=self._refine_ws)
+                                info=self.refine_info, status=self.refine_status, workspace=self._refine_ws, refresh=rf["refresh"], G=rf["G"])
         elif self.sensor is None:
             self.est.apply_device(self.scrn, noise, colmajor=True, out=self.x0, step=s)
         elif noise is None:                  # what a wavefront sensor measures on the same residual screen

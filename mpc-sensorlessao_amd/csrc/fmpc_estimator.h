@@ -113,10 +113,16 @@ struct FerParams {
     double* alpha;                      // the panel's first row, count x nmode
     double damping, tol;
     double* info; int* status;          // the panel's first rows, or NULL
+    // ---- the gain form (fmpc_est_refine_hold_device, refresh = 0): behind everything the Gauss-Newton kernels read.  A block
+    //      then holds no J: [header] [phi] [base] [y: p] [part: one slot]
+    const double* G = nullptr; long long ldG = 0;      // nmode x p, row j at G + j ldG
 };
 hipError_t fmpc_launch_refine_init(const FerParams& P, hipStream_t stream);
 // phi_b into the blocks; then as fmpc_launch_est_model_pass for every realisation.  final: the frozen realisations too.
 hipError_t fmpc_launch_refine_phi(const FerParams& P, int final, hipStream_t stream);
+hipError_t fmpc_launch_refine_phi_many(const FerParams& P, int final, hipStream_t stream);    // the same phi_b, 8 realisations per thread
 hipError_t fmpc_launch_refine_pass(const FerParams& P, int f0, int nf, int final, hipStream_t stream);
 hipError_t fmpc_launch_refine_step(const FerParams& P, int it, hipStream_t stream);
+// the gain form's step of a panel, alpha_b <- alpha_b + G (Y_b - y_b): 16 realisations per workgroup
+hipError_t fmpc_launch_refine_gain_step(const FerParams& P, int it, hipStream_t stream);
 hipError_t fmpc_launch_refine_final(const FerParams& P, int iters, hipStream_t stream);

@@ -11,6 +11,9 @@
 //             index, zero-padded to a multiple of 4 and split over the wavefronts; the partial sums meet in LDS in the order of
 //             the wavefronts.  Then an elimination without square roots on the upper triangle carrying the column g
 //             (H = U' D U: the pivots are those of the Cholesky factor, squared), a back substitution, and the update.
+//             On a held iteration (fmpc_est_refine_hold_device) the J in the block is the one of the last full iteration: the
+//             field-0 pass before it writes y, I_k and slot 0 alone.
+// fer_gain_step: the step without a Jacobian, alpha_b <- alpha_b + G (Y_b - y_b), for 16 realisations per workgroup (below).
 // fer_final:  the cost at alpha_out from field 0 alone, and the rows of info and status.
 // The status bits of a realisation live in its block; a workgroup of any of these kernels leaves at once when they are set.
 #include <hip/hip_runtime.h>
@@ -23,6 +26,7 @@
 #define FEM_NW 4
 
 #define FER_SH 65                        // row stride of H in LDS: 64 columns and g
+#define FER_GU 8                         // k-steps whose operands fer_gain_step loads ahead
 
 __device__ __forceinline__ double* fer_block(const FerParams& P, int r) { return P.ws + (size_t)r * P.stride; }
 __device__ __forceinline__ int fer_flags(const double* blk) { return *(const int*)(blk + FER_FLAG); }
@@ -44,6 +48,35 @@ __global__ void __launch_bounds__(256) fer_phi(FerParams P, int final) {
     double s = 0.0;
     for (int j = 0; j < P.M.nmode; ++j) s = fma(a[j], P.M.Z[(size_t)j * npx + px], s);
     blk[P.oPhi + px] = s;
+}
+
+// fer_phi for FER_PHI_R realisations per thread (the hold call): a map's pixel is read once for all of them instead of once
+// each -- the nmode maps are 27 x 2 MB at len 512, and on an iteration of one field that read is most of the work.  Every
+// realisation's sum is fer_phi's, term by term.
+#define FER_PHI_R 8
+__global__ void __launch_bounds__(256) fer_phi_many(FerParams P, int final) {
+    const size_t npx = (size_t)P.M.len * P.M.len, px = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int r0 = blockIdx.y * FER_PHI_R;
+    bool act[FER_PHI_R];
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < FER_PHI_R; ++i) {                    // (uniform over the workgroup)
+        act[i] = r0 + i < P.count && (final || !fer_flags(fer_block(P, r0 + i)));
+        any = any || act[i];
+    }
+    if (!any || px >= npx) return;
+    double s[FER_PHI_R];
+#pragma unroll
+    for (int i = 0; i < FER_PHI_R; ++i) s[i] = 0.0;
+    for (int j = 0; j < P.M.nmode; ++j) {
+        const double z = P.M.Z[(size_t)j * npx + px];
+#pragma unroll
+        for (int i = 0; i < FER_PHI_R; ++i)
+            if (act[i]) s[i] = fma(P.alpha[(size_t)(r0 + i) * P.M.nmode + j], z, s[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < FER_PHI_R; ++i)
+        if (act[i]) fer_block(P, r0 + i)[P.oPhi + px] = s[i];
 }
 
 __device__ __forceinline__ FemParams fer_model(const FerParams& P, double* blk) {
@@ -194,6 +227,97 @@ __global__ void __launch_bounds__(256) fer_step(FerParams P, int it) {
     }
 }
 
+// The gain form's step of 16 realisations: delta = R G' for R = (Y - y) of the tile, 16 x p, with v_mfma_f64_16x16x4_f64.  The
+// realisations are the rows of a tile (lane (g, c) holds r of realisation c at k-row 4 q + g: the A operand, formed in the lane
+// and never stored), the modes the columns in tiles of 16 (the same lane holds G[16 t + c][4 q + g]: the B operand), the p rows
+// the k index, zero-padded to a multiple of 4 and split over the wavefronts as in fer_step; ||r||^2 of realisation c rides on
+// its 16 lanes (4 wavefronts x 4 g) and is summed in that order.  A row of an MFMA's result depends on the same row of A alone,
+// so a realisation's bits do not depend on its place in the tile or on its neighbours; one that is frozen or beyond the panel's
+// count is switched off by a select (its r may be NaN, its rows of Y may not exist) and is written by nobody.
+__global__ void __launch_bounds__(256) fer_gain_step(FerParams P, int it) {
+    __shared__ double sD[16 * FER_SH];
+    __shared__ double sC[4][4][16];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, c = lane & 15;
+    const int r = blockIdx.x * 16 + c;
+    const int n = P.M.nmode, p = P.p;
+    double* blk = r < P.count ? fer_block(P, r) : nullptr;
+    const bool live = blk && !fer_flags(blk);
+    if (!__syncthreads_or(live)) return;
+    const double* Yb = live ? P.Y + (size_t)r * P.ldY : nullptr;
+    const double* y = live ? blk + P.oY : nullptr;
+
+    const int ntc = (n + 15) >> 4;
+    d4e acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = (d4e){0, 0, 0, 0};
+    double cs = 0.0;
+    const int kq = (p + 3) >> 2;
+    const int q0 = (int)((long long)kq * wv / 4), q1 = (int)((long long)kq * (wv + 1) / 4);
+    for (int qb = q0; qb < q1; qb += FER_GU) {               // the operands of FER_GU k-steps are loaded ahead of their products:
+        double x[FER_GU], gv[FER_GU][4];                     // one workgroup serves 16 realisations, so latency is what it pays
+#pragma unroll
+        for (int u = 0; u < FER_GU; ++u) {
+            const int k = 4 * (qb + u) + g;
+            const bool in = qb + u < q1 && k < p;
+            x[u] = 0.0;
+            if (live && in) x[u] = Yb[k] - y[k];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int jj = 16 * t + c;
+                gv[u][t] = 0.0;
+                if (t < ntc && jj < n && in) gv[u][t] = P.G[(size_t)jj * P.ldG + k];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < FER_GU; ++u) {
+            if (qb + u >= q1) break;                         // (uniform)
+            cs = fma(x[u], x[u], cs);
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (t < ntc) acc[t] = FE_MFMA(x[u], gv[u][t], acc[t]);                    // (uniform)
+        }
+    }
+    sC[wv][g][c] = cs;
+    // ---- the wavefronts' partial sums meet in LDS in their order: ((w0 + w1) + w2) + w3
+    for (int w = 0; w < 4; ++w) {
+        if (wv == w) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (t < ntc) {
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr) {          // register rr <-> realisation 4 rr + g of the tile, mode 16 t + c
+                        const int i = 4 * rr + g, j = 16 * t + c;
+                        sD[i * FER_SH + j] = w == 0 ? acc[t][rr] : sD[i * FER_SH + j] + acc[t][rr];
+                    }
+                }
+        }
+        __syncthreads();
+    }
+    if (tid >= 16 || !live) return;                          // thread c < 16: realisation c of the tile
+    double cost = 0.0;
+    for (int w = 0; w < 4; ++w)
+        for (int gg = 0; gg < 4; ++gg) cost += sC[w][gg][tid];
+    double* a = P.alpha + (size_t)r * n;
+    int* flags = (int*)(blk + FER_FLAG);
+    if (it == 0) blk[FMPC_REFINE_COST0] = cost;
+    if (!fer_finite(cost)) {                                 // as in fer_step: the row is NaN
+        for (int j = 0; j < n; ++j) a[j] = __builtin_nan("");
+        *flags |= FMPC_REFINE_BAD_INPUT;
+        return;
+    }
+    const double* dl = sD + tid * FER_SH;
+    double dd = 0.0, aa = 0.0;
+    for (int j = 0; j < n; ++j) {
+        const double an = a[j] + dl[j];
+        dd = fma(dl[j], dl[j], dd); aa = fma(an, an, aa);
+        a[j] = an;
+    }
+    const double step = sqrt(dd);
+    blk[FMPC_REFINE_STEP] = step;
+    blk[FMPC_REFINE_ITERS] += 1.0;
+    if (P.tol > 0.0 && step <= P.tol * (1.0 + sqrt(aa))) *flags |= FMPC_REFINE_CONVERGED;
+}
+
 __global__ void __launch_bounds__(256) fer_final(FerParams P, int iters) {
     __shared__ double sRed[256];
     const int r = blockIdx.x, tid = threadIdx.x, n = P.M.nmode;
@@ -236,6 +360,13 @@ hipError_t fmpc_launch_refine_phi(const FerParams& P, int final, hipStream_t str
     return hipGetLastError();
 }
 
+hipError_t fmpc_launch_refine_phi_many(const FerParams& P, int final, hipStream_t stream) {
+    if (!fer_params_ok(P)) return hipErrorInvalidValue;
+    const size_t npx = (size_t)P.M.len * P.M.len;
+    hipLaunchKernelGGL(fer_phi_many, dim3((unsigned)((npx + 255) / 256), (P.count + FER_PHI_R - 1) / FER_PHI_R), dim3(256), 0, stream, P, final);
+    return hipGetLastError();
+}
+
 hipError_t fmpc_launch_refine_pass(const FerParams& P, int f0, int nf, int final, hipStream_t stream) {
     if (!fer_params_ok(P) || f0 < 0 || nf < 1 || f0 + nf > P.M.nmode + 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(fer_psf, dim3(nf, P.M.len / 16, P.count), dim3(FEM_NW * 64), 0, stream, P, f0, final);
@@ -251,6 +382,12 @@ hipError_t fmpc_launch_refine_pass(const FerParams& P, int f0, int nf, int final
 hipError_t fmpc_launch_refine_step(const FerParams& P, int it, hipStream_t stream) {
     if (!fer_params_ok(P)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(fer_step, dim3(P.count), dim3(256), 0, stream, P, it);
+    return hipGetLastError();
+}
+
+hipError_t fmpc_launch_refine_gain_step(const FerParams& P, int it, hipStream_t stream) {
+    if (!fer_params_ok(P) || !P.G || P.ldG < P.p) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fer_gain_step, dim3((P.count + 15) / 16), dim3(256), 0, stream, P, it);
     return hipGetLastError();
 }
 

@@ -143,24 +143,52 @@ class EstimatorOptics:
             raise FastMPCError(rc, "fmpc_est_model_device")
         return At.t(), b
 
-    def refine_workspace_bytes(self, nmode, batch=1, minimum=False):
-        """Recommended workspace of `refine` in bytes (every field of up to 16 realisations at a time); minimum=True: the
-        smallest it takes (one realisation, one field at a time), whatever the batch."""
-        full = int(self._lib.fmpc_est_refine_workspace_bytes(self._h, int(nmode), int(batch)))
+    def refine_workspace_bytes(self, nmode, batch=1, minimum=False, refresh=1):
+        """Recommended workspace of `refine` in bytes (refresh >= 1: every field of up to 16 realisations at a time; refresh = 0,
+        the gain form: one field of up to 128); minimum=True: the smallest it takes (one realisation, one field at a time),
+        whatever the batch."""
+        if int(refresh) == 0:
+            return int(self._lib.fmpc_est_refine_hold_workspace_bytes(self._h, int(nmode), 1 if minimum else int(batch), 0))
+        if int(refresh) == 1:
+            full = int(self._lib.fmpc_est_refine_workspace_bytes(self._h, int(nmode), int(batch)))
+        else:
+            full = int(self._lib.fmpc_est_refine_hold_workspace_bytes(self._h, int(nmode), int(batch), int(refresh)))
         if not minimum or full == 0:
             return full
         one = int(self._lib.fmpc_est_refine_workspace_bytes(self._h, int(nmode), 1))
         return one - int(nmode) * self.ndiv * (self.len // 16) * 16384
 
-    def refine(self, Z, Y, alpha0=None, iters=3, damping=0.0, tol=0.0, workspace=None, out=None, info=None, status=None):
+    def gain(self, Z):
+        """The estimator's gain about zero aberration for the gain form of `refine`: pinv of `model(Z)`'s A_s as an (nmode, p)
+        contiguous HIP tensor (hand over the maps without the piston).  Runs the model, reads A_s back, takes the
+        pseudo-inverse on the host and uploads it: it synchronises and is not for the hot loop -- call it once and keep G."""
+        import torch
+        A, _ = self.model(Z)
+        torch.cuda.current_stream(Z.device).synchronize()
+        G = np.linalg.pinv(A.cpu().numpy())
+        return torch.from_numpy(np.ascontiguousarray(G)).to(Z.device)
+
+    def refine(self, Z, Y, alpha0=None, iters=3, damping=0.0, tol=0.0, workspace=None, out=None, info=None, status=None, refresh=1,
+               G=None):
         """Gauss-Newton on ||Y_b - y(alpha_b)||^2 with the exact image model (`fmpc_est_refine_device`).  Z: (nmode <= 64, len, len)
         HIP tensor indexed [j, column, row], every map an unknown (no piston); Y: (batch, p) measured images, unit column stride;
         alpha0: (batch, nmode) start, None: zero.  Returns alpha (batch, nmode) on torch's current stream: `out` if given
         (out may be alpha0 itself: refined in place), else a new tensor.  info: (batch, FMPC_REFINE_FIELDS) float64 and
         status: (batch,) int32 tensors to fill, or None.  workspace: a torch.uint8 HIP tensor of at least
-        `refine_workspace_bytes(nmode, minimum=True)`."""
+        `refine_workspace_bytes(nmode, minimum=True, refresh=refresh)`.
+        refresh (`fmpc_est_refine_hold_device`): 1, the default, rebuilds J every iteration (the call above); r > 1 rebuilds it
+        every r-th iteration and holds it in between (one field instead of nmode + 1); 0 is the gain form
+        alpha += G (Y - y(alpha)) without a Jacobian, G: (nmode, p) float64 HIP tensor with unit column stride, None:
+        `gain(Z)` (which synchronises: hand G over in a loop); damping must then be 0.  See include/fastmpc.h for when each
+        converges."""
         import torch
         nmode = self._maps(Z, None)
+        refresh = int(refresh)
+        if refresh == 0:
+            if G is None:
+                G = self.gain(Z)
+            if not G.is_cuda or G.dtype != torch.float64 or G.dim() != 2 or tuple(G.shape) != (nmode, self.p) or (self.p > 1 and G.stride(1) != 1):
+                raise FastMPCError(_lib.FMPC_E_DIM, "G: need a float64 HIP tensor (nmode, p) with unit column stride")
         if not Y.is_cuda or Y.dtype != torch.float64 or Y.dim() != 2 or Y.shape[1] != self.p or (self.p > 1 and Y.stride(1) != 1):
             raise FastMPCError(_lib.FMPC_E_DIM, "Y: need a float64 HIP tensor (batch, p) with unit column stride")
         batch = int(Y.shape[0])
@@ -180,12 +208,20 @@ class EstimatorOptics:
         if batch == 0:                       # (an empty tensor has no pointer to hand over; the library takes batch = 0 and does nothing)
             return alpha
         if workspace is None:
-            workspace = torch.empty(self.refine_workspace_bytes(nmode, batch), dtype=torch.uint8, device=Z.device)
+            workspace = torch.empty(self.refine_workspace_bytes(nmode, batch, refresh=max(refresh, 0)), dtype=torch.uint8, device=Z.device)
         vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        rc = self._lib.fmpc_est_refine_device(self._h, nmode, vp(Z), batch, vp(Y), ldY, vp(alpha), int(iters), float(damping), float(tol),
-                                              vp(info), vp(status), vp(workspace), workspace.numel(), _stream(Z.device))
+        if refresh == 1:
+            name = "fmpc_est_refine_device"
+            rc = self._lib.fmpc_est_refine_device(self._h, nmode, vp(Z), batch, vp(Y), ldY, vp(alpha), int(iters), float(damping), float(tol),
+                                                  vp(info), vp(status), vp(workspace), workspace.numel(), _stream(Z.device))
+        else:
+            name = "fmpc_est_refine_hold_device"
+            ldG = (int(G.stride(0)) if nmode > 1 else self.p) if refresh == 0 else 0
+            rc = self._lib.fmpc_est_refine_hold_device(self._h, nmode, vp(Z), batch, vp(Y), ldY, vp(alpha), int(iters), refresh,
+                                                       vp(G) if refresh == 0 else None, ldG, float(damping), float(tol), vp(info), vp(status),
+                                                       vp(workspace), workspace.numel(), _stream(Z.device))
         if rc != _lib.FMPC_OK:
-            raise FastMPCError(rc, "fmpc_est_refine_device")
+            raise FastMPCError(rc, name)
         return alpha
 
     def estimator(self, Z, skip=1, phi0=None):
