@@ -1203,6 +1203,54 @@ int fmpc_est_refine_hold_device(fmpc_est_optics o, int nmode, const double* Z, i
                                 int iters, int refresh, const double* G, long long ldG, double damping, double tol, double* info,
                                 int* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * The refinement weighted by the detector's photon and read-out noise.  ||Y - y(alpha)||^2 is the maximum-likelihood fit only
+ * when every measurement has the same variance; behind a detector (fmpc_detector above) the variance follows the signal, and the
+ * PSF window spans nine decades.  fmpc_est_refine_weighted_device is fmpc_est_refine_hold_device with refresh >= 1 and every row
+ * k weighted by the variance the detector gives the MODEL image at the current alpha_b (not the data: Fisher scoring, the
+ * Gaussian form of the Poisson likelihood).  Per realisation b, gain_b = det->gain or det->gain_dev[b]:
+ *
+ *     mu_k  = qe y_k(alpha)                                   the mean of Y_M: the detector scales the image by qe
+ *     lam_k = gain_b max(y_k(alpha), 0) + background          expected photo-electrons
+ *     var_k = (qe^2 (photon_noise ? max(lam_k, floor) : 0) + read_noise^2) / gain_b^2 ,   w_k = 1 / var_k
+ *     r = Y_b - mu ;  H = qe^2 J' W J ,  H_ii <- H_ii (1 + damping) ;  g = qe J' W r ;  alpha_b <- alpha_b + H \ g
+ *     chi^2 = sum_k w_k r_k^2
+ *
+ * Rounding     each product, sum and quotient is rounded once (the kernels form them with contraction off), in this order: qe2 = qe qe, rn2 = read_noise read_noise,
+ *              g2 = gain_b gain_b; per row gain_b max(y_k, 0), + background, the max with floor, qe2 x that, + rn2, / g2,
+ *              w_k = 1 / that, s_k = sqrt(w_k); qe y_k, r_k = Y_k - that.  Row k of [qe J  r] enters the products as
+ *              s_k (qe J_kj) (two roundings) and s_k r_k; a term of chi^2 is fma(w_k r_k, r_k, .).  With qe = 1 the mean and the
+ *              residual are those of the unweighted calls.
+ * floor        >= 0, photo-electrons: the photon variance of a row is never taken below it (1 = one photo-electron is the
+ *              usual choice; 0 with read_noise > 0 is the exact model).  det->seed, step, step_dev and first are ignored.
+ * refresh      >= 1, as for fmpc_est_refine_hold_device; the weights are formed from the current y(alpha_b) in every iteration,
+ *              held ones included (a held iteration re-forms H from the held J with the current weights).  refresh = 0 is
+ *              refused: the gain form has no weighted G.
+ * info         FMPC_REFINE_COST0 and FMPC_REFINE_COST are chi^2 at alpha_in and alpha_out, each with the weights of its own
+ *              alpha: against p - nmode a goodness-of-fit test.  FMPC_REFINE_STEP and FMPC_REFINE_ITERS as above.
+ * sigma        NULL, or batch x nmode on the device: sqrt(diag(H^-1)) of the last step the realisation took, H (damped) at
+ *              that step's linearisation point -- for damping = 0 the Cramer-Rao bound of every coefficient there.  It is
+ *              computed in the step kernel from the factor in LDS (the unit upper factor inverted by columns, one column per
+ *              thread, every sum in a fixed order), only when asked for.  A realisation that took no step gets NaN.
+ * status       FMPC_REFINE_BAD_INPUT also for a gain_b, a weight or a chi^2 that is not positive and finite, on that row alone and
+ *              with the rules above (alpha_b, both chi^2 and sigma NaN).  FMPC_REFINE_CONVERGED and FMPC_REFINE_FACTOR_FAILED as above.
+ * Z, Y, alpha, iters, damping, tol, the freeze rules, the workspace (fmpc_est_refine_weighted_workspace_bytes is
+ * fmpc_est_refine_hold_workspace_bytes for refresh >= 1, with the same minimum, panels and 4-slot form: the weights need no
+ * space) are as above.  No allocation, no synchronisation, no read-back: graph-recordable.  A realisation's alpha, info, status
+ * and sigma are bitwise the same whatever the batch, its place in it, the workspace and the call, and the same with a scalar
+ * gain as with that gain in gain_dev.  There is no host-pointer, bank, sharded or MATLAB form of this call, and no gain form.
+ * Answered before the device is touched, in this order: FMPC_E_NULL as above, and for a NULL det; FMPC_E_DIM as above, for
+ * refresh < 1, for a floor, read_noise, background or gain that is negative or not finite, for qe <= 0 or not finite, for
+ * gain == 0 without gain_dev, and where nothing bounds the variance from below: photon_noise ? floor + read_noise^2 :
+ * read_noise^2 is not > 0; FMPC_E_UNSUPPORTED for nmode > 64; then, with o's dimensions, FMPC_E_DIM for ldY < p or a workspace
+ * below the minimum.  batch = 0 does nothing.  fmpc_est_refine_weighted_workspace_bytes is 0 for refused arguments.
+ */
+size_t fmpc_est_refine_weighted_workspace_bytes(fmpc_est_optics o, int nmode, int batch, int refresh);
+int fmpc_est_refine_weighted_device(fmpc_est_optics o, int nmode, const double* Z, int batch, const double* Y, long long ldY,
+                                    double* alpha, int iters, int refresh, const fmpc_detector* det, double floor,
+                                    double damping, double tol, double* info, int* status, double* sigma,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
 /*
  * Deformable mirror of Gaussian actuators on the device: the reference's section "The influence matrix of Deformable Mirror (DM)
  * generation" (README.md:184-272) and the surface such a mirror makes.  A mirror is m actuators with centres (cx_t, cy_t), a

@@ -166,6 +166,9 @@ SIGNATURES = {
     "fmpc_est_refine_hold_workspace_bytes": (C.c_size_t, [_vp, C.c_int, C.c_int, C.c_int]),
     "fmpc_est_refine_hold_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_longlong, _vp, C.c_int, C.c_int, _vp, C.c_longlong,
                                               C.c_double, C.c_double, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fmpc_est_refine_weighted_workspace_bytes": (C.c_size_t, [_vp, C.c_int, C.c_int, C.c_int]),
+    "fmpc_est_refine_weighted_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_longlong, _vp, C.c_int, C.c_int, C.POINTER(Detector),
+                                                  C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fmpc_dm_influence_device": (C.c_int, [C.c_int] * 3 + [_vp] * 4 + [C.c_double] * 2 + [C.c_int] * 2 + [_vp, C.c_longlong, _vp]),
     "fmpc_dm_matrix_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "fmpc_dm_matrix_device": (C.c_int, [C.c_int] * 4 + [_vp] * 6 + [C.c_double] * 2 + [C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp]),

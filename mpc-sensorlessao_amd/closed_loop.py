@@ -203,7 +203,11 @@ class AOLoop:
     (`EstimatorOptics.refine` over the loop's own Z, the start the linear estimate) before the solve; `refine_info`
     (batch, FMPC_REFINE_FIELDS) and `refine_status` (batch,) hold the last call's rows; nothing else changes.  Not with sensor=.
     Two further keys are optional: refresh (1: J every iteration; r > 1: every r-th, held in between; 0: the gain form without a
-    Jacobian, damping 0) and G, the gain form's (n, p) matrix (None: `optics.gain(Z)`, computed once here)."""
+    Jacobian, damping 0) and G, the gain form's (n, p) matrix (None: `optics.gain(Z)`, computed once here).
+    weighted=True (with floor=1.0, refresh >= 1): a step whose `noise` is a `DetectorNoise` refines with that detector's
+    parameters (`EstimatorOptics.refine(detector=noise, floor=)`: the fit weighted by the photon and read-out variance);
+    `refine_info` then holds chi^2 and `refine_sigma` (batch, n) the predicted standard deviation of x0; a step with another
+    kind of noise, or none, raises.  Without the key every path is as above."""
 
     def __init__(self, handle, estimator, Z, batch, n_newton=1, k=1e-2, one_call=True, modal=None, z_colmajor=False, science=None, sensor=None,
                  refine=None, dm=None):
@@ -258,9 +262,9 @@ class AOLoop:
         if refine is not None:
             if sensor is not None:
                 raise ValueError("refine: the refinement works on the estimator's images; not together with sensor=")
-            unknown = set(refine) - {"optics", "iters", "damping", "tol", "refresh", "G"}
+            unknown = set(refine) - {"optics", "iters", "damping", "tol", "refresh", "G", "weighted", "floor"}
             if unknown or "optics" not in refine:
-                raise ValueError("refine: need dict(optics=, iters=, damping=, tol=[, refresh=, G=])")
+                raise ValueError("refine: need dict(optics=, iters=, damping=, tol=[, refresh=, G=, weighted=, floor=])")
             opt = refine["optics"]
             if (opt.len, opt.p) != (estimator.len, estimator.p):
                 raise ValueError("refine: need an EstimatorOptics of the estimator's grid, window and diversities")
@@ -268,11 +272,20 @@ class AOLoop:
             refresh = int(refine.get("refresh", 1))
             if refresh < 0:
                 raise ValueError("refine: refresh >= 0")
+            weighted = bool(refine.get("weighted", False))
+            if weighted and refresh < 1:
+                raise ValueError("refine: the weighted fit needs refresh >= 1 (the gain form has no weighted G)")
+            if "floor" in refine and not weighted:
+                raise ValueError("refine: floor= is the weighted fit's")
             G = refine.get("G")
             if refresh == 0 and G is None:   # the gain about zero aberration, once (it synchronises)
                 G = opt.gain(self.Z)
             self.refine = dict(optics=opt, iters=int(refine.get("iters", 3)), damping=float(refine.get("damping", 0.0)), tol=float(refine.get("tol", 0.0)),
-                               refresh=refresh, G=G if refresh == 0 else None)
+                               refresh=refresh, G=G if refresh == 0 else None, weighted=weighted, floor=float(refine.get("floor", 1.0)))
+            if weighted:
+                from .estimator import DetectorNoise
+                self._DetectorNoise = DetectorNoise
+                self.refine_sigma = torch.full((batch, n), float("nan"), **f64)
             self.refine_info = torch.zeros((batch, FMPC_REFINE_FIELDS), **f64)
             self.refine_status = torch.zeros(batch, dtype=torch.int32, device=dev)
             self._refine_ws = torch.empty(opt.refine_workspace_bytes(n, batch, refresh=refresh), dtype=torch.uint8, device=dev)
@@ -333,8 +346,15 @@ class AOLoop:
         if self.refine is not None:          # the linear estimate, then Gauss-Newton on the images it was made from
             Y = self.est.apply_device(self.scrn, noise, want_Y=True, colmajor=True, out=self.x0, step=s)[1]
             rf = self.refine
-            rf["optics"].refine(self.Z, Y, alpha0=self.x0, out=self.x0, iters=rf["iters"], damping=rf["damping"], tol=rf["tol"],
-                                info=self.refine_info, status=self.refine_status, workspace=self._refine_ws, refresh=rf["refresh"], G=rf["G"])
+            if rf["weighted"]:
+                if not isinstance(noise, self._DetectorNoise):
+                    raise TypeError("step: refine=dict(weighted=True) takes its weights from the step's DetectorNoise")
+                rf["optics"].refine(self.Z, Y, alpha0=self.x0, out=self.x0, iters=rf["iters"], damping=rf["damping"], tol=rf["tol"],
+                                    info=self.refine_info, status=self.refine_status, workspace=self._refine_ws, refresh=rf["refresh"],
+                                    detector=noise, floor=rf["floor"], sigma=self.refine_sigma)
+            else:
+                rf["optics"].refine(self.Z, Y, alpha0=self.x0, out=self.x0, iters=rf["iters"], damping=rf["damping"], tol=rf["tol"],
+                                    info=self.refine_info, status=self.refine_status, workspace=self._refine_ws, refresh=rf["refresh"], G=rf["G"])
         elif self.sensor is None:
             self.est.apply_device(self.scrn, noise, colmajor=True, out=self.x0, step=s)
         elif noise is None:                  # what a wavefront sensor measures on the same residual screen

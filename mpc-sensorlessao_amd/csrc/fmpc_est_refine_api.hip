@@ -1,4 +1,5 @@
-// C ABI of the estimator's Gauss-Newton refinement (include/fastmpc.h: fmpc_est_refine_*, fmpc_est_refine_hold_*).  The argument
+// C ABI of the estimator's Gauss-Newton refinement (include/fastmpc.h: fmpc_est_refine_*, fmpc_est_refine_hold_*,
+// fmpc_est_refine_weighted_*).  The argument
 // rules answer here, before the device is touched; the call only records launches: no allocation, no synchronisation, no
 // read-back.  Kernels: fmpc_kernel_est_refine.hip.
 #include <hip/hip_runtime.h>
@@ -42,14 +43,30 @@ extern "C" size_t fmpc_est_refine_hold_workspace_bytes(fmpc_est_optics o, int nm
     return held * blk;
 }
 
-// The plan of both calls.  refresh >= 1: iteration `it` evaluates every field when it % refresh == 0 and field 0 alone
-// otherwise (the J in the block is then the one of the last full iteration); refresh == 0: the gain form.
+extern "C" size_t fmpc_est_refine_weighted_workspace_bytes(fmpc_est_optics o, int nmode, int batch, int refresh) {
+    return refresh < 1 ? 0 : fmpc_est_refine_workspace_bytes(o, nmode, batch);
+}
+
+static bool refine_real_ok(double x) { return x >= 0.0 && !isinf(x); }      // not negative, finite (a NaN fails the comparison)
+
+// The plan of the three calls.  refresh >= 1: iteration `it` evaluates every field when it % refresh == 0 and field 0 alone
+// otherwise (the J in the block is then the one of the last full iteration); refresh == 0: the gain form.  `weighted`: the rows
+// weighted by det's variance at the model image (refresh >= 1 alone); the plan and the blocks are the same, the weights take no
+// space.
 static int refine_run(fmpc_est_optics o, int nmode, const double* Z, int batch, const double* Y, long long ldY, double* alpha, int iters,
                       int refresh, const double* G, long long ldG, double damping, double tol, double* info, int* status,
-                      void* workspace, size_t workspace_bytes, void* stream) {
-    if (!o || !Z || !Y || !alpha || !workspace || (refresh == 0 && !G)) return FMPC_E_NULL;
+                      void* workspace, size_t workspace_bytes, void* stream, bool weighted = false, const fmpc_detector* det = nullptr,
+                      double floor = 0.0, double* sigma = nullptr) {
+    if (!o || !Z || !Y || !alpha || !workspace || (refresh == 0 && !G && !weighted) || (weighted && !det)) return FMPC_E_NULL;
     if (nmode <= 0 || batch < 0 || iters < 0 || !(damping >= 0.0) || !(tol >= 0.0) || isinf(damping) || isinf(tol)) return FMPC_E_DIM;
-    if (refresh < 0 || (refresh == 0 && damping != 0.0)) return FMPC_E_DIM;
+    if (refresh < 0 || (refresh == 0 && (weighted || damping != 0.0))) return FMPC_E_DIM;
+    if (weighted) {
+        if (!refine_real_ok(floor) || !refine_real_ok(det->read_noise) || !refine_real_ok(det->background) || !refine_real_ok(det->gain)) return FMPC_E_DIM;
+        if (!(det->qe > 0.0) || isinf(det->qe)) return FMPC_E_DIM;
+        if (det->gain == 0.0 && !det->gain_dev) return FMPC_E_DIM;
+        // nothing else bounds the variance from below
+        if (!((det->photon_noise ? floor + det->read_noise * det->read_noise : det->read_noise * det->read_noise) > 0.0)) return FMPC_E_DIM;
+    }
     if (nmode > FER_MAXMODE) return FMPC_E_UNSUPPORTED;
     const bool gain = refresh == 0;
     const int p = o->ndiv * o->d * o->d;
@@ -88,12 +105,19 @@ static int refine_run(fmpc_est_optics o, int nmode, const double* Z, int batch, 
     P.oPart = gain ? P.oJ : P.oJ + (size_t)p * nmode;        // (the gain form's block holds no J: field 0 never writes one)
     P.p = p; P.ldY = ldY; P.damping = damping; P.tol = tol;
     P.G = gain ? G : nullptr; P.ldG = gain ? ldG : 0;
+    if (weighted) {
+        P.qe = det->qe; P.background = det->background; P.read_noise = det->read_noise; P.gain = det->gain; P.floor = floor;
+        P.photon_noise = det->photon_noise != 0;
+    }
+    hipError_t (*const step)(const FerParams&, int, hipStream_t) = weighted ? fmpc_launch_refine_step_weighted : fmpc_launch_refine_step;
+    hipError_t (*const last)(const FerParams&, int, hipStream_t) = weighted ? fmpc_launch_refine_final_weighted : fmpc_launch_refine_final;
     // phi_b of a panel: the existing call keeps its kernel; the schedules of this file's second call read a map once for 8 realisations
     hipError_t (*const phi)(const FerParams&, int, hipStream_t) = refresh == 1 ? fmpc_launch_refine_phi : fmpc_launch_refine_phi_many;
     for (int r0 = 0; r0 < batch; r0 += held_r) {
         P.count = batch - r0 < held_r ? batch - r0 : held_r;
         P.Y = Y + (size_t)r0 * ldY; P.alpha = alpha + (size_t)r0 * nmode;
         P.info = info ? info + (size_t)r0 * FMPC_REFINE_FIELDS : nullptr; P.status = status ? status + r0 : nullptr;
+        if (weighted) { P.gain_dev = det->gain_dev ? det->gain_dev + r0 : nullptr; P.sigma = sigma ? sigma + (size_t)r0 * nmode : nullptr; }
         if (fmpc_launch_refine_init(P, st) != hipSuccess) return FMPC_E_HIP;
         for (int it = 0; it < iters; ++it) {
             if (phi(P, 0, st) != hipSuccess) return FMPC_E_HIP;
@@ -106,11 +130,11 @@ static int refine_run(fmpc_est_optics o, int nmode, const double* Z, int batch, 
                 const int nf = fields - f0 < held_f ? fields - f0 : held_f;
                 if (fmpc_launch_refine_pass(P, f0, nf, 0, st) != hipSuccess) return FMPC_E_HIP;
             }
-            if (fmpc_launch_refine_step(P, it, st) != hipSuccess) return FMPC_E_HIP;
+            if (step(P, it, st) != hipSuccess) return FMPC_E_HIP;
         }
         // the cost at alpha_out: field 0 alone, for every realisation of the panel
         if (phi(P, 1, st) != hipSuccess || fmpc_launch_refine_pass(P, 0, 1, 1, st) != hipSuccess ||
-            fmpc_launch_refine_final(P, iters, st) != hipSuccess) return FMPC_E_HIP;
+            last(P, iters, st) != hipSuccess) return FMPC_E_HIP;
     }
     return FMPC_OK;
 }
@@ -125,4 +149,12 @@ extern "C" int fmpc_est_refine_hold_device(fmpc_est_optics o, int nmode, const d
                                            double* alpha, int iters, int refresh, const double* G, long long ldG, double damping,
                                            double tol, double* info, int* status, void* workspace, size_t workspace_bytes, void* stream) {
     return refine_run(o, nmode, Z, batch, Y, ldY, alpha, iters, refresh, G, ldG, damping, tol, info, status, workspace, workspace_bytes, stream);
+}
+
+extern "C" int fmpc_est_refine_weighted_device(fmpc_est_optics o, int nmode, const double* Z, int batch, const double* Y, long long ldY,
+                                               double* alpha, int iters, int refresh, const fmpc_detector* det, double floor,
+                                               double damping, double tol, double* info, int* status, double* sigma,
+                                               void* workspace, size_t workspace_bytes, void* stream) {
+    return refine_run(o, nmode, Z, batch, Y, ldY, alpha, iters, refresh, nullptr, 0, damping, tol, info, status, workspace, workspace_bytes, stream,
+                      true, det, floor, sigma);
 }

@@ -116,6 +116,12 @@ struct FerParams {
     // ---- the gain form (fmpc_est_refine_hold_device, refresh = 0): behind everything the Gauss-Newton kernels read.  A block
     //      then holds no J: [header] [phi] [base] [y: p] [part: one slot]
     const double* G = nullptr; long long ldG = 0;      // nmode x p, row j at G + j ldG
+    // ---- the weighted form (fmpc_est_refine_weighted_device): the scalars of the fmpc_detector, the floor of the photon
+    //      variance in photo-electrons, the panel's first gain (NULL: `gain` for all) and first row of sigma (NULL: not asked for)
+    double qe = 1.0, background = 0.0, read_noise = 0.0, gain = 1.0, floor = 0.0;
+    int photon_noise = 0;
+    const double* gain_dev = nullptr;
+    double* sigma = nullptr;
 };
 hipError_t fmpc_launch_refine_init(const FerParams& P, hipStream_t stream);
 // phi_b into the blocks; then as fmpc_launch_est_model_pass for every realisation.  final: the frozen realisations too.
@@ -126,3 +132,6 @@ hipError_t fmpc_launch_refine_step(const FerParams& P, int it, hipStream_t strea
 // the gain form's step of a panel, alpha_b <- alpha_b + G (Y_b - y_b): 16 realisations per workgroup
 hipError_t fmpc_launch_refine_gain_step(const FerParams& P, int it, hipStream_t stream);
 hipError_t fmpc_launch_refine_final(const FerParams& P, int iters, hipStream_t stream);
+// the step and the last pass with the rows weighted by the detector's variance at the model image; the step writes sigma on request
+hipError_t fmpc_launch_refine_step_weighted(const FerParams& P, int it, hipStream_t stream);
+hipError_t fmpc_launch_refine_final_weighted(const FerParams& P, int iters, hipStream_t stream);

@@ -15,6 +15,10 @@
 //             field-0 pass before it writes y, I_k and slot 0 alone.
 // fer_gain_step: the step without a Jacobian, alpha_b <- alpha_b + G (Y_b - y_b), for 16 realisations per workgroup (below).
 // fer_final:  the cost at alpha_out from field 0 alone, and the rows of info and status.
+// fer_step<true>, fer_final<true>: the forms of fmpc_est_refine_weighted_device, every row k weighted by the detector's variance
+//             at the model image (fer_weight below fixes the roundings, under contract(off)): lane (g, c) scales its operands of
+//             the MFMA by s_k = sqrt(w_k), so the products are qe^2 J' W J and qe J' W r; the cost is chi^2 = sum_k w_k r_k^2; on request
+//             sqrt(diag(H^-1)) comes from the factor while it is in LDS.  The <false> instances are the code they were.
 // The status bits of a realisation live in its block; a workgroup of any of these kernels leaves at once when they are set.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -36,6 +40,8 @@ __global__ void fer_init(FerParams P) {
     if (r >= P.count) return;
     double* blk = fer_block(P, r);
     for (int i = 0; i < FER_HDR; ++i) blk[i] = 0.0;          // (flags: the int 0 is the double 0's low word)
+    if (P.sigma)                                             // (the weighted call: NaN until the realisation takes a step)
+        for (int j = 0; j < P.M.nmode; ++j) P.sigma[(size_t)r * P.M.nmode + j] = __builtin_nan("");
 }
 
 __global__ void __launch_bounds__(256) fer_phi(FerParams P, int final) {
@@ -120,6 +126,71 @@ __device__ __forceinline__ double fer_cost(const double* Yb, const double* y, in
 
 __device__ __forceinline__ bool fer_finite(double x) { return fabs(x) <= 1.79769313486231570815e+308; }
 
+// The weights of fmpc_est_refine_weighted_device for realisation r of the panel.  Every product, sum and quotient is rounded
+// once, in the order written; the functions that form them are compiled under contract(off), as fmpc_detector.h is, so no
+// product is fused into the sum behind it:
+//     qe2 = qe qe ;  rn2 = read_noise read_noise ;  g2 = gain_r gain_r                         per realisation
+//     lam = gain_r max(y_k, 0) + background ;  v = photon_noise ? max(lam, floor) : 0
+//     var = (qe2 v + rn2) / g2 ;  w_k = 1 / var ;  s_k = sqrt(w_k) ;  r_k = Y_k - qe y_k
+struct FerWeights {
+    double qe, qe2, rn2, g2, gain, background, floor;
+    int photon;
+    bool ok;                                                 // gain_r positive and finite
+};
+__device__ __forceinline__ FerWeights fer_weights(const FerParams& P, int r) {
+#pragma clang fp contract(off)
+    FerWeights W;
+    W.gain = P.gain_dev ? P.gain_dev[r] : P.gain;
+    W.ok = W.gain > 0.0 && fer_finite(W.gain);
+    W.qe = P.qe; W.background = P.background; W.floor = P.floor; W.photon = P.photon_noise;
+    W.qe2 = P.qe * P.qe; W.rn2 = P.read_noise * P.read_noise; W.g2 = W.gain * W.gain;
+    return W;
+}
+__device__ __forceinline__ double fer_weight(const FerWeights& W, double y) {
+#pragma clang fp contract(off)
+    const double gy = W.gain * (y > 0.0 ? y : 0.0);
+    const double lam = gy + W.background;
+    const double v = W.photon ? (lam > W.floor ? lam : W.floor) : 0.0;
+    const double qv = W.qe2 * v;
+    const double var = (qv + W.rn2) / W.g2;
+    return 1.0 / var;
+}
+// r_k = Y_k - qe y_k: the product rounded, then the difference
+__device__ __forceinline__ double fer_residual(const FerWeights& W, double Y, double y) {
+#pragma clang fp contract(off)
+    const double qy = W.qe * y;
+    return Y - qy;
+}
+// row k of [qe J  r] times s_k: s_k (qe J_kj), two roundings, and s_k r_k
+__device__ __forceinline__ double fer_scale_j(const FerWeights& W, double s, double j) {
+#pragma clang fp contract(off)
+    const double qj = W.qe * j;
+    return s * qj;
+}
+
+// chi^2 = sum_k w_k r_k^2 of a realisation, the term fma(w_k r_k, r_k, .) with w_k r_k rounded, in fer_cost's order; NaN when the
+// gain, a weight or the sum itself is not positive and finite (the callers' BAD_INPUT path).
+__device__ __forceinline__ double fer_cost_weighted(const FerWeights& W, const double* Yb, const double* y, int p, double* sRed) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    double s = W.ok ? 0.0 : __builtin_nan("");
+    for (int k = tid; k < p; k += 256) {
+        const double yk = y[k], r = fer_residual(W, Yb[k], yk), w = fer_weight(W, yk);
+        const double wr = w * r;
+        s = w > 0.0 && fer_finite(w) ? fma(wr, r, s) : __builtin_nan("");
+    }
+    sRed[tid] = s;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (tid < w) sRed[tid] += sRed[tid + w];
+        __syncthreads();
+    }
+    const double c = sRed[0];
+    __syncthreads();
+    return c > 0.0 ? c : __builtin_nan("");
+}
+
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(256) fer_step(FerParams P, int it) {
     __shared__ double sH[64 * FER_SH];
     __shared__ double sRed[256];
@@ -134,7 +205,11 @@ __global__ void __launch_bounds__(256) fer_step(FerParams P, int it) {
     double* a = P.alpha + (size_t)r * n;
     int* flags = (int*)(blk + FER_FLAG);
 
-    const double cost = fer_cost(Yb, y, p, sRed);
+    [[maybe_unused]] FerWeights W;
+    if constexpr (WEIGHTED) W = fer_weights(P, r);
+    double cost;
+    if constexpr (WEIGHTED) cost = fer_cost_weighted(W, Yb, y, p, sRed);
+    else cost = fer_cost(Yb, y, p, sRed);
     if (it == 0 && tid == 0) blk[FMPC_REFINE_COST0] = cost;
     if (!fer_finite(cost)) {                                 // a phase beyond the range, a NaN in Y or in alpha: the row is NaN
         if (tid < n) a[tid] = __builtin_nan("");
@@ -154,6 +229,9 @@ __global__ void __launch_bounds__(256) fer_step(FerParams P, int it) {
     const int q0 = (int)((long long)kq * wv / 4), q1 = (int)((long long)kq * (wv + 1) / 4);
     for (int q = q0; q < q1; ++q) {
         const int k = 4 * q + g;
+        [[maybe_unused]] double yk = 0.0, Yk = 0.0;          // (the weighted form: its two operands are asked for ahead of J's)
+        if constexpr (WEIGHTED)
+            if (k < p) { yk = y[k]; Yk = Yb[k]; }
         double v[5];
 #pragma unroll
         for (int t = 0; t < 5; ++t) {
@@ -161,9 +239,20 @@ __global__ void __launch_bounds__(256) fer_step(FerParams P, int it) {
             double x = 0.0;
             if (t < ntc && k < p) {
                 if (jj < n) x = J[(size_t)jj * p + k];
-                else if (jj == n) x = Yb[k] - y[k];
+                else if (!WEIGHTED && jj == n) x = Yb[k] - y[k];
             }
             v[t] = x;
+        }
+        if constexpr (WEIGHTED) {                            // row k of [qe J  r] times s_k; s_k needs y_k alone, not the J loads above
+            const double sk = k < p ? sqrt(fer_weight(W, yk)) : 0.0;
+#pragma unroll
+            for (int t = 0; t < 5; ++t) {
+                const int jj = 16 * t + c;
+                if (t < ntc && k < p) {
+                    if (jj < n) v[t] = fer_scale_j(W, sk, v[t]);
+                    else if (jj == n) v[t] = sk * fer_residual(W, Yk, yk);
+                }
+            }
         }
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt)
@@ -212,6 +301,31 @@ __global__ void __launch_bounds__(256) fer_step(FerParams P, int it) {
         if (tid < kk) sH[tid * FER_SH + n] -= sH[tid * FER_SH + kk] * x;
         if (tid == kk) sD[kk] = x;
         __syncthreads();
+    }
+    if constexpr (WEIGHTED) {
+        // ---- sqrt(diag(H^-1)) on request.  The rows left in sH are R = D U (H = R' D^-1 R, R_kk = D_k), so H^-1 = R^-1 D R^-T and
+        //      (H^-1)_ii = sum_{k >= i} X_ik^2 D_k with X = R^-1.  Thread k < n makes column k of X by back substitution, the
+        //      sums over j descending, and keeps X_ik, i < k, at sH[k][i]: the strict lower triangle, which nobody else uses.
+        //      Then thread i sums its row over k ascending.
+        if (P.sigma) {
+            if (tid < n) {
+                const double xk = 1.0 / sH[tid * FER_SH + tid];
+                for (int i = tid - 1; i >= 0; --i) {
+                    double s = sH[i * FER_SH + tid] * xk;
+                    for (int j = tid - 1; j > i; --j) s = fma(sH[i * FER_SH + j], sH[tid * FER_SH + j], s);
+                    sH[tid * FER_SH + i] = -s / sH[i * FER_SH + i];
+                }
+            }
+            __syncthreads();
+            if (tid < n) {
+                double acc = 0.0;
+                for (int k = tid; k < n; ++k) {
+                    const double d = sH[k * FER_SH + k], x = k == tid ? 1.0 / d : sH[k * FER_SH + tid];
+                    acc = fma(x * x, d, acc);
+                }
+                P.sigma[(size_t)r * n + tid] = sqrt(acc);
+            }
+        }
     }
     if (tid == 0) {
         double dd = 0.0, aa = 0.0;
@@ -318,17 +432,22 @@ __global__ void __launch_bounds__(256) fer_gain_step(FerParams P, int it) {
     if (P.tol > 0.0 && step <= P.tol * (1.0 + sqrt(aa))) *flags |= FMPC_REFINE_CONVERGED;
 }
 
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(256) fer_final(FerParams P, int iters) {
     __shared__ double sRed[256];
     const int r = blockIdx.x, tid = threadIdx.x, n = P.M.nmode;
     double* blk = fer_block(P, r);
     int fl = fer_flags(blk);
-    double cost = fer_cost(P.Y + (size_t)r * P.ldY, blk + P.oY, P.p, sRed);
+    double cost;
+    if constexpr (WEIGHTED) cost = fer_cost_weighted(fer_weights(P, r), P.Y + (size_t)r * P.ldY, blk + P.oY, P.p, sRed);
+    else cost = fer_cost(P.Y + (size_t)r * P.ldY, blk + P.oY, P.p, sRed);
     const bool bad = (fl & FMPC_REFINE_BAD_INPUT) || !fer_finite(cost);
     if (bad) {
         fl |= FMPC_REFINE_BAD_INPUT;
         cost = __builtin_nan("");
         if (iters > 0 && tid < n) P.alpha[(size_t)r * n + tid] = cost;
+        if constexpr (WEIGHTED)
+            if (P.sigma && tid < n) P.sigma[(size_t)r * n + tid] = cost;
     }
     if (tid == 0) {
         if (P.info) {
@@ -381,7 +500,19 @@ hipError_t fmpc_launch_refine_pass(const FerParams& P, int f0, int nf, int final
 
 hipError_t fmpc_launch_refine_step(const FerParams& P, int it, hipStream_t stream) {
     if (!fer_params_ok(P)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(fer_step, dim3(P.count), dim3(256), 0, stream, P, it);
+    hipLaunchKernelGGL(fer_step<false>, dim3(P.count), dim3(256), 0, stream, P, it);
+    return hipGetLastError();
+}
+
+// the detector scalars of the weighted kernels (the C ABI has answered them already; a kernel reads gain_dev[r], r < count)
+static bool fer_weights_ok(const FerParams& P) {
+    return P.qe > 0.0 && P.background >= 0.0 && P.read_noise >= 0.0 && P.floor >= 0.0 && (P.gain_dev || P.gain > 0.0) &&
+           (P.photon_noise ? P.floor + P.read_noise * P.read_noise : P.read_noise * P.read_noise) > 0.0;
+}
+
+hipError_t fmpc_launch_refine_step_weighted(const FerParams& P, int it, hipStream_t stream) {
+    if (!fer_params_ok(P) || !fer_weights_ok(P)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fer_step<true>, dim3(P.count), dim3(256), 0, stream, P, it);
     return hipGetLastError();
 }
 
@@ -393,6 +524,12 @@ hipError_t fmpc_launch_refine_gain_step(const FerParams& P, int it, hipStream_t 
 
 hipError_t fmpc_launch_refine_final(const FerParams& P, int iters, hipStream_t stream) {
     if (!fer_params_ok(P)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(fer_final, dim3(P.count), dim3(256), 0, stream, P, iters);
+    hipLaunchKernelGGL(fer_final<false>, dim3(P.count), dim3(256), 0, stream, P, iters);
+    return hipGetLastError();
+}
+
+hipError_t fmpc_launch_refine_final_weighted(const FerParams& P, int iters, hipStream_t stream) {
+    if (!fer_params_ok(P) || !fer_weights_ok(P)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fer_final<true>, dim3(P.count), dim3(256), 0, stream, P, iters);
     return hipGetLastError();
 }

@@ -143,10 +143,16 @@ class EstimatorOptics:
             raise FastMPCError(rc, "fmpc_est_model_device")
         return At.t(), b
 
-    def refine_workspace_bytes(self, nmode, batch=1, minimum=False, refresh=1):
+    def refine_workspace_bytes(self, nmode, batch=1, minimum=False, refresh=1, detector=None):
         """Recommended workspace of `refine` in bytes (refresh >= 1: every field of up to 16 realisations at a time; refresh = 0,
         the gain form: one field of up to 128); minimum=True: the smallest it takes (one realisation, one field at a time),
-        whatever the batch."""
+        whatever the batch.  detector=: the size of the weighted call (that of the same refresh >= 1; 0 for refresh = 0, which
+        it refuses)."""
+        if detector is not None:
+            full = int(self._lib.fmpc_est_refine_weighted_workspace_bytes(self._h, int(nmode), int(batch), int(refresh)))
+            if not minimum or full == 0:
+                return full
+            return self.refine_workspace_bytes(nmode, batch, minimum=True)
         if int(refresh) == 0:
             return int(self._lib.fmpc_est_refine_hold_workspace_bytes(self._h, int(nmode), 1 if minimum else int(batch), 0))
         if int(refresh) == 1:
@@ -169,7 +175,7 @@ class EstimatorOptics:
         return torch.from_numpy(np.ascontiguousarray(G)).to(Z.device)
 
     def refine(self, Z, Y, alpha0=None, iters=3, damping=0.0, tol=0.0, workspace=None, out=None, info=None, status=None, refresh=1,
-               G=None):
+               G=None, detector=None, floor=1.0, sigma=None):
         """Gauss-Newton on ||Y_b - y(alpha_b)||^2 with the exact image model (`fmpc_est_refine_device`).  Z: (nmode <= 64, len, len)
         HIP tensor indexed [j, column, row], every map an unknown (no piston); Y: (batch, p) measured images, unit column stride;
         alpha0: (batch, nmode) start, None: zero.  Returns alpha (batch, nmode) on torch's current stream: `out` if given
@@ -180,11 +186,18 @@ class EstimatorOptics:
         every r-th iteration and holds it in between (one field instead of nmode + 1); 0 is the gain form
         alpha += G (Y - y(alpha)) without a Jacobian, G: (nmode, p) float64 HIP tensor with unit column stride, None:
         `gain(Z)` (which synchronises: hand G over in a loop); damping must then be 0.  See include/fastmpc.h for when each
-        converges."""
+        converges.
+        detector (`fmpc_est_refine_weighted_device`): a `DetectorNoise`; the fit is then weighted by the variance that detector
+        gives the model image -- its gain (a float or a tensor of batch doubles), qe, background, read_noise and photon_noise;
+        seed, first and counter are not used -- with `floor` photo-electrons the least photon variance of a row.  info then
+        holds chi^2 for the costs, and `sigma`, a contiguous (batch, nmode) float64 HIP tensor or None, takes
+        sqrt(diag(H^-1)) of every realisation's last step (NaN where it took none).  refresh >= 1; G is not used."""
         import torch
         nmode = self._maps(Z, None)
         refresh = int(refresh)
-        if refresh == 0:
+        if detector is None and sigma is not None:
+            raise FastMPCError(_lib.FMPC_E_DIM, "sigma: only with detector=")
+        if refresh == 0 and detector is None:
             if G is None:
                 G = self.gain(Z)
             if not G.is_cuda or G.dtype != torch.float64 or G.dim() != 2 or tuple(G.shape) != (nmode, self.p) or (self.p > 1 and G.stride(1) != 1):
@@ -205,12 +218,21 @@ class EstimatorOptics:
             raise FastMPCError(_lib.FMPC_E_DIM, "info: need a contiguous float64 HIP tensor (batch, FMPC_REFINE_FIELDS)")
         if status is not None and (not status.is_cuda or status.dtype != torch.int32 or not status.is_contiguous() or tuple(status.shape) != (batch,)):
             raise FastMPCError(_lib.FMPC_E_DIM, "status: need a contiguous int32 HIP tensor (batch,)")
+        if sigma is not None and (not sigma.is_cuda or sigma.dtype != torch.float64 or not sigma.is_contiguous() or tuple(sigma.shape) != (batch, nmode)):
+            raise FastMPCError(_lib.FMPC_E_DIM, "sigma: need a contiguous float64 HIP tensor (batch, nmode)")
         if batch == 0:                       # (an empty tensor has no pointer to hand over; the library takes batch = 0 and does nothing)
             return alpha
         if workspace is None:
-            workspace = torch.empty(self.refine_workspace_bytes(nmode, batch, refresh=max(refresh, 0)), dtype=torch.uint8, device=Z.device)
+            workspace = torch.empty(self.refine_workspace_bytes(nmode, batch, refresh=max(refresh, 0 if detector is None else 1)), dtype=torch.uint8,
+                                    device=Z.device)
         vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        if refresh == 1:
+        if detector is not None:
+            name = "fmpc_est_refine_weighted_device"
+            blk = detector._block(0, batch)
+            rc = self._lib.fmpc_est_refine_weighted_device(self._h, nmode, vp(Z), batch, vp(Y), ldY, vp(alpha), int(iters), refresh, C.byref(blk),
+                                                           float(floor), float(damping), float(tol), vp(info), vp(status), vp(sigma),
+                                                           vp(workspace), workspace.numel(), _stream(Z.device))
+        elif refresh == 1:
             name = "fmpc_est_refine_device"
             rc = self._lib.fmpc_est_refine_device(self._h, nmode, vp(Z), batch, vp(Y), ldY, vp(alpha), int(iters), float(damping), float(tol),
                                                   vp(info), vp(status), vp(workspace), workspace.numel(), _stream(Z.device))
